@@ -20,6 +20,13 @@ afterwards, so every step solves the same problem.
   optimize_only            optimize(10) alone, inputs resident in HBM (no PCIe in the region)
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload kitti00|kitti07|synth10k|localba]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything
+else: reflatten / structure_dirty / optimize_only, the kernel-timing passes (kernel_groups, kernels,
+roofline) and the CPU baseline with its parity check.  --dump-outputs DIR writes what the last timed
+step computed (poses, landmarks, chi2 and lambda per LM iteration) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): the graph is sharded by landmark
 ranges; every LM trial all-reduces [Hsc | bsc] and (F-hat, scale) with RCCL on the solver's stream
@@ -51,6 +58,7 @@ WORKLOADS = {
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_PEAK_TFLOPS = 78.6    # MI355X fp64 vector / matrix peak
 PROFILE_ROUND = "r04"
+POOL_MAX = 32              # optimisers built for the timed steps; more steps cycle over them
 
 
 def survey_bytes(group, E, P, L, B):
@@ -132,12 +140,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="kitti00", choices=sorted(WORKLOADS))
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other regimes (optimize-only, initialize-only, re-flattening, "
+                         "structure dirty), the kernel-timing passes with their roofline figures, and the CPU "
+                         "baseline with its parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline region (profiling runs): no dirty / optimize-only / event passes")
+                    help="with --full: no dirty / optimize-only / event passes (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (poses, landmarks, chi2 and lambda per LM "
+                         "iteration) as DIR/<name>.npy, float64")
     ap.add_argument("--float32", action="store_true",
                     help="fp32-internal mode (BASELINE config 5): float storage of the Hpl / T block streams")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras_on = args.full and not args.no_extras
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -264,9 +282,11 @@ def main():
             return float(t.item())
         return x
 
-    # ---- one optimiser per step, each warmed up the way the reference sample does it ----------
+    # ---- a pool of optimisers, each warmed up the way the reference sample does it ------------
+    # One optimiser per step up to POOL_MAX steps; beyond that the steps cycle over the pool, so that the set-up
+    # (graph, flattening, structure, ordering, symbolic factor per optimiser) and the memory do not grow with --steps.
     graphs, cold = [], None
-    for gi in range(args.warmup + args.steps):
+    for gi in range(min(args.steps, POOL_MAX)):
         g = new_graph()
         t0 = time.perf_counter()
         g.initialize()
@@ -278,26 +298,45 @@ def main():
                     "host_phase_ms": {k: v for k, v in g.time_profile().items() if v > 0}}
         reset(g)
         graphs.append(g)
-    for g in graphs[:args.warmup]:
+    for i in range(args.warmup):
+        g = graphs[i % len(graphs)]
         g.initialize()
         g.optimize(args.iters)
-    timed = graphs[args.warmup:]
+        reset(g)
+    timed = graphs
 
-    # ---- headline: K contiguous initialize()+optimize(10), structure clean -------------------
-    barrier()
-    t0 = time.perf_counter()
-    for g in timed:
-        g.initialize()
-        g.optimize(args.iters)
-    barrier()
-    elapsed = max_over_ranks(time.perf_counter() - t0)
+    # ---- headline: K initialize()+optimize(10), structure clean, contiguous within each pass over the pool ----
+    # (every optimiser starts a step from the reset estimates; between two passes the pool is reset, untimed)
+    elapsed, iters_total, left, last = 0.0, 0, args.steps, None
+    while left > 0:
+        run = timed[:min(left, len(timed))]
+        if last is not None:
+            for g in run:
+                reset(g)
+        barrier()
+        t0 = time.perf_counter()
+        for g in run:
+            g.initialize()
+            g.optimize(args.iters)
+        barrier()
+        elapsed += max_over_ranks(time.perf_counter() - t0)
+        iters_total += sum(len(g.stats()) for g in run)
+        left -= len(run)
+        last = run[-1]
 
     stats = [g.stats() for g in timed]
-    iters_total = sum(len(s) for s in stats)
     nedges = timed[0].n_active_edges()
     sstats = timed[0].structure_stats()
     gpu_chi = [s["chi2"] for s in stats[0]]
     gpu_pose, gpu_lm = timed[0].poses(), timed[0].landmarks()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from the last step: estimates by id and the LM trace
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        trace = last.stats()
+        outputs = {"poses": last.poses(), "landmarks": last.landmarks(),
+                   "chi2": [s["chi2"] for s in trace], "lambda": [s["lam"] for s in trace]}
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
     xstats = timed[0].exchange_stats() if world > 1 else None
     # every rank must have taken the same LM decisions and ended every iteration on the same chi2 (the exchanged
     # sums are the same bits on every rank): checked over the rendezvous group, reported in the line
@@ -315,7 +354,7 @@ def main():
             ranks_agree = all(torch.equal(t, every[0]) for t in every)
 
     extras = {}
-    if not args.no_extras:
+    if extras_on:
         # ---- optimize(10) alone, inputs resident in HBM --------------------------------------
         for g in timed:
             reset(g)
@@ -394,7 +433,7 @@ def main():
     # the rocprofv3 average of the same kernel (committed trace) and the fraction it gives are printed beside them
     groups, kernels, roofline = {}, {}, None
     groups_fit = None
-    if not args.no_extras:
+    if extras_on:
         gk = new_graph()
         gk.initialize()
         gk.optimize(1)
@@ -509,7 +548,7 @@ def main():
     # ---- CPU baseline: the oracle (restatement of the g2o-style path), same graph, same region ----
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import oracle
 
         def problem():
@@ -567,7 +606,7 @@ def main():
 
     if rank == 0:
         chol_share = None
-        if "cholesky" in groups and not args.no_extras:
+        if "cholesky" in groups and extras_on:
             # from the boundary-event pass: the groups add up to the device time of optimize()
             tot = sum(v["total_ms"] for k, v in groups.items() if k != "exchange")
             chol_share = groups["cholesky"]["total_ms"] / max(tot, 1e-9)
