@@ -322,6 +322,27 @@ class Graph:
         check(lib().cugo_graph_get_landmarks(self._g, len(ids), _p(ids, _i32p), _p(out, _f64p)))
         return out
 
+    def compute_covariances(self, poses=True, landmarks=True):
+        """marginal covariances at the current estimates: Sigma = H^-1 of the undamped J^T Omega J over the free
+        vertices (diagonal blocks); kept until the next initialize().  Raises CugoError (code -4) on a zero pivot."""
+        what = (1 if poses else 0) | (2 if landmarks else 0)
+        if what:
+            check(lib().cugo_graph_compute_covariances(self._g, what))
+
+    def pose_covariances(self, ids=None):
+        """[n, 6, 6] per pose id (tangent order [rotation, translation], left update); zeros for fixed poses"""
+        ids = self.pose_ids if ids is None else np.ascontiguousarray(ids, np.int32)
+        out = np.zeros((len(ids), 36))
+        check(lib().cugo_graph_get_pose_covariances(self._g, len(ids), _p(ids, _i32p), _p(out, _f64p)))
+        return out.reshape(-1, 6, 6).transpose(0, 2, 1).copy()  # (column-major blocks)
+
+    def landmark_covariances(self, ids=None):
+        """[n, 3, 3] per landmark id; zeros for fixed landmarks"""
+        ids = self.lm_ids if ids is None else np.ascontiguousarray(ids, np.int32)
+        out = np.zeros((len(ids), 9))
+        check(lib().cugo_graph_get_landmark_covariances(self._g, len(ids), _p(ids, _i32p), _p(out, _f64p)))
+        return out.reshape(-1, 3, 3).transpose(0, 2, 1).copy()
+
     def set_poses(self, ids, q_t7):
         ids = np.ascontiguousarray(ids, np.int32); q = np.ascontiguousarray(q_t7, np.float64)
         check(lib().cugo_graph_set_poses(self._g, len(ids), _p(ids, _i32p), _p(q, _f64p)))

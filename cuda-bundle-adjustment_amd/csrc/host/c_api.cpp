@@ -210,6 +210,27 @@ int cugo_chol_factor_solve(cugo_chol* s, const double* d_Hsc, double lambda, con
         s->factor_solve(d_Hsc, lambda, d_bsc, d_x, d_fail);
     });
 }
+int cugo_chol_selected_inverse(cugo_chol* s, double* d_sigma)
+{
+    bool ok = true;
+    const int rc = guarded([&] {
+        if (!s || !s->ctx || !s->analyzed || !s->factored)
+            throw std::runtime_error("cugo_chol_selected_inverse needs a factorisation (cugo_chol_factor_solve) since the "
+                                     "last analyze()");
+        if (s->own_subtrees())
+            throw std::runtime_error("cugo_chol_selected_inverse: not available when the solver factors rank-owned "
+                                     "subtrees");
+        ok = s->selected_inverse(d_sigma);
+    });
+    if (rc != CUGO_OK)
+        return rc;
+    if (!ok)
+    {
+        set_last_error("cugo_chol_selected_inverse: the factorisation hit a zero pivot");
+        return CUGO_ERR_NUMERIC;
+    }
+    return CUGO_OK;
+}
 #ifdef CUGO_DEBUG_HOOKS // diagnosis entry points: only libcugo_hip_hooks.so exports them (csrc/host/cugo_debug.h)
 int cugo_debug_pin_reference(void)
 {
@@ -318,6 +339,21 @@ int cugo_chol_plan_array(cugo_chol* s, const char* name, const int32_t** out)
     if (!v)
     {
         set_last_error("cugo_chol_plan_array: unknown array " + n);
+        return CUGO_ERR_INVALID;
+    }
+    *out = v->data();
+    return (int)v->size();
+}
+
+int cugo_chol_plan_array64(cugo_chol* s, const char* name, const int64_t** out)
+{
+    const CholPlan& P = s->plan;
+    const std::string n(name);
+    const std::vector<int64_t>* v = n == "off" ? &P.off : n == "ldf" ? &P.ldf : n == "woff" ? &P.woff
+                                  : n == "l21off" ? &P.l21off : nullptr;
+    if (!v)
+    {
+        set_last_error("cugo_chol_plan_array64: unknown array " + n);
         return CUGO_ERR_INVALID;
     }
     *out = v->data();
@@ -652,6 +688,42 @@ int cugo_graph_get_landmarks(cugo_graph* g, int n, const int32_t* ids, double* x
     return guarded([&] {
         for (int i = 0; i < n; i++)
             g->lms.getVertex(ids[i])->getEstimate().copyTo(xyz + 3 * (size_t)i);
+    });
+}
+int cugo_graph_compute_covariances(cugo_graph* g, int what)
+{
+    bool ok = true;
+    const int rc = guarded([&] {
+        if (what < 1 || what > 3)
+            throw std::invalid_argument("cugo_graph_compute_covariances: what must be 1 (poses), 2 (landmarks) or 3 (both)");
+        ok = g->opt->computeMarginals((what & 1) != 0, (what & 2) != 0);
+    });
+    if (rc != CUGO_OK)
+        return rc;
+    if (!ok)
+    {
+        set_last_error("cugo_graph_compute_covariances: zero pivot — H is singular at the current estimates (an "
+                       "unconstrained gauge, a free pose without edges or a landmark seen too little)");
+        return CUGO_ERR_NUMERIC;
+    }
+    return CUGO_OK;
+}
+int cugo_graph_get_pose_covariances(cugo_graph* g, int n, const int32_t* ids, double* cov36)
+{
+    return guarded([&] {
+        for (int i = 0; i < n; i++)
+            if (!g->opt->poseCovariance(g->poses.getVertex(ids[i]), cov36 + 36 * (size_t)i))
+                throw std::runtime_error("cugo_graph_get_pose_covariances: no pose covariances were computed since the "
+                                         "last initialize(), or the pose set changed since then");
+    });
+}
+int cugo_graph_get_landmark_covariances(cugo_graph* g, int n, const int32_t* ids, double* cov9)
+{
+    return guarded([&] {
+        for (int i = 0; i < n; i++)
+            if (!g->opt->landmarkCovariance(g->lms.getVertex(ids[i]), cov9 + 9 * (size_t)i))
+                throw std::runtime_error("cugo_graph_get_landmark_covariances: no landmark covariances were computed "
+                                         "since the last initialize(), or the landmark set changed since then");
     });
 }
 int cugo_graph_set_poses(cugo_graph* g, int n, const int32_t* ids, const double* qt)

@@ -205,6 +205,7 @@ void cugo_chol::analyze_host(int n, const int32_t* rowptr, const int32_t* colind
         chol_analyze(n, rowptr, colind, copt, plan);
     }
     lookahead = opt.lookahead;
+    factored = false, si_ready = false, last_fail = nullptr;
     trans32.assign(plan.blk_trans.begin(), plan.blk_trans.end());
     pack();
     if (plan.nc_max > cugo_k::chol_max_pivot_cols() ||
@@ -401,6 +402,7 @@ void cugo_chol::factor_solve(const double* d_Hsc, double lambda, const double* d
                              int32_t* d_fail)
 {
     hipStream_t s = ctx->stream;
+    factored = true, last_fail = d_fail;
 #ifdef CUGO_DEBUG_HOOKS
     cugo_chol_hooks hooks(*this);
 #endif
@@ -526,4 +528,68 @@ void cugo_chol::factor_solve(const double* d_Hsc, double lambda, const double* d
             }
     }
 #endif
+}
+
+// Selected inverse of the factorisation the last factor_solve left ("Marginal covariances"): top-down over
+// the stages the backward pass walks, the Sigma-fronts of a level from those of the level above.
+bool cugo_chol::selected_inverse(double* d_sigma)
+{
+    hipStream_t s = ctx->stream;
+    int32_t h_fail = 0;
+    CUGO_HIP(hipMemcpyAsync(&h_fail, last_fail, sizeof h_fail, hipMemcpyDeviceToHost, s));
+    CUGO_HIP(hipStreamSynchronize(s));
+    if (h_fail)
+        return false;
+    const CholPlan& P = plan;
+    if (!si_ready)
+    {
+        std::vector<int64_t> sinfo(4 * (size_t)P.n_super + 4, 0);
+        for (int f = 0; f < P.n_super; f++)
+        {
+            const int pa = P.sparent[f];
+            if (pa < 0)
+                continue;
+            sinfo[4 * f] = P.off[pa], sinfo[4 * f + 1] = P.ldf[pa], sinfo[4 * f + 2] = P.rel_ptr[f];
+            sinfo[4 * f + 3] = P.alias_of[pa] == f ? 0 : 1; // (the parent sits in this front's R x R region)
+        }
+        const int tile = cugo_k::selinv_row_tile();
+        std::vector<int32_t> items;
+        si_ptr.assign(P.n_stages + 1, 0);
+        for (int st = 0; st < P.n_stages; st++)
+        {
+            si_ptr[st] = (int32_t)(items.size() / 2);
+            if (!(P.has_subtree_stage && st == 0))
+                for (int t = P.stage_task_ptr[st]; t < P.stage_task_ptr[st + 1]; t++)
+                    for (int fi = P.task_ptr[t]; fi < P.task_ptr[t + 1]; fi++)
+                    {
+                        const int f = P.task_fronts[fi];
+                        for (int r0 = 0; r0 < 6 * (P.nb[f] - P.ncb[f]); r0 += tile)
+                            items.push_back(f), items.push_back(r0);
+                    }
+        }
+        si_ptr[P.n_stages] = (int32_t)(items.size() / 2);
+        items.resize(items.size() + 2, 0);
+        d_sinfo.upload(sinfo, s);
+        d_sitems.upload(items, s);
+        // (zeroed once: every entry a front reads is written before, the zeros only keep the rest defined)
+        d_sig.resize((size_t)P.front_doubles + 16);
+        d_sig.zero(s);
+        CUGO_HIP(hipStreamSynchronize(s)); // (the host vectors go out of scope)
+        si_ready = true;
+    }
+    for (int st = P.n_stages - 1; st >= 0; st--)
+    {
+        const int t0 = P.stage_task_ptr[st], t1 = P.stage_task_ptr[st + 1];
+        if (P.has_subtree_stage && st == 0)
+            cugo_k::launch_selinv_subtree(s, dev, d_fronts.data(), d_sig.data(), d_sinfo.data(), t0, t1 - t0);
+        else
+        {
+            cugo_k::launch_selinv_rows(s, dev, d_fronts.data(), d_sig.data(), d_sinfo.data(),
+                                       d_sitems.data() + 2L * si_ptr[st], si_ptr[st + 1] - si_ptr[st]);
+            cugo_k::launch_selinv_jj(s, dev, d_fronts.data(), d_sig.data(), t0, t1 - t0);
+        }
+    }
+    cugo_k::launch_selinv_gather(s, dev, d_sig.data(), d_sigma);
+    CUGO_HIP(hipGetLastError());
+    return true;
 }

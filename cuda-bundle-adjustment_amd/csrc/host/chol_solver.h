@@ -58,6 +58,20 @@ struct cugo_chol
 #endif
     bool own_subtrees() const { return bcast && plan.owned; }
 
+    // selected inverse (cugo_chol_selected_inverse): the zero-pivot flag of the last factor_solve, whether one ran
+    // since analyze(), and — built on the first call after analyze() — the Sigma-fronts (laid out like the fronts),
+    // per front {offset and leading dimension of the parent's Sigma-front, offset of its rel list, copy S_RR}, and
+    // per upper stage the (front, first row) items of the 64-row tiles of R
+    const int32_t* last_fail = nullptr;
+    bool factored = false;
+    bool si_ready = false;
+    cugo_host::DevBuf<double> d_sig;
+    cugo_host::DevBuf<int64_t> d_sinfo;
+    cugo_host::DevBuf<int32_t> d_sitems;
+    std::vector<int32_t> si_ptr; // [n_stages+1] item ranges
+    // false: the zero-pivot flag of the last factorisation is set (nothing queued)
+    bool selected_inverse(double* d_sigma);
+
     void analyze(int n, const int32_t* rowptr, const int32_t* colind);
     void analyze_host(int n, const int32_t* rowptr, const int32_t* colind); // without upload()
     void pack(); // host half of upload() (analyze_host calls it)

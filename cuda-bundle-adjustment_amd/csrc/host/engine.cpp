@@ -125,6 +125,10 @@ struct Engine::Impl : cugo_k::LaunchHook
     // linearisation: a fused build pass writes ONE block stream (G = Hpl L^-T, into d_T) and none of the three
     DevBuf<double> d_lmrec;
     bool hpp_valid = true;
+    // marginal covariances (Engine::compute_covariances; allocated by the first call only): the blocks of Sigma on
+    // the Hsc pattern, the landmark blocks, their positive-definiteness flag
+    DevBuf<double> d_cov_sigma, d_cov_pose, d_cov_lm;
+    DevBuf<int32_t> d_cov_fail;
     PinnedBuf<double> h_pin_poses, h_pin_lms; // refresh_estimates_pinned / download_pinned
     Clock::duration last_trial_wait{0};       // how long the host polled for the previous trial's result
     DevBuf<int32_t> d_hsc_rowptr, d_hsc_colind, d_off_ptr, d_off_ei, d_off_ej, d_fail;
@@ -2083,6 +2087,90 @@ std::vector<int32_t> Engine::reject_outliers()
         E_global_ -= (int)out.size();
     }
     return out;
+}
+
+int Engine::n_poses_free() const { return impl_->P; }
+int Engine::n_landmarks_free() const { return impl_->L; }
+
+void Engine::clear_covariances()
+{
+    cov_what_ = 0;
+    cov_pose_.clear();
+    cov_lm_.clear();
+}
+
+bool Engine::compute_covariances(int what)
+{
+    Impl& m = *impl_;
+    if (what < 1 || what > 3)
+        throw std::invalid_argument("cugo_graph_compute_covariances: what must be 1 (poses), 2 (landmarks) or 3 (both)");
+    if (m.plan_only)
+        throw std::runtime_error("cugo_graph_compute_covariances: plan-only optimiser (no HIP device in use)");
+    if (m.world > 1 || m.comm)
+        throw std::runtime_error("cugo_graph_compute_covariances: not available on a sharded (multi-GPU) optimiser");
+    if (m.ev.block_f32)
+        throw std::runtime_error("cugo_graph_compute_covariances: not available in the fp32-internal mode");
+    clear_covariances();
+    if (m.structure_dirty)
+        build_structure();
+    hipStream_t s = m.ctx.stream;
+    // H at the current estimates, undamped: the two-stream build pass (Hpp, b, Hll, Hpl), as a retried trial of
+    // optimize() queues it.  optimize() starts every call with a build pass of its own, so nothing it reads is lost.
+    cugo_k::launch_build(s, m.ev, m.d_poses[m.cur].data(), m.d_lms[m.cur].data(), m.rk, m.d_Hpp.data(), m.bp(),
+                         m.d_Hll.data(), m.bl(), m.d_Hpl.data(), m.rs(), nullptr, -1.0, nullptr, nullptr);
+    m.hpp_valid = true;
+    const int B = m.hs.n_blocks;
+    m.d_cov_sigma.resize(36 * (size_t)B + 16);
+    if (m.P > 0)
+    {
+        const bool use_rows = m.rows_on && cugo_k::schur_rows_usable(m.hs, m.max_row_nnz);
+        if (!m.splan_on && !use_rows && m.d_T.size() == 0)
+            m.d_T.resize(18 * (size_t)m.E + 16);
+        cugo_k::launch_schur(s, m.ev, m.hs, 0.0, 0, m.d_Hpp.data(), m.bp(), m.d_Hll.data(), m.bl(), m.d_Hpl.data(),
+                             m.d_invHll.data(), m.splan_on || use_rows ? nullptr : m.d_T.data(), m.bsc(), m.Hsc(), false,
+                             use_rows ? cugo_k::SchurRows{m.d_pose_rec.data(), m.max_row_nnz, nullptr, m.opt.hsc_mfma, m.opt.hsc_xcd}
+                                      : cugo_k::SchurRows{nullptr, 0, m.strip_on ? m.d_off_pi.data() : nullptr,
+                                                          m.opt.hsc_mfma, m.opt.hsc_xcd, nullptr,
+                                                          m.d_poses[m.cur].data(), m.rs(), m.bp()});
+        int32_t* d_fail = reinterpret_cast<int32_t*>(m.d_scal.data() + 4);
+        m.chol.factor_solve(m.Hsc(), 0.0, m.bsc(), m.xp(), d_fail);
+        if (!m.chol.selected_inverse(m.d_cov_sigma.data()))
+            return false;
+    }
+    std::vector<int32_t> fail(1, 0);
+    if (what & 2)
+    {
+        m.d_cov_lm.resize(9 * (size_t)m.L + 16);
+        m.d_cov_fail.resize(16);
+        m.d_cov_fail.zero(s);
+        cugo_k::launch_lm_covariance(s, m.L, m.ev.d_lm_ptr, m.ev.d_pose, m.ev.d_flags, m.d_Hll.data(),
+                                     reinterpret_cast<const double*>(m.d_Hpl.data()), m.hs.d_rowptr, m.hs.d_colind,
+                                     m.d_cov_sigma.data(), m.d_cov_lm.data(), m.d_cov_fail.data());
+        cov_lm_.resize(9 * (size_t)m.L);
+        if (m.L > 0)
+            CUGO_HIP(hipMemcpyAsync(cov_lm_.data(), m.d_cov_lm.data(), cov_lm_.size() * sizeof(double),
+                                    hipMemcpyDeviceToHost, s));
+        CUGO_HIP(hipMemcpyAsync(fail.data(), m.d_cov_fail.data(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    // the diagonal blocks of the poses, gathered on the device: only they travel to the host
+    if ((what & 1) && m.P > 0)
+    {
+        m.d_cov_pose.resize(36 * (size_t)m.P + 16);
+        cugo_k::launch_cov_pose_diag(s, m.P, m.hs.d_rowptr, m.d_cov_sigma.data(), m.d_cov_pose.data());
+        cov_pose_.resize(36 * (size_t)m.P);
+        CUGO_HIP(hipMemcpyAsync(cov_pose_.data(), m.d_cov_pose.data(), cov_pose_.size() * sizeof(double),
+                                hipMemcpyDeviceToHost, s));
+    }
+    CUGO_HIP(hipStreamSynchronize(s));
+    if (fail[0])
+    {
+        clear_covariances();
+        return false;
+    }
+    if (!(what & 1))
+        cov_pose_.clear();
+    cov_what_ = what;
+    return true;
 }
 
 void Engine::download(std::vector<double>& poses, std::vector<double>& lms)

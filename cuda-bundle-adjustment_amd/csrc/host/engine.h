@@ -122,6 +122,18 @@ public:
     // pass exceeds their set's threshold become inactive.  Returns their indices in the order of
     // the FlatGraph passed to initialize() (all ranks return the same list).
     std::vector<int32_t> reject_outliers();
+    // Extension: marginal covariances at the current estimates (include/cugo_hip.h, cugo_graph_compute_covariances).
+    // Builds J^T Omega J at lambda = 0, its Schur complement and factorisation, runs the selected inverse and, for
+    // what & 2, the landmark blocks; keeps the diagonal blocks (cov_pose [P][36], cov_lm [L][9], column-major) on the
+    // host.  Returns false on a zero pivot or a landmark whose Hll is not positive definite.  Leaves the estimates
+    // and everything the next optimize() reads as they were.
+    bool compute_covariances(int what);
+    void clear_covariances();
+    int covariances_held() const { return cov_what_; } // bit 0 poses, bit 1 landmarks
+    const std::vector<double>& cov_pose() const { return cov_pose_; }
+    const std::vector<double>& cov_lm() const { return cov_lm_; }
+    int n_poses_free() const;
+    int n_landmarks_free() const;
     int n_active_edges() const { return E_global_; }
     const StructureStats& structure_stats() const { return sstats_; }
     const double* profile_ms() const { return prof_; }
@@ -149,6 +161,8 @@ private:
     int E_global_ = 0;
     StructureStats sstats_;
     double prof_[PROF_COUNT] = {0};
+    int cov_what_ = 0;
+    std::vector<double> cov_pose_, cov_lm_;
 };
 
 } // namespace cugo_host

@@ -3,6 +3,7 @@
 // (initialize), src/optimisable_graph.hpp:84-154, 474-572 (index / flag / activeness rules).
 #include "../../include/cuda_graph_optimisation.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -137,6 +138,8 @@ void CudaGraphOptimisationImpl::initialize()
         lap_t = n;
     };
     engine_->set_float32_blocks(options.useFloat32);
+    engine_->clear_covariances();
+    initialized_ = false;
     FlatGraph& g = engine_->staging();
     // ---- unchanged graph: only the estimates are refreshed -------------------------------
     // If no vertex set or edge set has counted a change since the last full flattening (see
@@ -175,6 +178,7 @@ void CudaGraphOptimisationImpl::initialize()
             lap("graph: engine refresh");
             stats_.clear();
             trace_.clear();
+            initialized_ = true;
             return;
         }
         flattenValid_ = false;
@@ -422,6 +426,7 @@ void CudaGraphOptimisationImpl::initialize()
     flattenOptions_[0] = options.perEdgeInformation, flattenOptions_[1] = options.perEdgeCamera;
     flattenOptions_[2] = options.useFloat32;
     flattenValid_ = true;
+    initialized_ = true;
 }
 
 void CudaGraphOptimisationImpl::optimize(int niterations)
@@ -480,6 +485,58 @@ const TimeProfile& CudaGraphOptimisationImpl::timeProfile()
     for (int i = 0; i < cugo_host::PROF_COUNT; i++)
         timeProfile_[Engine::profile_name(i)] = engine_->profile_ms()[i];
     return timeProfile_;
+}
+
+bool CudaGraphOptimisationImpl::computeMarginals(bool poses, bool landmarks)
+{
+    if (!initialized_)
+        throw std::runtime_error("cugo: computeMarginals() needs initialize() first");
+    if (options.planOnly)
+        throw std::runtime_error("cugo: computeMarginals(): this optimiser is plan-only (no HIP device in use)");
+    if (options.useFloat32)
+        throw std::runtime_error("cugo: computeMarginals() is not available in the fp32-internal mode");
+    for (BaseVertexSet* vs : vertexSets)
+        if (!flattenedUnchanged(vs))
+            throw std::runtime_error("cugo: computeMarginals(): a vertex set changed since initialize() (vertex added, "
+                                     "removed or fixed / freed); call initialize() again");
+    const int what = (poses ? 1 : 0) | (landmarks ? 2 : 0);
+    if (!what)
+        return true;
+    return engine_->compute_covariances(what);
+}
+
+// the vertex set is one the last full flattening was made from, and nothing but estimates changed in it since:
+// the indices and fixed flags of its vertices are those the covariances were computed with
+bool CudaGraphOptimisationImpl::flattenedUnchanged(const BaseVertexSet* vs) const
+{
+    for (const auto& fc : flattenCounts_)
+        if (fc.first == vs)
+            return fc.second == vs->changeCount();
+    return false;
+}
+
+bool CudaGraphOptimisationImpl::poseCovariance(const BaseVertex* v, double cov[36]) const
+{
+    if (!(engine_->covariances_held() & 1) || !v || v->isMarginilised() || !flattenedUnchanged(v->ownerSet()))
+        return false;
+    const int i = v->getIndex();
+    if (v->isFixed() || i < 0 || i >= engine_->n_poses_free())
+        std::fill(cov, cov + 36, 0.0);
+    else
+        std::copy(engine_->cov_pose().begin() + 36 * (size_t)i, engine_->cov_pose().begin() + 36 * (size_t)i + 36, cov);
+    return true;
+}
+
+bool CudaGraphOptimisationImpl::landmarkCovariance(const BaseVertex* v, double cov[9]) const
+{
+    if (!(engine_->covariances_held() & 2) || !v || !v->isMarginilised() || !flattenedUnchanged(v->ownerSet()))
+        return false;
+    const int i = v->getIndex();
+    if (v->isFixed() || i < 0 || i >= engine_->n_landmarks_free())
+        std::fill(cov, cov + 9, 0.0);
+    else
+        std::copy(engine_->cov_lm().begin() + 9 * (size_t)i, engine_->cov_lm().begin() + 9 * (size_t)i + 9, cov);
+    return true;
 }
 
 } // namespace cugo

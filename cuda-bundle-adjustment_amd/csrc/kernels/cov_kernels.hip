@@ -1,0 +1,536 @@
+// Marginal covariances on gfx950 (fp64): the selected inverse of the multifrontal block LL^T of Hsc
+// (chol_kernels.hip) and the landmark blocks built from it.
+//
+// Selected inverse (supernodal Takahashi recurrences), top-down over the stages of the factorisation.
+// For a front with pivot columns J and boundary rows R (W = L11^-1 and L21 as dev_backward reads them):
+//
+//   S_RR  = Sigma on R x R, read from the parent's Sigma-front through the extend-add map `rel`
+//   S_RJ  = -S_RR L21 W
+//   S_JJ  = W^T (W - L21^T S_RJ)
+//
+// Every front owns a Sigma-front with the offset and leading dimension of its front (CholPlan::off / ldf): the
+// Sigma-front of a front stored in its only child's update block (alias chains) then already sits in that
+// child's R x R region, and the child reads it in place.  Other fronts copy the lower triangle of S_RR into
+// their own R x R region while they read it, so their children find it there.
+//
+//   k_selinv_rows    one workgroup per 64-row tile of R: S_RJ of those rows (and the copy of their S_RR rows)
+//   k_selinv_jj      one workgroup per front: S_JJ
+//   k_selinv_subtree one workgroup per subtree task of stage 0: both, front by front, top-down
+//   k_selinv_gather  the blocks of the Hsc pattern out of the Sigma-fronts (permutation and blk_trans undone)
+//
+// Every entry is one thread's sum in a fixed order: no atomics, the same bits on every call.
+//
+// Landmarks (k_lm_covariance): with Hll = L L^T and G_e = Hpl_e L^-T of the landmark's free-pose edges,
+//   Sigma_l = L^-T (I + sum_{e,f} G_e^T Sigma_{p(e) p(f)} G_f) L^-1,
+// one thread per landmark, the pose blocks looked up in the upper block CSR of Hsc.
+#include <algorithm>
+
+#include "kernels.h"
+
+namespace
+{
+
+using cugo_k::CholPlanDev;
+
+constexpr int SI_T = 256;        // workgroup size (16 x 16 threads)
+constexpr int SI_R = 64;         // rows of R per tile workgroup
+constexpr int SI_K = 32;         // depth of one LDS chunk
+constexpr int SI_N = 96;         // widest pivot block (scalars, NC_MAX of chol_kernels.hip)
+constexpr int SI_LD = SI_N + 1;  // LDS leading dimension
+constexpr size_t SI_LDS_ROWS = (size_t)SI_R * SI_LD;          // max(S chunk + L21 chunk + maps, Z tile)
+constexpr size_t SI_LDS_JJ = (size_t)SI_N * SI_LD;            // max(two chunks, W - T)
+static_assert((size_t)SI_R * (SI_K + 1) + (size_t)SI_K * SI_LD + (SI_R + SI_K) / 2 + 1 <= SI_LDS_ROWS, "LDS");
+static_assert((size_t)2 * SI_K * SI_LD <= SI_LDS_JJ, "LDS");
+
+__device__ __forceinline__ int pad16(int nc) { return (nc + 15) & ~15; }
+
+// where a front's W and L21 are: the places dev_backward (chol_kernels.hip) reads them from
+struct SelFront
+{
+    int ncs, nrs, ncp;
+    long off, ld, ldl;
+    const double* L; // L21[i][m] = L[m * ldl + i]
+    const double* W; // W[k][j] = W[j * ncp + k], j <= k < ncs (the rest is not defined)
+};
+__device__ __forceinline__ SelFront sel_front(const CholPlanDev& p, const double* __restrict__ fronts, int f)
+{
+    SelFront F;
+    F.ncs = 6 * p.ncb[f];
+    F.nrs = 6 * (p.nb[f] - p.ncb[f]);
+    F.ncp = pad16(F.ncs);
+    F.off = p.off[f];
+    F.ld = p.ldf[f];
+    const long l21o = p.l21off[f];
+    F.L = l21o >= 0 ? p.l21 + l21o : fronts + F.off + F.ncs;
+    F.ldl = l21o >= 0 ? F.nrs + 1 : F.ld;
+    F.W = p.winv + p.woff[f];
+    return F;
+}
+
+// S_RJ of the rows [r0, r0 + 64) of R.  sinfo[4 f ..]: offset and leading dimension of the parent's Sigma-front,
+// offset of the front's rel list, and whether S_RR must be copied into the front's own Sigma-front (0 when the
+// parent is stored in this front's update block: the copy would be the parent itself)
+__device__ void selinv_rows(const CholPlanDev& p, const double* __restrict__ fronts, double* sig,
+                            const int64_t* __restrict__ sinfo, int f, int r0, double* __restrict__ lds)
+{
+    const SelFront F = sel_front(p, fronts, f);
+    const long offp = sinfo[4 * f], ldp = sinfo[4 * f + 1];
+    const int32_t* __restrict__ rel = p.rel + sinfo[4 * f + 2];
+    const bool copy_s = sinfo[4 * f + 3] != 0;
+    const int nt = min(SI_R, F.nrs - r0);
+    double* Ss = lds;                        // [SI_R][SI_K + 1]
+    double* Ls = lds + SI_R * (SI_K + 1);    // [SI_K][SI_LD]
+    int* rmap = reinterpret_cast<int*>(Ls + SI_K * SI_LD); // row of the parent front of each tile row ...
+    int* kmap = rmap + SI_R;                               // ... and of each row of the chunk
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    __syncthreads(); // (the LDS may still be read by the previous front of a subtree task)
+    if (t < nt)
+    {
+        const int i = r0 + t;
+        rmap[t] = 6 * rel[i / 6] + i % 6;
+    }
+    double acc[4][6];
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+            acc[q][r] = 0.0;
+    // Z = S_RR[tile, :] L21
+    for (int k0 = 0; k0 < F.nrs; k0 += SI_K)
+    {
+        const int nk = min(SI_K, F.nrs - k0);
+        __syncthreads();
+        if (t < nk)
+        {
+            const int k = k0 + t;
+            kmap[t] = 6 * rel[k / 6] + k % 6;
+        }
+        __syncthreads();
+        for (int e = t; e < SI_R * SI_K; e += SI_T)
+        {
+            const int i = e / SI_K, k = e % SI_K;
+            double v = 0.0;
+            if (i < nt && k < nk)
+            {
+                const int a = rmap[i], b = kmap[k];
+                v = sig[offp + (long)min(a, b) * ldp + max(a, b)];
+                if (copy_s && k0 + k <= r0 + i)
+                    sig[F.off + (long)(F.ncs + k0 + k) * F.ld + F.ncs + r0 + i] = v;
+            }
+            Ss[i * (SI_K + 1) + k] = v;
+        }
+        for (int e = t; e < SI_K * SI_N; e += SI_T)
+        {
+            const int k = e % SI_K, m = e / SI_K;
+            Ls[k * SI_LD + m] = (k < nk && m < F.ncs) ? F.L[(long)m * F.ldl + k0 + k] : 0.0;
+        }
+        __syncthreads();
+        for (int k = 0; k < nk; k++)
+        {
+            double s[4], l[6];
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                s[q] = Ss[(ty + 16 * q) * (SI_K + 1) + k];
+#pragma unroll
+            for (int r = 0; r < 6; r++)
+                l[r] = Ls[k * SI_LD + tx + 16 * r];
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int r = 0; r < 6; r++)
+                    acc[q][r] += s[q] * l[r];
+        }
+    }
+    __syncthreads();
+    double* Zs = lds; // [SI_R][SI_LD]
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+            Zs[(ty + 16 * q) * SI_LD + tx + 16 * r] = acc[q][r];
+    __syncthreads();
+    // S_RJ[tile, j] = -sum_{m >= j} Z[tile, m] W[m, j]
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+            acc[q][r] = 0.0;
+    for (int m = 0; m < F.ncs; m++)
+    {
+        double w[6], z[4];
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+        {
+            const int j = tx + 16 * r;
+            w[r] = (j <= m) ? F.W[(long)j * F.ncp + m] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            z[q] = Zs[(ty + 16 * q) * SI_LD + m];
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int r = 0; r < 6; r++)
+                acc[q][r] += z[q] * w[r];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+        {
+            const int i = ty + 16 * q, j = tx + 16 * r;
+            if (i < nt && j < F.ncs)
+                sig[F.off + (long)j * F.ld + F.ncs + r0 + i] = -acc[q][r];
+        }
+}
+
+// S_JJ = W^T (W - L21^T S_RJ) of front f (S_RJ written before)
+__device__ void selinv_jj(const CholPlanDev& p, const double* __restrict__ fronts, double* sig, int f,
+                          double* __restrict__ lds)
+{
+    const SelFront F = sel_front(p, fronts, f);
+    double* La = lds;               // [SI_K][SI_LD]  L21 rows
+    double* Sa = lds + SI_K * SI_LD; // [SI_K][SI_LD]  S_RJ rows
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    double acc[6][6];
+#pragma unroll
+    for (int q = 0; q < 6; q++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+            acc[q][r] = 0.0;
+    // T = L21^T S_RJ (J x J), summed over R in row order
+    for (int i0 = 0; i0 < F.nrs; i0 += SI_K)
+    {
+        const int ni = min(SI_K, F.nrs - i0);
+        __syncthreads();
+        for (int e = t; e < SI_K * SI_N; e += SI_T)
+        {
+            const int i = e % SI_K, m = e / SI_K;
+            const bool ok = i < ni && m < F.ncs;
+            La[i * SI_LD + m] = ok ? F.L[(long)m * F.ldl + i0 + i] : 0.0;
+            Sa[i * SI_LD + m] = ok ? sig[F.off + (long)m * F.ld + F.ncs + i0 + i] : 0.0;
+        }
+        __syncthreads();
+        for (int i = 0; i < ni; i++)
+        {
+            double a[6], b[6];
+#pragma unroll
+            for (int q = 0; q < 6; q++)
+                a[q] = La[i * SI_LD + ty + 16 * q];
+#pragma unroll
+            for (int r = 0; r < 6; r++)
+                b[r] = Sa[i * SI_LD + tx + 16 * r];
+#pragma unroll
+            for (int q = 0; q < 6; q++)
+#pragma unroll
+                for (int r = 0; r < 6; r++)
+                    acc[q][r] += a[q] * b[r];
+        }
+    }
+    __syncthreads();
+    double* Ms = lds; // [SI_N][SI_LD]: W - T
+#pragma unroll
+    for (int q = 0; q < 6; q++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+        {
+            const int m = ty + 16 * q, j = tx + 16 * r;
+            const double w = (j <= m && m < F.ncs) ? F.W[(long)j * F.ncp + m] : 0.0;
+            Ms[m * SI_LD + j] = w - acc[q][r];
+        }
+    __syncthreads();
+    // S_JJ[a][b] = sum_{m >= a} W[m][a] M[m][b]
+#pragma unroll
+    for (int q = 0; q < 6; q++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+            acc[q][r] = 0.0;
+    for (int m = 0; m < F.ncs; m++)
+    {
+        double w[6], b[6];
+#pragma unroll
+        for (int q = 0; q < 6; q++)
+        {
+            const int a = ty + 16 * q;
+            w[q] = (a <= m) ? F.W[(long)a * F.ncp + m] : 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+            b[r] = Ms[m * SI_LD + tx + 16 * r];
+#pragma unroll
+        for (int q = 0; q < 6; q++)
+#pragma unroll
+            for (int r = 0; r < 6; r++)
+                acc[q][r] += w[q] * b[r];
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+        {
+            const int a = ty + 16 * q, b = tx + 16 * r;
+            if (a < F.ncs && b < F.ncs)
+                sig[F.off + (long)b * F.ld + a] = acc[q][r];
+        }
+}
+
+// items: (front, first row of the tile) pairs of one stage
+__global__ __launch_bounds__(SI_T) void k_selinv_rows(CholPlanDev p, const double* __restrict__ fronts, double* sig,
+                                                      const int64_t* __restrict__ sinfo, const int32_t* __restrict__ items)
+{
+    extern __shared__ double lds[];
+    const int32_t* it = items + 2 * blockIdx.x;
+    selinv_rows(p, fronts, sig, sinfo, it[0], it[1], lds);
+}
+
+__global__ __launch_bounds__(SI_T) void k_selinv_jj(CholPlanDev p, const double* __restrict__ fronts, double* sig,
+                                                    int task0)
+{
+    extern __shared__ double lds[];
+    const int t = task0 + blockIdx.x;
+    selinv_jj(p, fronts, sig, p.task_fronts[p.task_ptr[t]], lds);
+}
+
+// a subtree task of stage 0: its fronts are listed children first, so walked backwards every parent is done
+// before its children
+__global__ __launch_bounds__(SI_T) void k_selinv_subtree(CholPlanDev p, const double* __restrict__ fronts, double* sig,
+                                                         const int64_t* __restrict__ sinfo, int task0)
+{
+    extern __shared__ double lds[];
+    const int t = task0 + blockIdx.x;
+    for (int fi = p.task_ptr[t + 1] - 1; fi >= p.task_ptr[t]; fi--)
+    {
+        const int f = p.task_fronts[fi];
+        const int nrs = 6 * (p.nb[f] - p.ncb[f]);
+        for (int r0 = 0; r0 < nrs; r0 += SI_R)
+            selinv_rows(p, fronts, sig, sinfo, f, r0, lds);
+        __threadfence_block();
+        __syncthreads();
+        selinv_jj(p, fronts, sig, f, lds);
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+// out[k] (column-major 6 x 6) = the block of Sigma at the position of Hsc block k
+__global__ __launch_bounds__(SI_T) void k_selinv_gather(CholPlanDev p, const double* __restrict__ sig,
+                                                        double* __restrict__ out)
+{
+    const long i = (long)blockIdx.x * SI_T + threadIdx.x;
+    if (i >= 36L * p.n_hsc_blocks)
+        return;
+    const int k = (int)(i / 36), e = (int)(i % 36), r = e % 6, c = e / 6;
+    const int f = p.blk_front[k];
+    const bool tr = p.blk_trans[k] != 0;
+    const int ra = 6 * p.blk_row[k] + (tr ? c : r), ca = 6 * p.blk_col[k] + (tr ? r : c);
+    out[i] = sig[p.off[f] + (long)min(ra, ca) * p.ldf[f] + max(ra, ca)];
+}
+
+// ---------------------------------------------------------------- landmarks --------------
+// lower Cholesky factor of a 3x3 SPD block (column-major in), its inverse (lower, row-major li[r][c]); false on a
+// pivot <= 0 or NaN
+__device__ __forceinline__ bool chol3_inv(const double* __restrict__ H, double (&li)[3][3])
+{
+    const double l00 = H[0] > 0.0 ? sqrt(H[0]) : 0.0;
+    const double l10 = H[1] / l00, l20 = H[2] / l00;
+    const double d1 = H[4] - l10 * l10;
+    const double l11 = d1 > 0.0 ? sqrt(d1) : 0.0;
+    const double l21 = (H[5] - l20 * l10) / l11;
+    const double d2 = H[8] - l20 * l20 - l21 * l21;
+    const double l22 = d2 > 0.0 ? sqrt(d2) : 0.0;
+    if (!(l00 > 0.0 && l11 > 0.0 && l22 > 0.0))
+        return false;
+    li[0][0] = 1.0 / l00, li[1][1] = 1.0 / l11, li[2][2] = 1.0 / l22;
+    li[1][0] = -l10 * li[0][0] / l11;
+    li[2][1] = -l21 * li[1][1] / l22;
+    li[2][0] = -(l20 * li[0][0] + l21 * li[1][0]) / l22;
+    li[0][1] = li[0][2] = li[1][2] = 0.0;
+    return true;
+}
+
+// G = Hpl_e L^-T (6 x 3): G[r][c] = sum_k Hpl[r][k] Linv[c][k]
+__device__ __forceinline__ void lm_g(const double* __restrict__ hpl, const double (&li)[3][3], double (&g)[6][3])
+{
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                s += hpl[r + 6 * k] * li[c][k];
+            g[r][c] = s;
+        }
+}
+
+__global__ __launch_bounds__(256) void k_lm_covariance(int L, const int32_t* __restrict__ lm_ptr,
+                                                       const int32_t* __restrict__ e_pose, const uint8_t* __restrict__ flags,
+                                                       const double* __restrict__ Hll, const double* __restrict__ Hpl,
+                                                       const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                       const double* __restrict__ sigma, double* __restrict__ out,
+                                                       int32_t* __restrict__ fail)
+{
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= L)
+        return;
+    double li[3][3];
+    if (!chol3_inv(Hll + 9L * l, li))
+    {
+        *fail = 1; // (every writer stores the same value)
+        for (int k = 0; k < 9; k++)
+            out[9L * l + k] = 0.0;
+        return;
+    }
+    double M[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    const int e0 = lm_ptr[l], e1 = lm_ptr[l + 1];
+    for (int e = e0; e < e1; e++)
+    {
+        if (flags[e] & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P | CUGO_EDGE_INACTIVE))
+            continue;
+        double ge[6][3];
+        lm_g(Hpl + 18L * e, li, ge);
+        const int pe = e_pose[e];
+        for (int f = e0; f < e1; f++)
+        {
+            if (flags[f] & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P | CUGO_EDGE_INACTIVE))
+                continue;
+            const int pf = e_pose[f];
+            // the Hsc block (min, max) of the pair: row min(pe, pf) of the upper block CSR
+            const int a = min(pe, pf), b = max(pe, pf);
+            int lo = rowptr[a], hi = rowptr[a + 1] - 1;
+            while (lo < hi)
+            {
+                const int mid = (lo + hi) >> 1;
+                if (colind[mid] < b)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            const double* S = sigma + 36L * lo; // Sigma_{a b}, column-major; Sigma_{pe pf} is it or its transpose
+            const bool tr = pe > pf;
+            double gf[6][3];
+            lm_g(Hpl + 18L * f, li, gf);
+            // X = Sigma_{pe pf} G_f (6 x 3), then M += G_e^T X
+            double X[6][3];
+#pragma unroll
+            for (int r = 0; r < 6; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                {
+                    double s = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 6; k++)
+                        s += (tr ? S[k + 6 * r] : S[r + 6 * k]) * gf[k][c];
+                    X[r][c] = s;
+                }
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                {
+                    double s = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 6; k++)
+                        s += ge[k][r] * X[k][c];
+                    M[r][c] += s;
+                }
+        }
+    }
+    // Sigma_l = L^-T M L^-1: [r][c] = sum_{a, b} Linv[a][r] M[a][b] Linv[b][c]
+    double Y[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            Y[a][c] = M[a][0] * li[0][c] + M[a][1] * li[1][c] + M[a][2] * li[2][c];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            const int rr = max(r, c), cc = min(r, c); // (the lower triangle, mirrored: exactly symmetric)
+            out[9L * l + r + 3 * c] = li[0][rr] * Y[0][cc] + li[1][rr] * Y[1][cc] + li[2][rr] * Y[2][cc];
+        }
+}
+
+// out[p] = the diagonal block of pose p: the first block of row p of the upper block CSR
+__global__ __launch_bounds__(256) void k_cov_pose_diag(int P, const int32_t* __restrict__ rowptr,
+                                                       const double* __restrict__ sigma, double* __restrict__ out)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 36L * P)
+        return;
+    out[i] = sigma[36L * rowptr[i / 36] + i % 36];
+}
+
+void ensure_lds(const void* fn, size_t bytes)
+{
+    if (bytes > 48 * 1024)
+        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+} // namespace
+
+namespace cugo_k
+{
+
+void launch_selinv_rows(hipStream_t s, const CholPlanDev& p, const double* d_fronts, double* d_sig,
+                        const int64_t* d_sinfo, const int32_t* d_items, int nitems)
+{
+    if (nitems <= 0)
+        return;
+    const size_t lds = SI_LDS_ROWS * sizeof(double);
+    ensure_lds(reinterpret_cast<const void*>(k_selinv_rows), lds);
+    CUGO_LAUNCH(k_selinv_rows, dim3(nitems), dim3(SI_T), lds, s, p, d_fronts, d_sig, d_sinfo, d_items);
+}
+
+void launch_selinv_jj(hipStream_t s, const CholPlanDev& p, const double* d_fronts, double* d_sig, int task0,
+                      int ntasks)
+{
+    if (ntasks <= 0)
+        return;
+    const size_t lds = SI_LDS_JJ * sizeof(double);
+    ensure_lds(reinterpret_cast<const void*>(k_selinv_jj), lds);
+    CUGO_LAUNCH(k_selinv_jj, dim3(ntasks), dim3(SI_T), lds, s, p, d_fronts, d_sig, task0);
+}
+
+void launch_selinv_subtree(hipStream_t s, const CholPlanDev& p, const double* d_fronts, double* d_sig,
+                           const int64_t* d_sinfo, int task0, int ntasks)
+{
+    if (ntasks <= 0)
+        return;
+    const size_t lds = std::max(SI_LDS_ROWS, SI_LDS_JJ) * sizeof(double);
+    ensure_lds(reinterpret_cast<const void*>(k_selinv_subtree), lds);
+    CUGO_LAUNCH(k_selinv_subtree, dim3(ntasks), dim3(SI_T), lds, s, p, d_fronts, d_sig, d_sinfo, task0);
+}
+
+void launch_selinv_gather(hipStream_t s, const CholPlanDev& p, const double* d_sig, double* d_out)
+{
+    const long n = 36L * p.n_hsc_blocks;
+    if (n <= 0)
+        return;
+    CUGO_LAUNCH(k_selinv_gather, dim3((unsigned)((n + SI_T - 1) / SI_T)), dim3(SI_T), 0, s, p, d_sig, d_out);
+}
+
+int selinv_row_tile() { return SI_R; }
+
+void launch_cov_pose_diag(hipStream_t s, int P, const int32_t* d_rowptr, const double* d_sigma, double* d_out)
+{
+    const long n = 36L * P;
+    if (n <= 0)
+        return;
+    CUGO_LAUNCH(k_cov_pose_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, d_rowptr, d_sigma, d_out);
+}
+
+void launch_lm_covariance(hipStream_t s, int L, const int32_t* d_lm_ptr, const int32_t* d_e_pose,
+                          const uint8_t* d_flags, const double* d_Hll, const double* d_Hpl, const int32_t* d_rowptr,
+                          const int32_t* d_colind, const double* d_sigma, double* d_out, int32_t* d_fail)
+{
+    if (L <= 0)
+        return;
+    CUGO_LAUNCH(k_lm_covariance, dim3((L + 255) / 256), dim3(256), 0, s, L, d_lm_ptr, d_e_pose, d_flags, d_Hll, d_Hpl,
+                d_rowptr, d_colind, d_sigma, d_out, d_fail);
+}
+
+} // namespace cugo_k

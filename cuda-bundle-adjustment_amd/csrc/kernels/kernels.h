@@ -264,4 +264,27 @@ size_t chol_lds_factor_bytes(int nc_max);
 size_t chol_lds_backward_bytes(int nc_max, long ld_max);
 int chol_max_pivot_cols(); // widest pivot block the kernels support (scalars)
 
+// --- marginal covariances (cov_kernels.hip) ----------------------------------------------
+// selected inverse of the factorisation a factor_solve left (W, L21 where the backward pass reads them) into
+// Sigma-fronts laid out like the fronts.  d_sinfo [n_fronts][4]: offset and leading dimension of the parent's
+// Sigma-front, offset of the front's rel list, 1 = copy S_RR into the front's own Sigma-front
+// rows: items (front, first row) of 64-row tiles of R; jj: one workgroup per task of an upper stage;
+// subtree: one workgroup per subtree task of stage 0 (both parts, front by front)
+void launch_selinv_rows(hipStream_t s, const CholPlanDev& p, const double* d_fronts, double* d_sig,
+                        const int64_t* d_sinfo, const int32_t* d_items, int nitems);
+void launch_selinv_jj(hipStream_t s, const CholPlanDev& p, const double* d_fronts, double* d_sig, int task0,
+                      int ntasks);
+void launch_selinv_subtree(hipStream_t s, const CholPlanDev& p, const double* d_fronts, double* d_sig,
+                           const int64_t* d_sinfo, int task0, int ntasks);
+// d_out [n_hsc_blocks][36]: the blocks of Sigma on the Hsc pattern (layout of d_Hsc)
+void launch_selinv_gather(hipStream_t s, const CholPlanDev& p, const double* d_sig, double* d_out);
+int selinv_row_tile(); // rows of R per k_selinv_rows item
+// d_out [P][36]: the diagonal blocks of d_sigma (the first block of every row of the upper block CSR d_rowptr)
+void launch_cov_pose_diag(hipStream_t s, int P, const int32_t* d_rowptr, const double* d_sigma, double* d_out);
+// Sigma_l [L][9] of every free landmark from Hll, Hpl (landmark-major edge slots) and the pose blocks d_sigma on the
+// Hsc pattern (upper block CSR d_rowptr / d_colind); *d_fail = 1 if an Hll is not positive definite
+void launch_lm_covariance(hipStream_t s, int L, const int32_t* d_lm_ptr, const int32_t* d_e_pose,
+                          const uint8_t* d_flags, const double* d_Hll, const double* d_Hpl, const int32_t* d_rowptr,
+                          const int32_t* d_colind, const double* d_sigma, double* d_out, int32_t* d_fail);
+
 } // namespace cugo_k

@@ -153,6 +153,18 @@ public:
     /** a run-time switch of this optimiser ("flatten_reuse", "structure_reuse", "init_timing"; the optimiser took a
      *  snapshot of the CUGO_* environment variables when it was created); false: unknown name */
     bool setOption(const char* name, int value);
+    /** marginal covariances at the current estimates (g2o SparseOptimizer::computeMarginals, Ceres Covariance):
+     *  Sigma = H^-1 of the undamped J^T Omega J (robust weights included) over the free vertices, diagonal blocks
+     *  only; kept until the next initialize().  false: a zero pivot (an unconstrained gauge, a free pose without
+     *  edges, a landmark seen too little).  Throws std::runtime_error before initialize() and on plan-only,
+     *  sharded or fp32-internal optimisers. */
+    bool computeMarginals(bool poses = true, bool landmarks = true);
+    /** the 6x6 block of a pose (column-major, tangent order [rotation, translation] of the left update
+     *  T <- exp([w, v]) T); all zero for a fixed pose.  false: no pose blocks were computed since the last
+     *  initialize(), v is not a pose vertex, or its set changed since (vertex added, removed, fixed / freed) */
+    bool poseCovariance(const BaseVertex* v, double cov[36]) const;
+    /** the 3x3 block of a landmark (column-major); all zero for a fixed landmark.  false: as poseCovariance */
+    bool landmarkCovariance(const BaseVertex* v, double cov[9]) const;
 
 private:
     bool verbose = false;
@@ -169,6 +181,8 @@ private:
     std::vector<std::pair<const void*, unsigned long long>> flattenCounts_;
     bool flattenOptions_[3] = {false, false, false};
     bool flattenValid_ = false;
+    bool initialized_ = false; // initialize() ran (computeMarginals needs it)
+    bool flattenedUnchanged(const BaseVertexSet* vs) const;
     int flattenReuses_ = 0;
     // edges handed to the engine at initialize(), in that order (outlier rejection maps back)
     std::vector<BaseEdge*> flatEdges_;

@@ -204,6 +204,14 @@ int cugo_chol_analyze(cugo_chol* s, int n_block_rows, const int32_t* h_rowptr,
  * d_fail[0] (int32 device, 0 = ok) — ref: solve()->bool, zero pivot tol 1e-14. */
 int cugo_chol_factor_solve(cugo_chol* s, const double* d_Hsc, double lambda, const double* d_bsc,
                            double* d_x, int32_t* d_fail);
+/* Extension (g2o SparseOptimizer::computeMarginals, Ceres Covariance): after a successful
+ * cugo_chol_factor_solve(s, d_Hsc, lambda, ...): the blocks of (A + lambda I)^-1 on the analysed
+ * pattern, same layout as d_Hsc ([nnzb][36], upper block CSR, diagonal first, column-major).
+ * Synchronises once to read the zero-pivot flag of that factorisation (CUGO_ERR_NUMERIC if it is set;
+ * its d_fail must still be valid), then enqueues on the context's stream.  CUGO_ERR_INVALID if no
+ * factorisation ran since analyze(), or if the solver factors rank-owned subtrees.  The first call
+ * after analyze() allocates a buffer of the size of the fronts (cugo_chol_stats: front_bytes). */
+int cugo_chol_selected_inverse(cugo_chol* s, double* d_sigma);
 /* statistics of the analysis: nnz(L) in scalars, factorisation flops, #supernodes, #stages */
 int cugo_chol_stats(const cugo_chol* s, double* nnzL, double* flops, int* n_supernodes,
                     int* n_stages, double* front_bytes);
@@ -217,6 +225,10 @@ int cugo_chol_plan_get(const cugo_chol* s, int32_t* perm, int32_t* super_ptr, in
  * "task_fronts", "blk_front", "blk_row", "blk_col", "blk_trans"); pointer valid until the
  * next analyze()/destroy. Returns the length or a negative error. */
 int cugo_chol_plan_array(cugo_chol* s, const char* name, const int32_t** out);
+/* the same for the int64 per-front arrays of the storage layout: "off" (offset of the front in the
+ * fronts buffer, doubles), "ldf" (its leading dimension), "woff" (offset of W = L11^-1), "l21off"
+ * (offset of the compact L21, -1: in the front itself) */
+int cugo_chol_plan_array64(cugo_chol* s, const char* name, const int64_t** out);
 
 /* ref: gpu::schurComplementPost + updatePoses + updateLandmarks + computeScale
  * (cuda_block_solver.h:133-150; .cu:1419-1490).  Reads estimates from d_*_in, writes the
@@ -322,6 +334,19 @@ int cugo_graph_get_landmarks(cugo_graph* g, int n, const int32_t* ids, double* x
 int cugo_graph_set_poses(cugo_graph* g, int n, const int32_t* ids, const double* q_t7);
 int cugo_graph_set_landmarks(cugo_graph* g, int n, const int32_t* ids, const double* xyz);
 int cugo_graph_n_active_edges(cugo_graph* g);
+/* Extension: marginal covariances (g2o SparseOptimizer::computeMarginals, Ceres Covariance).
+ * what: 1 poses, 2 landmarks, 3 both.  Builds J^T Omega J at lambda = 0 at the current estimates (robust
+ * weights included, the edges of the current flattening), forms the Schur complement, factors it and runs
+ * the selected inverse (cugo_chol_selected_inverse); the landmark blocks follow from the pose blocks.  The
+ * results are kept until the next initialize(); the estimates and the LM state are left as they were.
+ * CUGO_ERR_NUMERIC on a zero pivot (e.g. an unconstrained gauge or an edgeless free pose),
+ * CUGO_ERR_INVALID before initialize(), on plan-only, sharded or fp32-internal graphs. */
+int cugo_graph_compute_covariances(cugo_graph* g, int what);
+/* diagonal blocks by caller id: cov36 [n][36] (6x6, column-major, tangent order [rotation, translation]
+ * of the left update T <- exp([w, v]) T), cov9 [n][9] (3x3, column-major); zeros for fixed vertices.
+ * CUGO_ERR_INVALID if that kind was not computed since the last initialize(). */
+int cugo_graph_get_pose_covariances(cugo_graph* g, int n, const int32_t* ids, double* cov36);
+int cugo_graph_get_landmark_covariances(cugo_graph* g, int n, const int32_t* ids, double* cov9);
 /* per-phase milliseconds accumulated since initialize(): ref getTimeProfile
  * (block_solver.cpp:470-488).  names is a '\n' separated list written into buf. */
 int cugo_graph_time_profile(cugo_graph* g, char* names_buf, int buf_len, double* ms, int cap);
