@@ -336,6 +336,8 @@ int cugo_chol_plan_array(cugo_chol* s, const char* name, const int32_t** out)
     }
     if (n == "blk_trans")
         v = &s->trans32;
+    if (n == "ea1") // kernels.h: CholPlanDev::ea1, EA1_REC ints per child link, fronts in order, children in child order
+        v = &s->ea1;
     if (!v)
     {
         set_last_error("cugo_chol_plan_array: unknown array " + n);

@@ -41,7 +41,9 @@ void cugo_chol::pack()
     // one 64-byte record per task (kernels.h: CholPlanDev::tmeta)
     const size_t ntask = P.task_ptr.empty() ? 0 : P.task_ptr.size() - 1; // (no free pose: an empty plan)
     // child records of the extend-add into F11 (kernels.h: CholPlanDev::ea1), per front in child order
-    std::vector<int32_t> ea1, ea1_ptr(P.n_super + 1, 0);
+    constexpr int R = cugo_k::EA1_REC;
+    std::vector<int32_t> ea1_ptr(P.n_super + 1, 0);
+    ea1.clear();
     for (int f = 0; f < P.n_super; f++)
     {
         if (P.alias_of[f] < 0)
@@ -50,14 +52,27 @@ void cugo_chol::pack()
                 const int c = P.child[k];
                 const int64_t ncs_c = 6 * (int64_t)P.ncb[c], ldc = P.ldf[c];
                 const int64_t q[2] = {P.off[c] + ncs_c * ldc + ncs_c, ldc};
-                int32_t r[8] = {c, P.nb[c] - P.ncb[c], P.la_np[c], P.rel_ptr[c], 0, 0, 0, 0};
+                int32_t r[R] = {c, P.nb[c] - P.ncb[c], P.la_np[c], P.rel_ptr[c]};
                 std::memcpy(r + 4, q, sizeof q);
-                ea1.insert(ea1.end(), r, r + 8);
+                // the parent pivot block rows the child's leading rows land on (rel is ascending: the child's
+                // leading block row b is the b-th set bit); a pivot block has <= 16 block columns
+                uint32_t mask = 0;
+                for (int b = 0; b < P.la_np[c]; b++)
+                {
+                    const int pr = P.rel[P.rel_ptr[c] + b];
+                    if (pr < 0 || pr >= 32 || pr >= P.ncb[f])
+                        throw std::runtime_error("cugo: a child's leading row lies outside its parent's pivot block");
+                    mask |= 1u << pr;
+                }
+                r[8] = (int32_t)mask;
+                ea1.insert(ea1.end(), r, r + R);
             }
-        ea1_ptr[f + 1] = (int32_t)(ea1.size() / 8);
+        ea1_ptr[f + 1] = (int32_t)(ea1.size() / R);
     }
-    ea1.resize(ea1.size() + 8, 0);
+    const size_t n_ea1 = ea1.size();
+    ea1.resize(n_ea1 + R, 0);
     const size_t o_ea1 = put32(ea1);
+    ea1.resize(n_ea1); // (cugo_chol_plan_array "ea1": the records alone)
     std::vector<int32_t> tmeta(cugo_k::TMETA * ntask, 0);
     for (size_t t = 0; t < ntask; t++)
     {
@@ -154,7 +169,7 @@ void cugo_chol::upload(hipStream_t s)
     D.n = P.n, D.perm = b32 + o_perm, D.col_front = b32 + o_col_front;
     D.junk = d_junk.data();
     D.woff = b64 + o_woff, D.winv = d_winv.data(), D.nc_max = P.nc_max;
-    D.ea_lds = opt.ea_lds, D.panel16 = opt.panel16;
+    D.ea_lds = opt.ea_lds, D.panel16 = opt.panel16, D.ea_direct = opt.ea_direct;
 #ifdef CUGO_DEBUG_HOOKS
     {
         const char* ka = std::getenv("CUGO_KERNEL_ACQUIRE");

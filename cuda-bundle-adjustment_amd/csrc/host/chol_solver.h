@@ -17,6 +17,7 @@ struct cugo_chol
     cugo_host::CholPlan plan;
     std::vector<int32_t> trans32; // blk_trans widened for cugo_chol_plan_array
     std::vector<int32_t> asm_info; // (cugo_chol_plan_array)
+    std::vector<int32_t> ea1;      // the child link records of CholPlanDev::ea1 (pack; cugo_chol_plan_array)
     cugo_k::CholPlanDev dev{};
     size_t lds_factor = 0, lds_backward = 0;
     // CUGO_LOOKAHEAD=1 at analyze(): the bulk of a level's update matrix is computed while the next level

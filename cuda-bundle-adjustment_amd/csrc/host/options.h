@@ -32,6 +32,7 @@ struct Options
     double own_min_gflop = 3.0;     // CUGO_OWN_MIN_GFLOP
     bool lookahead = false;         // CUGO_LOOKAHEAD
     bool ea_lds = true, panel16 = true, asm_fronts = true; // CUGO_EA_LDS / CUGO_PANEL16 / CUGO_ASM_FRONTS = 0
+    bool ea_direct = true;          // CUGO_EA_DIRECT=0: the potrf gathers its children's F11 terms unit by unit again
     // ---- multi-GPU exchange (engine.cpp) ----
     bool reduce_scatter = true;     // CUGO_REDUCE_SCATTER=0: all-reduce of [Hsc | bsc] also with rank-owned subtrees
 
@@ -71,6 +72,7 @@ struct Options
         if (const char* e = std::getenv("CUGO_LOOKAHEAD"))
             o.lookahead = std::atoi(e) != 0;
         o.ea_lds = !off("CUGO_EA_LDS"), o.panel16 = !off("CUGO_PANEL16"), o.asm_fronts = !off("CUGO_ASM_FRONTS");
+        o.ea_direct = !off("CUGO_EA_DIRECT");
         o.reduce_scatter = !off("CUGO_REDUCE_SCATTER");
         return o;
     }

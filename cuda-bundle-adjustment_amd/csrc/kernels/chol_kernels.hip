@@ -345,7 +345,7 @@ __device__ __forceinline__ void dev_extend_add_lead(const CholPlanDev& p, const 
     double* sink = p.junk + ((blockIdx.x & 63) << 10) + threadIdx.x;
     for (int k = e0; k < e1; k++)
     {
-        const int32_t* d = p.ea1 + 8 * k;
+        const int32_t* d = p.ea1 + cugo_k::EA1_REC * k;
         const long* d64 = reinterpret_cast<const long*>(d + 4);
         const int nbr = d[1], np = d[2];
         const int32_t* rel = p.rel + d[3];
@@ -394,7 +394,7 @@ __device__ __forceinline__ void l11_issue(const double* __restrict__ F, long ld,
         }
 }
 // MIRROR: the diagonal 16x16 tiles are stored symmetric right away (what dev_potrf16 otherwise does in a pass of
-// its own after the extend-add: a front without children to add needs no such pass)
+// its own after the extend-add: a front whose children's terms are added before the store needs no such pass)
 template <bool MIRROR = false>
 __device__ __forceinline__ void l11_store(int nc, const double (&v)[3][3], double* __restrict__ Ls)
 {
@@ -422,6 +422,66 @@ __device__ __forceinline__ void dev_load_l11(const double* __restrict__ F, long 
     double v[3][3];
     l11_issue(F, ld, nc, v);
     l11_store<MIRROR>(nc, v, Ls);
+}
+
+// The children's contributions to F11 added in registers between l11_issue and l11_store: the same terms as
+// dev_extend_add_lead, read straight from the children's update blocks.  A child's update block is final once
+// its tile launch has run; its leading np block rows land on the parent pivot block rows of the ea1 record's
+// block mask m, in order (rel is ascending: child block row b <-> the b-th set bit of m).  So parent entry
+// (r, c), r >= c, takes a term from child k iff blocks r/6 and c/6 are both in m, and the child's own row of
+// parent row r is 6 popcount(m below block r/6) + r mod 6 — no rel list, no per-child barrier, and the diagonal
+// tiles can be stored mirrored (no mirror pass).  Per entry the sum is ((F11 + u_1) + u_2) ..., children in ea1
+// order, positions a child does not cover are skipped (not added a zero): bit for bit the gather's values.
+// Two children per round, all their loads issued before the first add.
+__device__ __forceinline__ void l11_add_children(const CholPlanDev& p, const double* __restrict__ fronts, int e0,
+                                                 int e1, int nc, double (&v)[3][3])
+{
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    int cb[3], rb[3]; // block column of c = ty + 32u, block row of r = tx + 32q
+#pragma unroll
+    for (int u = 0; u < 3; u++)
+        cb[u] = (ty + 32 * u) / 6, rb[u] = (tx + 32 * u) / 6;
+    for (int k = e0; k < e1; k += 2)
+    {
+        double s[2][3][3];
+        bool ok[2][3][3];
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+        {
+            const int32_t* d = p.ea1 + cugo_k::EA1_REC * min(k + h, e1 - 1); // (uniform: scalar loads)
+            const long* d64 = reinterpret_cast<const long*>(d + 4);
+            const double* U = fronts + d64[0];
+            const unsigned ldc = (unsigned)d64[1], m = (unsigned)d[8] & (k + h < e1 ? 0xFFFFu : 0u);
+            unsigned jc[3], jr[3];
+            bool inc[3], inr[3];
+#pragma unroll
+            for (int u = 0; u < 3; u++)
+            {
+                const int c = ty + 32 * u, r = tx + 32 * u;
+                inc[u] = (m >> cb[u]) & 1u, inr[u] = (m >> rb[u]) & 1u;
+                jc[u] = 6 * __popc(m & ((1u << cb[u]) - 1u)) + (c - 6 * cb[u]);
+                jr[u] = 6 * __popc(m & ((1u << rb[u]) - 1u)) + (r - 6 * rb[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 3; u++)
+#pragma unroll
+                for (int q = 0; q < 3; q++)
+                {
+                    const int c = ty + 32 * u, r = tx + 32 * q;
+                    // masked positions read the child's first entry (a valid address, no branch)
+                    ok[h][u][q] = q >= u && inc[u] && inr[q] && r >= c && r < nc;
+                    s[h][u][q] = q < u ? 0.0 : ldg32(U, ok[h][u][q] ? jc[u] * ldc + jr[q] : 0u);
+                }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int u = 0; u < 3; u++)
+#pragma unroll
+                for (int q = 0; q < 3; q++)
+                    if (q >= u)
+                        v[u][q] = ok[h][u][q] ? v[u][q] + s[h][u][q] : v[u][q];
+    }
 }
 
 // Factor the 6-column panel starting at (j0,j0) of the LDS matrix Ls by ONE wave, in registers.
@@ -677,6 +737,20 @@ __device__ __forceinline__ void dev_potrf_load(const double* __restrict__ F, lon
     dev_load_l11<MIRROR>(F, ld, nc, Ls);
     if (threadIdx.x < NC_MAX)
         dinv[threadIdx.x] = 1.0; // identity padding; the panels overwrite the real columns
+    __syncthreads();
+}
+// the same with the children's contributions (ea1 records [e0, e1)) added on the way in (l11_add_children)
+template <bool MIRROR = false>
+__device__ __forceinline__ void dev_potrf_load_children(const CholPlanDev& p, const double* __restrict__ fronts,
+                                                        const double* __restrict__ F, long ld, int nc, int e0, int e1,
+                                                        double* __restrict__ Ls, double* __restrict__ dinv)
+{
+    double v[3][3];
+    l11_issue(F, ld, nc, v);
+    l11_add_children(p, fronts, e0, e1, nc, v);
+    l11_store<MIRROR>(nc, v, Ls);
+    if (threadIdx.x < NC_MAX)
+        dinv[threadIdx.x] = 1.0;
     __syncthreads();
 }
 
@@ -1081,7 +1155,7 @@ __device__ __forceinline__ void dev_potrf16(int ncp, double* __restrict__ lds, d
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // the diagonal 16x16 tiles become symmetric: the trailing update treats them as full tiles and a
     // panel load is then the same plain column walk for every lane
-    if (!mirrored) // (uniform; a front without children to add had its tiles mirrored by the load)
+    if (!mirrored) // (uniform; the load mirrored them when nothing is added to F11 after it)
     {
         for (int e = threadIdx.x; e < nblk * 256; e += blockDim.x)
         {
@@ -2272,14 +2346,25 @@ __global__ __launch_bounds__(BIG) void k_up_potrf(CholPlanDev p, double* __restr
         __threadfence_block();
         __syncthreads();
     }
-    const bool mirror_now = p.panel16 && !kids; // nothing will be added to F11: the diagonal tiles go in symmetric
-    if (mirror_now)
+    // the children's terms added in registers as F11 comes in (l11_add_children; CUGO_EA_DIRECT=0: gathered below)
+    const bool direct = kids && p.ea_lds && p.ea_direct;
+    // nothing will be added to F11 after the load: the diagonal tiles go in symmetric
+    const bool mirror_now = p.panel16 && (!kids || direct);
+    if (direct)
+    { // (hooks build, omission pattern 30: without the children's contributions)
+        const int e1 = DBG_DELAY(p) == 30 ? tm[16] : tm[17];
+        if (mirror_now)
+            dev_potrf_load_children<true>(p, fronts, fronts + foff, fld, ncs, tm[16], e1, Ls, dinv);
+        else
+            dev_potrf_load_children(p, fronts, fronts + foff, fld, ncs, tm[16], e1, Ls, dinv);
+    }
+    else if (mirror_now)
         dev_potrf_load<true>(fronts + foff, fld, ncs, Ls, dinv);
     else
         dev_potrf_load(fronts + foff, fld, ncs, Ls, dinv);
     stamp(0, 1);
-    if (kids && p.ea_lds)
-    { // straight into the LDS copy (Vs: unused until the W phase, serves as the masked lanes' sink).
+    if (kids && p.ea_lds && !direct)
+    { // (CUGO_EA_DIRECT=0) straight into the LDS copy (Vs: unused until the W phase, serves as the masked lanes' sink).
       // (Measured, not kept: the rel entries and update-block entries of two children fetched into registers
       // before / beside the loads of F11 — every global load of the phase in flight at once, only the LDS adds
       // child after child: 11.57 vs 11.22 ms per step on the kitti_00 shape, 38.1 vs 37.5 ms on the 10k-pose

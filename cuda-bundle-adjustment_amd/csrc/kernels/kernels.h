@@ -140,6 +140,7 @@ void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, 
 // --- multifrontal LL^T (chol_kernels.hip) -------------------------------------------------
 // Device-side plan; all index arrays in units of 6x6 blocks unless noted.
 constexpr int TMETA = 36; // ints per task record (CholPlanDev::tmeta)
+constexpr int EA1_REC = 16; // ints per child link record (CholPlanDev::ea1): one 64-byte line
 struct CholPlanDev
 {
     int n_fronts;
@@ -161,6 +162,9 @@ struct CholPlanDev
     int nc_max;                // widest pivot block (scalars)
     int ea_lds;                // potrf: children's contributions to F11 go straight into its LDS copy
     int panel16;               // potrf: 16-column register panels (CUGO_PANEL16=0: the 6-column LDS panels)
+    int ea_direct;             // potrf: the children's F11 terms are added in registers as F11 is loaded, read
+                               // straight from their lead blocks through the ea1 block masks (CUGO_EA_DIRECT=0: gathered
+                               // child after child into the LDS copy)
 #ifdef CUGO_DEBUG_HOOKS // (make HOOKS=1 -> libcugo_hip_hooks.so; the product build carries none of this)
     int kernel_acquire;        // CUGO_KERNEL_ACQUIRE: bit 0 = every kernel of the factorisation starts with an agent-scope acquire fence, bit 1 = ends with a release fence
     int dbg_delay;             // diagnosis (CUGO_DEBUG_DELAY): which waves / workgroups of the factorisation's kernels sleep (chol_kernels.hip: dbg_sleep)
@@ -177,9 +181,11 @@ struct CholPlanDev
     const int32_t* rel;        // position (block row in the parent front) of each boundary row
     // schedule
     int n_stages;
-    const int32_t* ea1;        // per child link: {child, its boundary block rows, its leading rows inside the
-                               // parent's pivots, offset of its rel list, update-block offset (int64), its leading
-                               // dimension (int64)} — the potrf workgroup's extend-add into F11 (tmeta[16..17])
+    const int32_t* ea1;        // per child link, EA1_REC ints: {child, its boundary block rows, its leading rows inside
+                               // the parent's pivots, offset of its rel list, update-block offset (int64), its leading
+                               // dimension (int64), block mask of the parent pivot block rows those leading rows land
+                               // on (bit rel[b], b < leading rows), 0 ...} — the potrf workgroup's extend-add into F11
+                               // (tmeta[16..17])
     const int32_t* tmeta;      // [n_tasks_total][TMETA] (16..17: range in ea1, 18..19 unused): {fronts in the task, first front, its ncb, nb, col0, bw_np,
                                // rows_ptr, has-children-to-add flag, off, ldf, woff, l21off (four int64)} (potrf, backward substitution);
                                // 20..35: the front's first 16 boundary block rows (those inside its parent's pivot block: the
