@@ -49,6 +49,19 @@ class Robust(C.Structure):
                 ("delta_stereo", C.c_double)]
 
 
+class IcpEdges(C.Structure):
+    """cugo_icp_edges: point-to-plane / point-to-line pose edges, pose-sorted structure of arrays (cugo_hip.h)."""
+    _fields_ = [("n_poses_total", C.c_int), ("n_poses_free", C.c_int),
+                ("n_plane", C.c_int), ("d_plane_pose", C.c_void_p), ("d_plane_pose_ptr", C.c_void_p),
+                ("d_plane_p", C.c_void_p), ("d_plane_nd", C.c_void_p), ("d_plane_omega", C.c_void_p),
+                ("n_plane_omega", C.c_int), ("d_plane_flags", C.c_void_p), ("rk_plane", C.c_int),
+                ("delta_plane", C.c_double),
+                ("n_line", C.c_int), ("d_line_pose", C.c_void_p), ("d_line_pose_ptr", C.c_void_p),
+                ("d_line_p", C.c_void_p), ("d_line_au", C.c_void_p), ("d_line_omega", C.c_void_p),
+                ("n_line_omega", C.c_int), ("d_line_flags", C.c_void_p), ("rk_line", C.c_int),
+                ("delta_line", C.c_double)]
+
+
 class HscStruct(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("d_rowptr", C.c_void_p), ("d_colind", C.c_void_p),
                 ("d_off_ptr", C.c_void_p), ("d_off_ei", C.c_void_p), ("d_off_ej", C.c_void_p),

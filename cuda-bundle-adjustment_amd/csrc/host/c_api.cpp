@@ -1,4 +1,5 @@
 // extern "C" surface of libcugo_hip.so (declared in include/cugo_hip.h).
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -137,6 +138,90 @@ int cugo_construct_quadratic_form(cugo_ctx* ctx, const cugo_edges* ev, const dou
     return guarded([&] {
         cugo_k::launch_build(ctx->stream, *ev, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl,
                              scratch_for(ctx, ev), d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+} // extern "C"
+
+namespace
+{
+// the ICP kernels index their partials by (chunk + pose) and read pose_ptr: before anything is launched, pose_ptr
+// (n_poses_total + 1 entries) is checked on the host and the pose index of every edge against it on the device
+// (one flag comes back), so that a bad layout is refused instead of addressing memory out of range
+void check_icp_kind(cugo_ctx* ctx, const char* what, int n, int P, const int32_t* d_pose, const int32_t* d_ptr,
+                    const double* d_p, const double* d_geo, const double* d_omega, int n_omega, int rk, double delta)
+{
+    const std::string in = std::string(" (") + what + ")";
+    if (n < 0)
+        throw std::runtime_error("cugo_icp: negative edge count" + in);
+    if (!d_ptr)
+        throw std::runtime_error("cugo_icp: no pose_ptr" + in);
+    if (rk < CUGO_RK_NONE || rk > CUGO_RK_HUBER || (rk != CUGO_RK_NONE && !(delta > 0.0 && std::isfinite(delta))))
+        throw std::runtime_error("cugo_icp: unknown robust kernel or bad delta" + in);
+    if (n > 0 && (!d_pose || !d_p || !d_geo || !d_omega || (n_omega != 1 && n_omega != n)))
+        throw std::runtime_error("cugo_icp: missing arrays" + in);
+    std::vector<int32_t> ptr(P + 1);
+    CUGO_HIP(hipMemcpyAsync(ptr.data(), d_ptr, sizeof(int32_t) * (P + 1), hipMemcpyDeviceToHost, ctx->stream));
+    CUGO_HIP(hipStreamSynchronize(ctx->stream));
+    if (ptr[0] != 0 || ptr[P] != n)
+        throw std::runtime_error("cugo_icp: pose_ptr does not span the edges" + in);
+    for (int p = 0; p < P; p++)
+        if (ptr[p + 1] < ptr[p])
+            throw std::runtime_error("cugo_icp: pose_ptr not ascending" + in);
+}
+
+void check_icp(cugo_ctx* ctx, const cugo_icp_edges* ev, cugo_k::ReduceScratch rs)
+{
+    check_icp_kind(ctx, "plane", ev->n_plane, ev->n_poses_total, ev->d_plane_pose, ev->d_plane_pose_ptr, ev->d_plane_p,
+                   ev->d_plane_nd, ev->d_plane_omega, ev->n_plane_omega, ev->rk_plane, ev->delta_plane);
+    check_icp_kind(ctx, "line", ev->n_line, ev->n_poses_total, ev->d_line_pose, ev->d_line_pose_ptr, ev->d_line_p,
+                   ev->d_line_au, ev->d_line_omega, ev->n_line_omega, ev->rk_line, ev->delta_line);
+    if (cugo_k::icp_check_indices(ctx->stream, *ev, rs))
+        throw std::runtime_error("cugo_icp: edges not sorted by pose, or a pose index disagrees with pose_ptr");
+}
+
+void check_icp_counts(const cugo_icp_edges* ev)
+{
+    if (!ev || ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total ||
+        ev->n_plane < 0 || ev->n_line < 0)
+        throw std::runtime_error("cugo_icp: bad pose or edge counts");
+}
+
+cugo_k::ReduceScratch icp_scratch_for(cugo_ctx* ctx, const cugo_icp_edges* ev)
+{
+    const size_t need = cugo_k::icp_scratch_doubles(*ev);
+    if (ctx->scratch.size() < need)
+    {
+        CUGO_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->scratch.resize(need);
+    }
+    return {ctx->scratch.data(), ctx->scratch.size()};
+}
+} // namespace
+
+extern "C" {
+
+int cugo_icp_compute_errors(cugo_ctx* ctx, const cugo_icp_edges* ev, const double* d_poses, double* d_chi,
+                            double* d_edge_chi)
+{
+    return guarded([&] {
+        check_icp_counts(ev);
+        const cugo_k::ReduceScratch rs = icp_scratch_for(ctx, ev);
+        check_icp(ctx, ev, rs);
+        cugo_k::launch_icp_errors(ctx->stream, *ev, d_poses, rs, d_chi, false, d_edge_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_icp_construct_quadratic_form(cugo_ctx* ctx, const cugo_icp_edges* ev, const double* d_poses, double* d_Hpp,
+                                      double* d_bp, double* d_chi)
+{
+    return guarded([&] {
+        check_icp_counts(ev);
+        const cugo_k::ReduceScratch rs = icp_scratch_for(ctx, ev);
+        check_icp(ctx, ev, rs);
+        cugo_k::launch_icp_build(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs, d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
 }

@@ -248,6 +248,9 @@ void CudaGraphOptimisationImpl::initialize()
     for (BaseEdgeSet* es : edgeSets)
     {
         const int dim = es->dim();
+        if (dim == 1) // PlaneEdgeSet / LineEdgeSet (icp_types.h)
+            throw std::runtime_error("cugo: the optimiser does not take point-to-plane / point-to-line edge sets yet "
+                                     "(their terms: cugo_icp_* in include/cugo_hip.h)");
         if (dim != 2 && dim != 3)
             throw std::runtime_error("cugo: only 2-d (mono) and 3-d (stereo) BA edge sets are supported");
         const uint8_t stereo_bit = dim == 3 ? CUGO_EDGE_STEREO : 0;

@@ -1,0 +1,423 @@
+// Point-to-plane and point-to-line pose edges (the reference's include/icp_types.h): unary edges on a pose vertex.
+// y = R(q) p + t is read as BA reads a pose (ba_math.h world_to_cam); the update is the left update in the tangent
+// order [omega, upsilon], so dy/dxi = [ -[y]x | I ].
+//   plane: r = n.y - d (scalar),            J = [ y x n | n^T ]          (1 x 6)
+//   line:  r = P (y - a), P = I - u u^T,    J = P [ -[y]x | I ]          (3 x 6; |r| is the distance to the line)
+// chi2 term rho(omega |r|^2), weight w = omega rho'(omega |r|^2); H += w J^T J, b -= w J^T r.  The minus is the BA
+// build pass's convention: its Jacobian is d(meas - proj)/dxi = -de/dxi (ba_math.h jac_pose), so its bp is minus half
+// the gradient of chi2, the solver takes H dx = b and the update applies exp(+dx) (k_backsubst_poses).  Edges on fixed
+// poses (index >= n_poses_free) and inactive edges contribute nothing.
+//
+// Layout and reduction (no atomics, one fixed order):  each kind's edges are sorted by pose index.  The edge range
+// is cut into chunks of ICP_CHUNK edges regardless of pose boundaries, one wave per chunk; a chunk writes one partial
+// of 28 doubles (21 of the upper triangle of H, 6 of b, chi2) per pose it touches.  Chunk c and pose p meet in at
+// most one partial, and along the sorted edges c and p never decrease and one of them grows at each step from one
+// (chunk, pose) pair to the next: c + p is therefore a unique slot index — no prefix sums, no plan.  The finishing
+// pass sums a pose's partials in chunk order (plane kind, then line kind) and adds them to Hpp / bp; the chi2 total
+// is the sum of the per-pose sums in pose order.  The error pass forms the very same chi2 partials, so its total has
+// the bits of the build pass's.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <climits>
+#include <stdexcept>
+
+#include "ba_math.h"
+#include "kernels.h"
+
+namespace
+{
+
+using namespace cugo_dev;
+
+constexpr int ICP_CHUNK = 512; // edges per wave
+constexpr int ICP_NP = 28;     // doubles per partial
+constexpr int ICP_WG = 256;
+
+struct IcpKind
+{
+    int n;
+    const int32_t* pose;
+    const int32_t* pose_ptr;
+    const double* p;   // [3][n]
+    const double* geo; // plane: [4][n] n, d; line: [6][n] a, u
+    const double* omega;
+    int n_omega;
+    const uint8_t* flags;
+    Robust rk;
+    double* part; // [n_chunks + n_poses_total][ICP_NP]
+};
+
+__device__ __forceinline__ int n_chunks(int n) { return (n + ICP_CHUNK - 1) / ICP_CHUNK; }
+
+// contribution of edge e of one kind: v[0..20] upper triangle of w J^T J (row-major packed), v[21..26] -w J^T r;
+// returns the chi2 term
+template <bool LINE, bool FULL>
+__device__ __forceinline__ double icp_edge(const IcpKind& k, int e, const double* __restrict__ pose, double (&v)[32])
+{
+    const int n = k.n;
+    const double pp[3] = {k.p[e], k.p[n + e], k.p[2 * (size_t)n + e]};
+    double y[3];
+    world_to_cam(pose, pp, y);
+    double r[3], J[3][6];
+    double sq;
+    if (!LINE)
+    {
+        const double nx = k.geo[e], ny = k.geo[n + e], nz = k.geo[2 * (size_t)n + e], d = k.geo[3 * (size_t)n + e];
+        r[0] = nx * y[0] + ny * y[1] + nz * y[2] - d;
+        sq = r[0] * r[0];
+        // y x n
+        J[0][0] = y[1] * nz - y[2] * ny;
+        J[0][1] = y[2] * nx - y[0] * nz;
+        J[0][2] = y[0] * ny - y[1] * nx;
+        J[0][3] = nx, J[0][4] = ny, J[0][5] = nz;
+    }
+    else
+    {
+        const double a[3] = {k.geo[e], k.geo[n + e], k.geo[2 * (size_t)n + e]};
+        const double u[3] = {k.geo[3 * (size_t)n + e], k.geo[4 * (size_t)n + e], k.geo[5 * (size_t)n + e]};
+        const double dv[3] = {y[0] - a[0], y[1] - a[1], y[2] - a[2]};
+        const double ud = u[0] * dv[0] + u[1] * dv[1] + u[2] * dv[2];
+        double P[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+        {
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                P[i][j] = (i == j ? 1.0 : 0.0) - u[i] * u[j];
+            r[i] = dv[i] - u[i] * ud;
+        }
+        sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+        // -[y]x columns: (0, -y2, y1), (y2, 0, -y0), (-y1, y0, 0)
+        const double S[3][3] = {{0.0, y[2], -y[1]}, {-y[2], 0.0, y[0]}, {y[1], -y[0], 0.0}};
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+            {
+                J[i][j] = P[i][0] * S[0][j] + P[i][1] * S[1][j] + P[i][2] * S[2][j];
+                J[i][3 + j] = P[i][j];
+            }
+    }
+    const double omega = k.omega[k.n_omega == 1 ? 0 : e];
+    const double x = omega * sq;
+    const double chi = rk_rho(k.rk, x);
+    if (FULL)
+    {
+        const double w = omega * rk_drho(k.rk, x);
+        constexpr int R = LINE ? 3 : 1;
+        int t = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int c = a; c < 6; c++)
+            {
+                double s = J[0][a] * J[0][c];
+#pragma unroll
+                for (int i = 1; i < R; i++)
+                    s += J[i][a] * J[i][c];
+                v[t++] = w * s;
+            }
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+        {
+            double s = J[0][a] * r[0];
+#pragma unroll
+            for (int i = 1; i < R; i++)
+                s += J[i][a] * r[i];
+            v[21 + a] = -(w * s);
+        }
+    }
+    return chi;
+}
+
+// 32 accumulators -> their 64-lane sums; afterwards a[0] of lane L holds the sum of accumulator L >> 1
+// (the halving exchange of ba_kernels.hip's wave_reduce32, fixed order)
+__device__ __forceinline__ void icp_wave_reduce32(double (&a)[32])
+{
+    const int lane = threadIdx.x & 63;
+#define CUGO_HALVE(N, OFF)                                     \
+    {                                                          \
+        const bool hi = (lane & OFF) != 0;                     \
+        _Pragma("unroll") for (int i = 0; i < N; i++)          \
+        {                                                      \
+            const double send = hi ? a[i] : a[i + N];          \
+            const double keep = hi ? a[i + N] : a[i];          \
+            a[i] = keep + __shfl_xor(send, OFF, 64);           \
+        }                                                      \
+    }
+    CUGO_HALVE(16, 32)
+    CUGO_HALVE(8, 16)
+    CUGO_HALVE(4, 8)
+    CUGO_HALVE(2, 4)
+    CUGO_HALVE(1, 2)
+#undef CUGO_HALVE
+    a[0] += __shfl_xor(a[0], 1, 64);
+}
+
+// sum over the wave in a fixed butterfly order (every lane gets it)
+__device__ __forceinline__ double icp_wave_sum(double x)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+// One wave per chunk of ICP_CHUNK edges of one kind.  FULL: partials of H, b and chi2; otherwise chi2 only (slot
+// element 27, the same value FULL writes there) and, with edge_chi, the chi2 term of every edge.
+template <bool LINE, bool FULL>
+__device__ void icp_chunk(const IcpKind& k, int c, int n_poses_free, const double* __restrict__ poses,
+                          double* __restrict__ edge_chi)
+{
+    const int lane = threadIdx.x & 63;
+    const int e0 = c * ICP_CHUNK, e1 = min(k.n, e0 + ICP_CHUNK);
+    int qcur = k.pose[e0]; // (wave-uniform)
+    double acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; i++)
+        acc[i] = 0.0;
+    double chi_acc = 0.0;
+    auto flush = [&](int q) {
+        const double cs = icp_wave_sum(chi_acc);
+        double* out = k.part + (size_t)(c + q) * ICP_NP;
+        if (FULL)
+        {
+            icp_wave_reduce32(acc);
+            if (!(lane & 1) && (lane >> 1) < 27)
+                out[lane >> 1] = acc[0];
+#pragma unroll
+            for (int i = 0; i < 32; i++)
+                acc[i] = 0.0;
+        }
+        if (lane == 0)
+            out[27] = cs;
+        chi_acc = 0.0;
+    };
+    for (int base = e0; base < e1; base += 64)
+    {
+        const int e = base + lane;
+        const bool in = e < e1;
+        const int q = in ? k.pose[e] : INT_MAX;
+        double v[32];
+        double chi = 0.0;
+        if (in && q < n_poses_free && !(k.flags && (k.flags[e] & CUGO_EDGE_INACTIVE)))
+            chi = icp_edge<LINE, FULL>(k, e, poses + 7 * (size_t)q, v);
+        else if (FULL)
+        {
+#pragma unroll
+            for (int i = 0; i < 27; i++)
+                v[i] = 0.0;
+        }
+        if (!FULL && edge_chi && in)
+            edge_chi[e] = chi;
+        // the poses of the 64 lanes ascend: the lanes of each pose in turn join the wave's accumulators
+        for (;;)
+        {
+            if (q == qcur)
+            {
+                chi_acc += chi;
+                if (FULL)
+                {
+#pragma unroll
+                    for (int i = 0; i < 27; i++)
+                        acc[i] += v[i];
+                }
+            }
+            const unsigned long long later = __ballot(in && q > qcur);
+            if (later == 0)
+                break;
+            const int qn = __shfl(q, __ffsll((long long)later) - 1, 64);
+            flush(qcur);
+            qcur = qn;
+        }
+    }
+    flush(qcur);
+}
+
+struct IcpArgs
+{
+    IcpKind plane, line;
+    int n_poses_free;
+    const double* poses;
+    double* edge_chi; // error pass: [n_plane + n_line] or nullptr
+};
+
+template <bool FULL>
+__global__ __launch_bounds__(ICP_WG) void k_icp_chunks(IcpArgs a)
+{
+    const int wave = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 6);
+    const int cp = n_chunks(a.plane.n), cl = n_chunks(a.line.n);
+    if (wave < cp)
+        icp_chunk<false, FULL>(a.plane, wave, a.n_poses_free, a.poses, a.edge_chi);
+    else if (wave < cp + cl)
+        icp_chunk<true, FULL>(a.line, wave - cp, a.n_poses_free, a.poses, a.edge_chi ? a.edge_chi + a.plane.n : nullptr);
+}
+
+// sum of pose p's partials of one kind, element t, in chunk order
+__device__ __forceinline__ double icp_pose_sum(const IcpKind& k, int p, int t)
+{
+    const int i0 = k.pose_ptr[p], i1 = k.pose_ptr[p + 1];
+    double s = 0.0;
+    if (i1 > i0)
+        for (int c = i0 / ICP_CHUNK, c1 = (i1 - 1) / ICP_CHUNK; c <= c1; c++)
+            s += k.part[(size_t)(c + p) * ICP_NP + t];
+    return s;
+}
+
+// 32 threads per free pose; thread t < 27 adds element t to Hpp / bp (FULL), thread 27 writes the pose's chi2
+template <bool FULL>
+__global__ __launch_bounds__(ICP_WG) void k_icp_finish(IcpArgs a, double* __restrict__ Hpp, double* __restrict__ bp,
+                                                        double* __restrict__ pchi)
+{
+    const int p = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 5), t = threadIdx.x & 31;
+    if (p >= a.n_poses_free || t >= ICP_NP || (!FULL && t != 27))
+        return;
+    const double s = icp_pose_sum(a.plane, p, t) + icp_pose_sum(a.line, p, t);
+    if (t == 27)
+        pchi[p] = s;
+    else if (t < 21)
+    {
+        int r = 0, k = t;
+        while (k >= 6 - r)
+            k -= 6 - r, r++;
+        const int c = r + k;
+        Hpp[36 * (size_t)p + r + 6 * c] += s;
+        if (r != c)
+            Hpp[36 * (size_t)p + c + 6 * r] += s;
+    }
+    else
+        bp[6 * (size_t)p + (t - 21)] += s;
+}
+
+// chi2 total: the per-pose sums in pose order (one workgroup: strided per thread, then the threads in order)
+__global__ __launch_bounds__(ICP_WG) void k_icp_chi_total(const double* __restrict__ pchi, int n, double* __restrict__ out,
+                                                           int add)
+{
+    __shared__ double s[ICP_WG];
+    double x = 0.0;
+    for (int i = threadIdx.x; i < n; i += ICP_WG)
+        x += pchi[i];
+    s[threadIdx.x] = x;
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        double tot = 0.0;
+        for (int i = 0; i < ICP_WG; i++)
+            tot += s[i];
+        out[0] = add ? out[0] + tot : tot;
+    }
+}
+
+// index check of one kind, with pose_ptr already known to ascend from 0 to n: every edge lies in its pose's range,
+// i.e. the edges are sorted by pose and agree with pose_ptr.  Offending threads write 1 (no atomics needed).
+__global__ __launch_bounds__(ICP_WG) void k_icp_check(const int32_t* __restrict__ pose, const int32_t* __restrict__ ptr,
+                                                       int n, int P, int* __restrict__ bad)
+{
+    for (int i = blockIdx.x * ICP_WG + threadIdx.x; i < n; i += gridDim.x * ICP_WG)
+    {
+        const int q = pose[i];
+        if (q < 0 || q >= P || i < ptr[q] || i >= ptr[q + 1])
+            bad[0] = 1;
+    }
+}
+
+IcpKind kind_of(const cugo_icp_edges& ev, bool line, double* part)
+{
+    IcpKind k;
+    if (!line)
+        k = IcpKind{ev.n_plane, ev.d_plane_pose, ev.d_plane_pose_ptr, ev.d_plane_p, ev.d_plane_nd,
+                    ev.d_plane_omega, ev.n_plane_omega, ev.d_plane_flags, Robust{ev.rk_plane, ev.delta_plane}, part};
+    else
+        k = IcpKind{ev.n_line, ev.d_line_pose, ev.d_line_pose_ptr, ev.d_line_p, ev.d_line_au,
+                    ev.d_line_omega, ev.n_line_omega, ev.d_line_flags, Robust{ev.rk_line, ev.delta_line}, part};
+    return k;
+}
+
+void launch_icp(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, double* d_Hpp,
+                double* d_bp, cugo_k::ReduceScratch rs, double* d_chi, bool chi_add, double* d_edge_chi)
+{
+    const size_t need = cugo_k::icp_scratch_doubles(ev);
+    if (rs.capacity < need)
+        throw std::runtime_error("cugo: ICP scratch too small");
+    const int P = ev.n_poses_free;
+    const size_t cp = (size_t)(ev.n_plane + ICP_CHUNK - 1) / ICP_CHUNK, cl = (size_t)(ev.n_line + ICP_CHUNK - 1) / ICP_CHUNK;
+    IcpArgs a;
+    a.plane = kind_of(ev, false, rs.d_partials);
+    a.line = kind_of(ev, true, rs.d_partials + (cp + ev.n_poses_total) * ICP_NP);
+    a.n_poses_free = P;
+    a.poses = d_poses;
+    a.edge_chi = full ? nullptr : d_edge_chi;
+    double* pchi = rs.d_partials + (cp + cl + 2 * (size_t)ev.n_poses_total) * ICP_NP;
+    const size_t waves = cp + cl;
+    if (waves > 0)
+    {
+        const unsigned grid = (unsigned)((waves * 64 + ICP_WG - 1) / ICP_WG);
+        if (full)
+            CUGO_LAUNCH(k_icp_chunks<true>, dim3(grid), dim3(ICP_WG), 0, s, a);
+        else
+            CUGO_LAUNCH(k_icp_chunks<false>, dim3(grid), dim3(ICP_WG), 0, s, a);
+    }
+    if (P > 0)
+    {
+        const unsigned grid = (unsigned)((32 * (size_t)P + ICP_WG - 1) / ICP_WG);
+        if (full)
+            CUGO_LAUNCH(k_icp_finish<true>, dim3(grid), dim3(ICP_WG), 0, s, a, d_Hpp, d_bp, pchi);
+        else
+            CUGO_LAUNCH(k_icp_finish<false>, dim3(grid), dim3(ICP_WG), 0, s, a, d_Hpp, d_bp, pchi);
+    }
+    if (d_chi)
+        CUGO_LAUNCH(k_icp_chi_total, dim3(1), dim3(ICP_WG), 0, s, pchi, P, d_chi, chi_add ? 1 : 0);
+}
+
+} // namespace
+
+namespace cugo_k
+{
+
+size_t icp_scratch_doubles(const cugo_icp_edges& ev)
+{
+    const size_t cp = (size_t)(ev.n_plane + ICP_CHUNK - 1) / ICP_CHUNK, cl = (size_t)(ev.n_line + ICP_CHUNK - 1) / ICP_CHUNK;
+    return (cp + cl + 2 * (size_t)ev.n_poses_total) * ICP_NP + (size_t)ev.n_poses_free + 16;
+}
+
+int icp_check_indices(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs)
+{
+    if (rs.capacity < icp_scratch_doubles(ev))
+        throw std::runtime_error("cugo: ICP scratch too small");
+    // the flag sits in the slack behind the per-pose chi2 of the scratch layout
+    const size_t cp = (size_t)(ev.n_plane + ICP_CHUNK - 1) / ICP_CHUNK, cl = (size_t)(ev.n_line + ICP_CHUNK - 1) / ICP_CHUNK;
+    int* d_bad = reinterpret_cast<int*>(rs.d_partials + (cp + cl + 2 * (size_t)ev.n_poses_total) * ICP_NP +
+                                        (size_t)ev.n_poses_free);
+    if (hipMemsetAsync(d_bad, 0, sizeof(int), s) != hipSuccess)
+        throw std::runtime_error("cugo: hipMemsetAsync failed");
+    const struct
+    {
+        const int32_t *pose, *ptr;
+        int n;
+    } kinds[2] = {{ev.d_plane_pose, ev.d_plane_pose_ptr, ev.n_plane}, {ev.d_line_pose, ev.d_line_pose_ptr, ev.n_line}};
+    for (const auto& k : kinds)
+        if (k.n > 0)
+        {
+            const unsigned grid = (unsigned)std::min<size_t>(1024, ((size_t)k.n + ICP_WG - 1) / ICP_WG);
+            CUGO_LAUNCH(k_icp_check, dim3(grid), dim3(ICP_WG), 0, s, k.pose, k.ptr, k.n, ev.n_poses_total, d_bad);
+        }
+    int bad = 0;
+    if (hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        throw std::runtime_error("cugo: ICP index check failed to run");
+    return bad;
+}
+
+void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
+                      ReduceScratch rs, double* d_chi, bool chi_add)
+{
+    launch_icp(s, ev, d_poses, true, d_Hpp, d_bp, rs, d_chi, chi_add, nullptr);
+}
+
+void launch_icp_errors(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, ReduceScratch rs, double* d_chi,
+                       bool chi_add, double* d_edge_chi)
+{
+    launch_icp(s, ev, d_poses, false, nullptr, nullptr, rs, d_chi, chi_add, d_edge_chi);
+}
+
+} // namespace cugo_k

@@ -133,6 +133,19 @@ void launch_errors_tail(hipStream_t s, const cugo_edges& ev, const double* d_pos
 
 size_t reduce_scratch_doubles(int n_edges, int n_poses, int n_landmarks);
 
+// --- point-to-plane / point-to-line pose edges (icp_kernels.hip) -------------------------
+// scratch both launchers need (chunk partials + per-pose chi2)
+size_t icp_scratch_doubles(const cugo_icp_edges& ev);
+// with pose_ptr known to ascend from 0 to n per kind: 1 if an edge does not lie in its pose's pose_ptr range (the
+// edges are not sorted by pose, or a pose index is out of range), else 0.  Synchronises the stream.
+int icp_check_indices(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs);
+// ADDS the ICP terms to d_Hpp / d_bp; chi2 total to d_chi[0] if given (added to what is there with chi_add)
+void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
+                      ReduceScratch rs, double* d_chi, bool chi_add = false);
+// chi2 only (the same bits as launch_icp_build's); d_edge_chi: per edge, plane edges first, or nullptr
+void launch_icp_errors(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, ReduceScratch rs, double* d_chi,
+                       bool chi_add = false, double* d_edge_chi = nullptr);
+
 // chi_e per edge slot (outlier rejection, ref: computeOutliersKernel cuda_block_solver.cu:1135)
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                      cugo_robust rk, double* d_chi_e);

@@ -241,6 +241,59 @@ int cugo_backsubst_update(cugo_ctx* ctx, const cugo_edges* ev, double lambda,
                           const double* d_poses_in, const double* d_lms_in, double* d_poses_out,
                           double* d_lms_out, double* d_scale);
 
+/*
+ * Point-to-plane and point-to-line pose edges (the reference's include/icp_types.h: PlaneEdgeSet, LineEdgeSet):
+ * unary edges on a pose.  With y = R(q) p + t (the pose read as the BA edges read it) and the left update in the
+ * tangent order [omega, upsilon]:
+ *   plane (normal n, offset d):        r = n.y - d,                        J = [ y x n | n^T ]      (1 x 6)
+ *   line (point a, unit direction u):  r = (I - u u^T)(y - a) (3-vector),  J = (I - u u^T)[ -[y]x | I ]
+ * chi2 term rho(omega |r|^2) with the kind's robust kernel, weight w = omega rho'(omega |r|^2).
+ * The edges of each kind are SORTED by pose index (ascending), in structure-of-arrays form; pose_ptr is the CSR
+ * over the pose index (the edges of pose p are [pose_ptr[p], pose_ptr[p+1])).  Edges on fixed poses (index >=
+ * n_poses_free) and edges flagged CUGO_EDGE_INACTIVE contribute nothing.
+ */
+typedef struct cugo_icp_edges
+{
+    int n_poses_total, n_poses_free;
+    int n_plane;
+    const int32_t* d_plane_pose;     /* [n_plane] ascending */
+    const int32_t* d_plane_pose_ptr; /* [n_poses_total+1] */
+    const double* d_plane_p;         /* [3][n_plane] pointP */
+    const double* d_plane_nd;        /* [4][n_plane] nx ny nz d */
+    const double* d_plane_omega;     /* [n_plane] or [1] */
+    int n_plane_omega;
+    const uint8_t* d_plane_flags;    /* [n_plane] CUGO_EDGE_INACTIVE, or NULL: all active */
+    int rk_plane;                    /* CUGO_RK_* */
+    double delta_plane;
+    int n_line;
+    const int32_t* d_line_pose;
+    const int32_t* d_line_pose_ptr;
+    const double* d_line_p;          /* [3][n_line] pointP */
+    const double* d_line_au;         /* [6][n_line] ax ay az ux uy uz (|u| = 1) */
+    const double* d_line_omega;
+    int n_line_omega;
+    const uint8_t* d_line_flags;
+    int rk_line;
+    double delta_line;
+} cugo_icp_edges;
+
+/* ref: gpu::computeActiveErrors_Plane / _Line.  Writes the total chi2 of both kinds to d_chi[0]; with d_edge_chi
+ * (optional, [n_plane + n_line], plane edges first, in the sorted order) also the chi2 term of every edge (0 for
+ * edges that do not count).  Before launching, checks pose_ptr on the host (n_poses_total + 1 entries) and the pose
+ * index of every edge against it on the device, and refuses a bad layout with CUGO_ERR_INVALID; the call therefore
+ * synchronises once (one flag is read back).  The robust-kernel codes are checked; the values (finite, |u| = 1) are
+ * the caller's, as for cugo_construct_quadratic_form.  Deterministic. */
+int cugo_icp_compute_errors(cugo_ctx* ctx, const cugo_icp_edges* ev, const double* d_poses, double* d_chi,
+                            double* d_edge_chi);
+
+/* ref: gpu::constructQuadraticForm_Plane / _Line.  ADDS sum w J^T J to d_Hpp [n_poses_free][36] and -sum w J^T r
+ * to d_bp [n_poses_free][6], J = dr/dxi: the layout and the sign of cugo_construct_quadratic_form, whose Jacobian is
+ * d(meas - proj)/dxi, so that bp stays minus half the gradient of chi2 and the step of H dx = bp is applied as
+ * exp(+dx) (cugo_backsubst_update).  Writes the chi2 total to d_chi[0] if d_chi != NULL (the bits of
+ * cugo_icp_compute_errors).  Index checks as above.  No atomics. */
+int cugo_icp_construct_quadratic_form(cugo_ctx* ctx, const cugo_icp_edges* ev, const double* d_poses, double* d_Hpp,
+                                      double* d_bp, double* d_chi);
+
 /* ---- (2) graph-level entry points ---------------------------------------------------- */
 
 typedef struct cugo_graph cugo_graph; /* CudaGraphOptimisationImpl + its vertex/edge sets */
