@@ -121,10 +121,8 @@ struct Engine::Impl : cugo_k::LaunchHook
     int cur = 0;
     DevBuf<double> d_Hpp, d_b, d_Hll, d_Hpl, d_T, d_invHll, d_x, d_sys, d_tmp, d_scal;
     // fused iteration (Options::pose_schur): {L^-1, L^-1 bl} of every landmark (Hll + lambda I = L L^T) in a 128-byte
-    // slot for k_pose_schur / k_backsubst_landmarks, and whether Hpp, Hpl and invHll are those of the current
-    // linearisation: a fused build pass writes ONE block stream (G = Hpl L^-T, into d_T) and none of the three
+    // slot for k_pose_schur / k_backsubst_landmarks (begin_call)
     DevBuf<double> d_lmrec;
-    bool hpp_valid = true;
     // marginal covariances (Engine::compute_covariances; allocated by the first call only): the blocks of Sigma on
     // the Hsc pattern, the landmark blocks, their positive-definiteness flag
     DevBuf<double> d_cov_sigma, d_cov_pose, d_cov_lm;
@@ -287,24 +285,31 @@ struct Engine::Impl : cugo_k::LaunchHook
     double* bsc() { return d_sys.data() + 36 * (size_t)hs.n_blocks; }
     cugo_k::ReduceScratch rs() { return {ctx.scratch.data(), ctx.scratch.size()}; }
 
-    // all-reduce of n doubles at d over the shards.  With a communicator (cugo_graph_set_comm) this
-    // is one ncclAllReduce queued on the solver's stream: no host synchronisation, no callback.
-    // The callback form (cugo_graph_set_shard) is the test hook: it has to wait for the stream.
-    void exchange(double* d, size_t n, int op)
+    // What the three collectives below share.  With a communicator (cugo_graph_set_comm) a collective is one RCCL
+    // call queued on the solver's stream (on_comm): no host synchronisation, no callback.  The callback form
+    // (cugo_graph_set_shard) is the test hook: it has to wait for the stream, then gets n_cb doubles and an op code
+    // (0 / 1: sum / max all-reduce, -1: reduce-scatter, 2 + root: broadcast).
+    template <typename Q>
+    void collective(double& bytes, int& calls, size_t n_counted, Q&& on_comm, double* d, size_t n_cb, int op_cb)
     {
-        if (world <= 1 && !comm) // a 1-rank communicator still issues its (identity) collectives
-            return;
-        xchg_bytes += 8.0 * (double)n;
-        xchg_calls++;
+        bytes += 8.0 * (double)n_counted;
+        calls++;
         if (comm)
         {
-            timed("exchange", [&] { comm->all_reduce(d, n, op, ctx.stream); });
+            timed("exchange", on_comm);
             return;
         }
         if (!xfn)
             throw std::runtime_error("cugo: sharded run without a communicator or an exchange function");
         CUGO_HIP(hipStreamSynchronize(ctx.stream));
-        xfn(d, n, op, xuser);
+        xfn(d, n_cb, op_cb, xuser);
+    }
+    // all-reduce of n doubles at d over the shards
+    void exchange(double* d, size_t n, int op)
+    {
+        if (world <= 1 && !comm) // a 1-rank communicator still issues its (identity) collectives
+            return;
+        collective(xchg_bytes, xchg_calls, n, [&] { comm->all_reduce(d, n, op, ctx.stream); }, d, n, op);
     }
     // the sparse LL^T of a sharded run: each rank factors the elimination subtrees it owns and the replicated
     // top of the tree (chol_symbolic: CholPlan::owner) and gets what crosses the boundary by broadcast
@@ -348,18 +353,9 @@ struct Engine::Impl : cugo_k::LaunchHook
         xs_ready = true;
     }
     void reduce_scatter(double* d, size_t n_seg)
-    {
-        xchg_bytes += 8.0 * (double)n_seg; // (bytes this rank receives)
-        xchg_calls++;
-        if (comm)
-        {
-            timed("exchange", [&] { comm->reduce_scatter(d, n_seg, ctx.stream); });
-            return;
-        }
-        if (!xfn)
-            throw std::runtime_error("cugo: sharded run without a communicator or an exchange function");
-        CUGO_HIP(hipStreamSynchronize(ctx.stream));
-        xfn(d, n_seg * (size_t)world, -1, xuser);
+    { // (counted: the bytes this rank receives)
+        collective(xchg_bytes, xchg_calls, n_seg, [&] { comm->reduce_scatter(d, n_seg, ctx.stream); }, d,
+                   n_seg * (size_t)world, -1);
     }
     void exchange_system()
     {
@@ -386,17 +382,230 @@ struct Engine::Impl : cugo_k::LaunchHook
     {
         if (world <= 1 && !comm)
             return;
-        bcast_bytes += 8.0 * (double)n;
-        bcast_calls++;
-        if (comm)
+        collective(bcast_bytes, bcast_calls, n, [&] { comm->broadcast(d, n, root, ctx.stream); }, d, n, 2 + root);
+    }
+    // ---- the LM loop's building blocks (Engine::optimize, Engine::compute_covariances) -------------------------------
+    // What a call works with, set once at its top (begin_call): everything these are made of (rows_on, splan_on,
+    // strip_on, lm_in_one_group, hs, max_row_nnz, the options, the communicator) is fixed once build_structure() has
+    // run, so none of them changes inside a call.
+    struct CallFacts
+    {
+        bool sharded = false;
+        bool use_rows = false;  // the Schur complement by block rows (k_hsc_rows): T is never written or read
+        // T = Hpl invHll is only materialised for the gather kernels (the landmark-major plan keeps it in LDS).  A
+        // build pass that knows the damping of the trial behind it leaves invHll and T for it: that trial's Schur
+        // complement then does not read the Hpl stream a second time (CUGO_FUSE_T=0: always the separate edge kernel)
+        bool can_fuse = false;
+        bool ps_on = false;     // ... in the one-stream form: G and the landmarks' lines, k_pose_schur (CUGO_POSE_SCHUR=0: never)
+        // Speculative build (single process, CUGO_SPECULATE=0 turns it off): behind the error pass of a first trial
+        // the host queues the NEXT iteration's build pass at the trial's estimates before it waits for the trial's
+        // result — the 15-20 us the host needs to read F-hat, decide and queue again then overlap with the build
+        // instead of leaving the device idle.  The damping that build prepares T for is lambda / 3: what an accepted
+        // trial with rho near 1 gives (ref: cuda_graph_optimisation.cpp:97-99, the lower clamp).  Accepted with
+        // another lambda: the Schur complement recomputes T (as without the fusion).  Rejected: H is rebuilt from
+        // the kept estimates before the retry.  Same arithmetic on the same data in every case.
+        bool speculate = false;
+        bool trial_poll = false;  // (CUGO_TRIAL_POLL=0: wait by event / stream synchronisation)
+        bool trial_event = false; // (CUGO_TRIAL_EVENT=0: wait for the whole stream, A/B)
+        // the trial's chi2 out of the NEXT iteration's build pass: that pass is queued behind a first trial anyway
+        // (speculation) and computes the residuals of every edge at the trial's estimates — the error pass would
+        // compute them a launch earlier and throw them away (CUGO_TRIAL_FROM_BUILD=0; needs the polled wait)
+        bool from_build = false;
+        size_t blkw = 0; // doubles in a block stream (Hpl, T): 18 per edge slot, 9 when the blocks are stored as float
+    } f;
+    // ... and the buffers only some forms need, allocated by the first call that takes such a form: T for the
+    // gather kernels, the landmarks' lines for the one-stream form of the loop
+    void begin_call(bool lm_loop)
+    {
+        f.sharded = world > 1 || comm;
+        f.use_rows = rows_on && cugo_k::schur_rows_usable(hs, max_row_nnz);
+        f.can_fuse = opt.fuse_t && !splan_on && lm_in_one_group;
+        f.ps_on = opt.pose_schur && f.can_fuse && !f.use_rows && !strip_on;
+        f.speculate = !f.sharded && !profile && opt.speculate;
+        f.trial_poll = !profile && opt.trial_poll;
+        f.trial_event = opt.trial_event;
+        f.from_build = opt.trial_from_build && f.speculate && f.trial_poll;
+        f.blkw = (ev.block_f32 ? 9 : 18) * (size_t)E;
+        if (!splan_on && !f.use_rows && d_T.size() == 0)
+            d_T.resize(f.blkw + 16);
+        if (lm_loop && f.ps_on && d_lmrec.size() < 16 * (size_t)std::max(L, 1))
+            d_lmrec.resize(16 * (size_t)std::max(L, 1));
+    }
+    // What the loop knows about the buffers H lives in; queue_build() keeps the first two, optimize() the rest.
+    struct LmState
+    {
+        // Hpp, Hpl and invHll are those of the build pass at hand: a fused build pass in the one-stream form writes
+        // ONE block stream (G = Hpl L^-T, into d_T) and none of the three, so only the trial it was fused for can
+        // run behind it
+        bool hpp_valid = true;
+        // the damping the build pass at hand left invHll and T (or G and the landmarks' lines) for; < 0: none
+        double fused_lambda = -1.0;
+        // the Schur complement of the build pass at hand is queued as well, for this damping (< 0: not): the trial
+        // that ended the previous iteration took its chi2 from that build pass, and the Schur complement for the
+        // predicted damping went out behind the reductions for the host to decide meanwhile
+        double schur_lambda = -1.0;
+        // H is NOT that of the estimates in force: the next iteration's build pass went out behind this iteration's
+        // first trial, at the trial's estimates.  Accepted: it is the next iteration's build pass.  Rejected: H is
+        // rebuilt before the retry.
+        bool spec_queued = false;
+        // the previous damping update hit the lower clamp (rho near 1: lambda / 3, the value the speculation
+        // predicts).  Only behind such a step does a trial take its chi2 from the next build pass: right after a step
+        // with a smaller gain ratio the prediction usually misses, and a missed Schur complement costs more than the
+        // error pass saves (10k graph: 0.8 ms against 0.05)
+        bool prev_clamped = false;
+    } st;
+    int32_t* d_fail_flag() { return reinterpret_cast<int32_t*>(d_scal.data() + 4); }
+    // The build pass at the estimates in buffer `buf`.  fuse_lambda < 0: the two-stream pass (Hpp, b, Hll, Hpl).
+    // fuse_lambda >= 0 (callers: only with f.can_fuse): it also leaves invHll and T for that damping or, with
+    // f.ps_on, G and the landmarks' lines in place of Hpl / invHll / Hpp.  (d_lmrec and skip_poses only go along
+    // with a damping: without d_invHll the launcher passes neither on, ba_kernels.hip: launch_build_t.)
+    void queue_build(int buf, double fuse_lambda, double* d_chi = nullptr, bool chi_behind_scale = false)
+    {
+        const bool fuse = fuse_lambda >= 0, one_stream = fuse && f.ps_on;
+        timed("build", [&] {
+            cugo_k::launch_build(ctx.stream, ev, d_poses[buf].data(), d_lms[buf].data(), rk, d_Hpp.data(), bp(),
+                                 d_Hll.data(), bl(), d_Hpl.data(), rs(), d_chi, fuse ? fuse_lambda : -1.0,
+                                 fuse ? d_invHll.data() : nullptr, fuse && !f.use_rows ? d_T.data() : nullptr,
+                                 one_stream ? d_lmrec.data() : nullptr, one_stream, chi_behind_scale);
+        });
+        st.hpp_valid = !one_stream;
+        st.fused_lambda = fuse ? fuse_lambda : -1.0;
+    }
+    // [Hsc | bsc] for this damping from the build pass at hand, linearised at buffer `buf`.  have_T: that pass left
+    // invHll and T for it; one_stream: ... in the one-stream form (k_pose_schur forms the diagonal blocks, bp and bsc)
+    void queue_schur(double lambda, bool have_T, bool one_stream, int buf)
+    {
+        timed("schur", [&] {
+            cugo_k::launch_schur(ctx.stream, ev, hs, lambda, 0, d_Hpp.data(), bp(), d_Hll.data(), bl(), d_Hpl.data(),
+                                 d_invHll.data(), splan_on || f.use_rows ? nullptr : d_T.data(), bsc(), Hsc(), have_T,
+                                 f.use_rows ? cugo_k::SchurRows{d_pose_rec.data(), max_row_nnz, nullptr, opt.hsc_mfma, opt.hsc_xcd}
+                                            : cugo_k::SchurRows{nullptr, 0, strip_on ? d_off_pi.data() : nullptr,
+                                                                opt.hsc_mfma, opt.hsc_xcd,
+                                                                one_stream ? d_lmrec.data() : nullptr,
+                                                                d_poses[buf].data(), rs(), bp()});
+        });
+    }
+    // diagnosis: CUGO_DEBUG_HASH=<file> — position-weighted integer checksums of the arrays every stage of the
+    // first trial of an iteration leaves behind, computed by kernels queued in the same stream (no host
+    // synchronisation: the flow of the loop stays what it is), appended to the file when optimize() returns
+    // (hooks build only, make HOOKS=1: the product build has neither the switch nor the checksum kernel)
+#ifdef CUGO_DEBUG_HOOKS
+    const char* hash_file = nullptr;
+    void hash_begin(int niterations)
+    {
+        hash_file = std::getenv("CUGO_DEBUG_HASH");
+        if (!hash_file)
+            return;
+        d_hash.resize(64 * (size_t)std::max(niterations, 1));
+        d_hash.zero(ctx.stream);
+    }
+    unsigned long long* hash_row(int iteration) { return hash_file && iteration >= 0 ? d_hash.data() + 64 * (size_t)iteration : nullptr; }
+    void hash(int iteration, int slot, const void* p, size_t words)
+    {
+        if (hash_row(iteration))
+            cugo_k::launch_hash_words(ctx.stream, p, words, hash_row(iteration) + slot);
+    }
+    void hash_end(size_t n_records)
+    {
+        if (!hash_file)
+            return;
+        std::vector<unsigned long long> h(d_hash.size());
+        CUGO_HIP(hipMemcpyAsync(h.data(), d_hash.data(), h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, ctx.stream));
+        CUGO_HIP(hipStreamSynchronize(ctx.stream));
+        if (FILE* fp = std::fopen(hash_file, "a"))
         {
-            timed("exchange", [&] { comm->broadcast(d, n, root, ctx.stream); });
+            std::fprintf(fp, "run\n");
+            for (size_t it = 0; it < n_records; it++)
+            {
+                for (int k = 0; k < 64; k++)
+                    std::fprintf(fp, "%016llx ", h[64 * it + k]);
+                std::fprintf(fp, "\n");
+            }
+            std::fclose(fp);
+        }
+    }
+#else
+    void hash_begin(int) {}
+    void hash(int, int, const void*, size_t) {}
+    void hash_end(size_t) {}
+#endif
+    // factorisation of Hsc + lambda I and the solve for xp; hash_iteration >= 0: with the stage checksums of that
+    // iteration (hooks build)
+    void queue_factor_solve(double lambda, int hash_iteration = -1)
+    {
+#ifdef CUGO_DEBUG_HOOKS
+        chol.dbg_hash = hash_row(hash_iteration);
+#endif
+        timed("cholesky", [&] { chol.factor_solve(Hsc(), lambda, bsc(), xp(), d_fail_flag()); });
+#ifdef CUGO_DEBUG_HOOKS
+        chol.dbg_hash = nullptr;
+#endif
+    }
+    // Returns when h_scal[2..4] hold the words of the trial queued last (F-hat, scale, factorisation flag).
+    // behind_spec: a speculative build is queued behind the trial — the host waits for the trial's own last launch
+    // only: it then decides and queues the next Schur complement while the build pass still runs.
+    // retries: StructureStats::trial_sync_retries.
+    void wait_for_trial(bool behind_spec, double& retries)
+    {
+        const volatile double* seq = h_scal.data() + 5;
+        if (!f.sharded && f.trial_poll)
+        {
+            // the trial's last launch ends by writing the trial's sequence number behind its three words in
+            // the pinned block (k_sum_partials2, system-scope release): the host polls that word — no event,
+            // no stream synchronisation, and whatever is queued behind the trial keeps running
+            const auto w0 = Clock::now();
+            auto next_query = w0 + std::chrono::milliseconds(10);
+            const auto spin_limit = std::max<Clock::duration>(std::chrono::milliseconds(2), 2 * last_trial_wait);
+            for (unsigned long spin = 1; *seq != (double)trial_seq; spin++)
+            {
+                cpu_relax();
+                if ((spin & 0x3FF) != 0)
+                    continue;
+                // a trial takes 1 ms (kitti_00 shape) to 3.5 ms (10k graph): the host spins through that — on a
+                // loaded host a yield hands the core away for a scheduler quantum, longer than the trial —; a
+                // wait that lasts longer than twice the previous one (at least 2 ms) offers the core to others
+                // between polls, and every ~10 ms the stream is asked whether it is still working
+                const auto now = Clock::now();
+                if (now - w0 > spin_limit)
+                    std::this_thread::yield();
+                if (now < next_query)
+                    continue;
+                next_query = now + std::chrono::milliseconds(10);
+                const hipError_t qe = hipStreamQuery(ctx.stream);
+                if (qe == hipErrorNotReady)
+                    continue;
+                CUGO_HIP(qe); // a failed stream will never deliver
+                // the stream is idle: everything queued has run, so the word is there (give the write a moment to
+                // become visible to this core before calling it lost)
+                bool there = false;
+                for (int k = 0; k < 100000 && !there; k++)
+                {
+                    std::atomic_thread_fence(std::memory_order_acquire);
+                    there = *seq == (double)trial_seq;
+                    cpu_relax();
+                }
+                if (!there)
+                    throw std::runtime_error("cugo: the result of an LM trial never arrived");
+            }
+            last_trial_wait = Clock::now() - w0;
+            std::atomic_thread_fence(std::memory_order_acquire);
             return;
         }
-        if (!xfn)
-            throw std::runtime_error("cugo: sharded run without a communicator or an exchange function");
-        CUGO_HIP(hipStreamSynchronize(ctx.stream));
-        xfn(d, n, 2 + root, xuser);
+        if (behind_spec && f.trial_event)
+            CUGO_HIP(hipEventSynchronize(trial_ev));
+        else
+            CUGO_HIP(hipStreamSynchronize(ctx.stream));
+        if (f.sharded) // (the three words came with a copy queued on the stream)
+            return;
+        // the three words in the pinned block are this trial's
+        for (long spin = 0; *seq != (double)trial_seq; spin++)
+        {
+            if (spin == 0)
+                retries += 1;
+            if (spin > 2000000000L)
+                throw std::runtime_error("cugo: the result of an LM trial never arrived");
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
     }
 };
 
@@ -1623,8 +1832,9 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
 
     if (m.structure_dirty)
         build_structure();
-    const bool sharded = m.world > 1 || m.comm;
-    int32_t* d_fail = reinterpret_cast<int32_t*>(m.d_scal.data() + 4);
+    m.begin_call(true);
+    const Impl::CallFacts& f = m.f;
+    Impl::LmState& st = m.st = Impl::LmState{};
     auto sync_prof = [&](int item, Clock::time_point t0) {
         if (m.profile)
         {
@@ -1632,102 +1842,39 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
             prof_[item] += ms_since(t0);
         }
     };
-
-    // Speculative build (single process, CUGO_SPECULATE=0 turns it off): behind the error pass of a first
-    // trial the host queues the NEXT iteration's build pass at the trial's estimates before it waits for the
-    // trial's result — the 15-20 us the host needs to read F-hat, decide and queue again then overlap with
-    // the build instead of leaving the device idle.  The damping that build prepares T for is lambda / 3:
-    // what an accepted trial with rho near 1 gives (ref: cuda_graph_optimisation.cpp:97-99, the lower clamp).
-    // Accepted with another lambda: the Schur complement recomputes T (as without the fusion).  Rejected:
-    // H is rebuilt from the kept estimates before the retry.  Same arithmetic on the same data in every case.
-    const bool speculate = !sharded && !m.profile && m.opt.speculate;
-    // diagnosis: CUGO_DEBUG_HASH=<file> — position-weighted integer checksums of the arrays every stage of the
-    // first trial of an iteration leaves behind, computed by kernels queued in the same stream (no host
-    // synchronisation: the flow of the loop stays what it is), appended to the file when optimize() returns
-    // (hooks build only, make HOOKS=1: the product build has neither the switch nor the checksum kernel)
-#ifdef CUGO_DEBUG_HOOKS
-    const char* hash_file = std::getenv("CUGO_DEBUG_HASH");
-    if (hash_file)
-    {
-        m.d_hash.resize(64 * (size_t)std::max(niterations, 1));
-        m.d_hash.zero(s);
-    }
-    auto hash = [&](int iteration, int slot, const void* p, size_t words) {
-        if (hash_file)
-            cugo_k::launch_hash_words(s, p, words, m.d_hash.data() + 64 * (size_t)iteration + slot);
-    };
-#else
-    auto hash = [](int, int, const void*, size_t) {};
-#endif
-    const bool trial_event = m.opt.trial_event;                // (CUGO_TRIAL_EVENT=0: wait for the whole stream, A/B)
-    const bool trial_poll = !m.profile && m.opt.trial_poll;    // (CUGO_TRIAL_POLL=0: wait by event / stream synchronisation)
-    bool have_build = false;      // the build pass of this iteration is already queued
-    double built_lambda = -1.0;   // ... with invHll / T for this damping (< 0: none)
-    // ... and so is its Schur complement for this damping (< 0: not): the trial that ended the previous iteration took
-    // its chi2 from that build pass instead of an error pass of its own (Options::trial_from_build), and the Schur
-    // complement for the predicted damping was queued behind the reductions for the host to decide meanwhile
-    double schur_ready_lambda = -1.0;
-    // Only behind a trial whose predecessor's damping update hit the lower clamp (rho near 1: lambda / 3, the value the
-    // speculation predicts): right after a step with a smaller gain ratio the prediction usually misses, and a missed
-    // Schur complement costs more than the error pass saves (10k graph: 0.8 ms against 0.05).
-    bool prev_clamped = false;
+    m.hash_begin(niterations);
 
     for (int iteration = 0; iteration < niterations; iteration++)
     {
         const auto it0 = Clock::now();
         // computeErrors + buildSystem fused: chi2 at the current estimates comes out of the
-        // build pass (ref: cuda_graph_optimisation.cpp:64-67)
+        // build pass (ref: cuda_graph_optimisation.cpp:64-67).  From the second iteration on the damping of the first
+        // trial is known when the build is queued — unless the pass went out behind the previous iteration's trial
         auto tb = Clock::now();
-        // T = Hpl invHll is only materialised for the gather kernels (the landmark-major plan keeps it
-        // in LDS).  From the second iteration on the damping of the first trial is known when the build
-        // is queued, and the build pass leaves invHll and T for it: that trial's Schur complement then
-        // does not read the Hpl stream a second time (CUGO_FUSE_T=0: always the separate edge kernel).
-        const bool use_rows = m.rows_on && cugo_k::schur_rows_usable(m.hs, m.max_row_nnz);
-        if (!m.splan_on && !use_rows && m.d_T.size() == 0)
-            m.d_T.resize((m.ev.block_f32 ? 9 : 18) * (size_t)m.E + 16);
-        const bool fuse_allowed = m.opt.fuse_t;
-        const bool can_fuse = fuse_allowed && !m.splan_on && m.lm_in_one_group;
-        const bool fused_T = have_build ? (can_fuse && built_lambda == lambda) : (can_fuse && iteration > 0);
-        const bool ps_on = m.opt.pose_schur && can_fuse && !use_rows && !m.strip_on;
-        if (ps_on && m.d_lmrec.size() < 16 * (size_t)std::max(m.L, 1))
-            m.d_lmrec.resize(16 * (size_t)std::max(m.L, 1));
-        if (!have_build)
-        m.timed("build", [&] {
-            // chi2 of the build pass is only consumed in the first iteration (see below)
-            cugo_k::launch_build(s, m.ev, m.d_poses[m.cur].data(), m.d_lms[m.cur].data(), m.rk,
-                                 m.d_Hpp.data(), m.bp(), m.d_Hll.data(), m.bl(), m.d_Hpl.data(),
-                                 m.rs(), iteration == 0 ? m.d_scal.data() : nullptr, fused_T ? lambda : -1.0,
-                                 fused_T ? m.d_invHll.data() : nullptr,
-                                 fused_T && !use_rows ? m.d_T.data() : nullptr, ps_on ? m.d_lmrec.data() : nullptr, ps_on);
-            m.hpp_valid = !(ps_on && fused_T);
-        });
-        have_build = false, built_lambda = -1.0;
+        if (!st.spec_queued) // (chi2 of the build pass is only consumed in the first iteration, see below)
+            m.queue_build(m.cur, f.can_fuse && iteration > 0 ? lambda : -1.0, iteration == 0 ? m.d_scal.data() : nullptr);
+        st.spec_queued = false;
         sync_prof(PROF_BUILD_SYSTEM, tb);
+        // chi2 at the current estimates is only read back in the first iteration: afterwards it is
+        // the F-hat of the accepted trial (same edges, same estimates), so the host does not have
+        // to wait for the build pass before queueing the Schur complement
         if (iteration == 0)
         {
             const double* hpp = m.d_Hpp.data();
-            if (sharded)
+            if (f.sharded)
             { // diag(Hpp) must be the global sum before taking the maximum
                 CUGO_HIP(hipMemcpyAsync(m.d_tmp.data(), m.d_Hpp.data(), 36 * (size_t)m.P * sizeof(double),
                                         hipMemcpyDeviceToDevice, s));
                 m.exchange(m.d_tmp.data(), 36 * (size_t)m.P, 0);
                 hpp = m.d_tmp.data();
             }
-            cugo_k::launch_max_diagonal(s, hpp, m.P, m.d_Hll.data(), m.L, m.rs(),
-                                        m.d_scal.data() + 1);
-        }
-        // chi2 at the current estimates is only read back in the first iteration: afterwards it is
-        // the F-hat of the accepted trial (same edges, same estimates), so the host does not have
-        // to wait for the build pass before queueing the Schur complement
-        if (iteration == 0)
-        {
-            if (sharded)
+            cugo_k::launch_max_diagonal(s, hpp, m.P, m.d_Hll.data(), m.L, m.rs(), m.d_scal.data() + 1);
+            if (f.sharded)
             {
                 m.exchange(m.d_scal.data(), 1, 0);
                 m.exchange(m.d_scal.data() + 1, 1, 1);
             }
-            CUGO_HIP(hipMemcpyAsync(m.h_scal.data(), m.d_scal.data(), 2 * sizeof(double),
-                                    hipMemcpyDeviceToHost, s));
+            CUGO_HIP(hipMemcpyAsync(m.h_scal.data(), m.d_scal.data(), 2 * sizeof(double), hipMemcpyDeviceToHost, s));
             CUGO_HIP(hipStreamSynchronize(s));
             F = m.h_scal[0];
             lambda = tau * m.h_scal[1];
@@ -1735,244 +1882,121 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
 
         int q = 0;
         double rho = -1.0;
-        bool spec_queued = false; // the next iteration's build went out behind this iteration's first trial
         for (; q < maxq && rho < 0; q++)
         {
-            if (spec_queued)
-            { // that trial was rejected: the speculative pass overwrote H, rebuild it from the kept estimates
-                m.timed("build", [&] {
-                    cugo_k::launch_build(s, m.ev, m.d_poses[m.cur].data(), m.d_lms[m.cur].data(), m.rk,
-                                         m.d_Hpp.data(), m.bp(), m.d_Hll.data(), m.bl(), m.d_Hpl.data(), m.rs(),
-                                         nullptr, -1.0, nullptr, nullptr);
-                    m.hpp_valid = true;
-                });
-                spec_queued = false;
+            const int hash_it = q == 0 ? iteration : -1; // (checksums: of an iteration's first trial)
+            // ---- H: invHll and T of this lambda came with the build pass (a first trial whose damping the pass knew)
+            const bool trial_fused = q == 0 && st.fused_lambda == lambda;
+            const bool one_stream = trial_fused && f.ps_on; // (the build pass wrote G into d_T and the landmarks' lines)
+            if (st.spec_queued || (!one_stream && !st.hpp_valid))
+            { // the previous trial was rejected and the speculative pass behind it overwrote H; or the build pass at
+              // hand was a one-stream one and this trial is not the one it was for — the predicted damping missed,
+              // or the fused trial was rejected with no speculative build behind it: the two-stream build pass at
+              // the estimates in force
+                m.queue_build(m.cur, -1.0);
+                st.spec_queued = false;
             }
-            const bool trial_fused = fused_T && q == 0; // invHll and T of this lambda came with the build pass
-            if (!(trial_fused && ps_on) && !m.hpp_valid)
-            { // the build pass at hand was a fused one (one block stream, no Hpp / Hpl / invHll) and this trial is
-              // not the one it was for — the predicted damping missed, or the fused trial was rejected with no
-              // speculative build behind it: the two-stream build pass at the estimates in force
-                m.timed("build", [&] {
-                    cugo_k::launch_build(s, m.ev, m.d_poses[m.cur].data(), m.d_lms[m.cur].data(), m.rk,
-                                         m.d_Hpp.data(), m.bp(), m.d_Hll.data(), m.bl(), m.d_Hpl.data(), m.rs(),
-                                         nullptr, -1.0, nullptr, nullptr);
-                    m.hpp_valid = true;
-                });
-            }
-            const size_t blkw = (m.ev.block_f32 ? 9 : 18) * (size_t)m.E;
-            if (q == 0)
-            { // what the build pass left
-                hash(iteration, 0, m.d_Hpp.data(), 36 * (size_t)m.P);
-                hash(iteration, 1, m.d_b.data(), 6 * (size_t)m.P + 3 * (size_t)m.L);
-                hash(iteration, 2, m.d_Hll.data(), 9 * (size_t)m.L);
-                hash(iteration, 3, m.d_Hpl.data(), blkw);
-            }
+            // what the build pass left
+            m.hash(hash_it, 0, m.d_Hpp.data(), 36 * (size_t)m.P);
+            m.hash(hash_it, 1, m.d_b.data(), 6 * (size_t)m.P + 3 * (size_t)m.L);
+            m.hash(hash_it, 2, m.d_Hll.data(), 9 * (size_t)m.L);
+            m.hash(hash_it, 3, m.d_Hpl.data(), f.blkw);
+            // ---- Schur complement (unless it was queued behind the previous trial, for this very damping)
             auto ts = Clock::now();
-            const bool schur_queued = q == 0 && trial_fused && schur_ready_lambda == lambda;
-            schur_ready_lambda = -1.0;
-            if (!schur_queued)
-            m.timed("schur", [&] {
-                cugo_k::launch_schur(s, m.ev, m.hs, lambda, 0, m.d_Hpp.data(), m.bp(),
-                                     m.d_Hll.data(), m.bl(), m.d_Hpl.data(), m.d_invHll.data(),
-                                     m.splan_on || use_rows ? nullptr : m.d_T.data(), m.bsc(), m.Hsc(), trial_fused,
-                                     use_rows ? cugo_k::SchurRows{m.d_pose_rec.data(), m.max_row_nnz, nullptr, m.opt.hsc_mfma, m.opt.hsc_xcd}
-                                              : cugo_k::SchurRows{nullptr, 0, m.strip_on ? m.d_off_pi.data() : nullptr,
-                                                                  m.opt.hsc_mfma, m.opt.hsc_xcd,
-                                                                  trial_fused && ps_on ? m.d_lmrec.data() : nullptr,
-                                                                  m.d_poses[m.cur].data(), m.rs(), m.bp()});
-            });
-            if (sharded)
+            if (!(trial_fused && st.schur_lambda == lambda))
+                m.queue_schur(lambda, trial_fused, one_stream, m.cur);
+            st.schur_lambda = -1.0;
+            if (f.sharded)
                 m.exchange_system();
             sync_prof(PROF_SCHUR, ts);
-            if (q == 0)
-            {
-                hash(iteration, 4, m.d_sys.data(), 36 * (size_t)m.hs.n_blocks + 6 * (size_t)m.P);
-                if (m.d_T.size())
-                    hash(iteration, 5, m.d_T.data(), blkw);
-                hash(iteration, 6, m.d_invHll.data(), 9 * (size_t)m.L);
-            }
+            m.hash(hash_it, 4, m.d_sys.data(), 36 * (size_t)m.hs.n_blocks + 6 * (size_t)m.P);
+            if (m.d_T.size())
+                m.hash(hash_it, 5, m.d_T.data(), f.blkw);
+            m.hash(hash_it, 6, m.d_invHll.data(), 9 * (size_t)m.L);
+            // ---- factorisation and solve
             auto tn = Clock::now();
-#ifdef CUGO_DEBUG_HOOKS
-            m.chol.dbg_hash = hash_file && q == 0 ? m.d_hash.data() + 64 * (size_t)iteration : nullptr;
-#endif
-            m.timed("cholesky", [&] {
-                m.chol.factor_solve(m.Hsc(), lambda, m.bsc(), m.xp(), d_fail);
-            });
-#ifdef CUGO_DEBUG_HOOKS
-            m.chol.dbg_hash = nullptr;
-#endif
+            m.queue_factor_solve(lambda, hash_it);
             sync_prof(PROF_NUMERIC, tn);
-            if (q == 0)
-                hash(iteration, 7, m.xp(), 6 * (size_t)m.P);
-            auto tu = Clock::now();
-            const int nxt = m.cur ^ 1;
+            m.hash(hash_it, 7, m.xp(), 6 * (size_t)m.P);
+            // ---- back-substitution and update into the other estimate buffer.
             // single process: the two reductions that end a trial (scale of the update pass, chi2 of
             // the error pass) share one launch, which also drops F-hat, scale and the factorisation flag
             // (slot 4) into the pinned block — no copy is queued behind it.  A shard has to all-reduce
             // the two sums first and keeps the separate launches and the read-back.
+            auto tu = Clock::now();
+            const int nxt = m.cur ^ 1;
             int n_scale_part = 0;
             m.timed("backsubst_update", [&] {
-                const bool gform = trial_fused && ps_on; // (the build pass wrote G into d_T and the landmarks' lines)
                 n_scale_part = cugo_k::launch_backsubst_update(
                     s, m.ev, lambda, (m.rank == 0 ? lambda : 0.0), m.d_invHll.data(), m.bl(), m.bp(),
-                    gform ? m.d_T.data() : m.d_Hpl.data(), m.xp(), m.xl(), m.d_poses[m.cur].data(), m.d_lms[m.cur].data(),
-                    m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rs(), sharded ? m.d_scal.data() + 3 : nullptr,
-                    gform ? m.d_lmrec.data() : nullptr);
+                    one_stream ? m.d_T.data() : m.d_Hpl.data(), m.xp(), m.xl(), m.d_poses[m.cur].data(), m.d_lms[m.cur].data(),
+                    m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rs(), f.sharded ? m.d_scal.data() + 3 : nullptr,
+                    one_stream ? m.d_lmrec.data() : nullptr);
             });
             sync_prof(PROF_UPDATE, tu);
-            if (q == 0)
-            {
-                hash(iteration, 8, m.xl(), 3 * (size_t)m.L);
-                hash(iteration, 9, m.d_poses[nxt].data(), 7 * (size_t)m.Pall);
-                hash(iteration, 10, m.d_lms[nxt].data(), 3 * (size_t)m.Lall);
-            }
+            m.hash(hash_it, 8, m.xl(), 3 * (size_t)m.L);
+            m.hash(hash_it, 9, m.d_poses[nxt].data(), 7 * (size_t)m.Pall);
+            m.hash(hash_it, 10, m.d_lms[nxt].data(), 3 * (size_t)m.Lall);
+            // ---- end of the trial: its chi2 from the next iteration's build pass or from an error pass, and the
+            // speculative work behind it, all for the damping an accepted step with rho near 1 gives
             auto te = Clock::now();
             const double lambda_pred = lambda * (1.0 / 3.0);
-            // the trial's chi2 out of the NEXT iteration's build pass: that pass is queued behind a first trial anyway
-            // (speculation) and computes the residuals of every edge at the trial's estimates — the error pass would
-            // compute them a launch earlier and throw them away
-            const bool from_build = m.opt.trial_from_build && speculate && !sharded && trial_poll && q == 0 &&
-                                    iteration + 1 < niterations && prev_clamped;
+            const double fuse_pred = f.can_fuse ? lambda_pred : -1.0;
+            const bool last = iteration + 1 == niterations;
+            const bool from_build = f.from_build && q == 0 && !last && st.prev_clamped;
             if (from_build)
             {
-                m.timed("build", [&] {
-                    cugo_k::launch_build(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk, m.d_Hpp.data(),
-                                         m.bp(), m.d_Hll.data(), m.bl(), m.d_Hpl.data(), m.rs(), nullptr,
-                                         can_fuse ? lambda_pred : -1.0, can_fuse ? m.d_invHll.data() : nullptr,
-                                         can_fuse && !use_rows ? m.d_T.data() : nullptr, ps_on ? m.d_lmrec.data() : nullptr, ps_on,
-                                         true);
-                    m.hpp_valid = !(ps_on && can_fuse);
-                });
+                m.queue_build(nxt, fuse_pred, nullptr, true);
                 m.timed("errors", [&] {
                     cugo_k::launch_trial_tail_from_build(s, m.ev, m.rs(), n_scale_part, m.d_scal.data() + 2,
                                                          m.d_scal.data() + 4, m.h_scal.data() + 2, (double)++m.trial_seq,
                                                          reinterpret_cast<unsigned*>(m.d_fail.data() + 2));
                 });
-                if (can_fuse && !m.splan_on)
+                if (f.can_fuse)
                 { // the Schur complement of the next iteration's first trial, should the damping be the predicted one:
                   // the host decides while it runs
-                    m.timed("schur", [&] {
-                        cugo_k::launch_schur(s, m.ev, m.hs, lambda_pred, 0, m.d_Hpp.data(), m.bp(), m.d_Hll.data(), m.bl(),
-                                             m.d_Hpl.data(), m.d_invHll.data(), use_rows ? nullptr : m.d_T.data(), m.bsc(),
-                                             m.Hsc(), true,
-                                             use_rows ? cugo_k::SchurRows{m.d_pose_rec.data(), m.max_row_nnz, nullptr, m.opt.hsc_mfma, m.opt.hsc_xcd}
-                                                      : cugo_k::SchurRows{nullptr, 0, m.strip_on ? m.d_off_pi.data() : nullptr,
-                                                                          m.opt.hsc_mfma, m.opt.hsc_xcd,
-                                                                          ps_on ? m.d_lmrec.data() : nullptr,
-                                                                          m.d_poses[nxt].data(), m.rs(), m.bp()});
-                    });
-                    schur_ready_lambda = lambda_pred;
+                    m.queue_schur(lambda_pred, true, f.ps_on, nxt);
+                    st.schur_lambda = lambda_pred;
                 }
-                spec_queued = true;
+                st.spec_queued = true;
             }
             else
             m.timed("errors", [&] {
-                if (sharded)
+                if (f.sharded)
                     cugo_k::launch_errors(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk,
                                           m.rs(), m.d_scal.data() + 2);
                 else
-                {
                     cugo_k::launch_errors_tail(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk, m.rs(),
                                                n_scale_part, m.d_scal.data() + 2, m.d_scal.data() + 4,
                                                m.h_scal.data() + 2, (double)++m.trial_seq,
                                                reinterpret_cast<unsigned*>(m.d_fail.data() + 2));
-                }
             });
             m.last_err_buf = nxt;
             sync_prof(PROF_COMPUTE_ERROR, te);
-            if (!from_build && speculate && q == 0 && iteration + 1 < niterations)
+            if (!from_build && f.speculate && q == 0 && !last)
             {
-                if (!trial_poll && trial_event)
+                if (!f.trial_poll && f.trial_event)
                 {
                     if (!m.trial_ev)
                         CUGO_HIP(hipEventCreateWithFlags(&m.trial_ev, hipEventDisableTiming));
                     CUGO_HIP(hipEventRecord(m.trial_ev, s));
                 }
-                m.timed("build", [&] {
-                    cugo_k::launch_build(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk, m.d_Hpp.data(),
-                                         m.bp(), m.d_Hll.data(), m.bl(), m.d_Hpl.data(), m.rs(), nullptr,
-                                         can_fuse ? lambda_pred : -1.0, can_fuse ? m.d_invHll.data() : nullptr,
-                                         can_fuse && !use_rows ? m.d_T.data() : nullptr, ps_on ? m.d_lmrec.data() : nullptr, ps_on);
-                    m.hpp_valid = !(ps_on && can_fuse);
-                });
-                spec_queued = true;
+                m.queue_build(nxt, fuse_pred);
+                st.spec_queued = true;
             }
-            const bool flag_summed = sharded && m.chol.own_subtrees();
-            if (sharded)
+            const bool flag_summed = f.sharded && m.chol.own_subtrees();
+            if (f.sharded)
             {
                 // ranks that factor different subtrees see different zero-pivot flags: as a double the flag
                 // rides in the same sum all-reduce as F-hat and the scale
                 if (flag_summed)
-                    cugo_k::launch_flag_to_double(s, d_fail);
+                    cugo_k::launch_flag_to_double(s, m.d_fail_flag());
                 m.exchange(m.d_scal.data() + 2, flag_summed ? 3 : 2, 0);
                 CUGO_HIP(hipMemcpyAsync(m.h_scal.data() + 2, m.d_scal.data() + 2, 3 * sizeof(double),
                                         hipMemcpyDeviceToHost, s));
             }
-            // behind a speculative build the host waits for the trial's own last launch only: it then
-            // decides and queues the next Schur complement while the build pass still runs
-            if (!sharded && trial_poll)
-            {
-                // the trial's last launch ends by writing the trial's sequence number behind its three words in
-                // the pinned block (k_sum_partials2, system-scope release): the host polls that word — no event,
-                // no stream synchronisation, and whatever is queued behind the trial keeps running
-                const volatile double* seq = m.h_scal.data() + 5;
-                const auto w0 = Clock::now();
-                auto next_query = w0 + std::chrono::milliseconds(10);
-                const auto spin_limit = std::max<Clock::duration>(std::chrono::milliseconds(2), 2 * m.last_trial_wait);
-                for (unsigned long spin = 1; *seq != (double)m.trial_seq; spin++)
-                {
-                    cpu_relax();
-                    if ((spin & 0x3FF) != 0)
-                        continue;
-                    // a trial takes 1 ms (kitti_00 shape) to 3.5 ms (10k graph): the host spins through that — on a
-                    // loaded host a yield hands the core away for a scheduler quantum, longer than the trial —; a
-                    // wait that lasts longer than twice the previous one (at least 2 ms) offers the core to others
-                    // between polls, and every ~10 ms the stream is asked whether it is still working
-                    const auto now = Clock::now();
-                    if (now - w0 > spin_limit)
-                        std::this_thread::yield();
-                    if (now < next_query)
-                        continue;
-                    next_query = now + std::chrono::milliseconds(10);
-                    const hipError_t qe = hipStreamQuery(s);
-                    if (qe == hipErrorNotReady)
-                        continue;
-                    CUGO_HIP(qe); // a failed stream will never deliver
-                    // the stream is idle: everything queued has run, so the word is there (give the write a moment to
-                    // become visible to this core before calling it lost)
-                    bool there = false;
-                    for (int k = 0; k < 100000 && !there; k++)
-                    {
-                        std::atomic_thread_fence(std::memory_order_acquire);
-                        there = *seq == (double)m.trial_seq;
-                        cpu_relax();
-                    }
-                    if (!there)
-                        throw std::runtime_error("cugo: the result of an LM trial never arrived");
-                }
-                m.last_trial_wait = Clock::now() - w0;
-                std::atomic_thread_fence(std::memory_order_acquire);
-            }
-            else
-            {
-                if (spec_queued && trial_event)
-                    CUGO_HIP(hipEventSynchronize(m.trial_ev));
-                else
-                    CUGO_HIP(hipStreamSynchronize(s));
-                if (!sharded)
-                { // the three words in the pinned block are this trial's
-                    const volatile double* seq = m.h_scal.data() + 5;
-                    for (long spin = 0; *seq != (double)m.trial_seq; spin++)
-                    {
-                        if (spin == 0)
-                            sstats_.trial_sync_retries += 1;
-                        if (spin > 2000000000L)
-                            throw std::runtime_error("cugo: the result of an LM trial never arrived");
-                    }
-                    std::atomic_thread_fence(std::memory_order_acquire);
-                }
-            }
+            m.wait_for_trial(st.spec_queued, sstats_.trial_sync_retries);
+            // ---- gain ratio and damping (ref: cuda_graph_optimisation.cpp:85-120)
             int32_t fail_flag;
             std::memcpy(&fail_flag, m.h_scal.data() + 4, sizeof fail_flag);
             if (flag_summed)
@@ -1985,22 +2009,20 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
             if (!success)
                 std::printf("factorize failed!\n"); // ref: cuda_linear_solver.cpp:48
             if (rho > 0)
-            {
+            { // ref: cuda_graph_optimisation.cpp:97-120
                 const double a = 1 - std::pow(2 * rho - 1, 3);
                 lambda *= std::max(1.0 / 3.0, std::min(a, 2.0 / 3.0));
-                prev_clamped = a <= 1.0 / 3.0;
+                st.prev_clamped = a <= 1.0 / 3.0;
                 nu = 2.0;
                 F = Fhat;
-                m.cur = nxt; // accept: the trial buffer becomes the estimate (no pop needed)
-                if (spec_queued)
-                    have_build = true, built_lambda = can_fuse ? lambda_pred : -1.0;
-                break;
+                m.cur = nxt; // accept: the trial buffer becomes the estimate (no pop needed), and a speculative
+                break;       // build pass behind the trial (st.spec_queued) the next iteration's build pass
             }
             else
             {
                 lambda *= nu;
                 nu *= 2.0;
-                prev_clamped = false;
+                st.prev_clamped = false;
                 if (!std::isfinite(lambda) || (success && Fdiff < 1e-4))
                     break;
             }
@@ -2013,25 +2035,7 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
         if (q == maxq || rho < 1e-6 || !std::isfinite(lambda))
             break;
     }
-#ifdef CUGO_DEBUG_HOOKS
-    if (hash_file)
-    {
-        std::vector<unsigned long long> h(m.d_hash.size());
-        CUGO_HIP(hipMemcpyAsync(h.data(), m.d_hash.data(), h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, s));
-        CUGO_HIP(hipStreamSynchronize(s));
-        if (FILE* fp = std::fopen(hash_file, "a"))
-        {
-            std::fprintf(fp, "run\n");
-            for (size_t it = 0; it < records.size(); it++)
-            {
-                for (int k = 0; k < 64; k++)
-                    std::fprintf(fp, "%016llx ", h[64 * it + k]);
-                std::fprintf(fp, "\n");
-            }
-            std::fclose(fp);
-        }
-    }
-#endif
+    m.hash_end(records.size());
     m.collect_times();
 }
 
@@ -2114,26 +2118,16 @@ bool Engine::compute_covariances(int what)
     if (m.structure_dirty)
         build_structure();
     hipStream_t s = m.ctx.stream;
+    m.begin_call(false);
     // H at the current estimates, undamped: the two-stream build pass (Hpp, b, Hll, Hpl), as a retried trial of
     // optimize() queues it.  optimize() starts every call with a build pass of its own, so nothing it reads is lost.
-    cugo_k::launch_build(s, m.ev, m.d_poses[m.cur].data(), m.d_lms[m.cur].data(), m.rk, m.d_Hpp.data(), m.bp(),
-                         m.d_Hll.data(), m.bl(), m.d_Hpl.data(), m.rs(), nullptr, -1.0, nullptr, nullptr);
-    m.hpp_valid = true;
+    m.queue_build(m.cur, -1.0);
     const int B = m.hs.n_blocks;
     m.d_cov_sigma.resize(36 * (size_t)B + 16);
     if (m.P > 0)
     {
-        const bool use_rows = m.rows_on && cugo_k::schur_rows_usable(m.hs, m.max_row_nnz);
-        if (!m.splan_on && !use_rows && m.d_T.size() == 0)
-            m.d_T.resize(18 * (size_t)m.E + 16);
-        cugo_k::launch_schur(s, m.ev, m.hs, 0.0, 0, m.d_Hpp.data(), m.bp(), m.d_Hll.data(), m.bl(), m.d_Hpl.data(),
-                             m.d_invHll.data(), m.splan_on || use_rows ? nullptr : m.d_T.data(), m.bsc(), m.Hsc(), false,
-                             use_rows ? cugo_k::SchurRows{m.d_pose_rec.data(), m.max_row_nnz, nullptr, m.opt.hsc_mfma, m.opt.hsc_xcd}
-                                      : cugo_k::SchurRows{nullptr, 0, m.strip_on ? m.d_off_pi.data() : nullptr,
-                                                          m.opt.hsc_mfma, m.opt.hsc_xcd, nullptr,
-                                                          m.d_poses[m.cur].data(), m.rs(), m.bp()});
-        int32_t* d_fail = reinterpret_cast<int32_t*>(m.d_scal.data() + 4);
-        m.chol.factor_solve(m.Hsc(), 0.0, m.bsc(), m.xp(), d_fail);
+        m.queue_schur(0.0, false, false, m.cur);
+        m.queue_factor_solve(0.0);
         if (!m.chol.selected_inverse(m.d_cov_sigma.data()))
             return false;
     }

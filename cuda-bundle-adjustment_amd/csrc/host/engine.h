@@ -150,9 +150,7 @@ public:
         int launches;
     };
     std::vector<KernelTime> kernel_times() const;
-    // device views for kernel-level tests / the C ABI
     struct Impl;
-    Impl* impl() { return impl_; }
 
 private:
     void build_structure();

@@ -744,6 +744,45 @@ def test_trial_chi2_out_of_the_next_build_pass_gives_the_same_bits(oracle_lib, m
         assert np.array_equal(runs[0]["pose"], runs[1]["pose"]) and np.array_equal(runs[0]["lm"], runs[1]["lm"])
 
 
+def test_ways_to_wait_for_a_trial_and_the_profiled_loop_give_the_same_bits(oracle_lib, monkeypatch):
+    """the documented switches of the LM loop that only change how the host waits.  CUGO_TRIAL_POLL=0 (the event
+    behind the trial's last launch) and CUGO_TRIAL_POLL=0 with CUGO_TRIAL_EVENT=0 (the whole stream) also switch the
+    chi2-from-the-build-pass form off, which is bit-neutral (the test above): the same (chi2, lambda, trials) per
+    iteration and the same bits at the end as the default run, and the sequence word is always there when the wait
+    returns.  CUGO_PROFILE=1 (a synchronisation per phase) also switches the speculative build off, and without it
+    other iterations run k_pose_schur (sums in another order): it is bitwise the CUGO_SPECULATE=0 run, not the default
+    one.  On a graph whose trials are all accepted and on golden cases with rejected trials and missed dampings."""
+    d, _ = synth_problem(oracle_lib, 200, 3000, 12500, seed=31, lc=100)
+    cases = [(d, (0, 0.0))]
+    for name in ("reject_8x60", "tukey_8x80", "tiny_3x8"):
+        g8 = np.load(golden_path(name + ".npz"))
+        cases.append(({k: g8[k] for k in PROBLEM_KEYS}, (int(g8["rk_type"]), float(g8["rk_delta"]))))
+    switches = ("CUGO_TRIAL_POLL", "CUGO_TRIAL_EVENT", "CUGO_PROFILE", "CUGO_SPECULATE")
+
+    def run(dd, rk, **env):
+        for k in switches:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        out = run_graph(dd, 10, rk=rk)
+        for k in switches:
+            monkeypatch.delenv(k, raising=False)
+        return out
+
+    def same_bits(a, b):
+        assert [(s["chi2"], s["lam"], s["trials"]) for s in a["stats"]] == \
+               [(s["chi2"], s["lam"], s["trials"]) for s in b["stats"]]
+        assert np.array_equal(a["pose"], b["pose"]) and np.array_equal(a["lm"], b["lm"])
+
+    for dd, rk in cases:
+        default = run(dd, rk)
+        for env in (dict(CUGO_TRIAL_POLL="0"), dict(CUGO_TRIAL_POLL="0", CUGO_TRIAL_EVENT="0")):
+            waited = run(dd, rk, **env)
+            same_bits(waited, default)
+            assert waited["sstats"]["trial_sync_retries"] == 0
+        same_bits(run(dd, rk, CUGO_PROFILE="1"), run(dd, rk, CUGO_SPECULATE="0"))
+
+
 def test_bitwise_reproducible(oracle_lib):
     d, _ = synth_problem(oracle_lib, 200, 3000, 12500, seed=21, lc=100)
     a, b = run_graph(d, 8), run_graph(d, 8)
