@@ -19,7 +19,8 @@ HOOKS_LIB_PATH = os.path.join(_HERE, "libcugo_hip_hooks.so")  # make HOOKS=1: de
 _lib = None
 
 OK = 0
-RK_NONE, RK_CAUCHY, RK_TUKEY = 0, 1, 2
+RK_NONE, RK_CAUCHY, RK_TUKEY, RK_HUBER = 0, 1, 2, 3
+ICP_PLANE, ICP_LINE = 0, 1
 EDGE_FIXED_L, EDGE_FIXED_P, EDGE_STEREO, EDGE_INACTIVE = 1, 2, 4, 8
 
 _i32p = C.POINTER(C.c_int32)
@@ -265,6 +266,48 @@ class Graph:
 
     def set_robust_kernel(self, dim, rk_type, delta):
         check(lib().cugo_graph_set_robust_kernel(self._g, dim, int(rk_type), C.c_double(delta)))
+
+    def add_plane_edges(self, pose_ids, pointP, normal, origin_distance, info=None):
+        """point-to-plane pose edges (ref: PlaneEdgeSet): residual normal . (R pointP + t) - origin_distance; the
+        normal must be of unit length (initialize() refuses otherwise).  info: per edge, or None for the set's value"""
+        n = len(pose_ids)
+        if n == 0:
+            return
+        pi = np.ascontiguousarray(pose_ids, np.int32)
+        p = np.ascontiguousarray(np.asarray(pointP, np.float64).reshape(n, 3))
+        nn = np.ascontiguousarray(np.asarray(normal, np.float64).reshape(n, 3))
+        d = np.ascontiguousarray(np.asarray(origin_distance, np.float64).reshape(n))
+        w = None if info is None else np.ascontiguousarray(np.broadcast_to(np.asarray(info, np.float64), (n,)))
+        check(lib().cugo_graph_add_plane_edges(self._g, n, _p(pi, _i32p), _p(p, _f64p), _p(nn, _f64p), _p(d, _f64p),
+                                               None if w is None else _p(w, _f64p)))
+
+    def add_line_edges(self, pose_ids, pointP, a, b, info=None):
+        """point-to-line pose edges (ref: LineEdgeSet): the distance of R pointP + t to the line through a and b"""
+        n = len(pose_ids)
+        if n == 0:
+            return
+        pi = np.ascontiguousarray(pose_ids, np.int32)
+        p = np.ascontiguousarray(np.asarray(pointP, np.float64).reshape(n, 3))
+        aa = np.ascontiguousarray(np.asarray(a, np.float64).reshape(n, 3))
+        bb = np.ascontiguousarray(np.asarray(b, np.float64).reshape(n, 3))
+        w = None if info is None else np.ascontiguousarray(np.broadcast_to(np.asarray(info, np.float64), (n,)))
+        check(lib().cugo_graph_add_line_edges(self._g, n, _p(pi, _i32p), _p(p, _f64p), _p(aa, _f64p), _p(bb, _f64p),
+                                              None if w is None else _p(w, _f64p)))
+
+    def set_icp_information(self, kind, info):
+        """kind: ICP_PLANE / ICP_LINE; the set's information (used when per_edge_information is off)"""
+        check(lib().cugo_graph_set_icp_information(self._g, int(kind), C.c_double(info)))
+
+    def set_icp_robust_kernel(self, kind, rk_type, delta):
+        check(lib().cugo_graph_set_icp_robust_kernel(self._g, int(kind), int(rk_type), C.c_double(delta)))
+
+    def set_icp_outlier_threshold(self, kind, threshold):
+        """only 0 is usable: initialize() refuses a positive threshold on these sets (not built yet)"""
+        check(lib().cugo_graph_set_icp_outlier_threshold(self._g, int(kind), C.c_double(threshold)))
+
+    def n_icp_edges(self, kind):
+        """active edges of the kind in the current flattening (edges on fixed poses are not counted)"""
+        return lib().cugo_graph_n_icp_edges(self._g, int(kind))
 
     def set_outlier_threshold(self, dim, threshold):
         """edges of the set (dim 2 mono / 3 stereo) with chi2 > threshold are inactivated at the

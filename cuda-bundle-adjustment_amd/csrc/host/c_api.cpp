@@ -7,6 +7,7 @@
 
 #include "../../../include/cugo_hip.h"
 #include "../../include/cuda_graph_optimisation.h"
+#include "../../include/icp_types.h"
 #include "../kernels/kernels.h"
 #include "chol_solver.h"
 #include "engine.h"
@@ -469,6 +470,10 @@ struct cugo_graph
     cugo::LandmarkVertexSet lms{true};
     cugo::MonoEdgeSet mono;
     cugo::StereoEdgeSet stereo;
+    cugo::PlaneEdgeSet plane;
+    cugo::LineEdgeSet line;
+    std::deque<cugo::PlaneEdge> plane_store;
+    std::deque<cugo::LineEdge> line_store;
     std::deque<cugo::PoseVertex> pose_store;
     std::deque<cugo::LandmarkVertex> lm_store;
     std::deque<cugo::MonoEdge> mono_store;
@@ -482,6 +487,8 @@ struct cugo_graph
         opt->addVertexSet(&lms);
         opt->addEdgeSet(&mono);
         opt->addEdgeSet(&stereo);
+        opt->addEdgeSet(&plane);
+        opt->addEdgeSet(&line);
         attached = true;
     }
 };
@@ -595,6 +602,95 @@ int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids,
             }
         }
     });
+}
+static cugo::PoseVertex* icp_pose(cugo_graph* g, int32_t id)
+{
+    try
+    {
+        return g->poses.getVertex(id);
+    }
+    catch (const std::out_of_range&)
+    {
+        throw std::invalid_argument("cugo_graph_add_*_edges: unknown pose id " + std::to_string(id));
+    }
+}
+int cugo_graph_add_plane_edges(cugo_graph* g, int n, const int32_t* pose_ids, const double* pointP,
+                               const double* normal, const double* origin_distance, const double* info)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids || !pointP || !normal || !origin_distance)))
+            throw std::invalid_argument("cugo_graph_add_plane_edges: missing arrays");
+        for (int i = 0; i < n; i++)
+            (void)icp_pose(g, pose_ids[i]); // (all or nothing: an unknown id adds no edge)
+        for (int i = 0; i < n; i++)
+        {
+            g->plane_store.emplace_back();
+            cugo::PlaneEdge& e = g->plane_store.back();
+            e.setVertex(icp_pose(g, pose_ids[i]), 0);
+            e.setMeasurement(cugo::PointToPlaneMatch<double>(cugo::Vec3d(normal + 3 * (size_t)i), origin_distance[i],
+                                                             cugo::Vec3d(pointP + 3 * (size_t)i)));
+            e.setInformation(info ? info[i] : 0.0);
+            g->plane.addEdge(&e);
+        }
+    });
+}
+int cugo_graph_add_line_edges(cugo_graph* g, int n, const int32_t* pose_ids, const double* pointP, const double* a,
+                              const double* b, const double* info)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids || !pointP || !a || !b)))
+            throw std::invalid_argument("cugo_graph_add_line_edges: missing arrays");
+        for (int i = 0; i < n; i++)
+            (void)icp_pose(g, pose_ids[i]);
+        for (int i = 0; i < n; i++)
+        {
+            g->line_store.emplace_back();
+            cugo::LineEdge& e = g->line_store.back();
+            e.setVertex(icp_pose(g, pose_ids[i]), 0);
+            cugo::PointToLineMatch<double> mz(cugo::Vec3d(a + 3 * (size_t)i), cugo::Vec3d(b + 3 * (size_t)i));
+            mz.pointP = cugo::Vec3d(pointP + 3 * (size_t)i);
+            e.setMeasurement(mz);
+            e.setInformation(info ? info[i] : 0.0);
+            g->line.addEdge(&e);
+        }
+    });
+}
+static cugo::BaseEdgeSet* icp_set(cugo_graph* g, int kind)
+{
+    if (kind == CUGO_ICP_PLANE)
+        return &g->plane;
+    if (kind == CUGO_ICP_LINE)
+        return &g->line;
+    throw std::invalid_argument("cugo: kind must be CUGO_ICP_PLANE (0) or CUGO_ICP_LINE (1)");
+}
+int cugo_graph_set_icp_information(cugo_graph* g, int kind, double info)
+{
+    return guarded([&] { icp_set(g, kind)->setInformation(info); });
+}
+int cugo_graph_set_icp_robust_kernel(cugo_graph* g, int kind, int type, double delta)
+{
+    return guarded([&] {
+        const cugo::RobustKernelType t = type == CUGO_RK_CAUCHY  ? cugo::RobustKernelType::Cauchy
+                                         : type == CUGO_RK_TUKEY ? cugo::RobustKernelType::Tukey
+                                         : type == CUGO_RK_HUBER ? cugo::RobustKernelType::Huber
+                                                                 : cugo::RobustKernelType::None;
+        icp_set(g, kind)->setRobustKernel(t, delta);
+    });
+}
+int cugo_graph_set_icp_outlier_threshold(cugo_graph* g, int kind, double threshold)
+{
+    return guarded([&] {
+        if (kind == CUGO_ICP_PLANE)
+            g->plane.setOutlierThreshold(threshold);
+        else if (kind == CUGO_ICP_LINE)
+            g->line.setOutlierThreshold(threshold);
+        else
+            icp_set(g, kind);
+    });
+}
+int cugo_graph_n_icp_edges(cugo_graph* g, int kind)
+{
+    return kind == CUGO_ICP_PLANE || kind == CUGO_ICP_LINE ? g->opt->nIcpEdges(kind) : -1;
 }
 int cugo_graph_set_camera(cugo_graph* g, int dim, const double* c)
 {

@@ -134,6 +134,26 @@ struct Engine::Impl : cugo_k::LaunchHook
     PinnedBuf<int32_t> h_fail;
 
     cugo_edges ev{};
+    // point-to-plane / point-to-line pose edges (icp_kernels.hip): each kind sorted by pose (stable: container order
+    // inside a pose), structure of arrays, on the device as long as the flattening lives.  Their partial sums have a
+    // scratch of their own: the BA scratch holds live scale / chi2 partials and records across the same span of the stream
+    struct IcpKindBufs
+    {
+        std::vector<int32_t> h_pose, h_ptr, slot_set, slot_edge;
+        std::vector<double> h_p, h_geo, h_omega;
+        DevBuf<int32_t> d_pose, d_ptr;
+        DevBuf<double> d_p, d_geo, d_omega;
+    } icpk[2];
+    cugo_icp_edges icp{};
+    int n_icp = 0;
+    DevBuf<double> d_icp_scratch;
+    cugo_k::ReduceScratch icp_rs() { return {d_icp_scratch.data(), d_icp_scratch.size()}; }
+    // the chi2 totals of the chunks of the last ICP pass, for the launch that ends a trial
+    const double* icp_chi(int* n)
+    {
+        *n = 0;
+        return n_icp ? cugo_k::icp_chunk_chi(icp, icp_rs(), n) : nullptr;
+    }
     cugo_hsc_struct hs{};
     SchurPlanDevice splan; // landmark-major product plan of the Schur complement (schur_plan.h)
     bool splan_on = false;
@@ -467,6 +487,15 @@ struct Engine::Impl : cugo_k::LaunchHook
                                  d_Hll.data(), bl(), d_Hpl.data(), rs(), d_chi, fuse ? fuse_lambda : -1.0,
                                  fuse ? d_invHll.data() : nullptr, fuse && !f.use_rows ? d_T.data() : nullptr,
                                  one_stream ? d_lmrec.data() : nullptr, one_stream, chi_behind_scale);
+            if (n_icp)
+            { // the chunk pass leaves the per-pose partials and the chunk chi2 totals; the add goes behind k_build_poses
+              // here or, in the one-stream form (Hpp is not written), behind k_pose_schur (queue_schur)
+                cugo_k::launch_icp_chunks(ctx.stream, icp, d_poses[buf].data(), true, icp_rs());
+                if (!one_stream)
+                    cugo_k::launch_icp_add(ctx.stream, icp, icp_rs(), d_Hpp.data(), bp());
+                if (d_chi)
+                    cugo_k::launch_icp_chi_total(ctx.stream, icp, icp_rs(), d_chi, true);
+            }
         });
         st.hpp_valid = !one_stream;
         st.fused_lambda = fuse ? fuse_lambda : -1.0;
@@ -483,6 +512,8 @@ struct Engine::Impl : cugo_k::LaunchHook
                                                                 opt.hsc_mfma, opt.hsc_xcd,
                                                                 one_stream ? d_lmrec.data() : nullptr,
                                                                 d_poses[buf].data(), rs(), bp()});
+            if (n_icp && one_stream)
+                cugo_k::launch_icp_add_schur(ctx.stream, icp, icp_rs(), hs.d_rowptr, Hsc(), bp(), bsc());
         });
     }
     // diagnosis: CUGO_DEBUG_HASH=<file> — position-weighted integer checksums of the arrays every stage of the
@@ -741,7 +772,10 @@ void Engine::initialize(FlatGraph& g)
     m.rk = g.rk;
     m.init_rank = m.rank, m.init_world = m.world;
     const int Etot = g.n_edges();
-    E_global_ = Etot;
+    E_global_ = Etot + g.plane.n() + g.line.n();
+    if ((g.plane.n() || g.line.n()) && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: point-to-plane / point-to-line edge sets are not supported on a landmark-sharded "
+                                 "(multi-GPU) optimiser yet");
 
     // ---- landmark-major order: counting sort by landmark, then by pose inside ----------
     // Threads own contiguous landmark ranges: each scans all edges (8 B per edge, from cache)
@@ -1242,6 +1276,63 @@ void Engine::initialize(FlatGraph& g)
         });
     }
     laps.lap("engine: pose-major view");
+    // ---- point-to-plane / point-to-line edges: stable counting sort by pose, structure of arrays ----
+    {
+        const FlatIcpKind* kinds[2] = {&g.plane, &g.line};
+        for (int k = 0; k < 2; k++)
+        {
+            const FlatIcpKind& fk = *kinds[k];
+            Impl::IcpKindBufs& b = m.icpk[k];
+            const int n = fk.n(), gw = k == 0 ? 4 : 6;
+            b.h_ptr.assign((size_t)m.Pall + 1, 0);
+            for (int e = 0; e < n; e++)
+            {
+                if (fk.pose[e] < 0 || fk.pose[e] >= m.P)
+                    throw std::runtime_error("cugo: a point-to-plane / point-to-line edge is not on a free pose");
+                b.h_ptr[(size_t)fk.pose[e] + 1]++;
+            }
+            for (int q = 0; q < m.Pall; q++)
+                b.h_ptr[q + 1] += b.h_ptr[q];
+            b.h_pose.resize(n), b.slot_set.resize(n), b.slot_edge.resize(n);
+            b.h_p.resize(3 * (size_t)n), b.h_geo.resize((size_t)gw * n);
+            const bool per_edge = fk.omega.size() > 1;
+            b.h_omega.assign(per_edge ? (size_t)n : 1, fk.omega.empty() ? 1.0 : fk.omega[0]);
+            std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1);
+            for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
+            {
+                const size_t i = (size_t)pos[fk.pose[e]]++;
+                b.h_pose[i] = fk.pose[e];
+                b.slot_set[i] = fk.src_set[e], b.slot_edge[i] = fk.src_edge[e];
+                for (int c = 0; c < 3; c++)
+                    b.h_p[(size_t)c * n + i] = fk.p[3 * (size_t)e + c];
+                for (int c = 0; c < gw; c++)
+                    b.h_geo[(size_t)c * n + i] = fk.geo[(size_t)gw * e + c];
+                if (per_edge)
+                    b.h_omega[i] = fk.omega[e];
+            }
+            if (!m.plan_only)
+            {
+                b.d_pose.upload(b.h_pose, s), b.d_ptr.upload(b.h_ptr, s);
+                b.d_p.upload(b.h_p, s), b.d_geo.upload(b.h_geo, s), b.d_omega.upload(b.h_omega, s);
+            }
+        }
+        m.n_icp = g.plane.n() + g.line.n();
+        cugo_icp_edges& iv = m.icp;
+        iv = cugo_icp_edges{};
+        iv.n_poses_total = m.Pall, iv.n_poses_free = m.P;
+        iv.n_plane = g.plane.n(), iv.n_line = g.line.n();
+        iv.d_plane_pose = m.icpk[0].d_pose.data(), iv.d_plane_pose_ptr = m.icpk[0].d_ptr.data();
+        iv.d_plane_p = m.icpk[0].d_p.data(), iv.d_plane_nd = m.icpk[0].d_geo.data();
+        iv.d_plane_omega = m.icpk[0].d_omega.data(), iv.n_plane_omega = (int)m.icpk[0].h_omega.size();
+        iv.rk_plane = g.plane.rk, iv.delta_plane = g.plane.delta;
+        iv.d_line_pose = m.icpk[1].d_pose.data(), iv.d_line_pose_ptr = m.icpk[1].d_ptr.data();
+        iv.d_line_p = m.icpk[1].d_p.data(), iv.d_line_au = m.icpk[1].d_geo.data();
+        iv.d_line_omega = m.icpk[1].d_omega.data(), iv.n_line_omega = (int)m.icpk[1].h_omega.size();
+        iv.rk_line = g.line.rk, iv.delta_line = g.line.delta;
+        if (m.n_icp && !m.plan_only)
+            m.d_icp_scratch.resize(cugo_k::icp_scratch_doubles(iv));
+    }
+    laps.lap("engine: ICP edge sort");
     // ---- upload (a plan-only engine has no device: it skips to the topology signature) -----
     if (!m.plan_only)
     {
@@ -1947,10 +2038,13 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
             if (from_build)
             {
                 m.queue_build(nxt, fuse_pred, nullptr, true);
-                m.timed("errors", [&] {
+                m.timed("errors", [&] { // (the ICP chunk totals are those of the build pass just queued)
+                    int n_icp_chi = 0;
+                    const double* icp_chi = m.icp_chi(&n_icp_chi);
                     cugo_k::launch_trial_tail_from_build(s, m.ev, m.rs(), n_scale_part, m.d_scal.data() + 2,
                                                          m.d_scal.data() + 4, m.h_scal.data() + 2, (double)++m.trial_seq,
-                                                         reinterpret_cast<unsigned*>(m.d_fail.data() + 2));
+                                                         reinterpret_cast<unsigned*>(m.d_fail.data() + 2), icp_chi,
+                                                         n_icp_chi);
                 });
                 if (f.can_fuse)
                 { // the Schur complement of the next iteration's first trial, should the damping be the predicted one:
@@ -1966,10 +2060,16 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
                     cugo_k::launch_errors(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk,
                                           m.rs(), m.d_scal.data() + 2);
                 else
+                {
+                    int n_icp_chi = 0;
+                    const double* icp_chi = m.icp_chi(&n_icp_chi);
+                    if (m.n_icp)
+                        cugo_k::launch_icp_chunks(s, m.icp, m.d_poses[nxt].data(), false, m.icp_rs());
                     cugo_k::launch_errors_tail(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk, m.rs(),
                                                n_scale_part, m.d_scal.data() + 2, m.d_scal.data() + 4,
                                                m.h_scal.data() + 2, (double)++m.trial_seq,
-                                               reinterpret_cast<unsigned*>(m.d_fail.data() + 2));
+                                               reinterpret_cast<unsigned*>(m.d_fail.data() + 2), icp_chi, n_icp_chi);
+                }
             });
             m.last_err_buf = nxt;
             sync_prof(PROF_COMPUTE_ERROR, te);
@@ -2093,6 +2193,12 @@ std::vector<int32_t> Engine::reject_outliers()
     return out;
 }
 
+int Engine::n_icp_edges(int kind) const { return kind == 0 ? impl_->icp.n_plane : kind == 1 ? impl_->icp.n_line : 0; }
+const std::vector<int32_t>& Engine::icp_slot_source(int kind, bool set) const
+{
+    const Impl::IcpKindBufs& b = impl_->icpk[kind == 1 ? 1 : 0];
+    return set ? b.slot_set : b.slot_edge;
+}
 int Engine::n_poses_free() const { return impl_->P; }
 int Engine::n_landmarks_free() const { return impl_->L; }
 

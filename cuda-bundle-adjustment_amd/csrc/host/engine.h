@@ -17,6 +17,26 @@ struct Options;
 
 // Result of flattening a graph (ref: VertexSet::generateEstimateData + EdgeSet::init,
 // src/optimisable_graph.hpp:84-126,474-572).  Indices: free vertices first.
+// Point-to-plane / point-to-line pose edges of one kind (icp_types.h), flattened in container order; edges on fixed
+// poses, inactive edges and everything invalid never get here (graph_optimisation.cpp validates and drops)
+struct FlatIcpKind
+{
+    std::vector<int32_t> pose; // free-first pose index per edge (always < P)
+    std::vector<double> p;     // E x 3 pointP
+    std::vector<double> geo;   // plane: E x 4 (normal, originDistance); line: E x 6 (a, unit direction)
+    std::vector<double> omega; // E, or 1 when uniform / perEdgeInformation is off
+    std::vector<int32_t> src_set, src_edge; // where an edge came from: edge set (position among the optimiser's edge
+                                            // sets) and position in that set's container
+    int rk = CUGO_RK_NONE;
+    double delta = 1.0;
+    int n() const { return (int)pose.size(); }
+    void clear()
+    {
+        pose.clear(), p.clear(), geo.clear(), omega.clear(), src_set.clear(), src_edge.clear();
+        rk = CUGO_RK_NONE, delta = 1.0;
+    }
+};
+
 struct FlatGraph
 {
     int Pall = 0, Lall = 0, P = 0, L = 0;
@@ -33,6 +53,7 @@ struct FlatGraph
     // outlier rejection (ref: EdgeSet::updateEdges, optimisable_graph.hpp:603-640): per edge
     // the chi2 threshold of its edge set, 0 = disabled; empty = disabled for all
     std::vector<double> e_outlier_threshold;
+    FlatIcpKind plane, line;
     int n_edges() const { return (int)e_pose.size(); }
 };
 
@@ -134,7 +155,11 @@ public:
     const std::vector<double>& cov_lm() const { return cov_lm_; }
     int n_poses_free() const;
     int n_landmarks_free() const;
-    int n_active_edges() const { return E_global_; }
+    int n_active_edges() const { return E_global_; } // BA + ICP edges of the current flattening
+    int n_icp_edges(int kind) const;                  // 0 plane, 1 line
+    // sorted slot of a kind -> {edge set, position in the set} as FlatIcpKind recorded them (kept for a later
+    // outlier rejection on these sets)
+    const std::vector<int32_t>& icp_slot_source(int kind, bool set) const;
     const StructureStats& structure_stats() const { return sstats_; }
     const double* profile_ms() const { return prof_; }
     static const char* profile_name(int i);

@@ -2,9 +2,11 @@
 // ref: src/cuda_graph_optimisation.cpp:42-183 (class), src/block_solver.cpp:21-137
 // (initialize), src/optimisable_graph.hpp:84-154, 474-572 (index / flag / activeness rules).
 #include "../../include/cuda_graph_optimisation.h"
+#include "../../include/icp_types.h"
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -67,6 +69,7 @@ void CudaGraphOptimisationImpl::exchangeStats(double& bytes, int& calls) const
 }
 
 int CudaGraphOptimisationImpl::nActiveEdges() const { return engine_->n_active_edges(); }
+int CudaGraphOptimisationImpl::nIcpEdges(int kind) const { return engine_->n_icp_edges(kind); }
 
 std::vector<double> CudaGraphOptimisationImpl::structureStats() const
 {
@@ -120,6 +123,97 @@ static int rk_code(RobustKernelType t)
     default:
         return CUGO_RK_NONE;
     }
+}
+
+// One PlaneEdgeSet / LineEdgeSet (icp_types.h) into the flat arrays of its kind, in container order.  This is the one
+// place where these edges are checked (the kernels take the layout as given): every active edge must sit on a pose
+// vertex of one of the optimiser's pose vertex sets and hold finite values, a plane normal of unit length (the header
+// says "used as given": refused, not normalised silently) or two distinct line points.  Inactive edges and edges on
+// fixed poses are dropped, as BA edges with two fixed ends are.  Several sets of a kind must agree on the robust kernel.
+static void flattenIcpSet(BaseEdgeSet* es, int setIndex, bool line, bool perInfo,
+                          const std::vector<BaseVertexSet*>& vertexSets, cugo_host::FlatIcpKind& out, bool& seen)
+{
+    const char* kind = line ? "point-to-line" : "point-to-plane";
+    auto refuse = [&](size_t i, const char* what) {
+        throw std::runtime_error(std::string("cugo: ") + kind + " edge " + std::to_string(i) + " of edge set " +
+                                 std::to_string(setIndex) + ": " + what);
+    };
+    if (es->getOutlierThreshold() > 0.0)
+        throw std::runtime_error(std::string("cugo: outlier rejection is not available on ") + kind +
+                                 " edge sets yet (setOutlierThreshold must stay 0)");
+    const RobustKernel& k = es->robustKernelData();
+    const int rk = rk_code(k.type());
+    const double delta = k.delta();
+    if (es->nedges() > 0)
+    {
+        if (seen && (rk != out.rk || (rk != CUGO_RK_NONE && delta != out.delta)))
+            throw std::runtime_error(std::string("cugo: the ") + kind + " edge sets of one optimiser must use the same robust kernel");
+        if (!std::isfinite(delta) || (rk != CUGO_RK_NONE && !(delta > 0.0)))
+            throw std::runtime_error(std::string("cugo: bad robust kernel delta on a ") + kind + " edge set");
+        out.rk = rk, out.delta = delta;
+        seen = true;
+    }
+    es->setOutlierCount(0);
+    const double set_info = es->informationValue();
+    size_t i = 0, kept = 0;
+    for (BaseEdge* e : es->get())
+    {
+        const size_t at = i++;
+        if (!e->isActive())
+            continue;
+        BaseVertex* v = e->getVertex(0);
+        bool known = false;
+        if (v && !v->isMarginilised())
+            for (const BaseVertexSet* vs : vertexSets)
+                known = known || (vs == v->ownerSet() && !vs->isMarginilised());
+        if (!known)
+            refuse(at, "its pose vertex is in no pose vertex set of this optimiser");
+        const double w = perInfo ? (double)e->informationValue() : set_info;
+        if (!std::isfinite(w))
+            refuse(at, "non-finite information");
+        double p[3], geo[6];
+        if (!line)
+        {
+            const auto& mz = *static_cast<const PointToPlaneMatch<double>*>(e->measurementData());
+            for (int c = 0; c < 3; c++)
+                p[c] = mz.pointP[c], geo[c] = mz.normal[c];
+            geo[3] = mz.originDistance;
+            for (int c = 0; c < 3; c++)
+                if (!std::isfinite(p[c]) || !std::isfinite(geo[c]))
+                    refuse(at, "non-finite point or normal");
+            if (!std::isfinite(geo[3]))
+                refuse(at, "non-finite originDistance");
+            const double len = std::sqrt(geo[0] * geo[0] + geo[1] * geo[1] + geo[2] * geo[2]);
+            if (!(std::fabs(len - 1.0) <= 1e-6))
+                refuse(at, "the plane normal is not of unit length (it is used as given)");
+        }
+        else
+        {
+            const auto& mz = *static_cast<const PointToLineMatch<double>*>(e->measurementData());
+            double d[3];
+            for (int c = 0; c < 3; c++)
+            {
+                p[c] = mz.pointP[c], geo[c] = mz.a[c], d[c] = mz.b[c] - mz.a[c];
+                if (!std::isfinite(p[c]) || !std::isfinite(mz.a[c]) || !std::isfinite(mz.b[c]))
+                    refuse(at, "non-finite point or line end");
+            }
+            const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+            if (!(len > 0.0) || !std::isfinite(len))
+                refuse(at, "the two points of the line coincide (a == b)");
+            for (int c = 0; c < 3; c++)
+                geo[3 + c] = d[c] / len;
+        }
+        if (v->isFixed())
+            continue;
+        out.pose.push_back(v->getIndex());
+        out.p.insert(out.p.end(), p, p + 3);
+        out.geo.insert(out.geo.end(), geo, geo + (line ? 6 : 4));
+        out.omega.push_back(w);
+        out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
+        kept++;
+    }
+    es->setActiveEdgeCount(kept);
+    es->setDirtyState(false);
 }
 
 void CudaGraphOptimisationImpl::initialize()
@@ -228,7 +322,10 @@ void CudaGraphOptimisationImpl::initialize()
     // the flattened order is exactly the container order.
     size_t cap = 0;
     for (BaseEdgeSet* es : edgeSets)
-        cap += es->nedges();
+        if (es->dim() != 1)
+            cap += es->nedges();
+    g.plane.clear(), g.line.clear();
+    bool seen_plane = false, seen_line = false;
     g.e_pose.resize(cap), g.e_lm.resize(cap), g.e_flags.resize(cap);
     g.e_meas.resize(3 * cap), g.e_omega.resize(cap), g.e_cam.resize(cap);
     g.e_outlier_threshold.resize(cap);
@@ -245,12 +342,20 @@ void CudaGraphOptimisationImpl::initialize()
     const unsigned hw = cugo_host::pool_threads();
     lap("graph: edge array alloc");
     size_t out = 0; // slots filled so far (compacted)
-    for (BaseEdgeSet* es : edgeSets)
+    for (size_t si = 0; si < edgeSets.size(); si++)
     {
+        BaseEdgeSet* es = edgeSets[si];
         const int dim = es->dim();
-        if (dim == 1) // PlaneEdgeSet / LineEdgeSet (icp_types.h)
-            throw std::runtime_error("cugo: the optimiser does not take point-to-plane / point-to-line edge sets yet "
-                                     "(their terms: cugo_icp_* in include/cugo_hip.h)");
+        if (dim == 1)
+        { // PlaneEdgeSet / LineEdgeSet (icp_types.h): both have dim() 1, the type tells them apart
+            if (dynamic_cast<PlaneEdgeSet*>(es))
+                flattenIcpSet(es, (int)si, false, options.perEdgeInformation, vertexSets, g.plane, seen_plane);
+            else if (dynamic_cast<LineEdgeSet*>(es))
+                flattenIcpSet(es, (int)si, true, options.perEdgeInformation, vertexSets, g.line, seen_line);
+            else
+                throw std::runtime_error("cugo: a 1-d edge set must be a PlaneEdgeSet or a LineEdgeSet (icp_types.h)");
+            continue;
+        }
         if (dim != 2 && dim != 3)
             throw std::runtime_error("cugo: only 2-d (mono) and 3-d (stereo) BA edge sets are supported");
         const uint8_t stereo_bit = dim == 3 ? CUGO_EDGE_STEREO : 0;
@@ -414,6 +519,14 @@ void CudaGraphOptimisationImpl::initialize()
         g.cams.assign(z, z + 5);
     }
     g.rk = rk;
+    for (cugo_host::FlatIcpKind* fk : {&g.plane, &g.line})
+    { // one information value for the whole kind: a single entry, as for the BA edges
+        bool uniform = !fk->omega.empty();
+        for (double w : fk->omega)
+            uniform = uniform && w == fk->omega[0];
+        if (uniform)
+            fk->omega.resize(1);
+    }
     lap("graph: edge flatten");
 
     engine_->initialize(g);

@@ -179,12 +179,15 @@ __global__ __launch_bounds__(SP_BS) void k_sum_partials(const double* __restrict
 // the two reductions at the end of an LM trial in ONE launch: workgroup 0 sums the chi2 partials of
 // the error pass, workgroup 1 the scale partials of the update pass — each exactly as k_sum_partials
 // does (same order, same result) — and both also deposit their value, workgroup 0 the factorisation
-// flag too, in a pinned host block: no device-to-host copy is queued behind them
+// flag too, in a pinned host block: no device-to-host copy is queued behind them.  partC / nC (graphs with
+// point-to-plane / point-to-line edges, else 0): the chi2 totals of the chunks of the ICP pass at the trial's estimates
+// (icp_kernels.hip); workgroup 0 sums them the same way, in their order, and adds the sum to the BA chi2
 __global__ __launch_bounds__(SP_BS) void k_sum_partials2(const double* __restrict__ partA, int nA,
                                                          const double* __restrict__ partB, int nB,
                                                          double* __restrict__ out, const double* __restrict__ flag,
                                                          double* __restrict__ host_out, double seq,
-                                                         unsigned* __restrict__ done)
+                                                         unsigned* __restrict__ done,
+                                                         const double* __restrict__ partC, int nC)
 {
     __shared__ double sm[SP_BS / 64];
     const double* part = blockIdx.x == 0 ? partA : partB;
@@ -198,7 +201,14 @@ __global__ __launch_bounds__(SP_BS) void k_sum_partials2(const double* __restric
     }
     for (; i < n; i += SP_BS)
         v0 += part[i];
-    const double v = block_sum((v0 + v1) + (v2 + v3), sm);
+    double v = block_sum((v0 + v1) + (v2 + v3), sm);
+    if (blockIdx.x == 0 && nC > 0)
+    { // (workgroup-uniform)
+        double c = 0;
+        for (int j = threadIdx.x; j < nC; j += SP_BS)
+            c += partC[j];
+        v += block_sum(c, sm);
+    }
     if (threadIdx.x == 0)
     {
         out[blockIdx.x] = v;
@@ -2448,7 +2458,8 @@ void launch_errors(hipStream_t s, const cugo_edges& e, const double* d_poses, co
 
 void launch_errors_tail(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                         cugo_robust rk, ReduceScratch rs, int n_scale_partials, double* d_out,
-                        const double* d_flag, double* h_out, double seq, unsigned* d_done)
+                        const double* d_flag, double* h_out, double seq, unsigned* d_done, const double* d_icp_chi,
+                        int n_icp_chi)
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E, BS);
@@ -2459,7 +2470,7 @@ void launch_errors_tail(hipStream_t s, const cugo_edges& e, const double* d_pose
         CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part);
     CUGO_LAUNCH(k_sum_partials2, dim3(2), dim3(SP_BS), 0, s, d_chi_part, nb, rs.d_partials, n_scale_partials,
-                d_out, d_flag, h_out, seq, d_done);
+                d_out, d_flag, h_out, seq, d_done, d_icp_chi, n_icp_chi);
 }
 
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
@@ -2523,12 +2534,13 @@ void launch_build(hipStream_t s, const cugo_edges& e, const double* d_poses, con
 // reduction as launch_errors_tail — chi2 partials + scale partials -> F-hat, scale, flag, sequence number in pinned memory.
 // The partials are those k_errors would have written (same residual code, same 256-slot blocks, zeros behind them).
 void launch_trial_tail_from_build(hipStream_t s, const cugo_edges& e, ReduceScratch rs, int n_scale_partials,
-                                  double* d_out, const double* d_flag, double* h_out, double seq, unsigned* d_done)
+                                  double* d_out, const double* d_flag, double* h_out, double seq, unsigned* d_done,
+                                  const double* d_icp_chi, int n_icp_chi)
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E > ev.L ? ev.E : ev.L, BS);
     CUGO_LAUNCH(k_sum_partials2, dim3(2), dim3(SP_BS), 0, s, rs.d_partials + spec_chi_offset(ev.E, ev.P, ev.L), nb,
-                rs.d_partials, n_scale_partials, d_out, d_flag, h_out, seq, d_done);
+                rs.d_partials, n_scale_partials, d_out, d_flag, h_out, seq, d_done, d_icp_chi, n_icp_chi);
 }
 
 void launch_max_diagonal(hipStream_t s, const double* d_Hpp, int nP, const double* d_Hll, int nL,

@@ -13,9 +13,12 @@
 // of 28 doubles (21 of the upper triangle of H, 6 of b, chi2) per pose it touches.  Chunk c and pose p meet in at
 // most one partial, and along the sorted edges c and p never decrease and one of them grows at each step from one
 // (chunk, pose) pair to the next: c + p is therefore a unique slot index — no prefix sums, no plan.  The finishing
-// pass sums a pose's partials in chunk order (plane kind, then line kind) and adds them to Hpp / bp; the chi2 total
-// is the sum of the per-pose sums in pose order.  The error pass forms the very same chi2 partials, so its total has
-// the bits of the build pass's.
+// pass sums a pose's partials in chunk order (plane kind, then line kind) and adds them to Hpp / bp or, behind
+// k_pose_schur in the one-stream form of the LM loop, to the pose's diagonal block of Hsc, to bp and to bsc.  Every
+// chunk also leaves ONE chi2 total (its partials in the order it wrote them); the chi2 total of the pass is the sum of
+// the chunk totals — plane chunks, then line chunks: a plain array that the reduction ending an LM trial sums next to
+// the BA partials (ba_kernels.hip: k_sum_partials2).  The error pass forms the very same chunk totals, so its total
+// has the bits of the build pass's.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -45,6 +48,7 @@ struct IcpKind
     const uint8_t* flags;
     Robust rk;
     double* part; // [n_chunks + n_poses_total][ICP_NP]
+    double* cchi; // [n_chunks] chi2 total of every chunk
 };
 
 __device__ __forceinline__ int n_chunks(int n) { return (n + ICP_CHUNK - 1) / ICP_CHUNK; }
@@ -176,9 +180,10 @@ __device__ void icp_chunk(const IcpKind& k, int c, int n_poses_free, const doubl
 #pragma unroll
     for (int i = 0; i < 32; i++)
         acc[i] = 0.0;
-    double chi_acc = 0.0;
+    double chi_acc = 0.0, chunk_chi = 0.0;
     auto flush = [&](int q) {
         const double cs = icp_wave_sum(chi_acc);
+        chunk_chi += cs; // (the same value in every lane)
         double* out = k.part + (size_t)(c + q) * ICP_NP;
         if (FULL)
         {
@@ -232,6 +237,8 @@ __device__ void icp_chunk(const IcpKind& k, int c, int n_poses_free, const doubl
         }
     }
     flush(qcur);
+    if (lane == 0)
+        k.cchi[c] = chunk_chi;
 }
 
 struct IcpArgs
@@ -243,7 +250,7 @@ struct IcpArgs
 };
 
 template <bool FULL>
-__global__ __launch_bounds__(ICP_WG) void k_icp_chunks(IcpArgs a)
+__device__ __forceinline__ void icp_chunks(const IcpArgs& a)
 {
     const int wave = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 6);
     const int cp = n_chunks(a.plane.n), cl = n_chunks(a.line.n);
@@ -251,6 +258,13 @@ __global__ __launch_bounds__(ICP_WG) void k_icp_chunks(IcpArgs a)
         icp_chunk<false, FULL>(a.plane, wave, a.n_poses_free, a.poses, a.edge_chi);
     else if (wave < cp + cl)
         icp_chunk<true, FULL>(a.line, wave - cp, a.n_poses_free, a.poses, a.edge_chi ? a.edge_chi + a.plane.n : nullptr);
+}
+
+__global__ __launch_bounds__(ICP_WG) void k_icp_chunks_build(IcpArgs a) { icp_chunks<true>(a); }
+// (six waves per SIMD, as before the chunk totals: the pass is bound by the loads it has in flight)
+__global__ __launch_bounds__(ICP_WG) __attribute__((amdgpu_waves_per_eu(6))) void k_icp_chunks_errors(IcpArgs a)
+{
+    icp_chunks<false>(a);
 }
 
 // sum of pose p's partials of one kind, element t, in chunk order
@@ -264,32 +278,40 @@ __device__ __forceinline__ double icp_pose_sum(const IcpKind& k, int p, int t)
     return s;
 }
 
-// 32 threads per free pose; thread t < 27 adds element t to Hpp / bp (FULL), thread 27 writes the pose's chi2
-template <bool FULL>
-__global__ __launch_bounds__(ICP_WG) void k_icp_finish(IcpArgs a, double* __restrict__ Hpp, double* __restrict__ bp,
-                                                        double* __restrict__ pchi)
+// 32 threads per free pose that has ICP edges; thread t < 27 adds element t of the pose's sums.  SCHUR = false: to
+// Hpp / bp (behind k_build_poses).  SCHUR = true: to the diagonal block of Hsc (the first block of the pose's row,
+// through rowptr), to bp and to bsc — behind k_pose_schur, which WRITES the three in the one-stream form of the loop
+// (there Hpp is not formed at all; the ICP terms of a pose enter its row of the Schur complement unchanged, as Hpp does)
+template <bool SCHUR>
+__global__ __launch_bounds__(ICP_WG) void k_icp_finish(IcpArgs a, double* __restrict__ H, const int32_t* __restrict__ rowptr,
+                                                        double* __restrict__ bp, double* __restrict__ bsc)
 {
     const int p = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 5), t = threadIdx.x & 31;
-    if (p >= a.n_poses_free || t >= ICP_NP || (!FULL && t != 27))
+    if (p >= a.n_poses_free || t >= 27)
         return;
+    if (a.plane.pose_ptr[p] == a.plane.pose_ptr[p + 1] && a.line.pose_ptr[p] == a.line.pose_ptr[p + 1])
+        return; // (nothing to add: the pose's blocks keep their bits, and its partial slots were never written)
     const double s = icp_pose_sum(a.plane, p, t) + icp_pose_sum(a.line, p, t);
-    if (t == 27)
-        pchi[p] = s;
-    else if (t < 21)
+    if (t < 21)
     {
         int r = 0, k = t;
         while (k >= 6 - r)
             k -= 6 - r, r++;
         const int c = r + k;
-        Hpp[36 * (size_t)p + r + 6 * c] += s;
+        double* blk = H + 36 * (size_t)(SCHUR ? rowptr[p] : p);
+        blk[r + 6 * c] += s;
         if (r != c)
-            Hpp[36 * (size_t)p + c + 6 * r] += s;
+            blk[c + 6 * r] += s;
     }
     else
+    {
         bp[6 * (size_t)p + (t - 21)] += s;
+        if (SCHUR)
+            bsc[6 * (size_t)p + (t - 21)] += s;
+    }
 }
 
-// chi2 total: the per-pose sums in pose order (one workgroup: strided per thread, then the threads in order)
+// chi2 total: the chunk totals in chunk order (one workgroup: strided per thread, then the threads in order)
 __global__ __launch_bounds__(ICP_WG) void k_icp_chi_total(const double* __restrict__ pchi, int n, double* __restrict__ out,
                                                            int add)
 {
@@ -321,53 +343,46 @@ __global__ __launch_bounds__(ICP_WG) void k_icp_check(const int32_t* __restrict_
     }
 }
 
-IcpKind kind_of(const cugo_icp_edges& ev, bool line, double* part)
+// scratch = [plane partials (cp + n_poses_total slots) | line partials (cl + n_poses_total) | chunk totals (cp + cl) | 16]
+struct IcpLayout
+{
+    size_t cp, cl, line_part, cchi, end;
+    explicit IcpLayout(const cugo_icp_edges& ev)
+    {
+        cp = (size_t)(ev.n_plane + ICP_CHUNK - 1) / ICP_CHUNK, cl = (size_t)(ev.n_line + ICP_CHUNK - 1) / ICP_CHUNK;
+        line_part = (cp + ev.n_poses_total) * ICP_NP;
+        cchi = (cp + cl + 2 * (size_t)ev.n_poses_total) * ICP_NP;
+        end = cchi + cp + cl;
+    }
+};
+
+IcpKind kind_of(const cugo_icp_edges& ev, bool line, double* part, double* cchi)
 {
     IcpKind k;
     if (!line)
         k = IcpKind{ev.n_plane, ev.d_plane_pose, ev.d_plane_pose_ptr, ev.d_plane_p, ev.d_plane_nd,
-                    ev.d_plane_omega, ev.n_plane_omega, ev.d_plane_flags, Robust{ev.rk_plane, ev.delta_plane}, part};
+                    ev.d_plane_omega, ev.n_plane_omega, ev.d_plane_flags, Robust{ev.rk_plane, ev.delta_plane}, part, cchi};
     else
         k = IcpKind{ev.n_line, ev.d_line_pose, ev.d_line_pose_ptr, ev.d_line_p, ev.d_line_au,
-                    ev.d_line_omega, ev.n_line_omega, ev.d_line_flags, Robust{ev.rk_line, ev.delta_line}, part};
+                    ev.d_line_omega, ev.n_line_omega, ev.d_line_flags, Robust{ev.rk_line, ev.delta_line}, part, cchi};
     return k;
 }
 
-void launch_icp(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, double* d_Hpp,
-                double* d_bp, cugo_k::ReduceScratch rs, double* d_chi, bool chi_add, double* d_edge_chi)
+IcpArgs args_of(const cugo_icp_edges& ev, const double* d_poses, cugo_k::ReduceScratch rs, double* d_edge_chi)
 {
-    const size_t need = cugo_k::icp_scratch_doubles(ev);
-    if (rs.capacity < need)
+    if (rs.capacity < cugo_k::icp_scratch_doubles(ev))
         throw std::runtime_error("cugo: ICP scratch too small");
-    const int P = ev.n_poses_free;
-    const size_t cp = (size_t)(ev.n_plane + ICP_CHUNK - 1) / ICP_CHUNK, cl = (size_t)(ev.n_line + ICP_CHUNK - 1) / ICP_CHUNK;
+    const IcpLayout lay(ev);
     IcpArgs a;
-    a.plane = kind_of(ev, false, rs.d_partials);
-    a.line = kind_of(ev, true, rs.d_partials + (cp + ev.n_poses_total) * ICP_NP);
-    a.n_poses_free = P;
+    a.plane = kind_of(ev, false, rs.d_partials, rs.d_partials + lay.cchi);
+    a.line = kind_of(ev, true, rs.d_partials + lay.line_part, rs.d_partials + lay.cchi + lay.cp);
+    a.n_poses_free = ev.n_poses_free;
     a.poses = d_poses;
-    a.edge_chi = full ? nullptr : d_edge_chi;
-    double* pchi = rs.d_partials + (cp + cl + 2 * (size_t)ev.n_poses_total) * ICP_NP;
-    const size_t waves = cp + cl;
-    if (waves > 0)
-    {
-        const unsigned grid = (unsigned)((waves * 64 + ICP_WG - 1) / ICP_WG);
-        if (full)
-            CUGO_LAUNCH(k_icp_chunks<true>, dim3(grid), dim3(ICP_WG), 0, s, a);
-        else
-            CUGO_LAUNCH(k_icp_chunks<false>, dim3(grid), dim3(ICP_WG), 0, s, a);
-    }
-    if (P > 0)
-    {
-        const unsigned grid = (unsigned)((32 * (size_t)P + ICP_WG - 1) / ICP_WG);
-        if (full)
-            CUGO_LAUNCH(k_icp_finish<true>, dim3(grid), dim3(ICP_WG), 0, s, a, d_Hpp, d_bp, pchi);
-        else
-            CUGO_LAUNCH(k_icp_finish<false>, dim3(grid), dim3(ICP_WG), 0, s, a, d_Hpp, d_bp, pchi);
-    }
-    if (d_chi)
-        CUGO_LAUNCH(k_icp_chi_total, dim3(1), dim3(ICP_WG), 0, s, pchi, P, d_chi, chi_add ? 1 : 0);
+    a.edge_chi = d_edge_chi;
+    return a;
 }
+
+unsigned finish_grid(const cugo_icp_edges& ev) { return (unsigned)((32 * (size_t)ev.n_poses_free + ICP_WG - 1) / ICP_WG); }
 
 } // namespace
 
@@ -376,18 +391,15 @@ namespace cugo_k
 
 size_t icp_scratch_doubles(const cugo_icp_edges& ev)
 {
-    const size_t cp = (size_t)(ev.n_plane + ICP_CHUNK - 1) / ICP_CHUNK, cl = (size_t)(ev.n_line + ICP_CHUNK - 1) / ICP_CHUNK;
-    return (cp + cl + 2 * (size_t)ev.n_poses_total) * ICP_NP + (size_t)ev.n_poses_free + 16;
+    return IcpLayout(ev).end + 16;
 }
 
 int icp_check_indices(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs)
 {
     if (rs.capacity < icp_scratch_doubles(ev))
         throw std::runtime_error("cugo: ICP scratch too small");
-    // the flag sits in the slack behind the per-pose chi2 of the scratch layout
-    const size_t cp = (size_t)(ev.n_plane + ICP_CHUNK - 1) / ICP_CHUNK, cl = (size_t)(ev.n_line + ICP_CHUNK - 1) / ICP_CHUNK;
-    int* d_bad = reinterpret_cast<int*>(rs.d_partials + (cp + cl + 2 * (size_t)ev.n_poses_total) * ICP_NP +
-                                        (size_t)ev.n_poses_free);
+    // the flag sits in the slack behind the chunk totals of the scratch layout
+    int* d_bad = reinterpret_cast<int*>(rs.d_partials + IcpLayout(ev).end);
     if (hipMemsetAsync(d_bad, 0, sizeof(int), s) != hipSuccess)
         throw std::runtime_error("cugo: hipMemsetAsync failed");
     const struct
@@ -408,16 +420,70 @@ int icp_check_indices(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs)
     return bad;
 }
 
+void launch_icp_chunks(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, ReduceScratch rs,
+                       double* d_edge_chi)
+{
+    const IcpArgs a = args_of(ev, d_poses, rs, full ? nullptr : d_edge_chi);
+    const IcpLayout lay(ev);
+    const size_t waves = lay.cp + lay.cl;
+    if (waves == 0)
+        return;
+    const unsigned grid = (unsigned)((waves * 64 + ICP_WG - 1) / ICP_WG);
+    if (full)
+        CUGO_LAUNCH(k_icp_chunks_build, dim3(grid), dim3(ICP_WG), 0, s, a);
+    else
+        CUGO_LAUNCH(k_icp_chunks_errors, dim3(grid), dim3(ICP_WG), 0, s, a);
+}
+
+void launch_icp_add(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_Hpp, double* d_bp)
+{
+    if (ev.n_poses_free <= 0 || ev.n_plane + ev.n_line == 0)
+        return;
+    const IcpArgs a = args_of(ev, nullptr, rs, nullptr);
+    LaunchScope scope("k_icp_add", s);
+    hipLaunchKernelGGL(k_icp_finish<false>, dim3(finish_grid(ev)), dim3(ICP_WG), 0, s, a, d_Hpp,
+                       (const int32_t*)nullptr, d_bp, (double*)nullptr);
+}
+
+void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, const int32_t* d_rowptr,
+                          double* d_Hsc, double* d_bp, double* d_bsc)
+{
+    if (ev.n_poses_free <= 0 || ev.n_plane + ev.n_line == 0)
+        return;
+    const IcpArgs a = args_of(ev, nullptr, rs, nullptr);
+    LaunchScope scope("k_icp_add_schur", s);
+    hipLaunchKernelGGL(k_icp_finish<true>, dim3(finish_grid(ev)), dim3(ICP_WG), 0, s, a, d_Hsc, d_rowptr, d_bp, d_bsc);
+}
+
+const double* icp_chunk_chi(const cugo_icp_edges& ev, ReduceScratch rs, int* n)
+{
+    const IcpLayout lay(ev);
+    *n = (int)(lay.cp + lay.cl);
+    return rs.d_partials + lay.cchi;
+}
+
+void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_chi, bool chi_add)
+{
+    int n = 0;
+    const double* cchi = icp_chunk_chi(ev, rs, &n);
+    CUGO_LAUNCH(k_icp_chi_total, dim3(1), dim3(ICP_WG), 0, s, cchi, n, d_chi, chi_add ? 1 : 0);
+}
+
 void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
                       ReduceScratch rs, double* d_chi, bool chi_add)
 {
-    launch_icp(s, ev, d_poses, true, d_Hpp, d_bp, rs, d_chi, chi_add, nullptr);
+    launch_icp_chunks(s, ev, d_poses, true, rs);
+    launch_icp_add(s, ev, rs, d_Hpp, d_bp);
+    if (d_chi)
+        launch_icp_chi_total(s, ev, rs, d_chi, chi_add);
 }
 
 void launch_icp_errors(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, ReduceScratch rs, double* d_chi,
                        bool chi_add, double* d_edge_chi)
 {
-    launch_icp(s, ev, d_poses, false, nullptr, nullptr, rs, d_chi, chi_add, d_edge_chi);
+    launch_icp_chunks(s, ev, d_poses, false, rs, d_edge_chi);
+    if (d_chi)
+        launch_icp_chi_total(s, ev, rs, d_chi, chi_add);
 }
 
 } // namespace cugo_k

@@ -71,8 +71,11 @@ void launch_build(hipStream_t s, const cugo_edges& ev, const double* d_poses, co
                   bool chi_behind_scale = false);
 
 // the reductions that end a trial, with the chi2 partials of a build pass queued with chi_behind_scale (ba_kernels.hip)
+// d_icp_chi / n_icp_chi (both tails): chi2 totals of the chunks of an ICP pass at the trial's estimates (icp_chunk_chi),
+// summed in their order and added to F-hat by the same launch; nullptr / 0: no such edges
 void launch_trial_tail_from_build(hipStream_t s, const cugo_edges& ev, ReduceScratch rs, int n_scale_partials,
-                                  double* d_out, const double* d_flag, double* h_out, double seq, unsigned* d_done);
+                                  double* d_out, const double* d_flag, double* h_out, double seq, unsigned* d_done,
+                                  const double* d_icp_chi = nullptr, int n_icp_chi = 0);
 
 void launch_max_diagonal(hipStream_t s, const double* d_Hpp, int nP, const double* d_Hll, int nL,
                          ReduceScratch rs, double* d_out);
@@ -129,12 +132,13 @@ int launch_backsubst_update(hipStream_t s, const cugo_edges& ev, double lambda, 
 // null) receives {chi2, scale, the 8 bytes at d_flag}: readable after the stream has been waited for
 void launch_errors_tail(hipStream_t s, const cugo_edges& ev, const double* d_poses, const double* d_lms,
                         cugo_robust rk, ReduceScratch rs, int n_scale_partials, double* d_out,
-                        const double* d_flag, double* h_out, double seq, unsigned* d_done);
+                        const double* d_flag, double* h_out, double seq, unsigned* d_done,
+                        const double* d_icp_chi = nullptr, int n_icp_chi = 0);
 
 size_t reduce_scratch_doubles(int n_edges, int n_poses, int n_landmarks);
 
 // --- point-to-plane / point-to-line pose edges (icp_kernels.hip) -------------------------
-// scratch both launchers need (chunk partials + per-pose chi2)
+// scratch the launchers need (chunk partials + one chi2 total per chunk)
 size_t icp_scratch_doubles(const cugo_icp_edges& ev);
 // with pose_ptr known to ascend from 0 to n per kind: 1 if an edge does not lie in its pose's pose_ptr range (the
 // edges are not sorted by pose, or a pose index is out of range), else 0.  Synchronises the stream.
@@ -145,6 +149,22 @@ void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_p
 // chi2 only (the same bits as launch_icp_build's); d_edge_chi: per edge, plane edges first, or nullptr
 void launch_icp_errors(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, ReduceScratch rs, double* d_chi,
                        bool chi_add = false, double* d_edge_chi = nullptr);
+// The pieces of the two above, for the LM loop (engine.cpp), which places them itself:
+// the chunk pass alone — full: the partials of H, b and chi2 of every (chunk, pose) pair; otherwise chi2 only — leaves
+// its partials and the chi2 total of every chunk in the scratch
+void launch_icp_chunks(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, ReduceScratch rs,
+                       double* d_edge_chi = nullptr);
+// the per-pose sums of a full chunk pass ADDED to d_Hpp / d_bp (behind k_build_poses) ...
+void launch_icp_add(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_Hpp, double* d_bp);
+// ... or to the diagonal blocks of d_Hsc (upper block CSR d_rowptr: the first block of a row), d_bp and d_bsc (behind
+// k_pose_schur, which writes the three in the one-stream form)
+void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, const int32_t* d_rowptr,
+                          double* d_Hsc, double* d_bp, double* d_bsc);
+// the chunk totals of the last chunk pass (plane chunks, then line chunks): what launch_errors_tail /
+// launch_trial_tail_from_build sum into F-hat
+const double* icp_chunk_chi(const cugo_icp_edges& ev, ReduceScratch rs, int* n);
+// their sum to d_chi[0] (added to what is there with chi_add), in a launch of its own
+void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_chi, bool chi_add);
 
 // chi_e per edge slot (outlier rejection, ref: computeOutliersKernel cuda_block_solver.cu:1135)
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,

@@ -137,6 +137,8 @@ public:
     void exchangeStats(double& bytes, int& calls) const;
     const std::vector<LmTrace>& lmTrace() const { return trace_; }
     int nActiveEdges() const;
+    /** active point-to-plane (kind 0) / point-to-line (kind 1) edges of the current flattening (icp_types.h) */
+    int nIcpEdges(int kind) const;
     /** B, M, nnz(L), flops, supernodes, stages, front bytes, off-diagonal products, then per
      *  factorisation: potrf / trsm / syrk flops, extend-add bytes, backward bytes */
     std::vector<double> structureStats() const;

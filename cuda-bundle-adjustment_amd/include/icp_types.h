@@ -3,9 +3,12 @@
 // y = R(q) pointP + t, the residuals are
 //   plane: n . y - originDistance                 (scalar; dim() = 1 as in the reference)
 //   line:  (I - u u^T)(y - a), u = (b - a) / |b - a|  (its length is the distance to the line)
-// The residuals, their Jacobians for the left update and the device kernels are in csrc/kernels/icp_kernels.hip and
-// are reached through the kernel-level C ABI (include/cugo_hip.h: cugo_icp_edges, cugo_icp_compute_errors,
-// cugo_icp_construct_quadratic_form).  The sets are plain containers, like the BA sets (ba_types.h).
+// The residuals, their Jacobians for the left update and the device kernels are in csrc/kernels/icp_kernels.hip.
+// The sets are plain containers, like the BA sets (ba_types.h): add them to the optimiser with addEdgeSet(), next to
+// (or instead of) mono / stereo sets; initialize() checks every active edge (finite values, unit normal, a != b, a pose
+// of one of the optimiser's pose sets) and optimize() minimises the joint cost.  The same terms are also reachable
+// through the kernel-level C ABI (include/cugo_hip.h: cugo_icp_edges, cugo_icp_compute_errors,
+// cugo_icp_construct_quadratic_form).
 #pragma once
 #include "measurements.h"
 #include "optimisable_graph.h"

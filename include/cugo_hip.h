@@ -322,6 +322,26 @@ int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids,
 int cugo_graph_set_camera(cugo_graph* g, int dim, const double* cam5);
 int cugo_graph_set_information(cugo_graph* g, int dim, double info);
 int cugo_graph_set_robust_kernel(cugo_graph* g, int dim, int type, double delta);
+/* Point-to-plane / point-to-line pose edges (the reference's PlaneEdgeSet / LineEdgeSet, include/icp_types.h), next to
+ * or instead of the BA edges; residuals and conventions as for cugo_icp_edges above.  pointP [n][3]; plane: unit normal
+ * [n][3] (used as given) and origin_distance [n]; line: two distinct points a, b [n][3]; info [n] or NULL (the set's
+ * value).  pose_ids must be ids given to cugo_graph_add_poses.  cugo_graph_initialize() refuses non-finite values, a
+ * normal whose length differs from 1 by more than 1e-6, a == b, an outlier threshold on these sets and a sharded
+ * optimiser; edges on fixed poses count for nothing.  The existing setters select a set by dim, which cannot tell the
+ * two kinds apart (both are 1-d): the two setters below take the kind. */
+#define CUGO_ICP_PLANE 0
+#define CUGO_ICP_LINE 1
+int cugo_graph_add_plane_edges(cugo_graph* g, int n, const int32_t* pose_ids, const double* pointP,
+                               const double* normal, const double* origin_distance, const double* info);
+int cugo_graph_add_line_edges(cugo_graph* g, int n, const int32_t* pose_ids, const double* pointP, const double* a,
+                              const double* b, const double* info);
+int cugo_graph_set_icp_information(cugo_graph* g, int kind, double info);
+int cugo_graph_set_icp_robust_kernel(cugo_graph* g, int kind, int type, double delta);
+/* outlier threshold of an ICP set (ref: EdgeSet::setOutlierThreshold).  Only 0 is usable for now: with a positive
+ * value cugo_graph_initialize() refuses the graph */
+int cugo_graph_set_icp_outlier_threshold(cugo_graph* g, int kind, double threshold);
+/* active edges of the kind in the current flattening (edges on fixed poses are not counted); -1: unknown kind */
+int cugo_graph_n_icp_edges(cugo_graph* g, int kind);
 /* multi-GPU: this process handles shard `rank` of `world` (landmark ranges).  exchange() is
  * called on the host with a DEVICE buffer that must be all-reduced in place over all ranks
  * (op 0 = sum, 1 = max) before it returns, or — op >= 2 — overwritten on every rank with rank
