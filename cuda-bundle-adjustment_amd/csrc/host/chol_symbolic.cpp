@@ -12,9 +12,11 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <numeric>
 #include <stdexcept>
 #include <thread>
+#include <tuple>
 
 namespace cugo_host
 {
@@ -42,6 +44,8 @@ CholOptions CholOptions::from_env()
         o.xcd_affinity = std::atoi(s) != 0;
     if (const char* s = std::getenv("CUGO_TILE32_MAX_TILES"))
         o.tile32_max_tiles = std::max(0, std::atoi(s));
+    if (const char* s = std::getenv("CUGO_ND_REFINE"))
+        o.nd_refine = std::min(2, std::max(0, std::atoi(s)));
     return o;
 }
 
@@ -100,7 +104,219 @@ struct ND
     };
     std::vector<NodeState> st;
     std::atomic<int> next_id{1};
-    ND(const Graph& g_, const CholOptions& o) : g(g_), opt(o), st(g_.n, NodeState{0, -1}) {}
+    const bool refine;                    // separators are refined by a minimum vertex cut (refine_split)
+    std::atomic<bool> refined_any{false}; // ... and one of them was replaced
+    std::vector<int> loc;                 // node -> its index in the flow network of its set (own nodes only, like st)
+    ND(const Graph& g_, const CholOptions& o, bool refine_)
+        : g(g_), opt(o), st(g_.n, NodeState{0, -1}), refine(refine_), loc(refine_ ? g_.n : 0)
+    {
+    }
+
+    // Maximum number of node-disjoint paths through the window graph of refine_split (Dinic, iterative): unit-capacity
+    // flow on the node-split graph, which is never built — vertex 2i is the entry of window node i, 2i+1 its exit,
+    // 2k the source, 2k+1 the sink, and the residual edges follow from the window's adjacency and, per node, whether
+    // a path holds it (`used`) and which node precedes it there (`pred`, -1: the source).  The buffers live as long
+    // as a thread's share of the recursion (one Scratch per thread).
+    struct Scratch
+    {
+        int k = 0;
+        std::vector<int> win, wptr, wadj; // window nodes; their neighbours inside the window (indices into win)
+        std::vector<int> srcs;            // window nodes with a neighbour on the source side
+        std::vector<char> to_snk, used;   // ... with one on the sink side; held by a path
+        std::vector<int> pred, lvl, it, queue, path;
+        // the residual edges of vertex v, one per call: position j moves on, -1 = no more
+        int next(int v, int& j) const
+        {
+            if (v >= 2 * k)
+                return v == 2 * k && j < (int)srcs.size() ? 2 * srcs[j++] : -1;
+            const int i = v >> 1;
+            if (!(v & 1)) // entry: through the node if it is free, else back along the path that holds it
+                return j++ > 0 ? -1 : !used[i] ? v + 1 : pred[i] >= 0 ? 2 * pred[i] + 1 : -1;
+            const int d = wptr[i + 1] - wptr[i];
+            if (j < d)
+                return 2 * wadj[wptr[i] + j++];
+            if (j == d && ++j && used[i])
+                return v - 1; // give the node up
+            if (j == d + 1 && ++j && to_snk[i])
+                return 2 * k + 1;
+            return -1;
+        }
+        // levels of the residual graph from the source, as far as the sink's level if it is reached (true).  After a
+        // false return lvl >= 0 marks the source side of a minimum cut.
+        bool levels()
+        {
+            const int s = 2 * k, t = 2 * k + 1;
+            lvl.assign(2 * k + 2, -1);
+            queue.clear();
+            queue.push_back(s);
+            lvl[s] = 0;
+            for (size_t h = 0; h < queue.size(); h++)
+            {
+                const int v = queue[h];
+                if (lvl[t] >= 0 && lvl[v] >= lvl[t])
+                    break;
+                int j = 0;
+                for (int u; (u = next(v, j)) != -1;)
+                    if (lvl[u] < 0)
+                    {
+                        lvl[u] = lvl[v] + 1;
+                        queue.push_back(u);
+                    }
+            }
+            return lvl[t] >= 0;
+        }
+        // stops at `limit` paths
+        int max_flow(int limit)
+        {
+            const int s = 2 * k, t = 2 * k + 1;
+            used.assign(k, 0);
+            pred.assign(k, -1);
+            int flow = 0;
+            while (flow < limit && levels())
+            {
+                it.assign(2 * k + 2, 0);
+                for (;;)
+                {
+                    path.clear();
+                    path.push_back(s);
+                    while (!path.empty() && path.back() != t)
+                    {
+                        const int v = path.back();
+                        int u;
+                        for (;;)
+                        { // it[v] stays AT an edge that was taken: its capacity may be unbounded
+                            int j = it[v];
+                            u = next(v, j);
+                            if (u == -1 || lvl[u] == lvl[v] + 1)
+                                break;
+                            it[v] = j;
+                        }
+                        if (u != -1)
+                            path.push_back(u);
+                        else
+                        {
+                            lvl[v] = -1; // dead end: out of this phase
+                            path.pop_back();
+                        }
+                    }
+                    if (path.empty())
+                        break;
+                    for (size_t q = 0; q + 2 < path.size(); q++) // (the last edge, exit -> sink, keeps no record)
+                    {
+                        const int a = path[q], b = path[q + 1];
+                        if (a == s)
+                            pred[b >> 1] = -1;
+                        else if (!(a & 1))
+                        {
+                            if (b == a + 1)
+                                used[a >> 1] = 1; // (else: back along the old path, whose record the new one replaces)
+                        }
+                        else if (b == a - 1)
+                            used[a >> 1] = 0;
+                        else
+                            pred[b >> 1] = a >> 1;
+                    }
+                    if (++flow >= limit)
+                        return flow;
+                }
+            }
+            return flow;
+        }
+    };
+
+    // Separator refinement.  The level separator S (level m, thinned from one side) of the connected set `comp`
+    // (BFS order, levels 0..h in st) is replaced by a minimum vertex cut between the levels <= m-2 and the levels
+    // >= m+2 (clamped so that level 0 stays on the one side and level h on the other): every node of the levels in
+    // between has capacity 1, every edge is unbounded, and the cut is the set of saturated nodes on the boundary of
+    // what the source still reaches in the residual graph.  The network holds the window only — a few hundred
+    // nodes — and the flow is at most |S|.  A is what the start node reaches without the cut, B the rest.  The
+    // old split stays if the cut is not smaller than S or a side falls below a quarter of the set.  (Windows of
+    // +-1 and +-3 levels, accepting only cuts that save a 16-column front, and trying the three best levels were
+    // all measured worse on the kitti_00 and 10k-pose shapes.)  Deterministic: it depends on comp's order alone.
+    bool refine_split(int id, int m, int h, const std::vector<int>& comp, std::vector<int>& A, std::vector<int>& B,
+                      std::vector<int>& S, Scratch& f)
+    {
+        const int lo = std::max(0, m - 2), hi = std::min(h, m + 2); // source: levels <= lo, sink: levels >= hi
+        f.win.clear();
+        for (int v : comp)
+            if (st[v].level > lo && st[v].level < hi)
+            {
+                loc[v] = (int)f.win.size();
+                f.win.push_back(v);
+            }
+        const int k = f.k = (int)f.win.size();
+        f.wptr.assign(1, 0), f.wadj.clear(), f.srcs.clear(), f.to_snk.assign(k, 0);
+        for (int i = 0; i < k; i++)
+        {
+            const int v = f.win[i];
+            bool from_src = false;
+            for (int e = g.ptr[v]; e < g.ptr[v + 1]; e++)
+            {
+                const int u = g.adj[e];
+                if (sid(u) != id)
+                    continue;
+                if (st[u].level <= lo)
+                    from_src = true;
+                else if (st[u].level >= hi)
+                    f.to_snk[i] = 1;
+                else
+                    f.wadj.push_back(loc[u]);
+            }
+            f.wptr.push_back((int)f.wadj.size());
+            if (from_src)
+                f.srcs.push_back(i);
+        }
+        const int old = (int)S.size();
+        const int flow = f.max_flow(old);
+        if (flow >= old)
+            return false; // (otherwise the search that found no further path has left the source side in f.lvl)
+        // The levels <= lo hang together through their BFS parents and hold no cut node, so what the start node
+        // reaches without the cut is all of them plus what they reach inside the window.  From here on the levels
+        // of the window are given up: -2 = in the cut, -3 = reached.
+        int ncut = 0;
+        for (int i = 0; i < k; i++)
+            if (f.lvl[2 * i] >= 0 && f.lvl[2 * i + 1] < 0)
+            {
+                st[f.win[i]].level = -2;
+                ncut++;
+            }
+        f.queue.clear();
+        for (int i : f.srcs)
+            if (st[f.win[i]].level != -2)
+            {
+                st[f.win[i]].level = -3;
+                f.queue.push_back(f.win[i]);
+            }
+        if (ncut != flow)
+            throw std::runtime_error("cugo: ordering: the vertex cut does not match the flow");
+        for (size_t q = 0; q < f.queue.size(); q++)
+        {
+            const int v = f.queue[q];
+            for (int e = g.ptr[v]; e < g.ptr[v + 1]; e++)
+            {
+                const int u = g.adj[e];
+                if (sid(u) == id && st[u].level > lo)
+                {
+                    st[u].level = -3;
+                    f.queue.push_back(u);
+                }
+            }
+        }
+        int na = (int)f.queue.size();
+        for (int v : comp)
+            if (st[v].level >= 0 && st[v].level <= lo)
+            {
+                st[v].level = -3;
+                na++;
+            }
+        const int total = (int)comp.size(), nb = total - na - ncut;
+        if (4 * std::min(na, nb) < total)
+            return false;
+        A.clear(), B.clear(), S.clear();
+        for (int v : comp)
+            (st[v].level == -3 ? A : st[v].level == -2 ? S : B).push_back(v);
+        return true;
+    }
     int sid(int v) const { return __atomic_load_n(&st[v].sid, __ATOMIC_RELAXED); }
     void set_sid(int v, int id) { __atomic_store_n(&st[v].sid, id, __ATOMIC_RELAXED); }
 
@@ -204,7 +420,7 @@ struct ND
     // appends the ordering of `nodes` to `order`; depth < kParallelDepth: the two halves run on
     // two threads (the result does not depend on it: A's order, then B's, then the separator)
     const int kParallelDepth = std::getenv("CUGO_ND_PAR") ? std::atoi(std::getenv("CUGO_ND_PAR")) : 4; // 0: one thread
-    void run(std::vector<int> nodes, std::vector<int>& order, int depth = 0)
+    void run(std::vector<int> nodes, std::vector<int>& order, Scratch& scratch, int depth = 0)
     {
         if ((int)nodes.size() <= opt.nd_leaf)
         {
@@ -231,7 +447,7 @@ struct ND
                     comps.push_back(comp);
                 }
             for (auto& c : comps)
-                run(c, order, depth + 1);
+                run(c, order, scratch, depth + 1);
             return;
         }
         // pseudo-peripheral start: repeat BFS from the last-visited node
@@ -300,6 +516,8 @@ struct ND
                 (touches_B ? S : A).push_back(v);
             }
         }
+        if (refine && refine_split(id, best, h, comp, A, B, S, scratch))
+            refined_any.store(true);
         // (a thread costs ~30 us to start; a half of 150+ nodes of a graph this dense — ~50 neighbours per pose —
         // takes longer than that to dissect: the kitti_00 shape, 1 322 poses, orders in 0.5 instead of 1.2 ms)
         if (depth < kParallelDepth && A.size() + B.size() > 300)
@@ -309,14 +527,15 @@ struct ND
             std::thread tb([&] {
                 try
                 {
-                    run(std::move(B), orderB, depth + 1);
+                    Scratch scratchB;
+                    run(std::move(B), orderB, scratchB, depth + 1);
                 }
                 catch (...)
                 {
                     err = std::current_exception();
                 }
             });
-            run(std::move(A), order, depth + 1);
+            run(std::move(A), order, scratch, depth + 1);
             tb.join();
             if (err)
                 std::rethrow_exception(err);
@@ -324,8 +543,8 @@ struct ND
         }
         else
         {
-            run(std::move(A), order, depth + 1);
-            run(std::move(B), order, depth + 1);
+            run(std::move(A), order, scratch, depth + 1);
+            run(std::move(B), order, scratch, depth + 1);
         }
         for (int v : S)
             order.push_back(v);
@@ -334,43 +553,39 @@ struct ND
 
 } // namespace
 
-void chol_analyze(int n, const int32_t* rowptr, const int32_t* colind, const CholOptions& opt,
-                  CholPlan& P)
+namespace
 {
-    // CUGO_INIT_TIMING=1: per-phase host times on stderr (diagnosis only)
-    const bool timing = std::getenv("CUGO_INIT_TIMING") != nullptr;
-    auto lap_t = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing)
-            return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[cugo symbolic] %-26s %8.3f ms\n", what,
-                     std::chrono::duration<double, std::milli>(now - lap_t).count());
-        lap_t = now;
-    };
+
+using Lap = std::function<void(const char*)>;
+
+// the ordering of the whole graph; `changed`: some separator was replaced by a smaller vertex cut
+std::vector<int> nd_order(const Graph& g, const CholOptions& opt, bool refine, bool* changed)
+{
+    ND nd(g, opt, refine);
+    std::vector<int> all(g.n), perm;
+    std::iota(all.begin(), all.end(), 0);
+    perm.reserve(g.n);
+    ND::Scratch scratch;
+    nd.run(std::move(all), perm, scratch);
+    if ((int)perm.size() != g.n)
+        throw std::runtime_error("cugo: ordering lost nodes");
+    if (changed)
+        *changed = nd.refined_any.load();
+    return perm;
+}
+
+// steps 2 - 7 of the analysis for one ordering: everything up to the stage schedule (`lower`: the fronts of the
+// subtree stage, which step 8 needs)
+void symbolic_schedule(const Graph& g, const int32_t* rowptr, const int32_t* colind, const CholOptions& opt,
+                       std::vector<int> perm, CholPlan& P, std::vector<char>& lower, const Lap& lap)
+{
+    const int n = g.n;
     P = CholPlan();
     P.n = n;
-    if (n == 0)
-        return;
-    const Graph g = build_graph(n, rowptr, colind);
-    lap("0 adjacency graph");
-
-    // ---- 1. fill-reducing, parallelism-exposing ordering --------------------------------
-    std::vector<int> perm;
-    {
-        ND nd(g, opt);
-        std::vector<int> all(n);
-        std::iota(all.begin(), all.end(), 0);
-        perm.reserve(n);
-        nd.run(std::move(all), perm);
-        if ((int)perm.size() != n)
-            throw std::runtime_error("cugo: ordering lost nodes");
-    }
     std::vector<int> iperm(n);
     for (int i = 0; i < n; i++)
         iperm[perm[i]] = i;
 
-    lap("1 ordering");
     // ---- 2. elimination tree (Liu, path compression) + postorder -----------------------
     auto etree = [&](const std::vector<int>& ip, const std::vector<int>& pm, std::vector<int>& parent) {
         parent.assign(n, -1);
@@ -769,7 +984,7 @@ void chol_analyze(int n, const int32_t* rowptr, const int32_t* colind, const Cho
         total += work[s];
     const double wtask = total / std::max(1, opt.target_tasks);
     // a front is "lower" if its subtree fits in one task
-    std::vector<char> lower(ns);
+    lower.resize(ns);
     for (int s = 0; s < ns; s++)
         lower[s] = sub[s] <= wtask;
     {
@@ -980,7 +1195,101 @@ void chol_analyze(int n, const int32_t* rowptr, const int32_t* colind, const Cho
         if (lower[s])
             P.has_subtree_stage = true;
 
+    // what the device pays for along the chain of stages: per stage, the 16-column potrf slots
+    // of its widest front — over ALL fronts of the level, so that every rank of a sharded run gets the same figure
+    {
+        std::vector<int> widest(P.n_stages, 0);
+        for (int s = 0; s < ns; s++)
+            widest[stage_of[s]] = std::max(widest[stage_of[s]], (6 * P.ncb[s] + 15) / 16);
+        P.sum_slots = std::accumulate(widest.begin(), widest.end(), 0);
+    }
     lap("7 schedule");
+}
+
+} // namespace
+
+void chol_analyze(int n, const int32_t* rowptr, const int32_t* colind, const CholOptions& opt,
+                  CholPlan& P)
+{
+    // CUGO_INIT_TIMING=1: per-phase host times on stderr (diagnosis only)
+    const bool timing = std::getenv("CUGO_INIT_TIMING") != nullptr;
+    auto lap_t = std::chrono::steady_clock::now();
+    const Lap lap = [&](const char* what) {
+        if (!timing)
+            return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[cugo symbolic] %-26s %8.3f ms\n", what,
+                     std::chrono::duration<double, std::milli>(now - lap_t).count());
+        lap_t = now;
+    };
+    P = CholPlan();
+    P.n = n;
+    if (n == 0)
+        return;
+    const Graph g = build_graph(n, rowptr, colind);
+    lap("0 adjacency graph");
+
+    // ---- 1. fill-reducing, parallelism-exposing ordering; 2 - 7: the plan up to its stage schedule --------------
+    // With separator refinement (ND::refine_split) the plan of the refined ordering is kept only if it is the better
+    // one by what the kernels pay for: (stages, potrf slots along the chain, flops), compared in that order.  A
+    // smaller separator usually gives fewer slots and flops, but the levels of the tree come out of the supernode
+    // amalgamation and now and then a stage is added (a 248-pose graph: 9 -> 10).  The unrefined candidate is
+    // analysed on a second thread meanwhile, so the choice costs the call little more than the flow computations.
+    std::vector<char> lower;
+    if (!opt.nd_refine || n <= opt.nd_leaf)
+    {
+        std::vector<int> perm = nd_order(g, opt, false, nullptr);
+        lap("1 ordering");
+        symbolic_schedule(g, rowptr, colind, opt, std::move(perm), P, lower, lap);
+    }
+    else
+    {
+        const bool guard = opt.nd_refine == 1;
+        CholPlan P0;
+        std::vector<char> lower0;
+        std::exception_ptr err;
+        std::thread t0;
+        if (guard)
+            t0 = std::thread([&] {
+                try
+                {
+                    symbolic_schedule(g, rowptr, colind, opt, nd_order(g, opt, false, nullptr), P0, lower0, [](const char*) {});
+                }
+                catch (...)
+                {
+                    err = std::current_exception();
+                }
+            });
+        bool changed = false;
+        try
+        {
+            std::vector<int> perm = nd_order(g, opt, true, &changed);
+            lap("1 ordering");
+            symbolic_schedule(g, rowptr, colind, opt, std::move(perm), P, lower, lap);
+        }
+        catch (...)
+        {
+            if (guard)
+                t0.join();
+            throw;
+        }
+        P.nd_refined = changed;
+        if (guard)
+        {
+            t0.join();
+            if (err)
+                std::rethrow_exception(err);
+            lap("7b unrefined plan (wait)");
+            const auto cost = [](const CholPlan& p) { return std::make_tuple(p.n_stages, p.sum_slots, p.flops); };
+            if (!changed || !(cost(P) < cost(P0)))
+            {
+                P = std::move(P0);
+                lower = std::move(lower0);
+            }
+        }
+    }
+    const int ns = P.n_super;
+    auto mine = [&](int s) { return P.owner[s] < 0 || P.owner[s] == opt.rank; };
     // ---- 8. work items of the batched upper-stage kernels ------------------------------
     P.nc_max = 6;
     for (int s = 0; s < ns; s++)

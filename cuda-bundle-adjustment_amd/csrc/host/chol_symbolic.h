@@ -9,6 +9,10 @@ namespace cugo_host
 
 struct CholOptions
 {
+    // nested dissection: every level separator is refined to a minimum vertex cut of the five BFS levels around it, and
+    // the refined ordering is used if its plan has fewer (stages, potrf slots, flops) — DESIGN.md section 5;
+    // CUGO_ND_REFINE=0: the level separators alone; 2: the refined ordering whatever its plan (tests, sweeps)
+    int nd_refine = 1;
     int nd_leaf = 96;        // nested dissection stops below this many block nodes (swept on MI355X: tools/sweep_ordering.sh)
     int max_super_cols = 16; // relaxed supernodes: at most this many block columns
     double zero_frac = 0.35; // relaxed supernodes: tolerated share of explicit zero blocks
@@ -64,6 +68,8 @@ struct CholPlan
     std::vector<int32_t> col_front;      // new column -> supernode
 
     int n_stages = 0;
+    int sum_slots = 0;  // sum over the stages of the 16-column potrf slots of the stage's widest front (all ranks' fronts)
+    int nd_refined = 0; // 1: the ordering with the refined separators won (CholOptions::nd_refine)
     std::vector<int32_t> stage_task_ptr; // [n_stages+1]
     std::vector<int32_t> task_ptr, task_fronts;
     bool has_subtree_stage = false; // stage 0 = multi-front subtree tasks (one workgroup each)
