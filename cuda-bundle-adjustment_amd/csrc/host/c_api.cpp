@@ -411,6 +411,9 @@ int cugo_chol_plan_array(cugo_chol* s, const char* name, const int32_t** out)
     CUGO_PLAN_FIELD(alias_of);
     CUGO_PLAN_FIELD(asm_map);
     CUGO_PLAN_FIELD(wl);
+    CUGO_PLAN_FIELD(bc_front);
+    CUGO_PLAN_FIELD(bc_seg_ptr);
+    CUGO_PLAN_FIELD(bc_seg);
 #undef CUGO_PLAN_FIELD
     if (n == "asm_info")
     { // [first assembly item in wl, items, then per front: offset of its map in asm_map or -1]

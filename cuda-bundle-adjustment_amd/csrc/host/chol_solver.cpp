@@ -123,6 +123,20 @@ void cugo_chol::pack()
         }
     }
     const size_t o_fat = put32(fat);
+    // the backward pass in one launch (kernels.h: CholPlanDev::bc_rec / bc_seg): one 64-byte record per ticket
+    std::vector<int32_t> bc_rec(cugo_k::BC_REC * P.bc_front.size(), 0), bc_seg(4 * (P.bc_seg.size() / 3) + 4, 0);
+    for (size_t t = 0; t < P.bc_front.size(); t++)
+    {
+        int32_t* m = bc_rec.data() + cugo_k::BC_REC * t;
+        const int f = P.bc_front[t];
+        m[0] = f, m[1] = P.ncb[f], m[2] = P.nb[f], m[3] = P.col0[f], m[4] = P.rows_ptr[f];
+        m[5] = P.bc_seg_ptr[f], m[6] = P.bc_seg_ptr[f + 1] - P.bc_seg_ptr[f];
+        const int64_t q[4] = {P.woff[f], P.l21off[f], P.off[f], P.ldf[f]};
+        std::memcpy(m + 8, q, sizeof q);
+    }
+    for (size_t k = 0; k < P.bc_seg.size() / 3; k++)
+        std::memcpy(bc_seg.data() + 4 * k, P.bc_seg.data() + 3 * k, 3 * sizeof(int32_t));
+    const size_t o_bc_rec = put32(bc_rec), o_bc_seg = put32(bc_seg);
     const size_t o_asm_map = put32(P.asm_map);
     const size_t o_trans = pack32.size(); // bytes
     pack32.resize(o_trans + (P.blk_trans.size() + 3) / 4 + 4, 0);
@@ -132,7 +146,7 @@ void cugo_chol::pack()
     const size_t o_off = put64(P.off), o_woff = put64(P.woff), o_l21off = put64(P.l21off), o_ldf = put64(P.ldf);
     po = {o_ncb, o_nb, o_col0, o_alias, o_bwnp, o_lanp, o_rows_ptr, o_rows, o_child_ptr, o_child, o_rel_ptr, o_rel,
           o_task_ptr, o_task_fronts, o_blk_front, o_blk_row, o_blk_col, o_perm, o_col_front, o_wl, o_ea1, o_tmeta,
-          o_fat, o_asm_map, o_trans, o_asm_off, o_off, o_woff, o_l21off, o_ldf};
+          o_fat, o_asm_map, o_trans, o_asm_off, o_off, o_woff, o_l21off, o_ldf, o_bc_rec, o_bc_seg};
 }
 
 void cugo_chol::upload(hipStream_t s)
@@ -144,6 +158,7 @@ void cugo_chol::upload(hipStream_t s)
     const size_t o_blk_col = po[16], o_perm = po[17], o_col_front = po[18], o_wl = po[19], o_ea1 = po[20];
     const size_t o_tmeta = po[21], o_fat = po[22], o_asm_map = po[23], o_trans = po[24], o_asm_off = po[25];
     const size_t o_off = po[26], o_woff = po[27], o_l21off = po[28], o_ldf = po[29];
+    const size_t o_bc_rec = po[30], o_bc_seg = po[31];
     d_pack32.upload(pack32, s), d_pack64.upload(pack64, s);
     d_fronts.resize((size_t)P.front_doubles + 16);
     d_fronts.zero(s); // once: afterwards only the lower triangles are cleared (k_clear_fronts)
@@ -151,6 +166,20 @@ void cugo_chol::upload(hipStream_t s)
     d_junk.resize(64 * 1024);
     d_winv.resize((size_t)P.winv_doubles + 16);
     d_l21.resize((size_t)P.l21_doubles + 16);
+    // the backward pass in one launch: where the plan allows it (every task one front: no subtree stage; no
+    // look-ahead schedule), unless CUGO_BW_CHAIN=0.  A plan with rank-owned subtrees takes it too — the list holds
+    // this rank's fronts, and all their ancestors are among them —: the owned form under a one-rank communicator
+    // must give the bits of the plain run.  Its words — ticket head, abort, error, one done word per front — are
+    // zeroed here, once; the calls then count on from there
+    bw_chain = opt.bw_chain && !opt.lookahead && !P.has_subtree_stage && !P.bc_front.empty();
+    if (bw_chain)
+    {
+        d_bc_state.resize((size_t)cugo_k::BC_DONE + P.n_super);
+        d_bc_state.zero(s);
+        h_bc_error.resize(1);
+        h_bc_error[0] = 0;
+        bc_base = 0, bc_epoch = 0;
+    }
     CUGO_HIP(hipStreamSynchronize(s)); // host vectors may be reused after return
 
     cugo_k::CholPlanDev& D = dev;
@@ -186,6 +215,7 @@ void cugo_chol::upload(hipStream_t s)
     d_wl_ptr = b32 + o_wl;
     D.wl_base = d_wl_ptr, D.fat = b32 + o_fat, D.ea1 = b32 + o_ea1;
     D.asm_map = b32 + o_asm_map, D.asm_off = b64 + o_asm_off;
+    D.bc_rec = b32 + o_bc_rec, D.bc_seg = b32 + o_bc_seg;
     asm_fronts = opt.asm_fronts; // (CUGO_ASM_FRONTS=0: clear + scatter, two launches)
     lds_factor = cugo_k::chol_lds_factor_bytes(P.nc_max);
     lds_backward = cugo_k::chol_lds_backward_bytes(P.nc_max, P.ld_max);
@@ -417,6 +447,7 @@ void cugo_chol::factor_solve(const double* d_Hsc, double lambda, const double* d
                              int32_t* d_fail)
 {
     hipStream_t s = ctx->stream;
+    check_chain_error();
     factored = true, last_fail = d_fail;
 #ifdef CUGO_DEBUG_HOOKS
     cugo_chol_hooks hooks(*this);
@@ -496,7 +527,53 @@ void cugo_chol::factor_solve(const double* d_Hsc, double lambda, const double* d
     CUGO_HOOK(hooks.hash(12, d_winv.data(), (size_t)plan.winv_doubles));
     CUGO_HOOK(hooks.hash(13, d_l21.data(), (size_t)plan.l21_doubles));
     CUGO_HOOK(hooks.hash(14, d_fronts.data(), (size_t)plan.front_doubles));
-    for (int st = plan.n_stages - 1; st >= 0; st--)
+    if (bw_chain)
+    { // one launch: a workgroup per front, x handed from front to front inside it (k_backward_chain)
+        const int nf = (int)plan.bc_front.size();
+        if (++bc_epoch == 0)
+            bc_epoch = 1;
+        cugo_k::launch_chol_backward_chain(s, dev, d_fronts.data(), nf, d_xnew.data(), d_x, d_bc_state.data(), bc_base,
+                                           bc_epoch, d_fail, h_bc_error.data());
+        bc_base += (uint32_t)nf; // (modulo 2^32, like the head word itself)
+#ifdef CUGO_STAMPS
+        if (dbg)
+        { // the fifth call's hops along the chain from the last ticket (a leaf) up to its root, in 10 ns ticks:
+          // wait = from the parent's done store to this front having seen it, work = from there to its own done store
+            static int chain_calls = 0;
+            static long long* d_cs = nullptr;
+            if (++chain_calls == 4)
+            {
+                CUGO_HIP(hipMalloc(reinterpret_cast<void**>(&d_cs), 3 * sizeof(long long) * (size_t)nf));
+                CUGO_HIP(hipMemset(d_cs, 0, 3 * sizeof(long long) * (size_t)nf));
+                cugo_k::set_chain_stamps(d_cs);
+            }
+            if (chain_calls == 5)
+            {
+                std::vector<long long> h(3 * (size_t)nf);
+                std::vector<int> ticket(plan.n_super, -1);
+                for (int t = 0; t < nf; t++)
+                    ticket[plan.bc_front[t]] = t;
+                CUGO_HIP(hipStreamSynchronize(s));
+                CUGO_HIP(hipMemcpy(h.data(), d_cs, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
+                cugo_k::set_chain_stamps(nullptr);
+                long long first = h[0], last = 0;
+                for (int t = 0; t < nf; t++)
+                    first = std::min(first, h[3 * t]), last = std::max(last, h[3 * t + 2]);
+                std::printf("chain stamps: %d fronts, first start to last done %lld ticks (10 ns)\n", nf, last - first);
+                for (int f = plan.bc_front[nf - 1]; f >= 0; f = plan.sparent[f])
+                {
+                    const int t = ticket[f], pa = plan.sparent[f];
+                    std::printf("  front %d ticket %d ncb %d rows %d: start +%lld", f, t, plan.ncb[f], plan.nb[f] - plan.ncb[f],
+                                h[3 * t] - first);
+                    if (pa >= 0)
+                        std::printf(" wait %lld work %lld", h[3 * t + 1] - h[3 * ticket[pa] + 2], h[3 * t + 2] - h[3 * t + 1]);
+                    std::printf(" done +%lld\n", h[3 * t + 2] - first);
+                }
+            }
+        }
+#endif
+    }
+    for (int st = plan.n_stages - 1; st >= 0 && !bw_chain; st--)
     {
         const int t0 = plan.stage_task_ptr[st], t1 = plan.stage_task_ptr[st + 1];
         // the level's fronts, plus the ahead-of-time mat-vecs of their children as extra workgroups
@@ -545,6 +622,14 @@ void cugo_chol::factor_solve(const double* d_Hsc, double lambda, const double* d
 #endif
 }
 
+// a wait of k_backward_chain ran into its time bound in an earlier call (the kernel has set the pinned word; it is
+// looked at where the host has synchronised or queues the next factorisation): a bug, reported as an error
+void cugo_chol::check_chain_error()
+{
+    if (bw_chain && h_bc_error.data() && *static_cast<volatile uint32_t*>(h_bc_error.data()) != 0)
+        throw std::runtime_error("cugo: the backward substitution gave up waiting for a front (k_backward_chain)");
+}
+
 // Selected inverse of the factorisation the last factor_solve left ("Marginal covariances"): top-down over
 // the stages the backward pass walks, the Sigma-fronts of a level from those of the level above.
 bool cugo_chol::selected_inverse(double* d_sigma)
@@ -553,6 +638,7 @@ bool cugo_chol::selected_inverse(double* d_sigma)
     int32_t h_fail = 0;
     CUGO_HIP(hipMemcpyAsync(&h_fail, last_fail, sizeof h_fail, hipMemcpyDeviceToHost, s));
     CUGO_HIP(hipStreamSynchronize(s));
+    check_chain_error();
     if (h_fail)
         return false;
     const CholPlan& P = plan;

@@ -30,11 +30,19 @@ struct cugo_chol
     // the plan's index arrays, packed (chol_solver.cpp: upload)
     std::vector<int32_t> pack32;
     std::vector<int64_t> pack64;
-    std::array<size_t, 30> po{}; // offsets of the arrays inside the packs (pack)
+    std::array<size_t, 32> po{}; // offsets of the arrays inside the packs (pack)
     cugo_host::DevBuf<int32_t> d_pack32;
     cugo_host::DevBuf<int64_t> d_pack64;
     const int32_t* d_wl_ptr = nullptr; // work-item triples inside d_pack32
     cugo_host::DevBuf<double> d_fronts, d_xnew, d_junk, d_winv, d_l21;
+    // the backward pass in one launch (k_backward_chain; CUGO_BW_CHAIN=0 or a plan it does not cover: one launch per
+    // stage): its device words (kernels.h: BC_HEAD ..., zeroed once in upload()), the pinned word the kernel sets
+    // when a wait runs into its time bound, what the ticket head holds before the next launch, the last epoch
+    bool bw_chain = false;
+    cugo_host::DevBuf<uint32_t> d_bc_state;
+    cugo_host::PinnedBuf<uint32_t> h_bc_error;
+    uint32_t bc_base = 0, bc_epoch = 0;
+    void check_chain_error(); // throws if an earlier call's k_backward_chain gave up
 
     // rank-owned elimination subtrees of a landmark-sharded run (CholPlan::owner): this rank factors its own
     // subtrees and the replicated top; update blocks that enter the top and the solution of the other ranks'

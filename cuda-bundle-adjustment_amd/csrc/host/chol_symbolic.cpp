@@ -1600,6 +1600,38 @@ void chol_analyze(int n, const int32_t* rowptr, const int32_t* colind, const Cho
         v += (int)P.wl.size() / 3;
     P.wl.insert(P.wl.end(), sb.begin(), sb.end());
     lap("8 work items");
+    // ---- 9. the backward pass as one launch (CholPlan::bc_front) ------------------------
+    // ticket order: the stages from the top down, the tasks of a stage in their order, the fronts of a task
+    // parents first — every ancestor of a front then holds a smaller ticket than the front
+    P.bc_front.clear(), P.bc_seg.clear();
+    P.bc_seg_ptr.assign(ns + 1, 0);
+    std::vector<int32_t> ticket(ns, -1);
+    for (int st = P.n_stages - 1; st >= 0; st--)
+        for (int t = P.stage_task_ptr[st]; t < P.stage_task_ptr[st + 1]; t++)
+            for (int fi = P.task_ptr[t + 1] - 1; fi >= P.task_ptr[t]; fi--)
+            {
+                ticket[P.task_fronts[fi]] = (int32_t)P.bc_front.size();
+                P.bc_front.push_back(P.task_fronts[fi]);
+            }
+    // segments: the boundary block rows of a front cut where the front that owns their columns changes (rows
+    // ascend, so do the ancestors: parent first) and after 16 block rows (what one pass of the kernel takes)
+    for (int f = 0; f < ns; f++)
+    {
+        const int r0 = P.rows_ptr[f], r1 = P.rows_ptr[f + 1];
+        for (int k = r0; k < r1;)
+        {
+            const int a = P.col_front[P.rows[k]];
+            int e = k + 1;
+            while (e < r1 && e - k < 16 && P.col_front[P.rows[e]] == a)
+                e++;
+            if (ticket[f] >= 0 && !(ticket[a] >= 0 && ticket[a] < ticket[f]))
+                throw std::runtime_error("cugo: a boundary row of a front belongs to a front scheduled after it");
+            P.bc_seg.push_back(a), P.bc_seg.push_back(k - r0), P.bc_seg.push_back(e - k);
+            k = e;
+        }
+        P.bc_seg_ptr[f + 1] = (int32_t)(P.bc_seg.size() / 3);
+    }
+    lap("9 backward chain");
 }
 
 } // namespace cugo_host

@@ -102,6 +102,12 @@ struct CholPlan
     // is done one launch ahead by extra workgroups riding with the parent's level (items bwg:
     // front, first column, -); -1: the front does its whole mat-vec itself
     std::vector<int32_t> bw_np;
+    // backward pass in ONE launch (k_backward_chain): bc_front = the scheduled fronts in ticket order, root first
+    // (stage descending, the tasks of a stage in their order) — every ancestor of a front comes before it.
+    // Per front f the segments bc_seg[3 * bc_seg_ptr[f] ..) of its boundary, in row order: (the ancestor front
+    // that solves these rows, first boundary block row, block rows <= 16).  The parent's segment comes first: it
+    // is the last to arrive and the last one the kernel adds.
+    std::vector<int32_t> bc_front, bc_seg_ptr, bc_seg;
     // ea = extend-add of the pivot block columns (before potrf), eab = of the boundary columns
     // (same launch as trsm)
     int nc_max = 6; // widest pivot block in scalars (LDS sizing)

@@ -33,6 +33,7 @@ struct Options
     bool lookahead = false;         // CUGO_LOOKAHEAD
     bool ea_lds = true, panel16 = true, asm_fronts = true; // CUGO_EA_LDS / CUGO_PANEL16 / CUGO_ASM_FRONTS = 0
     bool ea_direct = true;          // CUGO_EA_DIRECT=0: the potrf gathers its children's F11 terms unit by unit again
+    bool bw_chain = true;           // CUGO_BW_CHAIN=0: the backward pass one launch per stage (k_backward_stage) again
     // ---- multi-GPU exchange (engine.cpp) ----
     bool reduce_scatter = true;     // CUGO_REDUCE_SCATTER=0: all-reduce of [Hsc | bsc] also with rank-owned subtrees
 
@@ -73,6 +74,7 @@ struct Options
             o.lookahead = std::atoi(e) != 0;
         o.ea_lds = !off("CUGO_EA_LDS"), o.panel16 = !off("CUGO_PANEL16"), o.asm_fronts = !off("CUGO_ASM_FRONTS");
         o.ea_direct = !off("CUGO_EA_DIRECT");
+        o.bw_chain = !off("CUGO_BW_CHAIN");
         o.reduce_scatter = !off("CUGO_REDUCE_SCATTER");
         return o;
     }

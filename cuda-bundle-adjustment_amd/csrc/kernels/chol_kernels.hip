@@ -19,8 +19,10 @@
 //                         tiles, U -= X_i X_j^T, all v_mfma_f64_16x16x4_f64 (k_up_trsyrk32: 32x32
 //                         tiles on the levels with few fronts); the items of a front share an XCD
 //        (k_up_potrf_la / k_up_lead: the opt-in look-ahead schedule, CUGO_LOOKAHEAD=1)
-//   backward            : k_backward_stage per level, x_J = W^T (y_J - L21^T x_R): two mat-vecs;
-//                         the ancestor part of L21^T x_R is done one launch ahead (extra workgroups)
+//   backward            : x_J = W^T (y_J - L21^T x_R), two mat-vecs per front.  k_backward_chain: ONE launch, a
+//                         workgroup per front, x handed from front to front inside the launch; or (CUGO_BW_CHAIN=0,
+//                         subtree stage, look-ahead) k_backward_stage per level, the ancestor part of L21^T x_R
+//                         done one launch ahead by extra workgroups
 //   before every factorisation: k_assemble_fronts — ONE launch that zeroes every lower-triangle entry no Hsc block
 //                         or right-hand side entry lands on and scatters Hsc (+ lambda), the right-hand side and
 //                         the reset of the zero-pivot flag (CUGO_ASM_FRONTS=0: k_clear_fronts + k_assemble_blocks)
@@ -2655,6 +2657,189 @@ __global__ __launch_bounds__(BIG) void k_backward_stage(CholPlanDev p,
     kernel_release(p);
 }
 
+// ---- the backward substitution in ONE launch -------------------------------------------------------------------
+// One workgroup per front; a front's x block (<= 96 doubles) is handed to the fronts below it INSIDE the launch:
+//   * order: thread 0 draws a ticket from the head word; ticket t solves entry t of the plan's root-first list
+//     (CholPlan::bc_front).  A front waits only for fronts with smaller tickets, and whoever holds a ticket is
+//     running: no assumption about how many workgroups are resident, none about the dispatch order;
+//   * publish: x is stored write-through (8-byte agent-scope relaxed atomic stores), every wave waits for its
+//     stores, the workgroup meets at a barrier, ONE lane stores the front's done word (= this call's epoch);
+//   * consume: wave 0 polls ONE done word (relaxed, s_sleep between polls), the others wait at the barrier it
+//     then joins; EVERY load of another front's x is an agent-scope relaxed load to registers (bypasses this
+//     CU's vector cache), so no acquire fence follows the poll.  W, L21, y, the plan: written before the launch,
+//     plain loads;
+//   * the segments of the boundary (one ancestor front each, <= 96 rows) are added in a FIXED order — topmost
+//     ancestor first, the parent last, which is also the order of their arrival — whatever the timing: the same
+//     bits every run;
+//   * every wait is bounded by BW_SPIN_TICKS of the 100 MHz constant-rate counter: on expiry the workgroup sets
+//     the abort word (every poll reads it too, so all other waiters leave at once), raises the factorisation's
+//     failure flag and sets the sticky error words.  An expiry is a bug, not a numerical event.
+typedef __attribute__((address_space(1))) unsigned int gu32;
+typedef __attribute__((address_space(1))) unsigned long long gu64;
+// stamps build: per ticket the 100 MHz counter at {start, the parent's done word seen, own done store} (bc_stamp)
+#ifdef CUGO_STAMPS
+__device__ long long* g_bc_stamps = nullptr;
+__device__ __forceinline__ void bc_stamp(int ticket, int slot)
+{
+    if (g_bc_stamps && threadIdx.x == 0)
+        g_bc_stamps[3 * ticket + slot] = (long long)__builtin_amdgcn_s_memrealtime();
+}
+#else
+__device__ __forceinline__ void bc_stamp(int, int) {}
+#endif
+constexpr unsigned long long BW_SPIN_TICKS = 25000000ULL; // 250 ms
+
+__device__ __forceinline__ void bw_wait(gu32* word, unsigned epoch, gu32* st, int32_t* fail, unsigned* h_error)
+{
+    if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch)
+        return;
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    for (;;)
+    {
+        __builtin_amdgcn_s_sleep(1);
+        if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch)
+            return;
+        if (__hip_atomic_load(st + cugo_k::BC_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
+            return;
+        if (__builtin_amdgcn_s_memrealtime() - t0 > BW_SPIN_TICKS)
+        {
+            __hip_atomic_store(st + cugo_k::BC_ABORT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(st + cugo_k::BC_ERROR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(h_error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            return;
+        }
+    }
+}
+
+__global__ __launch_bounds__(BIG) void k_backward_chain(CholPlanDev p, const double* __restrict__ fronts,
+                                                        double* xnew, double* __restrict__ xout, unsigned* state,
+                                                        unsigned ticket_base, unsigned epoch, int32_t* fail,
+                                                        unsigned* h_error)
+{
+    kernel_acquire(p);
+    extern __shared__ double lds[];
+    dbg_fill_lds(p, lds);
+    gu32* st = (gu32*)state;
+    double* vs = lds;                                        // pad16(ncs) <= NC_MAX
+    int* tk = reinterpret_cast<int*>(lds + NC_MAX);          // the ticket, for the other waves
+    if (threadIdx.x == 0)
+        *tk = (int)(__hip_atomic_fetch_add(st + cugo_k::BC_HEAD, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - ticket_base);
+    __syncthreads();
+    const int t = __builtin_amdgcn_readfirstlane(*tk);
+    if (t < 0 || t >= (int)gridDim.x)
+        return; // (cannot happen: the head counts exactly the workgroups of the launches of this solver)
+#ifdef CUGO_DEBUG_HOOKS
+    const bool skip = p.dbg_skip_wg == t; // fault injection: no arithmetic, no x — but the front still publishes
+#else
+    const bool skip = false;
+#endif
+    bc_stamp(t, 0);
+    // the front's scalars: one 64-byte record per ticket
+    const int32_t* rc = p.bc_rec + cugo_k::BC_REC * t;
+    const int f = rc[0], ncb = rc[1], nb = rc[2], c0 = rc[3], nseg = rc[6];
+    const int32_t* rows = p.rows + rc[4];
+    const int32_t* sg = p.bc_seg + 4 * rc[5];
+    const long* r64 = reinterpret_cast<const long*>(rc + 8);
+    const long l21o = r64[1], ld = r64[3];
+    const int ncs = 6 * ncb, nrs = 6 * (nb - ncb), ncp = pad16(ncs);
+    const double* L = l21o >= 0 ? p.l21 + l21o : fronts + r64[2] + ncs;
+    const long ldl = l21o >= 0 ? nrs + 1 : ld;
+    const double* Wg = p.winv + r64[0];
+    // 8 lanes per pivot column (dev_backward): every thread knows its column now
+    const int g = threadIdx.x >> 3, l8 = threadIdx.x & 7;
+    const bool colok = g < ncs;
+    const int j = min(g, ncs - 1);
+    const double* col = L + (long)j * ldl;
+    const double* wcol = Wg + (long)j * ncp;
+    const int jb = j / 6, comp = j - 6 * jb;
+    // everything that does not depend on another front of this launch, issued before any wait
+    double wv[12];
+    const int k0 = (j & ~15) + 2 * l8;
+#pragma unroll
+    for (int u = 0; u < 6; u++)
+    {
+        const double2 v = *reinterpret_cast<const double2*>(wcol + min(k0 + 16 * u, ncp - 2));
+        wv[2 * u] = v.x, wv[2 * u + 1] = v.y;
+    }
+    const double y = col[nrs];
+    const int pj = p.perm[c0 + jb];
+    for (int jj = ncs + threadIdx.x; jj < ncp; jj += blockDim.x)
+        vs[jj] = 0.0;
+    gu64* xg = (gu64*)xnew;
+    double s = 0;
+    for (int q = nseg - 1; q >= 0; q--)
+    {
+        const int a = sg[4 * q], rb = sg[4 * q + 1], n6 = 6 * sg[4 * q + 2];
+        // this thread's slice of the segment's rows of L21 and the places of their x: rows 2 l8 + 16 u and the one
+        // after it (one block row: 6 is even), clamped into the segment
+        double b[12];
+        int xi[6];
+#pragma unroll
+        for (int u = 0; u < 6; u++)
+        {
+            const int i = min(2 * l8 + 16 * u, n6 - 2);
+            const double2 v = *reinterpret_cast<const double2*>(col + (6 * rb + i));
+            b[2 * u] = v.x, b[2 * u + 1] = v.y;
+            xi[u] = 6 * rows[rb + i / 6] + i % 6;
+        }
+#ifdef CUGO_DEBUG_HOOKS
+        if (p.dbg_delay == 31 && (t & 1) && q == nseg - 1)
+            dbg_sleep(); // (a) before the first poll
+#endif
+        if (threadIdx.x < 64)
+            bw_wait(st + cugo_k::BC_DONE + a, epoch, st, fail, h_error);
+        TILE_SYNC();
+        if (q == 0)
+            bc_stamp(t, 1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // (no instruction: keeps the loads below the poll)
+        double x[12];
+#pragma unroll
+        for (int u = 0; u < 6; u++)
+        {
+            x[2 * u] = __longlong_as_double((long long)__hip_atomic_load(xg + xi[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            x[2 * u + 1] = __longlong_as_double((long long)__hip_atomic_load(xg + xi[u] + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        }
+#pragma unroll
+        for (int u = 0; u < 12; u++)
+            s += (2 * l8 + 16 * (u >> 1) < n6) ? b[u] * x[u] : 0.0;
+    }
+    // v_j = y_j - sum_i L21[i,j] x_R[i]
+#pragma unroll
+    for (int off = 4; off > 0; off >>= 1)
+        s += __shfl_xor(s, off, 8);
+    if (l8 == 0 && colok)
+        vs[j] = y - s;
+    TILE_SYNC();
+    // x_j = sum_k W[k][j] v_k (dev_backward)
+    double xj = 0;
+#pragma unroll
+    for (int u = 0; u < 12; u++)
+    {
+        const int k = k0 + 16 * (u >> 1) + (u & 1);
+        xj += (k < ncp) ? wv[u] * vs[k] : 0.0;
+    }
+#pragma unroll
+    for (int off = 4; off > 0; off >>= 1)
+        xj += __shfl_xor(xj, off, 8);
+    if (l8 == 0 && colok && !skip)
+    {
+        __hip_atomic_store(xg + (6L * (c0 + jb) + comp), (unsigned long long)__double_as_longlong(xj), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        xout[6L * pj + comp] = xj;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every storing wave, before the barrier the signalling lane joins
+#ifdef CUGO_DEBUG_HOOKS
+    if (p.dbg_delay == 31 && (t & 1))
+        dbg_sleep(); // (b) between the last x store and the done store
+#endif
+    __syncthreads();
+    bc_stamp(t, 2);
+    if (threadIdx.x == 0)
+        __hip_atomic_store(st + cugo_k::BC_DONE + f, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    kernel_release(p);
+}
+
 // x[perm[j]] = xnew[j] for all block rows (after the solution ranges of other ranks' subtrees have arrived)
 __global__ __launch_bounds__(CBS) void k_unpermute(CholPlanDev p, const double* __restrict__ xnew, double* __restrict__ xout)
 {
@@ -2784,6 +2969,14 @@ void set_debug_stamps(long long* d_buf)
 {
 #ifdef CUGO_STAMPS
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &d_buf, sizeof(d_buf));
+#else
+    (void)d_buf;
+#endif
+}
+void set_chain_stamps(long long* d_buf)
+{
+#ifdef CUGO_STAMPS
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bc_stamps), &d_buf, sizeof(d_buf));
 #else
     (void)d_buf;
 #endif
@@ -2955,6 +3148,19 @@ void launch_chol_backward_stage(hipStream_t s, const CholPlanDev& p, double* d_f
     ensure_lds(reinterpret_cast<const void*>(k_backward_stage), lds_bytes);
     CUGO_LAUNCH(k_backward_stage, dim3(ntasks + ngemv), dim3(BIG), lds_bytes, s, with_lds(p, lds_bytes, "k_backward_stage", ntasks + ngemv, ntasks), d_fronts, task0,
                        ntasks, d_wl_gemv, d_xnew, d_x);
+}
+
+void launch_chol_backward_chain(hipStream_t s, const CholPlanDev& p, double* d_fronts, int nfronts, double* d_xnew,
+                                double* d_x, uint32_t* d_state, uint32_t ticket_base, uint32_t epoch, int32_t* d_fail,
+                                uint32_t* h_error)
+{
+    if (nfronts <= 0)
+        return;
+    // more than half a CU's LDS: one workgroup per CU, what the hand-off without an acquire fence was measured with
+    const size_t lds_bytes = 96 * 1024;
+    ensure_lds(reinterpret_cast<const void*>(k_backward_chain), lds_bytes);
+    CUGO_LAUNCH(k_backward_chain, dim3(nfronts), dim3(BIG), lds_bytes, s, with_lds(p, lds_bytes, "k_backward_chain", nfronts),
+                d_fronts, d_xnew, d_x, d_state, ticket_base, epoch, d_fail, h_error);
 }
 
 } // namespace cugo_k

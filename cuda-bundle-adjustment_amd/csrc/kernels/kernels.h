@@ -228,6 +228,9 @@ struct CholPlanDev
     const int64_t* asm_off;
     const int32_t* wl_base;    // the work-item triples (chol_symbolic.h: CholPlan::wl) ...
     const int32_t* fat;        // ... and one 64-byte record per item for the tile kernels (TileItem)
+    const int32_t* bc_rec;     // k_backward_chain, BC_REC ints per ticket (chol_symbolic.h: CholPlan::bc_front): {front, ncb, nb, col0,
+                               // rows_ptr, first segment, segments, 0, woff, l21off, off, ldf (four int64)}
+    const int32_t* bc_seg;     // ... and 4 ints per segment: {ancestor front, first boundary block row, block rows, 0}
     const int32_t* task_ptr;   // [n_tasks_total+1] into task_fronts
     const int32_t* task_fronts;
     // assembly of A (one entry per Hsc block)
@@ -282,6 +285,16 @@ void launch_chol_lead(hipStream_t s, const CholPlanDev& p, double* d_fronts, con
 void launch_chol_backward_stage(hipStream_t s, const CholPlanDev& p, double* d_fronts, int task0,
                                 int ntasks, size_t lds_bytes, double* d_xnew, double* d_x,
                                 const int32_t* d_wl_gemv, int ngemv);
+// the whole backward substitution in one launch, one workgroup per front, x handed from front to front inside
+// the launch (k_backward_chain).  d_state: the solver's words (uint32, hipMalloc, zeroed ONCE when they are
+// allocated): [BC_HEAD] the ticket head, [BC_ABORT] set by a workgroup whose wait ran into its time bound,
+// [BC_ERROR] the same, never cleared, [BC_DONE + f] = epoch once front f has published its x.  ticket_base: what
+// the head holds when the launch starts (nfronts per call, modulo 2^32); epoch: never 0, another one every call.
+// h_error: pinned host word that is set with [BC_ERROR] (the caller looks at it after a synchronisation)
+constexpr int BC_REC = 16, BC_HEAD = 0, BC_ABORT = 32, BC_ERROR = 33, BC_DONE = 64;
+void launch_chol_backward_chain(hipStream_t s, const CholPlanDev& p, double* d_fronts, int nfronts, double* d_xnew,
+                                double* d_x, uint32_t* d_state, uint32_t ticket_base, uint32_t epoch, int32_t* d_fail,
+                                uint32_t* h_error);
 #ifdef CUGO_DEBUG_HOOKS
 void launch_nop(hipStream_t s); // diagnosis (CUGO_DEBUG_GAP): an empty kernel
 // fault injection (CUGO_DEBUG_SKIP): the launches of the factorisation that follows are counted from 0; workgroup
@@ -299,6 +312,7 @@ void launch_xs_pack(hipStream_t s, const int64_t* d_off, int B, int n, const dou
 void launch_xs_unpack(hipStream_t s, const int64_t* d_off, int B, int n, const double* d_xbuf, double* d_sys, long lo,
                       long hi, long top0);
 void set_debug_stamps(long long* d_buf); // diagnostic s_memtime stamps (nullptr = off)
+void set_chain_stamps(long long* d_buf); // k_backward_chain: three 100 MHz stamps per ticket (stamps build; nullptr = off)
 size_t chol_lds_factor_bytes(int nc_max);
 size_t chol_lds_backward_bytes(int nc_max, long ld_max);
 int chol_max_pivot_cols(); // widest pivot block the kernels support (scalars)
