@@ -10,6 +10,7 @@
 #include "../../include/icp_types.h"
 #include "../kernels/kernels.h"
 #include "chol_solver.h"
+#include "edge_layout.h"
 #include "engine.h"
 #include "hip_util.h"
 #include "rccl_comm.h"

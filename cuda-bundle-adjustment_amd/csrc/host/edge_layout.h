@@ -1,0 +1,82 @@
+// Host-only layout of a flattened graph: what Engine::initialize() / build_structure() compute on plain vectors
+// before (or without) a device.  No HIP, no Engine::Impl: free functions over FlatGraph and caller-owned vectors (the
+// engine keeps its staging vectors between calls: a fresh 40 MB costs more in page faults than the work done on it,
+// so nothing here returns a vector by value).  Every sum and every order the kernels later see is fixed by these arrays.
+#pragma once
+#include <cstdint>
+#include <functional>
+#include <vector>
+
+#include "engine.h"
+
+namespace cugo_host
+{
+using Idx = std::vector<int32_t>;
+
+// Edge slots per group: k_build_edges, the back-substitution and the landmark-major Schur plan (kSchurGroup) sum a
+// landmark's edges inside one workgroup of this many threads
+constexpr int kSlotGroup = 256;
+
+// an active edge between a free pose and a free landmark: the only edges with an Hpl block
+inline bool is_free_free(uint8_t flags)
+{
+    return (flags & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P | CUGO_EDGE_INACTIVE)) == 0;
+}
+double count_free_free(const std::vector<uint8_t>& flags);
+
+// byte compare over the pool that stops at the first difference (the lists are megabytes, a new graph differs early)
+bool same_bytes(const void* a, const void* b, size_t bytes);
+template <typename T>
+inline bool same_bytes(const std::vector<T>& a, const std::vector<T>& b)
+{
+    return a.size() == b.size() && same_bytes(a.data(), b.data(), a.size() * sizeof(T));
+}
+
+// order[lm_cnt[l] .. lm_cnt[l + 1]): the edges of landmark l by pose, container order among equals
+void sort_landmark_major(const FlatGraph& g, Idx& lm_cnt, Idx& order);
+// global co-visibility (all shards): free landmark -> its free poses, ascending; throws on a duplicate free-free edge
+void build_covisibility(const FlatGraph& g, const Idx& lm_cnt, const Idx& order, Idx& cov_ptr, Idx& cov_pose);
+// contiguous landmark range of shard `rank`, balanced by edge count
+void shard_range(const Idx& lm_cnt, int rank, int world, int& l0, int& l1);
+// Slots of the edges of landmarks [l0, l1): landmark-major, padded with inactive slots so that no landmark with
+// <= kSlotGroup edges straddles a group boundary.  A padding slot belongs to the landmark before it; slot_src[i] =
+// index into `order`, or -1 for padding.  Returns whether every landmark's slots lie inside one group.
+bool pad_slot_layout(const Idx& lm_cnt, int l0, int l1, Idx& lm_ptr, Idx& slot_src);
+
+// what the edge kernels read per slot, and where a slot came from
+struct SlotArrays
+{
+    Idx pose, lm;
+    std::vector<uint8_t> flags;
+    std::vector<double> meas;  // planar: [3][E]
+    std::vector<double> omega; // E, or 1 when uniform
+    std::vector<uint16_t> cam; // E, or empty with a single camera
+    int n_omega = 1, n_cams = 1;
+    Idx slot_edge;                      // slot -> edge index of the FlatGraph (-1: padding)
+    std::vector<double> slot_threshold; // slot -> outlier threshold (empty: rejection disabled)
+};
+void fill_slots(const FlatGraph& g, const Idx& order, const Idx& slot_src, SlotArrays& out);
+// pose_edge[pose_ptr[p] .. pose_ptr[p + 1]): the real slots of pose p in slot order (= ascending landmark)
+void pose_major_view(int Pall, const Idx& slot_pose, const Idx& slot_src, Idx& pose_ptr, Idx& pose_edge);
+
+// point-to-plane / point-to-line edges of one kind sorted by pose (stable: container order inside a pose), planar
+struct IcpKindHost
+{
+    Idx h_pose, h_ptr, slot_set, slot_edge;
+    std::vector<double> h_p, h_geo, h_omega;
+};
+void sort_icp_by_pose(const FlatIcpKind& kind, int Pall, int P, int geo_width, IcpKindHost& out);
+
+// ---- the Hsc structure on the host: pattern (upper block CSR, diagonal first) and, from the LOCAL slots, the
+// contributions of the off-diagonal blocks (ascending landmark inside a block).  use_plan() is asked once the pattern
+// exists: true = a landmark-major plan (schur_plan.h) serves and the lists stay empty.  lap(label) after every pass.
+struct HostStructure
+{
+    double products = 0;         // all products of the graph (a free-free edge also has its diagonal one)
+    Idx off_ptr, off_ei, off_ej; // per block: the two edge slots of each contribution
+};
+void host_structure(int P, int L, const Idx& cov_ptr, const Idx& cov_pose, const SlotArrays& slots, const Idx& lm_ptr,
+                    const Idx& pose_ptr, const Idx& pose_edge, const std::function<bool()>& use_plan,
+                    const std::function<void(const char*)>& lap, Idx& rowptr, Idx& colind, HostStructure& out);
+
+} // namespace cugo_host

@@ -10,13 +10,12 @@
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 #include <memory>
-#include <numeric>
 #include <thread>
 
 #include "../kernels/kernels.h"
 #include "chol_solver.h"
+#include "edge_layout.h"
 #include "hip_util.h"
 #include "options.h"
 #include "rccl_comm.h"
@@ -45,25 +44,25 @@ double ms_since(Clock::time_point t0)
 }
 } // namespace
 
-void shard_range(const std::vector<int32_t>& lm_cnt, int rank, int world, int& l0, int& l1)
-{
-    const int Lall = (int)lm_cnt.size() - 1;
-    l0 = 0, l1 = Lall;
-    if (world <= 1)
-        return;
-    const int64_t Etot = lm_cnt[Lall];
-    auto cut = [&](int r) {
-        const int64_t target = Etot * r / world;
-        return (int)(std::lower_bound(lm_cnt.begin(), lm_cnt.end(), (int32_t)target) - lm_cnt.begin());
-    };
-    l0 = rank == 0 ? 0 : std::min(cut(rank), Lall);
-    l1 = rank == world - 1 ? Lall : std::min(cut(rank + 1), Lall);
-    if (l1 < l0)
-        l1 = l0;
-}
-
 void set_last_error(const std::string& s) { g_last_error = s; }
 const char* get_last_error() { return g_last_error.c_str(); }
+
+// CUGO_INIT_TIMING=1: per-section host times of initialize() on stderr (diagnosis only)
+struct InitLaps
+{
+    bool on;
+    explicit InitLaps(bool enabled) : on(enabled) {}
+    const Clock::time_point t0 = Clock::now(); // of the call
+    Clock::time_point t = t0;
+    void lap(const char* what)
+    {
+        if (!on)
+            return;
+        const auto n = Clock::now();
+        std::fprintf(stderr, "[cugo init] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
+        t = n;
+    }
+};
 
 struct Engine::Impl : cugo_k::LaunchHook
 {
@@ -83,23 +82,18 @@ struct Engine::Impl : cugo_k::LaunchHook
     int Pall = 0, Lall = 0, P = 0, L = 0, E = 0;
     int shard_l0 = 0, shard_l1 = 0; // landmark index range owned by this rank
     cugo_robust rk{CUGO_RK_NONE, 1.0, CUGO_RK_NONE, 1.0};
-    int n_omega = 1, n_cams = 1;
 
     // host copies (sorted, local shard)
-    std::vector<int32_t> h_e_pose, h_e_lm, h_lm_ptr, h_pose_ptr, h_pose_edge;
-    std::vector<int32_t> slot_edge;     // slot -> edge index of the FlatGraph (-1: padding)
+    std::vector<int32_t> h_lm_ptr, h_pose_ptr, h_pose_edge;
     // staging of initialize(), kept between calls: a fresh 40 MB of vectors costs more in page
     // faults than the work done on them
     FlatGraph staging;
     bool f32_blocks = false; // Hpl / T stored as float (fp32-internal mode)
     std::vector<int32_t> st_lm_cnt, st_order, st_slot_src;
-    std::vector<double> st_meas, st_omega;
-    std::vector<uint16_t> st_cam;
-    std::vector<double> slot_threshold; // slot -> outlier threshold (empty: rejection disabled)
-    int last_err_buf = 0;               // estimate buffer of the last error pass
-    bool lm_in_one_group = false;       // no landmark's slots straddle two 256-slot groups
+    SlotArrays slots;             // the slot arrays (the measurement part is only staging for the upload)
+    int last_err_buf = 0;         // estimate buffer of the last error pass
+    bool lm_in_one_group = false; // no landmark's slots straddle two groups of kSlotGroup slots
     int Etot = 0;
-    std::vector<uint8_t> h_flags;
     // global co-visibility: free landmark -> sorted free poses (free-free active edges, all shards)
     std::vector<int32_t> cov_ptr, cov_pose;
     // Hsc pattern (host)
@@ -137,10 +131,8 @@ struct Engine::Impl : cugo_k::LaunchHook
     // point-to-plane / point-to-line pose edges (icp_kernels.hip): each kind sorted by pose (stable: container order
     // inside a pose), structure of arrays, on the device as long as the flattening lives.  Their partial sums have a
     // scratch of their own: the BA scratch holds live scale / chi2 partials and records across the same span of the stream
-    struct IcpKindBufs
+    struct IcpKindBufs : IcpKindHost
     {
-        std::vector<int32_t> h_pose, h_ptr, slot_set, slot_edge;
-        std::vector<double> h_p, h_geo, h_omega;
         DevBuf<int32_t> d_pose, d_ptr;
         DevBuf<double> d_p, d_geo, d_omega;
     } icpk[2];
@@ -186,6 +178,10 @@ struct Engine::Impl : cugo_k::LaunchHook
         if (pat_thread.joinable())
             pat_thread.join();
     }
+    // the stages of Engine::initialize() that work on the device side (defined beside it)
+    struct SlotUpload;
+    bool start_pattern_helper(double* prof);
+    void bind_icp_edges(const FlatGraph& g);
     std::vector<uint8_t> sig_flags;
 
     // optional HIP-event timing: 1 = an event pair round every kernel group AND every kernel (each pair adds a few
@@ -732,23 +728,6 @@ void Engine::exchange_stats(double& bytes, int& calls) const
     bytes = impl_->xchg_bytes, calls = impl_->xchg_calls;
 }
 
-
-// CUGO_INIT_TIMING=1: per-section host times of initialize() on stderr (diagnosis only)
-struct InitLaps
-{
-    bool on;
-    explicit InitLaps(bool enabled) : on(enabled) {}
-    Clock::time_point t = Clock::now();
-    void lap(const char* what)
-    {
-        if (!on)
-            return;
-        const auto n = Clock::now();
-        std::fprintf(stderr, "[cugo init] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
-        t = n;
-    }
-};
-
 void Engine::set_float32_blocks(bool on)
 {
     impl_->f32_blocks = on;
@@ -759,676 +738,250 @@ FlatGraph& Engine::staging()
     return impl_->staging;
 }
 
+// ---- the device-side stages of Engine::initialize() (the index arithmetic is edge_layout.cpp) ---------------------
+// The co-visibility lists decide the Hsc pattern: if they changed, its build, the ordering and the symbolic
+// factorisation start NOW on a helper thread and a second stream (see Impl::pat_thread).  Invariant: from
+// here until the next join_pattern() nothing may touch P, L, the co-visibility lists or the solver's (rank, world).
+bool Engine::Impl::start_pattern_helper(double* prof)
+{
+    join_pattern();
+    if (pat_err)
+    {
+        pat_err = nullptr; // a failed helper of an earlier call: that structure was never used
+        pattern_dirty = true;
+    }
+    const bool pat_same = !pattern_dirty && opt.structure_reuse && P == pat_P && L == pat_L &&
+                          same_bytes(cov_ptr, pat_cov_ptr) && same_bytes(cov_pose, pat_cov_pose);
+    pat_async_ok = false;
+    lists_built = false;
+    pat_stage.store(0, std::memory_order_relaxed);
+    if (pat_same)
+        return false;
+    pattern_dirty = true;
+    plan_uploaded = false;
+    const bool device_build = !plan_only && !opt.schur_plan && !opt.host_structure;
+    if (!(device_build && opt.async_structure && P > 0 && !cov_pose.empty()))
+        return false;
+    if (!s2)
+        s2 = cache_stream_acquire();
+    pat_thread = std::thread([this, prof] {
+        try
+        {
+            // (the current device is per thread: a rank of a multi-GPU job runs on LOCAL_RANK, not 0)
+            CUGO_HIP(hipSetDevice(ctx.device));
+            const auto t0p = Clock::now();
+            if (!build_pattern_gpu(s2, P, L, cov_ptr.data(), cov_pose.data(), gstruct))
+            {
+                pat_stage.store(-1, std::memory_order_release);
+                return;
+            }
+            pat_stage.store(1, std::memory_order_release);
+            hsc_rowptr = gstruct.h_rowptr, hsc_colind = gstruct.h_colind;
+            prof[PROF_BUILD_STRUCTURE] += ms_since(t0p);
+            const auto t1p = Clock::now();
+            chol.analyze_host(P, hsc_rowptr.data(), hsc_colind.data());
+            // ... and the plan goes to the device from here as well (second stream; upload() waits for
+            // its copies): the first optimize() then only builds the contribution lists
+            chol.upload(s2);
+            plan_uploaded = true;
+            prof[PROF_SYMBOLIC] += ms_since(t1p);
+            pat_async_ok = true;
+        }
+        catch (...)
+        {
+            pat_err = std::current_exception();
+            pat_stage.store(-1, std::memory_order_release);
+        }
+    });
+    return true;
+}
+
+// Upload of the slot arrays and the estimates: copies from pageable memory block their caller, so a thread of its own
+// issues them beside the rest of initialize() (CUGO_UPLOAD_THREAD=0: the calling thread; plan-only: nothing).
+// Invariant: `err` is declared before the thread, which may still assign to it while the caller unwinds;
+// the destructor joins and then, short of finish(), waits for the stream: the staging of the copies is about to go.
+struct Engine::Impl::SlotUpload
+{
+    Impl& m;
+    const FlatGraph& g;
+    std::exception_ptr err;
+    std::thread t;
+    bool pending; // copies may be in flight
+    SlotUpload(Impl& impl, const FlatGraph& graph) : m(impl), g(graph), pending(!impl.plan_only)
+    {
+        if (!pending)
+            return;
+        // (sized by this thread: it reads the pointers while the copies are still being issued)
+        each([](auto& d, const auto& h) { d.resize(h.size()); });
+        if (m.opt.upload_thread)
+            t = std::thread([this] { copies(); });
+        else
+            copies(); // (finish() reports what went wrong)
+    }
+    ~SlotUpload()
+    {
+        if (t.joinable())
+            t.join();
+        if (pending && m.ctx.stream)
+            (void)hipStreamSynchronize(m.ctx.stream);
+    }
+    // f(device buffer, its host source) for everything that goes up, in the order of the copies
+    template <typename F>
+    void each(F&& f)
+    {
+        const SlotArrays& sl = m.slots;
+        f(m.d_e_pose, sl.pose), f(m.d_e_lm, sl.lm), f(m.d_flags, sl.flags), f(m.d_lm_ptr, m.h_lm_ptr);
+        f(m.d_meas, sl.meas), f(m.d_omega, sl.omega), f(m.d_cams, g.cams);
+        if (sl.n_cams > 1)
+            f(m.d_cam, sl.cam);
+        for (int k = 0; k < 2; k++)
+            f(m.d_poses[k], g.poses), f(m.d_lms[k], g.lms);
+    }
+    void copies()
+    {
+        try
+        {
+            CUGO_HIP(hipSetDevice(m.ctx.device)); // (the current device is per thread)
+            each([&](auto& d, const auto& h) { d.upload(h, m.ctx.stream); });
+        }
+        catch (...)
+        {
+            err = std::current_exception();
+        }
+    }
+    void finish()
+    {
+        if (!pending)
+            return;
+        if (t.joinable())
+            t.join();
+        if (err)
+            std::rethrow_exception(err);
+        CUGO_HIP(hipStreamSynchronize(m.ctx.stream));
+        pending = false;
+    }
+};
+
+// Point-to-plane / point-to-line edges: each kind sorted by pose, uploaded by the calling thread, and their view
+void Engine::Impl::bind_icp_edges(const FlatGraph& g)
+{
+    const FlatIcpKind* kinds[2] = {&g.plane, &g.line};
+    for (int k = 0; k < 2; k++)
+    {
+        IcpKindBufs& b = icpk[k];
+        sort_icp_by_pose(*kinds[k], Pall, P, k == 0 ? 4 : 6, b);
+        if (plan_only)
+            continue;
+        hipStream_t s = ctx.stream;
+        b.d_pose.upload(b.h_pose, s), b.d_ptr.upload(b.h_ptr, s);
+        b.d_p.upload(b.h_p, s), b.d_geo.upload(b.h_geo, s), b.d_omega.upload(b.h_omega, s);
+    }
+    n_icp = g.plane.n() + g.line.n();
+    cugo_icp_edges& iv = icp;
+    iv = cugo_icp_edges{};
+    iv.n_poses_total = Pall, iv.n_poses_free = P;
+    iv.n_plane = g.plane.n(), iv.n_line = g.line.n();
+    iv.d_plane_pose = icpk[0].d_pose.data(), iv.d_plane_pose_ptr = icpk[0].d_ptr.data();
+    iv.d_plane_p = icpk[0].d_p.data(), iv.d_plane_nd = icpk[0].d_geo.data();
+    iv.d_plane_omega = icpk[0].d_omega.data(), iv.n_plane_omega = (int)icpk[0].h_omega.size();
+    iv.rk_plane = g.plane.rk, iv.delta_plane = g.plane.delta;
+    iv.d_line_pose = icpk[1].d_pose.data(), iv.d_line_pose_ptr = icpk[1].d_ptr.data();
+    iv.d_line_p = icpk[1].d_p.data(), iv.d_line_au = icpk[1].d_geo.data();
+    iv.d_line_omega = icpk[1].d_omega.data(), iv.n_line_omega = (int)icpk[1].h_omega.size();
+    iv.rk_line = g.line.rk, iv.delta_line = g.line.delta;
+    if (n_icp && !plan_only)
+        d_icp_scratch.resize(cugo_k::icp_scratch_doubles(iv));
+}
+
 void Engine::initialize(FlatGraph& g)
 {
     const auto t0 = Clock::now();
     Impl& m = *impl_;
     InitLaps laps(m.opt.init_timing);
-    // the helper thread of the previous initialize() reads m.P / m.L, the co-visibility lists and the solver's
-    // (rank, world): nothing below may change them while it runs
+    // Invariant: the first statement that changes anything.  The helper thread of the previous
+    // initialize() reads m.P / m.L, the co-visibility lists and the solver's (rank, world).
     m.join_pattern();
     hipStream_t s = m.ctx.stream;
     m.Pall = g.Pall, m.Lall = g.Lall, m.P = g.P, m.L = g.L;
     m.rk = g.rk;
     m.init_rank = m.rank, m.init_world = m.world;
-    const int Etot = g.n_edges();
-    E_global_ = Etot + g.plane.n() + g.line.n();
+    m.Etot = g.n_edges();
+    E_global_ = m.Etot + g.plane.n() + g.line.n();
     if ((g.plane.n() || g.line.n()) && (m.world > 1 || m.comm))
         throw std::runtime_error("cugo: point-to-plane / point-to-line edge sets are not supported on a landmark-sharded "
                                  "(multi-GPU) optimiser yet");
-
-    // ---- landmark-major order: counting sort by landmark, then by pose inside ----------
-    // Threads own contiguous landmark ranges: each scans all edges (8 B per edge, from cache)
-    // and counts / places only the edges of its own landmarks, so no two threads write the same
-    // bin and the placement keeps the container order inside a landmark (stable).
-    std::vector<int32_t>& lm_cnt = m.st_lm_cnt;
-    std::vector<int32_t>& order = m.st_order;
-    lm_cnt.assign(m.Lall + 1, 0);
-    order.resize(Etot);
-    {
-        const int32_t* elm = g.e_lm.data();
-        auto sort_by_pose = [&](size_t la, size_t lb) {
-            for (size_t l = la; l < lb; l++)
-            {
-                int32_t* b = order.data() + lm_cnt[l];
-                const int k = lm_cnt[l + 1] - lm_cnt[l];
-                for (int i = 1; i < k; i++)
-                { // insertion sort by pose index (k is small)
-                    const int32_t v = b[i];
-                    const int pv = g.e_pose[v];
-                    int j = i - 1;
-                    while (j >= 0 && g.e_pose[b[j]] > pv)
-                    {
-                        b[j + 1] = b[j];
-                        j--;
-                    }
-                    b[j + 1] = v;
-                }
-            }
-        };
-        // Callers usually add the edges landmark by landmark (ORB-SLAM2 walks its map points):
-        // then the counting sort is the identity and only the counts are needed.
-        std::vector<uint8_t> chunk_sorted(pool_threads(), 1);
-        parallel_chunks((size_t)Etot, 100000, [&](size_t a, size_t b, unsigned t) {
-            bool ok = true;
-            for (size_t e = std::max<size_t>(a, 1); e < b; e++)
-                ok = ok && elm[e - 1] <= elm[e];
-            chunk_sorted[t] = ok;
-        });
-        bool sorted = true;
-        for (uint8_t c : chunk_sorted)
-            sorted = sorted && c;
-        if (sorted)
-        {
-            // a chunk's first and last landmark may continue in the neighbouring chunks: their
-            // counts are combined afterwards
-            struct Side
-            {
-                int32_t first = -1, nfirst = 0, last = -1, nlast = 0;
-            };
-            std::vector<Side> side(pool_threads());
-            parallel_chunks((size_t)Etot, 100000, [&](size_t a, size_t b, unsigned t) {
-                if (a == b)
-                    return;
-                Side sd;
-                sd.first = elm[a], sd.last = elm[b - 1];
-                for (size_t e = a; e < b; e++)
-                {
-                    const int32_t l = elm[e];
-                    if (l == sd.first)
-                        sd.nfirst++;
-                    else if (l == sd.last)
-                        sd.nlast++;
-                    else
-                        lm_cnt[l + 1]++;
-                    order[e] = (int32_t)e;
-                }
-                side[t] = sd;
-            });
-            for (const Side& sd : side)
-            {
-                if (sd.first >= 0)
-                    lm_cnt[sd.first + 1] += sd.nfirst;
-                if (sd.last >= 0 && sd.last != sd.first)
-                    lm_cnt[sd.last + 1] += sd.nlast;
-            }
-            for (int l = 0; l < m.Lall; l++)
-                lm_cnt[l + 1] += lm_cnt[l];
-            parallel_chunks((size_t)m.Lall, 65536, [&](size_t la, size_t lb, unsigned) { sort_by_pose(la, lb); });
-        }
-        else
-        {
-            // Not sorted as a whole — but callers add their edges set by set and, inside a set, landmark by
-            // landmark (the reference sample: all mono edges, then all stereo edges, each in landmark order): the
-            // container order is a FEW sorted runs.  Then the counting sort is a merge of runs: a thread owns a
-            // landmark range, finds its part of every run by binary search and lays the edges of each landmark
-            // down run after run (= container order: stable).  O(E) work in all, where the general path below
-            // has every thread scan all edges twice.
-            std::vector<int32_t> run_start(1, 0);
-            {
-                const unsigned ntd = pool_threads();
-                std::vector<std::vector<int32_t>> desc(ntd);
-                parallel_chunks((size_t)Etot, 100000, [&](size_t a, size_t b, unsigned t) {
-                    for (size_t e = std::max<size_t>(a, 1); e < b && desc[t].size() <= 64; e++)
-                        if (elm[e - 1] > elm[e])
-                            desc[t].push_back((int32_t)e);
-                });
-                for (const auto& d : desc)
-                    run_start.insert(run_start.end(), d.begin(), d.end());
-            }
-            const int nruns = (int)run_start.size();
-            run_start.push_back(Etot);
-            if (nruns <= 64)
-            {
-                const unsigned nt = std::max(1u, std::min<unsigned>(pool_threads(), (unsigned)std::max(1, m.Lall / 1024)));
-                std::vector<int64_t> base(nt + 1, 0);
-                auto lrange = [&](unsigned t) { return (size_t)m.Lall * t / nt; };
-                auto run_lo = [&](int r, size_t l) {
-                    return (int32_t)(std::lower_bound(elm + run_start[r], elm + run_start[r + 1], (int32_t)l) - elm);
-                };
-                struct MergeCtx
-                {
-                    const std::function<void(unsigned)>* fn;
-                };
-                auto run_threads = [&](const std::function<void(unsigned)>& fn) {
-                    MergeCtx c{&fn};
-                    pool_run(
-                        nt, [](void* p, unsigned t) { (*static_cast<MergeCtx*>(p)->fn)(t); }, &c);
-                };
-                run_threads([&](unsigned t) {
-                    int64_t c = 0;
-                    for (int r = 0; r < nruns; r++)
-                        c += run_lo(r, lrange(t + 1)) - run_lo(r, lrange(t));
-                    base[t + 1] = c;
-                });
-                for (unsigned t = 0; t < nt; t++)
-                    base[t + 1] += base[t];
-                run_threads([&](unsigned t) {
-                    const size_t la = lrange(t), lb = lrange(t + 1);
-                    if (la == lb)
-                        return;
-                    std::vector<int32_t> cur(nruns), lim(nruns);
-                    for (int r = 0; r < nruns; r++)
-                        cur[r] = run_lo(r, la), lim[r] = run_lo(r, lb);
-                    int32_t pos = (int32_t)base[t];
-                    for (size_t l = la; l < lb; l++)
-                    {
-                        lm_cnt[l] = pos; // (start of landmark l; lm_cnt[Lall] is set below)
-                        for (int r = 0; r < nruns; r++)
-                            while (cur[r] < lim[r] && elm[cur[r]] == (int32_t)l)
-                                order[pos++] = cur[r]++;
-                    }
-                });
-                lm_cnt[m.Lall] = Etot;
-                parallel_chunks((size_t)m.Lall, 65536, [&](size_t la, size_t lb, unsigned) { sort_by_pose(la, lb); });
-            }
-            else
-            {
-                parallel_chunks((size_t)m.Lall, 65536, [&](size_t la, size_t lb, unsigned) {
-                    for (int e = 0; e < Etot; e++)
-                    {
-                        const size_t l = (size_t)elm[e];
-                        if (l >= la && l < lb)
-                            lm_cnt[l + 1]++;
-                    }
-                });
-                for (int l = 0; l < m.Lall; l++)
-                    lm_cnt[l + 1] += lm_cnt[l];
-                parallel_chunks((size_t)m.Lall, 65536, [&](size_t la, size_t lb, unsigned) {
-                    if (la == lb)
-                        return;
-                    std::vector<int32_t> pos(lm_cnt.begin() + la, lm_cnt.begin() + lb);
-                    for (int e = 0; e < Etot; e++)
-                    {
-                        const size_t l = (size_t)elm[e];
-                        if (l >= la && l < lb)
-                            order[pos[l - la]++] = e;
-                    }
-                    sort_by_pose(la, lb);
-                });
-            }
-        }
-    }
+    sort_landmark_major(g, m.st_lm_cnt, m.st_order);
     laps.lap("engine: landmark sort");
-    // ---- global co-visibility (all shards): free landmark -> free poses ----------------
-    {
-        auto is_ff = [&](int e) {
-            return (g.e_flags[e] & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P | CUGO_EDGE_INACTIVE)) == 0;
-        };
-        m.cov_ptr.assign(m.L + 1, 0);
-        parallel_chunks((size_t)m.L, 65536, [&](size_t la, size_t lb, unsigned) {
-            for (size_t l = la; l < lb; l++)
-            {
-                int c = 0;
-                for (int i = lm_cnt[l]; i < lm_cnt[l + 1]; i++)
-                    c += is_ff(order[i]);
-                m.cov_ptr[l + 1] = c;
-            }
-        });
-        for (int l = 0; l < m.L; l++)
-            m.cov_ptr[l + 1] += m.cov_ptr[l];
-        m.cov_pose.resize((size_t)m.cov_ptr[m.L]);
-        std::atomic<int> dup_lm{-1};
-        parallel_chunks((size_t)m.L, 65536, [&](size_t la, size_t lb, unsigned) {
-            for (size_t l = la; l < lb; l++)
-            {
-                int o = m.cov_ptr[l];
-                for (int i = lm_cnt[l]; i < lm_cnt[l + 1]; i++)
-                    if (is_ff(order[i]))
-                    {
-                        // (the slots of a landmark are sorted by pose: equal poses are neighbours)
-                        if (o > m.cov_ptr[l] && m.cov_pose[o - 1] == g.e_pose[order[i]])
-                            dup_lm.store((int)l, std::memory_order_relaxed);
-                        m.cov_pose[o++] = g.e_pose[order[i]];
-                    }
-            }
-        });
-        // Two active edges between the same free pose and free landmark: the reference stores ONE Hpl block
-        // per (pose, landmark) pair and forms only one of the two cross products of such a pair
-        // (ref: .cu:1347-1378 iterates j >= i inside a column), i.e. it has no defined behaviour for them;
-        // here every structure (Hpl slots, Hsc lists, the device structure build) assumes distinct pairs.
-        if (dup_lm.load() >= 0)
-            throw std::runtime_error("cugo: two active edges join the same free pose and free landmark (landmark index " +
-                                     std::to_string(dup_lm.load()) + "): duplicate (pose, landmark) edges are not supported");
-    }
+    build_covisibility(g, m.st_lm_cnt, m.st_order, m.cov_ptr, m.cov_pose);
     laps.lap("engine: co-visibility");
-    bool helper_started = false;
-    // ---- the co-visibility lists decide the Hsc pattern: if they changed, its build, the ordering and the
-    // symbolic factorisation start NOW, beside the rest of this function (see Impl::pat_thread)
-    m.join_pattern();
-    if (m.pat_err)
-    {
-        m.pat_err = nullptr; // a failed helper of an earlier call: that structure was never used
-        m.pattern_dirty = true;
-    }
-    {
-        auto same = [](const auto& a, const auto& b) {
-            return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
-        };
-        const bool pat_same = !m.pattern_dirty && m.opt.structure_reuse && m.P == m.pat_P &&
-                              m.L == m.pat_L && same(m.cov_ptr, m.pat_cov_ptr) && same(m.cov_pose, m.pat_cov_pose);
-        m.pat_async_ok = false;
-        m.lists_built = false;
-        m.pat_stage.store(0, std::memory_order_relaxed);
-        if (!pat_same)
-        {
-            m.pattern_dirty = true;
-            m.plan_uploaded = false;
-            const bool device_build = !m.plan_only && !m.opt.schur_plan && !m.opt.host_structure;
-            if (device_build && m.opt.async_structure && m.P > 0 && !m.cov_pose.empty())
-            {
-                if (!m.s2)
-                    m.s2 = cache_stream_acquire();
-                m.pat_thread = std::thread([this] {
-                    Impl& mm = *impl_;
-                    try
-                    {
-                        // (the current device is per thread: a rank of a multi-GPU job runs on LOCAL_RANK, not 0)
-                        CUGO_HIP(hipSetDevice(mm.ctx.device));
-                        const auto t0p = Clock::now();
-                        if (!build_pattern_gpu(mm.s2, mm.P, mm.L, mm.cov_ptr.data(), mm.cov_pose.data(), mm.gstruct))
-                        {
-                            mm.pat_stage.store(-1, std::memory_order_release);
-                            return;
-                        }
-                        mm.pat_stage.store(1, std::memory_order_release);
-                        mm.hsc_rowptr = mm.gstruct.h_rowptr, mm.hsc_colind = mm.gstruct.h_colind;
-                        prof_[PROF_BUILD_STRUCTURE] += ms_since(t0p);
-                        const auto t1p = Clock::now();
-                        mm.chol.analyze_host(mm.P, mm.hsc_rowptr.data(), mm.hsc_colind.data());
-                        // ... and the plan goes to the device from here as well (second stream; upload() waits for
-                        // its copies): the first optimize() then only builds the contribution lists
-                        mm.chol.upload(mm.s2);
-                        mm.plan_uploaded = true;
-                        prof_[PROF_SYMBOLIC] += ms_since(t1p);
-                        mm.pat_async_ok = true;
-                    }
-                    catch (...)
-                    {
-                        mm.pat_err = std::current_exception();
-                        mm.pat_stage.store(-1, std::memory_order_release);
-                    }
-                });
-                helper_started = true;
-            }
-        }
-    }
-    // ---- shard: contiguous landmark range balanced by edge count -----------------------
-    int l0 = 0, l1 = m.Lall;
-    shard_range(lm_cnt, m.rank, m.world, l0, l1);
-    m.shard_l0 = l0, m.shard_l1 = l1;
-    // Slot layout of this shard's edges: landmark-major, padded with inactive slots so that no
-    // landmark with <= 256 edges straddles a 256-slot boundary (k_build_edges / the back-
-    // substitution sum a landmark's edges inside one workgroup).  A padding slot belongs to
-    // the landmark before it; slot_src[i] = index into `order`, or -1 for padding.
-    constexpr int kBlock = 256;
-    std::vector<int32_t>& slot_src = m.st_slot_src;
-    m.h_lm_ptr.assign(m.Lall + 1, 0);
-    {
-        // first the start slot of every landmark (sequential: a padding decision moves everything
-        // behind it), then the slots are filled per landmark range in parallel
-        std::vector<int32_t> start((size_t)(l1 - l0) + 1, 0);
-        int pos = 0, last_l = -1; // last_l: last landmark that owns slots
-        for (int l = l0; l < l1; l++)
-        {
-            const int k = lm_cnt[l + 1] - lm_cnt[l];
-            if (k > 0 && k <= kBlock && pos % kBlock + k > kBlock && last_l >= 0)
-            {
-                pos += kBlock - pos % kBlock;
-                for (int q = last_l + 1; q <= l; q++)
-                    m.h_lm_ptr[q] = pos; // the padding extends landmark last_l
-            }
-            m.h_lm_ptr[l] = pos;
-            start[l - l0] = pos;
-            pos += k;
-            if (k > 0)
-                last_l = l;
-        }
-        const int total = pos;
-        slot_src.assign((size_t)total, -1);
-        parallel_chunks((size_t)(l1 - l0), 65536, [&](size_t a, size_t b, unsigned) {
-            for (size_t q = a; q < b; q++)
-            {
-                const int l = l0 + (int)q;
-                int32_t* dst = slot_src.data() + start[q];
-                for (int i = lm_cnt[l]; i < lm_cnt[l + 1]; i++)
-                    *dst++ = i;
-            }
-        });
-        for (int l = l1; l <= m.Lall; l++)
-            m.h_lm_ptr[l] = total;
-        // lm_ptr[l] for l < l0 stays 0; fix up the entries between padded landmarks
-        for (int l = l0 + 1; l <= l1; l++)
-            m.h_lm_ptr[l] = std::max(m.h_lm_ptr[l], m.h_lm_ptr[l - 1]);
-    }
-    // does every landmark's slot range lie inside one 256-slot group?  (not if a landmark has more
-    // edges than that; the build pass may then not form T = Hpl invHll on the side, see optimize())
-    m.lm_in_one_group = true;
-    for (int l = 0; l < m.Lall && m.lm_in_one_group; l++)
-        if (m.h_lm_ptr[l + 1] > m.h_lm_ptr[l] && m.h_lm_ptr[l] / kBlock != (m.h_lm_ptr[l + 1] - 1) / kBlock)
-            m.lm_in_one_group = false;
+    // the helper starts before the slot work ...
+    const bool helper_started = m.start_pattern_helper(prof_);
+    shard_range(m.st_lm_cnt, m.rank, m.world, m.shard_l0, m.shard_l1);
+    m.lm_in_one_group = pad_slot_layout(m.st_lm_cnt, m.shard_l0, m.shard_l1, m.h_lm_ptr, m.st_slot_src);
     laps.lap("engine: slot layout");
-    const int E = (int)slot_src.size();
-    m.E = E;
-    m.h_e_pose.resize(E), m.h_e_lm.resize(E), m.h_flags.resize(E);
-    std::vector<double>&meas = m.st_meas, &omega = m.st_omega;
-    std::vector<uint16_t>& cam = m.st_cam;
-    meas.resize(3 * (size_t)E); // every slot is written by fill_slots
-    omega.clear(), cam.clear();
-    m.n_omega = g.e_omega.size() > 1 ? E : 1;
-    m.n_cams = (int)(g.cams.size() / 5);
-    if (m.n_omega > 1)
-        omega.resize(E);
-    else
-        omega.assign(1, g.e_omega.empty() ? 1.0 : g.e_omega[0]);
-    if (m.n_cams > 1)
-        cam.resize(E);
-    m.slot_edge.assign(E, -1);
-    m.slot_threshold.clear();
-    bool any_threshold = false;
-    for (double t : g.e_outlier_threshold)
-        any_threshold = any_threshold || t > 0.0;
-    if (any_threshold)
-        m.slot_threshold.assign(E, 0.0);
-    m.Etot = Etot;
+    m.E = (int)m.st_slot_src.size();
     m.last_err_buf = 0;
     m.xchg_bytes = 0, m.xchg_calls = 0;
-    auto fill_slots = [&](int ia, int ib) {
-        for (int i = ia; i < ib; i++)
-        {
-            if (slot_src[i] < 0)
-            { // padding: inactive edge of the landmark of the nearest real slot before it
-                int j = i - 1;
-                while (slot_src[j] < 0)
-                    j--;
-                m.h_e_pose[i] = 0;
-                m.h_e_lm[i] = g.e_lm[order[slot_src[j]]];
-                m.h_flags[i] = CUGO_EDGE_INACTIVE;
-                meas[i] = meas[(size_t)E + i] = meas[2 * (size_t)E + i] = 0.0;
-                if (m.n_omega > 1)
-                    omega[i] = 0.0;
-                if (m.n_cams > 1)
-                    cam[i] = 0;
-                continue;
-            }
-            const int e = order[slot_src[i]];
-            m.slot_edge[i] = e;
-            if (any_threshold)
-                m.slot_threshold[i] = g.e_outlier_threshold[e];
-            m.h_e_pose[i] = g.e_pose[e];
-            m.h_e_lm[i] = g.e_lm[e];
-            m.h_flags[i] = g.e_flags[e];
-            meas[i] = g.e_meas[3 * (size_t)e];
-            meas[(size_t)E + i] = g.e_meas[3 * (size_t)e + 1];
-            meas[2 * (size_t)E + i] = g.e_meas[3 * (size_t)e + 2];
-            if (m.n_omega > 1)
-                omega[i] = g.e_omega[e];
-            if (m.n_cams > 1)
-                cam[i] = g.e_cam[e];
-        }
-    };
-    // independent per slot: split over a few host threads for big graphs
-    parallel_chunks((size_t)E, 100000, [&](size_t a, size_t b, unsigned) { fill_slots((int)a, (int)b); });
+    fill_slots(g, m.st_order, m.st_slot_src, m.slots);
     laps.lap("engine: fill slots");
-    // ---- upload of the slot arrays and the estimates: copies from pageable memory block their caller, so a
-    // helper thread issues them while this one builds the pose-major view and hashes the topology (a plan-only
-    // engine has no device: it skips to the topology signature)
-    std::exception_ptr up_err; // (declared before the Joiner: the thread may still assign to it while unwinding)
-    struct Joiner
-    {
-        std::thread t;
-        hipStream_t s = nullptr;
-        bool wait_stream = false;
-        ~Joiner()
-        {
-            if (t.joinable())
-                t.join();
-            if (wait_stream && s) // unwinding: the staging vectors of the copies in flight are about to go
-                (void)hipStreamSynchronize(s);
-        }
-    } uploader;
-    uploader.s = s, uploader.wait_stream = !m.plan_only;
-    if (!m.plan_only)
-    {
-        m.d_e_pose.resize(m.h_e_pose.size()), m.d_e_lm.resize(m.h_e_lm.size()), m.d_flags.resize(m.h_flags.size());
-        m.d_meas.resize(meas.size()), m.d_omega.resize(omega.size()), m.d_cams.resize(g.cams.size());
-        if (m.n_cams > 1)
-            m.d_cam.resize(cam.size());
-        m.d_lm_ptr.resize(m.h_lm_ptr.size());
-        for (int k = 0; k < 2; k++)
-            m.d_poses[k].resize(g.poses.size()), m.d_lms[k].resize(g.lms.size());
-        auto uploads = [&] {
-            try
-            {
-                CUGO_HIP(hipSetDevice(m.ctx.device)); // (the current device is per thread)
-                m.d_e_pose.upload(m.h_e_pose, s), m.d_e_lm.upload(m.h_e_lm, s), m.d_flags.upload(m.h_flags, s);
-                m.d_lm_ptr.upload(m.h_lm_ptr, s);
-                m.d_meas.upload(meas, s), m.d_omega.upload(omega, s), m.d_cams.upload(g.cams, s);
-                if (m.n_cams > 1)
-                    m.d_cam.upload(cam, s);
-                for (int k = 0; k < 2; k++)
-                {
-                    m.d_poses[k].upload(g.poses, s);
-                    m.d_lms[k].upload(g.lms, s);
-                }
-            }
-            catch (...)
-            {
-                up_err = std::current_exception();
-            }
-        };
-        if (!m.opt.upload_thread) // (CUGO_UPLOAD_THREAD=0: the copies are issued by this thread)
-        {
-            uploads();
-            if (up_err)
-                std::rethrow_exception(up_err);
-        }
-        else
-            uploader.t = std::thread(uploads);
-    }
-    // ---- pose-major view (stable counting sort => ascending landmark inside a pose) ----
-    // threads own slot ranges: a histogram per thread, then offsets per (pose, thread) in thread
-    // order, so every thread places its own slots and the slot order inside a pose is kept
-    m.h_pose_ptr.assign(m.Pall + 1, 0);
-    m.h_pose_edge.assign(std::max(E, 1), 0);
-    {
-        const size_t serial_below = (size_t)m.Pall * pool_threads() > (size_t)E ? (size_t)E + 1 : 100000;
-        const int32_t* ep = m.h_e_pose.data();
-        const int32_t* src = slot_src.data();
-        std::vector<std::vector<int32_t>> hist(pool_threads());
-        const unsigned nt = parallel_chunks((size_t)E, serial_below, [&](size_t a, size_t b, unsigned t) {
-            std::vector<int32_t>& h = hist[t];
-            h.assign(m.Pall, 0);
-            for (size_t i = a; i < b; i++)
-                if (src[i] >= 0)
-                    h[ep[i]]++;
-        });
-        // per pose: its total over the threads' histograms (parallel over poses), the prefix sum over poses, then the
-        // first output position of every (pose, thread) — thread order inside a pose keeps the slot order
-        parallel_chunks((size_t)m.Pall, 2048, [&](size_t qa, size_t qb, unsigned) {
-            for (size_t q = qa; q < qb; q++)
-            {
-                int32_t c = 0;
-                for (unsigned t = 0; t < nt; t++)
-                    c += hist[t][q];
-                m.h_pose_ptr[q + 1] = c;
-            }
-        });
-        for (int q = 0; q < m.Pall; q++)
-            m.h_pose_ptr[q + 1] += m.h_pose_ptr[q];
-        parallel_chunks((size_t)m.Pall, 2048, [&](size_t qa, size_t qb, unsigned) {
-            for (size_t q = qa; q < qb; q++)
-            {
-                int32_t run = m.h_pose_ptr[q];
-                for (unsigned t = 0; t < nt; t++)
-                {
-                    const int32_t c = hist[t][q];
-                    hist[t][q] = run; // first output position of thread t for pose q
-                    run += c;
-                }
-            }
-        });
-        parallel_chunks((size_t)E, serial_below, [&](size_t a, size_t b, unsigned t) {
-            std::vector<int32_t>& pos = hist[t];
-            for (size_t i = a; i < b; i++)
-                if (src[i] >= 0)
-                    m.h_pose_edge[pos[ep[i]]++] = (int32_t)i;
-        });
-    }
+    // the upload of the slot arrays runs beside everything down to the upload sync
+    Impl::SlotUpload upload(m, g);
+    pose_major_view(m.Pall, m.slots.pose, m.st_slot_src, m.h_pose_ptr, m.h_pose_edge);
     laps.lap("engine: pose-major view");
-    // ---- point-to-plane / point-to-line edges: stable counting sort by pose, structure of arrays ----
-    {
-        const FlatIcpKind* kinds[2] = {&g.plane, &g.line};
-        for (int k = 0; k < 2; k++)
-        {
-            const FlatIcpKind& fk = *kinds[k];
-            Impl::IcpKindBufs& b = m.icpk[k];
-            const int n = fk.n(), gw = k == 0 ? 4 : 6;
-            b.h_ptr.assign((size_t)m.Pall + 1, 0);
-            for (int e = 0; e < n; e++)
-            {
-                if (fk.pose[e] < 0 || fk.pose[e] >= m.P)
-                    throw std::runtime_error("cugo: a point-to-plane / point-to-line edge is not on a free pose");
-                b.h_ptr[(size_t)fk.pose[e] + 1]++;
-            }
-            for (int q = 0; q < m.Pall; q++)
-                b.h_ptr[q + 1] += b.h_ptr[q];
-            b.h_pose.resize(n), b.slot_set.resize(n), b.slot_edge.resize(n);
-            b.h_p.resize(3 * (size_t)n), b.h_geo.resize((size_t)gw * n);
-            const bool per_edge = fk.omega.size() > 1;
-            b.h_omega.assign(per_edge ? (size_t)n : 1, fk.omega.empty() ? 1.0 : fk.omega[0]);
-            std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1);
-            for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
-            {
-                const size_t i = (size_t)pos[fk.pose[e]]++;
-                b.h_pose[i] = fk.pose[e];
-                b.slot_set[i] = fk.src_set[e], b.slot_edge[i] = fk.src_edge[e];
-                for (int c = 0; c < 3; c++)
-                    b.h_p[(size_t)c * n + i] = fk.p[3 * (size_t)e + c];
-                for (int c = 0; c < gw; c++)
-                    b.h_geo[(size_t)c * n + i] = fk.geo[(size_t)gw * e + c];
-                if (per_edge)
-                    b.h_omega[i] = fk.omega[e];
-            }
-            if (!m.plan_only)
-            {
-                b.d_pose.upload(b.h_pose, s), b.d_ptr.upload(b.h_ptr, s);
-                b.d_p.upload(b.h_p, s), b.d_geo.upload(b.h_geo, s), b.d_omega.upload(b.h_omega, s);
-            }
-        }
-        m.n_icp = g.plane.n() + g.line.n();
-        cugo_icp_edges& iv = m.icp;
-        iv = cugo_icp_edges{};
-        iv.n_poses_total = m.Pall, iv.n_poses_free = m.P;
-        iv.n_plane = g.plane.n(), iv.n_line = g.line.n();
-        iv.d_plane_pose = m.icpk[0].d_pose.data(), iv.d_plane_pose_ptr = m.icpk[0].d_ptr.data();
-        iv.d_plane_p = m.icpk[0].d_p.data(), iv.d_plane_nd = m.icpk[0].d_geo.data();
-        iv.d_plane_omega = m.icpk[0].d_omega.data(), iv.n_plane_omega = (int)m.icpk[0].h_omega.size();
-        iv.rk_plane = g.plane.rk, iv.delta_plane = g.plane.delta;
-        iv.d_line_pose = m.icpk[1].d_pose.data(), iv.d_line_pose_ptr = m.icpk[1].d_ptr.data();
-        iv.d_line_p = m.icpk[1].d_p.data(), iv.d_line_au = m.icpk[1].d_geo.data();
-        iv.d_line_omega = m.icpk[1].d_omega.data(), iv.n_line_omega = (int)m.icpk[1].h_omega.size();
-        iv.rk_line = g.line.rk, iv.delta_line = g.line.delta;
-        if (m.n_icp && !m.plan_only)
-            m.d_icp_scratch.resize(cugo_k::icp_scratch_doubles(iv));
-    }
+    m.bind_icp_edges(g);
     laps.lap("engine: ICP edge sort");
-    // ---- upload (a plan-only engine has no device: it skips to the topology signature) -----
+    // (a plan-only engine has no device: it skips to the topology compare)
     if (!m.plan_only)
     {
-    m.d_pose_ptr.upload(m.h_pose_ptr, s);
-    m.d_pose_edge.upload(m.h_pose_edge, s);
-    m.cur = 0;
-    m.d_Hpp.resize(36 * (size_t)m.P + 16), m.d_b.resize(6 * (size_t)m.P + 3 * (size_t)m.L + 16);
-    m.d_Hll.resize(9 * (size_t)m.L + 16), m.d_invHll.resize(9 * (size_t)m.L + 16);
-    {
+        m.d_pose_ptr.upload(m.h_pose_ptr, s);
+        m.d_pose_edge.upload(m.h_pose_edge, s);
+        m.cur = 0;
+        m.d_Hpp.resize(36 * (size_t)m.P + 16), m.d_b.resize(6 * (size_t)m.P + 3 * (size_t)m.L + 16);
+        m.d_Hll.resize(9 * (size_t)m.L + 16), m.d_invHll.resize(9 * (size_t)m.L + 16);
         // block streams: 18 doubles per edge slot, or 18 floats (= 9 doubles of storage)
         m.ev.block_f32 = (m.f32_blocks || m.opt.float32) ? 1 : 0;
-        const size_t per_edge = m.ev.block_f32 ? 9 : 18;
-        m.d_Hpl.resize(per_edge * (size_t)E + 16);
-        m.d_T.release(); // allocated on demand (gather kernels only), see optimize()
+        m.d_Hpl.resize((m.ev.block_f32 ? 9 : 18) * (size_t)m.E + 16);
+        m.d_T.release(); // allocated on demand (gather kernels only), see begin_call()
+        m.d_x.resize(6 * (size_t)m.P + 3 * (size_t)m.L + 16);
+        m.d_tmp.resize(36 * (size_t)m.P + 16);
+        m.d_scal.resize(16), m.d_fail.resize(4), m.h_scal.resize(16), m.h_fail.resize(4);
+        m.d_fail.zero(s); // [0] zero-pivot flag, [2] arrival counter of the trial's last launch
+        m.h_scal[5] = -1.0;
+        m.d_x.zero(s);
+        m.ctx.scratch.resize(cugo_k::reduce_scratch_doubles(m.E, m.P, m.L));
+        laps.lap("engine: enqueue uploads");
     }
-    m.d_x.resize(6 * (size_t)m.P + 3 * (size_t)m.L + 16);
-    m.d_tmp.resize(36 * (size_t)m.P + 16);
-    m.d_scal.resize(16), m.d_fail.resize(4), m.h_scal.resize(16), m.h_fail.resize(4);
-    m.d_fail.zero(s); // [0] zero-pivot flag, [2] arrival counter of the trial's last launch
-    m.h_scal[5] = -1.0;
-    m.d_x.zero(s);
-    m.ctx.scratch.resize(cugo_k::reduce_scratch_doubles(E, m.P, m.L));
-    laps.lap("engine: enqueue uploads");
-    }
-    bool uploads_done = m.plan_only;
-    auto finish_uploads = [&] {
-        if (uploads_done)
-            return;
-        if (uploader.t.joinable())
-            uploader.t.join();
-        if (up_err)
-            std::rethrow_exception(up_err);
-        CUGO_HIP(hipStreamSynchronize(s)); // host staging vectors go out of scope
-        uploader.wait_stream = false;
-        uploads_done = true;
-    };
-
-    cugo_edges& ev = m.ev;
-    ev.n_edges = E, ev.n_poses_total = m.Pall, ev.n_landmarks_total = m.Lall;
+    cugo_edges& ev = m.ev; // what the edge kernels get (null pointers on a plan-only engine)
+    ev.n_edges = m.E, ev.n_poses_total = m.Pall, ev.n_landmarks_total = m.Lall;
     ev.n_poses_free = m.P, ev.n_landmarks_free = m.L;
     ev.d_pose = m.d_e_pose.data(), ev.d_lm = m.d_e_lm.data(), ev.d_meas = m.d_meas.data();
-    ev.d_omega = m.d_omega.data(), ev.n_omega = m.n_omega, ev.d_flags = m.d_flags.data();
-    ev.d_cam = m.n_cams > 1 ? m.d_cam.data() : nullptr, ev.d_cams = m.d_cams.data();
-    ev.n_cams = m.n_cams, ev.d_lm_ptr = m.d_lm_ptr.data(), ev.d_pose_ptr = m.d_pose_ptr.data();
+    ev.d_omega = m.d_omega.data(), ev.n_omega = m.slots.n_omega, ev.d_flags = m.d_flags.data();
+    ev.d_cam = m.slots.n_cams > 1 ? m.d_cam.data() : nullptr, ev.d_cams = m.d_cams.data();
+    ev.n_cams = m.slots.n_cams, ev.d_lm_ptr = m.d_lm_ptr.data(), ev.d_pose_ptr = m.d_pose_ptr.data();
     ev.d_pose_edge = m.d_pose_edge.data();
+    // opt-in (CUGO_HSC_ROWS=1): the Schur complement by whole block rows (k_hsc_rows; slower)
+    m.rows_on = !m.plan_only && m.opt.hsc_rows && !m.opt.schur_plan;
+    if (m.rows_on)
     {
-        // opt-in (CUGO_HSC_ROWS=1): the Schur complement by whole block rows (k_hsc_rows).  Correct and
-        // list-free, but measured slower than the gather pair (355 vs 152 us per Schur complement on the
-        // kitti_00 shape): its per-product accumulation into LDS is a chain of dependent LDS round trips
-        // 
-        m.rows_on = !m.plan_only && m.opt.hsc_rows && !m.opt.schur_plan;
-        if (m.rows_on)
-        {
-            finish_uploads();
-            const int n = m.h_pose_ptr[m.Pall];
-            m.d_pose_rec.resize(4 * (size_t)std::max(n, 1) + 16);
-            cugo_k::launch_pose_rec(s, ev, n, m.d_pose_rec.data());
-        }
+        upload.finish();
+        const int n = m.h_pose_ptr[m.Pall];
+        m.d_pose_rec.resize(4 * (size_t)std::max(n, 1) + 16);
+        cugo_k::launch_pose_rec(s, m.ev, n, m.d_pose_rec.data());
     }
-    // Re-use of the Hsc structure, ordering and symbolic factor across optimize() calls when
-    // the topology is unchanged (ref: the isDirty logic of BlockSolver::buildStructure,
-    // block_solver.cpp:151-216, which skips the rebuild for clean edge sets).  Decided by comparing the
-    // flattened topology — slots, flags (a changed fixed flag is noticed too) and co-visibility lists — with
-    // the copy the structure at hand was built from: a parallel memcmp that stops at the first difference (a new
-    // graph costs next to nothing here; rounds 1-3 hashed all of it first, 0.4 ms of every full initialize()).
-    {
-        const int dims[8] = {m.Pall, m.Lall, m.P, m.L, E, m.rank, m.world, Etot};
-        auto same = [](const auto& a, const auto& b) {
-            if (a.size() != b.size())
-                return false;
-            const size_t bytes = a.size() * sizeof(a[0]);
-            if (bytes == 0)
-                return true;
-            const char* pa = reinterpret_cast<const char*>(a.data());
-            const char* pb = reinterpret_cast<const char*>(b.data());
-            std::atomic<bool> eq{true};
-            parallel_chunks(bytes, 1u << 18, [&](size_t lo, size_t hi, unsigned) {
-                for (size_t o = lo; o < hi && eq.load(std::memory_order_relaxed); o += 1u << 16)
-                    if (std::memcmp(pa + o, pb + o, std::min<size_t>(1u << 16, hi - o)) != 0)
-                        eq.store(false, std::memory_order_relaxed);
-            });
-            return eq.load();
-        };
-        const bool hit = m.opt.structure_reuse && m.sig_valid && std::memcmp(dims, m.sig_dims, sizeof dims) == 0 &&
-                         same(m.h_e_pose, m.sig_e_pose) && same(m.h_e_lm, m.sig_e_lm) &&
-                         same(m.h_flags, m.sig_flags) && same(m.cov_pose, m.sig_cov_pose);
-        if (!hit)
-            m.structure_dirty = true;
-        std::memcpy(m.pending_dims, dims, sizeof dims);
-    }
+    // Re-use of the Hsc structure, ordering and symbolic factor when the topology is unchanged (ref: the isDirty logic
+    // of BlockSolver::buildStructure, block_solver.cpp:151-216): slots, flags and co-visibility lists are compared with
+    // the copy the structure at hand was built from
+    const int dims[8] = {m.Pall, m.Lall, m.P, m.L, m.E, m.rank, m.world, m.Etot};
+    if (!(m.opt.structure_reuse && m.sig_valid && std::memcmp(dims, m.sig_dims, sizeof dims) == 0 &&
+          same_bytes(m.slots.pose, m.sig_e_pose) && same_bytes(m.slots.lm, m.sig_e_lm) &&
+          same_bytes(m.slots.flags, m.sig_flags) && same_bytes(m.cov_pose, m.sig_cov_pose)))
+        m.structure_dirty = true;
+    std::memcpy(m.pending_dims, dims, sizeof dims);
     laps.lap("engine: topology compare");
-    finish_uploads();
+    upload.finish();
     laps.lap("engine: upload sync");
-    // The contribution lists need the pattern (the helper's first 0.4 ms) and the slots on the device (just now):
-    // they are built here, on this stream, while the helper is still ordering and analysing — off the critical
-    // path of the first optimize()
+    // ... and the contribution lists, which need the helper's pattern and the slots on the device, are built after
+    // the upload sync, on this stream, while the helper is still ordering: off the path of the first optimize()
     if (helper_started && m.structure_dirty && !m.plan_only)
     {
         while (m.pat_stage.load(std::memory_order_acquire) == 0)
@@ -1460,7 +1013,7 @@ void Engine::fill_structure_stats(int B, double products, double offdiag_product
             char* to = reinterpret_cast<char*>(dst.data());
             parallel_chunks(bytes, 1u << 18, [&](size_t a, size_t b, unsigned) { std::memcpy(to + a, from + a, b - a); });
         };
-        copy(m.sig_e_pose, m.h_e_pose), copy(m.sig_e_lm, m.h_e_lm), copy(m.sig_flags, m.h_flags);
+        copy(m.sig_e_pose, m.slots.pose), copy(m.sig_e_lm, m.slots.lm), copy(m.sig_flags, m.slots.flags);
         copy(m.sig_cov_pose, m.cov_pose);
     }
     // row strips, opt-in (CUGO_HSC_STRIP=1; default: one wave per block anywhere): per product the position of
@@ -1617,19 +1170,122 @@ bool Engine::download_pinned(const double** poses, const double** lms)
     return true;
 }
 
-// Hsc pattern from landmark co-visibility + contribution lists + Cholesky analysis
-// (ref: buildStructure, block_solver.cpp:139-248)
+// ---- Engine::build_structure(): Hsc pattern from landmark co-visibility + contribution lists + Cholesky analysis
+// (ref: buildStructure, block_solver.cpp:139-248) — by one of two builders, adopted in one place
+void Engine::adopt_structure(const cugo_hsc_struct& hs, double products, double offdiag_products, double schur_slots)
+{
+    Impl& m = *impl_;
+    m.hs = hs;
+    if (!m.plan_only)
+        m.d_sys.resize(36 * (size_t)hs.n_blocks + 6 * (size_t)m.P + 16);
+    fill_structure_stats(hs.n_blocks, products, offdiag_products);
+    sstats_.schur_slots = schur_slots;
+    // (a plan-only engine builds its structure in every initialize(): nothing else would ever show a changed option)
+    m.structure_dirty = m.plan_only;
+}
+
+// Device-side build (structure_gpu.h): the same lists, in the same order, as the host passes; a shard builds the
+// pattern from the global co-visibility lists.  False: the device build refused, nothing was adopted.
+bool Engine::device_structure(InitLaps& laps)
+{
+    Impl& m = *impl_;
+    hipStream_t s = m.ctx.stream;
+    const int P = m.P, L = m.L;
+    const bool have_lists = m.lists_built && m.pat_async_ok; // (built at the end of initialize() for this pattern)
+    m.lists_built = false;
+    // phase 1 (unless the helper thread of initialize() has done it, or the lists are those of the
+    // pattern at hand): Hsc pattern from the co-visibility lists, ordering + symbolic factorisation
+    if (m.pattern_dirty && !m.pat_async_ok)
+    {
+        if (!build_pattern_gpu(s, P, L, m.cov_ptr.data(), m.cov_pose.data(), m.gstruct))
+            return false;
+        m.hsc_rowptr = m.gstruct.h_rowptr, m.hsc_colind = m.gstruct.h_colind;
+        prof_[PROF_BUILD_STRUCTURE] += ms_since(laps.t0);
+        const auto t1g = Clock::now();
+        m.chol.analyze_host(P, m.hsc_rowptr.data(), m.hsc_colind.data());
+        prof_[PROF_SYMBOLIC] += ms_since(t1g);
+    }
+    laps.lap("structure: pattern + symbolic (unless done beside initialize)");
+    // phase 2: the contribution lists from the slots on the device
+    const auto t2 = Clock::now();
+    if (!have_lists && !build_lists_gpu(s, m.E, P, m.Lall, m.d_e_pose.data(), m.d_flags.data(), m.d_lm_ptr.data(), m.gstruct))
+        return false;
+    laps.lap("structure: contribution lists (device)");
+    if (!m.plan_uploaded) // (the helper thread of initialize() uploads the plans it analyses)
+    {
+        m.chol.upload(s);
+        m.plan_uploaded = true;
+    }
+    if (m.pattern_dirty)
+        m.pat_P = P, m.pat_L = L, m.pat_cov_ptr = m.cov_ptr, m.pat_cov_pose = m.cov_pose;
+    m.pattern_dirty = false;
+    m.gstruct.scratch.release(), m.gstruct.scratch2.release();
+    cugo_hsc_struct hs{};
+    hs.n_blocks = m.gstruct.B;
+    hs.d_rowptr = m.gstruct.rowptr.data(), hs.d_colind = m.gstruct.colind.data();
+    hs.d_off_ptr = m.gstruct.off_ptr.data(), hs.d_off_ei = m.gstruct.off_ei.data();
+    hs.d_off_ej = m.gstruct.off_ej.data();
+    m.splan_on = false;
+    // all products of the graph (every free-free edge also has its diagonal one) / local off-diagonal ones
+    const double diag_products = m.world > 1 || m.comm ? (double)m.cov_pose.size() : count_free_free(m.slots.flags);
+    prof_[PROF_BUILD_STRUCTURE] += ms_since(t2);
+    laps.lap("structure: plan upload");
+    adopt_structure(hs, (double)m.gstruct.Mglobal + diag_products, (double)m.gstruct.Moff, 0);
+    return true;
+}
+
+void Engine::host_structure(InitLaps& laps)
+{
+    Impl& m = *impl_;
+    hipStream_t s = m.ctx.stream;
+    const int P = m.P;
+    // The landmark-major product plan (schur_plan.h) on request (CUGO_SCHUR_PLAN=1); unusable
+    // if a landmark's active edges straddle two slot groups
+    HostStructure hst;
+    SchurPlanHost sp;
+    cugo_host::host_structure(
+        P, m.L, m.cov_ptr, m.cov_pose, m.slots, m.h_lm_ptr, m.h_pose_ptr, m.h_pose_edge,
+        [&] {
+            if (m.opt.schur_plan)
+                build_schur_plan(m.E, P, m.slots.pose.data(), m.slots.lm.data(), m.slots.flags.data(),
+                                 m.hsc_rowptr.data(), m.hsc_colind.data(), sp);
+            laps.lap("structure: landmark-major product plan");
+            return m.splan_on = sp.usable;
+        },
+        [&](const char* what) { laps.lap(what); }, m.hsc_rowptr, m.hsc_colind, hst);
+    laps.lap("structure: product lists");
+    // off-diagonal products: from the lists, or (plan) all products minus one per free-free edge
+    const double n_offdiag = m.splan_on ? (double)sp.prod.size() - count_free_free(m.slots.flags) : (double)hst.off_ei.size();
+    cugo_hsc_struct hs{};
+    hs.n_blocks = (int)m.hsc_colind.size();
+    if (!m.plan_only)
+    {
+        m.d_hsc_rowptr.upload(m.hsc_rowptr, s), m.d_hsc_colind.upload(m.hsc_colind, s);
+        m.d_off_ptr.upload(hst.off_ptr, s), m.d_off_ei.upload(hst.off_ei, s), m.d_off_ej.upload(hst.off_ej, s);
+        CUGO_HIP(hipStreamSynchronize(s));
+        hs.d_rowptr = m.d_hsc_rowptr.data(), hs.d_colind = m.d_hsc_colind.data();
+        hs.d_off_ptr = m.d_off_ptr.data(), hs.d_off_ei = m.d_off_ei.data();
+        hs.d_off_ej = m.d_off_ej.data();
+        if (m.splan_on)
+        {
+            m.splan.upload(sp, s);
+            m.splan.fill(hs);
+        }
+        laps.lap("structure: uploads");
+    }
+    prof_[PROF_BUILD_STRUCTURE] += ms_since(laps.t0);
+    const auto t1 = Clock::now();
+    m.chol.analyze(P, m.hsc_rowptr.data(), m.hsc_colind.data());
+    prof_[PROF_SYMBOLIC] += ms_since(t1);
+    if (!m.plan_only)
+        laps.lap("structure: symbolic + plan upload");
+    adopt_structure(hs, hst.products, n_offdiag, m.splan_on ? sp.n_slots : 0);
+}
+
 void Engine::build_structure()
 {
     Impl& m = *impl_;
-    const auto t0 = Clock::now();
     InitLaps laps(m.opt.init_timing);
-    hipStream_t s = m.ctx.stream;
-    const int P = m.P, L = m.L;
-    // ---- device-side build: pairs per landmark -> stable radix sort by pose pair -> runs = off-diagonal
-    // blocks; the same lists, in the same order, as the host passes below (which remain for plan-only
-    // and forced runs).  A shard builds the pattern from the global co-visibility lists.
-    const bool shard = m.world > 1 || m.comm; // local slots are a subset: the pattern comes from the global lists
     m.join_pattern();
     if (m.pat_err)
     {
@@ -1637,278 +1293,13 @@ void Engine::build_structure()
         m.pat_err = nullptr;
         std::rethrow_exception(e);
     }
-    if (!m.plan_only && (m.E > 0 || shard) && !m.opt.schur_plan && !m.opt.host_structure &&
-        P > 0 && !m.cov_pose.empty())
-    {
-        // phase 1 (unless the helper thread of initialize() has done it, or the lists are those of the
-        // pattern at hand): Hsc pattern from the co-visibility lists, ordering + symbolic factorisation
-        bool ok = true;
-        if (m.pattern_dirty && !m.pat_async_ok)
-        {
-            ok = build_pattern_gpu(s, P, L, m.cov_ptr.data(), m.cov_pose.data(), m.gstruct);
-            if (ok)
-            {
-                m.hsc_rowptr = m.gstruct.h_rowptr, m.hsc_colind = m.gstruct.h_colind;
-                prof_[PROF_BUILD_STRUCTURE] += ms_since(t0);
-                const auto t1g = Clock::now();
-                m.chol.analyze_host(P, m.hsc_rowptr.data(), m.hsc_colind.data());
-                prof_[PROF_SYMBOLIC] += ms_since(t1g);
-            }
-        }
-        laps.lap("structure: pattern + symbolic (unless done beside initialize)");
-        // phase 2: the contribution lists from the slots on the device
-        const auto t2 = Clock::now();
-        const bool have_lists = m.lists_built && m.pat_async_ok; // (built at the end of initialize() for this pattern)
-        m.lists_built = false;
-        if (ok && (have_lists || build_lists_gpu(s, m.E, P, m.Lall, m.d_e_pose.data(), m.d_flags.data(), m.d_lm_ptr.data(), m.gstruct)))
-        {
-            laps.lap("structure: contribution lists (device)");
-            if (!m.plan_uploaded) // (the helper thread of initialize() uploads the plans it analyses)
-            {
-                m.chol.upload(s);
-                m.plan_uploaded = true;
-            }
-            if (m.pattern_dirty)
-                m.pat_P = P, m.pat_L = L, m.pat_cov_ptr = m.cov_ptr, m.pat_cov_pose = m.cov_pose;
-            m.pattern_dirty = false;
-            m.gstruct.scratch.release(), m.gstruct.scratch2.release();
-            const int B = m.gstruct.B;
-            m.d_sys.resize(36 * (size_t)B + 6 * (size_t)P + 16);
-            m.hs = cugo_hsc_struct{};
-            m.hs.n_blocks = B;
-            m.hs.d_rowptr = m.gstruct.rowptr.data(), m.hs.d_colind = m.gstruct.colind.data();
-            m.hs.d_off_ptr = m.gstruct.off_ptr.data(), m.hs.d_off_ei = m.gstruct.off_ei.data();
-            m.hs.d_off_ej = m.gstruct.off_ej.data();
-            m.splan_on = false;
-            double nff = 0;
-            {
-                std::vector<int64_t> part(pool_threads(), 0);
-                parallel_chunks((size_t)m.E, 100000, [&](size_t a, size_t b, unsigned t) {
-                    int64_t c = 0;
-                    for (size_t e = a; e < b; e++)
-                        c += (m.h_flags[e] & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P | CUGO_EDGE_INACTIVE)) == 0;
-                    part[t] = c;
-                });
-                for (int64_t c : part)
-                    nff += (double)c;
-            }
-            prof_[PROF_BUILD_STRUCTURE] += ms_since(t2);
-            laps.lap("structure: plan upload");
-            // all products of the graph (every free-free edge also has its diagonal one) / local off-diagonal ones
-            fill_structure_stats(B, (double)m.gstruct.Mglobal + (shard ? (double)m.cov_pose.size() : nff),
-                                 (double)m.gstruct.Moff);
-            sstats_.schur_slots = 0;
-            m.structure_dirty = false;
-            return;
-        }
-        m.pattern_dirty = true, m.plan_uploaded = false; // the host build below starts from scratch
-    }
-    m.pattern_dirty = true, m.plan_uploaded = false;
-    // pose-major view of the global co-visibility
-    std::vector<int32_t> pc_ptr(P + 1, 0), pc_lm(m.cov_pose.size());
-    for (int32_t p : m.cov_pose)
-        pc_ptr[p + 1]++;
-    for (int p = 0; p < P; p++)
-        pc_ptr[p + 1] += pc_ptr[p];
-    {
-        std::vector<int32_t> pos(pc_ptr.begin(), pc_ptr.end() - 1);
-        for (int l = 0; l < L; l++)
-            for (int k = m.cov_ptr[l]; k < m.cov_ptr[l + 1]; k++)
-                pc_lm[pos[m.cov_pose[k]]++] = l;
-    }
-    // The three passes below are independent per pose row: contiguous row ranges, balanced by
-    // their number of co-visibility entries, go to a few host threads (SLAM calls BA with a new
-    // topology every time, so this "cold" work is paid on every call there).
-    const unsigned nth = m.cov_pose.size() < 200000 ? 1u : std::max(1u, pool_threads());
-    std::vector<int> row_split(nth + 1, P);
-    row_split[0] = 0;
-    for (unsigned t = 1; t < nth; t++)
-    {
-        const int32_t target = (int32_t)((int64_t)pc_ptr[P] * t / nth);
-        row_split[t] = (int)(std::lower_bound(pc_ptr.begin(), pc_ptr.end(), target) - pc_ptr.begin());
-        row_split[t] = std::min(std::max(row_split[t], row_split[t - 1]), P);
-    }
-    auto parallel_rows = [&](const std::function<void(unsigned, int, int)>& fn) {
-        if (nth == 1)
-            return fn(0, 0, P);
-        struct RowCtx
-        {
-            const std::function<void(unsigned, int, int)>* fn;
-            const std::vector<int>* split;
-        } rc{&fn, &row_split};
-        pool_run(
-            nth,
-            [](void* p, unsigned t) {
-                RowCtx& c = *static_cast<RowCtx*>(p);
-                (*c.fn)(t, (*c.split)[t], (*c.split)[t + 1]);
-            },
-            &rc);
-    };
-    laps.lap("structure: pose-major covis");
-    // rows: diagonal first, then ascending columns (ref: sparse_block_matrix.cpp:80-155; O(M)
-    // with a marker array instead of the reference's dense P x P byte map)
-    m.hsc_rowptr.assign(P + 1, 0);
-    std::vector<std::vector<int32_t>> cols_t(nth);
-    std::vector<double> products_t(nth, 0.0);
-    parallel_rows([&](unsigned t, int p0, int p1) {
-        std::vector<int32_t> mark(P, -1);
-        std::vector<int32_t>& cols = cols_t[t];
-        double products = 0;
-        for (int p = p0; p < p1; p++)
-        {
-            const size_t start = cols.size();
-            cols.push_back(p);
-            mark[p] = p;
-            for (int i = pc_ptr[p]; i < pc_ptr[p + 1]; i++)
-            {
-                const int l = pc_lm[i];
-                for (int k = m.cov_ptr[l]; k < m.cov_ptr[l + 1]; k++)
-                {
-                    const int q = m.cov_pose[k];
-                    if (q >= p)
-                        products += 1;
-                    if (q > p && mark[q] != p)
-                    {
-                        mark[q] = p;
-                        cols.push_back(q);
-                    }
-                }
-            }
-            std::sort(cols.begin() + start + 1, cols.end());
-            m.hsc_rowptr[p + 1] = (int32_t)(cols.size() - start); // row length; prefix sum below
-        }
-        products_t[t] = products;
-    });
-    double products = 0;
-    m.hsc_colind.clear();
-    for (unsigned t = 0; t < nth; t++)
-    {
-        products += products_t[t];
-        m.hsc_colind.insert(m.hsc_colind.end(), cols_t[t].begin(), cols_t[t].end());
-    }
-    for (int p = 0; p < P; p++)
-        m.hsc_rowptr[p + 1] += m.hsc_rowptr[p];
-    const int B = (int)m.hsc_colind.size();
-    laps.lap("structure: Hsc pattern");
-    // Landmark-major product plan (schur_plan.h), on request (CUGO_SCHUR_PLAN=1): every Hpl block is
-    // then read once per Schur complement and T is never written (284 MB instead of 730 MB of
-    // memory-side traffic on the kitti_00 shape) — but the kernel pair takes as long as the
-    // destination-major gather kernels (196 vs 192 us there: half of its partial slots hold a single
-    // product) and the plan costs 4 ms more to build, so the gather kernels stay the default
-    // (DESIGN.md section 4b).  Unusable if a landmark's active edges straddle two 256-slot groups.
-    SchurPlanHost sp;
-    if (m.opt.schur_plan)
-        build_schur_plan(m.E, P, m.h_e_pose.data(), m.h_e_lm.data(), m.h_flags.data(), m.hsc_rowptr.data(),
-                         m.hsc_colind.data(), sp);
-    m.splan_on = sp.usable;
-    laps.lap("structure: landmark-major product plan");
-    // contribution lists of the off-diagonal blocks from the LOCAL edges, built row by row
-    // (pose-major): pos[q] gives the slot of column q in the current row, so every product is
-    // placed with O(1) work; inside a block the contributions are in ascending landmark order.
-    // A row only touches the counters / slots of its own blocks: rows are independent.
-    auto free_free = [&](int e) {
-        return (m.h_flags[e] & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P | CUGO_EDGE_INACTIVE)) == 0;
-    };
-    std::vector<int32_t> off_cnt(B + 1, 0);
-    if (!m.splan_on)
-    parallel_rows([&](unsigned, int p0, int p1) {
-        std::vector<int32_t> pos(P, -1);
-        for (int p = p0; p < p1; p++)
-        {
-            const int r0 = m.hsc_rowptr[p], r1 = m.hsc_rowptr[p + 1];
-            for (int k = r0; k < r1; k++)
-                pos[m.hsc_colind[k]] = k;
-            for (int i = m.h_pose_ptr[p]; i < m.h_pose_ptr[p + 1]; i++)
-            {
-                const int a = m.h_pose_edge[i];
-                if (!free_free(a))
-                    continue;
-                const int e1 = m.h_lm_ptr[m.h_e_lm[a] + 1];
-                for (int b = a + 1; b < e1; b++)
-                    if (free_free(b))
-                        off_cnt[pos[m.h_e_pose[b]] + 1]++;
-            }
-        }
-    });
-    for (int k = 0; k < B; k++)
-        off_cnt[k + 1] += off_cnt[k];
-    const size_t Moff = (size_t)off_cnt[B];
-    std::vector<int32_t> off_ei(Moff), off_ej(Moff);
-    if (!m.splan_on)
-    {
-        std::vector<int32_t> fill(off_cnt.begin(), off_cnt.end() - 1);
-        parallel_rows([&](unsigned, int p0, int p1) {
-            std::vector<int32_t> pos(P, -1);
-            for (int p = p0; p < p1; p++)
-            {
-                const int r0 = m.hsc_rowptr[p], r1 = m.hsc_rowptr[p + 1];
-                for (int k = r0; k < r1; k++)
-                    pos[m.hsc_colind[k]] = k;
-                for (int i = m.h_pose_ptr[p]; i < m.h_pose_ptr[p + 1]; i++)
-                {
-                    const int a = m.h_pose_edge[i];
-                    if (!free_free(a))
-                        continue;
-                    const int e1 = m.h_lm_ptr[m.h_e_lm[a] + 1];
-                    for (int b = a + 1; b < e1; b++)
-                        if (free_free(b))
-                        {
-                            const int q = fill[pos[m.h_e_pose[b]]]++;
-                            off_ei[q] = a;
-                            off_ej[q] = b;
-                        }
-                }
-            }
-        });
-    }
-    laps.lap("structure: product lists");
-    // off-diagonal products: from the lists, or (plan) all products minus one per free-free edge
-    double n_offdiag = (double)Moff;
-    if (m.splan_on)
-    {
-        double nff = 0;
-        for (int e = 0; e < m.E; e++)
-            nff += free_free(e);
-        n_offdiag = (double)sp.prod.size() - nff;
-    }
-    if (m.plan_only)
-    {
-        m.hs = cugo_hsc_struct{};
-        m.hs.n_blocks = B;
-        prof_[PROF_BUILD_STRUCTURE] += ms_since(t0);
-        const auto t1p = Clock::now();
-        m.chol.analyze(P, m.hsc_rowptr.data(), m.hsc_colind.data());
-        prof_[PROF_SYMBOLIC] += ms_since(t1p);
-        fill_structure_stats(B, products, n_offdiag);
-        sstats_.schur_slots = m.splan_on ? sp.n_slots : 0;
+    const bool shard = m.world > 1 || m.comm; // local slots are a subset: the pattern comes from the global lists
+    if (!m.plan_only && (m.E > 0 || shard) && !m.opt.schur_plan && !m.opt.host_structure && m.P > 0 &&
+        !m.cov_pose.empty() && device_structure(laps))
         return;
-    }
-    m.d_hsc_rowptr.upload(m.hsc_rowptr, s), m.d_hsc_colind.upload(m.hsc_colind, s);
-    m.d_off_ptr.upload(off_cnt, s), m.d_off_ei.upload(off_ei, s), m.d_off_ej.upload(off_ej, s);
-    m.d_sys.resize(36 * (size_t)B + 6 * (size_t)P + 16);
-    CUGO_HIP(hipStreamSynchronize(s));
-    m.hs.n_blocks = B;
-    m.hs.d_rowptr = m.d_hsc_rowptr.data(), m.hs.d_colind = m.d_hsc_colind.data();
-    m.hs.d_off_ptr = m.d_off_ptr.data(), m.hs.d_off_ei = m.d_off_ei.data();
-    m.hs.d_off_ej = m.d_off_ej.data();
-    if (m.splan_on)
-    {
-        m.splan.upload(sp, s);
-        m.splan.fill(m.hs);
-    }
-    else
-        SchurPlanDevice::clear(m.hs);
-    sstats_.schur_slots = m.splan_on ? sp.n_slots : 0;
-    laps.lap("structure: uploads");
-    prof_[PROF_BUILD_STRUCTURE] += ms_since(t0);
-
-    const auto t1 = Clock::now();
-    m.chol.analyze(P, m.hsc_rowptr.data(), m.hsc_colind.data());
-    prof_[PROF_SYMBOLIC] += ms_since(t1);
-    laps.lap("structure: symbolic + plan upload");
-
-    fill_structure_stats(B, products, n_offdiag);
-    m.structure_dirty = false;
+    // the host build starts from scratch, also after a refused device build
+    m.pattern_dirty = true, m.plan_uploaded = false;
+    host_structure(laps);
 }
 
 void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool verbose)
@@ -2143,7 +1534,7 @@ std::vector<int32_t> Engine::reject_outliers()
 {
     Impl& m = *impl_;
     std::vector<int32_t> out;
-    if (m.slot_threshold.empty() || m.E == 0)
+    if (m.slots.slot_threshold.empty() || m.E == 0)
         return out;
     hipStream_t s = m.ctx.stream;
     // chi2 per slot at the estimates of the last error pass (a rejected trial's estimates if the
@@ -2157,11 +1548,11 @@ std::vector<int32_t> Engine::reject_outliers()
     CUGO_HIP(hipStreamSynchronize(s));
     std::vector<int32_t> slots;
     for (int i = 0; i < m.E; i++)
-        if (m.slot_edge[i] >= 0 && m.slot_threshold[i] > 0.0 && !(m.h_flags[i] & CUGO_EDGE_INACTIVE) &&
-            chi[i] > m.slot_threshold[i])
+        if (m.slots.slot_edge[i] >= 0 && m.slots.slot_threshold[i] > 0.0 && !(m.slots.flags[i] & CUGO_EDGE_INACTIVE) &&
+            chi[i] > m.slots.slot_threshold[i])
             slots.push_back(i);
     for (int i : slots)
-        out.push_back(m.slot_edge[i]);
+        out.push_back(m.slots.slot_edge[i]);
     if (m.world > 1)
     { // every rank needs the union: one sum all-reduce of a 0/1 mask over the global edge ids
         std::vector<double> mask(m.Etot, 0.0);
@@ -2182,8 +1573,8 @@ std::vector<int32_t> Engine::reject_outliers()
     if (!out.empty())
     { // the flagged edges drop out of a further optimize() on the same initialisation, too
         for (int i : slots)
-            m.h_flags[i] |= CUGO_EDGE_INACTIVE;
-        m.d_flags.upload(m.h_flags, s);
+            m.slots.flags[i] |= CUGO_EDGE_INACTIVE;
+        m.d_flags.upload(m.slots.flags, s);
         if (m.rows_on) // the records of the pose-major list carry the flags
             cugo_k::launch_pose_rec(s, m.ev, m.h_pose_ptr[m.Pall], m.d_pose_rec.data());
         CUGO_HIP(hipStreamSynchronize(s));

@@ -13,6 +13,7 @@ namespace cugo_host
 {
 
 class RcclComm;
+struct InitLaps;
 struct Options;
 
 // Result of flattening a graph (ref: VertexSet::generateEstimateData + EdgeSet::init,
@@ -92,10 +93,6 @@ enum ProfItem
     PROF_UPDATE,
     PROF_COUNT
 };
-
-// contiguous landmark range of shard `rank`, balanced by edge count; lm_cnt is the
-// exclusive prefix sum of edges per landmark (size Lall+1)
-void shard_range(const std::vector<int32_t>& lm_cnt, int rank, int world, int& l0, int& l1);
 
 class Engine
 {
@@ -178,7 +175,10 @@ public:
     struct Impl;
 
 private:
-    void build_structure();
+    void build_structure(); // by device_structure() or host_structure(); both end in adopt_structure()
+    bool device_structure(InitLaps& laps);
+    void host_structure(InitLaps& laps);
+    void adopt_structure(const cugo_hsc_struct& hs, double products, double offdiag_products, double schur_slots);
     void fill_structure_stats(int B, double products, double offdiag_products);
     Impl* impl_;
     int E_global_ = 0;

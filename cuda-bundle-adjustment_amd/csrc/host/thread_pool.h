@@ -2,6 +2,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 namespace cugo_host
 {
@@ -37,6 +38,15 @@ inline unsigned parallel_chunks(size_t n, size_t serial_below, F&& f)
         },
         &ctx);
     return nt;
+}
+
+// f(t) for t in [0, nt), spread over the pool: for passes that cut their own ranges
+template <typename F>
+inline void pool_for(unsigned nt, F&& f)
+{
+    using Fn = typename std::remove_reference<F>::type;
+    pool_run(
+        nt, [](void* p, unsigned t) { (*static_cast<Fn*>(p))(t); }, const_cast<void*>(static_cast<const void*>(&f)));
 }
 
 } // namespace cugo_host

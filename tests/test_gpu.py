@@ -459,6 +459,27 @@ def test_structure_build_beside_initialize_is_the_synchronous_one(oracle_lib, mo
     assert runs[0][2][2]["hsc_blocks"] >= runs[0][0][2]["hsc_blocks"]
 
 
+def test_uploads_issued_by_the_calling_thread_give_the_same_run(oracle_lib, monkeypatch):
+    """initialize() hands the copies of the slot arrays and the estimates to an uploader thread (engine.cpp,
+    SlotUpload); CUGO_UPLOAD_THREAD=0 issues them from the calling thread.  Same arrays on the device either way:
+    bitwise the same run and the same structure"""
+    d, _ = synth_problem(oracle_lib, 150, 2200, 9000, seed=17, lc=60)
+    runs = []
+    for mode in (None, "0"):
+        if mode is None:
+            monkeypatch.delenv("CUGO_UPLOAD_THREAD", raising=False)
+        else:
+            monkeypatch.setenv("CUGO_UPLOAD_THREAD", mode)
+        g = cugo.graph_from_arrays(d)
+        g.initialize(); g.optimize(3)
+        runs.append(([s["chi2"] for s in g.stats()], g.poses().copy(), g.landmarks().copy(), g.structure_stats()))
+        g.close()
+    a, b = runs
+    assert a[0] and a[0] == b[0]
+    assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    assert a[3] == b[3]
+
+
 def test_initialize_again_with_more_landmarks_while_the_helper_may_still_run(oracle_lib):
     """initialize() starts a helper thread that reads the co-visibility lists, P and L; a second
     initialize() right behind it — on a graph that has GROWN (more landmarks, more edges: every one of those arrays is
