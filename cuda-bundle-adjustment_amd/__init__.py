@@ -63,6 +63,13 @@ class IcpEdges(C.Structure):
                 ("delta_line", C.c_double)]
 
 
+class PriorEdges(C.Structure):
+    """cugo_prior_edges: SE(3) pose priors with 6 x 6 information, pose-sorted structure of arrays (cugo_hip.h)."""
+    _fields_ = [("n_poses_total", C.c_int), ("n_poses_free", C.c_int), ("n", C.c_int),
+                ("d_pose", C.c_void_p), ("d_pose_ptr", C.c_void_p), ("d_meas", C.c_void_p), ("d_info", C.c_void_p),
+                ("n_info", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int), ("delta", C.c_double)]
+
+
 class HscStruct(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("d_rowptr", C.c_void_p), ("d_colind", C.c_void_p),
                 ("d_off_ptr", C.c_void_p), ("d_off_ei", C.c_void_p), ("d_off_ej", C.c_void_p),
@@ -308,6 +315,36 @@ class Graph:
     def n_icp_edges(self, kind):
         """active edges of the kind in the current flattening (edges on fixed poses are not counted)"""
         return lib().cugo_graph_n_icp_edges(self._g, int(kind))
+
+    def add_pose_priors(self, pose_ids, q_t7, info36=None):
+        """SE(3) pose priors (an extension; PosePriorEdgeSet): residual [Log_SO3(R R_z^T); t - R R_z^T t_z] against the
+        measured pose q_t7 [n, 7], cost r^T Omega r.  info36: [n, 6, 6] (or one 6 x 6 for all), order [rotation,
+        translation] as pose_covariances(); None for the set's matrix (set_prior_information)"""
+        n = len(pose_ids)
+        if n == 0:
+            return
+        pi = np.ascontiguousarray(pose_ids, np.int32)
+        z = np.ascontiguousarray(np.asarray(q_t7, np.float64).reshape(n, 7))
+        w = None if info36 is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(info36, np.float64).reshape(-1, 36), (n, 36)))
+        check(lib().cugo_graph_add_pose_priors(self._g, n, _p(pi, _i32p), _p(z, _f64p),
+                                               None if w is None else _p(w, _f64p)))
+
+    def set_prior_information(self, info36):
+        """the prior set's 6 x 6 information (used when per_edge_information is off, or for priors added without one)"""
+        w = np.ascontiguousarray(np.asarray(info36, np.float64).reshape(36))
+        check(lib().cugo_graph_set_prior_information(self._g, _p(w, _f64p)))
+
+    def set_prior_robust_kernel(self, rk_type, delta):
+        check(lib().cugo_graph_set_prior_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
+
+    def set_prior_outlier_threshold(self, threshold):
+        """only 0 is usable: initialize() refuses a positive threshold on the prior set (not built yet)"""
+        check(lib().cugo_graph_set_prior_outlier_threshold(self._g, C.c_double(threshold)))
+
+    def n_prior_edges(self):
+        """active priors in the current flattening (priors on fixed poses are not counted)"""
+        return lib().cugo_graph_n_prior_edges(self._g)
 
     def set_outlier_threshold(self, dim, threshold):
         """edges of the set (dim 2 mono / 3 stereo) with chi2 > threshold are inactivated at the

@@ -8,6 +8,7 @@
 #include "../../../include/cugo_hip.h"
 #include "../../include/cuda_graph_optimisation.h"
 #include "../../include/icp_types.h"
+#include "../../include/prior_types.h"
 #include "../kernels/kernels.h"
 #include "chol_solver.h"
 #include "edge_layout.h"
@@ -224,6 +225,74 @@ int cugo_icp_construct_quadratic_form(cugo_ctx* ctx, const cugo_icp_edges* ev, c
         const cugo_k::ReduceScratch rs = icp_scratch_for(ctx, ev);
         check_icp(ctx, ev, rs);
         cugo_k::launch_icp_build(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs, d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+} // extern "C"
+
+namespace
+{
+// as check_icp: pose_ptr on the host, the pose index of every edge against it on the device, before anything is launched
+cugo_k::ReduceScratch check_prior(cugo_ctx* ctx, const cugo_prior_edges* ev)
+{
+    if (!ev || ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total || ev->n < 0)
+        throw std::runtime_error("cugo_prior: bad pose or edge counts");
+    if (ev->n > (1 << 26))
+        throw std::runtime_error("cugo_prior: more than 2^26 edges (the kernel indexes the planar arrays with 32 bits)");
+    if (!ev->d_pose_ptr)
+        throw std::runtime_error("cugo_prior: no pose_ptr");
+    if (ev->rk < CUGO_RK_NONE || ev->rk > CUGO_RK_HUBER ||
+        (ev->rk != CUGO_RK_NONE && !(ev->delta > 0.0 && std::isfinite(ev->delta))))
+        throw std::runtime_error("cugo_prior: unknown robust kernel or bad delta");
+    if (ev->n > 0 && (!ev->d_pose || !ev->d_meas || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
+        throw std::runtime_error("cugo_prior: missing arrays");
+    const int P = ev->n_poses_total;
+    std::vector<int32_t> ptr(P + 1);
+    CUGO_HIP(hipMemcpyAsync(ptr.data(), ev->d_pose_ptr, sizeof(int32_t) * (P + 1), hipMemcpyDeviceToHost, ctx->stream));
+    CUGO_HIP(hipStreamSynchronize(ctx->stream));
+    if (ptr[0] != 0 || ptr[P] != ev->n)
+        throw std::runtime_error("cugo_prior: pose_ptr does not span the edges");
+    for (int p = 0; p < P; p++)
+        if (ptr[p + 1] < ptr[p])
+            throw std::runtime_error("cugo_prior: pose_ptr not ascending");
+    const size_t need = cugo_k::prior_scratch_doubles(*ev);
+    if (ctx->scratch.size() < need)
+    {
+        CUGO_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->scratch.resize(need);
+    }
+    const cugo_k::ReduceScratch rs{ctx->scratch.data(), ctx->scratch.size()};
+    if (cugo_k::prior_check_indices(ctx->stream, *ev, rs))
+        throw std::runtime_error("cugo_prior: edges not sorted by pose, or a pose index disagrees with pose_ptr");
+    return rs;
+}
+} // namespace
+
+extern "C" {
+
+int cugo_prior_compute_errors(cugo_ctx* ctx, const cugo_prior_edges* ev, const double* d_poses, double* d_chi,
+                              double* d_edge_chi)
+{
+    return guarded([&] {
+        const cugo_k::ReduceScratch rs = check_prior(ctx, ev);
+        if (d_edge_chi && ev->n > 0 && ev->n_poses_free < ev->n_poses_total) // (the kernel never visits a fixed pose)
+            CUGO_HIP(hipMemsetAsync(d_edge_chi, 0, sizeof(double) * ev->n, ctx->stream));
+        cugo_k::launch_prior_errors(ctx->stream, *ev, d_poses, rs.d_partials, d_edge_chi);
+        if (d_chi)
+            cugo_k::launch_prior_chi_total(ctx->stream, *ev, rs.d_partials, d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_prior_construct_quadratic_form(cugo_ctx* ctx, const cugo_prior_edges* ev, const double* d_poses, double* d_Hpp,
+                                        double* d_bp, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::ReduceScratch rs = check_prior(ctx, ev);
+        cugo_k::launch_prior_add(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs.d_partials);
+        if (d_chi)
+            cugo_k::launch_prior_chi_total(ctx->stream, *ev, rs.d_partials, d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
 }
@@ -476,6 +545,8 @@ struct cugo_graph
     cugo::StereoEdgeSet stereo;
     cugo::PlaneEdgeSet plane;
     cugo::LineEdgeSet line;
+    cugo::PosePriorEdgeSet prior;
+    std::deque<cugo::PosePriorEdge> prior_store;
     std::deque<cugo::PlaneEdge> plane_store;
     std::deque<cugo::LineEdge> line_store;
     std::deque<cugo::PoseVertex> pose_store;
@@ -493,6 +564,7 @@ struct cugo_graph
         opt->addEdgeSet(&stereo);
         opt->addEdgeSet(&plane);
         opt->addEdgeSet(&line);
+        opt->addEdgeSet(&prior);
         attached = true;
     }
 };
@@ -696,6 +768,47 @@ int cugo_graph_n_icp_edges(cugo_graph* g, int kind)
 {
     return kind == CUGO_ICP_PLANE || kind == CUGO_ICP_LINE ? g->opt->nIcpEdges(kind) : -1;
 }
+int cugo_graph_add_pose_priors(cugo_graph* g, int n, const int32_t* pose_ids, const double* q_t7, const double* info36)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids || !q_t7)))
+            throw std::invalid_argument("cugo_graph_add_pose_priors: missing arrays");
+        for (int i = 0; i < n; i++)
+            (void)icp_pose(g, pose_ids[i]); // (all or nothing: an unknown id adds no edge)
+        for (int i = 0; i < n; i++)
+        {
+            g->prior_store.emplace_back();
+            cugo::PosePriorEdge& e = g->prior_store.back();
+            e.setVertex(icp_pose(g, pose_ids[i]), 0);
+            const cugo::Se3D z(q_t7 + 7 * (size_t)i, q_t7 + 7 * (size_t)i + 4);
+            e.setMeasurement(cugo::PosePriorMatch<double>(z, info36 ? info36 + 36 * (size_t)i : g->prior.informationMatrix()));
+            g->prior.addEdge(&e);
+        }
+    });
+}
+int cugo_graph_set_prior_information(cugo_graph* g, const double* info36)
+{
+    return guarded([&] {
+        if (!info36)
+            throw std::invalid_argument("cugo_graph_set_prior_information: no matrix");
+        g->prior.setInformationMatrix(info36);
+    });
+}
+int cugo_graph_set_prior_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    return guarded([&] {
+        const cugo::RobustKernelType t = type == CUGO_RK_CAUCHY  ? cugo::RobustKernelType::Cauchy
+                                         : type == CUGO_RK_TUKEY ? cugo::RobustKernelType::Tukey
+                                         : type == CUGO_RK_HUBER ? cugo::RobustKernelType::Huber
+                                                                 : cugo::RobustKernelType::None;
+        g->prior.setRobustKernel(t, delta);
+    });
+}
+int cugo_graph_set_prior_outlier_threshold(cugo_graph* g, double threshold)
+{
+    return guarded([&] { g->prior.setOutlierThreshold(threshold); });
+}
+int cugo_graph_n_prior_edges(cugo_graph* g) { return g->opt->nPriorEdges(); }
 int cugo_graph_set_camera(cugo_graph* g, int dim, const double* c)
 {
     const cugo::Camera cam(c[0], c[1], c[2], c[3], c[4]);

@@ -407,6 +407,38 @@ void sort_icp_by_pose(const FlatIcpKind& fk, int Pall, int P, int gw, IcpKindHos
     }
 }
 
+void sort_priors_by_pose(const FlatPrior& fp, int Pall, int P, PriorHost& b)
+{
+    const int n = fp.n();
+    b.h_ptr.assign((size_t)Pall + 1, 0);
+    for (int e = 0; e < n; e++)
+    {
+        if (fp.pose[e] < 0 || fp.pose[e] >= P)
+            throw std::runtime_error("cugo: a pose prior is not on a free pose");
+        b.h_ptr[(size_t)fp.pose[e] + 1]++;
+    }
+    std::partial_sum(b.h_ptr.begin(), b.h_ptr.end(), b.h_ptr.begin());
+    b.h_pose.resize(n), b.slot_set.resize(n), b.slot_edge.resize(n);
+    b.h_meas.resize(7 * (size_t)n);
+    const bool per_edge = fp.info.size() > 21;
+    b.h_info.assign(21 * (per_edge ? (size_t)n : 1), 0.0);
+    if (!per_edge)
+        for (int c = 0; c < 21; c++)
+            b.h_info[c] = fp.info.empty() ? 0.0 : fp.info[c];
+    std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1);
+    for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
+    {
+        const size_t i = (size_t)pos[fp.pose[e]]++;
+        b.h_pose[i] = fp.pose[e];
+        b.slot_set[i] = fp.src_set[e], b.slot_edge[i] = fp.src_edge[e];
+        for (int c = 0; c < 7; c++)
+            b.h_meas[(size_t)c * n + i] = fp.z[7 * (size_t)e + c];
+        if (per_edge)
+            for (int c = 0; c < 21; c++)
+                b.h_info[(size_t)c * n + i] = fp.info[21 * (size_t)e + c];
+    }
+}
+
 // ---- the Hsc structure on the host: pose-major co-visibility, pattern (O(M) with a marker array instead of the
 // reference's dense P x P byte map, ref: sparse_block_matrix.cpp:80-155), then the off-diagonal product lists
 void host_structure(int P, int L, const Idx& cov_ptr, const Idx& cov_pose, const SlotArrays& slots, const Idx& lm_ptr,

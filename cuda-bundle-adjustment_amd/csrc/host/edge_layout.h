@@ -67,6 +67,14 @@ struct IcpKindHost
 };
 void sort_icp_by_pose(const FlatIcpKind& kind, int Pall, int P, int geo_width, IcpKindHost& out);
 
+// SE(3) pose priors sorted by pose (stable), planar: meas [7][n], info [21][n] or [21][1]
+struct PriorHost
+{
+    Idx h_pose, h_ptr, slot_set, slot_edge;
+    std::vector<double> h_meas, h_info;
+};
+void sort_priors_by_pose(const FlatPrior& prior, int Pall, int P, PriorHost& out);
+
 // ---- the Hsc structure on the host: pattern (upper block CSR, diagonal first) and, from the LOCAL slots, the
 // contributions of the off-diagonal blocks (ascending landmark inside a block).  use_plan() is asked once the pattern
 // exists: true = a landmark-major plan (schur_plan.h) serves and the lists stay empty.  lap(label) after every pass.

@@ -140,11 +140,30 @@ struct Engine::Impl : cugo_k::LaunchHook
     int n_icp = 0;
     DevBuf<double> d_icp_scratch;
     cugo_k::ReduceScratch icp_rs() { return {d_icp_scratch.data(), d_icp_scratch.size()}; }
-    // the chi2 totals of the chunks of the last ICP pass, for the launch that ends a trial
+    // SE(3) pose priors (prior_kernels.hip): sorted by pose, on the device as long as the flattening lives.  The chi2
+    // totals of their workgroups sit right behind the ICP chunk totals in d_icp_scratch (at its start without ICP edges)
+    struct PriorBufs : PriorHost
+    {
+        DevBuf<int32_t> d_pose, d_ptr;
+        DevBuf<double> d_meas, d_info;
+    } priork;
+    cugo_prior_edges prior{};
+    int n_prior = 0, n_prior_wg = 0;
+    double* prior_chi()
+    {
+        int n = 0;
+        return n_icp ? const_cast<double*>(cugo_k::icp_chunk_chi(icp, icp_rs(), &n)) + n : d_icp_scratch.data();
+    }
+    // the chi2 totals of the chunks of the last ICP pass and of the workgroups of the last prior pass, one array, for
+    // the launch that ends a trial
     const double* icp_chi(int* n)
     {
         *n = 0;
-        return n_icp ? cugo_k::icp_chunk_chi(icp, icp_rs(), n) : nullptr;
+        if (!n_icp && !n_prior_wg)
+            return nullptr;
+        const double* base = n_icp ? cugo_k::icp_chunk_chi(icp, icp_rs(), n) : d_icp_scratch.data();
+        *n += n_prior_wg;
+        return base;
     }
     cugo_hsc_struct hs{};
     SchurPlanDevice splan; // landmark-major product plan of the Schur complement (schur_plan.h)
@@ -182,6 +201,7 @@ struct Engine::Impl : cugo_k::LaunchHook
     struct SlotUpload;
     bool start_pattern_helper(double* prof);
     void bind_icp_edges(const FlatGraph& g);
+    void bind_prior_edges(const FlatGraph& g);
     std::vector<uint8_t> sig_flags;
 
     // optional HIP-event timing: 1 = an event pair round every kernel group AND every kernel (each pair adds a few
@@ -492,6 +512,17 @@ struct Engine::Impl : cugo_k::LaunchHook
                 if (d_chi)
                     cugo_k::launch_icp_chi_total(ctx.stream, icp, icp_rs(), d_chi, true);
             }
+            if (n_prior_wg)
+            { // ONE launch: the terms added to Hpp / bp behind k_build_poses, with the workgroups' chi2 totals.  In the
+              // one-stream form the add goes behind k_pose_schur (queue_schur), and only a pass whose chi2 is asked
+              // for — iteration 0, a trial that takes its chi2 from this pass — computes the totals here
+                if (!one_stream)
+                    cugo_k::launch_prior_add(ctx.stream, prior, d_poses[buf].data(), d_Hpp.data(), bp(), prior_chi());
+                else if (d_chi || chi_behind_scale)
+                    cugo_k::launch_prior_errors(ctx.stream, prior, d_poses[buf].data(), prior_chi());
+                if (d_chi) // (once per call, iteration 0)
+                    cugo_k::launch_prior_chi_total(ctx.stream, prior, prior_chi(), d_chi, true);
+            }
         });
         st.hpp_valid = !one_stream;
         st.fused_lambda = fuse ? fuse_lambda : -1.0;
@@ -510,6 +541,9 @@ struct Engine::Impl : cugo_k::LaunchHook
                                                                 d_poses[buf].data(), rs(), bp()});
             if (n_icp && one_stream)
                 cugo_k::launch_icp_add_schur(ctx.stream, icp, icp_rs(), hs.d_rowptr, Hsc(), bp(), bsc());
+            if (n_prior_wg && one_stream) // (the totals it leaves are those of the estimates in `buf` once more)
+                cugo_k::launch_prior_add_schur(ctx.stream, prior, d_poses[buf].data(), hs.d_rowptr, Hsc(), bp(), bsc(),
+                                               prior_chi());
         });
     }
     // diagnosis: CUGO_DEBUG_HASH=<file> — position-weighted integer checksums of the arrays every stage of the
@@ -893,6 +927,30 @@ void Engine::Impl::bind_icp_edges(const FlatGraph& g)
         d_icp_scratch.resize(cugo_k::icp_scratch_doubles(iv));
 }
 
+// SE(3) pose priors: sorted by pose, uploaded by the calling thread, and their view; the ICP scratch grows by their
+// workgroup totals (the 16 doubles of slack behind the chunk totals are only used by the kernel-level index check)
+void Engine::Impl::bind_prior_edges(const FlatGraph& g)
+{
+    sort_priors_by_pose(g.prior, Pall, P, priork);
+    n_prior = g.prior.n();
+    if (!plan_only && n_prior) // (a graph without priors uploads nothing and launches nothing)
+    {
+        hipStream_t s = ctx.stream;
+        priork.d_pose.upload(priork.h_pose, s), priork.d_ptr.upload(priork.h_ptr, s);
+        priork.d_meas.upload(priork.h_meas, s), priork.d_info.upload(priork.h_info, s);
+    }
+    cugo_prior_edges& pv = prior;
+    pv = cugo_prior_edges{};
+    pv.n_poses_total = Pall, pv.n_poses_free = P, pv.n = n_prior;
+    pv.d_pose = priork.d_pose.data(), pv.d_pose_ptr = priork.d_ptr.data();
+    pv.d_meas = priork.d_meas.data(), pv.d_info = priork.d_info.data();
+    pv.n_info = (int)(priork.h_info.size() / 21);
+    pv.rk = g.prior.rk, pv.delta = g.prior.delta;
+    n_prior_wg = cugo_k::prior_workgroups(pv);
+    if (n_prior_wg && !plan_only)
+        d_icp_scratch.resize((n_icp ? cugo_k::icp_scratch_doubles(icp) : 16) + (size_t)n_prior_wg);
+}
+
 void Engine::initialize(FlatGraph& g)
 {
     const auto t0 = Clock::now();
@@ -906,7 +964,9 @@ void Engine::initialize(FlatGraph& g)
     m.rk = g.rk;
     m.init_rank = m.rank, m.init_world = m.world;
     m.Etot = g.n_edges();
-    E_global_ = m.Etot + g.plane.n() + g.line.n();
+    E_global_ = m.Etot + g.plane.n() + g.line.n() + g.prior.n();
+    if (g.prior.n() && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: pose prior edge sets are not supported on a landmark-sharded (multi-GPU) optimiser yet");
     if ((g.plane.n() || g.line.n()) && (m.world > 1 || m.comm))
         throw std::runtime_error("cugo: point-to-plane / point-to-line edge sets are not supported on a landmark-sharded "
                                  "(multi-GPU) optimiser yet");
@@ -929,6 +989,7 @@ void Engine::initialize(FlatGraph& g)
     pose_major_view(m.Pall, m.slots.pose, m.st_slot_src, m.h_pose_ptr, m.h_pose_edge);
     laps.lap("engine: pose-major view");
     m.bind_icp_edges(g);
+    m.bind_prior_edges(g);
     laps.lap("engine: ICP edge sort");
     // (a plan-only engine has no device: it skips to the topology compare)
     if (!m.plan_only)
@@ -1456,6 +1517,8 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
                     const double* icp_chi = m.icp_chi(&n_icp_chi);
                     if (m.n_icp)
                         cugo_k::launch_icp_chunks(s, m.icp, m.d_poses[nxt].data(), false, m.icp_rs());
+                    if (m.n_prior_wg)
+                        cugo_k::launch_prior_errors(s, m.prior, m.d_poses[nxt].data(), m.prior_chi());
                     cugo_k::launch_errors_tail(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk, m.rs(),
                                                n_scale_part, m.d_scal.data() + 2, m.d_scal.data() + 4,
                                                m.h_scal.data() + 2, (double)++m.trial_seq,
@@ -1590,6 +1653,7 @@ const std::vector<int32_t>& Engine::icp_slot_source(int kind, bool set) const
     const Impl::IcpKindBufs& b = impl_->icpk[kind == 1 ? 1 : 0];
     return set ? b.slot_set : b.slot_edge;
 }
+int Engine::n_prior_edges() const { return impl_->n_prior; }
 int Engine::n_poses_free() const { return impl_->P; }
 int Engine::n_landmarks_free() const { return impl_->L; }
 

@@ -38,6 +38,24 @@ struct FlatIcpKind
     }
 };
 
+// SE(3) pose priors (prior_types.h), flattened in container order; priors on fixed poses, inactive ones and everything
+// invalid never get here (graph_optimisation.cpp validates and drops)
+struct FlatPrior
+{
+    std::vector<int32_t> pose; // free-first pose index per edge (always < P)
+    std::vector<double> z;     // E x 7 measured pose (q x y z w, t)
+    std::vector<double> info;  // E x 21 upper triangle of Omega, row-major packed; 21 when one matrix serves all
+    std::vector<int32_t> src_set, src_edge; // edge set (position among the optimiser's edge sets), position in its container
+    int rk = CUGO_RK_NONE;
+    double delta = 1.0;
+    int n() const { return (int)pose.size(); }
+    void clear()
+    {
+        pose.clear(), z.clear(), info.clear(), src_set.clear(), src_edge.clear();
+        rk = CUGO_RK_NONE, delta = 1.0;
+    }
+};
+
 struct FlatGraph
 {
     int Pall = 0, Lall = 0, P = 0, L = 0;
@@ -55,6 +73,7 @@ struct FlatGraph
     // the chi2 threshold of its edge set, 0 = disabled; empty = disabled for all
     std::vector<double> e_outlier_threshold;
     FlatIcpKind plane, line;
+    FlatPrior prior;
     int n_edges() const { return (int)e_pose.size(); }
 };
 
@@ -152,8 +171,9 @@ public:
     const std::vector<double>& cov_lm() const { return cov_lm_; }
     int n_poses_free() const;
     int n_landmarks_free() const;
-    int n_active_edges() const { return E_global_; } // BA + ICP edges of the current flattening
+    int n_active_edges() const { return E_global_; } // BA + ICP edges + priors of the current flattening
     int n_icp_edges(int kind) const;                  // 0 plane, 1 line
+    int n_prior_edges() const;
     // sorted slot of a kind -> {edge set, position in the set} as FlatIcpKind recorded them (kept for a later
     // outlier rejection on these sets)
     const std::vector<int32_t>& icp_slot_source(int kind, bool set) const;

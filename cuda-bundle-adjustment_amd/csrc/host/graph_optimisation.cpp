@@ -3,6 +3,7 @@
 // (initialize), src/optimisable_graph.hpp:84-154, 474-572 (index / flag / activeness rules).
 #include "../../include/cuda_graph_optimisation.h"
 #include "../../include/icp_types.h"
+#include "../../include/prior_types.h"
 
 #include <algorithm>
 #include <chrono>
@@ -70,6 +71,7 @@ void CudaGraphOptimisationImpl::exchangeStats(double& bytes, int& calls) const
 
 int CudaGraphOptimisationImpl::nActiveEdges() const { return engine_->n_active_edges(); }
 int CudaGraphOptimisationImpl::nIcpEdges(int kind) const { return engine_->n_icp_edges(kind); }
+int CudaGraphOptimisationImpl::nPriorEdges() const { return engine_->n_prior_edges(); }
 
 std::vector<double> CudaGraphOptimisationImpl::structureStats() const
 {
@@ -216,6 +218,135 @@ static void flattenIcpSet(BaseEdgeSet* es, int setIndex, bool line, bool perInfo
     es->setDirtyState(false);
 }
 
+// smallest and largest eigenvalue of a symmetric 6 x 6 matrix by cyclic Jacobi sweeps
+static void symEigenRange6(const double* A36, double& lo, double& hi)
+{
+    double a[6][6];
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++)
+            a[i][j] = 0.5 * (A36[6 * i + j] + A36[6 * j + i]);
+    for (int sweep = 0; sweep < 30; sweep++)
+    {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 6; j++)
+                (i == j ? diag : off) += a[i][j] * a[i][j];
+        if (off <= 1e-32 * diag || off == 0.0)
+            break;
+        for (int p = 0; p < 5; p++)
+            for (int q = p + 1; q < 6; q++)
+            {
+                if (a[p][q] == 0.0)
+                    continue;
+                const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+                for (int k = 0; k < 6; k++)
+                {
+                    const double akp = a[k][p], akq = a[k][q];
+                    a[k][p] = c * akp - sn * akq, a[k][q] = sn * akp + c * akq;
+                }
+                for (int k = 0; k < 6; k++)
+                {
+                    const double apk = a[p][k], aqk = a[q][k];
+                    a[p][k] = c * apk - sn * aqk, a[q][k] = sn * apk + c * aqk;
+                }
+            }
+    }
+    lo = hi = a[0][0];
+    for (int i = 1; i < 6; i++)
+        lo = std::min(lo, a[i][i]), hi = std::max(hi, a[i][i]);
+}
+
+// nullptr if Omega [36] can serve as an information matrix, else what is wrong with it
+static const char* checkInformation36(const double* A)
+{
+    double mx = 0.0;
+    for (int i = 0; i < 36; i++)
+    {
+        if (!std::isfinite(A[i]))
+            return "non-finite information";
+        mx = std::max(mx, std::fabs(A[i]));
+    }
+    for (int i = 0; i < 6; i++)
+        for (int j = i + 1; j < 6; j++)
+            if (std::fabs(A[6 * i + j] - A[6 * j + i]) > 1e-12 * mx)
+                return "the information matrix is not symmetric";
+    double lo, hi;
+    symEigenRange6(A, lo, hi);
+    if (lo < -1e-12 * std::max(hi, 0.0) || hi < 0.0)
+        return "the information matrix is not positive semi-definite";
+    return nullptr;
+}
+
+// One PosePriorEdgeSet (prior_types.h) into the flat arrays, in container order; the one place where these edges are
+// checked, as flattenIcpSet is for its kinds.  Omega goes on as the upper triangle of its symmetric part.
+static void flattenPriorSet(PosePriorEdgeSet* es, int setIndex, bool perInfo, const std::vector<BaseVertexSet*>& vertexSets,
+                            cugo_host::FlatPrior& out, bool& seen)
+{
+    auto refuse = [&](size_t i, const char* what) {
+        throw std::runtime_error("cugo: pose prior edge " + std::to_string(i) + " of edge set " + std::to_string(setIndex) +
+                                 ": " + what);
+    };
+    if (es->getOutlierThreshold() > 0.0)
+        throw std::runtime_error("cugo: outlier rejection is not available on pose prior edge sets yet "
+                                 "(setOutlierThreshold must stay 0)");
+    const RobustKernel& k = es->robustKernelData();
+    const int rk = rk_code(k.type());
+    const double delta = k.delta();
+    if (es->nedges() > 0)
+    {
+        if (seen && (rk != out.rk || (rk != CUGO_RK_NONE && delta != out.delta)))
+            throw std::runtime_error("cugo: the pose prior edge sets of one optimiser must use the same robust kernel");
+        if (!std::isfinite(delta) || (rk != CUGO_RK_NONE && !(delta > 0.0)))
+            throw std::runtime_error("cugo: bad robust kernel delta on a pose prior edge set");
+        out.rk = rk, out.delta = delta;
+        seen = true;
+        if (!perInfo)
+            if (const char* bad = checkInformation36(es->informationMatrix()))
+                throw std::runtime_error("cugo: pose prior edge set " + std::to_string(setIndex) + ": " + bad);
+    }
+    es->setOutlierCount(0);
+    size_t i = 0, kept = 0;
+    for (BaseEdge* e : es->get())
+    {
+        const size_t at = i++;
+        if (!e->isActive())
+            continue;
+        BaseVertex* v = e->getVertex(0);
+        bool known = false;
+        if (v && !v->isMarginilised())
+            for (const BaseVertexSet* vs : vertexSets)
+                known = known || (vs == v->ownerSet() && !vs->isMarginilised());
+        if (!known)
+            refuse(at, "its pose vertex is in no pose vertex set of this optimiser");
+        const auto& mz = *static_cast<const PosePriorMatch<double>*>(e->measurementData());
+        double z[7];
+        mz.pose.copyTo(z, z + 4);
+        for (int c = 0; c < 7; c++)
+            if (!std::isfinite(z[c]))
+                refuse(at, "non-finite measured pose");
+        const double len = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2] + z[3] * z[3]);
+        if (!(std::fabs(len - 1.0) <= 1e-6))
+            refuse(at, "the quaternion of the measured pose is not of unit length (it is used as given)");
+        const double* A = perInfo ? mz.information : es->informationMatrix();
+        if (perInfo)
+            if (const char* bad = checkInformation36(A))
+                refuse(at, bad);
+        if (v->isFixed())
+            continue;
+        out.pose.push_back(v->getIndex());
+        out.z.insert(out.z.end(), z, z + 7);
+        for (int r = 0; r < 6; r++)
+            for (int c = r; c < 6; c++)
+                out.info.push_back(0.5 * (A[6 * r + c] + A[6 * c + r]));
+        out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
+        kept++;
+    }
+    es->setActiveEdgeCount(kept);
+    es->setDirtyState(false);
+}
+
 void CudaGraphOptimisationImpl::initialize()
 {
     if (vertexSets.empty() || edgeSets.empty())
@@ -322,10 +453,10 @@ void CudaGraphOptimisationImpl::initialize()
     // the flattened order is exactly the container order.
     size_t cap = 0;
     for (BaseEdgeSet* es : edgeSets)
-        if (es->dim() != 1)
+        if (es->dim() != 1 && es->dim() != 6)
             cap += es->nedges();
-    g.plane.clear(), g.line.clear();
-    bool seen_plane = false, seen_line = false;
+    g.plane.clear(), g.line.clear(), g.prior.clear();
+    bool seen_plane = false, seen_line = false, seen_prior = false;
     g.e_pose.resize(cap), g.e_lm.resize(cap), g.e_flags.resize(cap);
     g.e_meas.resize(3 * cap), g.e_omega.resize(cap), g.e_cam.resize(cap);
     g.e_outlier_threshold.resize(cap);
@@ -354,6 +485,14 @@ void CudaGraphOptimisationImpl::initialize()
                 flattenIcpSet(es, (int)si, true, options.perEdgeInformation, vertexSets, g.line, seen_line);
             else
                 throw std::runtime_error("cugo: a 1-d edge set must be a PlaneEdgeSet or a LineEdgeSet (icp_types.h)");
+            continue;
+        }
+        if (dim == 6)
+        { // PosePriorEdgeSet (prior_types.h, an extension)
+            if (auto* ps = dynamic_cast<PosePriorEdgeSet*>(es))
+                flattenPriorSet(ps, (int)si, options.perEdgeInformation, vertexSets, g.prior, seen_prior);
+            else
+                throw std::runtime_error("cugo: a 6-d edge set must be a PosePriorEdgeSet (prior_types.h)");
             continue;
         }
         if (dim != 2 && dim != 3)
@@ -526,6 +665,14 @@ void CudaGraphOptimisationImpl::initialize()
             uniform = uniform && w == fk->omega[0];
         if (uniform)
             fk->omega.resize(1);
+    }
+    if (g.prior.n() > 1)
+    { // one matrix for all priors: a single entry
+        bool uniform = true;
+        for (size_t i = 21; uniform && i < g.prior.info.size(); i++)
+            uniform = g.prior.info[i] == g.prior.info[i % 21];
+        if (uniform)
+            g.prior.info.resize(21);
     }
     lap("graph: edge flatten");
 

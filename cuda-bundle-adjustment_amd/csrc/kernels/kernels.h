@@ -166,6 +166,28 @@ const double* icp_chunk_chi(const cugo_icp_edges& ev, ReduceScratch rs, int* n);
 // their sum to d_chi[0] (added to what is there with chi_add), in a launch of its own
 void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_chi, bool chi_add);
 
+// --- SE(3) pose priors with 6 x 6 information (prior_kernels.hip) --------------------------
+// One kernel per pass: 32 lanes per free pose walk its priors in container order and ADD their sums straight to the
+// destination; every workgroup leaves one chi2 total in d_wg_chi [prior_workgroups()].  The LM loop appends these
+// totals to the ICP chunk totals (icp_chunk_chi), so that the launch ending a trial sums them as well.
+int prior_workgroups(const cugo_prior_edges& ev); // 0 without edges or free poses: nothing is launched
+// scratch of the kernel-level entry points: the workgroup totals + 16 doubles (the flag of prior_check_indices)
+size_t prior_scratch_doubles(const cugo_prior_edges& ev);
+// with pose_ptr known to ascend from 0 to n: 1 if an edge does not lie in its pose's range, else 0.  Synchronises.
+int prior_check_indices(hipStream_t s, const cugo_prior_edges& ev, ReduceScratch rs);
+// chi2 only; d_edge_chi [n] (sorted order, 0 for edges that do not count) or nullptr
+void launch_prior_errors(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, double* d_wg_chi,
+                         double* d_edge_chi = nullptr);
+// the terms ADDED to d_Hpp / d_bp (behind k_build_poses) ...
+void launch_prior_add(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
+                      double* d_wg_chi);
+// ... or to the diagonal blocks of d_Hsc (upper block CSR d_rowptr: the first block of a row), d_bp and d_bsc (behind
+// k_pose_schur, which writes the three in the one-stream form)
+void launch_prior_add_schur(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, const int32_t* d_rowptr,
+                            double* d_Hsc, double* d_bp, double* d_bsc, double* d_wg_chi);
+// the sum of the workgroup totals to d_chi[0] (added to what is there with chi_add), in a launch of its own
+void launch_prior_chi_total(hipStream_t s, const cugo_prior_edges& ev, const double* d_wg_chi, double* d_chi, bool chi_add);
+
 // chi_e per edge slot (outlier rejection, ref: computeOutliersKernel cuda_block_solver.cu:1135)
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                      cugo_robust rk, double* d_chi_e);

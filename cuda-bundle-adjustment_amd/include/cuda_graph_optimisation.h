@@ -139,6 +139,8 @@ public:
     int nActiveEdges() const;
     /** active point-to-plane (kind 0) / point-to-line (kind 1) edges of the current flattening (icp_types.h) */
     int nIcpEdges(int kind) const;
+    /** active SE(3) pose priors of the current flattening (prior_types.h, an extension) */
+    int nPriorEdges() const;
     /** B, M, nnz(L), flops, supernodes, stages, front bytes, off-diagonal products, then per
      *  factorisation: potrf / trsm / syrk flops, extend-add bytes, backward bytes */
     std::vector<double> structureStats() const;

@@ -294,6 +294,46 @@ int cugo_icp_compute_errors(cugo_ctx* ctx, const cugo_icp_edges* ev, const doubl
 int cugo_icp_construct_quadratic_form(cugo_ctx* ctx, const cugo_icp_edges* ev, const double* d_poses, double* d_Hpp,
                                       double* d_bp, double* d_chi);
 
+/*
+ * Extension (the reference has no such edge): SE(3) pose priors, unary edges on a pose with a measurement
+ * Z = (q_z, t_z) and a full 6 x 6 information matrix Omega (symmetric, positive semi-definite).  With the pose (q, t)
+ * read as everywhere else and the left update T <- Exp([omega, upsilon]) T:
+ *   R_D = R(q) R(q_z)^T, t_D = t - R_D t_z (D = T Z^-1);  r = [ Log_SO3(R_D) ; t_D ]  (the tangent order of the
+ *   covariances of cugo_graph_get_pose_covariances);  J = dr/dxi = [ J_l^-1(phi) 0 ; -[t_D]x I ]
+ *   chi2 term rho(max(0, r^T Omega r)) with the set's robust kernel, weight w = rho'.
+ * At r = 0, J = I: a prior with Z = the estimate and Omega = Sigma^-1 is the Gaussian a marginal covariance describes.
+ * The edges are SORTED by pose index (ascending), structure of arrays; pose_ptr is the CSR over the pose index.  Edges
+ * on fixed poses (index >= n_poses_free) and edges flagged CUGO_EDGE_INACTIVE contribute nothing.
+ */
+typedef struct cugo_prior_edges
+{
+    int n_poses_total, n_poses_free;
+    int n;
+    const int32_t* d_pose;     /* [n] ascending */
+    const int32_t* d_pose_ptr; /* [n_poses_total+1] */
+    const double* d_meas;      /* [7][n] qx qy qz qw tx ty tz of Z */
+    const double* d_info;      /* [21][n] or [21][1]: upper triangle of Omega, row-major packed (00 01 .. 05 11 ..) */
+    int n_info;                /* n or 1 */
+    const uint8_t* d_flags;    /* [n] CUGO_EDGE_INACTIVE, or NULL: all active */
+    int rk;                    /* CUGO_RK_* */
+    double delta;
+} cugo_prior_edges;
+
+/* Writes the chi2 total to d_chi[0]; with d_edge_chi (optional, [n], sorted order) also the chi2 term of every edge
+ * (0 for edges that do not count).  Checks pose_ptr on the host and the pose index of every edge on the device before
+ * launching, and refuses a bad layout or an unknown kernel code with CUGO_ERR_INVALID (one flag is read back: the
+ * call synchronises once).  The values (finite, |q_z| = 1, Omega symmetric positive semi-definite) are the caller's.
+ * Deterministic. */
+int cugo_prior_compute_errors(cugo_ctx* ctx, const cugo_prior_edges* ev, const double* d_poses, double* d_chi,
+                              double* d_edge_chi);
+
+/* ADDS sum w J^T Omega J to d_Hpp [n_poses_free][36] and -sum w J^T Omega r to d_bp [n_poses_free][6], in the layout
+ * and with the sign of cugo_construct_quadratic_form / cugo_icp_construct_quadratic_form.  Writes the chi2 total to
+ * d_chi[0] if d_chi != NULL (the bits of cugo_prior_compute_errors).  A pose without priors keeps the bits of its
+ * blocks.  Index checks as above.  No atomics. */
+int cugo_prior_construct_quadratic_form(cugo_ctx* ctx, const cugo_prior_edges* ev, const double* d_poses, double* d_Hpp,
+                                        double* d_bp, double* d_chi);
+
 /* ---- (2) graph-level entry points ---------------------------------------------------- */
 
 typedef struct cugo_graph cugo_graph; /* CudaGraphOptimisationImpl + its vertex/edge sets */
@@ -342,6 +382,21 @@ int cugo_graph_set_icp_robust_kernel(cugo_graph* g, int kind, int type, double d
 int cugo_graph_set_icp_outlier_threshold(cugo_graph* g, int kind, double threshold);
 /* active edges of the kind in the current flattening (edges on fixed poses are not counted); -1: unknown kind */
 int cugo_graph_n_icp_edges(cugo_graph* g, int kind);
+/* Extension: SE(3) pose priors (PosePriorEdgeSet, cuda-bundle-adjustment_amd/include/prior_types.h), next to or instead
+ * of the other sets; term and conventions as for cugo_prior_edges above.  q_t7 [n][7]: the measured pose Z (q x y z w,
+ * then t); info36 [n][36]: Omega of every edge (symmetric, so row- and column-major agree), or NULL for the set's
+ * matrix (cugo_graph_set_prior_information; the identity until it is set).  As for the other sets, the per-edge values
+ * count when the graph was created with per_edge_information, the set's otherwise.  cugo_graph_initialize() refuses
+ * non-finite values, |q_z| off 1 by more than 1e-6, an Omega that is asymmetric beyond 1e-12 max|Omega| or has an
+ * eigenvalue below -1e-12 lambda_max (semi-definite is allowed: a translation-only prior), a pose of no pose set of
+ * the optimiser, an outlier threshold on the set and a sharded optimiser; edges on fixed poses count for nothing. */
+int cugo_graph_add_pose_priors(cugo_graph* g, int n, const int32_t* pose_ids, const double* q_t7, const double* info36);
+int cugo_graph_set_prior_information(cugo_graph* g, const double* info36);
+int cugo_graph_set_prior_robust_kernel(cugo_graph* g, int type, double delta);
+/* only 0 is usable for now: with a positive value cugo_graph_initialize() refuses the graph */
+int cugo_graph_set_prior_outlier_threshold(cugo_graph* g, double threshold);
+/* active priors in the current flattening (priors on fixed poses are not counted) */
+int cugo_graph_n_prior_edges(cugo_graph* g);
 /* multi-GPU: this process handles shard `rank` of `world` (landmark ranges).  exchange() is
  * called on the host with a DEVICE buffer that must be all-reduced in place over all ranks
  * (op 0 = sum, 1 = max) before it returns, or — op >= 2 — overwritten on every rank with rank
