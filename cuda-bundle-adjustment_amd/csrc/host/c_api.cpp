@@ -149,57 +149,69 @@ int cugo_construct_quadratic_form(cugo_ctx* ctx, const cugo_edges* ev, const dou
 
 namespace
 {
-// the ICP kernels index their partials by (chunk + pose) and read pose_ptr: before anything is launched, pose_ptr
-// (n_poses_total + 1 entries) is checked on the host and the pose index of every edge against it on the device
-// (one flag comes back), so that a bad layout is refused instead of addressing memory out of range
-void check_icp_kind(cugo_ctx* ctx, const char* what, int n, int P, const int32_t* d_pose, const int32_t* d_ptr,
-                    const double* d_p, const double* d_geo, const double* d_omega, int n_omega, int rk, double delta)
+// The pose edge kernels read pose_ptr and index by it (the ICP kernels their partials by chunk + pose): before anything
+// is launched, pose_ptr (P + 1 entries) is checked on the host and the pose index of every edge against it on the
+// device (check_pose_indices: one flag comes back), so that a bad layout is refused instead of addressing memory out
+// of range.  label: " (plane)" / " (line)" behind the ICP messages; arrays_missing: what the kind needs with n > 0
+void check_pose_kind(cugo_ctx* ctx, const char* prefix, const std::string& label, int n, int P, const int32_t* d_pose,
+                     const int32_t* d_ptr, int rk, double delta, bool arrays_missing)
 {
-    const std::string in = std::string(" (") + what + ")";
-    if (n < 0)
-        throw std::runtime_error("cugo_icp: negative edge count" + in);
+    auto refuse = [&](const char* what) { throw std::runtime_error(std::string(prefix) + ": " + what + label); };
     if (!d_ptr)
-        throw std::runtime_error("cugo_icp: no pose_ptr" + in);
+        refuse("no pose_ptr");
     if (rk < CUGO_RK_NONE || rk > CUGO_RK_HUBER || (rk != CUGO_RK_NONE && !(delta > 0.0 && std::isfinite(delta))))
-        throw std::runtime_error("cugo_icp: unknown robust kernel or bad delta" + in);
-    if (n > 0 && (!d_pose || !d_p || !d_geo || !d_omega || (n_omega != 1 && n_omega != n)))
-        throw std::runtime_error("cugo_icp: missing arrays" + in);
+        refuse("unknown robust kernel or bad delta");
+    if (n > 0 && (!d_pose || arrays_missing))
+        refuse("missing arrays");
     std::vector<int32_t> ptr(P + 1);
     CUGO_HIP(hipMemcpyAsync(ptr.data(), d_ptr, sizeof(int32_t) * (P + 1), hipMemcpyDeviceToHost, ctx->stream));
     CUGO_HIP(hipStreamSynchronize(ctx->stream));
     if (ptr[0] != 0 || ptr[P] != n)
-        throw std::runtime_error("cugo_icp: pose_ptr does not span the edges" + in);
+        refuse("pose_ptr does not span the edges");
     for (int p = 0; p < P; p++)
         if (ptr[p + 1] < ptr[p])
-            throw std::runtime_error("cugo_icp: pose_ptr not ascending" + in);
+            refuse("pose_ptr not ascending");
 }
 
-void check_icp(cugo_ctx* ctx, const cugo_icp_edges* ev, cugo_k::ReduceScratch rs)
+// the context's scratch with room for what a kind's launchers need + 16 doubles of slack for the flag of the index check
+cugo_k::ReduceScratch pose_scratch_for(cugo_ctx* ctx, size_t need)
 {
-    check_icp_kind(ctx, "plane", ev->n_plane, ev->n_poses_total, ev->d_plane_pose, ev->d_plane_pose_ptr, ev->d_plane_p,
-                   ev->d_plane_nd, ev->d_plane_omega, ev->n_plane_omega, ev->rk_plane, ev->delta_plane);
-    check_icp_kind(ctx, "line", ev->n_line, ev->n_poses_total, ev->d_line_pose, ev->d_line_pose_ptr, ev->d_line_p,
-                   ev->d_line_au, ev->d_line_omega, ev->n_line_omega, ev->rk_line, ev->delta_line);
-    if (cugo_k::icp_check_indices(ctx->stream, *ev, rs))
-        throw std::runtime_error("cugo_icp: edges not sorted by pose, or a pose index disagrees with pose_ptr");
+    if (ctx->scratch.size() < need + 16)
+    {
+        CUGO_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->scratch.resize(need + 16);
+    }
+    return {ctx->scratch.data(), ctx->scratch.size()};
 }
 
-void check_icp_counts(const cugo_icp_edges* ev)
+void check_pose_indices(cugo_ctx* ctx, const char* prefix, const char* who, std::initializer_list<cugo_k::PoseIndexCheck> kinds,
+                        int P, cugo_k::ReduceScratch rs, size_t need)
+{
+    if (cugo_k::pose_check_indices(ctx->stream, who, kinds.begin(), (int)kinds.size(), P, reinterpret_cast<int*>(rs.d_partials + need)))
+        throw std::runtime_error(std::string(prefix) + ": edges not sorted by pose, or a pose index disagrees with pose_ptr");
+}
+
+cugo_k::ReduceScratch check_icp(cugo_ctx* ctx, const cugo_icp_edges* ev)
 {
     if (!ev || ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total ||
         ev->n_plane < 0 || ev->n_line < 0)
         throw std::runtime_error("cugo_icp: bad pose or edge counts");
-}
-
-cugo_k::ReduceScratch icp_scratch_for(cugo_ctx* ctx, const cugo_icp_edges* ev)
-{
+    const int P = ev->n_poses_total;
     const size_t need = cugo_k::icp_scratch_doubles(*ev);
-    if (ctx->scratch.size() < need)
-    {
-        CUGO_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->scratch.resize(need);
-    }
-    return {ctx->scratch.data(), ctx->scratch.size()};
+    const cugo_k::ReduceScratch rs = pose_scratch_for(ctx, need);
+    check_pose_kind(ctx, "cugo_icp", " (plane)", ev->n_plane, P, ev->d_plane_pose, ev->d_plane_pose_ptr, ev->rk_plane,
+                    ev->delta_plane,
+                    !ev->d_plane_p || !ev->d_plane_nd || !ev->d_plane_omega ||
+                        (ev->n_plane_omega != 1 && ev->n_plane_omega != ev->n_plane));
+    check_pose_kind(ctx, "cugo_icp", " (line)", ev->n_line, P, ev->d_line_pose, ev->d_line_pose_ptr, ev->rk_line,
+                    ev->delta_line,
+                    !ev->d_line_p || !ev->d_line_au || !ev->d_line_omega ||
+                        (ev->n_line_omega != 1 && ev->n_line_omega != ev->n_line));
+    check_pose_indices(ctx, "cugo_icp", "ICP",
+                       {{ev->d_plane_pose, ev->d_plane_pose_ptr, ev->n_plane, "k_icp_check"},
+                        {ev->d_line_pose, ev->d_line_pose_ptr, ev->n_line, "k_icp_check"}},
+                       P, rs, need);
+    return rs;
 }
 } // namespace
 
@@ -209,9 +221,7 @@ int cugo_icp_compute_errors(cugo_ctx* ctx, const cugo_icp_edges* ev, const doubl
                             double* d_edge_chi)
 {
     return guarded([&] {
-        check_icp_counts(ev);
-        const cugo_k::ReduceScratch rs = icp_scratch_for(ctx, ev);
-        check_icp(ctx, ev, rs);
+        const cugo_k::ReduceScratch rs = check_icp(ctx, ev);
         cugo_k::launch_icp_errors(ctx->stream, *ev, d_poses, rs, d_chi, false, d_edge_chi);
         CUGO_HIP(hipGetLastError());
     });
@@ -221,9 +231,7 @@ int cugo_icp_construct_quadratic_form(cugo_ctx* ctx, const cugo_icp_edges* ev, c
                                       double* d_bp, double* d_chi)
 {
     return guarded([&] {
-        check_icp_counts(ev);
-        const cugo_k::ReduceScratch rs = icp_scratch_for(ctx, ev);
-        check_icp(ctx, ev, rs);
+        const cugo_k::ReduceScratch rs = check_icp(ctx, ev);
         cugo_k::launch_icp_build(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs, d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
@@ -240,31 +248,12 @@ cugo_k::ReduceScratch check_prior(cugo_ctx* ctx, const cugo_prior_edges* ev)
         throw std::runtime_error("cugo_prior: bad pose or edge counts");
     if (ev->n > (1 << 26))
         throw std::runtime_error("cugo_prior: more than 2^26 edges (the kernel indexes the planar arrays with 32 bits)");
-    if (!ev->d_pose_ptr)
-        throw std::runtime_error("cugo_prior: no pose_ptr");
-    if (ev->rk < CUGO_RK_NONE || ev->rk > CUGO_RK_HUBER ||
-        (ev->rk != CUGO_RK_NONE && !(ev->delta > 0.0 && std::isfinite(ev->delta))))
-        throw std::runtime_error("cugo_prior: unknown robust kernel or bad delta");
-    if (ev->n > 0 && (!ev->d_pose || !ev->d_meas || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
-        throw std::runtime_error("cugo_prior: missing arrays");
-    const int P = ev->n_poses_total;
-    std::vector<int32_t> ptr(P + 1);
-    CUGO_HIP(hipMemcpyAsync(ptr.data(), ev->d_pose_ptr, sizeof(int32_t) * (P + 1), hipMemcpyDeviceToHost, ctx->stream));
-    CUGO_HIP(hipStreamSynchronize(ctx->stream));
-    if (ptr[0] != 0 || ptr[P] != ev->n)
-        throw std::runtime_error("cugo_prior: pose_ptr does not span the edges");
-    for (int p = 0; p < P; p++)
-        if (ptr[p + 1] < ptr[p])
-            throw std::runtime_error("cugo_prior: pose_ptr not ascending");
-    const size_t need = cugo_k::prior_scratch_doubles(*ev);
-    if (ctx->scratch.size() < need)
-    {
-        CUGO_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->scratch.resize(need);
-    }
-    const cugo_k::ReduceScratch rs{ctx->scratch.data(), ctx->scratch.size()};
-    if (cugo_k::prior_check_indices(ctx->stream, *ev, rs))
-        throw std::runtime_error("cugo_prior: edges not sorted by pose, or a pose index disagrees with pose_ptr");
+    check_pose_kind(ctx, "cugo_prior", "", ev->n, ev->n_poses_total, ev->d_pose, ev->d_pose_ptr, ev->rk, ev->delta,
+                    !ev->d_meas || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n));
+    const size_t need = (size_t)cugo_k::prior_workgroups(*ev);
+    const cugo_k::ReduceScratch rs = pose_scratch_for(ctx, need);
+    check_pose_indices(ctx, "cugo_prior", "prior", {{ev->d_pose, ev->d_pose_ptr, ev->n, "k_prior_check"}}, ev->n_poses_total,
+                       rs, need);
     return rs;
 }
 } // namespace
@@ -280,7 +269,7 @@ int cugo_prior_compute_errors(cugo_ctx* ctx, const cugo_prior_edges* ev, const d
             CUGO_HIP(hipMemsetAsync(d_edge_chi, 0, sizeof(double) * ev->n, ctx->stream));
         cugo_k::launch_prior_errors(ctx->stream, *ev, d_poses, rs.d_partials, d_edge_chi);
         if (d_chi)
-            cugo_k::launch_prior_chi_total(ctx->stream, *ev, rs.d_partials, d_chi, false);
+            cugo_k::launch_pose_chi_total(ctx->stream, "k_prior_chi_total", rs.d_partials, cugo_k::prior_workgroups(*ev), d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
 }
@@ -292,7 +281,7 @@ int cugo_prior_construct_quadratic_form(cugo_ctx* ctx, const cugo_prior_edges* e
         const cugo_k::ReduceScratch rs = check_prior(ctx, ev);
         cugo_k::launch_prior_add(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs.d_partials);
         if (d_chi)
-            cugo_k::launch_prior_chi_total(ctx->stream, *ev, rs.d_partials, d_chi, false);
+            cugo_k::launch_pose_chi_total(ctx->stream, "k_prior_chi_total", rs.d_partials, cugo_k::prior_workgroups(*ev), d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
 }

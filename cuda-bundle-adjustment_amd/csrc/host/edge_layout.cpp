@@ -377,65 +377,36 @@ void pose_major_view(int Pall, const Idx& slot_pose, const Idx& slot_src, Idx& p
     });
 }
 
-void sort_icp_by_pose(const FlatIcpKind& fk, int Pall, int P, int gw, IcpKindHost& b)
+void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHost& b)
 {
-    const int n = fk.n();
+    const int n = fk.n(), mw = fk.meas_w, ww = fk.weight_w;
     b.h_ptr.assign((size_t)Pall + 1, 0);
     for (int e = 0; e < n; e++)
     {
         if (fk.pose[e] < 0 || fk.pose[e] >= P)
-            throw std::runtime_error("cugo: a point-to-plane / point-to-line edge is not on a free pose");
+            throw std::runtime_error(std::string("cugo: a ") + pose_kind_group(fk.kind) +
+                                     (fk.kind == POSE_KIND_PRIOR ? "" : " edge") + " is not on a free pose");
         b.h_ptr[(size_t)fk.pose[e] + 1]++;
     }
     std::partial_sum(b.h_ptr.begin(), b.h_ptr.end(), b.h_ptr.begin());
     b.h_pose.resize(n), b.slot_set.resize(n), b.slot_edge.resize(n);
-    b.h_p.resize(3 * (size_t)n), b.h_geo.resize((size_t)gw * n);
-    const bool per_edge = fk.omega.size() > 1;
-    b.h_omega.assign(per_edge ? (size_t)n : 1, fk.omega.empty() ? 1.0 : fk.omega[0]);
+    b.h_meas.resize((size_t)mw * n);
+    const bool per_edge = fk.weight.size() > (size_t)ww;
+    b.n_weight = per_edge ? n : 1;
+    b.h_weight.assign((size_t)ww * b.n_weight, 0.0);
+    if (!per_edge)
+        std::copy(fk.weight.begin(), fk.weight.end(), b.h_weight.begin());
     std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1);
     for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
     {
         const size_t i = (size_t)pos[fk.pose[e]]++;
         b.h_pose[i] = fk.pose[e];
         b.slot_set[i] = fk.src_set[e], b.slot_edge[i] = fk.src_edge[e];
-        for (int c = 0; c < 3; c++)
-            b.h_p[(size_t)c * n + i] = fk.p[3 * (size_t)e + c];
-        for (int c = 0; c < gw; c++)
-            b.h_geo[(size_t)c * n + i] = fk.geo[(size_t)gw * e + c];
+        for (int c = 0; c < mw; c++)
+            b.h_meas[(size_t)c * n + i] = fk.meas[(size_t)mw * e + c];
         if (per_edge)
-            b.h_omega[i] = fk.omega[e];
-    }
-}
-
-void sort_priors_by_pose(const FlatPrior& fp, int Pall, int P, PriorHost& b)
-{
-    const int n = fp.n();
-    b.h_ptr.assign((size_t)Pall + 1, 0);
-    for (int e = 0; e < n; e++)
-    {
-        if (fp.pose[e] < 0 || fp.pose[e] >= P)
-            throw std::runtime_error("cugo: a pose prior is not on a free pose");
-        b.h_ptr[(size_t)fp.pose[e] + 1]++;
-    }
-    std::partial_sum(b.h_ptr.begin(), b.h_ptr.end(), b.h_ptr.begin());
-    b.h_pose.resize(n), b.slot_set.resize(n), b.slot_edge.resize(n);
-    b.h_meas.resize(7 * (size_t)n);
-    const bool per_edge = fp.info.size() > 21;
-    b.h_info.assign(21 * (per_edge ? (size_t)n : 1), 0.0);
-    if (!per_edge)
-        for (int c = 0; c < 21; c++)
-            b.h_info[c] = fp.info.empty() ? 0.0 : fp.info[c];
-    std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1);
-    for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
-    {
-        const size_t i = (size_t)pos[fp.pose[e]]++;
-        b.h_pose[i] = fp.pose[e];
-        b.slot_set[i] = fp.src_set[e], b.slot_edge[i] = fp.src_edge[e];
-        for (int c = 0; c < 7; c++)
-            b.h_meas[(size_t)c * n + i] = fp.z[7 * (size_t)e + c];
-        if (per_edge)
-            for (int c = 0; c < 21; c++)
-                b.h_info[(size_t)c * n + i] = fp.info[21 * (size_t)e + c];
+            for (int c = 0; c < ww; c++)
+                b.h_weight[(size_t)c * n + i] = fk.weight[(size_t)ww * e + c];
     }
 }
 

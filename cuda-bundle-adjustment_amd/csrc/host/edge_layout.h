@@ -59,21 +59,15 @@ void fill_slots(const FlatGraph& g, const Idx& order, const Idx& slot_src, SlotA
 // pose_edge[pose_ptr[p] .. pose_ptr[p + 1]): the real slots of pose p in slot order (= ascending landmark)
 void pose_major_view(int Pall, const Idx& slot_pose, const Idx& slot_src, Idx& pose_ptr, Idx& pose_edge);
 
-// point-to-plane / point-to-line edges of one kind sorted by pose (stable: container order inside a pose), planar
-struct IcpKindHost
+// the unary pose edges of one kind sorted by pose (stable: container order inside a pose), planar: meas [meas_w][n],
+// weight [weight_w][n_weight] with n_weight = n, or 1 when one value serves all (an empty kind: one column of zeros)
+struct PoseKindHost
 {
     Idx h_pose, h_ptr, slot_set, slot_edge;
-    std::vector<double> h_p, h_geo, h_omega;
+    std::vector<double> h_meas, h_weight;
+    int n_weight = 1;
 };
-void sort_icp_by_pose(const FlatIcpKind& kind, int Pall, int P, int geo_width, IcpKindHost& out);
-
-// SE(3) pose priors sorted by pose (stable), planar: meas [7][n], info [21][n] or [21][1]
-struct PriorHost
-{
-    Idx h_pose, h_ptr, slot_set, slot_edge;
-    std::vector<double> h_meas, h_info;
-};
-void sort_priors_by_pose(const FlatPrior& prior, int Pall, int P, PriorHost& out);
+void sort_pose_edges_by_pose(const FlatPoseKind& kind, int Pall, int P, PoseKindHost& out);
 
 // ---- the Hsc structure on the host: pattern (upper block CSR, diagonal first) and, from the LOCAL slots, the
 // contributions of the off-diagonal blocks (ascending landmark inside a block).  use_plan() is asked once the pattern

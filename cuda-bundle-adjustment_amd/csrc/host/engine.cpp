@@ -128,43 +128,123 @@ struct Engine::Impl : cugo_k::LaunchHook
     PinnedBuf<int32_t> h_fail;
 
     cugo_edges ev{};
-    // point-to-plane / point-to-line pose edges (icp_kernels.hip): each kind sorted by pose (stable: container order
-    // inside a pose), structure of arrays, on the device as long as the flattening lives.  Their partial sums have a
-    // scratch of their own: the BA scratch holds live scale / chi2 partials and records across the same span of the stream
-    struct IcpKindBufs : IcpKindHost
+    // The unary pose edge kinds (FlatGraph::kinds): point-to-plane / point-to-line (icp_kernels.hip) and SE(3) priors
+    // (prior_kernels.hip).  Each kind sorted by pose (stable: container order inside a pose), structure of arrays, on
+    // the device as long as the flattening lives; the views the kernels take; and a scratch of their own (the BA scratch
+    // holds live scale / chi2 partials and records across the same span of the stream):
+    //     [ICP partials | ICP chunk chi2 totals | prior workgroup chi2 totals | 16 doubles of slack]
+    // The two runs of totals are adjacent, so that the launch ending a trial sums them as one array (chi_totals).
+    struct PoseEdges
     {
-        DevBuf<int32_t> d_pose, d_ptr;
-        DevBuf<double> d_p, d_geo, d_omega;
-    } icpk[2];
-    cugo_icp_edges icp{};
-    int n_icp = 0;
-    DevBuf<double> d_icp_scratch;
-    cugo_k::ReduceScratch icp_rs() { return {d_icp_scratch.data(), d_icp_scratch.size()}; }
-    // SE(3) pose priors (prior_kernels.hip): sorted by pose, on the device as long as the flattening lives.  The chi2
-    // totals of their workgroups sit right behind the ICP chunk totals in d_icp_scratch (at its start without ICP edges)
-    struct PriorBufs : PriorHost
-    {
-        DevBuf<int32_t> d_pose, d_ptr;
-        DevBuf<double> d_meas, d_info;
-    } priork;
-    cugo_prior_edges prior{};
-    int n_prior = 0, n_prior_wg = 0;
-    double* prior_chi()
-    {
-        int n = 0;
-        return n_icp ? const_cast<double*>(cugo_k::icp_chunk_chi(icp, icp_rs(), &n)) + n : d_icp_scratch.data();
-    }
-    // the chi2 totals of the chunks of the last ICP pass and of the workgroups of the last prior pass, one array, for
-    // the launch that ends a trial
-    const double* icp_chi(int* n)
-    {
-        *n = 0;
-        if (!n_icp && !n_prior_wg)
-            return nullptr;
-        const double* base = n_icp ? cugo_k::icp_chunk_chi(icp, icp_rs(), n) : d_icp_scratch.data();
-        *n += n_prior_wg;
-        return base;
-    }
+        struct KindBufs : PoseKindHost
+        {
+            DevBuf<int32_t> d_pose, d_ptr;
+            DevBuf<double> d_meas, d_weight;
+        } kind[POSE_KIND_COUNT];
+        cugo_icp_edges icp{};
+        cugo_prior_edges prior{};
+        int n_icp = 0, n_prior = 0;
+        int n_icp_chi = 0, n_prior_wg = 0; // totals an ICP pass / a prior pass leaves (0: the pass is not launched)
+        DevBuf<double> d_scratch;
+        size_t off_icp_chi = 0, off_prior_chi = 0; // the layout above, set by bind()
+
+        cugo_k::ReduceScratch icp_rs() { return {d_scratch.data(), d_scratch.size()}; }
+        double* prior_chi() { return d_scratch.data() + off_prior_chi; }
+        int n_edges(int k) const { return (int)kind[k].h_pose.size(); }
+        const std::vector<int32_t>& icp_slot_source(int k, bool set) const { return set ? kind[k].slot_set : kind[k].slot_edge; }
+        // the chi2 totals of the last ICP pass and of the last prior pass, one array; nullptr / 0 without such edges
+        const double* chi_totals(int* n)
+        {
+            *n = n_icp_chi + n_prior_wg;
+            return *n ? d_scratch.data() + off_icp_chi : nullptr;
+        }
+
+        // sort, upload by the calling thread (plan_only: no device), views and scratch layout
+        void bind(const FlatGraph& g, int Pall, int P, hipStream_t stream, bool plan_only)
+        {
+            n_icp = g.kinds[POSE_KIND_PLANE].n() + g.kinds[POSE_KIND_LINE].n();
+            n_prior = g.kinds[POSE_KIND_PRIOR].n();
+            for (int k = 0; k < POSE_KIND_COUNT; k++)
+            {
+                KindBufs& b = kind[k];
+                sort_pose_edges_by_pose(g.kinds[k], Pall, P, b);
+                // an empty kind uploads nothing, except that k_icp_finish reads the pose_ptr of BOTH ICP kinds whenever
+                // either has edges: the empty one's is all zeros
+                if (plan_only || !(g.kinds[k].n() || (k != POSE_KIND_PRIOR && n_icp)))
+                    continue;
+                b.d_pose.upload(b.h_pose, stream), b.d_ptr.upload(b.h_ptr, stream);
+                b.d_meas.upload(b.h_meas, stream), b.d_weight.upload(b.h_weight, stream);
+            }
+            const KindBufs &pl = kind[POSE_KIND_PLANE], &li = kind[POSE_KIND_LINE], &pr = kind[POSE_KIND_PRIOR];
+            icp = cugo_icp_edges{};
+            icp.n_poses_total = Pall, icp.n_poses_free = P;
+            icp.n_plane = n_edges(POSE_KIND_PLANE), icp.n_line = n_edges(POSE_KIND_LINE);
+            // (meas is planar: p [3][n], then n, d [4][n] or a, u [6][n])
+            icp.d_plane_pose = pl.d_pose.data(), icp.d_plane_pose_ptr = pl.d_ptr.data();
+            icp.d_plane_p = pl.d_meas.data(), icp.d_plane_nd = pl.d_meas.data() + 3 * (size_t)icp.n_plane;
+            icp.d_plane_omega = pl.d_weight.data(), icp.n_plane_omega = pl.n_weight;
+            icp.rk_plane = g.kinds[POSE_KIND_PLANE].rk, icp.delta_plane = g.kinds[POSE_KIND_PLANE].delta;
+            icp.d_line_pose = li.d_pose.data(), icp.d_line_pose_ptr = li.d_ptr.data();
+            icp.d_line_p = li.d_meas.data(), icp.d_line_au = li.d_meas.data() + 3 * (size_t)icp.n_line;
+            icp.d_line_omega = li.d_weight.data(), icp.n_line_omega = li.n_weight;
+            icp.rk_line = g.kinds[POSE_KIND_LINE].rk, icp.delta_line = g.kinds[POSE_KIND_LINE].delta;
+            prior = cugo_prior_edges{};
+            prior.n_poses_total = Pall, prior.n_poses_free = P, prior.n = n_prior;
+            prior.d_pose = pr.d_pose.data(), prior.d_pose_ptr = pr.d_ptr.data();
+            prior.d_meas = pr.d_meas.data(), prior.d_info = pr.d_weight.data(), prior.n_info = pr.n_weight;
+            prior.rk = g.kinds[POSE_KIND_PRIOR].rk, prior.delta = g.kinds[POSE_KIND_PRIOR].delta;
+            // the scratch layout (the chunk totals end the ICP part)
+            const size_t icp_doubles = n_icp ? cugo_k::icp_scratch_doubles(icp) : 0;
+            n_icp_chi = n_icp ? cugo_k::icp_chunk_count(icp) : 0;
+            n_prior_wg = cugo_k::prior_workgroups(prior);
+            off_icp_chi = icp_doubles - n_icp_chi, off_prior_chi = icp_doubles;
+            if ((n_icp || n_prior_wg) && !plan_only)
+                d_scratch.resize(icp_doubles + (size_t)n_prior_wg + 16);
+        }
+        // The pose edge terms of a build pass at `poses`.  Two-stream form: the ICP chunk pass and its add, then the
+        // priors' ONE launch (terms and workgroup totals), both behind k_build_poses.  One-stream form (Hpp is not
+        // written): the adds go behind k_pose_schur (queue_add_schur); the chunk pass still runs here, and the priors'
+        // totals are computed here only where a chi2 is asked for (want_totals: iteration 0, or a trial that takes its
+        // chi2 from this pass).  d_chi (once per call, iteration 0): the totals ADDED to it, ICP first
+        void queue_build(hipStream_t s, const double* poses, bool one_stream, double* Hpp, double* bp, bool want_totals,
+                         double* d_chi)
+        {
+            if (n_icp)
+            {
+                cugo_k::launch_icp_chunks(s, icp, poses, true, icp_rs());
+                if (!one_stream)
+                    cugo_k::launch_icp_add(s, icp, icp_rs(), Hpp, bp);
+                if (d_chi)
+                    cugo_k::launch_pose_chi_total(s, "k_icp_chi_total", d_scratch.data() + off_icp_chi, n_icp_chi, d_chi, true);
+            }
+            if (n_prior_wg)
+            {
+                if (!one_stream)
+                    cugo_k::launch_prior_add(s, prior, poses, Hpp, bp, prior_chi());
+                else if (want_totals)
+                    cugo_k::launch_prior_errors(s, prior, poses, prior_chi());
+                if (d_chi)
+                    cugo_k::launch_pose_chi_total(s, "k_prior_chi_total", prior_chi(), n_prior_wg, d_chi, true);
+            }
+        }
+        // one-stream form: the terms added to the diagonal blocks of Hsc, to bp and to bsc behind k_pose_schur (the
+        // totals the prior launch leaves are those of the estimates at `poses` once more)
+        void queue_add_schur(hipStream_t s, const double* poses, const int32_t* rowptr, double* Hsc, double* bp, double* bsc)
+        {
+            if (n_icp)
+                cugo_k::launch_icp_add_schur(s, icp, icp_rs(), rowptr, Hsc, bp, bsc);
+            if (n_prior_wg)
+                cugo_k::launch_prior_add_schur(s, prior, poses, rowptr, Hsc, bp, bsc, prior_chi());
+        }
+        // error pass: chi_totals() at `poses`
+        void queue_errors(hipStream_t s, const double* poses)
+        {
+            if (n_icp)
+                cugo_k::launch_icp_chunks(s, icp, poses, false, icp_rs());
+            if (n_prior_wg)
+                cugo_k::launch_prior_errors(s, prior, poses, prior_chi());
+        }
+    } pe;
     cugo_hsc_struct hs{};
     SchurPlanDevice splan; // landmark-major product plan of the Schur complement (schur_plan.h)
     bool splan_on = false;
@@ -200,8 +280,6 @@ struct Engine::Impl : cugo_k::LaunchHook
     // the stages of Engine::initialize() that work on the device side (defined beside it)
     struct SlotUpload;
     bool start_pattern_helper(double* prof);
-    void bind_icp_edges(const FlatGraph& g);
-    void bind_prior_edges(const FlatGraph& g);
     std::vector<uint8_t> sig_flags;
 
     // optional HIP-event timing: 1 = an event pair round every kernel group AND every kernel (each pair adds a few
@@ -503,26 +581,7 @@ struct Engine::Impl : cugo_k::LaunchHook
                                  d_Hll.data(), bl(), d_Hpl.data(), rs(), d_chi, fuse ? fuse_lambda : -1.0,
                                  fuse ? d_invHll.data() : nullptr, fuse && !f.use_rows ? d_T.data() : nullptr,
                                  one_stream ? d_lmrec.data() : nullptr, one_stream, chi_behind_scale);
-            if (n_icp)
-            { // the chunk pass leaves the per-pose partials and the chunk chi2 totals; the add goes behind k_build_poses
-              // here or, in the one-stream form (Hpp is not written), behind k_pose_schur (queue_schur)
-                cugo_k::launch_icp_chunks(ctx.stream, icp, d_poses[buf].data(), true, icp_rs());
-                if (!one_stream)
-                    cugo_k::launch_icp_add(ctx.stream, icp, icp_rs(), d_Hpp.data(), bp());
-                if (d_chi)
-                    cugo_k::launch_icp_chi_total(ctx.stream, icp, icp_rs(), d_chi, true);
-            }
-            if (n_prior_wg)
-            { // ONE launch: the terms added to Hpp / bp behind k_build_poses, with the workgroups' chi2 totals.  In the
-              // one-stream form the add goes behind k_pose_schur (queue_schur), and only a pass whose chi2 is asked
-              // for — iteration 0, a trial that takes its chi2 from this pass — computes the totals here
-                if (!one_stream)
-                    cugo_k::launch_prior_add(ctx.stream, prior, d_poses[buf].data(), d_Hpp.data(), bp(), prior_chi());
-                else if (d_chi || chi_behind_scale)
-                    cugo_k::launch_prior_errors(ctx.stream, prior, d_poses[buf].data(), prior_chi());
-                if (d_chi) // (once per call, iteration 0)
-                    cugo_k::launch_prior_chi_total(ctx.stream, prior, prior_chi(), d_chi, true);
-            }
+            pe.queue_build(ctx.stream, d_poses[buf].data(), one_stream, d_Hpp.data(), bp(), d_chi || chi_behind_scale, d_chi);
         });
         st.hpp_valid = !one_stream;
         st.fused_lambda = fuse ? fuse_lambda : -1.0;
@@ -539,11 +598,8 @@ struct Engine::Impl : cugo_k::LaunchHook
                                                                 opt.hsc_mfma, opt.hsc_xcd,
                                                                 one_stream ? d_lmrec.data() : nullptr,
                                                                 d_poses[buf].data(), rs(), bp()});
-            if (n_icp && one_stream)
-                cugo_k::launch_icp_add_schur(ctx.stream, icp, icp_rs(), hs.d_rowptr, Hsc(), bp(), bsc());
-            if (n_prior_wg && one_stream) // (the totals it leaves are those of the estimates in `buf` once more)
-                cugo_k::launch_prior_add_schur(ctx.stream, prior, d_poses[buf].data(), hs.d_rowptr, Hsc(), bp(), bsc(),
-                                               prior_chi());
+            if (one_stream)
+                pe.queue_add_schur(ctx.stream, d_poses[buf].data(), hs.d_rowptr, Hsc(), bp(), bsc());
         });
     }
     // diagnosis: CUGO_DEBUG_HASH=<file> — position-weighted integer checksums of the arrays every stage of the
@@ -896,61 +952,6 @@ struct Engine::Impl::SlotUpload
     }
 };
 
-// Point-to-plane / point-to-line edges: each kind sorted by pose, uploaded by the calling thread, and their view
-void Engine::Impl::bind_icp_edges(const FlatGraph& g)
-{
-    const FlatIcpKind* kinds[2] = {&g.plane, &g.line};
-    for (int k = 0; k < 2; k++)
-    {
-        IcpKindBufs& b = icpk[k];
-        sort_icp_by_pose(*kinds[k], Pall, P, k == 0 ? 4 : 6, b);
-        if (plan_only)
-            continue;
-        hipStream_t s = ctx.stream;
-        b.d_pose.upload(b.h_pose, s), b.d_ptr.upload(b.h_ptr, s);
-        b.d_p.upload(b.h_p, s), b.d_geo.upload(b.h_geo, s), b.d_omega.upload(b.h_omega, s);
-    }
-    n_icp = g.plane.n() + g.line.n();
-    cugo_icp_edges& iv = icp;
-    iv = cugo_icp_edges{};
-    iv.n_poses_total = Pall, iv.n_poses_free = P;
-    iv.n_plane = g.plane.n(), iv.n_line = g.line.n();
-    iv.d_plane_pose = icpk[0].d_pose.data(), iv.d_plane_pose_ptr = icpk[0].d_ptr.data();
-    iv.d_plane_p = icpk[0].d_p.data(), iv.d_plane_nd = icpk[0].d_geo.data();
-    iv.d_plane_omega = icpk[0].d_omega.data(), iv.n_plane_omega = (int)icpk[0].h_omega.size();
-    iv.rk_plane = g.plane.rk, iv.delta_plane = g.plane.delta;
-    iv.d_line_pose = icpk[1].d_pose.data(), iv.d_line_pose_ptr = icpk[1].d_ptr.data();
-    iv.d_line_p = icpk[1].d_p.data(), iv.d_line_au = icpk[1].d_geo.data();
-    iv.d_line_omega = icpk[1].d_omega.data(), iv.n_line_omega = (int)icpk[1].h_omega.size();
-    iv.rk_line = g.line.rk, iv.delta_line = g.line.delta;
-    if (n_icp && !plan_only)
-        d_icp_scratch.resize(cugo_k::icp_scratch_doubles(iv));
-}
-
-// SE(3) pose priors: sorted by pose, uploaded by the calling thread, and their view; the ICP scratch grows by their
-// workgroup totals (the 16 doubles of slack behind the chunk totals are only used by the kernel-level index check)
-void Engine::Impl::bind_prior_edges(const FlatGraph& g)
-{
-    sort_priors_by_pose(g.prior, Pall, P, priork);
-    n_prior = g.prior.n();
-    if (!plan_only && n_prior) // (a graph without priors uploads nothing and launches nothing)
-    {
-        hipStream_t s = ctx.stream;
-        priork.d_pose.upload(priork.h_pose, s), priork.d_ptr.upload(priork.h_ptr, s);
-        priork.d_meas.upload(priork.h_meas, s), priork.d_info.upload(priork.h_info, s);
-    }
-    cugo_prior_edges& pv = prior;
-    pv = cugo_prior_edges{};
-    pv.n_poses_total = Pall, pv.n_poses_free = P, pv.n = n_prior;
-    pv.d_pose = priork.d_pose.data(), pv.d_pose_ptr = priork.d_ptr.data();
-    pv.d_meas = priork.d_meas.data(), pv.d_info = priork.d_info.data();
-    pv.n_info = (int)(priork.h_info.size() / 21);
-    pv.rk = g.prior.rk, pv.delta = g.prior.delta;
-    n_prior_wg = cugo_k::prior_workgroups(pv);
-    if (n_prior_wg && !plan_only)
-        d_icp_scratch.resize((n_icp ? cugo_k::icp_scratch_doubles(icp) : 16) + (size_t)n_prior_wg);
-}
-
 void Engine::initialize(FlatGraph& g)
 {
     const auto t0 = Clock::now();
@@ -964,12 +965,11 @@ void Engine::initialize(FlatGraph& g)
     m.rk = g.rk;
     m.init_rank = m.rank, m.init_world = m.world;
     m.Etot = g.n_edges();
-    E_global_ = m.Etot + g.plane.n() + g.line.n() + g.prior.n();
-    if (g.prior.n() && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: pose prior edge sets are not supported on a landmark-sharded (multi-GPU) optimiser yet");
-    if ((g.plane.n() || g.line.n()) && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: point-to-plane / point-to-line edge sets are not supported on a landmark-sharded "
-                                 "(multi-GPU) optimiser yet");
+    E_global_ = m.Etot + g.n_pose_edges();
+    for (int k = POSE_KIND_COUNT - 1; k >= 0; k--) // (priors first: the message a graph with several kinds has always got)
+        if (g.kinds[k].n() && (m.world > 1 || m.comm))
+            throw std::runtime_error(std::string("cugo: ") + pose_kind_group(k) +
+                                     " edge sets are not supported on a landmark-sharded (multi-GPU) optimiser yet");
     sort_landmark_major(g, m.st_lm_cnt, m.st_order);
     laps.lap("engine: landmark sort");
     build_covisibility(g, m.st_lm_cnt, m.st_order, m.cov_ptr, m.cov_pose);
@@ -988,8 +988,7 @@ void Engine::initialize(FlatGraph& g)
     Impl::SlotUpload upload(m, g);
     pose_major_view(m.Pall, m.slots.pose, m.st_slot_src, m.h_pose_ptr, m.h_pose_edge);
     laps.lap("engine: pose-major view");
-    m.bind_icp_edges(g);
-    m.bind_prior_edges(g);
+    m.pe.bind(g, m.Pall, m.P, s, m.plan_only);
     laps.lap("engine: ICP edge sort");
     // (a plan-only engine has no device: it skips to the topology compare)
     if (!m.plan_only)
@@ -1492,7 +1491,7 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
                 m.queue_build(nxt, fuse_pred, nullptr, true);
                 m.timed("errors", [&] { // (the ICP chunk totals are those of the build pass just queued)
                     int n_icp_chi = 0;
-                    const double* icp_chi = m.icp_chi(&n_icp_chi);
+                    const double* icp_chi = m.pe.chi_totals(&n_icp_chi);
                     cugo_k::launch_trial_tail_from_build(s, m.ev, m.rs(), n_scale_part, m.d_scal.data() + 2,
                                                          m.d_scal.data() + 4, m.h_scal.data() + 2, (double)++m.trial_seq,
                                                          reinterpret_cast<unsigned*>(m.d_fail.data() + 2), icp_chi,
@@ -1514,11 +1513,8 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
                 else
                 {
                     int n_icp_chi = 0;
-                    const double* icp_chi = m.icp_chi(&n_icp_chi);
-                    if (m.n_icp)
-                        cugo_k::launch_icp_chunks(s, m.icp, m.d_poses[nxt].data(), false, m.icp_rs());
-                    if (m.n_prior_wg)
-                        cugo_k::launch_prior_errors(s, m.prior, m.d_poses[nxt].data(), m.prior_chi());
+                    const double* icp_chi = m.pe.chi_totals(&n_icp_chi);
+                    m.pe.queue_errors(s, m.d_poses[nxt].data());
                     cugo_k::launch_errors_tail(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk, m.rs(),
                                                n_scale_part, m.d_scal.data() + 2, m.d_scal.data() + 4,
                                                m.h_scal.data() + 2, (double)++m.trial_seq,
@@ -1647,13 +1643,12 @@ std::vector<int32_t> Engine::reject_outliers()
     return out;
 }
 
-int Engine::n_icp_edges(int kind) const { return kind == 0 ? impl_->icp.n_plane : kind == 1 ? impl_->icp.n_line : 0; }
+int Engine::n_icp_edges(int kind) const { return kind == 0 || kind == 1 ? impl_->pe.n_edges(kind) : 0; }
 const std::vector<int32_t>& Engine::icp_slot_source(int kind, bool set) const
 {
-    const Impl::IcpKindBufs& b = impl_->icpk[kind == 1 ? 1 : 0];
-    return set ? b.slot_set : b.slot_edge;
+    return impl_->pe.icp_slot_source(kind == 1 ? 1 : 0, set);
 }
-int Engine::n_prior_edges() const { return impl_->n_prior; }
+int Engine::n_prior_edges() const { return impl_->pe.n_prior; }
 int Engine::n_poses_free() const { return impl_->P; }
 int Engine::n_landmarks_free() const { return impl_->L; }
 

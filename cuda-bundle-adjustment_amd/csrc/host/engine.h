@@ -18,43 +18,44 @@ struct Options;
 
 // Result of flattening a graph (ref: VertexSet::generateEstimateData + EdgeSet::init,
 // src/optimisable_graph.hpp:84-126,474-572).  Indices: free vertices first.
-// Point-to-plane / point-to-line pose edges of one kind (icp_types.h), flattened in container order; edges on fixed
+// Unary edges of one kind on a pose vertex (icp_types.h, prior_types.h), flattened in container order; edges on fixed
 // poses, inactive edges and everything invalid never get here (graph_optimisation.cpp validates and drops)
-struct FlatIcpKind
+enum PoseKind
 {
-    std::vector<int32_t> pose; // free-first pose index per edge (always < P)
-    std::vector<double> p;     // E x 3 pointP
-    std::vector<double> geo;   // plane: E x 4 (normal, originDistance); line: E x 6 (a, unit direction)
-    std::vector<double> omega; // E, or 1 when uniform / perEdgeInformation is off
+    POSE_KIND_PLANE = 0,
+    POSE_KIND_LINE,
+    POSE_KIND_PRIOR,
+    POSE_KIND_COUNT
+};
+struct FlatPoseKind
+{
+    int kind = 0;                 // PoseKind
+    int meas_w = 0, weight_w = 0; // doubles per edge: plane 7 (p, n, d) + 1, line 9 (p, a, unit direction) + 1, prior
+                                  // 7 (q x y z w, t) + 21 (upper triangle of Omega, row-major packed)
+    std::vector<int32_t> pose;    // free-first pose index per edge (always < P)
+    std::vector<double> meas;     // E x meas_w
+    std::vector<double> weight;   // E x weight_w, or 1 x weight_w when one value serves all
     std::vector<int32_t> src_set, src_edge; // where an edge came from: edge set (position among the optimiser's edge
                                             // sets) and position in that set's container
     int rk = CUGO_RK_NONE;
     double delta = 1.0;
+    bool rk_seen = false; // a non-empty edge set has settled rk / delta (further sets must agree)
     int n() const { return (int)pose.size(); }
     void clear()
     {
-        pose.clear(), p.clear(), geo.clear(), omega.clear(), src_set.clear(), src_edge.clear();
-        rk = CUGO_RK_NONE, delta = 1.0;
+        pose.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear();
+        rk = CUGO_RK_NONE, delta = 1.0, rk_seen = false;
     }
 };
-
-// SE(3) pose priors (prior_types.h), flattened in container order; priors on fixed poses, inactive ones and everything
-// invalid never get here (graph_optimisation.cpp validates and drops)
-struct FlatPrior
+// a kind in messages about its edge sets, and in the engine's, which speak of the two ICP kinds as one
+inline const char* pose_kind_name(int kind)
 {
-    std::vector<int32_t> pose; // free-first pose index per edge (always < P)
-    std::vector<double> z;     // E x 7 measured pose (q x y z w, t)
-    std::vector<double> info;  // E x 21 upper triangle of Omega, row-major packed; 21 when one matrix serves all
-    std::vector<int32_t> src_set, src_edge; // edge set (position among the optimiser's edge sets), position in its container
-    int rk = CUGO_RK_NONE;
-    double delta = 1.0;
-    int n() const { return (int)pose.size(); }
-    void clear()
-    {
-        pose.clear(), z.clear(), info.clear(), src_set.clear(), src_edge.clear();
-        rk = CUGO_RK_NONE, delta = 1.0;
-    }
-};
+    return kind == POSE_KIND_PLANE ? "point-to-plane" : kind == POSE_KIND_LINE ? "point-to-line" : "pose prior";
+}
+inline const char* pose_kind_group(int kind)
+{
+    return kind == POSE_KIND_PRIOR ? "pose prior" : "point-to-plane / point-to-line";
+}
 
 struct FlatGraph
 {
@@ -72,8 +73,14 @@ struct FlatGraph
     // outlier rejection (ref: EdgeSet::updateEdges, optimisable_graph.hpp:603-640): per edge
     // the chi2 threshold of its edge set, 0 = disabled; empty = disabled for all
     std::vector<double> e_outlier_threshold;
-    FlatIcpKind plane, line;
-    FlatPrior prior;
+    FlatPoseKind kinds[POSE_KIND_COUNT]; // widths set by the constructor
+    FlatGraph()
+    {
+        const int w[POSE_KIND_COUNT][2] = {{7, 1}, {9, 1}, {7, 21}};
+        for (int k = 0; k < POSE_KIND_COUNT; k++)
+            kinds[k].kind = k, kinds[k].meas_w = w[k][0], kinds[k].weight_w = w[k][1];
+    }
+    int n_pose_edges() const { return kinds[0].n() + kinds[1].n() + kinds[2].n(); }
     int n_edges() const { return (int)e_pose.size(); }
 };
 
@@ -174,7 +181,7 @@ public:
     int n_active_edges() const { return E_global_; } // BA + ICP edges + priors of the current flattening
     int n_icp_edges(int kind) const;                  // 0 plane, 1 line
     int n_prior_edges() const;
-    // sorted slot of a kind -> {edge set, position in the set} as FlatIcpKind recorded them (kept for a later
+    // sorted slot of a kind -> {edge set, position in the set} as FlatPoseKind recorded them (kept for a later
     // outlier rejection on these sets)
     const std::vector<int32_t>& icp_slot_source(int kind, bool set) const;
     const StructureStats& structure_stats() const { return sstats_; }

@@ -127,97 +127,6 @@ static int rk_code(RobustKernelType t)
     }
 }
 
-// One PlaneEdgeSet / LineEdgeSet (icp_types.h) into the flat arrays of its kind, in container order.  This is the one
-// place where these edges are checked (the kernels take the layout as given): every active edge must sit on a pose
-// vertex of one of the optimiser's pose vertex sets and hold finite values, a plane normal of unit length (the header
-// says "used as given": refused, not normalised silently) or two distinct line points.  Inactive edges and edges on
-// fixed poses are dropped, as BA edges with two fixed ends are.  Several sets of a kind must agree on the robust kernel.
-static void flattenIcpSet(BaseEdgeSet* es, int setIndex, bool line, bool perInfo,
-                          const std::vector<BaseVertexSet*>& vertexSets, cugo_host::FlatIcpKind& out, bool& seen)
-{
-    const char* kind = line ? "point-to-line" : "point-to-plane";
-    auto refuse = [&](size_t i, const char* what) {
-        throw std::runtime_error(std::string("cugo: ") + kind + " edge " + std::to_string(i) + " of edge set " +
-                                 std::to_string(setIndex) + ": " + what);
-    };
-    if (es->getOutlierThreshold() > 0.0)
-        throw std::runtime_error(std::string("cugo: outlier rejection is not available on ") + kind +
-                                 " edge sets yet (setOutlierThreshold must stay 0)");
-    const RobustKernel& k = es->robustKernelData();
-    const int rk = rk_code(k.type());
-    const double delta = k.delta();
-    if (es->nedges() > 0)
-    {
-        if (seen && (rk != out.rk || (rk != CUGO_RK_NONE && delta != out.delta)))
-            throw std::runtime_error(std::string("cugo: the ") + kind + " edge sets of one optimiser must use the same robust kernel");
-        if (!std::isfinite(delta) || (rk != CUGO_RK_NONE && !(delta > 0.0)))
-            throw std::runtime_error(std::string("cugo: bad robust kernel delta on a ") + kind + " edge set");
-        out.rk = rk, out.delta = delta;
-        seen = true;
-    }
-    es->setOutlierCount(0);
-    const double set_info = es->informationValue();
-    size_t i = 0, kept = 0;
-    for (BaseEdge* e : es->get())
-    {
-        const size_t at = i++;
-        if (!e->isActive())
-            continue;
-        BaseVertex* v = e->getVertex(0);
-        bool known = false;
-        if (v && !v->isMarginilised())
-            for (const BaseVertexSet* vs : vertexSets)
-                known = known || (vs == v->ownerSet() && !vs->isMarginilised());
-        if (!known)
-            refuse(at, "its pose vertex is in no pose vertex set of this optimiser");
-        const double w = perInfo ? (double)e->informationValue() : set_info;
-        if (!std::isfinite(w))
-            refuse(at, "non-finite information");
-        double p[3], geo[6];
-        if (!line)
-        {
-            const auto& mz = *static_cast<const PointToPlaneMatch<double>*>(e->measurementData());
-            for (int c = 0; c < 3; c++)
-                p[c] = mz.pointP[c], geo[c] = mz.normal[c];
-            geo[3] = mz.originDistance;
-            for (int c = 0; c < 3; c++)
-                if (!std::isfinite(p[c]) || !std::isfinite(geo[c]))
-                    refuse(at, "non-finite point or normal");
-            if (!std::isfinite(geo[3]))
-                refuse(at, "non-finite originDistance");
-            const double len = std::sqrt(geo[0] * geo[0] + geo[1] * geo[1] + geo[2] * geo[2]);
-            if (!(std::fabs(len - 1.0) <= 1e-6))
-                refuse(at, "the plane normal is not of unit length (it is used as given)");
-        }
-        else
-        {
-            const auto& mz = *static_cast<const PointToLineMatch<double>*>(e->measurementData());
-            double d[3];
-            for (int c = 0; c < 3; c++)
-            {
-                p[c] = mz.pointP[c], geo[c] = mz.a[c], d[c] = mz.b[c] - mz.a[c];
-                if (!std::isfinite(p[c]) || !std::isfinite(mz.a[c]) || !std::isfinite(mz.b[c]))
-                    refuse(at, "non-finite point or line end");
-            }
-            const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            if (!(len > 0.0) || !std::isfinite(len))
-                refuse(at, "the two points of the line coincide (a == b)");
-            for (int c = 0; c < 3; c++)
-                geo[3 + c] = d[c] / len;
-        }
-        if (v->isFixed())
-            continue;
-        out.pose.push_back(v->getIndex());
-        out.p.insert(out.p.end(), p, p + 3);
-        out.geo.insert(out.geo.end(), geo, geo + (line ? 6 : 4));
-        out.omega.push_back(w);
-        out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
-        kept++;
-    }
-    es->setActiveEdgeCount(kept);
-    es->setDirtyState(false);
-}
-
 // smallest and largest eigenvalue of a symmetric 6 x 6 matrix by cyclic Jacobi sweeps
 static void symEigenRange6(const double* A36, double& lo, double& hi)
 {
@@ -279,32 +188,34 @@ static const char* checkInformation36(const double* A)
     return nullptr;
 }
 
-// One PosePriorEdgeSet (prior_types.h) into the flat arrays, in container order; the one place where these edges are
-// checked, as flattenIcpSet is for its kinds.  Omega goes on as the upper triangle of its symmetric part.
-static void flattenPriorSet(PosePriorEdgeSet* es, int setIndex, bool perInfo, const std::vector<BaseVertexSet*>& vertexSets,
-                            cugo_host::FlatPrior& out, bool& seen)
+// One edge set of unary pose edges (PlaneEdgeSet / LineEdgeSet of icp_types.h, PosePriorEdgeSet of prior_types.h) into
+// the flat arrays of its kind, in container order.  This is the one place where these edges are checked (the kernels
+// take the layout as given): every active edge must sit on a pose vertex of one of the optimiser's pose vertex sets and
+// hold what payload(e, refuse, meas, weight) accepts; the callable writes the edge's meas_w / weight_w columns and
+// refuses bad values through refuse(what).  Inactive edges and edges on fixed poses are dropped, as BA edges with two
+// fixed ends are.  Several sets of a kind must agree on the robust kernel; once that is settled, check_set() returns
+// what is wrong with a non-empty set as a whole, or nullptr.
+template <class Payload, class CheckSet>
+static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, const char* kind, const std::vector<BaseVertexSet*>& vertexSets,
+                               cugo_host::FlatPoseKind& out, Payload payload, CheckSet check_set)
 {
-    auto refuse = [&](size_t i, const char* what) {
-        throw std::runtime_error("cugo: pose prior edge " + std::to_string(i) + " of edge set " + std::to_string(setIndex) +
-                                 ": " + what);
-    };
+    const std::string name = kind;
     if (es->getOutlierThreshold() > 0.0)
-        throw std::runtime_error("cugo: outlier rejection is not available on pose prior edge sets yet "
-                                 "(setOutlierThreshold must stay 0)");
+        throw std::runtime_error("cugo: outlier rejection is not available on " + name +
+                                 " edge sets yet (setOutlierThreshold must stay 0)");
     const RobustKernel& k = es->robustKernelData();
     const int rk = rk_code(k.type());
     const double delta = k.delta();
     if (es->nedges() > 0)
     {
-        if (seen && (rk != out.rk || (rk != CUGO_RK_NONE && delta != out.delta)))
-            throw std::runtime_error("cugo: the pose prior edge sets of one optimiser must use the same robust kernel");
+        if (out.rk_seen && (rk != out.rk || (rk != CUGO_RK_NONE && delta != out.delta)))
+            throw std::runtime_error("cugo: the " + name + " edge sets of one optimiser must use the same robust kernel");
         if (!std::isfinite(delta) || (rk != CUGO_RK_NONE && !(delta > 0.0)))
-            throw std::runtime_error("cugo: bad robust kernel delta on a pose prior edge set");
+            throw std::runtime_error("cugo: bad robust kernel delta on a " + name + " edge set");
         out.rk = rk, out.delta = delta;
-        seen = true;
-        if (!perInfo)
-            if (const char* bad = checkInformation36(es->informationMatrix()))
-                throw std::runtime_error("cugo: pose prior edge set " + std::to_string(setIndex) + ": " + bad);
+        out.rk_seen = true;
+        if (const char* bad = check_set())
+            throw std::runtime_error("cugo: " + name + " edge set " + std::to_string(setIndex) + ": " + bad);
     }
     es->setOutlierCount(0);
     size_t i = 0, kept = 0;
@@ -313,38 +224,95 @@ static void flattenPriorSet(PosePriorEdgeSet* es, int setIndex, bool perInfo, co
         const size_t at = i++;
         if (!e->isActive())
             continue;
+        auto refuse = [&](const char* what) {
+            throw std::runtime_error("cugo: " + name + " edge " + std::to_string(at) + " of edge set " +
+                                     std::to_string(setIndex) + ": " + what);
+        };
         BaseVertex* v = e->getVertex(0);
         bool known = false;
         if (v && !v->isMarginilised())
             for (const BaseVertexSet* vs : vertexSets)
                 known = known || (vs == v->ownerSet() && !vs->isMarginilised());
         if (!known)
-            refuse(at, "its pose vertex is in no pose vertex set of this optimiser");
-        const auto& mz = *static_cast<const PosePriorMatch<double>*>(e->measurementData());
-        double z[7];
-        mz.pose.copyTo(z, z + 4);
-        for (int c = 0; c < 7; c++)
-            if (!std::isfinite(z[c]))
-                refuse(at, "non-finite measured pose");
-        const double len = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2] + z[3] * z[3]);
-        if (!(std::fabs(len - 1.0) <= 1e-6))
-            refuse(at, "the quaternion of the measured pose is not of unit length (it is used as given)");
-        const double* A = perInfo ? mz.information : es->informationMatrix();
-        if (perInfo)
-            if (const char* bad = checkInformation36(A))
-                refuse(at, bad);
+            refuse("its pose vertex is in no pose vertex set of this optimiser");
+        double meas[9], weight[21];
+        payload(e, refuse, meas, weight);
         if (v->isFixed())
             continue;
         out.pose.push_back(v->getIndex());
-        out.z.insert(out.z.end(), z, z + 7);
-        for (int r = 0; r < 6; r++)
-            for (int c = r; c < 6; c++)
-                out.info.push_back(0.5 * (A[6 * r + c] + A[6 * c + r]));
+        out.meas.insert(out.meas.end(), meas, meas + out.meas_w);
+        out.weight.insert(out.weight.end(), weight, weight + out.weight_w);
         out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
         kept++;
     }
     es->setActiveEdgeCount(kept);
     es->setDirtyState(false);
+}
+
+// The payloads of the three kinds: an edge's columns, validated.
+// plane / line: one information value, the edge's own or the set's
+template <class Refuse>
+static void icpInformation(BaseEdgeSet* es, BaseEdge* e, bool perInfo, Refuse& refuse, double* weight)
+{
+    weight[0] = perInfo ? (double)e->informationValue() : es->informationValue();
+    if (!std::isfinite(weight[0]))
+        refuse("non-finite information");
+}
+// plane: p, unit normal ("used as given": refused, not normalised silently), originDistance
+template <class Refuse>
+static void planePayload(BaseEdge* e, Refuse& refuse, double* m)
+{
+    const auto& mz = *static_cast<const PointToPlaneMatch<double>*>(e->measurementData());
+    for (int c = 0; c < 3; c++)
+        m[c] = mz.pointP[c], m[3 + c] = mz.normal[c];
+    m[6] = mz.originDistance;
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(m[c]) || !std::isfinite(m[3 + c]))
+            refuse("non-finite point or normal");
+    if (!std::isfinite(m[6]))
+        refuse("non-finite originDistance");
+    const double len = std::sqrt(m[3] * m[3] + m[4] * m[4] + m[5] * m[5]);
+    if (!(std::fabs(len - 1.0) <= 1e-6))
+        refuse("the plane normal is not of unit length (it is used as given)");
+}
+// line: p, a, unit direction of b - a (two distinct points)
+template <class Refuse>
+static void linePayload(BaseEdge* e, Refuse& refuse, double* m)
+{
+    const auto& mz = *static_cast<const PointToLineMatch<double>*>(e->measurementData());
+    double d[3];
+    for (int c = 0; c < 3; c++)
+    {
+        m[c] = mz.pointP[c], m[3 + c] = mz.a[c], d[c] = mz.b[c] - mz.a[c];
+        if (!std::isfinite(m[c]) || !std::isfinite(mz.a[c]) || !std::isfinite(mz.b[c]))
+            refuse("non-finite point or line end");
+    }
+    const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if (!(len > 0.0) || !std::isfinite(len))
+        refuse("the two points of the line coincide (a == b)");
+    for (int c = 0; c < 3; c++)
+        m[6 + c] = d[c] / len;
+}
+// prior: measured pose with a unit quaternion | the upper triangle of the symmetric part of Omega (A: the edge's own
+// matrix, checked here, or the set's, checked with the set)
+template <class Refuse>
+static void priorPayload(BaseEdge* e, const double* setInformation, Refuse& refuse, double* z, double* weight)
+{
+    const auto& mz = *static_cast<const PosePriorMatch<double>*>(e->measurementData());
+    mz.pose.copyTo(z, z + 4);
+    for (int c = 0; c < 7; c++)
+        if (!std::isfinite(z[c]))
+            refuse("non-finite measured pose");
+    const double len = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2] + z[3] * z[3]);
+    if (!(std::fabs(len - 1.0) <= 1e-6))
+        refuse("the quaternion of the measured pose is not of unit length (it is used as given)");
+    const double* A = setInformation ? setInformation : mz.information;
+    if (!setInformation)
+        if (const char* bad = checkInformation36(A))
+            refuse(bad);
+    for (int r = 0, t = 0; r < 6; r++)
+        for (int c = r; c < 6; c++)
+            weight[t++] = 0.5 * (A[6 * r + c] + A[6 * c + r]);
 }
 
 void CudaGraphOptimisationImpl::initialize()
@@ -455,8 +423,8 @@ void CudaGraphOptimisationImpl::initialize()
     for (BaseEdgeSet* es : edgeSets)
         if (es->dim() != 1 && es->dim() != 6)
             cap += es->nedges();
-    g.plane.clear(), g.line.clear(), g.prior.clear();
-    bool seen_plane = false, seen_line = false, seen_prior = false;
+    for (cugo_host::FlatPoseKind& fk : g.kinds)
+        fk.clear();
     g.e_pose.resize(cap), g.e_lm.resize(cap), g.e_flags.resize(cap);
     g.e_meas.resize(3 * cap), g.e_omega.resize(cap), g.e_cam.resize(cap);
     g.e_outlier_threshold.resize(cap);
@@ -479,20 +447,33 @@ void CudaGraphOptimisationImpl::initialize()
         const int dim = es->dim();
         if (dim == 1)
         { // PlaneEdgeSet / LineEdgeSet (icp_types.h): both have dim() 1, the type tells them apart
-            if (dynamic_cast<PlaneEdgeSet*>(es))
-                flattenIcpSet(es, (int)si, false, options.perEdgeInformation, vertexSets, g.plane, seen_plane);
-            else if (dynamic_cast<LineEdgeSet*>(es))
-                flattenIcpSet(es, (int)si, true, options.perEdgeInformation, vertexSets, g.line, seen_line);
-            else
+            const bool line = dynamic_cast<LineEdgeSet*>(es) != nullptr;
+            if (!line && !dynamic_cast<PlaneEdgeSet*>(es))
                 throw std::runtime_error("cugo: a 1-d edge set must be a PlaneEdgeSet or a LineEdgeSet (icp_types.h)");
+            const int kind = line ? cugo_host::POSE_KIND_LINE : cugo_host::POSE_KIND_PLANE;
+            const bool perInfo = options.perEdgeInformation;
+            flattenPoseEdgeSet(
+                es, (int)si, cugo_host::pose_kind_name(kind), vertexSets, g.kinds[kind],
+                [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
+                    icpInformation(es, e, perInfo, refuse, weight);
+                    line ? linePayload(e, refuse, meas) : planePayload(e, refuse, meas);
+                },
+                [] { return (const char*)nullptr; });
             continue;
         }
         if (dim == 6)
         { // PosePriorEdgeSet (prior_types.h, an extension)
-            if (auto* ps = dynamic_cast<PosePriorEdgeSet*>(es))
-                flattenPriorSet(ps, (int)si, options.perEdgeInformation, vertexSets, g.prior, seen_prior);
-            else
+            auto* ps = dynamic_cast<PosePriorEdgeSet*>(es);
+            if (!ps)
                 throw std::runtime_error("cugo: a 6-d edge set must be a PosePriorEdgeSet (prior_types.h)");
+            const double* setInformation = options.perEdgeInformation ? nullptr : ps->informationMatrix();
+            flattenPoseEdgeSet(
+                es, (int)si, cugo_host::pose_kind_name(cugo_host::POSE_KIND_PRIOR), vertexSets,
+                g.kinds[cugo_host::POSE_KIND_PRIOR],
+                [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
+                    priorPayload(e, setInformation, refuse, meas, weight);
+                },
+                [&] { return setInformation ? checkInformation36(setInformation) : nullptr; });
             continue;
         }
         if (dim != 2 && dim != 3)
@@ -658,21 +639,13 @@ void CudaGraphOptimisationImpl::initialize()
         g.cams.assign(z, z + 5);
     }
     g.rk = rk;
-    for (cugo_host::FlatIcpKind* fk : {&g.plane, &g.line})
-    { // one information value for the whole kind: a single entry, as for the BA edges
-        bool uniform = !fk->omega.empty();
-        for (double w : fk->omega)
-            uniform = uniform && w == fk->omega[0];
+    for (cugo_host::FlatPoseKind& fk : g.kinds)
+    { // one weight for the whole kind: a single entry, as for the BA edges
+        bool uniform = fk.n() > 0;
+        for (size_t i = fk.weight_w; uniform && i < fk.weight.size(); i++)
+            uniform = fk.weight[i] == fk.weight[i % fk.weight_w];
         if (uniform)
-            fk->omega.resize(1);
-    }
-    if (g.prior.n() > 1)
-    { // one matrix for all priors: a single entry
-        bool uniform = true;
-        for (size_t i = 21; uniform && i < g.prior.info.size(); i++)
-            uniform = g.prior.info[i] == g.prior.info[i % 21];
-        if (uniform)
-            g.prior.info.resize(21);
+            fk.weight.resize(fk.weight_w);
     }
     lap("graph: edge flatten");
 

@@ -324,4 +324,38 @@ __device__ __forceinline__ void pose_exp_update(const double* __restrict__ dx,
     pout[3] = invn * r3;
 }
 
+// ---- shared by the unary pose edge kinds (icp_kernels.hip, prior_kernels.hip): the 27 terms of a pose are the upper
+// triangle of its 6 x 6 block of H, row-major packed (t < 21), then b (t = 21..26)
+// entry t < 21 of the packed upper triangle -> (r, c), r <= c
+__device__ __forceinline__ void tri6_unpack(int t, int& r, int& c)
+{
+    r = 0;
+    int k = t;
+    while (k >= 6 - r)
+        k -= 6 - r, r++;
+    c = r + k;
+}
+// term t < 27 of pose p, value s, ADDED to its destination; (r, c) = tri6_unpack(t) where t < 21.  SCHUR = false: the
+// block of Hpp (mirrored off the diagonal) / bp.  SCHUR = true: the diagonal block of Hsc (the first block of the pose's
+// row, through rowptr), bp and bsc
+template <bool SCHUR>
+__device__ __forceinline__ void pose_term_add(int p, int t, int r, int c, double s, double* __restrict__ H,
+                                              const int32_t* __restrict__ rowptr, double* __restrict__ bp,
+                                              double* __restrict__ bsc)
+{
+    if (t < 21)
+    {
+        double* blk = H + 36 * (size_t)(SCHUR ? rowptr[p] : p);
+        blk[r + 6 * c] += s;
+        if (r != c)
+            blk[c + 6 * r] += s;
+    }
+    else if (t < 27)
+    {
+        bp[6 * (size_t)p + (t - 21)] += s;
+        if (SCHUR)
+            bsc[6 * (size_t)p + (t - 21)] += s;
+    }
+}
+
 } // namespace cugo_dev

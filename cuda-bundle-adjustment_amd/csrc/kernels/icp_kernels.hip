@@ -292,58 +292,13 @@ __global__ __launch_bounds__(ICP_WG) void k_icp_finish(IcpArgs a, double* __rest
     if (a.plane.pose_ptr[p] == a.plane.pose_ptr[p + 1] && a.line.pose_ptr[p] == a.line.pose_ptr[p + 1])
         return; // (nothing to add: the pose's blocks keep their bits, and its partial slots were never written)
     const double s = icp_pose_sum(a.plane, p, t) + icp_pose_sum(a.line, p, t);
+    int r = 0, c = 0;
     if (t < 21)
-    {
-        int r = 0, k = t;
-        while (k >= 6 - r)
-            k -= 6 - r, r++;
-        const int c = r + k;
-        double* blk = H + 36 * (size_t)(SCHUR ? rowptr[p] : p);
-        blk[r + 6 * c] += s;
-        if (r != c)
-            blk[c + 6 * r] += s;
-    }
-    else
-    {
-        bp[6 * (size_t)p + (t - 21)] += s;
-        if (SCHUR)
-            bsc[6 * (size_t)p + (t - 21)] += s;
-    }
+        tri6_unpack(t, r, c);
+    pose_term_add<SCHUR>(p, t, r, c, s, H, rowptr, bp, bsc);
 }
 
-// chi2 total: the chunk totals in chunk order (one workgroup: strided per thread, then the threads in order)
-__global__ __launch_bounds__(ICP_WG) void k_icp_chi_total(const double* __restrict__ pchi, int n, double* __restrict__ out,
-                                                           int add)
-{
-    __shared__ double s[ICP_WG];
-    double x = 0.0;
-    for (int i = threadIdx.x; i < n; i += ICP_WG)
-        x += pchi[i];
-    s[threadIdx.x] = x;
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        double tot = 0.0;
-        for (int i = 0; i < ICP_WG; i++)
-            tot += s[i];
-        out[0] = add ? out[0] + tot : tot;
-    }
-}
-
-// index check of one kind, with pose_ptr already known to ascend from 0 to n: every edge lies in its pose's range,
-// i.e. the edges are sorted by pose and agree with pose_ptr.  Offending threads write 1 (no atomics needed).
-__global__ __launch_bounds__(ICP_WG) void k_icp_check(const int32_t* __restrict__ pose, const int32_t* __restrict__ ptr,
-                                                       int n, int P, int* __restrict__ bad)
-{
-    for (int i = blockIdx.x * ICP_WG + threadIdx.x; i < n; i += gridDim.x * ICP_WG)
-    {
-        const int q = pose[i];
-        if (q < 0 || q >= P || i < ptr[q] || i >= ptr[q + 1])
-            bad[0] = 1;
-    }
-}
-
-// scratch = [plane partials (cp + n_poses_total slots) | line partials (cl + n_poses_total) | chunk totals (cp + cl) | 16]
+// scratch = [plane partials (cp + n_poses_total slots) | line partials (cl + n_poses_total) | chunk totals (cp + cl)]
 struct IcpLayout
 {
     size_t cp, cl, line_part, cchi, end;
@@ -370,7 +325,7 @@ IcpKind kind_of(const cugo_icp_edges& ev, bool line, double* part, double* cchi)
 
 IcpArgs args_of(const cugo_icp_edges& ev, const double* d_poses, cugo_k::ReduceScratch rs, double* d_edge_chi)
 {
-    if (rs.capacity < cugo_k::icp_scratch_doubles(ev))
+    if (rs.capacity < IcpLayout(ev).end)
         throw std::runtime_error("cugo: ICP scratch too small");
     const IcpLayout lay(ev);
     IcpArgs a;
@@ -391,33 +346,7 @@ namespace cugo_k
 
 size_t icp_scratch_doubles(const cugo_icp_edges& ev)
 {
-    return IcpLayout(ev).end + 16;
-}
-
-int icp_check_indices(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs)
-{
-    if (rs.capacity < icp_scratch_doubles(ev))
-        throw std::runtime_error("cugo: ICP scratch too small");
-    // the flag sits in the slack behind the chunk totals of the scratch layout
-    int* d_bad = reinterpret_cast<int*>(rs.d_partials + IcpLayout(ev).end);
-    if (hipMemsetAsync(d_bad, 0, sizeof(int), s) != hipSuccess)
-        throw std::runtime_error("cugo: hipMemsetAsync failed");
-    const struct
-    {
-        const int32_t *pose, *ptr;
-        int n;
-    } kinds[2] = {{ev.d_plane_pose, ev.d_plane_pose_ptr, ev.n_plane}, {ev.d_line_pose, ev.d_line_pose_ptr, ev.n_line}};
-    for (const auto& k : kinds)
-        if (k.n > 0)
-        {
-            const unsigned grid = (unsigned)std::min<size_t>(1024, ((size_t)k.n + ICP_WG - 1) / ICP_WG);
-            CUGO_LAUNCH(k_icp_check, dim3(grid), dim3(ICP_WG), 0, s, k.pose, k.ptr, k.n, ev.n_poses_total, d_bad);
-        }
-    int bad = 0;
-    if (hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        throw std::runtime_error("cugo: ICP index check failed to run");
-    return bad;
+    return IcpLayout(ev).end;
 }
 
 void launch_icp_chunks(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, ReduceScratch rs,
@@ -455,18 +384,15 @@ void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch
     hipLaunchKernelGGL(k_icp_finish<true>, dim3(finish_grid(ev)), dim3(ICP_WG), 0, s, a, d_Hsc, d_rowptr, d_bp, d_bsc);
 }
 
-const double* icp_chunk_chi(const cugo_icp_edges& ev, ReduceScratch rs, int* n)
+int icp_chunk_count(const cugo_icp_edges& ev)
 {
     const IcpLayout lay(ev);
-    *n = (int)(lay.cp + lay.cl);
-    return rs.d_partials + lay.cchi;
+    return (int)(lay.cp + lay.cl);
 }
 
-void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_chi, bool chi_add)
+static void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_chi, bool chi_add)
 {
-    int n = 0;
-    const double* cchi = icp_chunk_chi(ev, rs, &n);
-    CUGO_LAUNCH(k_icp_chi_total, dim3(1), dim3(ICP_WG), 0, s, cchi, n, d_chi, chi_add ? 1 : 0);
+    launch_pose_chi_total(s, "k_icp_chi_total", rs.d_partials + IcpLayout(ev).cchi, icp_chunk_count(ev), d_chi, chi_add);
 }
 
 void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,

@@ -71,7 +71,7 @@ void launch_build(hipStream_t s, const cugo_edges& ev, const double* d_poses, co
                   bool chi_behind_scale = false);
 
 // the reductions that end a trial, with the chi2 partials of a build pass queued with chi_behind_scale (ba_kernels.hip)
-// d_icp_chi / n_icp_chi (both tails): chi2 totals of the chunks of an ICP pass at the trial's estimates (icp_chunk_chi),
+// d_icp_chi / n_icp_chi (both tails): chi2 totals of the chunks of an ICP pass at the trial's estimates (icp_chunk_count),
 // summed in their order and added to F-hat by the same launch; nullptr / 0: no such edges
 void launch_trial_tail_from_build(hipStream_t s, const cugo_edges& ev, ReduceScratch rs, int n_scale_partials,
                                   double* d_out, const double* d_flag, double* h_out, double seq, unsigned* d_done,
@@ -137,12 +137,24 @@ void launch_errors_tail(hipStream_t s, const cugo_edges& ev, const double* d_pos
 
 size_t reduce_scratch_doubles(int n_edges, int n_poses, int n_landmarks);
 
+// --- shared by the unary pose edge kinds (pose_edge_kernels.hip) ---------------------------
+// the sum of n chi2 totals (ICP chunks, prior workgroups), in their order, to d_chi[0] (added to what is there with
+// chi_add), in a launch of its own under `label`
+void launch_pose_chi_total(hipStream_t s, const char* label, const double* d_totals, int n, double* d_chi, bool chi_add);
+// with pose_ptr known to ascend from 0 to n per kind: 1 if an edge of a kind does not lie in its pose's pose_ptr range
+// (the edges are not sorted by pose, or a pose index is out of range), else 0.  One launch per non-empty kind under
+// its label; d_bad: a device int for the flag.  Synchronises the stream.  `who` names the caller in the message
+struct PoseIndexCheck
+{
+    const int32_t *d_pose, *d_pose_ptr;
+    int n;
+    const char* label;
+};
+int pose_check_indices(hipStream_t s, const char* who, const PoseIndexCheck* kinds, int n_kinds, int n_poses_total, int* d_bad);
+
 // --- point-to-plane / point-to-line pose edges (icp_kernels.hip) -------------------------
-// scratch the launchers need (chunk partials + one chi2 total per chunk)
+// scratch the launchers need (chunk partials, then one chi2 total per chunk at its end)
 size_t icp_scratch_doubles(const cugo_icp_edges& ev);
-// with pose_ptr known to ascend from 0 to n per kind: 1 if an edge does not lie in its pose's pose_ptr range (the
-// edges are not sorted by pose, or a pose index is out of range), else 0.  Synchronises the stream.
-int icp_check_indices(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs);
 // ADDS the ICP terms to d_Hpp / d_bp; chi2 total to d_chi[0] if given (added to what is there with chi_add)
 void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
                       ReduceScratch rs, double* d_chi, bool chi_add = false);
@@ -160,21 +172,15 @@ void launch_icp_add(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, d
 // k_pose_schur, which writes the three in the one-stream form)
 void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, const int32_t* d_rowptr,
                           double* d_Hsc, double* d_bp, double* d_bsc);
-// the chunk totals of the last chunk pass (plane chunks, then line chunks): what launch_errors_tail /
-// launch_trial_tail_from_build sum into F-hat
-const double* icp_chunk_chi(const cugo_icp_edges& ev, ReduceScratch rs, int* n);
-// their sum to d_chi[0] (added to what is there with chi_add), in a launch of its own
-void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_chi, bool chi_add);
+// a chunk pass leaves the chi2 total of every chunk (plane chunks, then line chunks) in the LAST icp_chunk_count()
+// doubles of the scratch: what launch_errors_tail / launch_trial_tail_from_build sum into F-hat
+int icp_chunk_count(const cugo_icp_edges& ev);
 
 // --- SE(3) pose priors with 6 x 6 information (prior_kernels.hip) --------------------------
 // One kernel per pass: 32 lanes per free pose walk its priors in container order and ADD their sums straight to the
 // destination; every workgroup leaves one chi2 total in d_wg_chi [prior_workgroups()].  The LM loop appends these
-// totals to the ICP chunk totals (icp_chunk_chi), so that the launch ending a trial sums them as well.
+// totals to the ICP chunk totals (icp_chunk_count), so that the launch ending a trial sums them as well.
 int prior_workgroups(const cugo_prior_edges& ev); // 0 without edges or free poses: nothing is launched
-// scratch of the kernel-level entry points: the workgroup totals + 16 doubles (the flag of prior_check_indices)
-size_t prior_scratch_doubles(const cugo_prior_edges& ev);
-// with pose_ptr known to ascend from 0 to n: 1 if an edge does not lie in its pose's range, else 0.  Synchronises.
-int prior_check_indices(hipStream_t s, const cugo_prior_edges& ev, ReduceScratch rs);
 // chi2 only; d_edge_chi [n] (sorted order, 0 for edges that do not count) or nullptr
 void launch_prior_errors(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, double* d_wg_chi,
                          double* d_edge_chi = nullptr);
@@ -185,8 +191,6 @@ void launch_prior_add(hipStream_t s, const cugo_prior_edges& ev, const double* d
 // k_pose_schur, which writes the three in the one-stream form)
 void launch_prior_add_schur(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, const int32_t* d_rowptr,
                             double* d_Hsc, double* d_bp, double* d_bsc, double* d_wg_chi);
-// the sum of the workgroup totals to d_chi[0] (added to what is there with chi_add), in a launch of its own
-void launch_prior_chi_total(hipStream_t s, const cugo_prior_edges& ev, const double* d_wg_chi, double* d_chi, bool chi_add);
 
 // chi_e per edge slot (outlier rejection, ref: computeOutliersKernel cuda_block_solver.cu:1135)
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,

@@ -21,7 +21,6 @@
 // order); the error-only form computes exactly these totals, so its chi2 has the bits of the build pass's.  A pose
 // without priors keeps the bits of its blocks; fixed poses (index >= n_poses_free) are never visited.
 #include <hip/hip_runtime.h>
-#include <algorithm>
 #include <stdexcept>
 
 #include "ba_math.h"
@@ -200,12 +199,7 @@ __global__ __launch_bounds__(PRIOR_WG) void k_prior(PriorArgs a, double* __restr
     if (is_b)
         ri = t < 27 ? t - 21 : 0, ci = 6;
     else
-    {
-        int k = t;
-        while (k >= 6 - ri)
-            k -= 6 - ri, ri++;
-        ci = ri + k;
-    }
+        tri6_unpack(t, ri, ci);
     if (p < a.n_poses_free)
     {
         const double* pose = a.poses + 7 * (size_t)p;
@@ -232,21 +226,7 @@ __global__ __launch_bounds__(PRIOR_WG) void k_prior(PriorArgs a, double* __restr
     if (t == 0)
         s_chi[g] = chi;
     if (MODE != PRIOR_ERRORS && any)
-    {
-        if (t < 21)
-        {
-            double* blk = H + 36 * (size_t)(MODE == PRIOR_SCHUR ? rowptr[p] : p);
-            blk[ri + 6 * ci] += mine;
-            if (ri != ci)
-                blk[ci + 6 * ri] += mine;
-        }
-        else if (t < 27)
-        {
-            bp[6 * (size_t)p + (t - 21)] += mine;
-            if (MODE == PRIOR_SCHUR)
-                bsc[6 * (size_t)p + (t - 21)] += mine;
-        }
-    }
+        pose_term_add<MODE == PRIOR_SCHUR>(p, t, ri, ci, mine, H, rowptr, bp, bsc);
     __syncthreads();
     if (threadIdx.x == 0)
     {
@@ -255,37 +235,6 @@ __global__ __launch_bounds__(PRIOR_WG) void k_prior(PriorArgs a, double* __restr
         for (int i = 0; i < PRIOR_POSES; i++)
             tot += s_chi[i];
         a.wg_chi[blockIdx.x] = tot;
-    }
-}
-
-// chi2 total: the workgroup totals in order (one workgroup: strided per thread, then the threads in order)
-__global__ __launch_bounds__(PRIOR_WG) void k_prior_chi_total(const double* __restrict__ pchi, int n, double* __restrict__ out,
-                                                               int add)
-{
-    __shared__ double s[PRIOR_WG];
-    double x = 0.0;
-    for (int i = threadIdx.x; i < n; i += PRIOR_WG)
-        x += pchi[i];
-    s[threadIdx.x] = x;
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        double tot = 0.0;
-        for (int i = 0; i < PRIOR_WG; i++)
-            tot += s[i];
-        out[0] = add ? out[0] + tot : tot;
-    }
-}
-
-// with pose_ptr known to ascend from 0 to n: every edge lies in its pose's range.  Offending threads write 1.
-__global__ __launch_bounds__(PRIOR_WG) void k_prior_check(const int32_t* __restrict__ pose, const int32_t* __restrict__ ptr,
-                                                           int n, int P, int* __restrict__ bad)
-{
-    for (int i = blockIdx.x * PRIOR_WG + threadIdx.x; i < n; i += gridDim.x * PRIOR_WG)
-    {
-        const int q = pose[i];
-        if (q < 0 || q >= P || i < ptr[q] || i >= ptr[q + 1])
-            bad[0] = 1;
     }
 }
 
@@ -309,27 +258,6 @@ namespace cugo_k
 int prior_workgroups(const cugo_prior_edges& ev)
 {
     return ev.n > 0 && ev.n_poses_free > 0 ? (ev.n_poses_free + PRIOR_POSES - 1) / PRIOR_POSES : 0;
-}
-
-size_t prior_scratch_doubles(const cugo_prior_edges& ev) { return (size_t)prior_workgroups(ev) + 16; }
-
-int prior_check_indices(hipStream_t s, const cugo_prior_edges& ev, ReduceScratch rs)
-{
-    if (rs.capacity < prior_scratch_doubles(ev))
-        throw std::runtime_error("cugo: prior scratch too small");
-    int* d_bad = reinterpret_cast<int*>(rs.d_partials + prior_workgroups(ev)); // (the slack behind the totals)
-    if (hipMemsetAsync(d_bad, 0, sizeof(int), s) != hipSuccess)
-        throw std::runtime_error("cugo: hipMemsetAsync failed");
-    if (ev.n > 0)
-    {
-        const unsigned grid = (unsigned)std::min<size_t>(1024, ((size_t)ev.n + PRIOR_WG - 1) / PRIOR_WG);
-        CUGO_LAUNCH(k_prior_check, dim3(grid), dim3(PRIOR_WG), 0, s, ev.d_pose, ev.d_pose_ptr, ev.n, ev.n_poses_total, d_bad);
-    }
-    int bad = 0;
-    if (hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        throw std::runtime_error("cugo: prior index check failed to run");
-    return bad;
 }
 
 void launch_prior_errors(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, double* d_wg_chi,
@@ -365,11 +293,6 @@ void launch_prior_add_schur(hipStream_t s, const cugo_prior_edges& ev, const dou
     const PriorArgs a = args_of(ev, d_poses, d_wg_chi, nullptr);
     LaunchScope scope("k_prior_add_schur", s);
     hipLaunchKernelGGL(k_prior<PRIOR_SCHUR>, dim3(wgs), dim3(PRIOR_WG), 0, s, a, d_Hsc, d_rowptr, d_bp, d_bsc);
-}
-
-void launch_prior_chi_total(hipStream_t s, const cugo_prior_edges& ev, const double* d_wg_chi, double* d_chi, bool chi_add)
-{
-    CUGO_LAUNCH(k_prior_chi_total, dim3(1), dim3(PRIOR_WG), 0, s, d_wg_chi, prior_workgroups(ev), d_chi, chi_add ? 1 : 0);
 }
 
 } // namespace cugo_k

@@ -107,6 +107,59 @@ def test_lm_trajectory_against_the_reference(name, pose_schur, monkeypatch):
         assert out["sstats"]["hsc_blocks"] == 4
 
 
+def subset_recipe(seed=21):
+    """4 poses (pose 0 fixed) / 30 landmarks with BA edges, 600 plane edges on the free poses (two chunks of 512: the
+    priors' totals start behind more than one chunk total; per-edge omega, Huber), 40 line edges (less than a chunk;
+    pose 2 has none; one omega) and one dense-Omega prior per free pose"""
+    d = synth.make_problem(n_poses=4, n_landmarks=30, seed=seed, fixed_poses=(0,))
+    rng = np.random.default_rng(seed)
+    pl = R.icp_edges(rng, d, [0, 250, 200, 150], "plane", 0.02)
+    li = R.icp_edges(rng, d, [0, 25, 0, 15], "line", 0.02)
+    kinds = dict(plane=("plane", pl, rng.uniform(0.5, 2.0, len(pl["pose"])) * 2e3, np.ones(len(pl["pose"]), bool),
+                        (R.icp_ref.RK_HUBER, 4.0)),
+                 line=("line", li, np.array([2.4e3]), np.ones(len(li["pose"]), bool), (R.icp_ref.RK_NONE, 1.0)))
+    free = np.array([1, 2, 3])
+    gt = d["pose_gt"]
+    prior = PR.make_prior(free, [PR.displaced(rng, gt[p], 0.01, 0.05) for p in free], [PR.random_spd(rng, 50.0) for _ in free])
+    return d, kinds, prior
+
+
+_SUBSET_REF = {}
+SUBSETS = [("plane",), ("line",), ("prior",), ("plane", "line"), ("plane", "prior"), ("line", "prior"),
+           ("plane", "line", "prior")]
+
+
+@pytest.mark.parametrize("subset", SUBSETS, ids="+".join)
+def test_every_subset_of_pose_edge_kinds(subset, monkeypatch):
+    """BA edges + every non-empty subset of {plane, line, prior}: an ICP kind alone (the other one's pose_ptr is all
+    zeros), an ICP kind with priors, priors behind two chunk totals.  5 iterations in both forms of the loop against
+    prior_ref.PriorGraph, by the comparison and the tolerance rule of test_lm_trajectory_against_the_reference (from
+    reference_runs' own sensitivity), and two runs agree to the bit"""
+    niter = 5
+    d, kinds, prior = subset_recipe()
+    icp = [kinds[k] for k in ("plane", "line") if k in subset]
+    if subset not in _SUBSET_REF:
+        none = PR.make_prior(prior["pose"][:0], prior["z"][:0], prior["info"][:1])
+        tr, pose, lm, sens, est = PR.reference_runs(d, icp, prior if "prior" in subset else none, niter)
+        assert len(tr) == niter
+        assert all(abs(t["rho"]) >= 0.1 for t in tr), "a decision at rho near 0 is not a fair comparison"
+        _SUBSET_REF[subset] = (tr, pose, lm) + R.tolerances(sens, est)
+    tr, pose, lm, tol, etol = _SUBSET_REF[subset]
+    for pose_schur in ("1", "0"):
+        monkeypatch.setenv("CUGO_POSE_SCHUR", pose_schur)
+        out = run(d, icp, prior if "prior" in subset else None, niter)
+        for a, b in zip(out["stats"], tr):
+            print("+".join(subset), pose_schur, "chi2 %.15g ref %.15g rel %.3g lam %.6g ref %.6g trials %d ref %d" %
+                  (a["chi2"], b["chi2"], abs(a["chi2"] - b["chi2"]) / b["chi2"], a["lam"], b["lam"], a["trials"], b["trials"]))
+        assert out["n_prior"] == (3 if "prior" in subset else 0)
+        assert out["nedges"] == len(d["e_pose"]) + sum(len(k[1]["pose"]) for k in icp) + out["n_prior"]
+        assert_trajectories_match(out["stats"], tr, tol)
+        np.testing.assert_allclose(out["pose"], pose, rtol=0, atol=etol)
+        np.testing.assert_allclose(out["lm"], lm, rtol=0, atol=10 * etol)
+        assert out["sstats"]["trial_sync_retries"] == 0
+        same_bits(out, run(d, icp, prior if "prior" in subset else None, niter))
+
+
 def bit_cases():
     for name in ("gauge", "mixed", "reject"):
         d, icp, prior = PR.CASES[name][0]()
