@@ -2601,6 +2601,9 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
     if (ev.E > 0 && !have_T) // have_T: the build pass left invHll and T for this lambda (launch_build)
         CUGO_LAUNCH_T(k_schur_edges, S, dim3(div_up(ev.E, BS)), dim3(BS), 0, s, ev, lambda, d_Hll,
                       d_Hpl, d_invHll, d_T);
+    // one-stream form (k_build_edges with lmrec): T holds G and Hpl was not written, Hsc_ij = - sum G_i G_j^T — for the
+    // off-diagonal kernel on the matrix cores and for the one on the vector lanes (CUGO_HSC_MFMA=0) alike
+    const S* d_Hpl_off = (have_T && rows.d_lmrec) ? (const S*)d_T : d_Hpl;
     if (hs.n_blocks > 0 && rows.d_off_pi && hs.d_rowptr && ev.P > 0)
     { // one workgroup per block row, the row's T blocks staged in LDS (k_hsc_offdiag_strip)
         static bool attr_set[2] = {false, false};
@@ -2620,18 +2623,16 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
         // way the kernel is bound by its L2 misses, and rows that share T operands now meet in one L2 (the
         // vector-lane kernel, bound by LDS reads, was slower with this mapping: 123 vs 112 us)
         ::cugo_k::LaunchScope _scope("k_hsc_offdiag_mfma", s);
-        if (have_T && rows.d_lmrec) // one-stream form (k_build_edges with lmrec): T holds G, Hsc_ij = - sum G_i G_j^T
-            d_Hpl = (const S*)d_T;
         if (rows.xcd)
             hipLaunchKernelGGL((k_hsc_offdiag_mfma<S, true>), dim3(xcd_grid(div_up(hs.n_blocks, BS / 64))), dim3(BS), 0, s,
-                               hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl, (const S*)d_T, d_Hsc);
+                               hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl_off, (const S*)d_T, d_Hsc);
         else
             hipLaunchKernelGGL((k_hsc_offdiag_mfma<S, false>), dim3(div_up(hs.n_blocks, BS / 64)), dim3(BS), 0, s,
-                               hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl, (const S*)d_T, d_Hsc);
+                               hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl_off, (const S*)d_T, d_Hsc);
     }
     else if (hs.n_blocks > 0)
         CUGO_LAUNCH_T(k_hsc_offdiag, S, dim3(div_up(hs.n_blocks, BS / 64)), dim3(BS), 0, s,
-                      hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl, (const S*)d_T, d_Hsc);
+                      hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl_off, (const S*)d_T, d_Hsc);
     if (ev.P > 0 && have_T && rows.d_lmrec)
     { // fused iteration: diagonal blocks, bp and bsc from the build pass's records (its pose pass was skipped)
         const double* d_rec = rows.rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);

@@ -178,7 +178,9 @@ void cugo_hsc_plan_destroy(cugo_hsc_plan* plan);
 /* ref: gpu::addLambda(Hll) + gpu::computeBschure + gpu::computeHschure
  * (cuda_block_solver.h:83-109; .cu:1256-1345).  Damping is applied on the fly (Hpp/Hll are
  * left undamped, so no backup/restoreDiagonal pass exists).
- *   d_invHll [Lfree][9] = (Hll + lambda I)^-1,  d_T [E][18] = Hpl * invHll,
+ *   d_invHll [Lfree][9] = (Hll + lambda I)^-1 (written by the landmark's first edge slot: the block of a free landmark
+ *   without any edge slot is left untouched — nothing reads it, cugo_backsubst_update gives such a landmark a zero step),
+ *   d_T [E][18] = Hpl * invHll (zero blocks for edges with a fixed endpoint and for inactive slots),
  *   d_bsc [Pfree][6] = bp - sum T bl,
  *   d_Hsc [B][36] = Hpp(diag) - sum T Hpl^T            (+ lambda I on diagonal blocks when
  *   damp_hsc_diag != 0, which reproduces the reference's damped Hsc exactly).
@@ -234,7 +236,9 @@ int cugo_chol_plan_array64(cugo_chol* s, const char* name, const int64_t** out);
 /* ref: gpu::schurComplementPost + updatePoses + updateLandmarks + computeScale
  * (cuda_block_solver.h:133-150; .cu:1419-1490).  Reads estimates from d_*_in, writes the
  * updated ("trial") estimates to d_*_out (push/pop of block_solver.cpp:431-439 becomes a
- * buffer swap).  d_scale[0] = sum_i x_i (lambda x_i + b_i) over [xp; xl]. */
+ * buffer swap).  d_scale[0] = sum_i x_i (lambda x_i + b_i) over [xp; xl].  Only the rows of FREE vertices of
+ * d_poses_out / d_lms_out are written: the rows of fixed vertices are left untouched (the caller keeps them equal in
+ * both buffers).  A free landmark without any edge slot gets a zero step. */
 int cugo_backsubst_update(cugo_ctx* ctx, const cugo_edges* ev, double lambda,
                           const double* d_invHll, const double* d_bl, const double* d_bp,
                           const void* d_Hpl, const double* d_xp, double* d_xl,
