@@ -462,6 +462,7 @@ int cugo_chol_plan_array(cugo_chol* s, const char* name, const int32_t** out)
     CUGO_PLAN_FIELD(col0);
     CUGO_PLAN_FIELD(col_front);
     CUGO_PLAN_FIELD(stage_task_ptr);
+    CUGO_PLAN_FIELD(stage_tile);
     CUGO_PLAN_FIELD(task_ptr);
     CUGO_PLAN_FIELD(task_fronts);
     CUGO_PLAN_FIELD(blk_front);

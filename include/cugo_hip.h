@@ -224,7 +224,8 @@ int cugo_chol_plan_get(const cugo_chol* s, int32_t* perm, int32_t* super_ptr, in
                        int32_t* rows, int32_t* parent);
 /* named int32 plan array ("perm", "super_ptr", "rows_ptr", "rows", "sparent", "child_ptr",
  * "child", "rel_ptr", "rel", "ncb", "nb", "col0", "col_front", "stage_task_ptr", "task_ptr",
- * "task_fronts", "blk_front", "blk_row", "blk_col", "blk_trans"; "ea1": the potrf's child link
+ * "task_fronts", "blk_front", "blk_row", "blk_col", "blk_trans"; "stage_tile": per stage the edge of
+ * its update tiles, 32 or 64, 0 for the two-phase form; "ea1": the potrf's child link
  * records, 16 ints each); pointer valid until the next analyze()/destroy. Returns the length or a
  * negative error. */
 int cugo_chol_plan_array(cugo_chol* s, const char* name, const int32_t** out);

@@ -13,6 +13,7 @@ import pytest
 if __name__ == "__main__":  # (the child process of the delay test: the package lies one directory up)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import chol_designed
 from test_host import covis_pattern, patterns, plan_arrays, random_spd_bsr
 
 cugo = importlib.import_module("cuda-bundle-adjustment_amd")
@@ -40,6 +41,8 @@ def synth_pattern(n_poses, n_lm, n_edges, seed, lc):
 def pattern(name):
     if name == "synthetic":
         return synth_pattern(160, 2500, 10500, 3, 80)
+    if name in chol_designed.NAMES:
+        return chol_designed.design(name)[:2]
     return csr(patterns()[name])
 
 
@@ -70,7 +73,7 @@ HOST_ENVS = [{}, {"CUGO_ND_LEAF": "4", "CUGO_MAX_SUPER_COLS": "3", "CUGO_TARGET_
              {"CUGO_MAX_SUPER_COLS": "1"}]
 
 
-@pytest.mark.parametrize("name", list(patterns().keys()) + ["synthetic"])
+@pytest.mark.parametrize("name", list(patterns().keys()) + ["synthetic"] + list(chol_designed.NAMES))
 @pytest.mark.parametrize("env", HOST_ENVS)
 def test_ticket_order_and_segments_replay_the_backward_pass(lib, name, env, monkeypatch):
     """every front holds one ticket; every segment names a front with a smaller ticket; the segments of a front tile

@@ -9,7 +9,7 @@ import importlib
 import numpy as np
 import pytest
 
-from test_host import covis_pattern, patterns, plan_arrays, random_spd_bsr
+from test_host import covis_pattern, patterns, plan_arrays, random_spd_bsr, tri_inverse
 
 cugo = importlib.import_module("cuda-bundle-adjustment_amd")
 
@@ -40,8 +40,9 @@ def _plan(lib, rowptr, colind):
     return pl
 
 
-def _factor(pl, vals, lam):
-    """per front: L11^-1 (W) and L21, the factorisation the plan describes (extend-add through rel)"""
+def _factor(pl, vals, lam, explicit_w=False):
+    """per front: L11^-1 (W) and L21, the factorisation the plan describes (extend-add through rel); explicit_w: W by
+    forward substitution and L21 = B W^T, as the device forms them (the default goes through numpy's LU)"""
     ns = len(pl["ncb"])
     F = [np.zeros((6 * pl["nb"][f], 6 * pl["nb"][f])) for f in range(ns)]
     for k in range(len(pl["blk_front"])):
@@ -64,8 +65,12 @@ def _factor(pl, vals, lam):
                 A11 = np.tril(F[f][:nc, :nc])
                 A11 = A11 + np.tril(A11, -1).T
                 L11 = np.linalg.cholesky(A11)
-                l21 = np.linalg.solve(L11, F[f][nc:, :nc].T).T
-                W[f] = np.linalg.inv(L11)
+                if explicit_w:
+                    W[f] = tri_inverse(L11)
+                    l21 = F[f][nc:, :nc] @ W[f].T
+                else:
+                    l21 = np.linalg.solve(L11, F[f][nc:, :nc].T).T
+                    W[f] = np.linalg.inv(L11)
                 L21[f] = l21
                 F[f][nc:, nc:] -= l21 @ l21.T
     return W, L21

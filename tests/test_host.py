@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import chol_designed
 from conftest import ROOT
 
 cugo = importlib.import_module("cuda-bundle-adjustment_amd")
@@ -114,9 +115,40 @@ def plan_arrays(lib, s):
     return out
 
 
-def replay_multifrontal(pl, vals, lam, b):
+def tri_inverse(L):
+    """inverse of a lower triangular matrix by forward substitution, row by row"""
+    n = L.shape[0]
+    W = np.zeros((n, n))
+    for i in range(n):
+        W[i, :i] = -(L[i, :i] @ W[:i, :i]) / L[i, i]
+        W[i, i] = 1.0 / L[i, i]
+    return W
+
+
+def potrf_rsqrt(A, rel_err):
+    """right-looking Cholesky of the lower triangle of A whose every 1 / sqrt(pivot) is off by rel_err"""
+    A = np.tril(A).copy()
+    for j in range(A.shape[0]):
+        r = (1.0 + rel_err) / np.sqrt(A[j, j])
+        A[j:, j] *= r
+        A[j + 1:, j + 1:] -= np.tril(np.outer(A[j + 1:, j], A[j + 1:, j]))
+    return A
+
+
+def replay_multifrontal(pl, vals, lam, b, explicit_w=False, mutate=None):
     """numpy replay of the device algorithm using ONLY the plan's maps (assembly, extend-add
-    through rel, stage/task order, rhs-row trick, backward pass)."""
+    through rel, stage/task order, rhs-row trick, backward pass).
+
+    explicit_w: W = L11^-1 is formed, L21 = B W^T and the backward pass multiplies by W^T, as the device does (the
+    default solves with L11 through numpy's LU).
+    mutate: one deliberate mistake, for the tests that show a metric notices it (tests/test_chol_designed_host.py):
+      ("skip_rhs_update", f)   the rhs row of front f takes no part in its update
+      ("drop_child", f, k)     the k-th child of front f is not added
+      ("rel_shift", c, k, d)   rel entry k of child c is off by d
+      ("pad_leak", f)          the first padding column (6 ncb) of the first boundary row of front f's L21 holds 1.0
+                               instead of 0 and the update sums over the padded width
+      ("rsqrt_err", e)         every pivot's d^-1/2 carries the relative error e"""
+    mut = mutate[0] if mutate else None
     ns = len(pl["ncb"])
     n = len(pl["perm"])
     F = []
@@ -142,11 +174,16 @@ def replay_multifrontal(pl, vals, lam, b):
             for f in pl["task_fronts"][pl["task_ptr"][t]:pl["task_ptr"][t + 1]]:
                 order.append(f)
                 # children must be complete (earlier stage, or earlier in the same task)
-                for c in pl["child"][pl["child_ptr"][f]:pl["child_ptr"][f + 1]]:
+                for kc, c in enumerate(pl["child"][pl["child_ptr"][f]:pl["child_ptr"][f + 1]]):
                     assert done[c]
+                    if mut == "drop_child" and mutate[1] == f and mutate[2] == kc:
+                        continue
                     ncb, nb = pl["ncb"][c], pl["nb"][c]
                     rel = pl["rel"][pl["rel_ptr"][c]:pl["rel_ptr"][c + 1]]
                     assert len(rel) == nb - ncb
+                    if mut == "rel_shift" and mutate[1] == c:
+                        rel = rel.copy()
+                        rel[mutate[2]] += mutate[3]
                     idx = np.concatenate([6 * np.repeat(rel, 6) + np.tile(np.arange(6), len(rel)),
                                           [F[f].shape[0] - 1]]).astype(int)
                     U = F[c][6 * ncb:, 6 * ncb:]
@@ -155,11 +192,18 @@ def replay_multifrontal(pl, vals, lam, b):
                     F[f][-1, idx[:-1]] += U[-1]
                 nc = 6 * pl["ncb"][f]
                 A11 = np.tril(F[f][:nc, :nc]); A11 = A11 + np.tril(A11, -1).T
-                L11 = np.linalg.cholesky(A11)
-                L21 = np.linalg.solve(L11, F[f][nc:, :nc].T).T
+                L11 = potrf_rsqrt(A11, mutate[1]) if mut == "rsqrt_err" else np.linalg.cholesky(A11)
+                if explicit_w:
+                    L21 = F[f][nc:, :nc] @ tri_inverse(L11).T
+                else:
+                    L21 = np.linalg.solve(L11, F[f][nc:, :nc].T).T
                 F[f][:nc, :nc] = L11
                 F[f][nc:, :nc] = L21
                 S = L21 @ L21[:-1].T
+                if mut == "skip_rhs_update" and mutate[1] == f:
+                    S[-1] = 0.0
+                if mut == "pad_leak" and mutate[1] == f:
+                    S[0, 0] += 1.0
                 F[f][nc:, nc:] -= S
                 done[f] = True
     assert done.all() and len(order) == ns
@@ -171,7 +215,7 @@ def replay_multifrontal(pl, vals, lam, b):
         y = F[f][-1, :nc].copy()
         L21 = F[f][nc:-1, :nc]
         v = y - L21.T @ xnew[ridx]
-        xj = np.linalg.solve(F[f][:nc, :nc].T, v)
+        xj = tri_inverse(F[f][:nc, :nc]).T @ v if explicit_w else np.linalg.solve(F[f][:nc, :nc].T, v)
         c0 = 6 * pl["col0"][f]
         xnew[c0:c0 + nc] = xj
     x = np.zeros(6 * n)
@@ -299,7 +343,7 @@ def test_one_pass_assembly_map_equals_clear_plus_scatter(lib, name):
     lib.cugo_chol_destroy(s)
 
 
-@pytest.mark.parametrize("name", list(patterns().keys()) + ["synthetic"])
+@pytest.mark.parametrize("name", list(patterns().keys()) + ["synthetic"] + list(chol_designed.NAMES))
 @pytest.mark.parametrize("env", [{}, {"CUGO_ND_LEAF": "4", "CUGO_MAX_SUPER_COLS": "3", "CUGO_TARGET_TASKS": "4"},
                                  {"CUGO_ND_LEAF": "1000", "CUGO_MAX_SUPER_COLS": "1", "CUGO_TARGET_TASKS": "100000"}])
 def test_symbolic_plan_replay_solves_the_system(lib, name, env, monkeypatch):
@@ -312,6 +356,8 @@ def test_symbolic_plan_replay_solves_the_system(lib, name, env, monkeypatch):
         ep = d["e_pose"].astype(np.int64) - 1
         ep[ep < 0] = 10**6
         rowptr, colind = covis_pattern(119, ep, d["e_lm"])
+    elif name in chol_designed.NAMES:
+        rowptr, colind, _ = chol_designed.design(name)
     else:
         rows = patterns()[name]
         rowptr = np.array([0] + list(np.cumsum([len(r) for r in rows])), np.int32)
