@@ -115,6 +115,19 @@ def check(rc):
         raise CugoError("cugo error %d: %s" % (rc, lib().cugo_last_error().decode()))
 
 
+def icp_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
+    """cugo_icp_construct_quadratic_form_schur: the ICP terms of `ev` (IcpEdges) ADDED to the Schur destination, as the
+    default LM loop adds them.  ctx: a cugo_ctx handle; the d_* are device pointers; d_rowptr (int32): rowptr[p] is the
+    block index of pose p's diagonal block in d_Hsc; b goes to d_bp and to d_bsc alike.  Every handle and pointer must be a
+    ctypes.c_void_p (what tests/devmem.py's Ctx hands out): a plain Python int would be passed as a C int"""
+    check(lib().cugo_icp_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def prior_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
+    """cugo_prior_construct_quadratic_form_schur: as icp_construct_quadratic_form_schur, for PriorEdges"""
+    check(lib().cugo_prior_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
 def device_count():
     return lib().cugo_device_count()
 

@@ -237,6 +237,27 @@ int cugo_icp_construct_quadratic_form(cugo_ctx* ctx, const cugo_icp_edges* ev, c
     });
 }
 
+int cugo_icp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_icp_edges* ev, const double* d_poses,
+                                            const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::ReduceScratch rs = check_icp(ctx, ev);
+        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
+            throw std::runtime_error("cugo_icp: missing rowptr, Hsc, bp or bsc");
+        // (what the one-stream form of the LM loop queues: the chunk pass, the per-pose sums into the Schur destination,
+        //  the chunk totals at the end of the ICP scratch)
+        cugo_k::launch_icp_chunks(ctx->stream, *ev, d_poses, true, rs);
+        cugo_k::launch_icp_add_schur(ctx->stream, *ev, rs, d_rowptr, d_Hsc, d_bp, d_bsc);
+        if (d_chi)
+        {
+            const int n_chi = cugo_k::icp_chunk_count(*ev);
+            cugo_k::launch_pose_chi_total(ctx->stream, "k_icp_chi_total",
+                                          rs.d_partials + cugo_k::icp_scratch_doubles(*ev) - n_chi, n_chi, d_chi, false);
+        }
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
 } // extern "C"
 
 namespace
@@ -280,6 +301,20 @@ int cugo_prior_construct_quadratic_form(cugo_ctx* ctx, const cugo_prior_edges* e
     return guarded([&] {
         const cugo_k::ReduceScratch rs = check_prior(ctx, ev);
         cugo_k::launch_prior_add(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs.d_partials);
+        if (d_chi)
+            cugo_k::launch_pose_chi_total(ctx->stream, "k_prior_chi_total", rs.d_partials, cugo_k::prior_workgroups(*ev), d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_prior_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_prior_edges* ev, const double* d_poses,
+                                              const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::ReduceScratch rs = check_prior(ctx, ev);
+        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
+            throw std::runtime_error("cugo_prior: missing rowptr, Hsc, bp or bsc");
+        cugo_k::launch_prior_add_schur(ctx->stream, *ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, rs.d_partials);
         if (d_chi)
             cugo_k::launch_pose_chi_total(ctx->stream, "k_prior_chi_total", rs.d_partials, cugo_k::prior_workgroups(*ev), d_chi, false);
         CUGO_HIP(hipGetLastError());

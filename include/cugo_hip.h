@@ -299,6 +299,15 @@ int cugo_icp_compute_errors(cugo_ctx* ctx, const cugo_icp_edges* ev, const doubl
 int cugo_icp_construct_quadratic_form(cugo_ctx* ctx, const cugo_icp_edges* ev, const double* d_poses, double* d_Hpp,
                                       double* d_bp, double* d_chi);
 
+/* The same terms into the Schur destination, as the default LM loop adds them (the chunk pass, then the per-pose sums,
+ * then the chi2 total: the launches of that loop).  d_rowptr [>= n_poses_free]: rowptr[p] is the BLOCK INDEX of pose p's
+ * diagonal block in d_Hsc (the first block of row p of the upper block CSR of cugo_hsc_struct); sum w J^T J is ADDED to
+ * that 6 x 6 column-major block and to no other, -sum w J^T r is ADDED to d_bp [n_poses_free][6] and, the same term, to
+ * d_bsc [n_poses_free][6].  d_chi and the checks as above; rowptr is the caller's (it is not checked against a block
+ * count).  The diagonal blocks and bp receive the bits cugo_icp_construct_quadratic_form adds to Hpp and bp. */
+int cugo_icp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_icp_edges* ev, const double* d_poses,
+                                            const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi);
+
 /*
  * Extension (the reference has no such edge): SE(3) pose priors, unary edges on a pose with a measurement
  * Z = (q_z, t_z) and a full 6 x 6 information matrix Omega (symmetric, positive semi-definite).  With the pose (q, t)
@@ -338,6 +347,12 @@ int cugo_prior_compute_errors(cugo_ctx* ctx, const cugo_prior_edges* ev, const d
  * blocks.  Index checks as above.  No atomics. */
 int cugo_prior_construct_quadratic_form(cugo_ctx* ctx, const cugo_prior_edges* ev, const double* d_poses, double* d_Hpp,
                                         double* d_bp, double* d_chi);
+
+/* The same terms into the Schur destination (see cugo_icp_construct_quadratic_form_schur): rowptr[p] is the block index
+ * of pose p's diagonal block in d_Hsc; b is ADDED to d_bp and to d_bsc alike.  A pose without a counting prior keeps the
+ * bits of its blocks. */
+int cugo_prior_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_prior_edges* ev, const double* d_poses,
+                                              const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi);
 
 /* ---- (2) graph-level entry points ---------------------------------------------------- */
 
