@@ -70,6 +70,14 @@ class PriorEdges(C.Structure):
                 ("n_info", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int), ("delta", C.c_double)]
 
 
+class RelPoseEdges(C.Structure):
+    """cugo_relpose_edges: relative-pose SE(3) edges with 6 x 6 information in the caller's order; the layout (who walks
+    which edge, where the off-diagonal block goes) is the plan's (relpose_plan_create; cugo_hip.h)."""
+    _fields_ = [("n_poses_total", C.c_int), ("n_poses_free", C.c_int), ("n", C.c_int),
+                ("d_meas", C.c_void_p), ("d_info", C.c_void_p), ("n_info", C.c_int), ("d_flags", C.c_void_p),
+                ("rk", C.c_int), ("delta", C.c_double), ("plan", C.c_void_p)]
+
+
 class HscStruct(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("d_rowptr", C.c_void_p), ("d_colind", C.c_void_p),
                 ("d_off_ptr", C.c_void_p), ("d_off_ei", C.c_void_p), ("d_off_ej", C.c_void_p),
@@ -126,6 +134,73 @@ def icp_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, 
 def prior_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
     """cugo_prior_construct_quadratic_form_schur: as icp_construct_quadratic_form_schur, for PriorEdges"""
     check(lib().cugo_prior_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32)
+
+
+def relpose_pattern(n_poses_free, pose_a, pose_b, flags=None):
+    """cugo_relpose_pattern: (rowptr, colind) of the upper block CSR of a pure pose graph (host arrays, no GPU)"""
+    a, b = _i32(pose_a), _i32(pose_b)
+    fl = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+    args = (len(a), int(n_poses_free), a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p),
+            None if fl is None else fl.ctypes.data_as(_u8p))
+    nnzb = C.c_int(0)
+    rowptr = np.zeros(int(n_poses_free) + 1, np.int32)
+    check(lib().cugo_relpose_pattern(*args, rowptr.ctypes.data_as(_i32p), None, C.byref(nnzb)))
+    colind = np.zeros(max(nnzb.value, 1), np.int32)
+    check(lib().cugo_relpose_pattern(*args, rowptr.ctypes.data_as(_i32p), colind.ctypes.data_as(_i32p), C.byref(nnzb)))
+    return rowptr, colind[:nnzb.value]
+
+
+class RelPosePlan:
+    """cugo_relpose_plan: incidence lists and off-diagonal block indices of a set of relative-pose edges against an
+    upper block-CSR pattern (host arrays).  ctx: a cugo_ctx handle (ctypes.c_void_p), or None for a host-only plan"""
+
+    def __init__(self, ctx, n_poses_total, n_poses_free, pose_a, pose_b, flags, rowptr, colind):
+        a, b, rp, ci = _i32(pose_a), _i32(pose_b), _i32(rowptr), _i32(colind)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+        self._p = C.c_void_p()
+        self.n, self.n_poses_total, self.n_poses_free = len(a), int(n_poses_total), int(n_poses_free)
+        check(lib().cugo_relpose_plan_create(ctx, len(a), self.n_poses_total, self.n_poses_free,
+                                             a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p),
+                                             None if fl is None else fl.ctypes.data_as(_u8p),
+                                             rp.ctypes.data_as(_i32p), ci.ctypes.data_as(_i32p), C.byref(self._p)))
+
+    @property
+    def handle(self):
+        return self._p
+
+    def array(self, name):
+        """a copy of the plan array inc_ptr, inc (edge << 1 | side) or off_blk"""
+        out = _i32p()
+        n = lib().cugo_relpose_plan_array(self._p, name.encode(), C.byref(out))
+        if n < 0:
+            raise CugoError("cugo error %d: %s" % (n, lib().cugo_last_error().decode()))
+        return np.array(out[:n], np.int32)
+
+    def close(self):
+        if self._p:
+            lib().cugo_relpose_plan_destroy(self._p)
+            self._p = C.c_void_p()
+
+
+def relpose_compute_errors(ctx, ev, d_poses, d_chi, d_edge_chi=None):
+    """cugo_relpose_compute_errors: chi2 total of `ev` (RelPoseEdges) to d_chi[0], optionally the term of every edge"""
+    check(lib().cugo_relpose_compute_errors(ctx, C.byref(ev), d_poses, d_chi, d_edge_chi))
+
+
+def relpose_construct_quadratic_form(ctx, ev, d_poses, d_Hpp, d_bp, d_Hoff, d_chi=None):
+    """cugo_relpose_construct_quadratic_form: diagonal terms ADDED to d_Hpp / d_bp, off-diagonal blocks to d_Hoff
+    [nnzb][36] by the plan's block indices"""
+    check(lib().cugo_relpose_construct_quadratic_form(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_Hoff, d_chi))
+
+
+def relpose_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
+    """cugo_relpose_construct_quadratic_form_schur: as prior_construct_quadratic_form_schur, plus the off-diagonal
+    blocks into d_Hsc by the plan's block indices"""
+    check(lib().cugo_relpose_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
 
 
 def device_count():

@@ -15,6 +15,7 @@
 #include "engine.h"
 #include "hip_util.h"
 #include "rccl_comm.h"
+#include "relpose_plan.h"
 #include "schur_plan.h"
 
 using namespace cugo_host;
@@ -317,6 +318,152 @@ int cugo_prior_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_prior_ed
         cugo_k::launch_prior_add_schur(ctx->stream, *ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, rs.d_partials);
         if (d_chi)
             cugo_k::launch_pose_chi_total(ctx->stream, "k_prior_chi_total", rs.d_partials, cugo_k::prior_workgroups(*ev), d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+} // extern "C"
+
+// the plan of a set of relative-pose edges: the host plan (relpose_plan.h) and, with a context, its copy on the device
+struct cugo_relpose_plan
+{
+    cugo_host::RelPosePlanHost host;
+    bool on_device = false;
+    cugo_host::DevBuf<int32_t> pose_a, pose_b, inc_ptr, inc, off_blk;
+    cugo_k::RelPosePlanDev dev() const
+    {
+        return {host.n, host.n_poses_free, pose_a.data(), pose_b.data(), inc_ptr.data(), inc.data(), off_blk.data()};
+    }
+};
+
+namespace
+{
+// the layout is the plan's own, so nothing is checked on the device: counts against the plan, arrays, kernel code
+cugo_k::ReduceScratch check_relpose(cugo_ctx* ctx, const cugo_relpose_edges* ev)
+{
+    if (!ev || !ev->plan)
+        throw std::runtime_error("cugo_relpose: no edges or no plan (cugo_relpose_plan_create)");
+    const cugo_host::RelPosePlanHost& h = ev->plan->host;
+    if (ev->n != h.n || ev->n_poses_total != h.n_poses_total || ev->n_poses_free != h.n_poses_free)
+        throw std::runtime_error("cugo_relpose: the pose or edge counts are not those of the plan");
+    if (!ev->plan->on_device)
+        throw std::runtime_error("cugo_relpose: the plan is host-only (created without a context)");
+    if (ev->n > (1 << 26))
+        throw std::runtime_error("cugo_relpose: more than 2^26 edges (the kernel indexes the planar arrays with 32 bits)");
+    if (ev->rk < CUGO_RK_NONE || ev->rk > CUGO_RK_HUBER ||
+        (ev->rk != CUGO_RK_NONE && !(ev->delta > 0.0 && std::isfinite(ev->delta))))
+        throw std::runtime_error("cugo_relpose: unknown robust kernel or bad delta");
+    if (ev->n > 0 && (!ev->d_meas || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
+        throw std::runtime_error("cugo_relpose: missing arrays");
+    return pose_scratch_for(ctx, (size_t)cugo_k::relpose_workgroups(*ev));
+}
+void relpose_chi_total(cugo_ctx* ctx, const cugo_relpose_edges* ev, const cugo_k::ReduceScratch& rs, double* d_chi)
+{
+    if (!d_chi)
+        return;
+    const int wgs = cugo_k::relpose_workgroups(*ev);
+    if (wgs)
+        cugo_k::launch_pose_chi_total(ctx->stream, "k_relpose_chi_total", rs.d_partials, wgs, d_chi, false);
+    else
+        CUGO_HIP(hipMemsetAsync(d_chi, 0, sizeof(double), ctx->stream));
+}
+} // namespace
+
+extern "C" {
+
+int cugo_relpose_plan_create(cugo_ctx* ctx, int n, int n_poses_total, int n_poses_free, const int32_t* h_pose_a,
+                             const int32_t* h_pose_b, const uint8_t* h_flags, const int32_t* h_rowptr,
+                             const int32_t* h_colind, cugo_relpose_plan** out)
+{
+    return guarded([&] {
+        if (!out)
+            throw std::runtime_error("cugo_relpose_plan_create: null argument");
+        *out = nullptr;
+        if (n > (1 << 26))
+            throw std::runtime_error("cugo_relpose_plan_create: more than 2^26 edges");
+        auto p = std::make_unique<cugo_relpose_plan>();
+        cugo_host::build_relpose_plan(n, n_poses_total, n_poses_free, h_pose_a, h_pose_b, h_flags, h_rowptr, h_colind, p->host);
+        if (ctx)
+        {
+            p->pose_a.upload(h_pose_a, (size_t)n, ctx->stream);
+            p->pose_b.upload(h_pose_b, (size_t)n, ctx->stream);
+            p->inc_ptr.upload(p->host.inc_ptr, ctx->stream);
+            p->inc.upload(p->host.inc, ctx->stream);
+            p->off_blk.upload(p->host.off_blk, ctx->stream);
+            CUGO_HIP(hipStreamSynchronize(ctx->stream)); // (the caller's index arrays are pageable and may go away)
+            p->on_device = true;
+        }
+        *out = p.release();
+    });
+}
+void cugo_relpose_plan_destroy(cugo_relpose_plan* plan) { delete plan; }
+
+int cugo_relpose_plan_array(const cugo_relpose_plan* plan, const char* name, const int32_t** out)
+{
+    if (!plan || !name || !out)
+        return CUGO_ERR_INVALID;
+    const std::string n = name;
+    const std::vector<int32_t>* v = n == "inc_ptr" ? &plan->host.inc_ptr : n == "inc" ? &plan->host.inc
+                                    : n == "off_blk" ? &plan->host.off_blk : nullptr;
+    if (!v)
+    {
+        set_last_error("cugo_relpose_plan_array: unknown array " + n);
+        return CUGO_ERR_INVALID;
+    }
+    *out = v->data();
+    return (int)v->size();
+}
+
+int cugo_relpose_pattern(int n, int n_poses_free, const int32_t* h_pose_a, const int32_t* h_pose_b,
+                         const uint8_t* h_flags, int32_t* rowptr_out, int32_t* colind_out, int* nnzb)
+{
+    return guarded([&] {
+        if (!nnzb)
+            throw std::runtime_error("cugo_relpose_pattern: null argument");
+        *nnzb = cugo_host::relpose_pattern(n, n_poses_free, h_pose_a, h_pose_b, h_flags, rowptr_out, colind_out);
+    });
+}
+
+int cugo_relpose_compute_errors(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses, double* d_chi,
+                                double* d_edge_chi)
+{
+    return guarded([&] {
+        const cugo_k::ReduceScratch rs = check_relpose(ctx, ev);
+        if (d_edge_chi && ev->n > 0) // (the kernel writes the edges that count)
+            CUGO_HIP(hipMemsetAsync(d_edge_chi, 0, sizeof(double) * ev->n, ctx->stream));
+        cugo_k::launch_relpose_errors(ctx->stream, *ev, ev->plan->dev(), d_poses, rs.d_partials, d_edge_chi);
+        relpose_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_relpose_construct_quadratic_form(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses,
+                                          double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::ReduceScratch rs = check_relpose(ctx, ev);
+        if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
+            throw std::runtime_error("cugo_relpose: missing Hpp or bp");
+        if (!d_Hoff)
+            for (int32_t k : ev->plan->host.off_blk)
+                if (k >= 0)
+                    throw std::runtime_error("cugo_relpose: missing Hoff (an edge joins two free poses)");
+        cugo_k::launch_relpose_add(ctx->stream, *ev, ev->plan->dev(), d_poses, d_Hpp, d_bp, d_Hoff, rs.d_partials);
+        relpose_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_relpose_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses,
+                                                const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
+                                                double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::ReduceScratch rs = check_relpose(ctx, ev);
+        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
+            throw std::runtime_error("cugo_relpose: missing rowptr, Hsc, bp or bsc");
+        cugo_k::launch_relpose_add_schur(ctx->stream, *ev, ev->plan->dev(), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, rs.d_partials);
+        relpose_chi_total(ctx, ev, rs, d_chi);
         CUGO_HIP(hipGetLastError());
     });
 }

@@ -4,6 +4,7 @@
 #include "../../include/cuda_graph_optimisation.h"
 #include "../../include/icp_types.h"
 #include "../../include/prior_types.h"
+#include "../../include/relpose_types.h"
 
 #include <algorithm>
 #include <chrono>
@@ -461,6 +462,9 @@ void CudaGraphOptimisationImpl::initialize()
                 [] { return (const char*)nullptr; });
             continue;
         }
+        if (dim == 6 && dynamic_cast<RelPoseEdgeSet*>(es)) // (relpose_types.h, an extension: kernel level only so far)
+            throw std::runtime_error("cugo: the optimiser does not take relative-pose edge sets yet "
+                                     "(their terms: cugo_relpose_* in include/cugo_hip.h)");
         if (dim == 6)
         { // PosePriorEdgeSet (prior_types.h, an extension)
             auto* ps = dynamic_cast<PosePriorEdgeSet*>(es);

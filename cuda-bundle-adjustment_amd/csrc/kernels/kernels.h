@@ -192,6 +192,29 @@ void launch_prior_add(hipStream_t s, const cugo_prior_edges& ev, const double* d
 void launch_prior_add_schur(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, const int32_t* d_rowptr,
                             double* d_Hsc, double* d_bp, double* d_bsc, double* d_wg_chi);
 
+// --- relative-pose SE(3) edges (relpose_kernels.hip) ---------------------------------------
+// the device side of a cugo_relpose_plan (csrc/host/relpose_plan.h): index arrays and incidence lists
+struct RelPosePlanDev
+{
+    int n, n_poses_free;
+    const int32_t *pose_a, *pose_b; // [n]
+    const int32_t *inc_ptr, *inc;   // [n_poses_free + 1], [inc_ptr[n_poses_free]]: edge << 1 | side
+    const int32_t* off_blk;         // [n] block of the (lo, hi) term, -1 without one
+};
+// One kernel per pass: one 64-lane wave per free pose walks its incidence list in edge order and ADDS the pose's
+// diagonal term and b at the end, the off-diagonal term of every edge whose other end is a free pose of larger index
+// edge after edge; every workgroup leaves one chi2 total in d_wg_chi [relpose_workgroups()].
+int relpose_workgroups(const cugo_relpose_edges& ev); // 0 without edges or free poses: nothing is launched
+// chi2 only; d_edge_chi [n] (edge order; only the edges that count are written) or nullptr
+void launch_relpose_errors(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
+                           double* d_wg_chi, double* d_edge_chi = nullptr);
+// the terms ADDED to d_Hpp / d_bp, the off-diagonal blocks to d_Hoff [nnzb][36] by block index ...
+void launch_relpose_add(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
+                        double* d_Hpp, double* d_bp, double* d_Hoff, double* d_wg_chi);
+// ... or to d_Hsc (diagonal through d_rowptr, off-diagonal by block index), d_bp and d_bsc
+void launch_relpose_add_schur(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
+                              const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_wg_chi);
+
 // chi_e per edge slot (outlier rejection, ref: computeOutliersKernel cuda_block_solver.cu:1135)
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                      cugo_robust rk, double* d_chi_e);

@@ -1,0 +1,60 @@
+// EXTENSION (the reference has no such edge; g2o calls it EdgeSE3): relative-pose SE(3) edges of the cugo API — binary
+// edges between two pose vertices a and b with a measured relative pose Z ~ T_a T_b^-1 and a full 6 x 6 information
+// matrix Omega: odometry and IMU-preintegration constraints between keyframes, loop closures, the essential graph.
+// With the poses read as the BA edges read them (y = R(q) p + t) and the left update T <- Exp([omega, upsilon]) T:
+//   A = T_a T_b^-1 = (R_A, t_A),   D = A Z^-1 = (R_D, t_D)
+//   r = [ Log_SO3(R_D) ; t_D ]                     (tangent order [rotation, translation], as for the priors)
+//   J_a = dr/dxi_a = [ J_l^-1(phi) 0 ; -[t_D]x I ] (exactly the prior's Jacobian, prior_types.h, with this D)
+//   J_b = dr/dxi_b = -J_a Ad(A),   Ad(A) = [ R_A 0 ; [t_A]x R_A  R_A ]
+//   x = max(0, r^T Omega r), chi2 term rho(x) with the set's robust kernel, w = rho'(x)
+//   H_aa += w J_a^T Omega J_a,  H_bb += w J_b^T Omega J_b,  H_(lo,hi) += w J_lo^T Omega J_hi  (lo < hi: the pose indices)
+//   b_a -= w J_a^T Omega r,     b_b -= w J_b^T Omega r
+// With T_b the fixed identity this is the pose prior, term for term.  An edge with one fixed end counts in chi2 and adds
+// only its free end's block and b; an edge between two fixed poses counts for nothing; a == b is refused.
+// The residual, the Jacobians and the device kernel are in csrc/kernels/relpose_kernels.hip.  The set is a plain
+// container like the others, vertex 0 = a, vertex 1 = b.  The terms are reachable through the kernel-level C ABI
+// (include/cugo_hip.h: cugo_relpose_edges, cugo_relpose_plan_create, cugo_relpose_compute_errors,
+// cugo_relpose_construct_quadratic_form[_schur]); the optimiser does not take the set yet: initialize() recognises it
+// by type and refuses it, naming those entry points.
+#pragma once
+#include <algorithm>
+
+#include "prior_types.h"
+
+namespace cugo
+{
+
+/** measurement: PosePriorMatch (the measured relative pose Z and its 6 x 6 information); vertex 0 is a, vertex 1 is b */
+class CUGO_API RelPoseEdge : public Edge<6, PosePriorMatch<double>, PoseVertex, PoseVertex>
+{
+public:
+    void* getMeasurement() noexcept override
+    {
+        touchOwner(); // mutable pointer: counts as a change (optimisable_graph.h, change tracking)
+        return static_cast<void*>(&measurement);
+    }
+    const void* measurementData() const noexcept override { return static_cast<const void*>(&measurement); }
+};
+
+/** with GraphOptimisationOptions::perEdgeInformation the edges' own matrices count, otherwise the set's (the identity
+ *  until setInformationMatrix is called); the scalar setInformation() of the base class is not used by this set */
+class CUGO_API RelPoseEdgeSet : public EdgeSet<6, PosePriorMatch<double>, PoseVertex, PoseVertex>
+{
+public:
+    RelPoseEdgeSet()
+    {
+        for (int i = 0; i < 36; i++)
+            info36_[i] = i % 7 == 0 ? 1.0 : 0.0;
+    }
+    void setInformationMatrix(const double* info36) noexcept
+    {
+        touch();
+        std::copy(info36, info36 + 36, info36_);
+    }
+    const double* informationMatrix() const noexcept { return info36_; }
+
+private:
+    double info36_[36];
+};
+
+} // namespace cugo

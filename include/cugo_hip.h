@@ -354,6 +354,78 @@ int cugo_prior_construct_quadratic_form(cugo_ctx* ctx, const cugo_prior_edges* e
 int cugo_prior_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_prior_edges* ev, const double* d_poses,
                                               const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi);
 
+/*
+ * Extension (the reference has no such edge): relative-pose SE(3) edges, binary edges between poses a and b with a
+ * measurement Z = (q_z, t_z) ~ T_a T_b^-1 and a full 6 x 6 information matrix Omega (relpose_types.h).  Conventions as
+ * for cugo_prior_edges:
+ *   A = T_a T_b^-1 = (R_A, t_A),  D = A Z^-1,  r = [ Log_SO3(R_D) ; t_D ]
+ *   J_a = [ J_l^-1(phi) 0 ; -[t_D]x I ] (the prior's J with this D),  J_b = -J_a Ad(A),  Ad(A) = [ R_A 0 ; [t_A]x R_A  R_A ]
+ *   chi2 term rho(max(0, r^T Omega r)), w = rho';  H_aa += w J_a^T Omega J_a, H_bb += w J_b^T Omega J_b,
+ *   H_(lo,hi) += w J_lo^T Omega J_hi (lo < hi the two pose indices),  b_a -= w J_a^T Omega r,  b_b -= w J_b^T Omega r
+ * An edge with one fixed end (index >= n_poses_free) counts in chi2 and adds only its free end's block and b; an edge
+ * between two fixed poses, or flagged CUGO_EDGE_INACTIVE, counts for nothing.  The edges stay in the caller's order:
+ * the library's own plan (below) holds what every free pose walks and where the off-diagonal block of an edge goes.
+ *
+ * The plan.  h_* are HOST arrays: the two pose indices and the flags of every edge (h_flags may be NULL: all active),
+ * and an upper block-CSR pattern over the free poses, the diagonal block first in every row and the columns of a row
+ * ascending — the layout cugo_chol_analyze takes and cugo_hsc_struct describes.  Refused with CUGO_ERR_INVALID: an
+ * index outside [0, n_poses_total), a == b, a pattern of another form, and a counting edge between two free poses
+ * whose (lo, hi) block the pattern lacks.  The plan holds, per free pose, its counting edges with the side each is seen
+ * from, in edge order, and, per edge, the block index of its off-diagonal destination or -1, and uploads both with the
+ * index arrays.  ctx == NULL gives a host-only plan (cugo_relpose_plan_array reads it; the kernels refuse it).
+ */
+typedef struct cugo_relpose_plan cugo_relpose_plan;
+int cugo_relpose_plan_create(cugo_ctx* ctx, int n, int n_poses_total, int n_poses_free, const int32_t* h_pose_a,
+                             const int32_t* h_pose_b, const uint8_t* h_flags, const int32_t* h_rowptr,
+                             const int32_t* h_colind, cugo_relpose_plan** out);
+void cugo_relpose_plan_destroy(cugo_relpose_plan* plan);
+/* named int32 plan array: "inc_ptr" [n_poses_free + 1], "inc" [inc_ptr[n_poses_free]] (edge << 1 | side; side 0: the
+ * pose is the edge's a, 1: its b), "off_blk" [n].  The pointer is valid until the plan is destroyed.  Returns the
+ * length or a negative error. */
+int cugo_relpose_plan_array(const cugo_relpose_plan* plan, const char* name, const int32_t** out);
+/* The upper block-CSR pattern of a pure pose graph (host arrays): row p holds p, then every hi > p that a counting
+ * edge between two free poses joins to p.  rowptr_out [n_poses_free + 1] and colind_out may each be NULL; *nnzb
+ * receives the block count either way (call once for the size, once more with colind_out [*nnzb]).  Indices >=
+ * n_poses_free are fixed poses.  CUGO_ERR_INVALID on a negative index or a == b. */
+int cugo_relpose_pattern(int n, int n_poses_free, const int32_t* h_pose_a, const int32_t* h_pose_b,
+                         const uint8_t* h_flags, int32_t* rowptr_out, int32_t* colind_out, int* nnzb);
+
+typedef struct cugo_relpose_edges
+{
+    int n_poses_total, n_poses_free; /* those of the plan */
+    int n;                           /* that of the plan */
+    const double* d_meas;            /* [7][n] qx qy qz qw tx ty tz of Z */
+    const double* d_info;            /* [21][n] or [21][1]: upper triangle of Omega, row-major packed */
+    int n_info;                      /* n or 1 */
+    const uint8_t* d_flags;          /* [n] CUGO_EDGE_INACTIVE, or NULL.  The plan lists the edges that counted under
+                                        ITS flags: an edge it left out stays out; one flagged here in addition counts
+                                        for nothing */
+    int rk;                          /* CUGO_RK_* */
+    double delta;
+    const cugo_relpose_plan* plan;   /* with a device context */
+} cugo_relpose_edges;
+
+/* Writes the chi2 total to d_chi[0] (every counting edge once); with d_edge_chi (optional, [n], edge order) also the
+ * chi2 term of every edge (0 for edges that do not count).  The layout is the plan's, so no index check runs on the
+ * device; the counts, the arrays and the robust-kernel code are checked (CUGO_ERR_INVALID).  One launch plus the chi2
+ * total.  Deterministic: no atomics, one summation order. */
+int cugo_relpose_compute_errors(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses, double* d_chi,
+                                double* d_edge_chi);
+/* ADDS the diagonal terms to d_Hpp [n_poses_free][36] and b to d_bp [n_poses_free][6] (layout and sign of
+ * cugo_prior_construct_quadratic_form), and the off-diagonal terms to d_Hoff [nnzb][36]: block k of the plan's pattern,
+ * 6 x 6 column-major, holds H_(lo,hi) (rows: pose lo); the diagonal blocks of d_Hoff are not touched.  Edges on the
+ * same pair, in either orientation, are summed into one block.  A free pose without a counting edge and a block no
+ * counting edge maps to keep their bits.  chi2 total to d_chi[0] if d_chi != NULL (the bits of
+ * cugo_relpose_compute_errors).  d_Hoff may be NULL when no edge joins two free poses. */
+int cugo_relpose_construct_quadratic_form(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses,
+                                          double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi);
+/* The same terms into the Schur destination: the diagonal term of pose p into block d_rowptr[p] of d_Hsc (see
+ * cugo_icp_construct_quadratic_form_schur), the off-diagonal terms into d_Hsc by the plan's block indices, b into d_bp
+ * and d_bsc alike.  d_Hsc must be laid out by the pattern the plan was built against. */
+int cugo_relpose_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses,
+                                                const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
+                                                double* d_chi);
+
 /* ---- (2) graph-level entry points ---------------------------------------------------- */
 
 typedef struct cugo_graph cugo_graph; /* CudaGraphOptimisationImpl + its vertex/edge sets */
