@@ -197,6 +197,16 @@ def relpose_construct_quadratic_form(ctx, ev, d_poses, d_Hpp, d_bp, d_Hoff, d_ch
     check(lib().cugo_relpose_construct_quadratic_form(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_Hoff, d_chi))
 
 
+def relpose_construct_quadratic_form_diag(ctx, ev, d_poses, d_Hpp, d_bp, d_chi=None):
+    """cugo_relpose_construct_quadratic_form_diag: the build pass of the two-stream loop (diagonal terms and b alone)"""
+    check(lib().cugo_relpose_construct_quadratic_form_diag(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_chi))
+
+
+def relpose_add_offdiag_schur(ctx, ev, d_poses, d_Hsc):
+    """cugo_relpose_add_offdiag_schur: the off-diagonal terms alone ADDED to d_Hsc by the plan's block indices"""
+    check(lib().cugo_relpose_add_offdiag_schur(ctx, C.byref(ev), d_poses, d_Hsc))
+
+
 def relpose_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
     """cugo_relpose_construct_quadratic_form_schur: as prior_construct_quadratic_form_schur, plus the off-diagonal
     blocks into d_Hsc by the plan's block indices"""
@@ -433,6 +443,43 @@ class Graph:
     def n_prior_edges(self):
         """active priors in the current flattening (priors on fixed poses are not counted)"""
         return lib().cugo_graph_n_prior_edges(self._g)
+
+    def add_relpose_edges(self, pose_ids_a, pose_ids_b, q_t7, info36=None):
+        """relative-pose SE(3) edges (an extension; RelPoseEdgeSet): residual [Log_SO3(R_D); t_D] of D = T_a T_b^-1 Z^-1
+        against the measured relative pose q_t7 [n, 7], cost r^T Omega r.  info36 as for add_pose_priors; None for the
+        set's matrix (set_relpose_information).  The pose pairs become blocks of the Schur complement's pattern"""
+        n = len(pose_ids_a)
+        if n == 0:
+            return
+        if len(pose_ids_b) != n:
+            raise ValueError("add_relpose_edges: pose_ids_a and pose_ids_b differ in length")
+        pa, pb = _i32(pose_ids_a), _i32(pose_ids_b)
+        z = np.ascontiguousarray(np.asarray(q_t7, np.float64).reshape(n, 7))
+        w = None if info36 is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(info36, np.float64).reshape(-1, 36), (n, 36)))
+        check(lib().cugo_graph_add_relpose_edges(self._g, n, _p(pa, _i32p), _p(pb, _i32p), _p(z, _f64p),
+                                                 None if w is None else _p(w, _f64p)))
+
+    def set_relpose_information(self, info36):
+        """the relative-pose set's 6 x 6 information (used when per_edge_information is off, or for edges added without one)"""
+        w = np.ascontiguousarray(np.asarray(info36, np.float64).reshape(36))
+        check(lib().cugo_graph_set_relpose_information(self._g, _p(w, _f64p)))
+
+    def set_relpose_robust_kernel(self, rk_type, delta):
+        check(lib().cugo_graph_set_relpose_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
+
+    def set_relpose_outlier_threshold(self, threshold):
+        """only 0 is usable: initialize() refuses a positive threshold on the relative-pose set (not built yet)"""
+        check(lib().cugo_graph_set_relpose_outlier_threshold(self._g, C.c_double(threshold)))
+
+    def set_relpose_active(self, active, first=0):
+        """active flags of the relative-pose edges first, first + 1, ... (insertion order); takes effect at the next initialize()"""
+        a = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
+        check(lib().cugo_graph_set_relpose_active(self._g, int(first), len(a), _p(a, _u8p)))
+
+    def n_relpose_edges(self):
+        """relative-pose edges that count in the current flattening (edges between two fixed poses do not)"""
+        return lib().cugo_graph_n_relpose_edges(self._g)
 
     def set_outlier_threshold(self, dim, threshold):
         """edges of the set (dim 2 mono / 3 stereo) with chi2 > threshold are inactivated at the

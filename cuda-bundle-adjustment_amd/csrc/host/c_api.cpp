@@ -9,6 +9,7 @@
 #include "../../include/cuda_graph_optimisation.h"
 #include "../../include/icp_types.h"
 #include "../../include/prior_types.h"
+#include "../../include/relpose_types.h"
 #include "../kernels/kernels.h"
 #include "chol_solver.h"
 #include "edge_layout.h"
@@ -468,6 +469,30 @@ int cugo_relpose_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_relpos
     });
 }
 
+int cugo_relpose_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses,
+                                               double* d_Hpp, double* d_bp, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::ReduceScratch rs = check_relpose(ctx, ev);
+        if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
+            throw std::runtime_error("cugo_relpose: missing Hpp or bp");
+        cugo_k::launch_relpose_add(ctx->stream, *ev, ev->plan->dev(), d_poses, d_Hpp, d_bp, nullptr, rs.d_partials);
+        relpose_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_relpose_add_offdiag_schur(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses, double* d_Hsc)
+{
+    return guarded([&] {
+        (void)check_relpose(ctx, ev);
+        if (!d_Hsc)
+            throw std::runtime_error("cugo_relpose: missing Hsc");
+        cugo_k::launch_relpose_add_offdiag(ctx->stream, *ev, ev->plan->dev(), d_poses, d_Hsc);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
 int cugo_max_diagonal(cugo_ctx* ctx, const double* d_Hpp, int nP, const double* d_Hll, int nL,
                       double* d_out)
 {
@@ -719,6 +744,8 @@ struct cugo_graph
     cugo::LineEdgeSet line;
     cugo::PosePriorEdgeSet prior;
     std::deque<cugo::PosePriorEdge> prior_store;
+    cugo::RelPoseEdgeSet relpose;
+    std::deque<cugo::RelPoseEdge> relpose_store;
     std::deque<cugo::PlaneEdge> plane_store;
     std::deque<cugo::LineEdge> line_store;
     std::deque<cugo::PoseVertex> pose_store;
@@ -737,6 +764,7 @@ struct cugo_graph
         opt->addEdgeSet(&plane);
         opt->addEdgeSet(&line);
         opt->addEdgeSet(&prior);
+        opt->addEdgeSet(&relpose);
         attached = true;
     }
 };
@@ -747,6 +775,7 @@ int cugo_graph_create(int per_edge_information, int per_edge_camera, cugo_graph*
         auto g = std::make_unique<cugo_graph>();
         g->options.perEdgeInformation = per_edge_information != 0;
         g->options.perEdgeCamera = per_edge_camera != 0;
+        g->options.relativePoseEdges = true; // (only cugo_graph_add_relpose_edges fills the set)
         g->opt = std::make_unique<cugo::CudaGraphOptimisationImpl>(g->options);
         *out = g.release();
     });
@@ -784,6 +813,7 @@ int cugo_graph_create_plan_only(int per_edge_information, int per_edge_camera, c
         g->options.perEdgeInformation = per_edge_information != 0;
         g->options.perEdgeCamera = per_edge_camera != 0;
         g->options.planOnly = true;
+        g->options.relativePoseEdges = true; // (only cugo_graph_add_relpose_edges fills the set)
         g->opt = std::make_unique<cugo::CudaGraphOptimisationImpl>(g->options);
         *out = g.release();
     });
@@ -981,6 +1011,58 @@ int cugo_graph_set_prior_outlier_threshold(cugo_graph* g, double threshold)
     return guarded([&] { g->prior.setOutlierThreshold(threshold); });
 }
 int cugo_graph_n_prior_edges(cugo_graph* g) { return g->opt->nPriorEdges(); }
+int cugo_graph_add_relpose_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b,
+                                 const double* q_t7, const double* info36)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids_a || !pose_ids_b || !q_t7)))
+            throw std::invalid_argument("cugo_graph_add_relpose_edges: missing arrays");
+        for (int i = 0; i < n; i++) // (all or nothing: an unknown id adds no edge)
+            (void)icp_pose(g, pose_ids_a[i]), (void)icp_pose(g, pose_ids_b[i]);
+        for (int i = 0; i < n; i++)
+        {
+            g->relpose_store.emplace_back();
+            cugo::RelPoseEdge& e = g->relpose_store.back();
+            e.setVertex(icp_pose(g, pose_ids_a[i]), 0);
+            e.setVertex(icp_pose(g, pose_ids_b[i]), 1);
+            const cugo::Se3D z(q_t7 + 7 * (size_t)i, q_t7 + 7 * (size_t)i + 4);
+            e.setMeasurement(cugo::PosePriorMatch<double>(z, info36 ? info36 + 36 * (size_t)i : g->relpose.informationMatrix()));
+            g->relpose.addEdge(&e);
+        }
+    });
+}
+int cugo_graph_set_relpose_information(cugo_graph* g, const double* info36)
+{
+    return guarded([&] {
+        if (!info36)
+            throw std::invalid_argument("cugo_graph_set_relpose_information: no matrix");
+        g->relpose.setInformationMatrix(info36);
+    });
+}
+int cugo_graph_set_relpose_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    return guarded([&] {
+        const cugo::RobustKernelType t = type == CUGO_RK_CAUCHY  ? cugo::RobustKernelType::Cauchy
+                                         : type == CUGO_RK_TUKEY ? cugo::RobustKernelType::Tukey
+                                         : type == CUGO_RK_HUBER ? cugo::RobustKernelType::Huber
+                                                                 : cugo::RobustKernelType::None;
+        g->relpose.setRobustKernel(t, delta);
+    });
+}
+int cugo_graph_set_relpose_outlier_threshold(cugo_graph* g, double threshold)
+{
+    return guarded([&] { g->relpose.setOutlierThreshold(threshold); });
+}
+int cugo_graph_set_relpose_active(cugo_graph* g, int first, int n, const uint8_t* active)
+{
+    return guarded([&] {
+        if (first < 0 || n < 0 || (size_t)first + (size_t)n > g->relpose_store.size() || (n > 0 && !active))
+            throw std::invalid_argument("cugo_graph_set_relpose_active: bad edge range or no flags");
+        for (int i = 0; i < n; i++)
+            active[i] ? g->relpose_store[(size_t)first + i].setActive() : g->relpose_store[(size_t)first + i].inactivate();
+    });
+}
+int cugo_graph_n_relpose_edges(cugo_graph* g) { return g->opt->nRelPoseEdges(); }
 int cugo_graph_set_camera(cugo_graph* g, int dim, const double* c)
 {
     const cugo::Camera cam(c[0], c[1], c[2], c[3], c[4]);

@@ -414,7 +414,8 @@ void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHo
 // reference's dense P x P byte map, ref: sparse_block_matrix.cpp:80-155), then the off-diagonal product lists
 void host_structure(int P, int L, const Idx& cov_ptr, const Idx& cov_pose, const SlotArrays& slots, const Idx& lm_ptr,
                     const Idx& pose_ptr, const Idx& pose_edge, const std::function<bool()>& use_plan,
-                    const std::function<void(const char*)>& lap, Idx& rowptr, Idx& colind, HostStructure& out)
+                    const std::function<void(const char*)>& lap, Idx& rowptr, Idx& colind, HostStructure& out,
+                    const Idx* pair_lo, const Idx* pair_hi)
 {
     Idx pc_ptr(P + 1, 0), pc_lm(cov_pose.size());
     for (int32_t p : cov_pose)
@@ -459,6 +460,17 @@ void host_structure(int P, int L, const Idx& cov_ptr, const Idx& cov_pose, const
                     if (q >= p)
                         products += 1;
                     if (q > p && mark[q] != p)
+                    {
+                        mark[q] = p;
+                        cols.push_back(q);
+                    }
+                }
+            if (pair_lo && !pair_lo->empty()) // the pose pairs of row p (no products)
+                for (size_t i = std::lower_bound(pair_lo->begin(), pair_lo->end(), p) - pair_lo->begin();
+                     i < pair_lo->size() && (*pair_lo)[i] == p; i++)
+                {
+                    const int q = (*pair_hi)[i];
+                    if (mark[q] != p)
                     {
                         mark[q] = p;
                         cols.push_back(q);

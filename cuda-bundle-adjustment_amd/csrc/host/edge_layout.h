@@ -72,6 +72,9 @@ void sort_pose_edges_by_pose(const FlatPoseKind& kind, int Pall, int P, PoseKind
 // ---- the Hsc structure on the host: pattern (upper block CSR, diagonal first) and, from the LOCAL slots, the
 // contributions of the off-diagonal blocks (ascending landmark inside a block).  use_plan() is asked once the pattern
 // exists: true = a landmark-major plan (schur_plan.h) serves and the lists stay empty.  lap(label) after every pass.
+// pair_lo / pair_hi (optional, ascending by (lo, hi), lo < hi < P): pose pairs joined by relative-pose edges; each gets a
+// block of the pattern, with an empty contribution range unless the two poses share a landmark.  The products and the
+// lists come from the slots alone.
 struct HostStructure
 {
     double products = 0;         // all products of the graph (a free-free edge also has its diagonal one)
@@ -79,6 +82,7 @@ struct HostStructure
 };
 void host_structure(int P, int L, const Idx& cov_ptr, const Idx& cov_pose, const SlotArrays& slots, const Idx& lm_ptr,
                     const Idx& pose_ptr, const Idx& pose_edge, const std::function<bool()>& use_plan,
-                    const std::function<void(const char*)>& lap, Idx& rowptr, Idx& colind, HostStructure& out);
+                    const std::function<void(const char*)>& lap, Idx& rowptr, Idx& colind, HostStructure& out,
+                    const Idx* pair_lo = nullptr, const Idx* pair_hi = nullptr);
 
 } // namespace cugo_host

@@ -19,6 +19,7 @@
 #include "hip_util.h"
 #include "options.h"
 #include "rccl_comm.h"
+#include "relpose_plan.h"
 #include "schur_plan.h"
 #include "structure_gpu.h"
 #include "thread_pool.h"
@@ -96,6 +97,33 @@ struct Engine::Impl : cugo_k::LaunchHook
     int Etot = 0;
     // global co-visibility: free landmark -> sorted free poses (free-free active edges, all shards)
     std::vector<int32_t> cov_ptr, cov_pose;
+    // The distinct (lo, hi) pairs of free poses that a counting relative-pose edge joins, ascending: each is a block of the
+    // Hsc pattern whether or not the two poses share a landmark.  For the pattern alone a pair is a landmark seen by
+    // exactly two poses: aug_* are the co-visibility lists with one such entry appended per pair (empty without pairs).
+    // They feed the pattern builders only; products, contribution lists and sharding come from the real lists.
+    std::vector<int32_t> pair_lo, pair_hi, aug_ptr, aug_pose;
+    const std::vector<int32_t>& pat_ptr() const { return pair_lo.empty() ? cov_ptr : aug_ptr; }
+    const std::vector<int32_t>& pat_pose() const { return pair_lo.empty() ? cov_pose : aug_pose; }
+    int pat_lists() const { return L + (int)pair_lo.size(); }
+    void build_pair_lists(const FlatRelPose& fr)
+    {
+        std::vector<std::pair<int32_t, int32_t>> pr;
+        for (int e = 0; e < fr.n(); e++)
+            if (fr.pose_a[e] < P && fr.pose_b[e] < P)
+                pr.emplace_back(std::min(fr.pose_a[e], fr.pose_b[e]), std::max(fr.pose_a[e], fr.pose_b[e]));
+        std::sort(pr.begin(), pr.end());
+        pr.erase(std::unique(pr.begin(), pr.end()), pr.end());
+        pair_lo.clear(), pair_hi.clear(), aug_ptr.clear(), aug_pose.clear();
+        if (pr.empty())
+            return;
+        aug_ptr = cov_ptr, aug_pose = cov_pose;
+        for (const auto& q : pr)
+        {
+            pair_lo.push_back(q.first), pair_hi.push_back(q.second);
+            aug_pose.push_back(q.first), aug_pose.push_back(q.second);
+            aug_ptr.push_back((int32_t)aug_pose.size());
+        }
+    }
     // Hsc pattern (host)
     std::vector<int32_t> hsc_rowptr, hsc_colind;
 
@@ -134,6 +162,9 @@ struct Engine::Impl : cugo_k::LaunchHook
     // holds live scale / chi2 partials and records across the same span of the stream):
     //     [ICP partials | ICP chunk chi2 totals | prior workgroup chi2 totals | 16 doubles of slack]
     // The two runs of totals are adjacent, so that the launch ending a trial sums them as one array (chi_totals).
+    // The relative-pose edges (FlatGraph::relpose, relpose_kernels.hip) live here too: binary, in container order, with
+    // a plan (relpose_plan.h) against the Hsc pattern in place of a sort; their workgroup totals are a third run behind
+    // the priors'.  Every launch of theirs sits under n_relpose_wg: a graph without such edges queues what it always did.
     struct PoseEdges
     {
         struct KindBufs : PoseKindHost
@@ -146,7 +177,20 @@ struct Engine::Impl : cugo_k::LaunchHook
         int n_icp = 0, n_prior = 0;
         int n_icp_chi = 0, n_prior_wg = 0; // totals an ICP pass / a prior pass leaves (0: the pass is not launched)
         DevBuf<double> d_scratch;
-        size_t off_icp_chi = 0, off_prior_chi = 0; // the layout above, set by bind()
+        size_t off_icp_chi = 0, off_prior_chi = 0, off_relpose_chi = 0; // the layout above, set by bind()
+        struct RelPose
+        {
+            std::vector<int32_t> h_pose_a, h_pose_b;
+            std::vector<double> h_meas, h_info; // planar [7][n], [21][n_info]
+            DevBuf<int32_t> d_pose_a, d_pose_b, d_inc_ptr, d_inc, d_off_blk;
+            DevBuf<double> d_meas, d_info;
+            RelPosePlanHost plan;
+            bool plan_dirty = true; // the plan is not that of the edges and the Hsc pattern at hand
+            cugo_k::RelPosePlanDev dev{};
+        } rp;
+        cugo_relpose_edges relpose{};
+        int n_relpose = 0, n_relpose_wg = 0; // edges; totals a relative-pose pass leaves (0: never launched)
+        double* relpose_chi() { return d_scratch.data() + off_relpose_chi; }
 
         cugo_k::ReduceScratch icp_rs() { return {d_scratch.data(), d_scratch.size()}; }
         double* prior_chi() { return d_scratch.data() + off_prior_chi; }
@@ -155,7 +199,7 @@ struct Engine::Impl : cugo_k::LaunchHook
         // the chi2 totals of the last ICP pass and of the last prior pass, one array; nullptr / 0 without such edges
         const double* chi_totals(int* n)
         {
-            *n = n_icp_chi + n_prior_wg;
+            *n = n_icp_chi + n_prior_wg + n_relpose_wg;
             return *n ? d_scratch.data() + off_icp_chi : nullptr;
         }
 
@@ -198,8 +242,60 @@ struct Engine::Impl : cugo_k::LaunchHook
             n_icp_chi = n_icp ? cugo_k::icp_chunk_count(icp) : 0;
             n_prior_wg = cugo_k::prior_workgroups(prior);
             off_icp_chi = icp_doubles - n_icp_chi, off_prior_chi = icp_doubles;
-            if ((n_icp || n_prior_wg) && !plan_only)
-                d_scratch.resize(icp_doubles + (size_t)n_prior_wg + 16);
+            bind_relpose(g.relpose, Pall, P, stream, plan_only);
+            off_relpose_chi = off_prior_chi + (size_t)n_prior_wg;
+            if ((n_icp || n_prior_wg || n_relpose_wg) && !plan_only)
+                d_scratch.resize(icp_doubles + (size_t)n_prior_wg + (size_t)n_relpose_wg + 16);
+        }
+        // the relative-pose edges: planar copies, upload, the view the kernels take.  The plan waits for the Hsc pattern
+        // (bind_relpose_plan)
+        void bind_relpose(const FlatRelPose& fr, int Pall, int P, hipStream_t stream, bool plan_only)
+        {
+            const int n = n_relpose = fr.n();
+            rp.plan_dirty = true;
+            relpose = cugo_relpose_edges{};
+            relpose.n_poses_total = Pall, relpose.n_poses_free = P, relpose.n = n;
+            relpose.rk = fr.rk, relpose.delta = fr.delta;
+            n_relpose_wg = cugo_k::relpose_workgroups(relpose);
+            if (!n)
+                return;
+            if (n > (1 << 26))
+                throw std::runtime_error("cugo: more than 2^26 relative-pose edges");
+            rp.h_pose_a = fr.pose_a, rp.h_pose_b = fr.pose_b;
+            const int n_info = fr.weight.size() > 21 ? n : 1;
+            rp.h_meas.resize(7 * (size_t)n), rp.h_info.resize(21 * (size_t)n_info);
+            for (int e = 0; e < n; e++)
+                for (int c = 0; c < 7; c++)
+                    rp.h_meas[(size_t)c * n + e] = fr.meas[7 * (size_t)e + c];
+            for (int e = 0; e < n_info; e++)
+                for (int c = 0; c < 21; c++)
+                    rp.h_info[(size_t)c * n_info + e] = fr.weight[21 * (size_t)e + c];
+            relpose.n_info = n_info;
+            if (plan_only)
+                return;
+            rp.d_pose_a.upload(rp.h_pose_a, stream), rp.d_pose_b.upload(rp.h_pose_b, stream);
+            rp.d_meas.upload(rp.h_meas, stream), rp.d_info.upload(rp.h_info, stream);
+            relpose.d_meas = rp.d_meas.data(), relpose.d_info = rp.d_info.data();
+        }
+        // the plan against the Hsc pattern at hand (upper block CSR over the free poses): the engine made the pattern
+        // from these very pairs, so a pair missing from it is a defect of the engine and throws
+        void bind_relpose_plan(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colind, hipStream_t stream,
+                               bool plan_only)
+        {
+            if (!rp.plan_dirty)
+                return;
+            rp.plan_dirty = false;
+            if (!n_relpose)
+                return;
+            build_relpose_plan(n_relpose, relpose.n_poses_total, relpose.n_poses_free, rp.h_pose_a.data(), rp.h_pose_b.data(),
+                               nullptr, rowptr.data(), colind.data(), rp.plan);
+            if (plan_only)
+                return;
+            rp.d_inc_ptr.upload(rp.plan.inc_ptr, stream), rp.d_inc.upload(rp.plan.inc, stream);
+            rp.d_off_blk.upload(rp.plan.off_blk, stream);
+            CUGO_HIP(hipStreamSynchronize(stream));
+            rp.dev = cugo_k::RelPosePlanDev{n_relpose, relpose.n_poses_free, rp.d_pose_a.data(), rp.d_pose_b.data(),
+                                            rp.d_inc_ptr.data(), rp.d_inc.data(), rp.d_off_blk.data()};
         }
         // The pose edge terms of a build pass at `poses`.  Two-stream form: the ICP chunk pass and its add, then the
         // priors' ONE launch (terms and workgroup totals), both behind k_build_poses.  One-stream form (Hpp is not
@@ -226,6 +322,22 @@ struct Engine::Impl : cugo_k::LaunchHook
                 if (d_chi)
                     cugo_k::launch_pose_chi_total(s, "k_prior_chi_total", prior_chi(), n_prior_wg, d_chi, true);
             }
+            if (n_relpose_wg)
+            { // as the priors: ONE launch; the off-diagonal terms wait for the Schur pass (queue_offdiag_schur)
+                if (!one_stream)
+                    cugo_k::launch_relpose_add(s, relpose, rp.dev, poses, Hpp, bp, nullptr, relpose_chi());
+                else if (want_totals)
+                    cugo_k::launch_relpose_errors(s, relpose, rp.dev, poses, relpose_chi());
+                if (d_chi)
+                    cugo_k::launch_pose_chi_total(s, "k_relpose_chi_total", relpose_chi(), n_relpose_wg, d_chi, true);
+            }
+        }
+        // two-stream form: the off-diagonal terms of the relative-pose edges ADDED to their blocks of Hsc behind a Schur
+        // pass (which wrote every block), at the poses the build pass at hand linearised at
+        void queue_offdiag_schur(hipStream_t s, const double* poses, double* Hsc)
+        {
+            if (n_relpose_wg)
+                cugo_k::launch_relpose_add_offdiag(s, relpose, rp.dev, poses, Hsc);
         }
         // one-stream form: the terms added to the diagonal blocks of Hsc, to bp and to bsc behind k_pose_schur (the
         // totals the prior launch leaves are those of the estimates at `poses` once more)
@@ -235,6 +347,8 @@ struct Engine::Impl : cugo_k::LaunchHook
                 cugo_k::launch_icp_add_schur(s, icp, icp_rs(), rowptr, Hsc, bp, bsc);
             if (n_prior_wg)
                 cugo_k::launch_prior_add_schur(s, prior, poses, rowptr, Hsc, bp, bsc, prior_chi());
+            if (n_relpose_wg)
+                cugo_k::launch_relpose_add_schur(s, relpose, rp.dev, poses, rowptr, Hsc, bp, bsc, relpose_chi());
         }
         // error pass: chi_totals() at `poses`
         void queue_errors(hipStream_t s, const double* poses)
@@ -243,6 +357,8 @@ struct Engine::Impl : cugo_k::LaunchHook
                 cugo_k::launch_icp_chunks(s, icp, poses, false, icp_rs());
             if (n_prior_wg)
                 cugo_k::launch_prior_errors(s, prior, poses, prior_chi());
+            if (n_relpose_wg)
+                cugo_k::launch_relpose_errors(s, relpose, rp.dev, poses, relpose_chi());
         }
     } pe;
     cugo_hsc_struct hs{};
@@ -253,7 +369,7 @@ struct Engine::Impl : cugo_k::LaunchHook
     bool sig_valid = false; // sig_* hold the topology the structure at hand was built from
     // ... and the topology itself (compared on a hash hit), saved by build_structure()
     int sig_dims[8] = {0}, pending_dims[8] = {0};
-    std::vector<int32_t> sig_e_pose, sig_e_lm, sig_cov_pose;
+    std::vector<int32_t> sig_e_pose, sig_e_lm, sig_cov_pose, sig_pair_lo, sig_pair_hi;
     // The Hsc pattern, the ordering and the symbolic factor depend on the co-visibility lists alone.  When
     // those change, initialize() starts their build on a helper thread and a second stream the moment the
     // lists exist — the slot layout, the slot arrays, their upload and the topology hash then run beside
@@ -600,6 +716,8 @@ struct Engine::Impl : cugo_k::LaunchHook
                                                                 d_poses[buf].data(), rs(), bp()});
             if (one_stream)
                 pe.queue_add_schur(ctx.stream, d_poses[buf].data(), hs.d_rowptr, Hsc(), bp(), bsc());
+            else
+                pe.queue_offdiag_schur(ctx.stream, d_poses[buf].data(), Hsc());
         });
     }
     // diagnosis: CUGO_DEBUG_HASH=<file> — position-weighted integer checksums of the arrays every stage of the
@@ -840,8 +958,9 @@ bool Engine::Impl::start_pattern_helper(double* prof)
         pat_err = nullptr; // a failed helper of an earlier call: that structure was never used
         pattern_dirty = true;
     }
-    const bool pat_same = !pattern_dirty && opt.structure_reuse && P == pat_P && L == pat_L &&
-                          same_bytes(cov_ptr, pat_cov_ptr) && same_bytes(cov_pose, pat_cov_pose);
+    // (the lists the pattern is made from: with relative-pose pairs the augmented ones)
+    const bool pat_same = !pattern_dirty && opt.structure_reuse && P == pat_P && pat_lists() == pat_L &&
+                          same_bytes(pat_ptr(), pat_cov_ptr) && same_bytes(pat_pose(), pat_cov_pose);
     pat_async_ok = false;
     lists_built = false;
     pat_stage.store(0, std::memory_order_relaxed);
@@ -850,6 +969,7 @@ bool Engine::Impl::start_pattern_helper(double* prof)
     pattern_dirty = true;
     plan_uploaded = false;
     const bool device_build = !plan_only && !opt.schur_plan && !opt.host_structure;
+    // (a pure pose graph, no BA edge, takes the host build: build_structure)
     if (!(device_build && opt.async_structure && P > 0 && !cov_pose.empty()))
         return false;
     if (!s2)
@@ -860,7 +980,7 @@ bool Engine::Impl::start_pattern_helper(double* prof)
             // (the current device is per thread: a rank of a multi-GPU job runs on LOCAL_RANK, not 0)
             CUGO_HIP(hipSetDevice(ctx.device));
             const auto t0p = Clock::now();
-            if (!build_pattern_gpu(s2, P, L, cov_ptr.data(), cov_pose.data(), gstruct))
+            if (!build_pattern_gpu(s2, P, pat_lists(), pat_ptr().data(), pat_pose().data(), gstruct))
             {
                 pat_stage.store(-1, std::memory_order_release);
                 return;
@@ -965,7 +1085,14 @@ void Engine::initialize(FlatGraph& g)
     m.rk = g.rk;
     m.init_rank = m.rank, m.init_world = m.world;
     m.Etot = g.n_edges();
-    E_global_ = m.Etot + g.n_pose_edges();
+    E_global_ = m.Etot + g.n_pose_edges() + g.relpose.n();
+    if (g.relpose.n() && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: relative-pose edge sets are not supported on a landmark-sharded (multi-GPU) "
+                                 "optimiser yet");
+    // (k_hsc_offdiag_strip reads the list entry before a block's range: a pair block without products has none)
+    if (g.relpose.n() && m.opt.hsc_strip)
+        throw std::runtime_error("cugo: relative-pose edge sets cannot be combined with CUGO_HSC_STRIP=1: the row-strip "
+                                 "form of the Schur complement cannot hold a block without landmark products");
     for (int k = POSE_KIND_COUNT - 1; k >= 0; k--) // (priors first: the message a graph with several kinds has always got)
         if (g.kinds[k].n() && (m.world > 1 || m.comm))
             throw std::runtime_error(std::string("cugo: ") + pose_kind_group(k) +
@@ -973,6 +1100,7 @@ void Engine::initialize(FlatGraph& g)
     sort_landmark_major(g, m.st_lm_cnt, m.st_order);
     laps.lap("engine: landmark sort");
     build_covisibility(g, m.st_lm_cnt, m.st_order, m.cov_ptr, m.cov_pose);
+    m.build_pair_lists(g.relpose);
     laps.lap("engine: co-visibility");
     // the helper starts before the slot work ...
     const bool helper_started = m.start_pattern_helper(prof_);
@@ -1034,7 +1162,8 @@ void Engine::initialize(FlatGraph& g)
     const int dims[8] = {m.Pall, m.Lall, m.P, m.L, m.E, m.rank, m.world, m.Etot};
     if (!(m.opt.structure_reuse && m.sig_valid && std::memcmp(dims, m.sig_dims, sizeof dims) == 0 &&
           same_bytes(m.slots.pose, m.sig_e_pose) && same_bytes(m.slots.lm, m.sig_e_lm) &&
-          same_bytes(m.slots.flags, m.sig_flags) && same_bytes(m.cov_pose, m.sig_cov_pose)))
+          same_bytes(m.slots.flags, m.sig_flags) && same_bytes(m.cov_pose, m.sig_cov_pose) &&
+          m.pair_lo == m.sig_pair_lo && m.pair_hi == m.sig_pair_hi))
         m.structure_dirty = true;
     std::memcpy(m.pending_dims, dims, sizeof dims);
     laps.lap("engine: topology compare");
@@ -1053,6 +1182,8 @@ void Engine::initialize(FlatGraph& g)
     prof_[PROF_INITIALIZE] += ms_since(t0);
     if (m.plan_only && m.structure_dirty)
         build_structure(); // no optimize() will follow: the structure is all there is to do
+    if (m.plan_only)
+        m.pe.bind_relpose_plan(m.hsc_rowptr, m.hsc_colind, s, true);
 }
 
 void Engine::fill_structure_stats(int B, double products, double offdiag_products)
@@ -1075,6 +1206,7 @@ void Engine::fill_structure_stats(int B, double products, double offdiag_product
         };
         copy(m.sig_e_pose, m.slots.pose), copy(m.sig_e_lm, m.slots.lm), copy(m.sig_flags, m.slots.flags);
         copy(m.sig_cov_pose, m.cov_pose);
+        m.sig_pair_lo = m.pair_lo, m.sig_pair_hi = m.pair_hi;
     }
     // row strips, opt-in (CUGO_HSC_STRIP=1; default: one wave per block anywhere): per product the position of
     // its T edge in the edge list of its pose.  Bit for bit the gather kernel's sums with each T block read once,
@@ -1242,6 +1374,7 @@ void Engine::adopt_structure(const cugo_hsc_struct& hs, double products, double 
     sstats_.schur_slots = schur_slots;
     // (a plan-only engine builds its structure in every initialize(): nothing else would ever show a changed option)
     m.structure_dirty = m.plan_only;
+    m.pe.rp.plan_dirty = true; // (the block indices of the relative-pose plan are those of the pattern)
 }
 
 // Device-side build (structure_gpu.h): the same lists, in the same order, as the host passes; a shard builds the
@@ -1250,14 +1383,14 @@ bool Engine::device_structure(InitLaps& laps)
 {
     Impl& m = *impl_;
     hipStream_t s = m.ctx.stream;
-    const int P = m.P, L = m.L;
+    const int P = m.P;
     const bool have_lists = m.lists_built && m.pat_async_ok; // (built at the end of initialize() for this pattern)
     m.lists_built = false;
     // phase 1 (unless the helper thread of initialize() has done it, or the lists are those of the
     // pattern at hand): Hsc pattern from the co-visibility lists, ordering + symbolic factorisation
     if (m.pattern_dirty && !m.pat_async_ok)
     {
-        if (!build_pattern_gpu(s, P, L, m.cov_ptr.data(), m.cov_pose.data(), m.gstruct))
+        if (!build_pattern_gpu(s, P, m.pat_lists(), m.pat_ptr().data(), m.pat_pose().data(), m.gstruct))
             return false;
         m.hsc_rowptr = m.gstruct.h_rowptr, m.hsc_colind = m.gstruct.h_colind;
         prof_[PROF_BUILD_STRUCTURE] += ms_since(laps.t0);
@@ -1277,7 +1410,7 @@ bool Engine::device_structure(InitLaps& laps)
         m.plan_uploaded = true;
     }
     if (m.pattern_dirty)
-        m.pat_P = P, m.pat_L = L, m.pat_cov_ptr = m.cov_ptr, m.pat_cov_pose = m.cov_pose;
+        m.pat_P = P, m.pat_L = m.pat_lists(), m.pat_cov_ptr = m.pat_ptr(), m.pat_cov_pose = m.pat_pose();
     m.pattern_dirty = false;
     m.gstruct.scratch.release(), m.gstruct.scratch2.release();
     cugo_hsc_struct hs{};
@@ -1290,7 +1423,10 @@ bool Engine::device_structure(InitLaps& laps)
     const double diag_products = m.world > 1 || m.comm ? (double)m.cov_pose.size() : count_free_free(m.slots.flags);
     prof_[PROF_BUILD_STRUCTURE] += ms_since(t2);
     laps.lap("structure: plan upload");
-    adopt_structure(hs, (double)m.gstruct.Mglobal + diag_products, (double)m.gstruct.Moff, 0);
+    // (with relative-pose pairs the pattern's lists hold one entry per pair that is no product: single process, so the
+    //  off-diagonal products of the graph are those of the local lists)
+    const double offdiag_global = m.pair_lo.empty() ? (double)m.gstruct.Mglobal : (double)m.gstruct.Moff;
+    adopt_structure(hs, offdiag_global + diag_products, (double)m.gstruct.Moff, 0);
     return true;
 }
 
@@ -1312,7 +1448,7 @@ void Engine::host_structure(InitLaps& laps)
             laps.lap("structure: landmark-major product plan");
             return m.splan_on = sp.usable;
         },
-        [&](const char* what) { laps.lap(what); }, m.hsc_rowptr, m.hsc_colind, hst);
+        [&](const char* what) { laps.lap(what); }, m.hsc_rowptr, m.hsc_colind, hst, &m.pair_lo, &m.pair_hi);
     laps.lap("structure: product lists");
     // off-diagonal products: from the lists, or (plan) all products minus one per free-free edge
     const double n_offdiag = m.splan_on ? (double)sp.prod.size() - count_free_free(m.slots.flags) : (double)hst.off_ei.size();
@@ -1374,6 +1510,11 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
 
     if (m.structure_dirty)
         build_structure();
+    if (m.pe.n_relpose && m.pe.rp.plan_dirty)
+    {
+        m.join_pattern(); // (the helper of initialize() writes the host pattern)
+        m.pe.bind_relpose_plan(m.hsc_rowptr, m.hsc_colind, s, false);
+    }
     m.begin_call(true);
     const Impl::CallFacts& f = m.f;
     Impl::LmState& st = m.st = Impl::LmState{};
@@ -1649,6 +1790,7 @@ const std::vector<int32_t>& Engine::icp_slot_source(int kind, bool set) const
     return impl_->pe.icp_slot_source(kind == 1 ? 1 : 0, set);
 }
 int Engine::n_prior_edges() const { return impl_->pe.n_prior; }
+int Engine::n_relpose_edges() const { return impl_->pe.n_relpose; }
 int Engine::n_poses_free() const { return impl_->P; }
 int Engine::n_landmarks_free() const { return impl_->L; }
 
@@ -1674,6 +1816,11 @@ bool Engine::compute_covariances(int what)
     if (m.structure_dirty)
         build_structure();
     hipStream_t s = m.ctx.stream;
+    if (m.pe.n_relpose && m.pe.rp.plan_dirty)
+    {
+        m.join_pattern(); // (the helper of initialize() writes the host pattern)
+        m.pe.bind_relpose_plan(m.hsc_rowptr, m.hsc_colind, s, false);
+    }
     m.begin_call(false);
     // H at the current estimates, undamped: the two-stream build pass (Hpp, b, Hll, Hpl), as a retried trial of
     // optimize() queues it.  optimize() starts every call with a build pass of its own, so nothing it reads is lost.

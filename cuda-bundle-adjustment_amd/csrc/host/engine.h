@@ -57,6 +57,26 @@ inline const char* pose_kind_group(int kind)
     return kind == POSE_KIND_PRIOR ? "pose prior" : "point-to-plane / point-to-line";
 }
 
+// Relative-pose edges (relpose_types.h): binary, so they have a record of their own.  Container order over all the sets
+// (the plan fixes the summation order, not a sort); only edges that count get here: active, at least one free end
+// (graph_optimisation.cpp validates and drops)
+struct FlatRelPose
+{
+    std::vector<int32_t> pose_a, pose_b; // free-first pose indices (one of the two may be a fixed pose, >= P)
+    std::vector<double> meas;            // E x 7 (q x y z w, t) of Z ~ T_a T_b^-1
+    std::vector<double> weight;          // E x 21 (upper triangle of Omega, row-major packed), or 1 x 21
+    std::vector<int32_t> src_set, src_edge;
+    int rk = CUGO_RK_NONE;
+    double delta = 1.0;
+    bool rk_seen = false;
+    int n() const { return (int)pose_a.size(); }
+    void clear()
+    {
+        pose_a.clear(), pose_b.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear();
+        rk = CUGO_RK_NONE, delta = 1.0, rk_seen = false;
+    }
+};
+
 struct FlatGraph
 {
     int Pall = 0, Lall = 0, P = 0, L = 0;
@@ -74,6 +94,7 @@ struct FlatGraph
     // the chi2 threshold of its edge set, 0 = disabled; empty = disabled for all
     std::vector<double> e_outlier_threshold;
     FlatPoseKind kinds[POSE_KIND_COUNT]; // widths set by the constructor
+    FlatRelPose relpose;
     FlatGraph()
     {
         const int w[POSE_KIND_COUNT][2] = {{7, 1}, {9, 1}, {7, 21}};
@@ -178,9 +199,10 @@ public:
     const std::vector<double>& cov_lm() const { return cov_lm_; }
     int n_poses_free() const;
     int n_landmarks_free() const;
-    int n_active_edges() const { return E_global_; } // BA + ICP edges + priors of the current flattening
+    int n_active_edges() const { return E_global_; } // BA + ICP edges + priors + relative-pose edges of the current flattening
     int n_icp_edges(int kind) const;                  // 0 plane, 1 line
     int n_prior_edges() const;
+    int n_relpose_edges() const;
     // sorted slot of a kind -> {edge set, position in the set} as FlatPoseKind recorded them (kept for a later
     // outlier rejection on these sets)
     const std::vector<int32_t>& icp_slot_source(int kind, bool set) const;

@@ -73,6 +73,7 @@ void CudaGraphOptimisationImpl::exchangeStats(double& bytes, int& calls) const
 int CudaGraphOptimisationImpl::nActiveEdges() const { return engine_->n_active_edges(); }
 int CudaGraphOptimisationImpl::nIcpEdges(int kind) const { return engine_->n_icp_edges(kind); }
 int CudaGraphOptimisationImpl::nPriorEdges() const { return engine_->n_prior_edges(); }
+int CudaGraphOptimisationImpl::nRelPoseEdges() const { return engine_->n_relpose_edges(); }
 
 std::vector<double> CudaGraphOptimisationImpl::structureStats() const
 {
@@ -189,6 +190,41 @@ static const char* checkInformation36(const double* A)
     return nullptr;
 }
 
+// What the pose edge kinds, unary and binary, share per set: no outlier threshold, one robust kernel per kind (rk, delta,
+// rk_seen: the kind's record), check_set()
+template <class CheckSet>
+static void settlePoseEdgeSet(BaseEdgeSet* es, int setIndex, const std::string& name, int& out_rk, double& out_delta,
+                              bool& out_rk_seen, CheckSet check_set)
+{
+    if (es->getOutlierThreshold() > 0.0)
+        throw std::runtime_error("cugo: outlier rejection is not available on " + name +
+                                 " edge sets yet (setOutlierThreshold must stay 0)");
+    const RobustKernel& k = es->robustKernelData();
+    const int rk = rk_code(k.type());
+    const double delta = k.delta();
+    if (es->nedges() > 0)
+    {
+        if (out_rk_seen && (rk != out_rk || (rk != CUGO_RK_NONE && delta != out_delta)))
+            throw std::runtime_error("cugo: the " + name + " edge sets of one optimiser must use the same robust kernel");
+        if (!std::isfinite(delta) || (rk != CUGO_RK_NONE && !(delta > 0.0)))
+            throw std::runtime_error("cugo: bad robust kernel delta on a " + name + " edge set");
+        out_rk = rk, out_delta = delta;
+        out_rk_seen = true;
+        if (const char* bad = check_set())
+            throw std::runtime_error("cugo: " + name + " edge set " + std::to_string(setIndex) + ": " + bad);
+    }
+    es->setOutlierCount(0);
+}
+// v is a pose vertex of one of the optimiser's pose vertex sets
+static bool knownPoseVertex(const BaseVertex* v, const std::vector<BaseVertexSet*>& vertexSets)
+{
+    bool known = false;
+    if (v && !v->isMarginilised())
+        for (const BaseVertexSet* vs : vertexSets)
+            known = known || (vs == v->ownerSet() && !vs->isMarginilised());
+    return known;
+}
+
 // One edge set of unary pose edges (PlaneEdgeSet / LineEdgeSet of icp_types.h, PosePriorEdgeSet of prior_types.h) into
 // the flat arrays of its kind, in container order.  This is the one place where these edges are checked (the kernels
 // take the layout as given): every active edge must sit on a pose vertex of one of the optimiser's pose vertex sets and
@@ -201,24 +237,7 @@ static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, const char* kind, 
                                cugo_host::FlatPoseKind& out, Payload payload, CheckSet check_set)
 {
     const std::string name = kind;
-    if (es->getOutlierThreshold() > 0.0)
-        throw std::runtime_error("cugo: outlier rejection is not available on " + name +
-                                 " edge sets yet (setOutlierThreshold must stay 0)");
-    const RobustKernel& k = es->robustKernelData();
-    const int rk = rk_code(k.type());
-    const double delta = k.delta();
-    if (es->nedges() > 0)
-    {
-        if (out.rk_seen && (rk != out.rk || (rk != CUGO_RK_NONE && delta != out.delta)))
-            throw std::runtime_error("cugo: the " + name + " edge sets of one optimiser must use the same robust kernel");
-        if (!std::isfinite(delta) || (rk != CUGO_RK_NONE && !(delta > 0.0)))
-            throw std::runtime_error("cugo: bad robust kernel delta on a " + name + " edge set");
-        out.rk = rk, out.delta = delta;
-        out.rk_seen = true;
-        if (const char* bad = check_set())
-            throw std::runtime_error("cugo: " + name + " edge set " + std::to_string(setIndex) + ": " + bad);
-    }
-    es->setOutlierCount(0);
+    settlePoseEdgeSet(es, setIndex, name, out.rk, out.delta, out.rk_seen, check_set);
     size_t i = 0, kept = 0;
     for (BaseEdge* e : es->get())
     {
@@ -230,11 +249,7 @@ static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, const char* kind, 
                                      std::to_string(setIndex) + ": " + what);
         };
         BaseVertex* v = e->getVertex(0);
-        bool known = false;
-        if (v && !v->isMarginilised())
-            for (const BaseVertexSet* vs : vertexSets)
-                known = known || (vs == v->ownerSet() && !vs->isMarginilised());
-        if (!known)
+        if (!knownPoseVertex(v, vertexSets))
             refuse("its pose vertex is in no pose vertex set of this optimiser");
         double meas[9], weight[21];
         payload(e, refuse, meas, weight);
@@ -316,6 +331,45 @@ static void priorPayload(BaseEdge* e, const double* setInformation, Refuse& refu
             weight[t++] = 0.5 * (A[6 * r + c] + A[6 * c + r]);
 }
 
+// One RelPoseEdgeSet (relpose_types.h) into the flat record, in container order: the binary counterpart of
+// flattenPoseEdgeSet.  The measurement and Omega are the prior's (priorPayload checks them).  Refused: a == b, an end in
+// no pose vertex set of the optimiser; dropped: inactive edges and edges between two fixed poses.
+static void flattenRelPoseEdgeSet(RelPoseEdgeSet* es, int setIndex, bool perEdgeInformation,
+                                  const std::vector<BaseVertexSet*>& vertexSets, cugo_host::FlatRelPose& out)
+{
+    const std::string name = "relative-pose";
+    const double* setInformation = perEdgeInformation ? nullptr : es->informationMatrix();
+    settlePoseEdgeSet(es, setIndex, name, out.rk, out.delta, out.rk_seen,
+                      [&] { return setInformation ? checkInformation36(setInformation) : nullptr; });
+    size_t i = 0, kept = 0;
+    for (BaseEdge* e : es->get())
+    {
+        const size_t at = i++;
+        if (!e->isActive())
+            continue;
+        auto refuse = [&](const char* what) {
+            throw std::runtime_error("cugo: " + name + " edge " + std::to_string(at) + " of edge set " +
+                                     std::to_string(setIndex) + ": " + what);
+        };
+        BaseVertex *va = e->getVertex(0), *vb = e->getVertex(1);
+        if (!knownPoseVertex(va, vertexSets) || !knownPoseVertex(vb, vertexSets))
+            refuse("one of its pose vertices is in no pose vertex set of this optimiser");
+        if (va == vb)
+            refuse("it joins a pose to itself (a == b)");
+        double meas[9], weight[21];
+        priorPayload(e, setInformation, refuse, meas, weight);
+        if (va->isFixed() && vb->isFixed())
+            continue;
+        out.pose_a.push_back(va->getIndex()), out.pose_b.push_back(vb->getIndex());
+        out.meas.insert(out.meas.end(), meas, meas + 7);
+        out.weight.insert(out.weight.end(), weight, weight + 21);
+        out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
+        kept++;
+    }
+    es->setActiveEdgeCount(kept);
+    es->setDirtyState(false);
+}
+
 void CudaGraphOptimisationImpl::initialize()
 {
     if (vertexSets.empty() || edgeSets.empty())
@@ -346,7 +400,7 @@ void CudaGraphOptimisationImpl::initialize()
     {
         bool same = flattenValid_ && eopt.flatten_reuse && eopt.structure_reuse &&
                     flattenOptions_[0] == options.perEdgeInformation && flattenOptions_[1] == options.perEdgeCamera &&
-                    flattenOptions_[2] == options.useFloat32 &&
+                    flattenOptions_[2] == options.useFloat32 && flattenOptions_[3] == options.relativePoseEdges &&
                     flattenCounts_.size() == vertexSets.size() + edgeSets.size();
         size_t q = 0;
         for (size_t i = 0; same && i < vertexSets.size(); i++, q++)
@@ -426,6 +480,7 @@ void CudaGraphOptimisationImpl::initialize()
             cap += es->nedges();
     for (cugo_host::FlatPoseKind& fk : g.kinds)
         fk.clear();
+    g.relpose.clear();
     g.e_pose.resize(cap), g.e_lm.resize(cap), g.e_flags.resize(cap);
     g.e_meas.resize(3 * cap), g.e_omega.resize(cap), g.e_cam.resize(cap);
     g.e_outlier_threshold.resize(cap);
@@ -462,9 +517,15 @@ void CudaGraphOptimisationImpl::initialize()
                 [] { return (const char*)nullptr; });
             continue;
         }
-        if (dim == 6 && dynamic_cast<RelPoseEdgeSet*>(es)) // (relpose_types.h, an extension: kernel level only so far)
-            throw std::runtime_error("cugo: the optimiser does not take relative-pose edge sets yet "
-                                     "(their terms: cugo_relpose_* in include/cugo_hip.h)");
+        if (auto* rs = dim == 6 ? dynamic_cast<RelPoseEdgeSet*>(es) : nullptr)
+        { // RelPoseEdgeSet (relpose_types.h, an extension): opt-in
+            if (!options.relativePoseEdges)
+                throw std::runtime_error("cugo: the optimiser does not take relative-pose edge sets unless "
+                                         "GraphOptimisationOptions::relativePoseEdges is on "
+                                         "(their terms alone: cugo_relpose_* in include/cugo_hip.h)");
+            flattenRelPoseEdgeSet(rs, (int)si, options.perEdgeInformation, vertexSets, g.relpose);
+            continue;
+        }
         if (dim == 6)
         { // PosePriorEdgeSet (prior_types.h, an extension)
             auto* ps = dynamic_cast<PosePriorEdgeSet*>(es);
@@ -651,6 +712,14 @@ void CudaGraphOptimisationImpl::initialize()
         if (uniform)
             fk.weight.resize(fk.weight_w);
     }
+    {
+        std::vector<double>& w = g.relpose.weight;
+        bool uniform = g.relpose.n() > 0;
+        for (size_t i = 21; uniform && i < w.size(); i++)
+            uniform = w[i] == w[i % 21];
+        if (uniform)
+            w.resize(21);
+    }
     lap("graph: edge flatten");
 
     engine_->initialize(g);
@@ -664,7 +733,7 @@ void CudaGraphOptimisationImpl::initialize()
     for (BaseEdgeSet* es : edgeSets)
         flattenCounts_.emplace_back(es, es->changeCount());
     flattenOptions_[0] = options.perEdgeInformation, flattenOptions_[1] = options.perEdgeCamera;
-    flattenOptions_[2] = options.useFloat32;
+    flattenOptions_[2] = options.useFloat32, flattenOptions_[3] = options.relativePoseEdges;
     flattenValid_ = true;
     initialized_ = true;
 }

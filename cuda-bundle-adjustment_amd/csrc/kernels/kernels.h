@@ -208,12 +208,18 @@ int relpose_workgroups(const cugo_relpose_edges& ev); // 0 without edges or free
 // chi2 only; d_edge_chi [n] (edge order; only the edges that count are written) or nullptr
 void launch_relpose_errors(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
                            double* d_wg_chi, double* d_edge_chi = nullptr);
-// the terms ADDED to d_Hpp / d_bp, the off-diagonal blocks to d_Hoff [nnzb][36] by block index ...
+// the terms ADDED to d_Hpp / d_bp, the off-diagonal blocks to d_Hoff [nnzb][36] by block index (d_Hoff null: the
+// off-diagonal terms are stored nowhere, launch_relpose_add_offdiag adds them later) ...
 void launch_relpose_add(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
                         double* d_Hpp, double* d_bp, double* d_Hoff, double* d_wg_chi);
 // ... or to d_Hsc (diagonal through d_rowptr, off-diagonal by block index), d_bp and d_bsc
 void launch_relpose_add_schur(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
                               const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_wg_chi);
+// ... or the off-diagonal terms alone ADDED to d_Hsc by block index: behind a Schur pass of the two-stream form, which
+// has just overwritten every block, at the poses the build pass (launch_relpose_add with a null d_Hoff) linearised at.
+// The terms and their order are those of launch_relpose_add_schur; no chi2 totals are written
+void launch_relpose_add_offdiag(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
+                                double* d_Hsc);
 
 // chi_e per edge slot (outlier rejection, ref: computeOutliersKernel cuda_block_solver.cu:1135)
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,

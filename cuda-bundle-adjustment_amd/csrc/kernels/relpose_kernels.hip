@@ -32,6 +32,12 @@
 // is free, else that of b; every workgroup leaves one chi2 total (its poses in order) and the error-only form walks the
 // same lists, so its chi2 has the bits of the build pass's.  A pose whose list is empty or all flagged inactive keeps
 // the bits of its blocks; fixed poses are never walked.
+//
+// The LM loop's two-stream form builds Hpp first and the Schur complement, which OVERWRITES every block of Hsc, later
+// and possibly more than once (a retried trial).  There the build form gets no off-diagonal destination (Hoff null: its
+// lanes 27..62 store nothing) and a fourth form, queued behind the Schur pass at the same poses, walks only the edges
+// whose off-diagonal term belongs to the pose and adds lanes 27..62's element into Hsc by block index: the same terms in
+// the same order as the Schur form adds them, no second Hsc-sized buffer, nothing else written (no chi2 totals).
 #include <hip/hip_runtime.h>
 
 #include "ba_math.h"
@@ -49,8 +55,9 @@ constexpr int RELPOSE_POSES = RELPOSE_WG / RELPOSE_LANES; // poses per workgroup
 enum RelPoseMode
 {
     RELPOSE_ERRORS = 0, // chi2 only
-    RELPOSE_HPP = 1,    // + diagonal into Hpp [P][36], b into bp, off-diagonal into Hoff [nnzb][36]
-    RELPOSE_SCHUR = 2   // + diagonal (through rowptr) and off-diagonal into Hsc, b into bp and bsc
+    RELPOSE_HPP = 1,    // + diagonal into Hpp [P][36], b into bp, off-diagonal into Hoff [nnzb][36] (or nowhere: Hoff null)
+    RELPOSE_SCHUR = 2,  // + diagonal (through rowptr) and off-diagonal into Hsc, b into bp and bsc
+    RELPOSE_OFFDIAG = 3 // the off-diagonal terms alone into Hoff (= Hsc) by block index; no chi2 totals
 };
 
 struct RelPoseArgs
@@ -271,6 +278,8 @@ __global__ __launch_bounds__(RELPOSE_WG) void k_relpose(RelPoseArgs a, double* H
             const bool counts_chi = side == 0 || other >= P;
             if (MODE == RELPOSE_ERRORS && !counts_chi)
                 continue;
+            if (MODE == RELPOSE_OFFDIAG && !(other < P && p < other))
+                continue;
             const double* op = a.poses + 7 * (size_t)other;
             const double* pa = side ? op : self;
             const double* pb = side ? self : op;
@@ -283,7 +292,7 @@ __global__ __launch_bounds__(RELPOSE_WG) void k_relpose(RelPoseArgs a, double* H
             asm volatile("" : "+v"(ri_e), "+v"(ci_e));
             const double c = relpose_edge<MODE != RELPOSE_ERRORS>(a, e, pa, pb, side, is_off, ri_e, ci_e, is_b ? -1.0 : 1.0, term);
             any = true;
-            if (counts_chi)
+            if (MODE != RELPOSE_OFFDIAG && counts_chi)
             {
                 chi += c;
                 if (MODE == RELPOSE_ERRORS && a.edge_chi && t == 0)
@@ -293,11 +302,13 @@ __global__ __launch_bounds__(RELPOSE_WG) void k_relpose(RelPoseArgs a, double* H
             {
                 if (!is_off)
                     mine += term;
-                else if (off)
+                else if (off && Hoff)
                     Hoff[36 * (size_t)a.plan.off_blk[e] + (t - 27)] += term;
             }
         }
     }
+    if (MODE == RELPOSE_OFFDIAG)
+        return;
     if (t == 0)
         s_chi[g] = chi;
     if (MODE != RELPOSE_ERRORS && any)
@@ -369,6 +380,18 @@ void launch_relpose_add_schur(hipStream_t s, const cugo_relpose_edges& ev, const
     const RelPoseArgs a = args_of(ev, plan, d_poses, d_wg_chi, nullptr);
     LaunchScope scope("k_relpose_add_schur", s);
     hipLaunchKernelGGL(k_relpose<RELPOSE_SCHUR>, dim3(wgs), dim3(RELPOSE_WG), 0, s, a, d_Hsc, d_Hsc, d_rowptr, d_bp, d_bsc);
+}
+
+void launch_relpose_add_offdiag(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
+                                double* d_Hsc)
+{
+    const int wgs = relpose_workgroups(ev);
+    if (!wgs)
+        return;
+    const RelPoseArgs a = args_of(ev, plan, d_poses, nullptr, nullptr);
+    LaunchScope scope("k_relpose_add_offdiag", s);
+    hipLaunchKernelGGL(k_relpose<RELPOSE_OFFDIAG>, dim3(wgs), dim3(RELPOSE_WG), 0, s, a, (double*)nullptr, d_Hsc,
+                       (const int32_t*)nullptr, (double*)nullptr, (double*)nullptr);
 }
 
 } // namespace cugo_k

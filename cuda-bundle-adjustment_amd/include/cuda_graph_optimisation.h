@@ -141,6 +141,9 @@ public:
     int nIcpEdges(int kind) const;
     /** active SE(3) pose priors of the current flattening (prior_types.h, an extension) */
     int nPriorEdges() const;
+    /** relative-pose edges of the current flattening that count: active, at least one free end (relpose_types.h, an
+     *  extension; GraphOptimisationOptions::relativePoseEdges) */
+    int nRelPoseEdges() const;
     /** B, M, nnz(L), flops, supernodes, stages, front bytes, off-diagonal products, then per
      *  factorisation: potrf / trsm / syrk flops, extend-add bytes, backward bytes */
     std::vector<double> structureStats() const;
@@ -183,7 +186,7 @@ private:
     // change counts of the sets at the last full flattening (initialize() refreshes only the
     // estimates while they stand)
     std::vector<std::pair<const void*, unsigned long long>> flattenCounts_;
-    bool flattenOptions_[3] = {false, false, false};
+    bool flattenOptions_[4] = {false, false, false, false};
     bool flattenValid_ = false;
     bool initialized_ = false; // initialize() ran (computeMarginals needs it)
     bool flattenedUnchanged(const BaseVertexSet* vs) const;

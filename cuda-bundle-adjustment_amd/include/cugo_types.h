@@ -149,6 +149,10 @@ struct CUGO_API GraphOptimisationOptions
     // symbolic factorisation — what structureStats() reports); optimize() fails.  Used to size a
     // problem ahead of time and to run the host code under sanitizers (make SAN=1).
     bool planOnly = false;
+    // Extension: take relative-pose SE(3) edge sets (relpose_types.h) into the optimiser.  Off (the default):
+    // initialize() refuses such a set, as before the optimiser could take it.  On: the set is flattened and checked,
+    // its pose pairs join the Hsc pattern and optimize() minimises the joint cost.
+    bool relativePoseEdges = false;
 };
 
 enum class RobustKernelType

@@ -12,10 +12,15 @@
 // With T_b the fixed identity this is the pose prior, term for term.  An edge with one fixed end counts in chi2 and adds
 // only its free end's block and b; an edge between two fixed poses counts for nothing; a == b is refused.
 // The residual, the Jacobians and the device kernel are in csrc/kernels/relpose_kernels.hip.  The set is a plain
-// container like the others, vertex 0 = a, vertex 1 = b.  The terms are reachable through the kernel-level C ABI
-// (include/cugo_hip.h: cugo_relpose_edges, cugo_relpose_plan_create, cugo_relpose_compute_errors,
-// cugo_relpose_construct_quadratic_form[_schur]); the optimiser does not take the set yet: initialize() recognises it
-// by type and refuses it, naming those entry points.
+// container like the others, vertex 0 = a, vertex 1 = b: add it with addEdgeSet() next to (or instead of) the others.
+// The optimiser takes it when GraphOptimisationOptions::relativePoseEdges is on: initialize() recognises the set by
+// type, checks every active edge (finite values, |q_z| = 1 to 1e-6, Omega symmetric to 1e-12 max|Omega| and positive
+// semi-definite to -1e-12 lambda_max, a != b, both ends in pose sets of the optimiser), merges the pose pairs into the
+// Hsc pattern and optimize() minimises the joint cost; inactive edges and edges between two fixed poses are dropped.
+// Outlier thresholds on the set, sets that disagree on the robust kernel and sharded optimisers are refused.  With the
+// option off (the default) initialize() refuses the set and names the option and the kernel-level C ABI, through which
+// the terms are reachable as well (include/cugo_hip.h: cugo_relpose_edges, cugo_relpose_plan_create,
+// cugo_relpose_compute_errors, cugo_relpose_construct_quadratic_form[_schur]).
 #pragma once
 #include <algorithm>
 

@@ -426,6 +426,15 @@ int cugo_relpose_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_relpos
                                                 const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
                                                 double* d_chi);
 
+/* The two launches the two-stream form of the LM loop makes of the same terms.  The build pass: the diagonal terms and
+ * b ADDED to d_Hpp / d_bp as cugo_relpose_construct_quadratic_form adds them, the off-diagonal terms stored nowhere ... */
+int cugo_relpose_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses,
+                                               double* d_Hpp, double* d_bp, double* d_chi);
+/* ... and, behind a Schur pass (which has written every block of d_Hsc), the off-diagonal terms alone ADDED to d_Hsc by
+ * the plan's block indices, at the same poses: the terms, in the order, of cugo_relpose_construct_quadratic_form_schur.
+ * Nothing else is written.  Deterministic: no atomics, one summation order. */
+int cugo_relpose_add_offdiag_schur(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses, double* d_Hsc);
+
 /* ---- (2) graph-level entry points ---------------------------------------------------- */
 
 typedef struct cugo_graph cugo_graph; /* CudaGraphOptimisationImpl + its vertex/edge sets */
@@ -489,6 +498,26 @@ int cugo_graph_set_prior_robust_kernel(cugo_graph* g, int type, double delta);
 int cugo_graph_set_prior_outlier_threshold(cugo_graph* g, double threshold);
 /* active priors in the current flattening (priors on fixed poses are not counted) */
 int cugo_graph_n_prior_edges(cugo_graph* g);
+/* Extension: relative-pose SE(3) edges (RelPoseEdgeSet, cuda-bundle-adjustment_amd/include/relpose_types.h), next to or
+ * instead of the other sets; term and conventions as for cugo_relpose_edges above (Z ~ T_a T_b^-1).  pose_ids_a /
+ * pose_ids_b [n]: ids given to cugo_graph_add_poses; q_t7 [n][7] the measured relative pose; info36 [n][36] or NULL for
+ * the set's matrix (cugo_graph_set_relpose_information; the identity until it is set), with the per_edge_information
+ * rule of the priors.  The graph object switches GraphOptimisationOptions::relativePoseEdges on itself.
+ * cugo_graph_initialize() refuses a == b, a pose of no pose set of the optimiser, non-finite values, |q_z| off 1 by more
+ * than 1e-6, an Omega that is asymmetric or indefinite (the bounds of the priors), an outlier threshold on the set and a
+ * sharded optimiser; inactive edges and edges between two fixed poses count for nothing, an edge with one fixed end
+ * counts in chi2 and adds its free end's terms.  The pose pairs join the Hsc pattern. */
+int cugo_graph_add_relpose_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b,
+                                 const double* q_t7, const double* info36);
+int cugo_graph_set_relpose_information(cugo_graph* g, const double* info36);
+int cugo_graph_set_relpose_robust_kernel(cugo_graph* g, int type, double delta);
+/* only 0 is usable for now: with a positive value cugo_graph_initialize() refuses the graph */
+int cugo_graph_set_relpose_outlier_threshold(cugo_graph* g, double threshold);
+/* active flag of the edges [first, first + n) of the set, in insertion order (an inactive edge is left out by the next
+ * cugo_graph_initialize(); a pair no active edge joins any more leaves the Hsc pattern) */
+int cugo_graph_set_relpose_active(cugo_graph* g, int first, int n, const uint8_t* active);
+/* relative-pose edges that count in the current flattening */
+int cugo_graph_n_relpose_edges(cugo_graph* g);
 /* multi-GPU: this process handles shard `rank` of `world` (landmark ranges).  exchange() is
  * called on the host with a DEVICE buffer that must be all-reduced in place over all ranks
  * (op 0 = sum, 1 = max) before it returns, or — op >= 2 — overwritten on every rank with rank
