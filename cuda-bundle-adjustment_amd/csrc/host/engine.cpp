@@ -1609,12 +1609,19 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
             auto tu = Clock::now();
             const int nxt = m.cur ^ 1;
             int n_scale_part = 0;
+            // one_stream: G^T dx_p from the build pass's records (CUGO_BS_RECORDS=0: from the G blocks).  The records
+            // are valid from a build pass until the first error pass behind it (launch_errors_tail parks its chi2
+            // partials in their area).  A one-stream trial is the first trial behind the fused build pass it was for,
+            // at the estimates in m.cur: queued at the top of this iteration, or behind the previous trial — then
+            // after that trial's error pass, or (from_build) in its place — and between that build pass and here only
+            // the Schur pass (which reads the same records), the factorisation and the solve have run.  A retry
+            // rebuilds H with the two-stream pass (fused_lambda < 0 above), so it is never one_stream
             m.timed("backsubst_update", [&] {
                 n_scale_part = cugo_k::launch_backsubst_update(
                     s, m.ev, lambda, (m.rank == 0 ? lambda : 0.0), m.d_invHll.data(), m.bl(), m.bp(),
                     one_stream ? m.d_T.data() : m.d_Hpl.data(), m.xp(), m.xl(), m.d_poses[m.cur].data(), m.d_lms[m.cur].data(),
                     m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rs(), f.sharded ? m.d_scal.data() + 3 : nullptr,
-                    one_stream ? m.d_lmrec.data() : nullptr);
+                    one_stream ? m.d_lmrec.data() : nullptr, one_stream && m.opt.bs_records);
             });
             sync_prof(PROF_UPDATE, tu);
             m.hash(hash_it, 8, m.xl(), 3 * (size_t)m.L);

@@ -16,6 +16,7 @@ struct Options
     bool fuse_t = true;    // CUGO_FUSE_T=0: T = Hpl invHll always by the Schur edge kernel
     bool pose_schur = true; // CUGO_POSE_SCHUR=0: Hsc's diagonal blocks always by k_build_poses + k_hsc_diag*, never by k_pose_schur
     bool float32 = false;  // CUGO_FLOAT32=1
+    bool bs_records = true; // CUGO_BS_RECORDS=0: the one-stream back-substitution reads the G blocks instead of re-forming them from the build pass's records
     // ---- LM loop ----
     bool speculate = true, trial_event = true, trial_poll = true; // CUGO_SPECULATE / CUGO_TRIAL_EVENT / CUGO_TRIAL_POLL = 0
     bool trial_from_build = true; // CUGO_TRIAL_FROM_BUILD=0: every trial ends with an error pass of its own
@@ -57,6 +58,7 @@ struct Options
         o.fuse_t = !off("CUGO_FUSE_T");
         o.pose_schur = !off("CUGO_POSE_SCHUR");
         o.float32 = on("CUGO_FLOAT32");
+        o.bs_records = !off("CUGO_BS_RECORDS");
         o.speculate = !off("CUGO_SPECULATE"), o.trial_event = !off("CUGO_TRIAL_EVENT"), o.trial_poll = !off("CUGO_TRIAL_POLL");
         o.trial_from_build = !off("CUGO_TRIAL_FROM_BUILD");
         o.profile = flag("CUGO_PROFILE");

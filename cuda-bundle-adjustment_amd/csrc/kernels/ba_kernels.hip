@@ -316,8 +316,14 @@ __device__ __forceinline__ LmContrib lm_contrib(const double JL[3][3], const Edg
 {
     const int dim = stereo ? 3 : 2;
     double s00 = 0, s01 = 0, s02 = 0, s11 = 0, s12 = 0, s22 = 0, t0 = 0, t1 = 0, t2 = 0;
-    for (int m = 0; m < dim; m++)
+    // three rows unrolled, the third skipped for a monocular edge: with the run-time bound `m < dim` the loop stays a
+    // loop, JL[m][.] is indexed at run time and all nine doubles of JL live in private memory (72 bytes per lane
+    // stored and reloaded).  Same operations in the same order
+#pragma unroll
+    for (int m = 0; m < 3; m++)
     {
+        if (m >= dim)
+            continue;
         s00 += JL[m][0] * JL[m][0];
         s01 += JL[m][0] * JL[m][1];
         s02 += JL[m][0] * JL[m][2];
@@ -332,7 +338,7 @@ __device__ __forceinline__ LmContrib lm_contrib(const double JL[3][3], const Edg
                      g.w * t0, g.w * t1, g.w * t2};
 }
 
-// (144 VGPRs: three waves per SIMD.  Capped at 128 — four waves — the kernel spills ~230 bytes per lane and takes
+// (153 VGPRs, no private segment: three waves per SIMD — tools/kernel_resources.sh.  Capped at 128 — four waves — the kernel spills ~230 bytes per lane and takes
 // 75 instead of 56 us: 11.43 vs 11.17 ms per step, 38.9 vs 38.2 ms on the 10k-pose graph.)
 template <typename S>
 __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restrict__ poses,
@@ -2301,21 +2307,68 @@ __device__ __forceinline__ void dev_update_poses(int blk, int nP, double lambda,
         partials[blk] = sc;
 }
 
+// G_e^T x of one slot with G_e = Hpl_e L^-T re-formed from what the build pass left instead of read from memory: the
+// slot's record r8 (k_build_edges: Xc, e, w, {camera index, stereo bit, ...}), the pose the pass linearised at and
+// q = L^-1 of the landmark's line.  H = w (JP^T JL) and G = H L^-T are the build pass's own expressions in its
+// association (the translation unit is compiled with -ffp-contract=off), every entry of G goes through S as its
+// store does, and the three sums run in hplT_x's order: the same bits as hplT_x on the stored block.
 template <typename S>
+__device__ __forceinline__ void gT_x_from_record(const double* r8, const double* __restrict__ pose,
+                                                 const double* __restrict__ cams, const double* __restrict__ q,
+                                                 const double* x, double& s0, double& s1, double& s2)
+{
+    const double Xc[3] = {r8[0], r8[1], r8[2]};
+    const double w = r8[6];
+    const long long bits = __double_as_longlong(r8[7]);
+    const double* cam = cams + 5 * (int)(bits & 0xffff);
+    const bool stereo = ((bits >> 16) & 1) != 0;
+    double JL[3][3], JP[3][6];
+    jac_landmark(Xc, pose, cam, stereo, JL);
+    jac_pose(Xc, cam, stereo, JP);
+    const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
+    s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+    for (int m = 0; m < 6; m++)
+    {
+        double h[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            double s = JP[0][m] * JL[0][c] + JP[1][m] * JL[1][c];
+            s += JP[2][m] * JL[2][c];
+            h[c] = w * s;
+        }
+        const double g0 = (double)(S)(h[0] * q0);
+        const double g1 = (double)(S)(h[0] * q1 + h[1] * q2);
+        const double g2 = (double)(S)(h[0] * q3 + h[1] * q4 + h[2] * q5);
+        const double xm = x[m];
+        s0 += g0 * xm;
+        s1 += g1 * xm;
+        s2 += g2 * xm;
+    }
+}
+
+// REC (only with lmrec, the one-stream form): the workgroup stages the 64-byte records of its 256 slots (`rec`, what
+// k_build_edges wrote and k_pose_schur reads) instead of the 144-byte G blocks and every lane re-forms its G^T x
+// (gT_x_from_record): 64 + 0 instead of 144 bytes per slot from memory, 24.6 instead of 36.9 KB of LDS.  The records
+// must be those of the build pass that wrote lmrec and G, at poses_in (see the call in engine.cpp).
+template <typename S, bool REC>
 __global__ __launch_bounds__(BS) void k_backsubst_landmarks(
     EV ev, double lambda, const double* __restrict__ invHll, const double* __restrict__ bl,
     const S* __restrict__ Hpl, const double* __restrict__ xp, double* __restrict__ xl,
     const double* __restrict__ lms_in, double* __restrict__ lms_out,
     double* __restrict__ partials, int nbl, double lambda_pose, const double* __restrict__ bp,
-    const double* __restrict__ poses_in, double* __restrict__ poses_out, const double* __restrict__ lmrec)
+    const double* __restrict__ poses_in, double* __restrict__ poses_out, const double* __restrict__ lmrec,
+    const double* __restrict__ rec)
 {
     // lmrec != nullptr: the one-stream form of the fused iteration (k_build_edges): `Hpl` holds G = Hpl L^-T and the
     // landmark's line {L^-1, y = L^-1 bl}:  dx_l = L^-T (y - sum G_e^T dx_p)  in place of  invHll (bl - sum Hpl_e^T dx_p)
     __shared__ double sm[BS / 64];
-    __shared__ double2 hs[BS * 9 + 1];
+    // REC: the records at a 9-double lane stride (as k_build_edges holds them), the products behind them
+    __shared__ double2 hs[REC ? BS * 6 : BS * 9 + 1];
     // the per-slot products Hpl^T x take the place of the staged blocks once every lane has consumed its own
     // (37 KB of LDS per workgroup instead of 43: four workgroups per CU instead of three)
-    double(*cs)[BS] = reinterpret_cast<double(*)[BS]>(hs);
+    double(*cs)[BS] = reinterpret_cast<double(*)[BS]>(reinterpret_cast<double*>(hs) + (REC ? 9 * BS : 0));
     if ((int)blockIdx.x >= nbl)
     { // pose update + its scale partials ride in the same launch (ref: updatePosesKernel .cu:1444)
         dev_update_poses(blockIdx.x - nbl, ev.P, lambda_pose, xp, bp, poses_in, poses_out,
@@ -2325,6 +2378,25 @@ __global__ __launch_bounds__(BS) void k_backsubst_landmarks(
     const int t = threadIdx.x;
     const int ebase = blockIdx.x * BS;
     const int e = ebase + t;
+    if constexpr (REC)
+    { // the records of the block's slots -> LDS, coalesced as they were written (zeros past the last slot)
+        double* rs_ = reinterpret_cast<double*>(hs);
+        const long base = 8L * ebase, limit = 8L * ev.E;
+        double2 v[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+        {
+            const int f = 2 * (i * BS + t); // flat double index within the block's records
+            v[i] = base + f < limit ? *reinterpret_cast<const double2*>(rec + base + f) : make_double2(0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+        {
+            const int f = 2 * (i * BS + t);
+            rs_[9 * (f >> 3) + (f & 7)] = v[i].x, rs_[9 * (f >> 3) + (f & 7) + 1] = v[i].y;
+        }
+    }
+    else
     { // stream the block's Hpl slots into LDS (zeros past the end)
         const long nvalid = 9L * max(0, min(BS, ev.E - ebase));
         // a workgroup past the last edge slot (the launch also covers the landmarks without edges; a SHARD
@@ -2357,6 +2429,15 @@ __global__ __launch_bounds__(BS) void k_backsubst_landmarks(
         }
     }
     __syncthreads();
+    if constexpr (REC)
+    {
+        double s0 = 0, s1 = 0, s2 = 0;
+        if (act && l < ev.L)
+            gT_x_from_record<S>(reinterpret_cast<const double*>(hs) + 9 * t, poses_in + 7 * (size_t)ev.pose[e], ev.cams,
+                                lmrec + 16 * (size_t)l, x, s0, s1, s2);
+        cs[0][t] = s0, cs[1][t] = s1, cs[2][t] = s2;
+    }
+    else
     {
         double s0 = 0, s1 = 0, s2 = 0;
         if (act)
@@ -2691,14 +2772,25 @@ static int launch_backsubst_update_t(hipStream_t s, const cugo_edges& e, double 
                                       const double* d_invHll, const double* d_bl, const double* d_bp,
                                       const S* d_Hpl, const double* d_xp, double* d_xl,
                                       const double* d_poses_in, const double* d_lms_in, double* d_poses_out,
-                                      double* d_lms_out, ReduceScratch rs, double* d_scale, const double* d_lmrec)
+                                      double* d_lms_out, ReduceScratch rs, double* d_scale, const double* d_lmrec,
+                                      bool from_records)
 {
     const EV ev = make_ev(e);
     const int nbl = div_up(ev.E > ev.L ? ev.E : ev.L, BS), nbp = div_up(ev.P, BS);
     if (nbl + nbp > 0)
-        CUGO_LAUNCH_T(k_backsubst_landmarks, S, dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda, d_invHll,
-                      d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl,
-                      lambda_pose, d_bp, d_poses_in, d_poses_out, d_lmrec);
+    {
+        ::cugo_k::LaunchScope _scope("k_backsubst_landmarks", s);
+        // from_records: G^T dx_p from the build pass's records in the scratch instead of the G stream
+        const double* d_rec = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
+        if (from_records && d_lmrec)
+            hipLaunchKernelGGL((k_backsubst_landmarks<S, true>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda, d_invHll,
+                               d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
+                               d_poses_in, d_poses_out, d_lmrec, d_rec);
+        else
+            hipLaunchKernelGGL((k_backsubst_landmarks<S, false>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda, d_invHll,
+                               d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
+                               d_poses_in, d_poses_out, d_lmrec, d_rec);
+    }
     if (d_scale) // nullptr: the partials stay in the scratch for launch_errors_tail
         CUGO_LAUNCH(k_sum_partials, dim3(1), dim3(SP_BS), 0, s, rs.d_partials, nbl + nbp, d_scale);
     return nbl + nbp;
@@ -2708,13 +2800,14 @@ int launch_backsubst_update(hipStream_t s, const cugo_edges& e, double lambda, d
                             const double* d_invHll, const double* d_bl, const double* d_bp,
                             const void* d_Hpl, const double* d_xp, double* d_xl,
                             const double* d_poses_in, const double* d_lms_in, double* d_poses_out,
-                            double* d_lms_out, ReduceScratch rs, double* d_scale, const double* d_lmrec)
+                            double* d_lms_out, ReduceScratch rs, double* d_scale, const double* d_lmrec,
+                            bool from_records)
 {
     if (e.block_f32)
         return launch_backsubst_update_t(s, e, lambda, lambda_pose, d_invHll, d_bl, d_bp, static_cast<const float*>(d_Hpl),
-                                  d_xp, d_xl, d_poses_in, d_lms_in, d_poses_out, d_lms_out, rs, d_scale, d_lmrec);
+                                  d_xp, d_xl, d_poses_in, d_lms_in, d_poses_out, d_lms_out, rs, d_scale, d_lmrec, from_records);
     return launch_backsubst_update_t(s, e, lambda, lambda_pose, d_invHll, d_bl, d_bp, static_cast<const double*>(d_Hpl),
-                                  d_xp, d_xl, d_poses_in, d_lms_in, d_poses_out, d_lms_out, rs, d_scale, d_lmrec);
+                                  d_xp, d_xl, d_poses_in, d_lms_in, d_poses_out, d_lms_out, rs, d_scale, d_lmrec, from_records);
 }
 
 } // namespace cugo_k

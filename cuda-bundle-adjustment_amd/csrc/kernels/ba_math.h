@@ -231,6 +231,19 @@ __device__ __forceinline__ Sym3 sym3_inv(const double* __restrict__ A, double la
     return s;
 }
 
+// quaternion of a rotation whose trace is not positive, I the index of its largest diagonal entry (ref: .cu:721-754)
+template <int I>
+__device__ __forceinline__ void quat_of_rot_diag(const double R[3][3], double dq[4])
+{
+    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
+    double t = sqrt(R[I][I] - R[J][J] - R[K][K] + 1);
+    dq[I] = 0.5 * t;
+    t = 0.5 / t;
+    dq[3] = (R[K][J] - R[J][K]) * t;
+    dq[J] = (R[J][I] + R[I][J]) * t;
+    dq[K] = (R[K][I] + R[I][K]) * t;
+}
+
 // T <- exp([w,v]) * T  (ref: updateExp .cu:781-809, updatePose .cu:811-823)
 __device__ __forceinline__ void pose_exp_update(const double* __restrict__ dx,
                                                 const double* __restrict__ pin,
@@ -279,18 +292,16 @@ __device__ __forceinline__ void pose_exp_update(const double* __restrict__ dx,
     }
     else
     {
-        int i = 0;
-        if (R[1][1] > R[0][0])
-            i = 1;
-        if (R[2][2] > R[i][i])
-            i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(R[i][i] - R[j][j] - R[k][k] + 1);
-        dq[i] = 0.5 * t;
-        t = 0.5 / t;
-        dq[3] = (R[k][j] - R[j][k]) * t;
-        dq[j] = (R[j][i] + R[i][j]) * t;
-        dq[k] = (R[k][i] + R[i][k]) * t;
+        // the largest diagonal entry picks one of three cases, each with compile-time indices: R[i][i] and dq[i] with
+        // a run-time i would put both arrays into private memory (and a private segment on every wave of the launch)
+        const bool c1 = R[1][1] > R[0][0];
+        const bool c2 = R[2][2] > (c1 ? R[1][1] : R[0][0]);
+        if (c2)
+            quat_of_rot_diag<2>(R, dq);
+        else if (c1)
+            quat_of_rot_diag<1>(R, dq);
+        else
+            quat_of_rot_diag<0>(R, dq);
     }
     const double dt0 = V[0][0] * dx[3] + V[0][1] * dx[4] + V[0][2] * dx[5];
     const double dt1 = V[1][0] * dx[3] + V[1][1] * dx[4] + V[1][2] * dx[5];

@@ -126,7 +126,13 @@ int launch_backsubst_update(hipStream_t s, const cugo_edges& ev, double lambda, 
                             const void* d_Hpl, const double* d_xp, double* d_xl,
                             const double* d_poses_in, const double* d_lms_in, double* d_poses_out,
                             double* d_lms_out, ReduceScratch rs, double* d_scale,
-                            const double* d_lmrec = nullptr); // d_lmrec: d_Hpl holds G, see k_backsubst_landmarks
+                            const double* d_lmrec = nullptr, // d_lmrec: d_Hpl holds G, see k_backsubst_landmarks
+                            bool from_records = false);
+// from_records (only with d_lmrec): the kernel re-forms G_e^T dx_p from the 64-byte records the build pass left in the
+// scratch `rs`, the poses it linearised at (d_poses_in) and the landmarks' lines instead of reading the 144-byte G
+// blocks — the same bits.  The records live from a build pass until the first error pass behind it
+// (launch_errors_tail parks its chi2 partials in their area): the caller vouches that none has run since the build
+// pass that wrote d_lmrec and G.
 // error pass of an LM trial + BOTH final reductions in one launch: d_out[0] = chi2, d_out[1] = scale
 // (from the n_scale_partials left by launch_backsubst_update); h_out (pinned host memory, may be
 // null) receives {chi2, scale, the 8 bytes at d_flag}: readable after the stream has been waited for
