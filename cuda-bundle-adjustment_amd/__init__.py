@@ -21,6 +21,10 @@ _lib = None
 OK = 0
 RK_NONE, RK_CAUCHY, RK_TUKEY, RK_HUBER = 0, 1, 2, 3
 ICP_PLANE, ICP_LINE = 0, 1
+# the four pose edge kinds of Graph.n_pose_edge_outliers / pose_edge_active (the first two are ICP_PLANE / ICP_LINE)
+POSE_KIND_PLANE, POSE_KIND_LINE, POSE_KIND_PRIOR, POSE_KIND_RELPOSE = 0, 1, 2, 3
+# pose_edges_reject: edges one trip of its grid covers (1024 workgroups of 256); beyond, a workgroup walks several runs
+POSE_REJECT_GRID_EDGES = 1024 * 256
 EDGE_FIXED_L, EDGE_FIXED_P, EDGE_STEREO, EDGE_INACTIVE = 1, 2, 4, 8
 
 _i32p = C.POINTER(C.c_int32)
@@ -211,6 +215,17 @@ def relpose_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_
     """cugo_relpose_construct_quadratic_form_schur: as prior_construct_quadratic_form_schur, plus the off-diagonal
     blocks into d_Hsc by the plan's block indices"""
     check(lib().cugo_relpose_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def pose_edges_reject(ctx, n, d_edge_chi, d_threshold, n_threshold, d_flags, d_rejected):
+    """cugo_pose_edges_reject: the outlier pass of the pose edge kinds.  Edge e goes iff it is not flagged EDGE_INACTIVE,
+    its threshold t (d_threshold[0] with n_threshold == 1, else d_threshold[e]) is > 0 and d_edge_chi[e] > t; its flag byte
+    gains EDGE_INACTIVE and its index goes to d_rejected (int32 [n], ascending).  Returns the number of edges that went.
+    Handles and pointers as for icp_construct_quadratic_form_schur (ctypes.c_void_p)"""
+    count = C.c_int(0)
+    check(lib().cugo_pose_edges_reject(ctx, int(n), d_edge_chi, d_threshold, int(n_threshold), d_flags, d_rejected,
+                                       C.byref(count)))
+    return count.value
 
 
 def device_count():
@@ -407,7 +422,9 @@ class Graph:
         check(lib().cugo_graph_set_icp_robust_kernel(self._g, int(kind), int(rk_type), C.c_double(delta)))
 
     def set_icp_outlier_threshold(self, kind, threshold):
-        """only 0 is usable: initialize() refuses a positive threshold on these sets (not built yet)"""
+        """chi2 threshold of the set (kind: ICP_PLANE / ICP_LINE; ref: EdgeSet::setOutlierThreshold).  With
+        set_option("pose_edge_outliers", 1) the edges above it are inactivated at the end of optimize(); without the
+        option initialize() refuses a positive threshold.  0 (or any value that is not a finite positive number) disables"""
         check(lib().cugo_graph_set_icp_outlier_threshold(self._g, int(kind), C.c_double(threshold)))
 
     def n_icp_edges(self, kind):
@@ -437,7 +454,7 @@ class Graph:
         check(lib().cugo_graph_set_prior_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
 
     def set_prior_outlier_threshold(self, threshold):
-        """only 0 is usable: initialize() refuses a positive threshold on the prior set (not built yet)"""
+        """chi2 threshold of the prior set, as set_icp_outlier_threshold (needs set_option("pose_edge_outliers", 1))"""
         check(lib().cugo_graph_set_prior_outlier_threshold(self._g, C.c_double(threshold)))
 
     def n_prior_edges(self):
@@ -469,7 +486,8 @@ class Graph:
         check(lib().cugo_graph_set_relpose_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
 
     def set_relpose_outlier_threshold(self, threshold):
-        """only 0 is usable: initialize() refuses a positive threshold on the relative-pose set (not built yet)"""
+        """chi2 threshold of the relative-pose set, as set_icp_outlier_threshold (needs set_option("pose_edge_outliers",
+        1)): false loop closures are dropped at the end of optimize() and left out by the next initialize()"""
         check(lib().cugo_graph_set_relpose_outlier_threshold(self._g, C.c_double(threshold)))
 
     def set_relpose_active(self, active, first=0):
@@ -492,6 +510,19 @@ class Graph:
     def edge_active(self, dim, n):
         out = np.zeros(n, np.uint8)
         check(lib().cugo_graph_get_edge_active(self._g, dim, n, _p(out, _u8p)))
+        return out.astype(bool)
+
+    def n_pose_edge_outliers(self, kind):
+        """outliers found in the set of the kind (POSE_KIND_*) since the last initialize()"""
+        n = lib().cugo_graph_n_pose_edge_outliers(self._g, int(kind))
+        if n < 0:
+            raise CugoError("cugo error %d: %s" % (n, lib().cugo_last_error().decode()))
+        return n
+
+    def pose_edge_active(self, kind, n):
+        """active flag of the first n edges of the kind (POSE_KIND_*), in insertion order"""
+        out = np.zeros(n, np.uint8)
+        check(lib().cugo_graph_get_pose_edge_active(self._g, int(kind), int(n), _p(out, _u8p)))
         return out.astype(bool)
 
     def set_shard(self, rank, world, fn):
@@ -519,7 +550,9 @@ class Graph:
 
     def set_option(self, name, value):
         """one run-time switch of this optimiser: "flatten_reuse", "structure_reuse", "init_timing" (the CUGO_*
-        environment variables are read once, when the optimiser is created)"""
+        environment variables are read once, when the optimiser is created), and "pose_edge_outliers" (1: outlier
+        thresholds on plane / line / prior / relative-pose sets are taken, GraphOptimisationOptions::
+        poseEdgeOutlierRejection; off by default; takes effect at the next initialize())"""
         check(lib().cugo_graph_set_option(self._g, name.encode(), int(value)))
 
     def flatten_reuses(self):

@@ -323,6 +323,33 @@ int cugo_prior_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_prior_ed
     });
 }
 
+int cugo_pose_edges_reject(cugo_ctx* ctx, int n, const double* d_edge_chi, const double* d_threshold, int n_threshold,
+                           uint8_t* d_flags, int32_t* d_rejected, int* n_rejected)
+{
+    return guarded([&] {
+        if (!ctx || !n_rejected || n < 0)
+            throw std::runtime_error("cugo_pose_edges_reject: no context, no count or a negative edge count");
+        *n_rejected = 0;
+        if (n == 0)
+            return;
+        if (n > (1 << 26))
+            throw std::runtime_error("cugo_pose_edges_reject: more than 2^26 edges");
+        if (!d_edge_chi || !d_threshold || !d_flags || !d_rejected)
+            throw std::runtime_error("cugo_pose_edges_reject: missing arrays");
+        if (n_threshold != 1 && n_threshold != n)
+            throw std::runtime_error("cugo_pose_edges_reject: n_threshold must be 1 or n");
+        // (the counts of the workgroups live in the context's scratch, as ints)
+        const cugo_k::ReduceScratch rs = pose_scratch_for(ctx, (cugo_k::pose_reject_work_ints(n) + 1) / 2);
+        const int32_t* d_count = cugo_k::launch_pose_reject(ctx->stream, n, d_edge_chi, d_threshold, n_threshold == n && n > 1,
+                                                            d_flags, d_rejected, reinterpret_cast<int32_t*>(rs.d_partials));
+        CUGO_HIP(hipGetLastError());
+        int32_t count = 0;
+        CUGO_HIP(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+        CUGO_HIP(hipStreamSynchronize(ctx->stream));
+        *n_rejected = count;
+    });
+}
+
 } // extern "C"
 
 // the plan of a set of relative-pose edges: the host plan (relpose_plan.h) and, with a context, its copy on the device
@@ -1113,6 +1140,43 @@ int cugo_graph_get_edge_active(cugo_graph* g, int dim, int n, uint8_t* active)
         else
             for (int i = 0; i < n && i < (int)g->mono_store.size(); i++)
                 active[i] = g->mono_store[i].isActive() ? 1 : 0;
+    });
+}
+static cugo::BaseEdgeSet* pose_kind_set(cugo_graph* g, int kind)
+{
+    if (!g)
+        throw std::invalid_argument("cugo: null graph");
+    switch (kind)
+    {
+    case CUGO_POSE_KIND_PLANE: return &g->plane;
+    case CUGO_POSE_KIND_LINE: return &g->line;
+    case CUGO_POSE_KIND_PRIOR: return &g->prior;
+    case CUGO_POSE_KIND_RELPOSE: return &g->relpose;
+    }
+    throw std::invalid_argument("cugo: kind must be one of CUGO_POSE_KIND_PLANE (0), _LINE (1), _PRIOR (2), _RELPOSE (3)");
+}
+int cugo_graph_n_pose_edge_outliers(cugo_graph* g, int kind)
+{
+    int n = -1;
+    const int rc = guarded([&] { n = (int)pose_kind_set(g, kind)->getOutlierCount(); });
+    return rc == CUGO_OK ? n : rc;
+}
+int cugo_graph_get_pose_edge_active(cugo_graph* g, int kind, int n, uint8_t* active)
+{
+    return guarded([&] {
+        (void)pose_kind_set(g, kind);
+        if (n < 0 || (n > 0 && !active))
+            throw std::invalid_argument("cugo_graph_get_pose_edge_active: bad count or no array");
+        auto fill = [&](const auto& store) {
+            if ((size_t)n > store.size())
+                throw std::invalid_argument("cugo_graph_get_pose_edge_active: the set holds fewer edges");
+            for (int i = 0; i < n; i++)
+                active[i] = store[(size_t)i].isActive() ? 1 : 0;
+        };
+        kind == CUGO_POSE_KIND_PLANE  ? fill(g->plane_store)
+        : kind == CUGO_POSE_KIND_LINE ? fill(g->line_store)
+        : kind == CUGO_POSE_KIND_PRIOR ? fill(g->prior_store)
+                                       : fill(g->relpose_store);
     });
 }
 int cugo_graph_set_shard(cugo_graph* g, int rank, int world, cugo_exchange_fn fn, void* user)

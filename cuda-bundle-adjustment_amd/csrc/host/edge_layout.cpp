@@ -396,6 +396,8 @@ void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHo
     b.h_weight.assign((size_t)ww * b.n_weight, 0.0);
     if (!per_edge)
         std::copy(fk.weight.begin(), fk.weight.end(), b.h_weight.begin());
+    const bool per_edge_threshold = fk.threshold.size() > 1;
+    b.h_threshold = fk.threshold; // (empty or one entry: as it is)
     std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1);
     for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
     {
@@ -407,6 +409,8 @@ void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHo
         if (per_edge)
             for (int c = 0; c < ww; c++)
                 b.h_weight[(size_t)c * n + i] = fk.weight[(size_t)ww * e + c];
+        if (per_edge_threshold)
+            b.h_threshold[i] = fk.threshold[e];
     }
 }
 

@@ -66,6 +66,7 @@ struct PoseKindHost
     Idx h_pose, h_ptr, slot_set, slot_edge;
     std::vector<double> h_meas, h_weight;
     int n_weight = 1;
+    std::vector<double> h_threshold; // FlatPoseKind::threshold in the sorted order (n entries, 1, or empty)
 };
 void sort_pose_edges_by_pose(const FlatPoseKind& kind, int Pall, int P, PoseKindHost& out);
 

@@ -181,6 +181,7 @@ struct Engine::Impl : cugo_k::LaunchHook
         struct RelPose
         {
             std::vector<int32_t> h_pose_a, h_pose_b;
+            std::vector<int32_t> src_set, src_edge; // FlatRelPose's: where an edge came from
             std::vector<double> h_meas, h_info; // planar [7][n], [21][n_info]
             DevBuf<int32_t> d_pose_a, d_pose_b, d_inc_ptr, d_inc, d_off_blk;
             DevBuf<double> d_meas, d_info;
@@ -190,6 +191,44 @@ struct Engine::Impl : cugo_k::LaunchHook
         } rp;
         cugo_relpose_edges relpose{};
         int n_relpose = 0, n_relpose_wg = 0; // edges; totals a relative-pose pass leaves (0: never launched)
+        // Outlier rejection (Engine::reject_pose_outliers), per kind (PoseKind, then the relative-pose edges) and only
+        // for a kind in which some threshold is positive: the run-time flags the kind's view points at (all zero until
+        // edges go), a host copy of them, and the thresholds in the order of the edges on the device (n or 1).  Every
+        // other kind keeps a NULL flag pointer in its view and queues what it always queued.
+        static constexpr int REJ_RELPOSE = POSE_KIND_COUNT, REJ_KINDS = POSE_KIND_COUNT + 1;
+        struct Reject
+        {
+            DevBuf<uint8_t> d_flags;
+            std::vector<uint8_t> h_flags;
+            DevBuf<double> d_threshold;
+            int n_threshold = 0; // 0: the kind has no threshold
+            bool on() const { return n_threshold > 0; }
+        } rej[REJ_KINDS];
+        DevBuf<double> d_rej_chi;              // the chi2 term of every edge of the kind(s) at hand
+        DevBuf<int32_t> d_rej_list, d_rej_work; // the outlier pass's list and its workgroup counts
+        bool any_reject() const
+        {
+            bool any = false;
+            for (const Reject& r : rej)
+                any = any || r.on();
+            return any;
+        }
+        // flags and thresholds of kind k over its n edges: nullptr (and nothing allocated) without a positive threshold
+        const uint8_t* bind_reject(int k, int n, const std::vector<double>& threshold, hipStream_t stream, bool plan_only)
+        {
+            Reject& r = rej[k];
+            r.n_threshold = 0;
+            r.h_flags.clear();
+            if (!n || threshold.empty())
+                return nullptr;
+            r.n_threshold = (int)threshold.size();
+            r.h_flags.assign((size_t)n, 0);
+            if (plan_only)
+                return nullptr;
+            r.d_flags.resize((size_t)n), r.d_flags.zero(stream);
+            r.d_threshold.upload(threshold, stream);
+            return r.d_flags.data();
+        }
         double* relpose_chi() { return d_scratch.data() + off_relpose_chi; }
 
         cugo_k::ReduceScratch icp_rs() { return {d_scratch.data(), d_scratch.size()}; }
@@ -232,11 +271,14 @@ struct Engine::Impl : cugo_k::LaunchHook
             icp.d_line_p = li.d_meas.data(), icp.d_line_au = li.d_meas.data() + 3 * (size_t)icp.n_line;
             icp.d_line_omega = li.d_weight.data(), icp.n_line_omega = li.n_weight;
             icp.rk_line = g.kinds[POSE_KIND_LINE].rk, icp.delta_line = g.kinds[POSE_KIND_LINE].delta;
+            icp.d_plane_flags = bind_reject(POSE_KIND_PLANE, icp.n_plane, pl.h_threshold, stream, plan_only);
+            icp.d_line_flags = bind_reject(POSE_KIND_LINE, icp.n_line, li.h_threshold, stream, plan_only);
             prior = cugo_prior_edges{};
             prior.n_poses_total = Pall, prior.n_poses_free = P, prior.n = n_prior;
             prior.d_pose = pr.d_pose.data(), prior.d_pose_ptr = pr.d_ptr.data();
             prior.d_meas = pr.d_meas.data(), prior.d_info = pr.d_weight.data(), prior.n_info = pr.n_weight;
             prior.rk = g.kinds[POSE_KIND_PRIOR].rk, prior.delta = g.kinds[POSE_KIND_PRIOR].delta;
+            prior.d_flags = bind_reject(POSE_KIND_PRIOR, n_prior, pr.h_threshold, stream, plan_only);
             // the scratch layout (the chunk totals end the ICP part)
             const size_t icp_doubles = n_icp ? cugo_k::icp_scratch_doubles(icp) : 0;
             n_icp_chi = n_icp ? cugo_k::icp_chunk_count(icp) : 0;
@@ -257,11 +299,14 @@ struct Engine::Impl : cugo_k::LaunchHook
             relpose.n_poses_total = Pall, relpose.n_poses_free = P, relpose.n = n;
             relpose.rk = fr.rk, relpose.delta = fr.delta;
             n_relpose_wg = cugo_k::relpose_workgroups(relpose);
+            // (run-time flags: the plan is still built with none, and an edge flagged here "counts for nothing")
+            relpose.d_flags = bind_reject(REJ_RELPOSE, n, fr.threshold, stream, plan_only);
             if (!n)
                 return;
             if (n > (1 << 26))
                 throw std::runtime_error("cugo: more than 2^26 relative-pose edges");
             rp.h_pose_a = fr.pose_a, rp.h_pose_b = fr.pose_b;
+            rp.src_set = fr.src_set, rp.src_edge = fr.src_edge;
             const int n_info = fr.weight.size() > 21 ? n : 1;
             rp.h_meas.resize(7 * (size_t)n), rp.h_info.resize(21 * (size_t)n_info);
             for (int e = 0; e < n; e++)
@@ -1788,6 +1833,74 @@ std::vector<int32_t> Engine::reject_outliers()
         m.structure_dirty = true;
         E_global_ -= (int)out.size();
     }
+    return out;
+}
+
+std::vector<Engine::PoseOutliers> Engine::reject_pose_outliers()
+{
+    Impl& m = *impl_;
+    Impl::PoseEdges& pe = m.pe;
+    std::vector<PoseOutliers> out(Impl::PoseEdges::REJ_KINDS);
+    if (m.plan_only || !pe.any_reject())
+        return out;
+    hipStream_t s = m.ctx.stream;
+    const double* poses = m.d_poses[m.last_err_buf].data(); // (the estimates the BA path judges at)
+    // the outlier pass over the n edges of kind k whose chi2 terms are at d_chi, and the way back to the edge sets
+    // through set_of / edge_of (the kind's order on the device)
+    auto reject = [&](int k, int n, const double* d_chi, const std::vector<int32_t>& set_of, const std::vector<int32_t>& edge_of) {
+        Impl::PoseEdges::Reject& r = pe.rej[k];
+        pe.d_rej_list.resize((size_t)n), pe.d_rej_work.resize(cugo_k::pose_reject_work_ints(n));
+        const int32_t* d_count = cugo_k::launch_pose_reject(s, n, d_chi, r.d_threshold.data(), r.n_threshold > 1,
+                                                            r.d_flags.data(), pe.d_rej_list.data(), pe.d_rej_work.data());
+        int32_t count = 0;
+        CUGO_HIP(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, s));
+        CUGO_HIP(hipStreamSynchronize(s));
+        if (count <= 0)
+            return;
+        std::vector<int32_t> list((size_t)count);
+        CUGO_HIP(hipMemcpyAsync(list.data(), pe.d_rej_list.data(), sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, s));
+        CUGO_HIP(hipStreamSynchronize(s));
+        for (int32_t e : list)
+        {
+            r.h_flags[(size_t)e] |= CUGO_EDGE_INACTIVE;
+            out[k].emplace_back(set_of[(size_t)e], edge_of[(size_t)e]);
+        }
+        std::sort(out[k].begin(), out[k].end());
+    };
+    m.timed("pose_outliers", [&] {
+        // The error passes below overwrite the chi2 totals in the pose-edge scratch (and the ICP partials).  Nothing
+        // reads them afterwards: every optimize() starts from a fresh LmState (no speculative pass is pending) with a
+        // build pass that writes partials and totals anew, flags included.
+        const int n_plane = pe.icp.n_plane, n_line = pe.icp.n_line;
+        if (pe.rej[POSE_KIND_PLANE].on() || pe.rej[POSE_KIND_LINE].on())
+        { // (plane edges first, then the line edges)
+            pe.d_rej_chi.resize((size_t)n_plane + n_line);
+            pe.d_rej_chi.zero(s);
+            cugo_k::launch_icp_chunks(s, pe.icp, poses, false, pe.icp_rs(), pe.d_rej_chi.data());
+            for (int k : {POSE_KIND_PLANE, POSE_KIND_LINE})
+                if (pe.rej[k].on())
+                    reject(k, k == POSE_KIND_PLANE ? n_plane : n_line, pe.d_rej_chi.data() + (k == POSE_KIND_PLANE ? 0 : n_plane),
+                           pe.kind[k].slot_set, pe.kind[k].slot_edge);
+        }
+        if (pe.rej[POSE_KIND_PRIOR].on())
+        {
+            pe.d_rej_chi.resize((size_t)pe.n_prior);
+            pe.d_rej_chi.zero(s);
+            cugo_k::launch_prior_errors(s, pe.prior, poses, pe.prior_chi(), pe.d_rej_chi.data());
+            reject(POSE_KIND_PRIOR, pe.n_prior, pe.d_rej_chi.data(), pe.kind[POSE_KIND_PRIOR].slot_set,
+                   pe.kind[POSE_KIND_PRIOR].slot_edge);
+        }
+        if (pe.rej[Impl::PoseEdges::REJ_RELPOSE].on() && pe.n_relpose_wg)
+        { // (the pass writes only the edges that count: the rest stay 0)
+            pe.d_rej_chi.resize((size_t)pe.n_relpose);
+            pe.d_rej_chi.zero(s);
+            cugo_k::launch_relpose_errors(s, pe.relpose, pe.rp.dev, poses, pe.relpose_chi(), pe.d_rej_chi.data());
+            reject(Impl::PoseEdges::REJ_RELPOSE, pe.n_relpose, pe.d_rej_chi.data(), pe.rp.src_set, pe.rp.src_edge);
+        }
+    });
+    m.collect_times();
+    for (const PoseOutliers& k : out)
+        E_global_ -= (int)k.size();
     return out;
 }
 

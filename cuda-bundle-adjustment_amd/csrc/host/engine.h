@@ -37,13 +37,15 @@ struct FlatPoseKind
     std::vector<double> weight;   // E x weight_w, or 1 x weight_w when one value serves all
     std::vector<int32_t> src_set, src_edge; // where an edge came from: edge set (position among the optimiser's edge
                                             // sets) and position in that set's container
+    std::vector<double> threshold; // outlier threshold of the edge's set (> 0, or 0: none), per edge; one entry when one
+                                   // value serves all, empty when no set has one (collapse_thresholds)
     int rk = CUGO_RK_NONE;
     double delta = 1.0;
     bool rk_seen = false; // a non-empty edge set has settled rk / delta (further sets must agree)
     int n() const { return (int)pose.size(); }
     void clear()
     {
-        pose.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear();
+        pose.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear(), threshold.clear();
         rk = CUGO_RK_NONE, delta = 1.0, rk_seen = false;
     }
 };
@@ -66,16 +68,29 @@ struct FlatRelPose
     std::vector<double> meas;            // E x 7 (q x y z w, t) of Z ~ T_a T_b^-1
     std::vector<double> weight;          // E x 21 (upper triangle of Omega, row-major packed), or 1 x 21
     std::vector<int32_t> src_set, src_edge;
+    std::vector<double> threshold; // as FlatPoseKind::threshold
     int rk = CUGO_RK_NONE;
     double delta = 1.0;
     bool rk_seen = false;
     int n() const { return (int)pose_a.size(); }
     void clear()
     {
-        pose_a.clear(), pose_b.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear();
+        pose_a.clear(), pose_b.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear(), threshold.clear();
         rk = CUGO_RK_NONE, delta = 1.0, rk_seen = false;
     }
 };
+
+// per-edge thresholds as flattened -> empty when none is positive, one entry when all are the same
+inline void collapse_thresholds(std::vector<double>& t)
+{
+    bool uniform = true, any = false;
+    for (size_t i = 0; i < t.size(); i++)
+        uniform = uniform && t[i] == t[0], any = any || t[i] > 0.0;
+    if (!any)
+        t.clear();
+    else if (uniform)
+        t.resize(1);
+}
 
 struct FlatGraph
 {
@@ -187,6 +202,14 @@ public:
     // pass exceeds their set's threshold become inactive.  Returns their indices in the order of
     // the FlatGraph passed to initialize() (all ranks return the same list).
     std::vector<int32_t> reject_outliers();
+    // The same on the pose edge kinds that carry a threshold (FlatPoseKind::threshold, FlatRelPose::threshold), at the
+    // same estimates: one error pass with the chi2 term of every edge and the outlier pass (cugo_pose_edges_reject) per
+    // such kind, all on the device; the flags stay there, so a further optimize() on the same initialisation runs
+    // without the edges.  Returns, per kind (PoseKind, then the relative-pose edges), the {edge set, position in the
+    // set} of every edge that went, ascending.  The Hsc pattern is left as it is (a pair that lost its last edge keeps
+    // an empty block until the next flattening), and n_*_edges() keep describing the flattening.
+    using PoseOutliers = std::vector<std::pair<int32_t, int32_t>>;
+    std::vector<PoseOutliers> reject_pose_outliers();
     // Extension: marginal covariances at the current estimates (include/cugo_hip.h, cugo_graph_compute_covariances).
     // Builds J^T Omega J at lambda = 0, its Schur complement and factorisation, runs the selected inverse and, for
     // what & 2, the landmark blocks; keeps the diagonal blocks (cov_pose [P][36], cov_lm [L][9], column-major) on the

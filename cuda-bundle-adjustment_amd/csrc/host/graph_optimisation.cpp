@@ -97,6 +97,8 @@ bool CudaGraphOptimisationImpl::setOption(const char* name, int value)
         o.structure_reuse = value != 0;
     else if (n == "init_timing")
         o.init_timing = value != 0;
+    else if (n == "pose_edge_outliers") // (an option of the graph, not of the engine: compared by the next initialize())
+        options.poseEdgeOutlierRejection = value != 0;
     else
         return false;
     return true;
@@ -190,13 +192,15 @@ static const char* checkInformation36(const double* A)
     return nullptr;
 }
 
-// What the pose edge kinds, unary and binary, share per set: no outlier threshold, one robust kernel per kind (rk, delta,
-// rk_seen: the kind's record), check_set()
+// What the pose edge kinds, unary and binary, share per set: the outlier threshold (refused unless
+// GraphOptimisationOptions::poseEdgeOutlierRejection is on; returned: finite and > 0, or 0 = no rejection on this set), one
+// robust kernel per kind (rk, delta, rk_seen: the kind's record), check_set()
 template <class CheckSet>
-static void settlePoseEdgeSet(BaseEdgeSet* es, int setIndex, const std::string& name, int& out_rk, double& out_delta,
-                              bool& out_rk_seen, CheckSet check_set)
+static double settlePoseEdgeSet(BaseEdgeSet* es, int setIndex, const std::string& name, bool rejection, int& out_rk,
+                                double& out_delta, bool& out_rk_seen, CheckSet check_set)
 {
-    if (es->getOutlierThreshold() > 0.0)
+    const double set_threshold = es->getOutlierThreshold();
+    if (set_threshold > 0.0 && !rejection)
         throw std::runtime_error("cugo: outlier rejection is not available on " + name +
                                  " edge sets yet (setOutlierThreshold must stay 0)");
     const RobustKernel& k = es->robustKernelData();
@@ -214,6 +218,7 @@ static void settlePoseEdgeSet(BaseEdgeSet* es, int setIndex, const std::string& 
             throw std::runtime_error("cugo: " + name + " edge set " + std::to_string(setIndex) + ": " + bad);
     }
     es->setOutlierCount(0);
+    return std::isfinite(set_threshold) && set_threshold > 0.0 ? set_threshold : 0.0;
 }
 // v is a pose vertex of one of the optimiser's pose vertex sets
 static bool knownPoseVertex(const BaseVertex* v, const std::vector<BaseVertexSet*>& vertexSets)
@@ -234,10 +239,13 @@ static bool knownPoseVertex(const BaseVertex* v, const std::vector<BaseVertexSet
 // what is wrong with a non-empty set as a whole, or nullptr.
 template <class Payload, class CheckSet>
 static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, const char* kind, const std::vector<BaseVertexSet*>& vertexSets,
-                               cugo_host::FlatPoseKind& out, Payload payload, CheckSet check_set)
+                               bool rejection, cugo_host::FlatPoseKind& out, std::vector<BaseEdge*>& setEdges, Payload payload,
+                               CheckSet check_set)
 {
     const std::string name = kind;
-    settlePoseEdgeSet(es, setIndex, name, out.rk, out.delta, out.rk_seen, check_set);
+    const double threshold = settlePoseEdgeSet(es, setIndex, name, rejection, out.rk, out.delta, out.rk_seen, check_set);
+    if (threshold > 0.0) // (a set that can lose edges: where its flattened edges are, by position in the container)
+        setEdges.assign(es->nedges(), nullptr);
     size_t i = 0, kept = 0;
     for (BaseEdge* e : es->get())
     {
@@ -259,6 +267,9 @@ static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, const char* kind, 
         out.meas.insert(out.meas.end(), meas, meas + out.meas_w);
         out.weight.insert(out.weight.end(), weight, weight + out.weight_w);
         out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
+        out.threshold.push_back(threshold);
+        if (threshold > 0.0)
+            setEdges[at] = e;
         kept++;
     }
     es->setActiveEdgeCount(kept);
@@ -335,12 +346,16 @@ static void priorPayload(BaseEdge* e, const double* setInformation, Refuse& refu
 // flattenPoseEdgeSet.  The measurement and Omega are the prior's (priorPayload checks them).  Refused: a == b, an end in
 // no pose vertex set of the optimiser; dropped: inactive edges and edges between two fixed poses.
 static void flattenRelPoseEdgeSet(RelPoseEdgeSet* es, int setIndex, bool perEdgeInformation,
-                                  const std::vector<BaseVertexSet*>& vertexSets, cugo_host::FlatRelPose& out)
+                                  const std::vector<BaseVertexSet*>& vertexSets, bool rejection, cugo_host::FlatRelPose& out,
+                                  std::vector<BaseEdge*>& setEdges)
 {
     const std::string name = "relative-pose";
     const double* setInformation = perEdgeInformation ? nullptr : es->informationMatrix();
-    settlePoseEdgeSet(es, setIndex, name, out.rk, out.delta, out.rk_seen,
-                      [&] { return setInformation ? checkInformation36(setInformation) : nullptr; });
+    const double threshold =
+        settlePoseEdgeSet(es, setIndex, name, rejection, out.rk, out.delta, out.rk_seen,
+                          [&] { return setInformation ? checkInformation36(setInformation) : nullptr; });
+    if (threshold > 0.0)
+        setEdges.assign(es->nedges(), nullptr);
     size_t i = 0, kept = 0;
     for (BaseEdge* e : es->get())
     {
@@ -364,6 +379,9 @@ static void flattenRelPoseEdgeSet(RelPoseEdgeSet* es, int setIndex, bool perEdge
         out.meas.insert(out.meas.end(), meas, meas + 7);
         out.weight.insert(out.weight.end(), weight, weight + 21);
         out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
+        out.threshold.push_back(threshold);
+        if (threshold > 0.0)
+            setEdges[at] = e;
         kept++;
     }
     es->setActiveEdgeCount(kept);
@@ -401,6 +419,7 @@ void CudaGraphOptimisationImpl::initialize()
         bool same = flattenValid_ && eopt.flatten_reuse && eopt.structure_reuse &&
                     flattenOptions_[0] == options.perEdgeInformation && flattenOptions_[1] == options.perEdgeCamera &&
                     flattenOptions_[2] == options.useFloat32 && flattenOptions_[3] == options.relativePoseEdges &&
+                    flattenOptions_[4] == options.poseEdgeOutlierRejection &&
                     flattenCounts_.size() == vertexSets.size() + edgeSets.size();
         size_t q = 0;
         for (size_t i = 0; same && i < vertexSets.size(); i++, q++)
@@ -481,6 +500,8 @@ void CudaGraphOptimisationImpl::initialize()
     for (cugo_host::FlatPoseKind& fk : g.kinds)
         fk.clear();
     g.relpose.clear();
+    poseSetEdges_.assign(edgeSets.size(), {});
+    const bool rejection = options.poseEdgeOutlierRejection;
     g.e_pose.resize(cap), g.e_lm.resize(cap), g.e_flags.resize(cap);
     g.e_meas.resize(3 * cap), g.e_omega.resize(cap), g.e_cam.resize(cap);
     g.e_outlier_threshold.resize(cap);
@@ -509,7 +530,7 @@ void CudaGraphOptimisationImpl::initialize()
             const int kind = line ? cugo_host::POSE_KIND_LINE : cugo_host::POSE_KIND_PLANE;
             const bool perInfo = options.perEdgeInformation;
             flattenPoseEdgeSet(
-                es, (int)si, cugo_host::pose_kind_name(kind), vertexSets, g.kinds[kind],
+                es, (int)si, cugo_host::pose_kind_name(kind), vertexSets, rejection, g.kinds[kind], poseSetEdges_[si],
                 [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
                     icpInformation(es, e, perInfo, refuse, weight);
                     line ? linePayload(e, refuse, meas) : planePayload(e, refuse, meas);
@@ -523,7 +544,7 @@ void CudaGraphOptimisationImpl::initialize()
                 throw std::runtime_error("cugo: the optimiser does not take relative-pose edge sets unless "
                                          "GraphOptimisationOptions::relativePoseEdges is on "
                                          "(their terms alone: cugo_relpose_* in include/cugo_hip.h)");
-            flattenRelPoseEdgeSet(rs, (int)si, options.perEdgeInformation, vertexSets, g.relpose);
+            flattenRelPoseEdgeSet(rs, (int)si, options.perEdgeInformation, vertexSets, rejection, g.relpose, poseSetEdges_[si]);
             continue;
         }
         if (dim == 6)
@@ -533,8 +554,8 @@ void CudaGraphOptimisationImpl::initialize()
                 throw std::runtime_error("cugo: a 6-d edge set must be a PosePriorEdgeSet (prior_types.h)");
             const double* setInformation = options.perEdgeInformation ? nullptr : ps->informationMatrix();
             flattenPoseEdgeSet(
-                es, (int)si, cugo_host::pose_kind_name(cugo_host::POSE_KIND_PRIOR), vertexSets,
-                g.kinds[cugo_host::POSE_KIND_PRIOR],
+                es, (int)si, cugo_host::pose_kind_name(cugo_host::POSE_KIND_PRIOR), vertexSets, rejection,
+                g.kinds[cugo_host::POSE_KIND_PRIOR], poseSetEdges_[si],
                 [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
                     priorPayload(e, setInformation, refuse, meas, weight);
                 },
@@ -711,6 +732,7 @@ void CudaGraphOptimisationImpl::initialize()
             uniform = fk.weight[i] == fk.weight[i % fk.weight_w];
         if (uniform)
             fk.weight.resize(fk.weight_w);
+        cugo_host::collapse_thresholds(fk.threshold);
     }
     {
         std::vector<double>& w = g.relpose.weight;
@@ -719,6 +741,7 @@ void CudaGraphOptimisationImpl::initialize()
             uniform = w[i] == w[i % 21];
         if (uniform)
             w.resize(21);
+        cugo_host::collapse_thresholds(g.relpose.threshold);
     }
     lap("graph: edge flatten");
 
@@ -734,6 +757,7 @@ void CudaGraphOptimisationImpl::initialize()
         flattenCounts_.emplace_back(es, es->changeCount());
     flattenOptions_[0] = options.perEdgeInformation, flattenOptions_[1] = options.perEdgeCamera;
     flattenOptions_[2] = options.useFloat32, flattenOptions_[3] = options.relativePoseEdges;
+    flattenOptions_[4] = options.poseEdgeOutlierRejection;
     flattenValid_ = true;
     initialized_ = true;
 }
@@ -774,6 +798,16 @@ void CudaGraphOptimisationImpl::optimize(int niterations)
         es->setOutlierCount(es->getOutlierCount() + 1);
         es->setDirtyState(true);
     }
+    // the same on the pose edge sets (GraphOptimisationOptions::poseEdgeOutlierRejection): the engine has flagged them
+    // on the device and hands back where each came from
+    for (const auto& kind : engine_->reject_pose_outliers())
+        for (const auto& se : kind)
+        {
+            BaseEdgeSet* es = edgeSets[se.first];
+            poseSetEdges_[se.first][se.second]->inactivate();
+            es->setOutlierCount(es->getOutlierCount() + 1);
+            es->setDirtyState(true);
+        }
     // ref: finalize(): estimates go back into the user's vertex objects
     const double *hp = nullptr, *hl = nullptr;
     if (!engine_->download_pinned(&hp, &hl))

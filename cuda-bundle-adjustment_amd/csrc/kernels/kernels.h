@@ -157,6 +157,16 @@ struct PoseIndexCheck
     const char* label;
 };
 int pose_check_indices(hipStream_t s, const char* who, const PoseIndexCheck* kinds, int n_kinds, int n_poses_total, int* d_bad);
+// Outlier pass of the four pose edge kinds (include/cugo_hip.h: cugo_pose_edges_reject): edge e goes iff it is not
+// flagged CUGO_EDGE_INACTIVE, its threshold (d_threshold[per_edge ? e : 0]) is > 0 and d_edge_chi[e] > threshold.  Its
+// flag byte gains the bit and d_rejected receives the indices, ascending.  Three launches (count, scan, place) and no
+// synchronisation; d_work: pose_reject_work_ints(n) ints of scratch.  Returns the device address of the count (inside
+// d_work), or nullptr when nothing was launched (n == 0).  A workgroup walks a contiguous run of edges; beyond
+// pose_reject_grid_cap() workgroups of 256 edges each walks several tiles.
+size_t pose_reject_work_ints(int n);
+int pose_reject_grid_cap();
+const int32_t* launch_pose_reject(hipStream_t s, int n, const double* d_edge_chi, const double* d_threshold, bool per_edge,
+                                  uint8_t* d_flags, int32_t* d_rejected, int32_t* d_work);
 
 // --- point-to-plane / point-to-line pose edges (icp_kernels.hip) -------------------------
 // scratch the launchers need (chunk partials, then one chi2 total per chunk at its end)

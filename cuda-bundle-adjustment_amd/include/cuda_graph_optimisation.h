@@ -158,7 +158,9 @@ public:
     int flattenReuses() const { return flattenReuses_; }
     bool useFloat32() const { return options.useFloat32; }
     /** a run-time switch of this optimiser ("flatten_reuse", "structure_reuse", "init_timing"; the optimiser took a
-     *  snapshot of the CUGO_* environment variables when it was created); false: unknown name */
+     *  snapshot of the CUGO_* environment variables when it was created), or "pose_edge_outliers"
+     *  (GraphOptimisationOptions::poseEdgeOutlierRejection after construction; takes effect at the next
+     *  initialize()); false: unknown name */
     bool setOption(const char* name, int value);
     /** marginal covariances at the current estimates (g2o SparseOptimizer::computeMarginals, Ceres Covariance):
      *  Sigma = H^-1 of the undamped J^T Omega J (robust weights included) over the free vertices, diagonal blocks
@@ -186,7 +188,7 @@ private:
     // change counts of the sets at the last full flattening (initialize() refreshes only the
     // estimates while they stand)
     std::vector<std::pair<const void*, unsigned long long>> flattenCounts_;
-    bool flattenOptions_[4] = {false, false, false, false};
+    bool flattenOptions_[5] = {false, false, false, false, false};
     bool flattenValid_ = false;
     bool initialized_ = false; // initialize() ran (computeMarginals needs it)
     bool flattenedUnchanged(const BaseVertexSet* vs) const;
@@ -194,6 +196,9 @@ private:
     // edges handed to the engine at initialize(), in that order (outlier rejection maps back)
     std::vector<BaseEdge*> flatEdges_;
     std::vector<BaseEdgeSet*> flatEdgeSets_;
+    // the same for the pose edge sets that carry an outlier threshold: per edge set (position in edgeSets), the
+    // flattened edge at every position of its container (nullptr: not flattened); empty for every other set
+    std::vector<std::vector<BaseEdge*>> poseSetEdges_;
     std::vector<double> downloadPoses_, downloadLms_; // staging of the estimates that optimize() writes back
 };
 

@@ -153,6 +153,13 @@ struct CUGO_API GraphOptimisationOptions
     // initialize() refuses such a set, as before the optimiser could take it.  On: the set is flattened and checked,
     // its pose pairs join the Hsc pattern and optimize() minimises the joint cost.
     bool relativePoseEdges = false;
+    // Extension to the extension sets, the reference's behaviour on its own PlaneEdgeSet / LineEdgeSet: outlier
+    // rejection on point-to-plane, point-to-line, pose prior and relative-pose edge sets (ref: EdgeSet::
+    // setOutlierThreshold / updateEdges, optimisable_graph.hpp:415, 603-640).  Off (the default): initialize() refuses a
+    // positive threshold on such a set, as before.  On: at the end of optimize() every edge of such a set whose chi2
+    // term exceeds the set's threshold (finite and > 0; anything else disables) is inactivated, counted in the set's
+    // getOutlierCount() and left out by the next initialize().
+    bool poseEdgeOutlierRejection = false;
 };
 
 enum class RobustKernelType

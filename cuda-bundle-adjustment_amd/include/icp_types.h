@@ -6,7 +6,11 @@
 // The residuals, their Jacobians for the left update and the device kernels are in csrc/kernels/icp_kernels.hip.
 // The sets are plain containers, like the BA sets (ba_types.h): add them to the optimiser with addEdgeSet(), next to
 // (or instead of) mono / stereo sets; initialize() checks every active edge (finite values, unit normal, a != b, a pose
-// of one of the optimiser's pose sets) and optimize() minimises the joint cost.  The same terms are also reachable
+// of one of the optimiser's pose sets) and optimize() minimises the joint cost.  setOutlierThreshold(t > 0) on a set
+// (ref: EdgeSet::setOutlierThreshold / updateEdges, which the reference's sets inherit) takes effect with
+// GraphOptimisationOptions::poseEdgeOutlierRejection: at the end of optimize() every edge of the set whose chi2 term
+// exceeds t is inactivated and counted in getOutlierCount(); several sets of a kind may carry different thresholds.
+// With the option off (the default) such a threshold is refused by initialize().  The same terms are also reachable
 // through the kernel-level C ABI (include/cugo_hip.h: cugo_icp_edges, cugo_icp_compute_errors,
 // cugo_icp_construct_quadratic_form).
 #pragma once

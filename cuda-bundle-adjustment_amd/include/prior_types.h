@@ -11,7 +11,9 @@
 // like the BA and ICP sets: add it with addEdgeSet() next to (or instead of) the others; initialize() recognises it by
 // type, checks every active edge (finite values, |q_z| = 1 to 1e-6, Omega symmetric to 1e-12 max|Omega| and positive
 // semi-definite to -1e-12 lambda_max, a pose of one of the optimiser's pose sets) and optimize() minimises the joint
-// cost.  Outlier thresholds on the set and sharded optimisers are refused.  Also reachable through the kernel-level C
+// cost.  setOutlierThreshold(t > 0) on the set takes effect with GraphOptimisationOptions::poseEdgeOutlierRejection: at
+// the end of optimize() every prior whose chi2 term exceeds t is inactivated and counted in getOutlierCount(); with the
+// option off (the default) such a threshold is refused.  Sharded optimisers are refused.  Also reachable through the kernel-level C
 // ABI (include/cugo_hip.h: cugo_prior_edges, cugo_prior_compute_errors, cugo_prior_construct_quadratic_form).
 #pragma once
 #include <algorithm>

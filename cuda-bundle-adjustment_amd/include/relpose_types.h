@@ -17,7 +17,11 @@
 // type, checks every active edge (finite values, |q_z| = 1 to 1e-6, Omega symmetric to 1e-12 max|Omega| and positive
 // semi-definite to -1e-12 lambda_max, a != b, both ends in pose sets of the optimiser), merges the pose pairs into the
 // Hsc pattern and optimize() minimises the joint cost; inactive edges and edges between two fixed poses are dropped.
-// Outlier thresholds on the set, sets that disagree on the robust kernel and sharded optimisers are refused.  With the
+// setOutlierThreshold(t > 0) on the set — the gate for false loop closures — takes effect with GraphOptimisationOptions::
+// poseEdgeOutlierRejection: at the end of optimize() every edge whose chi2 term exceeds t is inactivated, counted in
+// getOutlierCount() and left out by the next initialize() (a pair that loses its last edge leaves the pattern then);
+// with that option off (the default) such a threshold is refused.  Sets that disagree on the robust kernel and sharded
+// optimisers are refused.  With the relativePoseEdges
 // option off (the default) initialize() refuses the set and names the option and the kernel-level C ABI, through which
 // the terms are reachable as well (include/cugo_hip.h: cugo_relpose_edges, cugo_relpose_plan_create,
 // cugo_relpose_compute_errors, cugo_relpose_construct_quadratic_form[_schur]).

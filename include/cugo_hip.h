@@ -435,6 +435,22 @@ int cugo_relpose_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_relpose
  * Nothing else is written.  Deterministic: no atomics, one summation order. */
 int cugo_relpose_add_offdiag_schur(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses, double* d_Hsc);
 
+/*
+ * Outlier pass of the four pose edge kinds (ref: EdgeSet::updateEdges, optimisable_graph.hpp:603-640), over the chi2
+ * term of every edge as cugo_icp_compute_errors / cugo_prior_compute_errors / cugo_relpose_compute_errors write it.
+ * Edge e becomes an outlier iff !(d_flags[e] & CUGO_EDGE_INACTIVE) && t_e > 0 && d_edge_chi[e] > t_e
+ * (t_e = d_threshold[n_threshold == 1 ? 0 : e]; strict '>', ref: computeOutliersKernel, cuda_block_solver.cu:1145;
+ * a NaN chi2 is therefore kept, +inf goes).  For those edges d_flags[e] |= CUGO_EDGE_INACTIVE; no other bit and no
+ * other byte changes.  d_rejected[0 .. *n_rejected) receives their indices in ASCENDING order; entries behind
+ * them are not written.  One host synchronisation (the count).  n == 0: nothing is launched.
+ * On the device: a count pass, a scan of the workgroups' counts and a place pass, lane per edge; positions come from
+ * ballots and fixed-order integer sums, so two calls on equal inputs give equal bytes (no atomics, no floating-point
+ * arithmetic).  Up to 1024 workgroups of 256 edges; beyond 262144 edges every workgroup walks several runs of 256.
+ * CUGO_ERR_INVALID: a null array with n > 0, n_threshold other than 1 or n, n < 0 or n > 2^26.
+ */
+int cugo_pose_edges_reject(cugo_ctx* ctx, int n, const double* d_edge_chi, const double* d_threshold, int n_threshold,
+                           uint8_t* d_flags, int32_t* d_rejected /* [n] */, int* n_rejected);
+
 /* ---- (2) graph-level entry points ---------------------------------------------------- */
 
 typedef struct cugo_graph cugo_graph; /* CudaGraphOptimisationImpl + its vertex/edge sets */
@@ -467,8 +483,8 @@ int cugo_graph_set_robust_kernel(cugo_graph* g, int dim, int type, double delta)
  * or instead of the BA edges; residuals and conventions as for cugo_icp_edges above.  pointP [n][3]; plane: unit normal
  * [n][3] (used as given) and origin_distance [n]; line: two distinct points a, b [n][3]; info [n] or NULL (the set's
  * value).  pose_ids must be ids given to cugo_graph_add_poses.  cugo_graph_initialize() refuses non-finite values, a
- * normal whose length differs from 1 by more than 1e-6, a == b, an outlier threshold on these sets and a sharded
- * optimiser; edges on fixed poses count for nothing.  The existing setters select a set by dim, which cannot tell the
+ * normal whose length differs from 1 by more than 1e-6, a == b, an outlier threshold on these sets unless the option
+ * "pose_edge_outliers" is on (cugo_graph_set_option) and a sharded optimiser; edges on fixed poses count for nothing.  The existing setters select a set by dim, which cannot tell the
  * two kinds apart (both are 1-d): the two setters below take the kind. */
 #define CUGO_ICP_PLANE 0
 #define CUGO_ICP_LINE 1
@@ -478,8 +494,11 @@ int cugo_graph_add_line_edges(cugo_graph* g, int n, const int32_t* pose_ids, con
                               const double* b, const double* info);
 int cugo_graph_set_icp_information(cugo_graph* g, int kind, double info);
 int cugo_graph_set_icp_robust_kernel(cugo_graph* g, int kind, int type, double delta);
-/* outlier threshold of an ICP set (ref: EdgeSet::setOutlierThreshold).  Only 0 is usable for now: with a positive
- * value cugo_graph_initialize() refuses the graph */
+/* outlier threshold of an ICP set (ref: EdgeSet::setOutlierThreshold).  With cugo_graph_set_option(g,
+ * "pose_edge_outliers", 1): at the end of cugo_graph_optimize every edge of the set whose chi2 term exceeds a finite
+ * threshold > 0 becomes inactive (left out by the next initialize; cugo_graph_n_pose_edge_outliers,
+ * cugo_graph_get_pose_edge_active); any other value disables.  Without the option a positive value makes
+ * cugo_graph_initialize() refuse the graph */
 int cugo_graph_set_icp_outlier_threshold(cugo_graph* g, int kind, double threshold);
 /* active edges of the kind in the current flattening (edges on fixed poses are not counted); -1: unknown kind */
 int cugo_graph_n_icp_edges(cugo_graph* g, int kind);
@@ -490,11 +509,12 @@ int cugo_graph_n_icp_edges(cugo_graph* g, int kind);
  * count when the graph was created with per_edge_information, the set's otherwise.  cugo_graph_initialize() refuses
  * non-finite values, |q_z| off 1 by more than 1e-6, an Omega that is asymmetric beyond 1e-12 max|Omega| or has an
  * eigenvalue below -1e-12 lambda_max (semi-definite is allowed: a translation-only prior), a pose of no pose set of
- * the optimiser, an outlier threshold on the set and a sharded optimiser; edges on fixed poses count for nothing. */
+ * the optimiser, an outlier threshold on the set unless the option "pose_edge_outliers" is on and a sharded optimiser;
+ * edges on fixed poses count for nothing. */
 int cugo_graph_add_pose_priors(cugo_graph* g, int n, const int32_t* pose_ids, const double* q_t7, const double* info36);
 int cugo_graph_set_prior_information(cugo_graph* g, const double* info36);
 int cugo_graph_set_prior_robust_kernel(cugo_graph* g, int type, double delta);
-/* only 0 is usable for now: with a positive value cugo_graph_initialize() refuses the graph */
+/* as cugo_graph_set_icp_outlier_threshold (refused by cugo_graph_initialize() unless "pose_edge_outliers" is on) */
 int cugo_graph_set_prior_outlier_threshold(cugo_graph* g, double threshold);
 /* active priors in the current flattening (priors on fixed poses are not counted) */
 int cugo_graph_n_prior_edges(cugo_graph* g);
@@ -504,14 +524,16 @@ int cugo_graph_n_prior_edges(cugo_graph* g);
  * the set's matrix (cugo_graph_set_relpose_information; the identity until it is set), with the per_edge_information
  * rule of the priors.  The graph object switches GraphOptimisationOptions::relativePoseEdges on itself.
  * cugo_graph_initialize() refuses a == b, a pose of no pose set of the optimiser, non-finite values, |q_z| off 1 by more
- * than 1e-6, an Omega that is asymmetric or indefinite (the bounds of the priors), an outlier threshold on the set and a
- * sharded optimiser; inactive edges and edges between two fixed poses count for nothing, an edge with one fixed end
+ * than 1e-6, an Omega that is asymmetric or indefinite (the bounds of the priors), an outlier threshold on the set unless
+ * the option "pose_edge_outliers" is on and a sharded optimiser; inactive edges and edges between two fixed poses count for nothing, an edge with one fixed end
  * counts in chi2 and adds its free end's terms.  The pose pairs join the Hsc pattern. */
 int cugo_graph_add_relpose_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b,
                                  const double* q_t7, const double* info36);
 int cugo_graph_set_relpose_information(cugo_graph* g, const double* info36);
 int cugo_graph_set_relpose_robust_kernel(cugo_graph* g, int type, double delta);
-/* only 0 is usable for now: with a positive value cugo_graph_initialize() refuses the graph */
+/* as cugo_graph_set_icp_outlier_threshold (refused by cugo_graph_initialize() unless "pose_edge_outliers" is on): the
+ * gate for false loop closures.  A pair whose last edge goes keeps its (then empty) block of Hsc until the next
+ * cugo_graph_initialize() */
 int cugo_graph_set_relpose_outlier_threshold(cugo_graph* g, double threshold);
 /* active flag of the edges [first, first + n) of the set, in insertion order (an inactive edge is left out by the next
  * cugo_graph_initialize(); a pair no active edge joins any more leaves the Hsc pattern) */
@@ -536,6 +558,16 @@ int cugo_graph_set_outlier_threshold(cugo_graph* g, int dim, double threshold);
 int cugo_graph_n_outliers(cugo_graph* g, int dim);
 /* active flag of the first n edges of the set, in insertion order */
 int cugo_graph_get_edge_active(cugo_graph* g, int dim, int n, uint8_t* active);
+/* The same for the four pose edge kinds: CUGO_ICP_PLANE / CUGO_ICP_LINE under their other names, the priors and the
+ * relative-pose edges.  Outliers found in the kind's set since the last initialize (a negative error code for an
+ * unknown kind), and the active flag of its first n edges in insertion order (CUGO_ERR_INVALID: unknown kind, n
+ * beyond the edges added). */
+#define CUGO_POSE_KIND_PLANE 0
+#define CUGO_POSE_KIND_LINE 1
+#define CUGO_POSE_KIND_PRIOR 2
+#define CUGO_POSE_KIND_RELPOSE 3
+int cugo_graph_n_pose_edge_outliers(cugo_graph* g, int kind);
+int cugo_graph_get_pose_edge_active(cugo_graph* g, int kind, int n, uint8_t* active);
 int cugo_graph_set_shard(cugo_graph* g, int rank, int world, cugo_exchange_fn fn, void* user);
 /* Native exchange (one process per GPU, RCCL over xGMI; not in the reference, which is single-GPU:
  * src/cuda_device.cpp:264-282).  Rank 0 of the job calls cugo_comm_unique_id() (ncclGetUniqueId,
@@ -571,6 +603,10 @@ int cugo_graph_flatten_reuses(cugo_graph* g);
  *   "structure_reuse" (0 = CUGO_NO_STRUCTURE_REUSE: Hsc pattern, lists, ordering, symbolic factor rebuilt every time —
  *                      what a caller that builds a new graph per call, e.g. ORB-SLAM2, pays)
  *   "init_timing"     (1 = CUGO_INIT_TIMING: per-section host times of initialize / optimize on stderr)
+ * and one option of the graph itself, off by default, which takes effect at the next cugo_graph_initialize() (a kept
+ * flattening is not reused across a change of it):
+ *   "pose_edge_outliers" (1 = GraphOptimisationOptions::poseEdgeOutlierRejection: outlier thresholds on the plane, line,
+ *                      prior and relative-pose sets are taken instead of refused)
  * Returns CUGO_ERR_INVALID for an unknown name. */
 int cugo_graph_set_option(cugo_graph* g, const char* name, int value);
 int cugo_graph_optimize(cugo_graph* g, int n_iters);  /* ref: optimize(n)  :153 */
