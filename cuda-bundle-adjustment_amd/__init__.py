@@ -604,6 +604,27 @@ class Graph:
         check(lib().cugo_graph_get_landmark_covariances(self._g, len(ids), _p(ids, _i32p), _p(out, _f64p)))
         return out.reshape(-1, 3, 3).transpose(0, 2, 1).copy()
 
+    def _pair_blocks(self, fn, ids_a, ids_b):
+        a = np.ascontiguousarray(ids_a, np.int32).reshape(-1)
+        b = np.ascontiguousarray(ids_b, np.int32).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("ids_a and ids_b must have the same length")
+        out = np.zeros((len(a), 36))
+        check(fn(self._g, len(a), _p(a, _i32p), _p(b, _i32p), _p(out, _f64p)))
+        return out.reshape(-1, 6, 6).transpose(0, 2, 1).copy()  # (column-major blocks)
+
+    def pose_cross_covariances(self, ids_a, ids_b):
+        """[n, 6, 6]: Sigma_ab of the pose pairs (ids_a[k], ids_b[k]) at the current estimates — any pairs, inside the
+        Hsc pattern or not (rows a, columns b; tangent order as pose_covariances(); a == b gives the diagonal block,
+        zeros when either pose is fixed).  Does not touch what compute_covariances() stored.  Raises CugoError (code
+        -4) on a zero pivot."""
+        return self._pair_blocks(lib().cugo_graph_compute_pose_cross_covariances, ids_a, ids_b)
+
+    def relative_pose_covariances(self, ids_a, ids_b):
+        """[n, 6, 6]: covariance of the relative pose T_a T_b^-1 in the tangent convention of the relative-pose edges;
+        its inverse is the information of an edge that summarises the graph between a and b.  a == b is refused."""
+        return self._pair_blocks(lib().cugo_graph_relative_pose_covariances, ids_a, ids_b)
+
     def set_poses(self, ids, q_t7):
         ids = np.ascontiguousarray(ids, np.int32); q = np.ascontiguousarray(q_t7, np.float64)
         check(lib().cugo_graph_set_poses(self._g, len(ids), _p(ids, _i32p), _p(q, _f64p)))

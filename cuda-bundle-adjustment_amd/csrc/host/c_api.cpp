@@ -610,6 +610,35 @@ int cugo_chol_selected_inverse(cugo_chol* s, double* d_sigma)
     }
     return CUGO_OK;
 }
+int cugo_chol_inverse_blocks(cugo_chol* s, int n_pairs, const int32_t* h_rows, const int32_t* h_cols, double* d_out)
+{
+    bool ok = true;
+    const int rc = guarded([&] {
+        if (!s || !s->analyzed)
+            throw std::runtime_error("cugo_chol_inverse_blocks needs an analysed solver");
+        if (n_pairs < 0)
+            throw std::invalid_argument("cugo_chol_inverse_blocks: negative count");
+        for (int k = 0; k < n_pairs; k++)
+            if (h_rows[k] < 0 || h_rows[k] >= s->plan.n || h_cols[k] < 0 || h_cols[k] >= s->plan.n)
+                throw std::invalid_argument("cugo_chol_inverse_blocks: pair " + std::to_string(k) + " names a block row "
+                                            "outside [0, " + std::to_string(s->plan.n) + ")");
+        if (!s->ctx || !s->factored)
+            throw std::runtime_error("cugo_chol_inverse_blocks needs a factorisation (cugo_chol_factor_solve) since the "
+                                     "last analyze()");
+        if (s->own_subtrees())
+            throw std::runtime_error("cugo_chol_inverse_blocks: not available when the solver factors rank-owned "
+                                     "subtrees");
+        ok = s->inverse_blocks(n_pairs, h_rows, h_cols, d_out);
+    });
+    if (rc != CUGO_OK)
+        return rc;
+    if (!ok)
+    {
+        set_last_error("cugo_chol_inverse_blocks: the factorisation hit a zero pivot");
+        return CUGO_ERR_NUMERIC;
+    }
+    return CUGO_OK;
+}
 #ifdef CUGO_DEBUG_HOOKS // diagnosis entry points: only libcugo_hip_hooks.so exports them (csrc/host/cugo_debug.h)
 int cugo_debug_pin_reference(void)
 {
@@ -1344,6 +1373,118 @@ int cugo_graph_get_landmark_covariances(cugo_graph* g, int n, const int32_t* ids
                                          "since the last initialize(), or the landmark set changed since then");
     });
 }
+namespace
+{
+// Sigma_ab of the pose pairs by caller id; CUGO_ERR_NUMERIC on a zero pivot
+int pose_cross_blocks(cugo_graph* g, const char* who, int n, const int32_t* ids_a, const int32_t* ids_b, double* cov36)
+{
+    bool ok = true;
+    const int rc = guarded([&] {
+        if (n < 0)
+            throw std::invalid_argument(std::string(who) + ": negative count");
+        std::vector<const cugo::BaseVertex*> a(n), b(n);
+        for (int i = 0; i < n; i++)
+            a[i] = g->poses.getVertex(ids_a[i]), b[i] = g->poses.getVertex(ids_b[i]);
+        ok = g->opt->poseCrossCovariances(n, a.data(), b.data(), cov36);
+    });
+    if (rc != CUGO_OK)
+        return rc;
+    if (!ok)
+    {
+        set_last_error(std::string(who) + ": zero pivot — H is singular at the current estimates");
+        return CUGO_ERR_NUMERIC;
+    }
+    return CUGO_OK;
+}
+
+// Ad(A) of A = T_a T_b^-1 (row-major 6 x 6, tangent order [rotation, translation]): [ R 0 ; [t]x R  R ]
+void relative_adjoint(const cugo::Se3D& Ta, const cugo::Se3D& Tb, double (&Ad)[6][6])
+{
+    auto rot = [](const cugo::Se3D& T, double (&R)[3][3]) {
+        double q[4], t[3];
+        T.copyTo(q, t);
+        const double x = q[0], y = q[1], z = q[2], w = q[3];
+        R[0][0] = 1 - 2 * (y * y + z * z), R[0][1] = 2 * (x * y - z * w), R[0][2] = 2 * (x * z + y * w);
+        R[1][0] = 2 * (x * y + z * w), R[1][1] = 1 - 2 * (x * x + z * z), R[1][2] = 2 * (y * z - x * w);
+        R[2][0] = 2 * (x * z - y * w), R[2][1] = 2 * (y * z + x * w), R[2][2] = 1 - 2 * (x * x + y * y);
+    };
+    double Ra[3][3], Rb[3][3], R[3][3], qa[4], ta[3], qb[4], tb[3], t[3];
+    rot(Ta, Ra), rot(Tb, Rb);
+    Ta.copyTo(qa, ta), Tb.copyTo(qb, tb);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            R[i][j] = Ra[i][0] * Rb[j][0] + Ra[i][1] * Rb[j][1] + Ra[i][2] * Rb[j][2]; // R_a R_b^T
+    for (int i = 0; i < 3; i++)
+        t[i] = ta[i] - (R[i][0] * tb[0] + R[i][1] * tb[1] + R[i][2] * tb[2]); // t_a - R t_b
+    const double tx[3][3] = {{0, -t[2], t[1]}, {t[2], 0, -t[0]}, {-t[1], t[0], 0}};
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+        {
+            Ad[i][j] = Ad[3 + i][3 + j] = R[i][j];
+            Ad[i][3 + j] = 0.0;
+            Ad[3 + i][j] = tx[i][0] * R[0][j] + tx[i][1] * R[1][j] + tx[i][2] * R[2][j];
+        }
+}
+} // namespace
+
+int cugo_graph_compute_pose_cross_covariances(cugo_graph* g, int n, const int32_t* ids_a, const int32_t* ids_b,
+                                              double* cov36)
+{
+    return pose_cross_blocks(g, "cugo_graph_compute_pose_cross_covariances", n, ids_a, ids_b, cov36);
+}
+
+int cugo_graph_relative_pose_covariances(cugo_graph* g, int n, const int32_t* ids_a, const int32_t* ids_b, double* cov36)
+{
+    const char* who = "cugo_graph_relative_pose_covariances";
+    std::vector<int32_t> qa, qb;
+    std::vector<double> blk;
+    int rc = guarded([&] {
+        if (n < 0)
+            throw std::invalid_argument(std::string(who) + ": negative count");
+        for (int i = 0; i < n; i++)
+        {
+            if (ids_a[i] == ids_b[i])
+                throw std::invalid_argument(std::string(who) + ": a == b (the relative pose of a pose to itself)");
+            // Sigma_aa, Sigma_ab, Sigma_bb of every pair
+            qa.insert(qa.end(), {ids_a[i], ids_a[i], ids_b[i]});
+            qb.insert(qb.end(), {ids_a[i], ids_b[i], ids_b[i]});
+        }
+        blk.resize(36 * qa.size());
+    });
+    if (rc != CUGO_OK)
+        return rc;
+    rc = pose_cross_blocks(g, who, (int)qa.size(), qa.data(), qb.data(), blk.data());
+    if (rc != CUGO_OK)
+        return rc;
+    return guarded([&] {
+        for (int i = 0; i < n; i++)
+        {
+            double Ad[6][6];
+            relative_adjoint(g->poses.getVertex(ids_a[i])->getEstimate(), g->poses.getVertex(ids_b[i])->getEstimate(), Ad);
+            // column-major blocks: S(r, c) = S[r + 6 c]
+            const double *Saa = blk.data() + 108 * (size_t)i, *Sab = Saa + 36, *Sbb = Saa + 72;
+            double M[6][6], N[6][6]; // M = Ad Sigma_ba = Ad Sigma_ab^T, N = Ad Sigma_bb
+            for (int r = 0; r < 6; r++)
+                for (int c = 0; c < 6; c++)
+                {
+                    double m = 0.0, nn = 0.0;
+                    for (int k = 0; k < 6; k++)
+                        m += Ad[r][k] * Sab[c + 6 * k], nn += Ad[r][k] * Sbb[k + 6 * c];
+                    M[r][c] = m, N[r][c] = nn;
+                }
+            double* out = cov36 + 36 * (size_t)i;
+            for (int r = 0; r < 6; r++)
+                for (int c = 0; c < 6; c++)
+                {
+                    double v = 0.0;
+                    for (int k = 0; k < 6; k++)
+                        v += N[r][k] * Ad[c][k];
+                    out[r + 6 * c] = Saa[r + 6 * c] - M[c][r] - M[r][c] + v;
+                }
+        }
+    });
+}
+
 int cugo_graph_set_poses(cugo_graph* g, int n, const int32_t* ids, const double* qt)
 {
     return guarded([&] {

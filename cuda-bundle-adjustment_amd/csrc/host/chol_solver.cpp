@@ -3,6 +3,7 @@
 // (src/cholesky.hpp:170-309): initialize(pattern) once, solve(A, b, x)->bool per LM trial.
 #include "chol_solver.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -250,7 +251,7 @@ void cugo_chol::analyze_host(int n, const int32_t* rowptr, const int32_t* colind
         chol_analyze(n, rowptr, colind, copt, plan);
     }
     lookahead = opt.lookahead;
-    factored = false, si_ready = false, last_fail = nullptr;
+    factored = false, si_ready = false, xc_ready = false, last_fail = nullptr;
     trans32.assign(plan.blk_trans.begin(), plan.blk_trans.end());
     pack();
     if (plan.nc_max > cugo_k::chol_max_pivot_cols() ||
@@ -691,6 +692,85 @@ bool cugo_chol::selected_inverse(double* d_sigma)
         }
     }
     cugo_k::launch_selinv_gather(s, dev, d_sig.data(), d_sigma);
+    CUGO_HIP(hipGetLastError());
+    return true;
+}
+
+// Blocks of (A + lambda I)^-1 for arbitrary pairs from the factorisation the last factor_solve left (DESIGN.md,
+// "Cross-covariances of any pair"): Y_v = L^-1 E_v of every distinct query row by a walk up the elimination tree, then
+// Y_a^T Y_b per pair.  The pairs are cut into batches whose distinct rows fit the workspace.
+bool cugo_chol::inverse_blocks(int n_pairs, const int32_t* h_rows, const int32_t* h_cols, double* d_out)
+{
+    hipStream_t s = ctx->stream;
+    int32_t h_fail = 0;
+    CUGO_HIP(hipMemcpyAsync(&h_fail, last_fail, sizeof h_fail, hipMemcpyDeviceToHost, s));
+    CUGO_HIP(hipStreamSynchronize(s));
+    check_chain_error();
+    if (h_fail)
+        return false;
+    if (n_pairs == 0)
+        return true;
+    const CholPlan& P = plan;
+    if (!xc_ready)
+    {
+        d_sparent.upload(P.sparent, s);
+        CUGO_HIP(hipStreamSynchronize(s)); // (analyze() may replace the plan's vectors)
+        xc_ready = true;
+    }
+    const size_t per_row = 36 * (size_t)P.n; // doubles
+    size_t cap = std::max<size_t>(2, XCOV_WS_BYTES / (per_row * sizeof(double)));
+    if (opt.xcov_batch > 0)
+        cap = std::max<size_t>(2, std::min<size_t>(cap, (size_t)opt.xcov_batch));
+    // per batch: its distinct rows (solver's ordering), then {slot of a, slot of b, a} per pair
+    struct Batch
+    {
+        size_t rows_off, pairs_off;
+        int nrows, npairs, pair0;
+    };
+    std::vector<Batch> batches;
+    std::vector<int32_t> rows, pairs;
+    xc_meta.clear();
+    xc_slot.assign((size_t)P.n, -1);
+    int pair0 = 0;
+    auto close = [&](int upto) {
+        if (pairs.empty())
+            return;
+        Batch b;
+        b.rows_off = xc_meta.size(), b.nrows = (int)rows.size();
+        xc_meta.insert(xc_meta.end(), rows.begin(), rows.end());
+        b.pairs_off = xc_meta.size(), b.npairs = (int)(pairs.size() / 3), b.pair0 = pair0;
+        xc_meta.insert(xc_meta.end(), pairs.begin(), pairs.end());
+        batches.push_back(b);
+        for (int32_t r : rows)
+            xc_slot[r] = -1;
+        rows.clear(), pairs.clear();
+        pair0 = upto;
+    };
+    for (int q = 0; q < n_pairs; q++)
+    {
+        const int32_t a = P.iperm[h_rows[q]], b = P.iperm[h_cols[q]];
+        const size_t need = (xc_slot[a] < 0 ? 1 : 0) + (b != a && xc_slot[b] < 0 ? 1 : 0);
+        if (rows.size() + need > cap)
+            close(q);
+        for (int32_t v : {a, b})
+            if (xc_slot[v] < 0)
+                xc_slot[v] = (int32_t)rows.size(), rows.push_back(v);
+        pairs.push_back(xc_slot[a]), pairs.push_back(xc_slot[b]), pairs.push_back(a);
+    }
+    close(n_pairs);
+    size_t max_rows = 0;
+    for (const Batch& b : batches)
+        max_rows = std::max(max_rows, (size_t)b.nrows);
+    d_xc_ws.resize(max_rows * per_row + 16);
+    d_xc_meta.upload(xc_meta, s);
+    for (const Batch& b : batches)
+    {
+        CUGO_HIP(hipMemsetAsync(d_xc_ws.data(), 0, (size_t)b.nrows * per_row * sizeof(double), s));
+        cugo_k::launch_inv_path_walk(s, dev, d_fronts.data(), d_sparent.data(), d_xc_meta.data() + b.rows_off, b.nrows,
+                                     d_xc_ws.data());
+        cugo_k::launch_inv_pair_blocks(s, dev, d_sparent.data(), d_xc_meta.data() + b.pairs_off, b.npairs,
+                                       d_xc_ws.data(), d_out + 36 * (size_t)b.pair0);
+    }
     CUGO_HIP(hipGetLastError());
     return true;
 }

@@ -81,6 +81,17 @@ struct cugo_chol
     // false: the zero-pivot flag of the last factorisation is set (nothing queued)
     bool selected_inverse(double* d_sigma);
 
+    // blocks of the inverse for arbitrary pairs (cugo_chol_inverse_blocks): h_rows / h_cols in the caller's numbering,
+    // d_out [n_pairs][36].  The distinct rows of a batch of pairs each take a [6 n][6] workspace (at most
+    // XCOV_WS_BYTES in all, or CUGO_XCOV_BATCH rows); sparent goes to the device on the first call after analyze().
+    // false: the zero-pivot flag of the last factorisation is set (nothing queued)
+    static constexpr size_t XCOV_WS_BYTES = size_t(512) << 20;
+    bool xc_ready = false;
+    cugo_host::DevBuf<int32_t> d_sparent, d_xc_meta;
+    cugo_host::DevBuf<double> d_xc_ws;
+    std::vector<int32_t> xc_meta, xc_slot; // the batches' row and pair lists (kept until the next call: the copy reads it)
+    bool inverse_blocks(int n_pairs, const int32_t* h_rows, const int32_t* h_cols, double* d_out);
+
     void analyze(int n, const int32_t* rowptr, const int32_t* colind);
     void analyze_host(int n, const int32_t* rowptr, const int32_t* colind); // without upload()
     void pack(); // host half of upload() (analyze_host calls it)

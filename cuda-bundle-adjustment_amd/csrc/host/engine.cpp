@@ -147,7 +147,7 @@ struct Engine::Impl : cugo_k::LaunchHook
     DevBuf<double> d_lmrec;
     // marginal covariances (Engine::compute_covariances; allocated by the first call only): the blocks of Sigma on
     // the Hsc pattern, the landmark blocks, their positive-definiteness flag
-    DevBuf<double> d_cov_sigma, d_cov_pose, d_cov_lm;
+    DevBuf<double> d_cov_sigma, d_cov_pose, d_cov_lm, d_xcov; // (d_xcov: Engine::pose_cross_covariances)
     DevBuf<int32_t> d_cov_fail;
     PinnedBuf<double> h_pin_poses, h_pin_lms; // refresh_estimates_pinned / download_pinned
     Clock::duration last_trial_wait{0};       // how long the host polled for the previous trial's result
@@ -1921,18 +1921,25 @@ void Engine::clear_covariances()
     cov_lm_.clear();
 }
 
-bool Engine::compute_covariances(int what)
+// The optimisers both covariance entry points refuse
+void Engine::check_covariance_call(const char* who) const
+{
+    const Impl& m = *impl_;
+    const std::string w(who);
+    if (m.plan_only)
+        throw std::runtime_error(w + ": plan-only optimiser (no HIP device in use)");
+    if (m.world > 1 || m.comm)
+        throw std::runtime_error(w + ": not available on a sharded (multi-GPU) optimiser");
+    if (m.ev.block_f32)
+        throw std::runtime_error(w + ": not available in the fp32-internal mode");
+}
+
+// What both covariance entry points queue first: H at the current estimates, undamped — the two-stream build pass (Hpp,
+// b, Hll, Hpl) as a retried trial of optimize() queues it —, its Schur complement and one factorisation at lambda = 0.
+// optimize() starts every call with a build pass of its own, so nothing it reads is lost.
+void Engine::queue_covariance_system()
 {
     Impl& m = *impl_;
-    if (what < 1 || what > 3)
-        throw std::invalid_argument("cugo_graph_compute_covariances: what must be 1 (poses), 2 (landmarks) or 3 (both)");
-    if (m.plan_only)
-        throw std::runtime_error("cugo_graph_compute_covariances: plan-only optimiser (no HIP device in use)");
-    if (m.world > 1 || m.comm)
-        throw std::runtime_error("cugo_graph_compute_covariances: not available on a sharded (multi-GPU) optimiser");
-    if (m.ev.block_f32)
-        throw std::runtime_error("cugo_graph_compute_covariances: not available in the fp32-internal mode");
-    clear_covariances();
     if (m.structure_dirty)
         build_structure();
     hipStream_t s = m.ctx.stream;
@@ -1942,18 +1949,27 @@ bool Engine::compute_covariances(int what)
         m.pe.bind_relpose_plan(m.hsc_rowptr, m.hsc_colind, s, false);
     }
     m.begin_call(false);
-    // H at the current estimates, undamped: the two-stream build pass (Hpp, b, Hll, Hpl), as a retried trial of
-    // optimize() queues it.  optimize() starts every call with a build pass of its own, so nothing it reads is lost.
     m.queue_build(m.cur, -1.0);
-    const int B = m.hs.n_blocks;
-    m.d_cov_sigma.resize(36 * (size_t)B + 16);
     if (m.P > 0)
     {
         m.queue_schur(0.0, false, false, m.cur);
         m.queue_factor_solve(0.0);
-        if (!m.chol.selected_inverse(m.d_cov_sigma.data()))
-            return false;
     }
+}
+
+bool Engine::compute_covariances(int what)
+{
+    Impl& m = *impl_;
+    if (what < 1 || what > 3)
+        throw std::invalid_argument("cugo_graph_compute_covariances: what must be 1 (poses), 2 (landmarks) or 3 (both)");
+    check_covariance_call("cugo_graph_compute_covariances");
+    clear_covariances();
+    queue_covariance_system();
+    hipStream_t s = m.ctx.stream;
+    const int B = m.hs.n_blocks;
+    m.d_cov_sigma.resize(36 * (size_t)B + 16);
+    if (m.P > 0 && !m.chol.selected_inverse(m.d_cov_sigma.data()))
+        return false;
     std::vector<int32_t> fail(1, 0);
     if (what & 2)
     {
@@ -1987,6 +2003,36 @@ bool Engine::compute_covariances(int what)
     if (!(what & 1))
         cov_pose_.clear();
     cov_what_ = what;
+    return true;
+}
+
+// Sigma_ab of the pairs (ia[k], ib[k]) of free pose indices (-1: a fixed pose, the block is zero) through
+// cugo_chol::inverse_blocks on the same factorisation compute_covariances() runs; the stored marginals stay.
+bool Engine::pose_cross_covariances(int n, const int32_t* ia, const int32_t* ib, double* cov36)
+{
+    Impl& m = *impl_;
+    check_covariance_call("cugo_graph_compute_pose_cross_covariances");
+    std::vector<int32_t> ra, rb, where;
+    for (int k = 0; k < n; k++)
+        if (ia[k] >= 0 && ib[k] >= 0)
+        {
+            if (ia[k] >= m.P || ib[k] >= m.P)
+                throw std::invalid_argument("cugo_graph_compute_pose_cross_covariances: pose index out of range");
+            ra.push_back(ia[k]), rb.push_back(ib[k]), where.push_back(k);
+        }
+    std::fill(cov36, cov36 + 36 * (size_t)n, 0.0);
+    if (ra.empty()) // (every pair holds a fixed pose: nothing to factor)
+        return true;
+    queue_covariance_system();
+    hipStream_t s = m.ctx.stream;
+    m.d_xcov.resize(36 * ra.size() + 16);
+    if (!m.chol.inverse_blocks((int)ra.size(), ra.data(), rb.data(), m.d_xcov.data()))
+        return false;
+    std::vector<double> h(36 * ra.size());
+    CUGO_HIP(hipMemcpyAsync(h.data(), m.d_xcov.data(), h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    CUGO_HIP(hipStreamSynchronize(s));
+    for (size_t q = 0; q < where.size(); q++)
+        std::copy(h.begin() + 36 * q, h.begin() + 36 * q + 36, cov36 + 36 * (size_t)where[q]);
     return true;
 }
 

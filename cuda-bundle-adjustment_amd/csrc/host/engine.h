@@ -216,6 +216,10 @@ public:
     // host.  Returns false on a zero pivot or a landmark whose Hll is not positive definite.  Leaves the estimates
     // and everything the next optimize() reads as they were.
     bool compute_covariances(int what);
+    // Extension: the blocks Sigma_ab of n pose pairs, given by free pose index (-1: a fixed pose, its blocks are zero),
+    // into cov36 [n][36] (host, column-major, rows a).  The same build pass, Schur complement and factorisation, then
+    // cugo_chol::inverse_blocks; the marginals kept by compute_covariances() are not touched.  false: a zero pivot.
+    bool pose_cross_covariances(int n, const int32_t* ia, const int32_t* ib, double* cov36);
     void clear_covariances();
     int covariances_held() const { return cov_what_; } // bit 0 poses, bit 1 landmarks
     const std::vector<double>& cov_pose() const { return cov_pose_; }
@@ -247,6 +251,8 @@ public:
     struct Impl;
 
 private:
+    void check_covariance_call(const char* who) const; // throws on plan-only, sharded and fp32-internal optimisers
+    void queue_covariance_system();                    // build pass at lambda = 0, Schur complement, factorisation
     void build_structure(); // by device_structure() or host_structure(); both end in adopt_structure()
     bool device_structure(InitLaps& laps);
     void host_structure(InitLaps& laps);

@@ -870,6 +870,34 @@ bool CudaGraphOptimisationImpl::poseCovariance(const BaseVertex* v, double cov[3
     return true;
 }
 
+bool CudaGraphOptimisationImpl::poseCrossCovariances(int n, const BaseVertex* const* a, const BaseVertex* const* b,
+                                                     double* cov36)
+{
+    if (!initialized_)
+        throw std::runtime_error("cugo: poseCrossCovariances() needs initialize() first");
+    if (options.planOnly)
+        throw std::runtime_error("cugo: poseCrossCovariances(): this optimiser is plan-only (no HIP device in use)");
+    if (options.useFloat32)
+        throw std::runtime_error("cugo: poseCrossCovariances() is not available in the fp32-internal mode");
+    if (n < 0)
+        throw std::invalid_argument("cugo: poseCrossCovariances(): negative count");
+    for (BaseVertexSet* vs : vertexSets)
+        if (!flattenedUnchanged(vs))
+            throw std::runtime_error("cugo: poseCrossCovariances(): a vertex set changed since initialize() (vertex "
+                                     "added, removed or fixed / freed); call initialize() again");
+    // free pose index in the flattening, -1 for a fixed pose
+    std::vector<int32_t> ia(n), ib(n);
+    auto index_of = [this](const BaseVertex* v) {
+        if (!v || v->isMarginilised() || !flattenedUnchanged(v->ownerSet()))
+            throw std::invalid_argument("cugo: poseCrossCovariances(): a vertex is not a pose of the current flattening");
+        const int i = v->getIndex();
+        return v->isFixed() || i < 0 || i >= engine_->n_poses_free() ? -1 : i;
+    };
+    for (int k = 0; k < n; k++)
+        ia[k] = index_of(a[k]), ib[k] = index_of(b[k]);
+    return engine_->pose_cross_covariances(n, ia.data(), ib.data(), cov36);
+}
+
 bool CudaGraphOptimisationImpl::landmarkCovariance(const BaseVertex* v, double cov[9]) const
 {
     if (!(engine_->covariances_held() & 2) || !v || !v->isMarginilised() || !flattenedUnchanged(v->ownerSet()))

@@ -35,6 +35,7 @@ struct Options
     bool ea_lds = true, panel16 = true, asm_fronts = true; // CUGO_EA_LDS / CUGO_PANEL16 / CUGO_ASM_FRONTS = 0
     bool ea_direct = true;          // CUGO_EA_DIRECT=0: the potrf gathers its children's F11 terms unit by unit again
     bool bw_chain = true;           // CUGO_BW_CHAIN=0: the backward pass one launch per stage (k_backward_stage) again
+    int xcov_batch = 0;             // CUGO_XCOV_BATCH: distinct query rows per batch of cugo_chol_inverse_blocks (0: what 512 MB hold)
     // ---- multi-GPU exchange (engine.cpp) ----
     bool reduce_scatter = true;     // CUGO_REDUCE_SCATTER=0: all-reduce of [Hsc | bsc] also with rank-owned subtrees
 
@@ -77,6 +78,8 @@ struct Options
         o.ea_lds = !off("CUGO_EA_LDS"), o.panel16 = !off("CUGO_PANEL16"), o.asm_fronts = !off("CUGO_ASM_FRONTS");
         o.ea_direct = !off("CUGO_EA_DIRECT");
         o.bw_chain = !off("CUGO_BW_CHAIN");
+        if (const char* e = std::getenv("CUGO_XCOV_BATCH"))
+            o.xcov_batch = std::atoi(e);
         o.reduce_scatter = !off("CUGO_REDUCE_SCATTER");
         return o;
     }

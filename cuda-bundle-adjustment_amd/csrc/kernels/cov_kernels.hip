@@ -20,6 +20,10 @@
 //
 // Every entry is one thread's sum in a fixed order: no atomics, the same bits on every call.
 //
+// Blocks off the pattern (any pair a, b) come from forward solves on the same W and L21 instead:
+//   k_inv_path_walk   one workgroup per distinct query row: Y_v = L^-1 E_v along the path from v's front to the root
+//   k_inv_pair_blocks one workgroup per pair: Y_a^T Y_b
+//
 // Landmarks (k_lm_covariance): with Hll = L L^T and G_e = Hpl_e L^-T of the landmark's free-pose edges,
 //   Sigma_l = L^-T (I + sum_{e,f} G_e^T Sigma_{p(e) p(f)} G_f) L^-1,
 // one thread per landmark, the pose blocks looked up in the upper block CSR of Hsc.
@@ -464,6 +468,106 @@ __global__ __launch_bounds__(256) void k_cov_pose_diag(int P, const int32_t* __r
     out[i] = sigma[36L * rowptr[i / 36] + i % 36];
 }
 
+// ---------------------------------------------------------------- blocks of the inverse off the pattern --------------
+// (A + lambda I)^-1 [a, b] = Y_a^T Y_b with Y_v = L^-1 E_v (6 columns).  Y_v is non-zero only on the pivot columns of
+// the fronts on the path from v's front to the root of the elimination tree: the boundary rows of a front are pivot
+// columns of its ancestors, and every front of the path has one child on it, so one workgroup walks the path alone.
+constexpr int XC_T = 256;     // workgroup size of both kernels
+constexpr int XC_SLICES = 7;  // k_inv_pair_blocks: 7 x 36 threads, slice s sums the columns k = s (mod 7)
+
+// One workgroup per distinct query row.  rows[g]: the row's block index in the solver's ordering; its workspace
+// t = ws + g * 36 n ([6 n][6], zeroed by the caller) holds Y_v afterwards.
+__global__ __launch_bounds__(XC_T) void k_inv_path_walk(CholPlanDev p, const double* __restrict__ fronts,
+                                                        const int32_t* __restrict__ sparent,
+                                                        const int32_t* __restrict__ rows, double* ws)
+{
+    __shared__ double tj[SI_N * 6]; // t_J, then y_J
+    __shared__ double yj[SI_N * 6];
+    const int tid = threadIdx.x;
+    const int v = rows[blockIdx.x];
+    double* t = ws + (size_t)blockIdx.x * 36 * (size_t)p.n;
+    if (tid < 6)
+        t[(6L * v + tid) * 6 + tid] = 1.0;
+    __threadfence_block();
+    __syncthreads();
+    for (int f = p.col_front[v]; f >= 0; f = sparent[f])
+    {
+        const SelFront F = sel_front(p, fronts, f);
+        double* tJ = t + 36L * p.col0[f];
+        for (int e = tid; e < 6 * F.ncs; e += XC_T)
+            tj[e] = tJ[e];
+        __syncthreads();
+        // y_J = W t_J: y[k][c] = sum_{j <= k} W[k][j] t[j][c], j ascending
+        for (int e = tid; e < 6 * F.ncs; e += XC_T)
+        {
+            const int k = e % F.ncs, c = e / F.ncs;
+            double s = 0.0;
+#pragma unroll 8 // (the loads of eight steps in flight: the walk is bound by their latency)
+            for (int j = 0; j <= k; j++)
+                s += F.W[(long)j * F.ncp + k] * tj[6 * j + c];
+            yj[6 * k + c] = s;
+            tJ[6 * k + c] = s;
+        }
+        __syncthreads();
+        // t_R -= L21 y_J, one boundary row per thread (the right-hand-side row behind a compact L21 is not a row of it)
+        const int32_t* __restrict__ rb = p.rows + p.rows_ptr[f];
+        for (int i = tid; i < F.nrs; i += XC_T)
+        {
+            double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll 8
+            for (int j = 0; j < F.ncs; j++)
+            {
+                const double l = F.L[(long)j * F.ldl + i];
+#pragma unroll
+                for (int c = 0; c < 6; c++)
+                    acc[c] += l * yj[6 * j + c];
+            }
+            double* tr = t + (6L * rb[i / 6] + i % 6) * 6;
+#pragma unroll
+            for (int c = 0; c < 6; c++)
+                tr[c] -= acc[c];
+        }
+        __threadfence_block();
+        __syncthreads(); // this front's stores before the next front's loads
+    }
+}
+
+// One workgroup per pair.  pairs[q] = {slot of a, slot of b, a's block index in the solver's ordering}; the sum runs
+// over the pivot columns of a's path (Y_b is zero on those that are not on b's path too).  Slice s adds the columns
+// k = s (mod 7) in ascending path order and the slices are added in order, whichever of the two paths is walked: the
+// block of (b, a) is the transpose of the block of (a, b) bit for bit.
+__global__ __launch_bounds__(XC_T) void k_inv_pair_blocks(CholPlanDev p, const int32_t* __restrict__ sparent,
+                                                          const int32_t* __restrict__ pairs, const double* __restrict__ ws,
+                                                          double* __restrict__ out)
+{
+    __shared__ double part[XC_SLICES * 36];
+    const int tid = threadIdx.x;
+    const int32_t* pr = pairs + 3L * blockIdx.x;
+    const double* __restrict__ ya = ws + (size_t)pr[0] * 36 * (size_t)p.n;
+    const double* __restrict__ yb = ws + (size_t)pr[1] * 36 * (size_t)p.n;
+    if (tid < XC_SLICES * 36)
+    {
+        const int s = tid / 36, e = tid % 36, r = e % 6, c = e / 6;
+        double acc = 0.0;
+        for (int f = p.col_front[pr[2]]; f >= 0; f = sparent[f])
+        {
+            const long k0 = 6L * p.col0[f], k1 = k0 + 6L * p.ncb[f];
+            for (long k = k0 + (s + XC_SLICES - (int)(k0 % XC_SLICES)) % XC_SLICES; k < k1; k += XC_SLICES)
+                acc += ya[6 * k + r] * yb[6 * k + c];
+        }
+        part[tid] = acc;
+    }
+    __syncthreads();
+    if (tid < 36)
+    {
+        double sum = part[tid];
+#pragma unroll
+        for (int s = 1; s < XC_SLICES; s++)
+            sum += part[36 * s + tid];
+        out[36L * blockIdx.x + tid] = sum; // column-major: rows a, columns b
+    }
+}
+
 void ensure_lds(const void* fn, size_t bytes)
 {
     if (bytes > 48 * 1024)
@@ -514,6 +618,22 @@ void launch_selinv_gather(hipStream_t s, const CholPlanDev& p, const double* d_s
 }
 
 int selinv_row_tile() { return SI_R; }
+
+void launch_inv_path_walk(hipStream_t s, const CholPlanDev& p, const double* d_fronts, const int32_t* d_sparent,
+                          const int32_t* d_rows, int nrows, double* d_ws)
+{
+    if (nrows <= 0)
+        return;
+    CUGO_LAUNCH(k_inv_path_walk, dim3(nrows), dim3(XC_T), 0, s, p, d_fronts, d_sparent, d_rows, d_ws);
+}
+
+void launch_inv_pair_blocks(hipStream_t s, const CholPlanDev& p, const int32_t* d_sparent, const int32_t* d_pairs,
+                            int npairs, const double* d_ws, double* d_out)
+{
+    if (npairs <= 0)
+        return;
+    CUGO_LAUNCH(k_inv_pair_blocks, dim3(npairs), dim3(XC_T), 0, s, p, d_sparent, d_pairs, d_ws, d_out);
+}
 
 void launch_cov_pose_diag(hipStream_t s, int P, const int32_t* d_rowptr, const double* d_sigma, double* d_out)
 {

@@ -403,6 +403,15 @@ void launch_selinv_subtree(hipStream_t s, const CholPlanDev& p, const double* d_
 // d_out [n_hsc_blocks][36]: the blocks of Sigma on the Hsc pattern (layout of d_Hsc)
 void launch_selinv_gather(hipStream_t s, const CholPlanDev& p, const double* d_sig, double* d_out);
 int selinv_row_tile(); // rows of R per k_selinv_rows item
+// blocks of the inverse for arbitrary pairs, from forward solves alone (k_inv_path_walk, k_inv_pair_blocks).
+// d_rows [nrows]: distinct query block rows in the solver's ordering; d_ws [nrows][6 n][6], zeroed by the caller, holds
+// Y_v = L^-1 E_v of row g at d_ws + g * 36 n afterwards.  d_sparent [n_fronts]: CholPlan::sparent
+void launch_inv_path_walk(hipStream_t s, const CholPlanDev& p, const double* d_fronts, const int32_t* d_sparent,
+                          const int32_t* d_rows, int nrows, double* d_ws);
+// d_pairs [npairs][3]: {workspace slot of a, slot of b, a in the solver's ordering}; d_out [npairs][36]: Y_a^T Y_b,
+// column-major (rows a, columns b)
+void launch_inv_pair_blocks(hipStream_t s, const CholPlanDev& p, const int32_t* d_sparent, const int32_t* d_pairs,
+                            int npairs, const double* d_ws, double* d_out);
 // d_out [P][36]: the diagonal blocks of d_sigma (the first block of every row of the upper block CSR d_rowptr)
 void launch_cov_pose_diag(hipStream_t s, int P, const int32_t* d_rowptr, const double* d_sigma, double* d_out);
 // Sigma_l [L][9] of every free landmark from Hll, Hpl (landmark-major edge slots) and the pose blocks d_sigma on the

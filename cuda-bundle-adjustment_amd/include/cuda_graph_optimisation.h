@@ -174,6 +174,13 @@ public:
     bool poseCovariance(const BaseVertex* v, double cov[36]) const;
     /** the 3x3 block of a landmark (column-major); all zero for a fixed landmark.  false: as poseCovariance */
     bool landmarkCovariance(const BaseVertex* v, double cov[9]) const;
+    /** cross-covariances of ANY pose pairs (g2o computeMarginals(spinv, blockIndices)): cov36 [n][36], block k is
+     *  Sigma_ab of (a[k], b[k]) at the current estimates, 6x6 column-major with rows a and columns b, tangent order as
+     *  poseCovariance; a == b gives the diagonal block, a block with a fixed pose is zero.  The pairs need not be in
+     *  the Hsc pattern: the joint uncertainty of a loop-closure candidate before its edge exists.  Runs what
+     *  computeMarginals runs up to the factorisation and leaves the marginals stored by it untouched.  false: a zero
+     *  pivot.  Throws as computeMarginals does, and for a vertex that is not a pose of the current flattening. */
+    bool poseCrossCovariances(int n, const BaseVertex* const* a, const BaseVertex* const* b, double* cov36);
 
 private:
     bool verbose = false;

@@ -214,6 +214,16 @@ int cugo_chol_factor_solve(cugo_chol* s, const double* d_Hsc, double lambda, con
  * factorisation ran since analyze(), or if the solver factors rank-owned subtrees.  The first call
  * after analyze() allocates a buffer of the size of the fronts (cugo_chol_stats: front_bytes). */
 int cugo_chol_selected_inverse(cugo_chol* s, double* d_sigma);
+/* Extension (g2o computeMarginals(spinv, blockIndices)): the blocks (h_rows[k], h_cols[k]) of (A + lambda I)^-1 for
+ * ANY block pairs of the analysed numbering — off the pattern, below the diagonal (a > b) and a == b included —
+ * from the factorisation the last cugo_chol_factor_solve left.  d_out [n_pairs][36] (device), each block 6x6
+ * column-major with rows a and columns b, as a block of d_sigma above.  The index lists are host arrays.  The
+ * contract of cugo_chol_selected_inverse: one synchronisation for the zero-pivot flag (CUGO_ERR_NUMERIC if set),
+ * then enqueued on the context's stream; CUGO_ERR_INVALID before any factorisation, on a host-only solver, with
+ * rank-owned subtrees, for n_pairs < 0 or an index outside [0, n_block_rows).  Every distinct query row takes a
+ * workspace of 288 n_block_rows bytes; the pairs are processed in batches whose rows fit 512 MB (or CUGO_XCOV_BATCH
+ * rows, read when the solver is created).  The same bits on every call, whatever the batches. */
+int cugo_chol_inverse_blocks(cugo_chol* s, int n_pairs, const int32_t* h_rows, const int32_t* h_cols, double* d_out);
 /* statistics of the analysis: nnz(L) in scalars, factorisation flops, #supernodes, #stages */
 int cugo_chol_stats(const cugo_chol* s, double* nnzL, double* flops, int* n_supernodes,
                     int* n_stages, double* front_bytes);
@@ -633,6 +643,20 @@ int cugo_graph_compute_covariances(cugo_graph* g, int what);
  * CUGO_ERR_INVALID if that kind was not computed since the last initialize(). */
 int cugo_graph_get_pose_covariances(cugo_graph* g, int n, const int32_t* ids, double* cov36);
 int cugo_graph_get_landmark_covariances(cugo_graph* g, int n, const int32_t* ids, double* cov9);
+/* Extension: the cross-covariance blocks Sigma_ab of the pose pairs (ids_a[k], ids_b[k]) — any pairs, in the Hsc
+ * pattern or not — at the current estimates: cov36 [n][36] (host), layout and tangent order as above, rows a and
+ * columns b; a == b gives the diagonal block, a fixed pose in the pair gives zeros.  Runs the build pass at
+ * lambda = 0, the Schur complement and one factorisation as cugo_graph_compute_covariances does, then
+ * cugo_chol_inverse_blocks.  Same error codes; also CUGO_ERR_INVALID for an id that is not a pose of the current
+ * flattening.  Leaves the estimates, the LM state and the marginals kept by cugo_graph_compute_covariances alone. */
+int cugo_graph_compute_pose_cross_covariances(cugo_graph* g, int n, const int32_t* ids_a, const int32_t* ids_b,
+                                              double* cov36);
+/* covariance of the relative pose A = T_a T_b^-1 in the tangent convention of relpose_types.h (J_a = I,
+ * J_b = -Ad(A) at Z = A):  Sigma_aa - Sigma_ab Ad(A)^T - Ad(A) Sigma_ba + Ad(A) Sigma_bb Ad(A)^T, on the host from the
+ * blocks above and the current estimates.  A positive definite result inverts to the information of a relative-pose
+ * edge that summarises the graph between a and b.  CUGO_ERR_INVALID for a == b. */
+int cugo_graph_relative_pose_covariances(cugo_graph* g, int n, const int32_t* ids_a, const int32_t* ids_b,
+                                         double* cov36);
 /* per-phase milliseconds accumulated since initialize(): ref getTimeProfile
  * (block_solver.cpp:470-488).  names is a '\n' separated list written into buf. */
 int cugo_graph_time_profile(cugo_graph* g, char* names_buf, int buf_len, double* ms, int cap);
