@@ -264,15 +264,28 @@ int cugo_icp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_icp_edges*
 
 namespace
 {
+// what the two SE(3) kinds check alike: the edge count against the kernels' 32-bit indices, the robust kernel, the arrays
+template <class Edges>
+void check_se3_edges(const char* prefix, const Edges* ev)
+{
+    auto refuse = [&](const char* what) { throw std::runtime_error(std::string(prefix) + ": " + what); };
+    if (ev->n > (1 << 26))
+        refuse("more than 2^26 edges (the kernel indexes the planar arrays with 32 bits)");
+    if (ev->rk < CUGO_RK_NONE || ev->rk > CUGO_RK_HUBER ||
+        (ev->rk != CUGO_RK_NONE && !(ev->delta > 0.0 && std::isfinite(ev->delta))))
+        refuse("unknown robust kernel or bad delta");
+    if (ev->n > 0 && (!ev->d_meas || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
+        refuse("missing arrays");
+}
 // as check_icp: pose_ptr on the host, the pose index of every edge against it on the device, before anything is launched
 cugo_k::ReduceScratch check_prior(cugo_ctx* ctx, const cugo_prior_edges* ev)
 {
     if (!ev || ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total || ev->n < 0)
         throw std::runtime_error("cugo_prior: bad pose or edge counts");
-    if (ev->n > (1 << 26))
-        throw std::runtime_error("cugo_prior: more than 2^26 edges (the kernel indexes the planar arrays with 32 bits)");
-    check_pose_kind(ctx, "cugo_prior", "", ev->n, ev->n_poses_total, ev->d_pose, ev->d_pose_ptr, ev->rk, ev->delta,
-                    !ev->d_meas || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n));
+    if (!ev->d_pose_ptr) // (check_pose_kind's first refusal comes before those of the shared check)
+        throw std::runtime_error("cugo_prior: no pose_ptr");
+    check_se3_edges("cugo_prior", ev);
+    check_pose_kind(ctx, "cugo_prior", "", ev->n, ev->n_poses_total, ev->d_pose, ev->d_pose_ptr, ev->rk, ev->delta, false);
     const size_t need = (size_t)cugo_k::prior_workgroups(*ev);
     const cugo_k::ReduceScratch rs = pose_scratch_for(ctx, need);
     check_pose_indices(ctx, "cugo_prior", "prior", {{ev->d_pose, ev->d_pose_ptr, ev->n, "k_prior_check"}}, ev->n_poses_total,
@@ -376,13 +389,7 @@ cugo_k::ReduceScratch check_relpose(cugo_ctx* ctx, const cugo_relpose_edges* ev)
         throw std::runtime_error("cugo_relpose: the pose or edge counts are not those of the plan");
     if (!ev->plan->on_device)
         throw std::runtime_error("cugo_relpose: the plan is host-only (created without a context)");
-    if (ev->n > (1 << 26))
-        throw std::runtime_error("cugo_relpose: more than 2^26 edges (the kernel indexes the planar arrays with 32 bits)");
-    if (ev->rk < CUGO_RK_NONE || ev->rk > CUGO_RK_HUBER ||
-        (ev->rk != CUGO_RK_NONE && !(ev->delta > 0.0 && std::isfinite(ev->delta))))
-        throw std::runtime_error("cugo_relpose: unknown robust kernel or bad delta");
-    if (ev->n > 0 && (!ev->d_meas || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
-        throw std::runtime_error("cugo_relpose: missing arrays");
+    check_se3_edges("cugo_relpose", ev);
     return pose_scratch_for(ctx, (size_t)cugo_k::relpose_workgroups(*ev));
 }
 void relpose_chi_total(cugo_ctx* ctx, const cugo_relpose_edges* ev, const cugo_k::ReduceScratch& rs, double* d_chi)
@@ -937,6 +944,13 @@ int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids,
         }
     });
 }
+static cugo::RobustKernelType rk_type_of(int type)
+{
+    return type == CUGO_RK_CAUCHY  ? cugo::RobustKernelType::Cauchy
+           : type == CUGO_RK_TUKEY ? cugo::RobustKernelType::Tukey
+           : type == CUGO_RK_HUBER ? cugo::RobustKernelType::Huber
+                                   : cugo::RobustKernelType::None;
+}
 static cugo::PoseVertex* icp_pose(cugo_graph* g, int32_t id)
 {
     try
@@ -1004,11 +1018,7 @@ int cugo_graph_set_icp_information(cugo_graph* g, int kind, double info)
 int cugo_graph_set_icp_robust_kernel(cugo_graph* g, int kind, int type, double delta)
 {
     return guarded([&] {
-        const cugo::RobustKernelType t = type == CUGO_RK_CAUCHY  ? cugo::RobustKernelType::Cauchy
-                                         : type == CUGO_RK_TUKEY ? cugo::RobustKernelType::Tukey
-                                         : type == CUGO_RK_HUBER ? cugo::RobustKernelType::Huber
-                                                                 : cugo::RobustKernelType::None;
-        icp_set(g, kind)->setRobustKernel(t, delta);
+        icp_set(g, kind)->setRobustKernel(rk_type_of(type), delta);
     });
 }
 int cugo_graph_set_icp_outlier_threshold(cugo_graph* g, int kind, double threshold)
@@ -1026,23 +1036,59 @@ int cugo_graph_n_icp_edges(cugo_graph* g, int kind)
 {
     return kind == CUGO_ICP_PLANE || kind == CUGO_ICP_LINE ? g->opt->nIcpEdges(kind) : -1;
 }
+// the body of cugo_graph_add_pose_priors (binary false: no ids_b) and of cugo_graph_add_relpose_edges: all or nothing
+extern "C++" {
+template <class Edge, class Set>
+static void add_se3_edges(cugo_graph* g, const char* who, std::deque<Edge>& store, Set& set, int n, const int32_t* ids_a,
+                          const int32_t* ids_b, bool binary, const double* q_t7, const double* info36)
+{
+    if (n < 0 || (n > 0 && (!ids_a || (binary && !ids_b) || !q_t7)))
+        throw std::invalid_argument(std::string(who) + ": missing arrays");
+    for (int i = 0; i < n; i++) // (an unknown id adds no edge)
+    {
+        (void)icp_pose(g, ids_a[i]);
+        if (binary)
+            (void)icp_pose(g, ids_b[i]);
+    }
+    for (int i = 0; i < n; i++)
+    {
+        store.emplace_back();
+        Edge& e = store.back();
+        e.setVertex(icp_pose(g, ids_a[i]), 0);
+        if (binary)
+            e.setVertex(icp_pose(g, ids_b[i]), 1);
+        const cugo::Se3D z(q_t7 + 7 * (size_t)i, q_t7 + 7 * (size_t)i + 4);
+        e.setMeasurement(cugo::PosePriorMatch<double>(z, info36 ? info36 + 36 * (size_t)i : set.informationMatrix()));
+        set.addEdge(&e);
+    }
+}
+}
 int cugo_graph_add_pose_priors(cugo_graph* g, int n, const int32_t* pose_ids, const double* q_t7, const double* info36)
 {
     return guarded([&] {
-        if (n < 0 || (n > 0 && (!pose_ids || !q_t7)))
-            throw std::invalid_argument("cugo_graph_add_pose_priors: missing arrays");
-        for (int i = 0; i < n; i++)
-            (void)icp_pose(g, pose_ids[i]); // (all or nothing: an unknown id adds no edge)
-        for (int i = 0; i < n; i++)
-        {
-            g->prior_store.emplace_back();
-            cugo::PosePriorEdge& e = g->prior_store.back();
-            e.setVertex(icp_pose(g, pose_ids[i]), 0);
-            const cugo::Se3D z(q_t7 + 7 * (size_t)i, q_t7 + 7 * (size_t)i + 4);
-            e.setMeasurement(cugo::PosePriorMatch<double>(z, info36 ? info36 + 36 * (size_t)i : g->prior.informationMatrix()));
-            g->prior.addEdge(&e);
-        }
+        add_se3_edges(g, "cugo_graph_add_pose_priors", g->prior_store, g->prior, n, pose_ids, nullptr, false, q_t7, info36);
     });
+}
+int cugo_graph_add_relpose_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b,
+                                 const double* q_t7, const double* info36)
+{
+    return guarded([&] {
+        add_se3_edges(g, "cugo_graph_add_relpose_edges", g->relpose_store, g->relpose, n, pose_ids_a, pose_ids_b, true, q_t7,
+                      info36);
+    });
+}
+static cugo::BaseEdgeSet* pose_kind_set(cugo_graph* g, int kind)
+{
+    if (!g)
+        throw std::invalid_argument("cugo: null graph");
+    switch (kind)
+    {
+    case CUGO_POSE_KIND_PLANE: return &g->plane;
+    case CUGO_POSE_KIND_LINE: return &g->line;
+    case CUGO_POSE_KIND_PRIOR: return &g->prior;
+    case CUGO_POSE_KIND_RELPOSE: return &g->relpose;
+    }
+    throw std::invalid_argument("cugo: kind must be one of CUGO_POSE_KIND_PLANE (0), _LINE (1), _PRIOR (2), _RELPOSE (3)");
 }
 int cugo_graph_set_prior_information(cugo_graph* g, const double* info36)
 {
@@ -1050,41 +1096,6 @@ int cugo_graph_set_prior_information(cugo_graph* g, const double* info36)
         if (!info36)
             throw std::invalid_argument("cugo_graph_set_prior_information: no matrix");
         g->prior.setInformationMatrix(info36);
-    });
-}
-int cugo_graph_set_prior_robust_kernel(cugo_graph* g, int type, double delta)
-{
-    return guarded([&] {
-        const cugo::RobustKernelType t = type == CUGO_RK_CAUCHY  ? cugo::RobustKernelType::Cauchy
-                                         : type == CUGO_RK_TUKEY ? cugo::RobustKernelType::Tukey
-                                         : type == CUGO_RK_HUBER ? cugo::RobustKernelType::Huber
-                                                                 : cugo::RobustKernelType::None;
-        g->prior.setRobustKernel(t, delta);
-    });
-}
-int cugo_graph_set_prior_outlier_threshold(cugo_graph* g, double threshold)
-{
-    return guarded([&] { g->prior.setOutlierThreshold(threshold); });
-}
-int cugo_graph_n_prior_edges(cugo_graph* g) { return g->opt->nPriorEdges(); }
-int cugo_graph_add_relpose_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b,
-                                 const double* q_t7, const double* info36)
-{
-    return guarded([&] {
-        if (n < 0 || (n > 0 && (!pose_ids_a || !pose_ids_b || !q_t7)))
-            throw std::invalid_argument("cugo_graph_add_relpose_edges: missing arrays");
-        for (int i = 0; i < n; i++) // (all or nothing: an unknown id adds no edge)
-            (void)icp_pose(g, pose_ids_a[i]), (void)icp_pose(g, pose_ids_b[i]);
-        for (int i = 0; i < n; i++)
-        {
-            g->relpose_store.emplace_back();
-            cugo::RelPoseEdge& e = g->relpose_store.back();
-            e.setVertex(icp_pose(g, pose_ids_a[i]), 0);
-            e.setVertex(icp_pose(g, pose_ids_b[i]), 1);
-            const cugo::Se3D z(q_t7 + 7 * (size_t)i, q_t7 + 7 * (size_t)i + 4);
-            e.setMeasurement(cugo::PosePriorMatch<double>(z, info36 ? info36 + 36 * (size_t)i : g->relpose.informationMatrix()));
-            g->relpose.addEdge(&e);
-        }
     });
 }
 int cugo_graph_set_relpose_information(cugo_graph* g, const double* info36)
@@ -1095,20 +1106,23 @@ int cugo_graph_set_relpose_information(cugo_graph* g, const double* info36)
         g->relpose.setInformationMatrix(info36);
     });
 }
+int cugo_graph_set_prior_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    return guarded([&] { pose_kind_set(g, CUGO_POSE_KIND_PRIOR)->setRobustKernel(rk_type_of(type), delta); });
+}
 int cugo_graph_set_relpose_robust_kernel(cugo_graph* g, int type, double delta)
 {
-    return guarded([&] {
-        const cugo::RobustKernelType t = type == CUGO_RK_CAUCHY  ? cugo::RobustKernelType::Cauchy
-                                         : type == CUGO_RK_TUKEY ? cugo::RobustKernelType::Tukey
-                                         : type == CUGO_RK_HUBER ? cugo::RobustKernelType::Huber
-                                                                 : cugo::RobustKernelType::None;
-        g->relpose.setRobustKernel(t, delta);
-    });
+    return guarded([&] { pose_kind_set(g, CUGO_POSE_KIND_RELPOSE)->setRobustKernel(rk_type_of(type), delta); });
+}
+int cugo_graph_set_prior_outlier_threshold(cugo_graph* g, double threshold)
+{
+    return guarded([&] { g->prior.setOutlierThreshold(threshold); });
 }
 int cugo_graph_set_relpose_outlier_threshold(cugo_graph* g, double threshold)
 {
     return guarded([&] { g->relpose.setOutlierThreshold(threshold); });
 }
+int cugo_graph_n_prior_edges(cugo_graph* g) { return g->opt->nPriorEdges(); }
 int cugo_graph_set_relpose_active(cugo_graph* g, int first, int n, const uint8_t* active)
 {
     return guarded([&] {
@@ -1138,14 +1152,10 @@ int cugo_graph_set_information(cugo_graph* g, int dim, double info)
 }
 int cugo_graph_set_robust_kernel(cugo_graph* g, int dim, int type, double delta)
 {
-    const cugo::RobustKernelType t = type == CUGO_RK_CAUCHY  ? cugo::RobustKernelType::Cauchy
-                                     : type == CUGO_RK_TUKEY ? cugo::RobustKernelType::Tukey
-                                     : type == CUGO_RK_HUBER ? cugo::RobustKernelType::Huber
-                                                             : cugo::RobustKernelType::None;
     if (dim == 3)
-        g->stereo.setRobustKernel(t, delta);
+        g->stereo.setRobustKernel(rk_type_of(type), delta);
     else
-        g->mono.setRobustKernel(t, delta);
+        g->mono.setRobustKernel(rk_type_of(type), delta);
     return CUGO_OK;
 }
 int cugo_graph_set_outlier_threshold(cugo_graph* g, int dim, double threshold)
@@ -1170,19 +1180,6 @@ int cugo_graph_get_edge_active(cugo_graph* g, int dim, int n, uint8_t* active)
             for (int i = 0; i < n && i < (int)g->mono_store.size(); i++)
                 active[i] = g->mono_store[i].isActive() ? 1 : 0;
     });
-}
-static cugo::BaseEdgeSet* pose_kind_set(cugo_graph* g, int kind)
-{
-    if (!g)
-        throw std::invalid_argument("cugo: null graph");
-    switch (kind)
-    {
-    case CUGO_POSE_KIND_PLANE: return &g->plane;
-    case CUGO_POSE_KIND_LINE: return &g->line;
-    case CUGO_POSE_KIND_PRIOR: return &g->prior;
-    case CUGO_POSE_KIND_RELPOSE: return &g->relpose;
-    }
-    throw std::invalid_argument("cugo: kind must be one of CUGO_POSE_KIND_PLANE (0), _LINE (1), _PRIOR (2), _RELPOSE (3)");
 }
 int cugo_graph_n_pose_edge_outliers(cugo_graph* g, int kind)
 {

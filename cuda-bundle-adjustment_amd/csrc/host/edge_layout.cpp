@@ -377,19 +377,10 @@ void pose_major_view(int Pall, const Idx& slot_pose, const Idx& slot_src, Idx& p
     });
 }
 
-void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHost& b)
+void copy_pose_edges_planar(const FlatPoseKind& fk, const int32_t* slot_of, PoseKindHost& b)
 {
     const int n = fk.n(), mw = fk.meas_w, ww = fk.weight_w;
-    b.h_ptr.assign((size_t)Pall + 1, 0);
-    for (int e = 0; e < n; e++)
-    {
-        if (fk.pose[e] < 0 || fk.pose[e] >= P)
-            throw std::runtime_error(std::string("cugo: a ") + pose_kind_group(fk.kind) +
-                                     (fk.kind == POSE_KIND_PRIOR ? "" : " edge") + " is not on a free pose");
-        b.h_ptr[(size_t)fk.pose[e] + 1]++;
-    }
-    std::partial_sum(b.h_ptr.begin(), b.h_ptr.end(), b.h_ptr.begin());
-    b.h_pose.resize(n), b.slot_set.resize(n), b.slot_edge.resize(n);
+    b.h_pose.resize(n), b.h_pose_b.resize(fk.pose_b.size()), b.slot_set.resize(n), b.slot_edge.resize(n);
     b.h_meas.resize((size_t)mw * n);
     const bool per_edge = fk.weight.size() > (size_t)ww;
     b.n_weight = per_edge ? n : 1;
@@ -398,11 +389,12 @@ void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHo
         std::copy(fk.weight.begin(), fk.weight.end(), b.h_weight.begin());
     const bool per_edge_threshold = fk.threshold.size() > 1;
     b.h_threshold = fk.threshold; // (empty or one entry: as it is)
-    std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1);
-    for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
+    for (int e = 0; e < n; e++)
     {
-        const size_t i = (size_t)pos[fk.pose[e]]++;
+        const size_t i = slot_of ? (size_t)slot_of[e] : (size_t)e;
         b.h_pose[i] = fk.pose[e];
+        if (!fk.pose_b.empty())
+            b.h_pose_b[i] = fk.pose_b[e];
         b.slot_set[i] = fk.src_set[e], b.slot_edge[i] = fk.src_edge[e];
         for (int c = 0; c < mw; c++)
             b.h_meas[(size_t)c * n + i] = fk.meas[(size_t)mw * e + c];
@@ -412,6 +404,24 @@ void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHo
         if (per_edge_threshold)
             b.h_threshold[i] = fk.threshold[e];
     }
+}
+
+void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHost& b)
+{
+    const int n = fk.n();
+    b.h_ptr.assign((size_t)Pall + 1, 0);
+    for (int e = 0; e < n; e++)
+    {
+        if (fk.pose[e] < 0 || fk.pose[e] >= P)
+            throw std::runtime_error(std::string("cugo: a ") + pose_kind_group(fk.kind) +
+                                     (fk.kind == POSE_KIND_PRIOR ? "" : " edge") + " is not on a free pose");
+        b.h_ptr[(size_t)fk.pose[e] + 1]++;
+    }
+    std::partial_sum(b.h_ptr.begin(), b.h_ptr.end(), b.h_ptr.begin());
+    std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1), slot_of(n);
+    for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
+        slot_of[e] = pos[fk.pose[e]]++;
+    copy_pose_edges_planar(fk, slot_of.data(), b);
 }
 
 // ---- the Hsc structure on the host: pose-major co-visibility, pattern (O(M) with a marker array instead of the

@@ -59,15 +59,20 @@ void fill_slots(const FlatGraph& g, const Idx& order, const Idx& slot_src, SlotA
 // pose_edge[pose_ptr[p] .. pose_ptr[p + 1]): the real slots of pose p in slot order (= ascending landmark)
 void pose_major_view(int Pall, const Idx& slot_pose, const Idx& slot_src, Idx& pose_ptr, Idx& pose_edge);
 
-// the unary pose edges of one kind sorted by pose (stable: container order inside a pose), planar: meas [meas_w][n],
-// weight [weight_w][n_weight] with n_weight = n, or 1 when one value serves all (an empty kind: one column of zeros)
+// the pose edges of one kind as the kernels read them, planar: meas [meas_w][n], weight [weight_w][n_weight] with
+// n_weight = n, or 1 when one value serves all (an empty kind: one column of zeros)
 struct PoseKindHost
 {
-    Idx h_pose, h_ptr, slot_set, slot_edge;
+    Idx h_pose, h_pose_b, h_ptr, slot_set, slot_edge; // (h_pose_b: relative pose alone; h_ptr: the unary kinds alone)
     std::vector<double> h_meas, h_weight;
     int n_weight = 1;
-    std::vector<double> h_threshold; // FlatPoseKind::threshold in the sorted order (n entries, 1, or empty)
+    std::vector<double> h_threshold; // FlatPoseKind::threshold in the order of the slots (n entries, 1, or empty)
 };
+// edge e of the kind to slot slot_of[e] (nullptr: the edges stay in container order); slot_set / slot_edge: where the
+// edge of a slot came from
+void copy_pose_edges_planar(const FlatPoseKind& kind, const int32_t* slot_of, PoseKindHost& out);
+// a unary kind sorted by pose (stable: container order inside a pose), with the CSR h_ptr over all Pall poses; throws
+// on an edge that is not on a free pose
 void sort_pose_edges_by_pose(const FlatPoseKind& kind, int Pall, int P, PoseKindHost& out);
 
 // ---- the Hsc structure on the host: pattern (upper block CSR, diagonal first) and, from the LOCAL slots, the

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <memory>
 #include <thread>
 
@@ -105,12 +106,12 @@ struct Engine::Impl : cugo_k::LaunchHook
     const std::vector<int32_t>& pat_ptr() const { return pair_lo.empty() ? cov_ptr : aug_ptr; }
     const std::vector<int32_t>& pat_pose() const { return pair_lo.empty() ? cov_pose : aug_pose; }
     int pat_lists() const { return L + (int)pair_lo.size(); }
-    void build_pair_lists(const FlatRelPose& fr)
+    void build_pair_lists(const FlatPoseKind& fr)
     {
         std::vector<std::pair<int32_t, int32_t>> pr;
         for (int e = 0; e < fr.n(); e++)
-            if (fr.pose_a[e] < P && fr.pose_b[e] < P)
-                pr.emplace_back(std::min(fr.pose_a[e], fr.pose_b[e]), std::max(fr.pose_a[e], fr.pose_b[e]));
+            if (fr.pose[e] < P && fr.pose_b[e] < P)
+                pr.emplace_back(std::min(fr.pose[e], fr.pose_b[e]), std::max(fr.pose[e], fr.pose_b[e]));
         std::sort(pr.begin(), pr.end());
         pr.erase(std::unique(pr.begin(), pr.end()), pr.end());
         pair_lo.clear(), pair_hi.clear(), aug_ptr.clear(), aug_pose.clear();
@@ -156,46 +157,42 @@ struct Engine::Impl : cugo_k::LaunchHook
     PinnedBuf<int32_t> h_fail;
 
     cugo_edges ev{};
-    // The unary pose edge kinds (FlatGraph::kinds): point-to-plane / point-to-line (icp_kernels.hip) and SE(3) priors
-    // (prior_kernels.hip).  Each kind sorted by pose (stable: container order inside a pose), structure of arrays, on
-    // the device as long as the flattening lives; the views the kernels take; and a scratch of their own (the BA scratch
-    // holds live scale / chi2 partials and records across the same span of the stream):
-    //     [ICP partials | ICP chunk chi2 totals | prior workgroup chi2 totals | 16 doubles of slack]
-    // The two runs of totals are adjacent, so that the launch ending a trial sums them as one array (chi_totals).
-    // The relative-pose edges (FlatGraph::relpose, relpose_kernels.hip) live here too: binary, in container order, with
-    // a plan (relpose_plan.h) against the Hsc pattern in place of a sort; their workgroup totals are a third run behind
-    // the priors'.  Every launch of theirs sits under n_relpose_wg: a graph without such edges queues what it always did.
+    // The pose edge kinds (FlatGraph::kinds): point-to-plane / point-to-line (icp_kernels.hip), SE(3) priors
+    // (prior_kernels.hip) and relative-pose edges (relpose_kernels.hip).  Each kind planar (structure of arrays) on the
+    // device as long as the flattening lives — the unary kinds sorted by pose (stable: container order inside a pose),
+    // the relative-pose edges in container order with a plan (relpose_plan.h) against the Hsc pattern in place of a
+    // sort; the views the kernels take; and a scratch of their own (the BA scratch holds live scale / chi2 partials and
+    // records across the same span of the stream):
+    //     [ICP partials | ICP chunk chi2 totals | prior workgroup chi2 totals | relative-pose workgroup chi2 totals |
+    //      16 doubles of slack]
+    // The runs of totals are adjacent, so that the launch ending a trial sums them as one array (chi_totals).  Every
+    // launch of a kind sits under its count of totals: a graph without the kind queues what it always did.
     struct PoseEdges
     {
         struct KindBufs : PoseKindHost
         {
-            DevBuf<int32_t> d_pose, d_ptr;
+            DevBuf<int32_t> d_pose, d_pose_b, d_ptr;
             DevBuf<double> d_meas, d_weight;
         } kind[POSE_KIND_COUNT];
         cugo_icp_edges icp{};
         cugo_prior_edges prior{};
-        int n_icp = 0, n_prior = 0;
-        int n_icp_chi = 0, n_prior_wg = 0; // totals an ICP pass / a prior pass leaves (0: the pass is not launched)
+        cugo_relpose_edges relpose{};
+        int n_icp = 0, n_prior = 0, n_relpose = 0;
+        // totals an ICP pass / a prior pass / a relative-pose pass leaves (0: the pass is not launched)
+        int n_icp_chi = 0, n_prior_wg = 0, n_relpose_wg = 0;
         DevBuf<double> d_scratch;
         size_t off_icp_chi = 0, off_prior_chi = 0, off_relpose_chi = 0; // the layout above, set by bind()
-        struct RelPose
+        struct RelPosePlan
         {
-            std::vector<int32_t> h_pose_a, h_pose_b;
-            std::vector<int32_t> src_set, src_edge; // FlatRelPose's: where an edge came from
-            std::vector<double> h_meas, h_info; // planar [7][n], [21][n_info]
-            DevBuf<int32_t> d_pose_a, d_pose_b, d_inc_ptr, d_inc, d_off_blk;
-            DevBuf<double> d_meas, d_info;
+            DevBuf<int32_t> d_inc_ptr, d_inc, d_off_blk;
             RelPosePlanHost plan;
             bool plan_dirty = true; // the plan is not that of the edges and the Hsc pattern at hand
             cugo_k::RelPosePlanDev dev{};
         } rp;
-        cugo_relpose_edges relpose{};
-        int n_relpose = 0, n_relpose_wg = 0; // edges; totals a relative-pose pass leaves (0: never launched)
-        // Outlier rejection (Engine::reject_pose_outliers), per kind (PoseKind, then the relative-pose edges) and only
-        // for a kind in which some threshold is positive: the run-time flags the kind's view points at (all zero until
-        // edges go), a host copy of them, and the thresholds in the order of the edges on the device (n or 1).  Every
-        // other kind keeps a NULL flag pointer in its view and queues what it always queued.
-        static constexpr int REJ_RELPOSE = POSE_KIND_COUNT, REJ_KINDS = POSE_KIND_COUNT + 1;
+        // Outlier rejection (Engine::reject_pose_outliers), per kind and only for a kind in which some threshold is
+        // positive: the run-time flags the kind's view points at (all zero until edges go), a host copy of them, and the
+        // thresholds in the order of the edges on the device (n or 1).  Every other kind keeps a NULL flag pointer in its
+        // view and queues what it always queued.
         struct Reject
         {
             DevBuf<uint8_t> d_flags;
@@ -203,7 +200,7 @@ struct Engine::Impl : cugo_k::LaunchHook
             DevBuf<double> d_threshold;
             int n_threshold = 0; // 0: the kind has no threshold
             bool on() const { return n_threshold > 0; }
-        } rej[REJ_KINDS];
+        } rej[POSE_KIND_COUNT];
         DevBuf<double> d_rej_chi;              // the chi2 term of every edge of the kind(s) at hand
         DevBuf<int32_t> d_rej_list, d_rej_work; // the outlier pass's list and its workgroup counts
         bool any_reject() const
@@ -213,9 +210,11 @@ struct Engine::Impl : cugo_k::LaunchHook
                 any = any || r.on();
             return any;
         }
-        // flags and thresholds of kind k over its n edges: nullptr (and nothing allocated) without a positive threshold
-        const uint8_t* bind_reject(int k, int n, const std::vector<double>& threshold, hipStream_t stream, bool plan_only)
+        // flags and thresholds of kind k over its edges: nullptr (and nothing allocated) without a positive threshold
+        const uint8_t* bind_reject(int k, hipStream_t stream, bool plan_only)
         {
+            const int n = n_edges(k);
+            const std::vector<double>& threshold = kind[k].h_threshold;
             Reject& r = rej[k];
             r.n_threshold = 0;
             r.h_flags.clear();
@@ -235,30 +234,39 @@ struct Engine::Impl : cugo_k::LaunchHook
         double* prior_chi() { return d_scratch.data() + off_prior_chi; }
         int n_edges(int k) const { return (int)kind[k].h_pose.size(); }
         const std::vector<int32_t>& icp_slot_source(int k, bool set) const { return set ? kind[k].slot_set : kind[k].slot_edge; }
-        // the chi2 totals of the last ICP pass and of the last prior pass, one array; nullptr / 0 without such edges
+        // the chi2 totals of the last ICP, prior and relative-pose pass, one array; nullptr / 0 without such edges
         const double* chi_totals(int* n)
         {
             *n = n_icp_chi + n_prior_wg + n_relpose_wg;
             return *n ? d_scratch.data() + off_icp_chi : nullptr;
         }
 
-        // sort, upload by the calling thread (plan_only: no device), views and scratch layout
+        // planar copies (the unary kinds: sorted), upload by the calling thread (plan_only: no device), views and scratch
+        // layout.  The relative-pose plan waits for the Hsc pattern (bind_relpose_plan)
         void bind(const FlatGraph& g, int Pall, int P, hipStream_t stream, bool plan_only)
         {
             n_icp = g.kinds[POSE_KIND_PLANE].n() + g.kinds[POSE_KIND_LINE].n();
-            n_prior = g.kinds[POSE_KIND_PRIOR].n();
+            n_prior = g.kinds[POSE_KIND_PRIOR].n(), n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
             for (int k = 0; k < POSE_KIND_COUNT; k++)
             {
                 KindBufs& b = kind[k];
-                sort_pose_edges_by_pose(g.kinds[k], Pall, P, b);
+                const bool binary = k == POSE_KIND_RELPOSE, is_icp = k == POSE_KIND_PLANE || k == POSE_KIND_LINE;
+                if (!binary)
+                    sort_pose_edges_by_pose(g.kinds[k], Pall, P, b);
+                else if (n_relpose > (1 << 26))
+                    throw std::runtime_error("cugo: more than 2^26 relative-pose edges");
+                else
+                    copy_pose_edges_planar(g.kinds[k], nullptr, b);
                 // an empty kind uploads nothing, except that k_icp_finish reads the pose_ptr of BOTH ICP kinds whenever
                 // either has edges: the empty one's is all zeros
-                if (plan_only || !(g.kinds[k].n() || (k != POSE_KIND_PRIOR && n_icp)))
+                if (plan_only || !(g.kinds[k].n() || (is_icp && n_icp)))
                     continue;
-                b.d_pose.upload(b.h_pose, stream), b.d_ptr.upload(b.h_ptr, stream);
+                b.d_pose.upload(b.h_pose, stream);
+                binary ? b.d_pose_b.upload(b.h_pose_b, stream) : b.d_ptr.upload(b.h_ptr, stream);
                 b.d_meas.upload(b.h_meas, stream), b.d_weight.upload(b.h_weight, stream);
             }
-            const KindBufs &pl = kind[POSE_KIND_PLANE], &li = kind[POSE_KIND_LINE], &pr = kind[POSE_KIND_PRIOR];
+            const KindBufs &pl = kind[POSE_KIND_PLANE], &li = kind[POSE_KIND_LINE], &pr = kind[POSE_KIND_PRIOR],
+                           &rl = kind[POSE_KIND_RELPOSE];
             icp = cugo_icp_edges{};
             icp.n_poses_total = Pall, icp.n_poses_free = P;
             icp.n_plane = n_edges(POSE_KIND_PLANE), icp.n_line = n_edges(POSE_KIND_LINE);
@@ -271,56 +279,29 @@ struct Engine::Impl : cugo_k::LaunchHook
             icp.d_line_p = li.d_meas.data(), icp.d_line_au = li.d_meas.data() + 3 * (size_t)icp.n_line;
             icp.d_line_omega = li.d_weight.data(), icp.n_line_omega = li.n_weight;
             icp.rk_line = g.kinds[POSE_KIND_LINE].rk, icp.delta_line = g.kinds[POSE_KIND_LINE].delta;
-            icp.d_plane_flags = bind_reject(POSE_KIND_PLANE, icp.n_plane, pl.h_threshold, stream, plan_only);
-            icp.d_line_flags = bind_reject(POSE_KIND_LINE, icp.n_line, li.h_threshold, stream, plan_only);
+            icp.d_plane_flags = bind_reject(POSE_KIND_PLANE, stream, plan_only);
+            icp.d_line_flags = bind_reject(POSE_KIND_LINE, stream, plan_only);
             prior = cugo_prior_edges{};
             prior.n_poses_total = Pall, prior.n_poses_free = P, prior.n = n_prior;
             prior.d_pose = pr.d_pose.data(), prior.d_pose_ptr = pr.d_ptr.data();
             prior.d_meas = pr.d_meas.data(), prior.d_info = pr.d_weight.data(), prior.n_info = pr.n_weight;
             prior.rk = g.kinds[POSE_KIND_PRIOR].rk, prior.delta = g.kinds[POSE_KIND_PRIOR].delta;
-            prior.d_flags = bind_reject(POSE_KIND_PRIOR, n_prior, pr.h_threshold, stream, plan_only);
+            prior.d_flags = bind_reject(POSE_KIND_PRIOR, stream, plan_only);
+            relpose = cugo_relpose_edges{};
+            relpose.n_poses_total = Pall, relpose.n_poses_free = P, relpose.n = n_relpose;
+            relpose.d_meas = rl.d_meas.data(), relpose.d_info = rl.d_weight.data(), relpose.n_info = rl.n_weight;
+            relpose.rk = g.kinds[POSE_KIND_RELPOSE].rk, relpose.delta = g.kinds[POSE_KIND_RELPOSE].delta;
+            // (run-time flags: the plan is still built with none, and an edge flagged here "counts for nothing")
+            relpose.d_flags = bind_reject(POSE_KIND_RELPOSE, stream, plan_only);
+            rp.plan_dirty = true;
             // the scratch layout (the chunk totals end the ICP part)
             const size_t icp_doubles = n_icp ? cugo_k::icp_scratch_doubles(icp) : 0;
             n_icp_chi = n_icp ? cugo_k::icp_chunk_count(icp) : 0;
-            n_prior_wg = cugo_k::prior_workgroups(prior);
+            n_prior_wg = cugo_k::prior_workgroups(prior), n_relpose_wg = cugo_k::relpose_workgroups(relpose);
             off_icp_chi = icp_doubles - n_icp_chi, off_prior_chi = icp_doubles;
-            bind_relpose(g.relpose, Pall, P, stream, plan_only);
             off_relpose_chi = off_prior_chi + (size_t)n_prior_wg;
             if ((n_icp || n_prior_wg || n_relpose_wg) && !plan_only)
                 d_scratch.resize(icp_doubles + (size_t)n_prior_wg + (size_t)n_relpose_wg + 16);
-        }
-        // the relative-pose edges: planar copies, upload, the view the kernels take.  The plan waits for the Hsc pattern
-        // (bind_relpose_plan)
-        void bind_relpose(const FlatRelPose& fr, int Pall, int P, hipStream_t stream, bool plan_only)
-        {
-            const int n = n_relpose = fr.n();
-            rp.plan_dirty = true;
-            relpose = cugo_relpose_edges{};
-            relpose.n_poses_total = Pall, relpose.n_poses_free = P, relpose.n = n;
-            relpose.rk = fr.rk, relpose.delta = fr.delta;
-            n_relpose_wg = cugo_k::relpose_workgroups(relpose);
-            // (run-time flags: the plan is still built with none, and an edge flagged here "counts for nothing")
-            relpose.d_flags = bind_reject(REJ_RELPOSE, n, fr.threshold, stream, plan_only);
-            if (!n)
-                return;
-            if (n > (1 << 26))
-                throw std::runtime_error("cugo: more than 2^26 relative-pose edges");
-            rp.h_pose_a = fr.pose_a, rp.h_pose_b = fr.pose_b;
-            rp.src_set = fr.src_set, rp.src_edge = fr.src_edge;
-            const int n_info = fr.weight.size() > 21 ? n : 1;
-            rp.h_meas.resize(7 * (size_t)n), rp.h_info.resize(21 * (size_t)n_info);
-            for (int e = 0; e < n; e++)
-                for (int c = 0; c < 7; c++)
-                    rp.h_meas[(size_t)c * n + e] = fr.meas[7 * (size_t)e + c];
-            for (int e = 0; e < n_info; e++)
-                for (int c = 0; c < 21; c++)
-                    rp.h_info[(size_t)c * n_info + e] = fr.weight[21 * (size_t)e + c];
-            relpose.n_info = n_info;
-            if (plan_only)
-                return;
-            rp.d_pose_a.upload(rp.h_pose_a, stream), rp.d_pose_b.upload(rp.h_pose_b, stream);
-            rp.d_meas.upload(rp.h_meas, stream), rp.d_info.upload(rp.h_info, stream);
-            relpose.d_meas = rp.d_meas.data(), relpose.d_info = rp.d_info.data();
         }
         // the plan against the Hsc pattern at hand (upper block CSR over the free poses): the engine made the pattern
         // from these very pairs, so a pair missing from it is a defect of the engine and throws
@@ -332,14 +313,15 @@ struct Engine::Impl : cugo_k::LaunchHook
             rp.plan_dirty = false;
             if (!n_relpose)
                 return;
-            build_relpose_plan(n_relpose, relpose.n_poses_total, relpose.n_poses_free, rp.h_pose_a.data(), rp.h_pose_b.data(),
+            KindBufs& rl = kind[POSE_KIND_RELPOSE];
+            build_relpose_plan(n_relpose, relpose.n_poses_total, relpose.n_poses_free, rl.h_pose.data(), rl.h_pose_b.data(),
                                nullptr, rowptr.data(), colind.data(), rp.plan);
             if (plan_only)
                 return;
             rp.d_inc_ptr.upload(rp.plan.inc_ptr, stream), rp.d_inc.upload(rp.plan.inc, stream);
             rp.d_off_blk.upload(rp.plan.off_blk, stream);
             CUGO_HIP(hipStreamSynchronize(stream));
-            rp.dev = cugo_k::RelPosePlanDev{n_relpose, relpose.n_poses_free, rp.d_pose_a.data(), rp.d_pose_b.data(),
+            rp.dev = cugo_k::RelPosePlanDev{n_relpose, relpose.n_poses_free, rl.d_pose.data(), rl.d_pose_b.data(),
                                             rp.d_inc_ptr.data(), rp.d_inc.data(), rp.d_off_blk.data()};
         }
         // The pose edge terms of a build pass at `poses`.  Two-stream form: the ICP chunk pass and its add, then the
@@ -1130,22 +1112,23 @@ void Engine::initialize(FlatGraph& g)
     m.rk = g.rk;
     m.init_rank = m.rank, m.init_world = m.world;
     m.Etot = g.n_edges();
-    E_global_ = m.Etot + g.n_pose_edges() + g.relpose.n();
-    if (g.relpose.n() && (m.world > 1 || m.comm))
+    const int n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
+    E_global_ = m.Etot + g.n_pose_edges() + n_relpose;
+    if (n_relpose && (m.world > 1 || m.comm))
         throw std::runtime_error("cugo: relative-pose edge sets are not supported on a landmark-sharded (multi-GPU) "
                                  "optimiser yet");
     // (k_hsc_offdiag_strip reads the list entry before a block's range: a pair block without products has none)
-    if (g.relpose.n() && m.opt.hsc_strip)
+    if (n_relpose && m.opt.hsc_strip)
         throw std::runtime_error("cugo: relative-pose edge sets cannot be combined with CUGO_HSC_STRIP=1: the row-strip "
                                  "form of the Schur complement cannot hold a block without landmark products");
-    for (int k = POSE_KIND_COUNT - 1; k >= 0; k--) // (priors first: the message a graph with several kinds has always got)
+    for (int k = POSE_KIND_PRIOR; k >= 0; k--) // (priors first: the message a graph with several kinds has always got)
         if (g.kinds[k].n() && (m.world > 1 || m.comm))
             throw std::runtime_error(std::string("cugo: ") + pose_kind_group(k) +
                                      " edge sets are not supported on a landmark-sharded (multi-GPU) optimiser yet");
     sort_landmark_major(g, m.st_lm_cnt, m.st_order);
     laps.lap("engine: landmark sort");
     build_covisibility(g, m.st_lm_cnt, m.st_order, m.cov_ptr, m.cov_pose);
-    m.build_pair_lists(g.relpose);
+    m.build_pair_lists(g.kinds[POSE_KIND_RELPOSE]);
     laps.lap("engine: co-visibility");
     // the helper starts before the slot work ...
     const bool helper_started = m.start_pattern_helper(prof_);
@@ -1840,15 +1823,17 @@ std::vector<Engine::PoseOutliers> Engine::reject_pose_outliers()
 {
     Impl& m = *impl_;
     Impl::PoseEdges& pe = m.pe;
-    std::vector<PoseOutliers> out(Impl::PoseEdges::REJ_KINDS);
+    std::vector<PoseOutliers> out(POSE_KIND_COUNT);
     if (m.plan_only || !pe.any_reject())
         return out;
     hipStream_t s = m.ctx.stream;
     const double* poses = m.d_poses[m.last_err_buf].data(); // (the estimates the BA path judges at)
-    // the outlier pass over the n edges of kind k whose chi2 terms are at d_chi, and the way back to the edge sets
-    // through set_of / edge_of (the kind's order on the device)
-    auto reject = [&](int k, int n, const double* d_chi, const std::vector<int32_t>& set_of, const std::vector<int32_t>& edge_of) {
+    // the outlier pass over the edges of kind k whose chi2 terms are at d_chi, and the way back to the edge sets through
+    // the kind's slot_set / slot_edge (its order on the device)
+    auto reject = [&](int k, const double* d_chi) {
         Impl::PoseEdges::Reject& r = pe.rej[k];
+        const int n = pe.n_edges(k);
+        const std::vector<int32_t>&set_of = pe.kind[k].slot_set, &edge_of = pe.kind[k].slot_edge;
         pe.d_rej_list.resize((size_t)n), pe.d_rej_work.resize(cugo_k::pose_reject_work_ints(n));
         const int32_t* d_count = cugo_k::launch_pose_reject(s, n, d_chi, r.d_threshold.data(), r.n_threshold > 1,
                                                             r.d_flags.data(), pe.d_rej_list.data(), pe.d_rej_work.data());
@@ -1871,31 +1856,35 @@ std::vector<Engine::PoseOutliers> Engine::reject_pose_outliers()
         // The error passes below overwrite the chi2 totals in the pose-edge scratch (and the ICP partials).  Nothing
         // reads them afterwards: every optimize() starts from a fresh LmState (no speculative pass is pending) with a
         // build pass that writes partials and totals anew, flags included.
+        // Per kind: the error pass that leaves the chi2 term of each of its n_pass edges (the two ICP kinds share one,
+        // the line edges behind the plane edges; a relative-pose pass writes only the edges that count: the rest stay 0)
+        // and where the kind's terms begin in it
+        using Pass = std::function<void(double*)>;
+        const Pass icp = [&](double* d) { cugo_k::launch_icp_chunks(s, pe.icp, poses, false, pe.icp_rs(), d); };
+        const Pass prior = [&](double* d) { cugo_k::launch_prior_errors(s, pe.prior, poses, pe.prior_chi(), d); };
+        const Pass relpose = [&](double* d) { cugo_k::launch_relpose_errors(s, pe.relpose, pe.rp.dev, poses, pe.relpose_chi(), d); };
         const int n_plane = pe.icp.n_plane, n_line = pe.icp.n_line;
-        if (pe.rej[POSE_KIND_PLANE].on() || pe.rej[POSE_KIND_LINE].on())
-        { // (plane edges first, then the line edges)
-            pe.d_rej_chi.resize((size_t)n_plane + n_line);
-            pe.d_rej_chi.zero(s);
-            cugo_k::launch_icp_chunks(s, pe.icp, poses, false, pe.icp_rs(), pe.d_rej_chi.data());
-            for (int k : {POSE_KIND_PLANE, POSE_KIND_LINE})
-                if (pe.rej[k].on())
-                    reject(k, k == POSE_KIND_PLANE ? n_plane : n_line, pe.d_rej_chi.data() + (k == POSE_KIND_PLANE ? 0 : n_plane),
-                           pe.kind[k].slot_set, pe.kind[k].slot_edge);
-        }
-        if (pe.rej[POSE_KIND_PRIOR].on())
+        const struct
         {
-            pe.d_rej_chi.resize((size_t)pe.n_prior);
-            pe.d_rej_chi.zero(s);
-            cugo_k::launch_prior_errors(s, pe.prior, poses, pe.prior_chi(), pe.d_rej_chi.data());
-            reject(POSE_KIND_PRIOR, pe.n_prior, pe.d_rej_chi.data(), pe.kind[POSE_KIND_PRIOR].slot_set,
-                   pe.kind[POSE_KIND_PRIOR].slot_edge);
-        }
-        if (pe.rej[Impl::PoseEdges::REJ_RELPOSE].on() && pe.n_relpose_wg)
-        { // (the pass writes only the edges that count: the rest stay 0)
-            pe.d_rej_chi.resize((size_t)pe.n_relpose);
-            pe.d_rej_chi.zero(s);
-            cugo_k::launch_relpose_errors(s, pe.relpose, pe.rp.dev, poses, pe.relpose_chi(), pe.d_rej_chi.data());
-            reject(Impl::PoseEdges::REJ_RELPOSE, pe.n_relpose, pe.d_rej_chi.data(), pe.rp.src_set, pe.rp.src_edge);
+            int kind, n_pass;
+            const Pass* pass;
+            size_t off;
+        } table[] = {{POSE_KIND_PLANE, n_plane + n_line, &icp, 0},
+                     {POSE_KIND_LINE, n_plane + n_line, &icp, (size_t)n_plane},
+                     {POSE_KIND_PRIOR, pe.n_prior, &prior, 0},
+                     {POSE_KIND_RELPOSE, pe.n_relpose_wg ? pe.n_relpose : 0, &relpose, 0}};
+        const Pass* ran = nullptr;
+        for (const auto& row : table)
+        {
+            if (!pe.rej[row.kind].on() || !row.n_pass)
+                continue;
+            if (row.pass != ran)
+            {
+                pe.d_rej_chi.resize((size_t)row.n_pass);
+                pe.d_rej_chi.zero(s);
+                (*(ran = row.pass))(pe.d_rej_chi.data());
+            }
+            reject(row.kind, pe.d_rej_chi.data() + row.off);
         }
     });
     m.collect_times();

@@ -18,21 +18,24 @@ struct Options;
 
 // Result of flattening a graph (ref: VertexSet::generateEstimateData + EdgeSet::init,
 // src/optimisable_graph.hpp:84-126,474-572).  Indices: free vertices first.
-// Unary edges of one kind on a pose vertex (icp_types.h, prior_types.h), flattened in container order; edges on fixed
-// poses, inactive edges and everything invalid never get here (graph_optimisation.cpp validates and drops)
+// Edges of one kind on pose vertices alone (icp_types.h, prior_types.h: unary; relpose_types.h: binary), flattened in
+// container order; inactive edges, edges all of whose poses are fixed and everything invalid never get here
+// (graph_optimisation.cpp validates and drops)
 enum PoseKind
 {
     POSE_KIND_PLANE = 0,
     POSE_KIND_LINE,
     POSE_KIND_PRIOR,
+    POSE_KIND_RELPOSE,
     POSE_KIND_COUNT
 };
 struct FlatPoseKind
 {
     int kind = 0;                 // PoseKind
-    int meas_w = 0, weight_w = 0; // doubles per edge: plane 7 (p, n, d) + 1, line 9 (p, a, unit direction) + 1, prior
-                                  // 7 (q x y z w, t) + 21 (upper triangle of Omega, row-major packed)
-    std::vector<int32_t> pose;    // free-first pose index per edge (always < P)
+    int meas_w = 0, weight_w = 0; // doubles per edge: plane 7 (p, n, d) + 1, line 9 (p, a, unit direction) + 1, prior and
+                                  // relative pose 7 (q x y z w, t) + 21 (upper triangle of Omega, row-major packed)
+    std::vector<int32_t> pose;    // free-first pose index per edge: always < P on a unary kind; a of a relative-pose edge
+    std::vector<int32_t> pose_b;  // relative pose: b (one of a, b may be a fixed pose, >= P); empty on the unary kinds
     std::vector<double> meas;     // E x meas_w
     std::vector<double> weight;   // E x weight_w, or 1 x weight_w when one value serves all
     std::vector<int32_t> src_set, src_edge; // where an edge came from: edge set (position among the optimiser's edge
@@ -45,40 +48,22 @@ struct FlatPoseKind
     int n() const { return (int)pose.size(); }
     void clear()
     {
-        pose.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear(), threshold.clear();
+        pose.clear(), pose_b.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear(), threshold.clear();
         rk = CUGO_RK_NONE, delta = 1.0, rk_seen = false;
     }
 };
 // a kind in messages about its edge sets, and in the engine's, which speak of the two ICP kinds as one
 inline const char* pose_kind_name(int kind)
 {
-    return kind == POSE_KIND_PLANE ? "point-to-plane" : kind == POSE_KIND_LINE ? "point-to-line" : "pose prior";
+    return kind == POSE_KIND_PLANE  ? "point-to-plane"
+           : kind == POSE_KIND_LINE ? "point-to-line"
+           : kind == POSE_KIND_PRIOR ? "pose prior"
+                                     : "relative-pose";
 }
 inline const char* pose_kind_group(int kind)
 {
-    return kind == POSE_KIND_PRIOR ? "pose prior" : "point-to-plane / point-to-line";
+    return kind == POSE_KIND_RELPOSE ? "relative-pose" : kind == POSE_KIND_PRIOR ? "pose prior" : "point-to-plane / point-to-line";
 }
-
-// Relative-pose edges (relpose_types.h): binary, so they have a record of their own.  Container order over all the sets
-// (the plan fixes the summation order, not a sort); only edges that count get here: active, at least one free end
-// (graph_optimisation.cpp validates and drops)
-struct FlatRelPose
-{
-    std::vector<int32_t> pose_a, pose_b; // free-first pose indices (one of the two may be a fixed pose, >= P)
-    std::vector<double> meas;            // E x 7 (q x y z w, t) of Z ~ T_a T_b^-1
-    std::vector<double> weight;          // E x 21 (upper triangle of Omega, row-major packed), or 1 x 21
-    std::vector<int32_t> src_set, src_edge;
-    std::vector<double> threshold; // as FlatPoseKind::threshold
-    int rk = CUGO_RK_NONE;
-    double delta = 1.0;
-    bool rk_seen = false;
-    int n() const { return (int)pose_a.size(); }
-    void clear()
-    {
-        pose_a.clear(), pose_b.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear(), threshold.clear();
-        rk = CUGO_RK_NONE, delta = 1.0, rk_seen = false;
-    }
-};
 
 // per-edge thresholds as flattened -> empty when none is positive, one entry when all are the same
 inline void collapse_thresholds(std::vector<double>& t)
@@ -109,14 +94,13 @@ struct FlatGraph
     // the chi2 threshold of its edge set, 0 = disabled; empty = disabled for all
     std::vector<double> e_outlier_threshold;
     FlatPoseKind kinds[POSE_KIND_COUNT]; // widths set by the constructor
-    FlatRelPose relpose;
     FlatGraph()
     {
-        const int w[POSE_KIND_COUNT][2] = {{7, 1}, {9, 1}, {7, 21}};
+        const int w[POSE_KIND_COUNT][2] = {{7, 1}, {9, 1}, {7, 21}, {7, 21}};
         for (int k = 0; k < POSE_KIND_COUNT; k++)
             kinds[k].kind = k, kinds[k].meas_w = w[k][0], kinds[k].weight_w = w[k][1];
     }
-    int n_pose_edges() const { return kinds[0].n() + kinds[1].n() + kinds[2].n(); }
+    int n_pose_edges() const { return kinds[0].n() + kinds[1].n() + kinds[2].n(); } // the unary kinds
     int n_edges() const { return (int)e_pose.size(); }
 };
 
@@ -202,10 +186,10 @@ public:
     // pass exceeds their set's threshold become inactive.  Returns their indices in the order of
     // the FlatGraph passed to initialize() (all ranks return the same list).
     std::vector<int32_t> reject_outliers();
-    // The same on the pose edge kinds that carry a threshold (FlatPoseKind::threshold, FlatRelPose::threshold), at the
+    // The same on the pose edge kinds that carry a threshold (FlatPoseKind::threshold), at the
     // same estimates: one error pass with the chi2 term of every edge and the outlier pass (cugo_pose_edges_reject) per
     // such kind, all on the device; the flags stay there, so a further optimize() on the same initialisation runs
-    // without the edges.  Returns, per kind (PoseKind, then the relative-pose edges), the {edge set, position in the
+    // without the edges.  Returns, per kind (PoseKind: the relative-pose edges last), the {edge set, position in the
     // set} of every edge that went, ascending.  The Hsc pattern is left as it is (a pair that lost its last edge keeps
     // an empty block until the next flattening), and n_*_edges() keep describing the flattening.
     using PoseOutliers = std::vector<std::pair<int32_t, int32_t>>;

@@ -230,17 +230,18 @@ static bool knownPoseVertex(const BaseVertex* v, const std::vector<BaseVertexSet
     return known;
 }
 
-// One edge set of unary pose edges (PlaneEdgeSet / LineEdgeSet of icp_types.h, PosePriorEdgeSet of prior_types.h) into
-// the flat arrays of its kind, in container order.  This is the one place where these edges are checked (the kernels
-// take the layout as given): every active edge must sit on a pose vertex of one of the optimiser's pose vertex sets and
-// hold what payload(e, refuse, meas, weight) accepts; the callable writes the edge's meas_w / weight_w columns and
-// refuses bad values through refuse(what).  Inactive edges and edges on fixed poses are dropped, as BA edges with two
+// One edge set of pose edges (PlaneEdgeSet / LineEdgeSet of icp_types.h, PosePriorEdgeSet of prior_types.h: arity 1;
+// RelPoseEdgeSet of relpose_types.h: arity 2, vertex 0 = a, vertex 1 = b) into the flat arrays of its kind, in container
+// order.  This is the one place where these edges are checked (the kernels take the layout as given): every active edge
+// must sit on pose vertices of the optimiser's pose vertex sets (arity 2: two different ones) and hold what
+// payload(e, refuse, meas, weight) accepts; the callable writes the edge's meas_w / weight_w columns and refuses bad
+// values through refuse(what).  Inactive edges and edges all of whose poses are fixed are dropped, as BA edges with two
 // fixed ends are.  Several sets of a kind must agree on the robust kernel; once that is settled, check_set() returns
 // what is wrong with a non-empty set as a whole, or nullptr.
 template <class Payload, class CheckSet>
-static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, const char* kind, const std::vector<BaseVertexSet*>& vertexSets,
-                               bool rejection, cugo_host::FlatPoseKind& out, std::vector<BaseEdge*>& setEdges, Payload payload,
-                               CheckSet check_set)
+static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, int arity, const char* kind,
+                               const std::vector<BaseVertexSet*>& vertexSets, bool rejection, cugo_host::FlatPoseKind& out,
+                               std::vector<BaseEdge*>& setEdges, Payload payload, CheckSet check_set)
 {
     const std::string name = kind;
     const double threshold = settlePoseEdgeSet(es, setIndex, name, rejection, out.rk, out.delta, out.rk_seen, check_set);
@@ -256,14 +257,19 @@ static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, const char* kind, 
             throw std::runtime_error("cugo: " + name + " edge " + std::to_string(at) + " of edge set " +
                                      std::to_string(setIndex) + ": " + what);
         };
-        BaseVertex* v = e->getVertex(0);
-        if (!knownPoseVertex(v, vertexSets))
-            refuse("its pose vertex is in no pose vertex set of this optimiser");
+        BaseVertex *v = e->getVertex(0), *vb = arity == 2 ? e->getVertex(1) : nullptr;
+        if (!knownPoseVertex(v, vertexSets) || (arity == 2 && !knownPoseVertex(vb, vertexSets)))
+            refuse(arity == 2 ? "one of its pose vertices is in no pose vertex set of this optimiser"
+                              : "its pose vertex is in no pose vertex set of this optimiser");
+        if (v == vb)
+            refuse("it joins a pose to itself (a == b)");
         double meas[9], weight[21];
         payload(e, refuse, meas, weight);
-        if (v->isFixed())
+        if (v->isFixed() && (arity == 1 || vb->isFixed()))
             continue;
         out.pose.push_back(v->getIndex());
+        if (arity == 2)
+            out.pose_b.push_back(vb->getIndex());
         out.meas.insert(out.meas.end(), meas, meas + out.meas_w);
         out.weight.insert(out.weight.end(), weight, weight + out.weight_w);
         out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
@@ -276,7 +282,7 @@ static void flattenPoseEdgeSet(BaseEdgeSet* es, int setIndex, const char* kind, 
     es->setDirtyState(false);
 }
 
-// The payloads of the three kinds: an edge's columns, validated.
+// The payloads of the kinds: an edge's columns, validated.
 // plane / line: one information value, the edge's own or the set's
 template <class Refuse>
 static void icpInformation(BaseEdgeSet* es, BaseEdge* e, bool perInfo, Refuse& refuse, double* weight)
@@ -320,8 +326,8 @@ static void linePayload(BaseEdge* e, Refuse& refuse, double* m)
     for (int c = 0; c < 3; c++)
         m[6 + c] = d[c] / len;
 }
-// prior: measured pose with a unit quaternion | the upper triangle of the symmetric part of Omega (A: the edge's own
-// matrix, checked here, or the set's, checked with the set)
+// prior and relative pose: measured pose with a unit quaternion | the upper triangle of the symmetric part of Omega (A:
+// the edge's own matrix, checked here, or the set's, checked with the set)
 template <class Refuse>
 static void priorPayload(BaseEdge* e, const double* setInformation, Refuse& refuse, double* z, double* weight)
 {
@@ -340,52 +346,6 @@ static void priorPayload(BaseEdge* e, const double* setInformation, Refuse& refu
     for (int r = 0, t = 0; r < 6; r++)
         for (int c = r; c < 6; c++)
             weight[t++] = 0.5 * (A[6 * r + c] + A[6 * c + r]);
-}
-
-// One RelPoseEdgeSet (relpose_types.h) into the flat record, in container order: the binary counterpart of
-// flattenPoseEdgeSet.  The measurement and Omega are the prior's (priorPayload checks them).  Refused: a == b, an end in
-// no pose vertex set of the optimiser; dropped: inactive edges and edges between two fixed poses.
-static void flattenRelPoseEdgeSet(RelPoseEdgeSet* es, int setIndex, bool perEdgeInformation,
-                                  const std::vector<BaseVertexSet*>& vertexSets, bool rejection, cugo_host::FlatRelPose& out,
-                                  std::vector<BaseEdge*>& setEdges)
-{
-    const std::string name = "relative-pose";
-    const double* setInformation = perEdgeInformation ? nullptr : es->informationMatrix();
-    const double threshold =
-        settlePoseEdgeSet(es, setIndex, name, rejection, out.rk, out.delta, out.rk_seen,
-                          [&] { return setInformation ? checkInformation36(setInformation) : nullptr; });
-    if (threshold > 0.0)
-        setEdges.assign(es->nedges(), nullptr);
-    size_t i = 0, kept = 0;
-    for (BaseEdge* e : es->get())
-    {
-        const size_t at = i++;
-        if (!e->isActive())
-            continue;
-        auto refuse = [&](const char* what) {
-            throw std::runtime_error("cugo: " + name + " edge " + std::to_string(at) + " of edge set " +
-                                     std::to_string(setIndex) + ": " + what);
-        };
-        BaseVertex *va = e->getVertex(0), *vb = e->getVertex(1);
-        if (!knownPoseVertex(va, vertexSets) || !knownPoseVertex(vb, vertexSets))
-            refuse("one of its pose vertices is in no pose vertex set of this optimiser");
-        if (va == vb)
-            refuse("it joins a pose to itself (a == b)");
-        double meas[9], weight[21];
-        priorPayload(e, setInformation, refuse, meas, weight);
-        if (va->isFixed() && vb->isFixed())
-            continue;
-        out.pose_a.push_back(va->getIndex()), out.pose_b.push_back(vb->getIndex());
-        out.meas.insert(out.meas.end(), meas, meas + 7);
-        out.weight.insert(out.weight.end(), weight, weight + 21);
-        out.src_set.push_back(setIndex), out.src_edge.push_back((int32_t)at);
-        out.threshold.push_back(threshold);
-        if (threshold > 0.0)
-            setEdges[at] = e;
-        kept++;
-    }
-    es->setActiveEdgeCount(kept);
-    es->setDirtyState(false);
 }
 
 void CudaGraphOptimisationImpl::initialize()
@@ -499,7 +459,6 @@ void CudaGraphOptimisationImpl::initialize()
             cap += es->nedges();
     for (cugo_host::FlatPoseKind& fk : g.kinds)
         fk.clear();
-    g.relpose.clear();
     poseSetEdges_.assign(edgeSets.size(), {});
     const bool rejection = options.poseEdgeOutlierRejection;
     g.e_pose.resize(cap), g.e_lm.resize(cap), g.e_flags.resize(cap);
@@ -530,7 +489,7 @@ void CudaGraphOptimisationImpl::initialize()
             const int kind = line ? cugo_host::POSE_KIND_LINE : cugo_host::POSE_KIND_PLANE;
             const bool perInfo = options.perEdgeInformation;
             flattenPoseEdgeSet(
-                es, (int)si, cugo_host::pose_kind_name(kind), vertexSets, rejection, g.kinds[kind], poseSetEdges_[si],
+                es, (int)si, 1, cugo_host::pose_kind_name(kind), vertexSets, rejection, g.kinds[kind], poseSetEdges_[si],
                 [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
                     icpInformation(es, e, perInfo, refuse, weight);
                     line ? linePayload(e, refuse, meas) : planePayload(e, refuse, meas);
@@ -538,24 +497,22 @@ void CudaGraphOptimisationImpl::initialize()
                 [] { return (const char*)nullptr; });
             continue;
         }
-        if (auto* rs = dim == 6 ? dynamic_cast<RelPoseEdgeSet*>(es) : nullptr)
-        { // RelPoseEdgeSet (relpose_types.h, an extension): opt-in
-            if (!options.relativePoseEdges)
+        if (dim == 6)
+        { // RelPoseEdgeSet (relpose_types.h; opt-in) or PosePriorEdgeSet (prior_types.h), extensions: the type tells them apart
+            auto* rs = dynamic_cast<RelPoseEdgeSet*>(es);
+            auto* ps = dynamic_cast<PosePriorEdgeSet*>(es);
+            if (rs && !options.relativePoseEdges)
                 throw std::runtime_error("cugo: the optimiser does not take relative-pose edge sets unless "
                                          "GraphOptimisationOptions::relativePoseEdges is on "
                                          "(their terms alone: cugo_relpose_* in include/cugo_hip.h)");
-            flattenRelPoseEdgeSet(rs, (int)si, options.perEdgeInformation, vertexSets, rejection, g.relpose, poseSetEdges_[si]);
-            continue;
-        }
-        if (dim == 6)
-        { // PosePriorEdgeSet (prior_types.h, an extension)
-            auto* ps = dynamic_cast<PosePriorEdgeSet*>(es);
-            if (!ps)
+            if (!rs && !ps)
                 throw std::runtime_error("cugo: a 6-d edge set must be a PosePriorEdgeSet (prior_types.h)");
-            const double* setInformation = options.perEdgeInformation ? nullptr : ps->informationMatrix();
+            const int kind = rs ? cugo_host::POSE_KIND_RELPOSE : cugo_host::POSE_KIND_PRIOR;
+            const double* setInformation =
+                options.perEdgeInformation ? nullptr : rs ? rs->informationMatrix() : ps->informationMatrix();
             flattenPoseEdgeSet(
-                es, (int)si, cugo_host::pose_kind_name(cugo_host::POSE_KIND_PRIOR), vertexSets, rejection,
-                g.kinds[cugo_host::POSE_KIND_PRIOR], poseSetEdges_[si],
+                es, (int)si, rs ? 2 : 1, cugo_host::pose_kind_name(kind), vertexSets, rejection, g.kinds[kind],
+                poseSetEdges_[si],
                 [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
                     priorPayload(e, setInformation, refuse, meas, weight);
                 },
@@ -733,15 +690,6 @@ void CudaGraphOptimisationImpl::initialize()
         if (uniform)
             fk.weight.resize(fk.weight_w);
         cugo_host::collapse_thresholds(fk.threshold);
-    }
-    {
-        std::vector<double>& w = g.relpose.weight;
-        bool uniform = g.relpose.n() > 0;
-        for (size_t i = 21; uniform && i < w.size(); i++)
-            uniform = w[i] == w[i % 21];
-        if (uniform)
-            w.resize(21);
-        cugo_host::collapse_thresholds(g.relpose.threshold);
     }
     lap("graph: edge flatten");
 

@@ -369,4 +369,105 @@ __device__ __forceinline__ void pose_term_add(int p, int t, int r, int c, double
     }
 }
 
+// the chi2 total of a workgroup of N pose groups: lane 0 of group g has stored the group's chi2 to s_chi[g] (shared
+// memory; the store stays in the kernel, in front of the group's term adds); thread 0 sums them in group order
+template <int N>
+__device__ __forceinline__ void pose_groups_chi_total(const double* s_chi, double* wg_chi)
+{
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        double tot = 0.0;
+#pragma unroll
+        for (int i = 0; i < N; i++)
+            tot += s_chi[i];
+        wg_chi[blockIdx.x] = tot;
+    }
+}
+
+// ---- shared by the SE(3) edge kinds (prior_kernels.hip, relpose_kernels.hip): the residual of D = T Z^-1 (the prior) or
+// D = T_a T_b^-1 Z^-1 (a relative-pose edge) under a full 6 x 6 information matrix, every lane in registers.
+// Z = (q_z, t_z) of edge e from the planar meas [7][n].  Returns the stride n as an opaque per-lane value: the 28
+// multiples of n the planar arrays are read at would otherwise each take a pair of scalar registers across the edge
+// loop (32-bit indices: 21 n stays far below 2^31)
+__device__ __forceinline__ int se3_load_meas(const double* meas, int n, int e, double qz[4], double tz[3])
+{
+    int stride = n;
+    asm volatile("" : "+v"(stride));
+    int i = e;
+#pragma unroll
+    for (int c = 0; c < 4; c++, i += stride)
+        qz[c] = meas[i];
+#pragma unroll
+    for (int c = 0; c < 3; c++, i += stride)
+        tz[c] = meas[i];
+    return stride;
+}
+// r = [ phi ; t - R_D t_z ], phi = Log_SO3(R_D) = theta / sin(theta) * vee(D - D^T) / 2 with
+// theta = atan2(|vee| / 2, (tr D - 1) / 2) in [0, pi]; sn and cs ARE sin theta and cos theta
+__device__ __forceinline__ void se3_residual(const double D[3][3], const double* t, const double tz[3], double r[6],
+                                             double& sn, double& cs, double& theta)
+{
+    const double s0 = 0.5 * (D[2][1] - D[1][2]), s1 = 0.5 * (D[0][2] - D[2][0]), s2 = 0.5 * (D[1][0] - D[0][1]);
+    sn = sqrt(s0 * s0 + s1 * s1 + s2 * s2);
+    cs = 0.5 * (D[0][0] + D[1][1] + D[2][2] - 1.0);
+    theta = atan2(sn, cs);
+    const double f = sn > 1e-12 ? theta / sn : 1.0;
+    r[0] = f * s0, r[1] = f * s1, r[2] = f * s2;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        r[3 + i] = t[i] - (D[i][0] * tz[0] + D[i][1] * tz[1] + D[i][2] * tz[2]);
+}
+// Omega of edge e, full symmetric, from its packed upper triangle info [21][n_info] (n_info == 1: one for all);
+// stride: what se3_load_meas returned
+__device__ __forceinline__ void se3_load_info(const double* info, int n_info, int e, int stride, double Om[6][6])
+{
+    int at = n_info == 1 ? 0 : e;
+    const int step = n_info == 1 ? 1 : stride;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = i; j < 6; j++)
+        {
+            const double w = info[at];
+            Om[i][j] = w, Om[j][i] = w;
+            at += step;
+        }
+}
+// Or = Omega r; returns x = max(0, r^T Omega r)
+__device__ __forceinline__ double se3_quadratic(const double Om[6][6], const double r[6], double Or[6])
+{
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+    {
+        double s = Om[i][0] * r[0];
+#pragma unroll
+        for (int j = 1; j < 6; j++)
+            s += Om[i][j] * r[j];
+        Or[i] = s;
+    }
+    double x = r[0] * Or[0];
+#pragma unroll
+    for (int i = 1; i < 6; i++)
+        x += r[i] * Or[i];
+    return fmax(0.0, x);
+}
+// J_l^-1(phi) = I - 1/2 [phi]x + c(theta) [phi]x^2, phi = r[0..2]; no call of sin / cos (sn, cs of se3_residual)
+__device__ __forceinline__ void se3_jl_inv(const double r[6], double theta, double sn, double cs, double Jl[3][3])
+{
+    const double th2 = theta * theta;
+    const double c = theta < 1e-3 ? 1.0 / 12 + th2 * (1.0 / 720) : 1.0 / th2 - (1.0 + cs) / (2.0 * theta * sn);
+    const double p0 = r[0], p1 = r[1], p2 = r[2];
+    // [phi]x and its square
+    const double K[3][3] = {{0.0, -p2, p1}, {p2, 0.0, -p0}, {-p1, p0, 0.0}};
+    const double K2[3][3] = {{-(p1 * p1 + p2 * p2), p0 * p1, p0 * p2},
+                             {p0 * p1, -(p0 * p0 + p2 * p2), p1 * p2},
+                             {p0 * p2, p1 * p2, -(p0 * p0 + p1 * p1)}};
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            Jl[i][j] = (i == j ? 1.0 : 0.0) - 0.5 * K[i][j] + c * K2[i][j];
+}
+
 } // namespace cugo_dev

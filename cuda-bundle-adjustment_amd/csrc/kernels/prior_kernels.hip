@@ -63,20 +63,8 @@ template <bool FULL>
 __device__ __forceinline__ double prior_edge(const PriorArgs& a, int e, const double* __restrict__ pose, int ri, int ci,
                                              double sign, double& mine)
 {
-    // (the stride as an opaque per-lane value: the 28 multiples of n the planar arrays are read at would otherwise
-    //  each take a pair of scalar registers across the edge loop; 32-bit indices: 21 n stays far below 2^31)
-    int stride = a.n;
-    asm volatile("" : "+v"(stride));
     double qz[4], tz[3];
-    {
-        int i = e;
-#pragma unroll
-        for (int c = 0; c < 4; c++, i += stride)
-            qz[c] = a.meas[i];
-#pragma unroll
-        for (int c = 0; c < 3; c++, i += stride)
-            tz[c] = a.meas[i];
-    }
+    const int stride = se3_load_meas(a.meas, a.n, e, qz, tz);
     double R[3][3], Rz[3][3], D[3][3];
     quat_to_rot(pose, R);
     quat_to_rot(qz, Rz);
@@ -85,67 +73,23 @@ __device__ __forceinline__ double prior_edge(const PriorArgs& a, int e, const do
 #pragma unroll
         for (int j = 0; j < 3; j++)
             D[i][j] = R[i][0] * Rz[j][0] + R[i][1] * Rz[j][1] + R[i][2] * Rz[j][2];
-    // phi = theta / sin(theta) * vee(D - D^T) / 2, theta = atan2(|vee| / 2, (tr D - 1) / 2) in [0, pi]
-    const double s0 = 0.5 * (D[2][1] - D[1][2]), s1 = 0.5 * (D[0][2] - D[2][0]), s2 = 0.5 * (D[1][0] - D[0][1]);
-    const double sn = sqrt(s0 * s0 + s1 * s1 + s2 * s2);
-    const double cs = 0.5 * (D[0][0] + D[1][1] + D[2][2] - 1.0);
-    const double theta = atan2(sn, cs);
-    const double f = sn > 1e-12 ? theta / sn : 1.0;
-    double r[6];
-    r[0] = f * s0, r[1] = f * s1, r[2] = f * s2;
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-        r[3 + i] = pose[4 + i] - (D[i][0] * tz[0] + D[i][1] * tz[1] + D[i][2] * tz[2]);
-    // Omega, full symmetric
-    double Om[6][6];
-    {
-        int at = a.n_info == 1 ? 0 : e;
-        const int step = a.n_info == 1 ? 1 : stride;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = i; j < 6; j++)
-            {
-                const double w = a.info[at];
-                Om[i][j] = w, Om[j][i] = w;
-                at += step;
-            }
-    }
-    double Or[6]; // Omega r
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-    {
-        double s = Om[i][0] * r[0];
-#pragma unroll
-        for (int j = 1; j < 6; j++)
-            s += Om[i][j] * r[j];
-        Or[i] = s;
-    }
-    double x = r[0] * Or[0];
-#pragma unroll
-    for (int i = 1; i < 6; i++)
-        x += r[i] * Or[i];
-    x = fmax(0.0, x);
+    double r[6], sn, cs, theta;
+    se3_residual(D, pose + 4, tz, r, sn, cs, theta);
+    double Om[6][6], Or[6];
+    se3_load_info(a.info, a.n_info, e, stride, Om);
+    const double x = se3_quadratic(Om, r, Or);
     const double chi = rk_rho(a.rk, x);
     if (FULL)
     {
         const double w = rk_drho(a.rk, x);
-        const double th2 = theta * theta;
-        // (sn and cs ARE sin theta and cos theta: no call of sin / cos)
-        const double c = theta < 1e-3 ? 1.0 / 12 + th2 * (1.0 / 720) : 1.0 / th2 - (1.0 + cs) / (2.0 * theta * sn);
-        const double p0 = r[0], p1 = r[1], p2 = r[2];
-        // [phi]x and its square
-        const double K[3][3] = {{0.0, -p2, p1}, {p2, 0.0, -p0}, {-p1, p0, 0.0}};
-        const double K2[3][3] = {{-(p1 * p1 + p2 * p2), p0 * p1, p0 * p2},
-                                 {p0 * p1, -(p0 * p0 + p2 * p2), p1 * p2},
-                                 {p0 * p2, p1 * p2, -(p0 * p0 + p1 * p1)}};
-        double J[6][6];
+        double Jl[3][3], J[6][6];
+        se3_jl_inv(r, theta, sn, cs, Jl);
 #pragma unroll
         for (int i = 0; i < 3; i++)
 #pragma unroll
             for (int j = 0; j < 3; j++)
             {
-                J[i][j] = (i == j ? 1.0 : 0.0) - 0.5 * K[i][j] + c * K2[i][j];
+                J[i][j] = Jl[i][j];
                 J[i][3 + j] = 0.0;
                 J[3 + i][3 + j] = i == j ? 1.0 : 0.0;
             }
@@ -227,19 +171,16 @@ __global__ __launch_bounds__(PRIOR_WG) void k_prior(PriorArgs a, double* __restr
         s_chi[g] = chi;
     if (MODE != PRIOR_ERRORS && any)
         pose_term_add<MODE == PRIOR_SCHUR>(p, t, ri, ci, mine, H, rowptr, bp, bsc);
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        double tot = 0.0;
-#pragma unroll
-        for (int i = 0; i < PRIOR_POSES; i++)
-            tot += s_chi[i];
-        a.wg_chi[blockIdx.x] = tot;
-    }
+    pose_groups_chi_total<PRIOR_POSES>(s_chi, a.wg_chi);
 }
 
-PriorArgs args_of(const cugo_prior_edges& ev, const double* d_poses, double* d_wg_chi, double* d_edge_chi)
+template <int MODE>
+void launch(hipStream_t s, const char* label, const cugo_prior_edges& ev, const double* d_poses, double* d_wg_chi,
+            double* d_edge_chi, double* d_H, const int32_t* d_rowptr, double* d_bp, double* d_bsc)
 {
+    const int wgs = cugo_k::prior_workgroups(ev);
+    if (!wgs)
+        return;
     PriorArgs a;
     a.n = ev.n, a.n_poses_free = ev.n_poses_free;
     a.pose_ptr = ev.d_pose_ptr, a.meas = ev.d_meas, a.info = ev.d_info, a.n_info = ev.n_info;
@@ -247,7 +188,8 @@ PriorArgs args_of(const cugo_prior_edges& ev, const double* d_poses, double* d_w
     a.rk = Robust{ev.rk, ev.delta};
     a.poses = d_poses;
     a.wg_chi = d_wg_chi, a.edge_chi = d_edge_chi;
-    return a;
+    cugo_k::LaunchScope scope(label, s);
+    hipLaunchKernelGGL(k_prior<MODE>, dim3(wgs), dim3(PRIOR_WG), 0, s, a, d_H, d_rowptr, d_bp, d_bsc);
 }
 
 } // namespace
@@ -263,36 +205,19 @@ int prior_workgroups(const cugo_prior_edges& ev)
 void launch_prior_errors(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, double* d_wg_chi,
                          double* d_edge_chi)
 {
-    const int wgs = prior_workgroups(ev);
-    if (!wgs)
-        return;
-    const PriorArgs a = args_of(ev, d_poses, d_wg_chi, d_edge_chi);
-    LaunchScope scope("k_prior_errors", s);
-    hipLaunchKernelGGL(k_prior<PRIOR_ERRORS>, dim3(wgs), dim3(PRIOR_WG), 0, s, a, (double*)nullptr, (const int32_t*)nullptr,
-                       (double*)nullptr, (double*)nullptr);
+    launch<PRIOR_ERRORS>(s, "k_prior_errors", ev, d_poses, d_wg_chi, d_edge_chi, nullptr, nullptr, nullptr, nullptr);
 }
 
 void launch_prior_add(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
                       double* d_wg_chi)
 {
-    const int wgs = prior_workgroups(ev);
-    if (!wgs)
-        return;
-    const PriorArgs a = args_of(ev, d_poses, d_wg_chi, nullptr);
-    LaunchScope scope("k_prior_add", s);
-    hipLaunchKernelGGL(k_prior<PRIOR_HPP>, dim3(wgs), dim3(PRIOR_WG), 0, s, a, d_Hpp, (const int32_t*)nullptr, d_bp,
-                       (double*)nullptr);
+    launch<PRIOR_HPP>(s, "k_prior_add", ev, d_poses, d_wg_chi, nullptr, d_Hpp, nullptr, d_bp, nullptr);
 }
 
 void launch_prior_add_schur(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, const int32_t* d_rowptr,
                             double* d_Hsc, double* d_bp, double* d_bsc, double* d_wg_chi)
 {
-    const int wgs = prior_workgroups(ev);
-    if (!wgs)
-        return;
-    const PriorArgs a = args_of(ev, d_poses, d_wg_chi, nullptr);
-    LaunchScope scope("k_prior_add_schur", s);
-    hipLaunchKernelGGL(k_prior<PRIOR_SCHUR>, dim3(wgs), dim3(PRIOR_WG), 0, s, a, d_Hsc, d_rowptr, d_bp, d_bsc);
+    launch<PRIOR_SCHUR>(s, "k_prior_add_schur", ev, d_poses, d_wg_chi, nullptr, d_Hsc, d_rowptr, d_bp, d_bsc);
 }
 
 } // namespace cugo_k

@@ -82,20 +82,8 @@ __device__ __forceinline__ double relpose_edge(const RelPoseArgs& a, int e, cons
                                                const double* __restrict__ pb, int side, bool use_other, int ri, int ci,
                                                double sign, double& mine)
 {
-    // (the stride as an opaque per-lane value, as in prior_edge: the 28 multiples of n would otherwise each take a pair
-    //  of scalar registers across the edge loop; 32-bit indices: 21 n stays far below 2^31)
-    int stride = a.plan.n;
-    asm volatile("" : "+v"(stride));
     double qz[4], tz[3];
-    {
-        int i = e;
-#pragma unroll
-        for (int c = 0; c < 4; c++, i += stride)
-            qz[c] = a.meas[i];
-#pragma unroll
-        for (int c = 0; c < 3; c++, i += stride)
-            tz[c] = a.meas[i];
-    }
+    const int stride = se3_load_meas(a.meas, a.plan.n, e, qz, tz);
     double RA[3][3], tA[3], D[3][3];
     {
         double Ra[3][3], Rb[3][3], Rz[3][3];
@@ -116,66 +104,18 @@ __device__ __forceinline__ double relpose_edge(const RelPoseArgs& a, int e, cons
             for (int j = 0; j < 3; j++)
                 D[i][j] = RA[i][0] * Rz[j][0] + RA[i][1] * Rz[j][1] + RA[i][2] * Rz[j][2];
     }
-    // phi = theta / sin(theta) * vee(D - D^T) / 2, theta = atan2(|vee| / 2, (tr D - 1) / 2) in [0, pi]
-    const double s0 = 0.5 * (D[2][1] - D[1][2]), s1 = 0.5 * (D[0][2] - D[2][0]), s2 = 0.5 * (D[1][0] - D[0][1]);
-    const double sn = sqrt(s0 * s0 + s1 * s1 + s2 * s2);
-    const double cs = 0.5 * (D[0][0] + D[1][1] + D[2][2] - 1.0);
-    const double theta = atan2(sn, cs);
-    const double f = sn > 1e-12 ? theta / sn : 1.0;
-    double r[6];
-    r[0] = f * s0, r[1] = f * s1, r[2] = f * s2;
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-        r[3 + i] = tA[i] - (D[i][0] * tz[0] + D[i][1] * tz[1] + D[i][2] * tz[2]);
-    // Omega, full symmetric
-    double Om[6][6];
-    {
-        int at = a.n_info == 1 ? 0 : e;
-        const int step = a.n_info == 1 ? 1 : stride;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = i; j < 6; j++)
-            {
-                const double w = a.info[at];
-                Om[i][j] = w, Om[j][i] = w;
-                at += step;
-            }
-    }
-    double Or[6]; // Omega r
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-    {
-        double s = Om[i][0] * r[0];
-#pragma unroll
-        for (int j = 1; j < 6; j++)
-            s += Om[i][j] * r[j];
-        Or[i] = s;
-    }
-    double x = r[0] * Or[0];
-#pragma unroll
-    for (int i = 1; i < 6; i++)
-        x += r[i] * Or[i];
-    x = fmax(0.0, x);
+    double r[6], sn, cs, theta;
+    se3_residual(D, tA, tz, r, sn, cs, theta);
+    double Om[6][6], Or[6];
+    se3_load_info(a.info, a.n_info, e, stride, Om);
+    const double x = se3_quadratic(Om, r, Or);
     const double chi = rk_rho(a.rk, x);
     if (FULL)
     {
         const double w = rk_drho(a.rk, x);
-        const double th2 = theta * theta;
-        // (sn and cs ARE sin theta and cos theta: no call of sin / cos)
-        const double c = theta < 1e-3 ? 1.0 / 12 + th2 * (1.0 / 720) : 1.0 / th2 - (1.0 + cs) / (2.0 * theta * sn);
-        const double p0 = r[0], p1 = r[1], p2 = r[2];
-        const double K[3][3] = {{0.0, -p2, p1}, {p2, 0.0, -p0}, {-p1, p0, 0.0}};
-        const double K2[3][3] = {{-(p1 * p1 + p2 * p2), p0 * p1, p0 * p2},
-                                 {p0 * p1, -(p0 * p0 + p2 * p2), p1 * p2},
-                                 {p0 * p2, p1 * p2, -(p0 * p0 + p1 * p1)}};
         // the 27 entries of J_a and of J_b that are not structurally zero: left half [6][3], lower right [3][3]
-        double Jl[3][3]; // J_l^-1(phi)
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++)
-                Jl[i][j] = (i == j ? 1.0 : 0.0) - 0.5 * K[i][j] + c * K2[i][j];
+        double Jl[3][3];
+        se3_jl_inv(r, theta, sn, cs, Jl);
         // [u]x with u = t_D - t_A
         const double u0 = r[3] - tA[0], u1 = r[4] - tA[1], u2 = r[5] - tA[2];
         const bool sb = side != 0; // self is b
@@ -313,20 +253,17 @@ __global__ __launch_bounds__(RELPOSE_WG) void k_relpose(RelPoseArgs a, double* H
         s_chi[g] = chi;
     if (MODE != RELPOSE_ERRORS && any)
         pose_term_add<MODE == RELPOSE_SCHUR>(p, t, ri, ci, mine, H, rowptr, bp, bsc);
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        double tot = 0.0;
-#pragma unroll
-        for (int i = 0; i < RELPOSE_POSES; i++)
-            tot += s_chi[i];
-        a.wg_chi[blockIdx.x] = tot;
-    }
+    pose_groups_chi_total<RELPOSE_POSES>(s_chi, a.wg_chi);
 }
 
-RelPoseArgs args_of(const cugo_relpose_edges& ev, const cugo_k::RelPosePlanDev& plan, const double* d_poses,
-                    double* d_wg_chi, double* d_edge_chi)
+template <int MODE>
+void launch(hipStream_t s, const char* label, const cugo_relpose_edges& ev, const cugo_k::RelPosePlanDev& plan,
+            const double* d_poses, double* d_wg_chi, double* d_edge_chi, double* d_H, double* d_Hoff, const int32_t* d_rowptr,
+            double* d_bp, double* d_bsc)
 {
+    const int wgs = cugo_k::relpose_workgroups(ev);
+    if (!wgs)
+        return;
     RelPoseArgs a;
     a.plan = plan;
     a.meas = ev.d_meas, a.info = ev.d_info, a.n_info = ev.n_info;
@@ -334,7 +271,8 @@ RelPoseArgs args_of(const cugo_relpose_edges& ev, const cugo_k::RelPosePlanDev& 
     a.rk = Robust{ev.rk, ev.delta};
     a.poses = d_poses;
     a.wg_chi = d_wg_chi, a.edge_chi = d_edge_chi;
-    return a;
+    cugo_k::LaunchScope scope(label, s);
+    hipLaunchKernelGGL(k_relpose<MODE>, dim3(wgs), dim3(RELPOSE_WG), 0, s, a, d_H, d_Hoff, d_rowptr, d_bp, d_bsc);
 }
 
 } // namespace
@@ -350,48 +288,27 @@ int relpose_workgroups(const cugo_relpose_edges& ev)
 void launch_relpose_errors(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
                            double* d_wg_chi, double* d_edge_chi)
 {
-    const int wgs = relpose_workgroups(ev);
-    if (!wgs)
-        return;
-    const RelPoseArgs a = args_of(ev, plan, d_poses, d_wg_chi, d_edge_chi);
-    LaunchScope scope("k_relpose_errors", s);
-    hipLaunchKernelGGL(k_relpose<RELPOSE_ERRORS>, dim3(wgs), dim3(RELPOSE_WG), 0, s, a, (double*)nullptr, (double*)nullptr,
-                       (const int32_t*)nullptr, (double*)nullptr, (double*)nullptr);
+    launch<RELPOSE_ERRORS>(s, "k_relpose_errors", ev, plan, d_poses, d_wg_chi, d_edge_chi, nullptr, nullptr, nullptr, nullptr,
+                           nullptr);
 }
 
 void launch_relpose_add(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
                         double* d_Hpp, double* d_bp, double* d_Hoff, double* d_wg_chi)
 {
-    const int wgs = relpose_workgroups(ev);
-    if (!wgs)
-        return;
-    const RelPoseArgs a = args_of(ev, plan, d_poses, d_wg_chi, nullptr);
-    LaunchScope scope("k_relpose_add", s);
-    hipLaunchKernelGGL(k_relpose<RELPOSE_HPP>, dim3(wgs), dim3(RELPOSE_WG), 0, s, a, d_Hpp, d_Hoff, (const int32_t*)nullptr,
-                       d_bp, (double*)nullptr);
+    launch<RELPOSE_HPP>(s, "k_relpose_add", ev, plan, d_poses, d_wg_chi, nullptr, d_Hpp, d_Hoff, nullptr, d_bp, nullptr);
 }
 
 void launch_relpose_add_schur(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
                               const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_wg_chi)
 {
-    const int wgs = relpose_workgroups(ev);
-    if (!wgs)
-        return;
-    const RelPoseArgs a = args_of(ev, plan, d_poses, d_wg_chi, nullptr);
-    LaunchScope scope("k_relpose_add_schur", s);
-    hipLaunchKernelGGL(k_relpose<RELPOSE_SCHUR>, dim3(wgs), dim3(RELPOSE_WG), 0, s, a, d_Hsc, d_Hsc, d_rowptr, d_bp, d_bsc);
+    launch<RELPOSE_SCHUR>(s, "k_relpose_add_schur", ev, plan, d_poses, d_wg_chi, nullptr, d_Hsc, d_Hsc, d_rowptr, d_bp, d_bsc);
 }
 
 void launch_relpose_add_offdiag(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
                                 double* d_Hsc)
 {
-    const int wgs = relpose_workgroups(ev);
-    if (!wgs)
-        return;
-    const RelPoseArgs a = args_of(ev, plan, d_poses, nullptr, nullptr);
-    LaunchScope scope("k_relpose_add_offdiag", s);
-    hipLaunchKernelGGL(k_relpose<RELPOSE_OFFDIAG>, dim3(wgs), dim3(RELPOSE_WG), 0, s, a, (double*)nullptr, d_Hsc,
-                       (const int32_t*)nullptr, (double*)nullptr, (double*)nullptr);
+    launch<RELPOSE_OFFDIAG>(s, "k_relpose_add_offdiag", ev, plan, d_poses, nullptr, nullptr, nullptr, d_Hsc, nullptr, nullptr,
+                            nullptr);
 }
 
 } // namespace cugo_k

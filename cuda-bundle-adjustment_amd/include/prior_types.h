@@ -39,36 +39,48 @@ public:
     PosePriorMatch(const Se3<S>& z, const S* info36) : pose(z) { std::copy(info36, info36 + 36, information); }
 };
 
-class CUGO_API PosePriorEdge : public Edge<6, PosePriorMatch<double>, PoseVertex>
+/** what the SE(3) edge kinds share over their vertex list (one pose: the prior; two: relpose_types.h): the edge ... */
+template <typename... VertexTypes>
+class Se3Edge : public Edge<6, PosePriorMatch<double>, VertexTypes...>
 {
 public:
     void* getMeasurement() noexcept override
     {
-        touchOwner(); // mutable pointer: counts as a change (optimisable_graph.h, change tracking)
-        return static_cast<void*>(&measurement);
+        this->touchOwner(); // mutable pointer: counts as a change (optimisable_graph.h, change tracking)
+        return static_cast<void*>(&this->measurement);
     }
-    const void* measurementData() const noexcept override { return static_cast<const void*>(&measurement); }
+    const void* measurementData() const noexcept override { return static_cast<const void*>(&this->measurement); }
 };
 
-/** with GraphOptimisationOptions::perEdgeInformation the edges' own matrices count, otherwise the set's (the identity
- *  until setInformationMatrix is called); the scalar setInformation() of the base class is not used by this set */
-class CUGO_API PosePriorEdgeSet : public EdgeSet<6, PosePriorMatch<double>, PoseVertex>
+/** ... and the set.  With GraphOptimisationOptions::perEdgeInformation the edges' own matrices count, otherwise the
+ *  set's (the identity until setInformationMatrix is called); the scalar setInformation() of the base class is not
+ *  used by these sets */
+template <typename... VertexTypes>
+class Se3EdgeSet : public EdgeSet<6, PosePriorMatch<double>, VertexTypes...>
 {
 public:
-    PosePriorEdgeSet()
+    Se3EdgeSet()
     {
         for (int i = 0; i < 36; i++)
             info36_[i] = i % 7 == 0 ? 1.0 : 0.0;
     }
     void setInformationMatrix(const double* info36) noexcept
     {
-        touch();
+        this->touch();
         std::copy(info36, info36 + 36, info36_);
     }
     const double* informationMatrix() const noexcept { return info36_; }
 
 private:
     double info36_[36];
+};
+
+class CUGO_API PosePriorEdge : public Se3Edge<PoseVertex>
+{
+};
+
+class CUGO_API PosePriorEdgeSet : public Se3EdgeSet<PoseVertex>
+{
 };
 
 } // namespace cugo

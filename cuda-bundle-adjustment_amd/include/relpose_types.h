@@ -26,44 +26,19 @@
 // the terms are reachable as well (include/cugo_hip.h: cugo_relpose_edges, cugo_relpose_plan_create,
 // cugo_relpose_compute_errors, cugo_relpose_construct_quadratic_form[_schur]).
 #pragma once
-#include <algorithm>
-
 #include "prior_types.h"
 
 namespace cugo
 {
 
 /** measurement: PosePriorMatch (the measured relative pose Z and its 6 x 6 information); vertex 0 is a, vertex 1 is b */
-class CUGO_API RelPoseEdge : public Edge<6, PosePriorMatch<double>, PoseVertex, PoseVertex>
+class CUGO_API RelPoseEdge : public Se3Edge<PoseVertex, PoseVertex>
 {
-public:
-    void* getMeasurement() noexcept override
-    {
-        touchOwner(); // mutable pointer: counts as a change (optimisable_graph.h, change tracking)
-        return static_cast<void*>(&measurement);
-    }
-    const void* measurementData() const noexcept override { return static_cast<const void*>(&measurement); }
 };
 
-/** with GraphOptimisationOptions::perEdgeInformation the edges' own matrices count, otherwise the set's (the identity
- *  until setInformationMatrix is called); the scalar setInformation() of the base class is not used by this set */
-class CUGO_API RelPoseEdgeSet : public EdgeSet<6, PosePriorMatch<double>, PoseVertex, PoseVertex>
+/** the information matrix of the set: as PosePriorEdgeSet's (prior_types.h: Se3EdgeSet) */
+class CUGO_API RelPoseEdgeSet : public Se3EdgeSet<PoseVertex, PoseVertex>
 {
-public:
-    RelPoseEdgeSet()
-    {
-        for (int i = 0; i < 36; i++)
-            info36_[i] = i % 7 == 0 ? 1.0 : 0.0;
-    }
-    void setInformationMatrix(const double* info36) noexcept
-    {
-        touch();
-        std::copy(info36, info36 + 36, info36_);
-    }
-    const double* informationMatrix() const noexcept { return info36_; }
-
-private:
-    double info36_[36];
 };
 
 } // namespace cugo

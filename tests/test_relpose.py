@@ -270,6 +270,49 @@ def test_one_shared_information_matrix_and_a_singular_one(ctx):
     assert chi > 0 and np.linalg.matrix_rank(H[3]) <= 6
 
 
+@pytest.mark.parametrize("rk", RKS)
+def test_an_edge_to_the_fixed_identity_is_the_prior_term_for_term(ctx, rk):
+    """relpose_types.h: "With T_b the fixed identity this is the pose prior, term for term."  5 free poses and a fixed
+    pose at the identity; the same measurements (every angle of ANGLES on every pose) and per-edge Omegas once as priors
+    and once as relative-pose edges a = the free pose, b = the fixed one.  The two kernels share the residual and J_l^-1
+    (ba_math.h), R_a I^T and t_a - R_A 0 are exact up to the sign of a zero and the products sum in the same order, so
+    H, b, chi2 and the per-edge chi2 of the two entry points are the same bits (measured before it was asserted: see
+    profiles/se3_edges_refactor_ab.txt)."""
+    rng = np.random.default_rng(40 + rk[0])
+    poses = np.array([icp_ref.random_pose(rng) for _ in range(5)] + [[0, 0, 0, 1.0, 0, 0, 0]])
+    E = 5 * len(ANGLES)
+    pose = np.repeat(np.arange(5, dtype=np.int32), len(ANGLES))  # (sorted by pose: the walks of both kernels are this order)
+    z = np.zeros((E, 7))
+    for i, p in enumerate(pose):  # as tests/test_prior.py make_case: the residual angle is exact
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        z[i] = icp_ref.left_update(poses[p], np.concatenate([-ANGLES[i % len(ANGLES)] * axis, rng.normal(0, 0.5, 3)]))
+    info = np.array([PR.random_spd(rng, rng.uniform(0.5, 3.0)) for _ in range(E)])
+    pr = PR.make_prior(pose, z, info, rk=rk)
+    rp = RR.make_edges(pose, np.full(E, 5), z, info, rk=rk)
+    # the priors
+    evp = PR.upload(ctx, 6, 5, pr)
+    d_poses = ctx.to_dev(poses)
+    d_H, d_b, d_chi, d_edge = ctx.to_dev(np.zeros((5, 36))), ctx.to_dev(np.zeros((5, 6))), ctx.empty(2), ctx.empty(E)
+    cugo.check(cugo.lib().cugo_prior_construct_quadratic_form(ctx.h, C.byref(evp), d_poses, d_H, d_b, d_chi))
+    Hp, bp, chip = blocks(ctx.to_host(d_H, (5, 36)), 5), ctx.to_host(d_b, (5, 6)), ctx.to_host(d_chi, 1)[0]
+    cugo.check(cugo.lib().cugo_prior_compute_errors(ctx.h, C.byref(evp), d_poses, d_chi, d_edge))
+    chip_e, edgep = ctx.to_host(d_chi, 1)[0], ctx.to_host(d_edge, E)
+    # the relative-pose edges
+    rowptr, colind = RR.pattern(rp, 5)
+    assert len(colind) == 5  # no pair of free poses
+    H, b, Hoff, chi, (ev, pl, d_poses2) = run_build(ctx, poses, 5, rp, rowptr, colind)
+    chi_e, edge = run_errors(ctx, ev, d_poses2, E)
+    pl.close()
+    assert Hp.any() and bp.any() and chip > 0 and (edgep > 0).all() and not Hoff.any()
+    for what, got, want in (("H", H, Hp), ("b", b, bp), ("chi2", chi, chip), ("chi2 (error pass)", chi_e, chip_e),
+                            ("edge chi2", edge, edgep)):
+        got, want = np.asarray(got), np.asarray(want)
+        print("%s: max |relpose - prior| %.3g of scale %.3g" % (what, np.abs(got - want).max(), np.abs(want).max()))
+    assert np.array_equal(H, Hp) and np.array_equal(b, bp) and chi == chip
+    assert chi_e == chip_e and np.array_equal(edge, edgep)
+
+
 def test_terms_are_added_and_unreferenced_blocks_keep_their_canaries(ctx):
     rng, poses, rp = designed(seed=15)
     rowptr, colind = full_pattern(5)
