@@ -119,6 +119,9 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.cugo_last_error.restype = C.c_char_p
         _lib.cugo_ctx_stream.restype = C.c_void_p
+        # (ctx, ev, hs, d_Hll, d_Hpl, d_sigma, d_cov9, d_fail): device pointers as c_void_p, None = NULL
+        _lib.cugo_landmark_covariances.argtypes = [C.c_void_p, C.POINTER(Edges), C.POINTER(HscStruct)] + [C.c_void_p] * 5
+        _lib.cugo_landmark_covariances.restype = C.c_int
     return _lib
 
 

@@ -646,6 +646,24 @@ int cugo_chol_inverse_blocks(cugo_chol* s, int n_pairs, const int32_t* h_rows, c
     }
     return CUGO_OK;
 }
+int cugo_landmark_covariances(cugo_ctx* ctx, const cugo_edges* ev, const cugo_hsc_struct* hs, const double* d_Hll,
+                              const double* d_Hpl, const double* d_sigma, double* d_cov9, int32_t* d_fail)
+{
+    return guarded([&] {
+        if (!ctx || !ev || !hs || !d_Hll || !d_Hpl || !d_sigma || !d_cov9 || !d_fail)
+            throw std::invalid_argument("cugo_landmark_covariances: null argument");
+        if (ev->block_f32)
+            throw std::invalid_argument("cugo_landmark_covariances: the kernel reads Hpl as fp64 (ev->block_f32 is set)");
+        if (ev->n_landmarks_free <= 0)
+            return;
+        if (!ev->d_lm_ptr || !ev->d_pose || !ev->d_flags || !hs->d_rowptr || !hs->d_colind)
+            throw std::invalid_argument("cugo_landmark_covariances: null array in ev or hs");
+        CUGO_HIP(hipMemsetAsync(d_fail, 0, sizeof(int32_t), ctx->stream));
+        cugo_k::launch_lm_covariance(ctx->stream, ev->n_landmarks_free, ev->d_lm_ptr, ev->d_pose, ev->d_flags, d_Hll,
+                                     d_Hpl, hs->d_rowptr, hs->d_colind, d_sigma, d_cov9, d_fail);
+        CUGO_HIP(hipGetLastError());
+    });
+}
 #ifdef CUGO_DEBUG_HOOKS // diagnosis entry points: only libcugo_hip_hooks.so exports them (csrc/host/cugo_debug.h)
 int cugo_debug_pin_reference(void)
 {

@@ -224,6 +224,27 @@ int cugo_chol_selected_inverse(cugo_chol* s, double* d_sigma);
  * workspace of 288 n_block_rows bytes; the pairs are processed in batches whose rows fit 512 MB (or CUGO_XCOV_BATCH
  * rows, read when the solver is created).  The same bits on every call, whatever the batches. */
 int cugo_chol_inverse_blocks(cugo_chol* s, int n_pairs, const int32_t* h_rows, const int32_t* h_cols, double* d_out);
+/* Extension: the 3x3 marginal covariances of the free landmarks from the pose blocks of the inverse.  With
+ * Hll_l = L L^T and G_e = Hpl_e L^-T,
+ *   d_cov9[l] = L^-T (I + sum_{e, f} G_e^T Sigma_{p(e) p(f)} G_f) L^-1      (3x3, column-major, exactly symmetric),
+ * e and f over the edge slots [lm_ptr[l], lm_ptr[l+1]) of landmark l that COUNT: those with none of
+ * CUGO_EDGE_FIXED_L, CUGO_EDGE_FIXED_P, CUGO_EDGE_INACTIVE set.  Of every other slot only the flag is read: its pose
+ * index and its Hpl block may hold anything.  A landmark without a counted edge gets Hll^-1.
+ *   d_Hll [Lfree][9], d_Hpl [E][18] (double: CUGO_ERR_INVALID with ev->block_f32), as cugo_construct_quadratic_form
+ *   leaves them (undamped);
+ *   d_sigma [hs->n_blocks][36]: the blocks of the pose covariance on the pattern of hs (d_rowptr / d_colind: upper
+ *   block CSR, diagonal block first, columns ascending), each 6x6 column-major with the rows of the block row — the
+ *   layout cugo_chol_selected_inverse writes, diagonal blocks exactly symmetric as it writes them (the result is the
+ *   lower triangle of the expression above, mirrored).  The pattern must hold the block (min, max) of every pair of poses that
+ *   counted edges of one landmark join; Sigma_{ab} with a > b is read as the transpose of block (b, a).
+ * d_fail[0] (int32, device) is zeroed here and set to 1 by every landmark whose Hll has a pivot <= 0 or a NaN in its
+ * 3x3 Cholesky factorisation (a free landmark without any active edge at lambda = 0 among them): the block of such a
+ * landmark is nine zeros, every other block is as without it.  Asynchronous on the context's stream; the flag stays on
+ * the device, as cugo_chol_factor_solve leaves its own.  One thread per landmark, no atomics: the same bits on every
+ * call.  CUGO_ERR_INVALID for a null argument; CUGO_OK with nothing launched when n_landmarks_free == 0. */
+int cugo_landmark_covariances(cugo_ctx* ctx, const cugo_edges* ev, const cugo_hsc_struct* hs, const double* d_Hll,
+                              const double* d_Hpl, const double* d_sigma, double* d_cov9 /* [9 * n_landmarks_free] */,
+                              int32_t* d_fail);
 /* statistics of the analysis: nnz(L) in scalars, factorisation flops, #supernodes, #stages */
 int cugo_chol_stats(const cugo_chol* s, double* nnzL, double* flops, int* n_supernodes,
                     int* n_stages, double* front_bytes);
@@ -635,7 +656,10 @@ int cugo_graph_n_active_edges(cugo_graph* g);
  * weights included, the edges of the current flattening), forms the Schur complement, factors it and runs
  * the selected inverse (cugo_chol_selected_inverse); the landmark blocks follow from the pose blocks.  The
  * results are kept until the next initialize(); the estimates and the LM state are left as they were.
- * CUGO_ERR_NUMERIC on a zero pivot (e.g. an unconstrained gauge or an edgeless free pose),
+ * CUGO_ERR_NUMERIC on a zero pivot (e.g. an unconstrained gauge or an edgeless free pose).  A free landmark without
+ * an active edge — it never had one, or outlier rejection took them all — has Hll = 0 at lambda = 0: what = 2 and
+ * what = 3 then fail as a whole with CUGO_ERR_NUMERIC and keep nothing, what = 1 succeeds (the poses do not depend on
+ * it); fix such a landmark or remove it to get the others.
  * CUGO_ERR_INVALID before initialize(), on plan-only, sharded or fp32-internal graphs. */
 int cugo_graph_compute_covariances(cugo_graph* g, int what);
 /* diagonal blocks by caller id: cov36 [n][36] (6x6, column-major, tangent order [rotation, translation]
