@@ -6,7 +6,10 @@ change of a recipe cannot silently lose what the layout is for.
 
 An ICP kind is a dict pose [E] (ascending), p [E,3], n [E,3] + d [E] (plane) or a, b, u [E,3] (line; u = (b - a) / |b - a| in
 double, the array the device is given), omega [E] or [1], active [E] bool, flags [E] uint8, rk (type, delta).  A prior set is
-the dict of prior_ref.make_prior, sorted by pose, with flags."""
+the dict of prior_ref.make_prior, sorted by pose, with flags.
+
+The relative-pose kernel (relpose_kernels.hip: RELPOSE_POSES = 4 poses per workgroup, one wave walks a pose's incidence
+list) has its layouts at the end of the file (relpose_layout); test_relpose_ref_host.py asserts their census."""
 import functools
 
 import numpy as np
@@ -301,3 +304,273 @@ def schur_rows(P, seed=77):
     rowptr = np.concatenate([[1], 1 + np.cumsum(n)]).astype(np.int32)
     assert np.all(rowptr[:P] != np.arange(P))
     return rowptr, int(rowptr[-1])
+
+
+# ---------------------------------------------------------------- relative-pose edges (relpose_kernels.hip)
+# A layout is dict(poses [P,7], n_free, P (all poses, free first), rp (relpose_ref.make_edges + flags = the plan's flags,
+# rt_active / rt_flags = what the device is given), rowptr, colind (the pattern of the plan's edges plus spare blocks no edge
+# maps to: (p, n_free - 1) in every row), census).  RELPOSE_POSES = 4 poses (waves) per workgroup.
+RELPOSE_POSES = 4
+RELPOSE_NAMES = (["R-wg%d" % n for n in (1, 3, 4, 5, 8, 9)] + ["R-sides", "R-angles", "R-far"] + ["R-rk%d" % k for k in range(4)] +
+                 ["R-info_perEdge", "R-info_one", "R-info_singular", "R-info_indef"])
+RELPOSE_ZERO = ["R-zero%d" % k for k in range(4)]
+RELPOSE_TOTALS = ["R-totals%d" % n for n in (1024, 1025, 1029)]
+SIDES_HUB, SIDES_BIG, SIDES_EMPTY, SIDES_PLAN_OFF, SIDES_RT_OFF, SIDES_ONE, SIDES_FREE = 3, 0, 4, 10, 11, 12, 13
+RK_X = [0.1, 0.5, 0.9, 1.1, 2.0, 10.0]          # R-rk: x / delta^2 of the edges, in turn
+
+
+def relpose_pattern_with_spares(rp, n_free):
+    import relpose_ref as RR
+    rowptr, colind = RR.pattern(rp, n_free)
+    rows = [set(colind[rowptr[p] + 1:rowptr[p + 1]].tolist()) | ({n_free - 1} if p < n_free - 1 else set()) for p in range(n_free)]
+    ci, rp_ = [], [0]
+    for p in range(n_free):
+        ci += [p] + sorted(rows[p])
+        rp_.append(len(ci))
+    return np.array(rp_, np.int32), np.array(ci, np.int32)
+
+
+def relpose_census(lay, inc_ptr=None, inc=None, off_blk=None):
+    """what k_relpose meets, from the plan's arrays (those of relpose_ref.plan unless the C plan's are handed in)"""
+    import relpose_ref as RR
+    rp, nf = lay["rp"], lay["n_free"]
+    if inc_ptr is None:
+        inc_ptr, inc, off_blk = RR.plan(rp, nf, lay["rowptr"], lay["colind"])
+    a, b = np.asarray(rp["a"], int), np.asarray(rp["b"], int)
+    E = len(a)
+    rt = np.asarray(rp["rt_active"], bool)
+    deg = np.diff(inc_ptr)
+    wgs = (nf + RELPOSE_POSES - 1) // RELPOSE_POSES if E and nf else 0
+    walked = np.zeros(E, bool)
+    walked[np.asarray(inc, int) >> 1] = True
+    touching = [np.flatnonzero((a == p) | (b == p)) for p in range(nf)]
+    c = dict(workgroups=wgs, idle_waves_in_last_workgroup=wgs * RELPOSE_POSES - nf, degrees=deg.tolist(),
+             fixed_fixed=int(((a >= nf) & (b >= nf)).sum()), fixed_fixed_walked=int((walked & (a >= nf) & (b >= nf)).sum()),
+             poses_without_any_edge_between_active=[p for p in range(1, nf - 1) if len(touching[p]) == 0 and deg[p - 1] and deg[p + 1]],
+             poses_all_inactive_in_plan=[p for p in range(nf) if len(touching[p]) and deg[p] == 0],
+             poses_inactive_at_run_time_only=[p for p in range(nf) if deg[p] and not rt[touching[p]].any() and rp["active"][touching[p]].all()],
+             blocks_no_edge_maps_to=int(len(lay["colind"]) - nf - len(set(off_blk[off_blk >= 0].tolist()))),
+             rows_with_rowptr_ne_p=int((lay["rowptr"][:nf] != np.arange(nf)).sum()))
+    k = np.asarray(off_blk)
+    cnt = RR.counting(rp, nf)
+    nb = np.zeros(E, bool)
+    nb[:-1] |= k[1:] >= 0
+    nb[1:] |= k[:-1] >= 0
+    c["no_block_next_to_block"] = int((cnt & (k < 0) & nb).sum())
+    per_pair, mixed = {}, {}
+    for e in np.flatnonzero(k >= 0):
+        per_pair[k[e]] = per_pair.get(k[e], 0) + 1
+        mixed.setdefault(k[e], set()).add(bool(a[e] < b[e]))
+    c["edges_per_pair"] = sorted(set(per_pair.values()))
+    c["pairs_in_mixed_orientation"] = sorted(per_pair[q] for q in per_pair if len(mixed[q]) == 2)
+    h = lay.get("hub")
+    if h is not None:
+        cases = dict(a_hi=0, a_lo=0, b_hi=0, b_lo=0, a_fixed=0, b_fixed=0)
+        for rec in inc[inc_ptr[h]:inc_ptr[h + 1]]:
+            e, side = int(rec) >> 1, int(rec) & 1
+            other = a[e] if side else b[e]
+            cases[("b_" if side else "a_") + ("fixed" if other >= nf else "hi" if other > h else "lo")] += 1
+        c["hub"] = cases
+    return c
+
+
+def _rel_finish(poses, n_free, rp, rt_active=None, **extra):
+    rp["flags"] = np.where(rp["active"], 0, INACTIVE).astype(np.uint8)
+    rp["rt_active"] = rp["active"].copy() if rt_active is None else np.asarray(rt_active, bool) & rp["active"]
+    rp["rt_flags"] = np.where(rp["rt_active"], 0, INACTIVE).astype(np.uint8)
+    rowptr, colind = relpose_pattern_with_spares(rp, n_free)
+    lay = dict(poses=poses, n_free=n_free, P=len(poses), rp=rp, rowptr=rowptr, colind=colind, **extra)
+    lay["census"] = relpose_census(lay)
+    return lay
+
+
+def _chain_pairs(n_free):
+    """n_free free poses and two fixed ones with mid-range ids (remapped to the tail: free first): a chain in alternating
+    orientation plus two chords"""
+    N = n_free + 2
+    fixed = [N // 3, (2 * N) // 3] if N > 3 else [1, 2]
+    new = {}
+    for i in range(N):
+        if i not in fixed:
+            new[i] = len(new)
+    for i in fixed:
+        new[i] = len(new)
+    pairs = [(new[i], new[i + 1]) if i % 2 == 0 else (new[i + 1], new[i]) for i in range(N - 1)]
+    pairs += [(new[0], new[N - 1]), (new[N // 2], new[0])]
+    return pairs
+
+
+def _rel_random(seed, n_free, pairs, rk=(0, 1.0), rot=0.05, trans=0.3, per_edge_info=True, P=None):
+    import relpose_ref as RR
+    rng = np.random.default_rng(seed)
+    P = n_free + 2 if P is None else P
+    poses = np.array([icp_ref.random_pose(rng) for _ in range(P)])
+    return rng, poses, RR.random_edges(rng, poses, pairs, rk=rk, rot=rot, trans=trans, per_edge_info=per_edge_info)
+
+
+def _sides(seed, rk, scale_to_rk=False):
+    """R-sides: see the census.  13 free poses, 2 fixed"""
+    nf = SIDES_FREE
+    h, f0, f1 = SIDES_HUB, nf, nf + 1
+    pairs = [(h, f0), (h, 5), (h, 1), (5, h), (1, h), (f1, h),            # the hub: a to fixed (no block) next to a to hi
+             (f0, f1),                                                      # fixed-fixed
+             (6, 8), (8, 6), (6, 8),                                        # three on one pair
+             (SIDES_ONE, 2)]                                                # a pose with this one edge
+    pairs += [(7, 9) if k % 2 == 0 else (9, 7) for k in range(40)]          # 40 on one pair, alternating
+    n_plan_off = len(pairs)
+    pairs += [(SIDES_PLAN_OFF, 2), (1, SIDES_PLAN_OFF)]                     # inactive in the plan
+    n_rt_off = len(pairs)
+    pairs += [(SIDES_RT_OFF, 2), (5, SIDES_RT_OFF), (SIDES_RT_OFF, f0)]     # inactive at run time only
+    n_big = len(pairs)
+    partners = [1, 2, 5, 6, 7, 8, 9, f0, f1]
+    rng0 = np.random.default_rng(seed + 1000)
+    for k in range(300):
+        q = partners[k % len(partners)]
+        pairs.append((SIDES_BIG, q) if rng0.random() < 0.5 else (q, SIDES_BIG))
+    rng, poses, rp = _rel_random(seed, nf, pairs, rk=rk, rot=0.1, trans=0.3)
+    rp["active"][n_plan_off:n_rt_off] = False
+    rt = np.ones(len(pairs), bool)
+    rt[n_rt_off:n_big] = False
+    if scale_to_rk:
+        import relpose_ref as RR
+        d2 = rk[1] ** 2
+        for e in range(len(pairs)):
+            r = RR.residual(poses[rp["a"][e]], poses[rp["b"][e]], rp["z"][e])
+            rp["info"][e] *= RK_X[e % len(RK_X)] * d2 / float(r @ rp["info"][e] @ r)
+    return _rel_finish(poses, nf, rp, rt, hub=h)
+
+
+def _census_x(lay):
+    """R-rk: counting edges inside / outside delta^2 (x in double)"""
+    import relpose_ref as RR
+    rp = lay["rp"]
+    eff = dict(rp, active=rp["rt_active"])
+    x = np.array([float(RR.residual(lay["poses"][a], lay["poses"][b], z) @ Om @ RR.residual(lay["poses"][a], lay["poses"][b], z))
+                  for a, b, z, Om in zip(rp["a"], rp["b"], rp["z"], np.broadcast_to(rp["info"], (len(rp["a"]), 6, 6)))])
+    x = x[RR.counting(eff, lay["n_free"])]
+    return dict(inside=int((x <= rp["rk"][1] ** 2).sum()), outside=int((x > rp["rk"][1] ** 2).sum()), negative=int((x < 0).sum()))
+
+
+def _census_angles(lay):
+    """theta and sin theta of D from its quaternion, in double, per edge (as _census_prior)"""
+    import synth
+    rp, poses = lay["rp"], lay["poses"]
+    th, sn = [], []
+
+    def conj(q):
+        return np.array([-q[0], -q[1], -q[2], q[3]])
+    for a, b, z in zip(rp["a"], rp["b"], rp["z"]):
+        q = synth.quat_mul(synth.quat_mul(poses[a][:4], conj(poses[b][:4])), conj(z[:4]))
+        nv, w = np.linalg.norm(q[:3]), abs(q[3])
+        th.append(2 * np.arctan2(nv, w)), sn.append(2 * w * nv)
+    th, sn = np.array(th), np.array(sn)
+    return {"theta": th, "sn": sn, "sn_le_1e-12": int((sn <= 1e-12).sum()), "sn_gt_1e-12": int((sn > 1e-12).sum()),
+            "theta_lt_1e-3": int((th < 1e-3).sum()), "theta_ge_1e-3": int((th >= 1e-3).sum()), "near_pi": int((np.pi - th < 2e-3).sum())}
+
+
+HURWITZ = [np.array(q, float) for q in
+           [(1, 0, 0, 0), (0, -1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1), (.5, .5, .5, .5), (-.5, .5, .5, .5), (.5, -.5, .5, .5),
+            (.5, .5, -.5, .5), (-.5, -.5, .5, .5), (.5, -.5, -.5, .5)]]
+
+
+@functools.lru_cache(maxsize=None)
+def relpose_layout(name):
+    """'R-wg<n_free>', 'R-sides', 'R-angles', 'R-far', 'R-zero<k>', 'R-rk<k>' (k: index into RKS), 'R-info_<perEdge | one | singular |
+    indef>', 'R-totals<n_free>'"""
+    import relpose_ref as RR
+    import synth
+    if name.startswith("R-wg"):
+        nf = int(name[4:])
+        rng, poses, rp = _rel_random(400 + nf, nf, _chain_pairs(nf), rk=RKS[nf % 4], rot=0.2, trans=0.5)
+        return _rel_finish(poses, nf, rp)
+    if name == "R-sides":
+        return _sides(420, (0, 1.0))
+    if name.startswith("R-rk"):
+        lay = _sides(421, RKS[int(name[4:])], scale_to_rk=True)
+        lay["census"]["x"] = _census_x(lay)
+        return lay
+    if name == "R-angles":
+        # hub 3; partners 0..2, 4..6 free, 7 fixed; R_partner = Rot(2 rad about its own axis)^T R_hub, so R_A is that rotation
+        # (or its transpose with the hub as b) and D is small only because Z cancels it
+        rng = np.random.default_rng(430)
+        nf, h = 7, 3
+        poses = np.zeros((8, 7))
+        poses[h] = icp_ref.random_pose(rng)
+        for p in range(8):
+            if p != h:
+                ax = rng.normal(size=3)
+                q = synth.quat_mul(synth.quat_from_rotvec(-rng.uniform(1.9, 2.1) * ax / np.linalg.norm(ax)), poses[h][:4])
+                poses[p] = np.concatenate([q / np.linalg.norm(q), rng.normal(0, 2.0, 3)])
+        free = [0, 1, 2, 4, 5, 6]
+        pairs, angles = [], []
+        for role in range(3):
+            for i, th in enumerate(ANGLES):
+                for k in range(3):
+                    q = free[(3 * i + k) % 6]
+                    pairs.append([(h, q), (q, h), (h, 7)][role])
+                    angles.append(th)
+        z = np.array([RR.measured(rng, poses[a], poses[b], trans=1.0, angle=th) for (a, b), th in zip(pairs, angles)])
+        info = np.array([prior_ref.random_spd(rng, rng.uniform(0.5, 3.0)) for _ in pairs])
+        pairs = np.array(pairs, np.int32)
+        lay = _rel_finish(poses, nf, RR.make_edges(pairs[:, 0], pairs[:, 1], z, info), hub=h)
+        lay["census"]["angles"] = _census_angles(lay)
+        lay["angles"] = np.array(angles)
+        RA = [RR.relative(poses[a], poses[b])[0] for a, b in pairs]
+        lay["census"]["R_A_angle"] = (min(np.arccos((np.trace(R) - 1) / 2) for R in RA), max(np.arccos((np.trace(R) - 1) / 2) for R in RA))
+        return lay
+    if name == "R-far":
+        # camera centres c = C0 + N(0, 1), t = -R c: |t| ~ 1e3, t_A = R_a (c_b - c_a) of order 1
+        rng = np.random.default_rng(440)
+        nf = 10
+        poses = np.array([icp_ref.random_pose(rng) for _ in range(12)])
+        for p in range(12):
+            poses[p, 4:] = -synth.quat_to_R(poses[p, :4]) @ (np.array([600.0, -500.0, 700.0]) + rng.normal(0, 1.0, 3))
+        pairs = _chain_pairs(nf) + [(2, 7), (9, 4), (5, 1)]
+        rp = RR.random_edges(rng, poses, pairs, rot=0.05, trans=1e-2)
+        lay = _rel_finish(poses, nf, rp)
+        t = [RR.relative(poses[a], poses[b]) for a, b in pairs]
+        lay["census"]["tA_rel"] = [float(np.linalg.norm(tA) / (np.abs(poses[a][4:]).sum() + (np.abs(RA) @ np.abs(poses[b][4:])).sum()))
+                                   for (RA, tA), (a, b) in zip(t, pairs)]
+        lay["census"]["t_norm"] = [float(np.linalg.norm(p[4:])) for p in poses]
+        lay["census"]["tD_norm"] = [float(np.linalg.norm(RR.residual(poses[a], poses[b], z)[3:])) for (a, b), z in zip(pairs, rp["z"])]
+        return lay
+    if name.startswith("R-zero"):
+        # unit quaternions with entries in {0, +-1, +-1/2} (their products are again such: exact), translations in quarters
+        rng = np.random.default_rng(450)
+        nf = 6
+        poses = np.array([np.concatenate([HURWITZ[i], rng.integers(-16, 17, 3) / 4.0]) for i in rng.permutation(len(HURWITZ))[:nf + 1]])
+        pairs = [(0, 1), (2, 1), (2, 3), (4, 3), (4, 5), (6, 5), (0, 6), (5, 0), (3, 1), (1, 3)]
+        z = []
+        for a, b in pairs:
+            qb = poses[b][:4] * np.array([-1, -1, -1, 1.0])
+            RA = synth.quat_to_R(poses[a][:4]) @ synth.quat_to_R(poses[b][:4]).T
+            z.append(np.concatenate([synth.quat_mul(poses[a][:4], qb), poses[a][4:] - RA @ poses[b][4:]]))
+        info = np.array([prior_ref.random_spd(rng, 1.5) for _ in pairs])
+        pairs = np.array(pairs, np.int32)
+        return _rel_finish(poses, nf, RR.make_edges(pairs[:, 0], pairs[:, 1], np.array(z), info, rk=RKS[int(name[6:])]))
+    if name.startswith("R-info_"):
+        kind = name[7:]
+        nf = 9
+        rng, poses, rp = _rel_random(460, nf, _chain_pairs(nf) + [(0, 1), (4, 2)], rk=RKS[1] if kind in ("perEdge", "one") else (0, 1.0),
+                                     rot=0.3, trans=0.3)
+        E = len(rp["a"])
+        S = np.diag([1e3] * 3 + [1.0] * 3)          # Omega = A A^T: rotation block 1e6 x the translation block
+        per = np.array([(lambda A: A @ A.T)(S @ rng.normal(size=(6, 6))) for _ in range(E)])
+        rp["info"] = {"perEdge": per, "one": per[:1], "singular": np.diag([0, 0, 0, 4.0, 2.0, 1.0])[None],
+                      "indef": np.diag([-1.0, -1.0, -1.0, 1.0, 1.0, 1.0])[None]}[kind]
+        lay = _rel_finish(poses, nf, rp)
+        lay["census"]["x"] = _census_x(lay)
+        return lay
+    if name.startswith("R-totals"):
+        nf = int(name[8:])
+        N = nf + 1                                   # a ring, one fixed pose (index nf), one edge per pose
+        rng = np.random.default_rng(470)
+        poses = np.array([icp_ref.random_pose(rng) for _ in range(N)])
+        pairs = [(i, (i + 1) % N) for i in range(N)]
+        rp = RR.random_edges(rng, poses, pairs, rk=(3, 4.0), per_edge_info=False, rot=0.1, trans=0.3)
+        return _rel_finish(poses, nf, rp)
+    raise KeyError(name)
+
+
+def relpose_per_edge_info(rp):
+    return dict(rp, info=np.tile(rp["info"], (len(rp["a"]), 1, 1))) if len(rp["info"]) == 1 else rp

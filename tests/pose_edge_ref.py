@@ -1,5 +1,6 @@
 """Extended-precision reference of the unary pose edges (point-to-plane / point-to-line: icp_kernels.hip; SE(3) priors:
-prior_kernels.hip) with PER-ENTRY error bounds, in the manner of tests/kernel_ref.py (numpy, test only).
+prior_kernels.hip) and of the binary relative-pose SE(3) edges (relpose_kernels.hip, last section) with PER-ENTRY error
+bounds, in the manner of tests/kernel_ref.py (numpy, test only).
 
 Written from the formulas in the header comments of the two kernel files, in np.longdouble, vectorised over the edges.
 Inputs are plain arrays in the device order (edges sorted by pose); poses [P, 7] = (q x y z w, t).
@@ -69,6 +70,44 @@ K_* are not rounding counts but library / propagation allowances.  Measured on t
 numpy's sqrt, arctan2, log against longdouble on the layouts' values; the largest error in units of u of the result),
 4 x rounded up:
     sqrt 0.49 -> K_SQRT = 2;   arctan2 1.18 -> K_ATAN = 5;   rho, rho' (log, sqrt, the cube) 1.62 -> K_RHO = 7
+
+Relative-pose edges (relpose_kernels.hip): the prior's running error carried through A = T_a T_b^-1
+----------------------------------------------------------------------------------------------------
+The same two rules, per entry; no new allowance constant.  Roundings on the longest path of one entry (what the
+running error adds up; the masses are those of the operands, so t_A and u carry the digits they lose):
+    R_a, R_b, R_z                        the explicit formula                                     ->  4
+    R_A = R_a R_b^T                      4 + 4, product 1, 2 additions                            -> 11
+    t_A = t_a - R_A t_b                  11, product 1, 2 additions, the subtraction              -> 15   (|t_a| + |R_A| |t_b|)
+    D = R_A R_z^T                        11 + 4, product 1, 2 additions, + 6 for |q|^2 - 1 of the
+                                         THREE input quaternions (2 u each, as the prior's + 4)   -> 24
+    s, cs, sn, theta, f, c, phi          so3_log_terms: the prior's derivation on this D          (shared code)
+    t_D = t_A - D t_z                    24, product 1, 2 additions, the subtraction (15 beside)  -> 28   (|t_A| + |D| |t_z|)
+    J_a = [[J_l^-1, 0], [-[t_D]x, I]]    se3_jacobian: the prior's J                              (shared code)
+    J_b top left  -J_l^-1 R_A            e(J_l^-1) + 11, product 1, 2 additions
+        bottom left ([u]x R_A)_ij        u = t_D - t_A a COUNTED subtraction (28 + 15 + 1, mass |t_D| + |t_A|), times
+                                         R_A (11), product 1, the subtraction 1
+        bottom right -R_A                11
+    Or = Omega r, x = r.Or               6 terms each (1 product, 5 additions); x = max(0, .) is 1-Lipschitz
+    rho, w                               E_chi = rho' E_x + K_RHO (|rho| + rho0),  E_w = |rho''| E_x + K_RHO w
+    Omega J, J^T (Omega J), J^T Or       6 terms each, then w times the sum (1)
+H_aa, H_bb, b_a, b_b and the block H_(lo,hi) = J_lo^T Omega J_hi (J_a^T Omega J_b when a is lo, J_b^T Omega J_a when b is: the
+kernel forms it from the side of lo and never transposes) are V-valued per edge; relpose_build scatters value, error
+and |value| into H, b, Hoff, chi per pose (at the pose whose walk counts the edge), chi per edge and chi with
+    bound = u (X_err + n X_mass)                                            (relpose_bound = prior_bound)
+n = the number of edge terms in the entry (the walk's sum, the block's read-modify-write chain, the totals).
+Largest error / bound per output over the layouts of pose_designed.relpose_layout (every ratio is printed by the tests):
+    float64 replay in the device's order (x86-64, test_relpose_ref_host.py)
+        H 0.055   Hoff 0.079   b 0.037   chi 0.019   chi per edge 0.092   chi per pose 0.080
+    MI355X (gfx950, test_relpose_shapes.py)
+        H 0.062   Hoff 0.095   b 0.032   chi 0.019   chi per edge 0.18 (R-rk2: Tukey, x next to delta^2)
+    per layout on the MI355X, H / Hoff / b / chi / chi per edge:
+        R-wg1 .0086 / 0 / .0069 / .0042 / .013     R-wg3 .014 / .023 / .012 / .0030 / .019    R-wg4 .053 / .067 / .018 / 1.1e-4 / .010
+        R-wg5 .0069 / .015 / .0032 / 6.4e-5 / .011 R-wg8 .053 / .064 / .015 / .0012 / .014    R-wg9 .011 / .030 / .0063 / 1.2e-4 / .016
+        R-sides .048 / .057 / .0074 / 4.9e-4 / .027   R-angles .044 / .066 / .017 / 5.5e-4 / .025   R-far .045 / .076 / .032 / 2.2e-4 / .034
+        R-rk0 .059 / .080 / .0078 / 4.7e-4 / .032  R-rk1 .0068 / .021 / .0040 / .0026 / .025  R-rk2 .0068 / .0093 / .0078 / .0031 / .18
+        R-rk3 .0056 / .025 / .0046 / .0022 / .032  R-info_perEdge .017 / .029 / .021 / .0077 / .068   R-info_one .021 / .028 / .015 / .019 / .060
+        R-info_singular .062 / .095 / .018 / 4.7e-4 / .022   R-info_indef .046 / .095 / .018 / 1.3e-4 / .019
+        R-zero0..3 .042 / .017 / 0 / 0 / 0         R-totals1024 / 1025 / 1029: chi 1.3e-4 / .0010 / .0018, chi per edge .041 / .035 / .029
 """
 import numpy as np
 
@@ -78,6 +117,7 @@ C_ICP = dict(H=63, b=64, chi=38)
 C_ICP_PLANE = dict(H=51, b=53, chi=34)
 K_SQRT, K_ATAN, K_RHO = 2.0, 5.0, 7.0
 ICP_CHUNK, PRIOR_POSES, TOTAL_WG = 512, 8, 256
+RELPOSE_POSES = 4
 
 
 def _rot(q):
@@ -244,31 +284,26 @@ def c_theta(theta, cot_half):
     return np.where(theta < 0.3, ser, big)
 
 
-def prior_terms(poses, n_free, pr, dtype=LD, route="quat", sn_switch=1e-12, series_below=1e-3, full=True, w_scale=None):
-    """per-edge terms of a prior set pr = dict(pose [E], z [E,7], info [E or 1,6,6], active [E], rk): V-valued H [E,6,6],
-    b [E,6], chi [E] (zero where the edge does not count) and the angle quantities theta, sn.  route 'quat': the
-    well-conditioned reference values (longdouble); 'matrix': the formula under test as it stands (what a double
-    evaluation does; sn_switch and series_below are its two switches)"""
-    dt = dtype
-    pose = np.asarray(pr["pose"], int)
-    E = len(pose)
-    P7 = np.asarray(poses, dt)[pose]
-    z = np.asarray(pr["z"], dt).reshape(E, 7)
-    Om = np.broadcast_to(np.asarray(pr["info"], dt).reshape(-1, 6, 6), (E, 6, 6))
-    Rv, aR = _rot(P7[:, :4])
-    Zv, aZ = _rot(z[:, :4])
-    R, Rz = V(Rv, 4 * aR), V(Zv, 4 * aZ)
-    D = mm("eik,ejk->eij", R, Rz, 3)
-    D.e = D.e + 4                                         # |q|^2 - 1 of the two input quaternions
+def _qmul_conj(va, wa, vb, wb):
+    """(v, w) of q_a (x) conj(q_b); v [E,3], w [E,1]"""
+    return wb * va - wa * vb - np.cross(va, vb), wa * wb + (va * vb).sum(1)[:, None]
+
+
+def _unit(q):
+    return q / np.sqrt((q ** 2).sum(1))[:, None]
+
+
+def so3_log_terms(D, route, qD=None, sn_switch=1e-12, series_below=1e-3):
+    """from D (a V, [E,3,3]) to phi = Log_SO3(D) (a V) and c(theta), its error e_c, theta, sn: the part the prior and the
+    relative-pose edges share.  route 'quat': the values from qD = (v [E,3], w [E]), the quaternion of D in longdouble
+    (any sign), the errors those of the matrix formula; 'matrix': the formula under test on D.v as it stands"""
+    dt = D.v.dtype.type
+    E = len(D.v)
     s = _stack([(D[:, 2, 1] - D[:, 1, 2]).half(), (D[:, 0, 2] - D[:, 2, 0]).half(), (D[:, 1, 0] - D[:, 0, 1]).half()])
     one = V(np.ones(E, dt))
     cs = (D[:, 0, 0] + D[:, 1, 1] + D[:, 2, 2] - one).half()
     if route == "quat":
-        qa = P7[:, :4] / np.sqrt((P7[:, :4] ** 2).sum(1))[:, None]
-        qb = z[:, :4] / np.sqrt((z[:, :4] ** 2).sum(1))[:, None]
-        va, wa, vb, wb = qa[:, :3], qa[:, 3:], qb[:, :3], qb[:, 3:]
-        v = wb * va - wa * vb - np.cross(va, vb)
-        w = wa[:, 0] * wb[:, 0] + (va * vb).sum(1)
+        v, w = qD
         sg = np.where(w < 0, -1, 1).astype(dt)
         v, w = v * sg[:, None], w * sg
         nv = np.sqrt((v * v).sum(1))
@@ -299,6 +334,52 @@ def prior_terms(poses, n_free, pr, dtype=LD, route="quat", sn_switch=1e-12, seri
     phi = V(f[:, None] * s.v, f[:, None] * s.e + np.abs(s.v) * e_f[:, None] + np.abs(f[:, None] * s.v))
     if route == "quat":
         phi.v = phi_v
+    return phi, cc, e_c, theta, sn
+
+
+def se3_jacobian(phi, cc, e_c, tD):
+    """J = [[J_l^-1, 0], [-[tD]x, I]] (a V, [E,6,6]) and J_l^-1 = I - K/2 + c K2, K = [phi]x, K2 = K K written out"""
+    dt = phi.v.dtype.type
+    E = len(phi.v)
+    p0, p1, p2 = phi[:, 0], phi[:, 1], phi[:, 2]
+    zero = V(np.zeros(E, dt))
+    K = _stack([_stack([zero, -p2, p1]), _stack([p2, zero, -p0]), _stack([-p1, p0, zero])])
+    K2 = _stack([_stack([-(p1 * p1 + p2 * p2), p0 * p1, p0 * p2]), _stack([p0 * p1, -(p0 * p0 + p2 * p2), p1 * p2]),
+                 _stack([p0 * p2, p1 * p2, -(p0 * p0 + p1 * p1)])])
+    cV = V(cc[:, None, None] + 0 * K2.v, e_c[:, None, None] + 0 * K2.v)
+    I3 = V(np.broadcast_to(np.eye(3, dtype=dt), (E, 3, 3)).copy())
+    Jr = (I3 - K.half()) + cV * K2
+    t0, t1, t2 = tD[:, 0], tD[:, 1], tD[:, 2]
+    Jt = _stack([_stack([zero, t2, -t1]), _stack([-t2, zero, t0]), _stack([t1, -t0, zero])])
+    J = V(np.zeros((E, 6, 6), dt))
+    J.v[:, :3, :3], J.e[:, :3, :3] = Jr.v, Jr.e
+    J.v[:, 3:, :3], J.e[:, 3:, :3] = Jt.v, Jt.e
+    J.v[:, 3:, 3:] = np.eye(3, dtype=dt)
+    return J, Jr
+
+
+def prior_terms(poses, n_free, pr, dtype=LD, route="quat", sn_switch=1e-12, series_below=1e-3, full=True, w_scale=None):
+    """per-edge terms of a prior set pr = dict(pose [E], z [E,7], info [E or 1,6,6], active [E], rk): V-valued H [E,6,6],
+    b [E,6], chi [E] (zero where the edge does not count) and the angle quantities theta, sn.  route 'quat': the
+    well-conditioned reference values (longdouble); 'matrix': the formula under test as it stands (what a double
+    evaluation does; sn_switch and series_below are its two switches)"""
+    dt = dtype
+    pose = np.asarray(pr["pose"], int)
+    E = len(pose)
+    P7 = np.asarray(poses, dt)[pose]
+    z = np.asarray(pr["z"], dt).reshape(E, 7)
+    Om = np.broadcast_to(np.asarray(pr["info"], dt).reshape(-1, 6, 6), (E, 6, 6))
+    Rv, aR = _rot(P7[:, :4])
+    Zv, aZ = _rot(z[:, :4])
+    R, Rz = V(Rv, 4 * aR), V(Zv, 4 * aZ)
+    D = mm("eik,ejk->eij", R, Rz, 3)
+    D.e = D.e + 4                                         # |q|^2 - 1 of the two input quaternions
+    qD = None
+    if route == "quat":
+        qa, qb = _unit(P7[:, :4]), _unit(z[:, :4])
+        v, w = _qmul_conj(qa[:, :3], qa[:, 3:], qb[:, :3], qb[:, 3:])
+        qD = (v, w[:, 0])
+    phi, cc, e_c, theta, sn = so3_log_terms(D, route, qD, sn_switch, series_below)
     T = V(P7[:, 4:].copy())
     tD = T - mm("eij,ej->ei", D, V(z[:, 4:].copy()), 3)
     r = V(np.concatenate([phi.v, tD.v], 1), np.concatenate([phi.e, tD.e], 1))
@@ -315,21 +396,7 @@ def prior_terms(poses, n_free, pr, dtype=LD, route="quat", sn_switch=1e-12, seri
     w = V(live * drho, live * (d2rho * xr.e + K_RHO * drho))
     if w_scale is not None:                 # (the sensitivity test)
         w.v = w.v * dt(w_scale)
-    # J = [[I - K/2 + c K2, 0], [-[tD]x, I]], K = [phi]x, K2 = K K written out
-    p0, p1, p2 = phi[:, 0], phi[:, 1], phi[:, 2]
-    zero = V(np.zeros(E, dt))
-    K = _stack([_stack([zero, -p2, p1]), _stack([p2, zero, -p0]), _stack([-p1, p0, zero])])
-    K2 = _stack([_stack([-(p1 * p1 + p2 * p2), p0 * p1, p0 * p2]), _stack([p0 * p1, -(p0 * p0 + p2 * p2), p1 * p2]),
-                 _stack([p0 * p2, p1 * p2, -(p0 * p0 + p1 * p1)])])
-    cV = V(cc[:, None, None] + 0 * K2.v, e_c[:, None, None] + 0 * K2.v)
-    I3 = V(np.broadcast_to(np.eye(3, dtype=dt), (E, 3, 3)).copy())
-    Jr = (I3 - K.half()) + cV * K2
-    t0, t1, t2 = tD[:, 0], tD[:, 1], tD[:, 2]
-    Jt = _stack([_stack([zero, t2, -t1]), _stack([-t2, zero, t0]), _stack([t1, -t0, zero])])
-    J = V(np.zeros((E, 6, 6), dt))
-    J.v[:, :3, :3], J.e[:, :3, :3] = Jr.v, Jr.e
-    J.v[:, 3:, :3], J.e[:, 3:, :3] = Jt.v, Jt.e
-    J.v[:, 3:, 3:] = np.eye(3, dtype=dt)
+    J, _ = se3_jacobian(phi, cc, e_c, tD)
     OJ = mm("eik,ekj->eij", OmV, J, 6)
     Hs = mm("eka,ekc->eac", J, OJ, 6)
     bs = mm("eka,ek->ea", J, Or, 6)
@@ -493,3 +560,219 @@ def prior_replay(poses, n_free, pr, mut=None):
                 tot += cp[g * PRIOR_POSES + i]
         wg[g] = tot
     return H, b, chi_total(wg, TOTAL_WG if mut == "totals_256" else None), t["chi"].v, cp
+
+
+# ------------------------------------------------------------------ relative-pose edges (relpose_kernels.hip)
+def relpose_effective(rp):
+    """the edge dict with the run-time flags folded in: an edge counts when the plan's flags (rp['active']) AND the
+    flags the device is given (rp['rt_active'], optional) leave it active"""
+    rt = rp.get("rt_active")
+    return rp if rt is None else dict(rp, active=np.asarray(rp["active"], bool) & np.asarray(rt, bool))
+
+
+def _bc(w, like):
+    """a per-edge V broadcast to the shape of `like`"""
+    idx = (slice(None),) + (None,) * (like.v.ndim - 1)
+    return V(w.v[idx] + 0 * like.v, w.e[idx] + 0 * like.v)
+
+
+def relpose_terms(poses, n_free, rp, dtype=LD, route="quat", full=True, w_scale=None, sn_switch=1e-12, series_below=1e-3):
+    """per-edge terms of a relpose_ref.make_edges dict (optionally with rt_active): V-valued chi [E], and with `full`
+    H_aa, H_bb, H_lohi [E,6,6] (the block (lo, hi) = J_lo^T Omega J_hi whichever of a, b is lo), b_a, b_b [E,6]; each is zero
+    where the edge does not count or the pose it belongs to is fixed.  Routes as prior_terms"""
+    import relpose_ref as RR
+    dt = dtype
+    a, b = np.asarray(rp["a"], int), np.asarray(rp["b"], int)
+    E = len(a)
+    Pa, Pb = np.asarray(poses, dt)[a], np.asarray(poses, dt)[b]
+    z = np.asarray(rp["z"], dt).reshape(E, 7)
+    Om = np.broadcast_to(np.asarray(rp["info"], dt).reshape(-1, 6, 6), (E, 6, 6))
+    Ra, Rb, Rz = (V(v, 4 * m) for v, m in (_rot(Pa[:, :4]), _rot(Pb[:, :4]), _rot(z[:, :4])))
+    RA = mm("eik,ejk->eij", Ra, Rb, 3)
+    tA = V(Pa[:, 4:].copy()) - mm("eij,ej->ei", RA, V(Pb[:, 4:].copy()), 3)
+    D = mm("eik,ejk->eij", RA, Rz, 3)
+    D.e = D.e + 6                                         # |q|^2 - 1 of the three input quaternions, 2 u each as for the prior
+    qD = None
+    if route == "quat":
+        qa, qb, qz = _unit(Pa[:, :4]), _unit(Pb[:, :4]), _unit(z[:, :4])
+        v, w = _qmul_conj(qa[:, :3], qa[:, 3:], qb[:, :3], qb[:, 3:])
+        v, w = _qmul_conj(v, w, qz[:, :3], qz[:, 3:])
+        qD = (v, w[:, 0])
+    phi, cc, e_c, theta, sn = so3_log_terms(D, route, qD, sn_switch, series_below)
+    tD = tA - mm("eij,ej->ei", D, V(z[:, 4:].copy()), 3)
+    r = V(np.concatenate([phi.v, tD.v], 1), np.concatenate([phi.e, tD.e], 1))
+    OmV = V(np.ascontiguousarray(Om))
+    Or = mm("eij,ej->ei", OmV, r, 6)
+    xr = mm("ei,ei->e", r, Or, 6)
+    x = np.maximum(0, xr.v)
+    kind, delta = int(rp["rk"][0]), rp["rk"][1]
+    rho, drho, d2rho = _rho(kind, delta, x, dt)
+    eff = relpose_effective(rp)
+    cnt = RR.counting(eff, n_free)
+    live = cnt.astype(dt)
+    chi = V(live * rho, live * (drho * xr.e + K_RHO * (np.abs(rho) + _rho0(kind, delta, x, dt))))
+    tA_rel = np.sqrt((tA.v ** 2).sum(1)) / np.maximum(np.abs(Pa[:, 4:]).sum(1) + np.einsum("eij,ej->ei", np.abs(RA.v), np.abs(Pb[:, 4:])).sum(1), dt(1e-300))
+    out = dict(chi=chi, theta=theta, sn=sn, x=x, xr=xr.v, live=cnt, r=r.v, tA=tA.v, tA_rel=tA_rel)
+    if not full:
+        return out
+    w = V(live * drho, live * (d2rho * xr.e + K_RHO * drho))
+    if w_scale is not None:                 # (the sensitivity test: one factor, or one per edge)
+        w.v = w.v * np.asarray(w_scale, dt)
+    Ja, Jl = se3_jacobian(phi, cc, e_c, tD)
+    # J_b entry by entry as the kernel writes it: [[-J_l^-1 R_A, 0], [[u]x R_A, -R_A]], u = t_D - t_A
+    u = tD - tA
+    u0, u1, u2 = (V(u.v[:, k:k + 1], u.e[:, k:k + 1]) for k in range(3))
+    bot = _stack([u1 * RA[:, 2, :] - u2 * RA[:, 1, :], u2 * RA[:, 0, :] - u0 * RA[:, 2, :], u0 * RA[:, 1, :] - u1 * RA[:, 0, :]])
+    top = -mm("eik,ekj->eij", Jl, RA, 3)
+    Jb = V(np.zeros((E, 6, 6), dt))
+    Jb.v[:, :3, :3], Jb.e[:, :3, :3] = top.v, top.e
+    Jb.v[:, 3:, :3], Jb.e[:, 3:, :3] = bot.v, bot.e
+    Jb.v[:, 3:, 3:], Jb.e[:, 3:, 3:] = -RA.v, RA.e
+    OJa, OJb = mm("eik,ekj->eij", OmV, Ja, 6), mm("eik,ekj->eij", OmV, Jb, 6)
+    fa, fb = (a < n_free).astype(dt), (b < n_free).astype(dt)
+    a_lo = a < b
+
+    def scaled(Xs, keep):
+        t = _bc(w, Xs) * Xs
+        k = keep[(slice(None),) + (None,) * (Xs.v.ndim - 1)]
+        return V(t.v * k, t.e * k)
+    Hab, Hba = mm("eka,ekc->eac", Ja, OJb, 6), mm("eka,ekc->eac", Jb, OJa, 6)
+    lohi = V(np.where(a_lo[:, None, None], Hab.v, Hba.v), np.where(a_lo[:, None, None], Hab.e, Hba.e))
+    out.update(H_aa=scaled(mm("eka,ekc->eac", Ja, OJa, 6), fa), H_bb=scaled(mm("eka,ekc->eac", Jb, OJb, 6), fb),
+               H_lohi=scaled(lohi, fa * fb), b_a=-scaled(mm("eka,ek->ea", Ja, Or, 6), fa), b_b=-scaled(mm("eka,ek->ea", Jb, Or, 6), fb),
+               w=w.v, Ja=Ja.v, Jb=Jb.v)
+    return out
+
+
+def relpose_build(poses, n_free, rp, rowptr=None, colind=None, dtype=LD, route="quat", full=True, w_scale=None):
+    """H [P,6,6], b [P,6], Hoff [nnzb,6,6] on the pattern (relpose_ref.pattern of the plan's edges unless one is given; only
+    the (lo, hi) blocks are filled), chi_pose [P] (an edge's term at the pose whose walk counts it: a when a is free,
+    else b), chi_edge [E], chi; each with X_err, X_mass, X_n (relpose_bound).  An edge counts as relpose_ref.counting says"""
+    import relpose_ref as RR
+    dt = dtype
+    P = n_free
+    if rowptr is None:
+        rowptr, colind = RR.pattern(rp, n_free)
+    nnzb = len(colind)
+    a, b = np.asarray(rp["a"], int), np.asarray(rp["b"], int)
+    t = relpose_terms(poses, n_free, rp, dt, route, full=full, w_scale=w_scale)
+    live = t["live"]
+    out = dict(terms=t)
+
+    def put(key, idx, n, parts):
+        """parts: list of (edge mask, V) scattered by idx[mask]"""
+        val = err = mass = 0
+        cnt = np.zeros(n, np.int64)
+        for (m, X), ix in zip(parts, idx):
+            val = val + _scatter(ix[m], X.v[m], n)
+            err = err + _scatter(ix[m], X.e[m], n)
+            mass = mass + _scatter(ix[m], np.abs(X.v[m]), n)
+            cnt += np.bincount(ix[m], minlength=n)[:n]
+        out[key], out[key + "_err"], out[key + "_mass"] = val, err, mass
+        out[key + "_n"] = cnt.reshape((n,) + (1,) * (np.ndim(val) - 1))
+    ma, mb = live & (a < P), live & (b < P)
+    if full:
+        put("H", (a, b), P, [(ma, t["H_aa"]), (mb, t["H_bb"])])
+        put("b", (a, b), P, [(ma, t["b_a"]), (mb, t["b_b"])])
+        both = ma & mb
+        blk = np.full(len(a), 0, int)
+        for e in np.flatnonzero(both):
+            blk[e] = RR.block_of(rowptr, colind, min(a[e], b[e]), max(a[e], b[e]))
+        put("Hoff", (blk,), nnzb, [(both, t["H_lohi"])])
+    owner = np.where(a < P, a, b)
+    put("chi_pose", (owner,), P, [(live, t["chi"])])
+    out["chi_edge"], out["chi_edge_err"], out["chi_edge_mass"], out["chi_edge_n"] = t["chi"].v, t["chi"].e, np.abs(t["chi"].v), 0
+    out["chi"], out["chi_err"], out["chi_mass"], out["chi_n"] = t["chi"].v.sum(), t["chi"].e.sum(), np.abs(t["chi"].v).sum(), int(live.sum())
+    return out
+
+
+def relpose_bound(ref, key):
+    return prior_bound(ref, key)
+
+
+def relpose_chi_in_device_order(chi_edge, n_free, rp, rowptr, colind):
+    """the chi2 total of given per-edge terms summed as relpose_kernels.hip sums them (float64 additions only, so the
+    device's own per-edge terms give the device's total bit for bit): per free pose the terms its walk counts, in edge
+    order; one total per RELPOSE_POSES poses; chi_total"""
+    import relpose_ref as RR
+    P = n_free
+    a, b = np.asarray(rp["a"], int), np.asarray(rp["b"], int)
+    inc_ptr, inc, _ = RR.plan(rp, n_free, rowptr, colind)
+    rt = np.ones(len(a), bool) if rp.get("rt_active") is None else np.asarray(rp["rt_active"], bool)
+    chi_edge = np.asarray(chi_edge, np.float64)
+    wg = np.zeros((P + RELPOSE_POSES - 1) // RELPOSE_POSES)
+    for g in range(len(wg)):
+        tot = 0.0
+        for p in range(g * RELPOSE_POSES, min((g + 1) * RELPOSE_POSES, P)):
+            chi = 0.0
+            for rec in inc[inc_ptr[p]:inc_ptr[p + 1]]:
+                e, side = int(rec) >> 1, int(rec) & 1
+                if rt[e] and (side == 0 or (a[e] if side else b[e]) >= P):
+                    chi += chi_edge[e]
+            tot += chi
+        wg[g] = tot
+    return chi_total(wg)
+
+
+def relpose_replay(poses, n_free, rp, rowptr, colind, mut=None):
+    """float64 evaluation in the order of relpose_kernels.hip: per free pose its incidence list in edge order (the plan of
+    relpose_ref.plan over rp['active']; rp['rt_active'] are the flags the device skips by), the diagonal term and b
+    summed over the walk and added once (upper triangle, mirrored), Hoff added edge after edge in the walk of lo, chi2
+    counted by the walk of a when a is free, else by b's, one total per RELPOSE_POSES poses, then chi_total.  Per-edge
+    terms from relpose_ref.edge_terms.  mut: None, 'chi2_twice', 'transposed', 'no_tA' (= u = t_D instead of t_D - t_A),
+    'overwrite', 'Ja_for_Jb_fixed', 'chi_from_b', 'rt_counted', 'drop_second', 'totals_256'.
+    Returns H [P,6,6], b [P,6], Hoff [nnzb,6,6], chi, chi_edge [E], chi per pose [P]"""
+    import relpose_ref as RR
+    P = n_free
+    a, b = np.asarray(rp["a"], int), np.asarray(rp["b"], int)
+    E = len(a)
+    inc_ptr, inc, off = RR.plan(rp, n_free, rowptr, colind)
+    rt = np.ones(E, bool) if rp.get("rt_active") is None or mut == "rt_counted" else np.asarray(rp["rt_active"], bool)
+    Om = np.broadcast_to(np.asarray(rp["info"], np.float64).reshape(-1, 6, 6), (E, 6, 6)) if E else None
+    rk = rp.get("rk", (0, 1.0))
+    poses = np.asarray(poses, np.float64)
+    terms = {}
+    H, bb, Hoff = np.zeros((P, 6, 6)), np.zeros((P, 6)), np.zeros((len(colind), 6, 6))
+    ce, cp = np.zeros(E), np.zeros(P)
+    iu = np.triu_indices(6)
+    seen = {}
+    for p in range(P):
+        mH, mb, chi = np.zeros((6, 6)), np.zeros(6), 0.0
+        for rec in inc[inc_ptr[p]:inc_ptr[p + 1]]:
+            e, side = int(rec) >> 1, int(rec) & 1
+            if not rt[e]:
+                continue
+            if e not in terms:
+                terms[e] = RR.edge_terms(poses[a[e]], poses[b[e]], rp["z"][e], Om[e], rk, with_tA=mut != "no_tA")
+            c, Haa, Hbb, Hab, ba, b_b = terms[e]
+            other = a[e] if side else b[e]
+            counts_chi = (side == 1 or other >= P) if mut == "chi_from_b" else (side == 0 or other >= P)
+            if mut == "chi2_twice":
+                counts_chi = True
+            if counts_chi:
+                chi += c
+                ce[e] = c
+            own_b = side == 1 and not (mut == "Ja_for_Jb_fixed" and other >= P)
+            mH += Hbb if own_b else Haa
+            mb += b_b if own_b else ba
+            if other < P and p < other:
+                k = off[e]
+                seen[k] = seen.get(k, 0) + 1
+                blk = Hab if side == 0 or mut == "transposed" else Hab.T
+                if mut == "overwrite":
+                    Hoff[k] = blk
+                elif not (mut == "drop_second" and seen[k] == 2):
+                    Hoff[k] += blk
+        H[p][iu] += mH[iu]
+        bb[p] += mb
+        cp[p] = chi
+    H[:, iu[1], iu[0]] = H[:, iu[0], iu[1]]
+    nwg = (P + RELPOSE_POSES - 1) // RELPOSE_POSES
+    wg = np.zeros(nwg)
+    for g in range(nwg):
+        tot = 0.0
+        for i in range(RELPOSE_POSES):
+            if g * RELPOSE_POSES + i < P:
+                tot += cp[g * RELPOSE_POSES + i]
+        wg[g] = tot
+    return H, bb, Hoff, chi_total(wg, TOTAL_WG if mut == "totals_256" else None), ce, cp

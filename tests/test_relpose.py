@@ -173,9 +173,12 @@ def test_poses_with_0_1_63_64_65_and_300_incident_edges(ctx):
     assert not H[0].any() and not b[0].any()
 
 
-@pytest.mark.parametrize("n_free", [7, 8, 9, 70])
+@pytest.mark.parametrize("n_free", [3, 4, 5, 7, 8, 9, 70])
 def test_free_pose_counts_round_a_workgroup_with_fixed_poses_and_repeatable_bits(ctx, n_free):
-    rng, poses = random_poses(10 + n_free, n_free + 3)
+    """a workgroup holds four poses (RELPOSE_POSES, one wave each): 3, 4, 5 and 7, 8, 9 free poses stand round one and two
+    workgroups, 70 leaves the last one half empty"""
+    # (seed 14 draws no edge between two free poses for n_free = 4, which the pattern assertion below asks for)
+    rng, poses = random_poses(114 if n_free == 4 else 10 + n_free, n_free + 3)
     Pall = n_free + 3
     E = 3 * n_free
     a = rng.integers(0, Pall, E)
