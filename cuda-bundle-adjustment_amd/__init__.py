@@ -74,6 +74,14 @@ class PriorEdges(C.Structure):
                 ("n_info", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int), ("delta", C.c_double)]
 
 
+class LmPriorEdges(C.Structure):
+    """cugo_lm_prior_edges: landmark position priors with 3 x 3 information, landmark-sorted structure of arrays
+    (cugo_hip.h)."""
+    _fields_ = [("n_landmarks_total", C.c_int), ("n_landmarks_free", C.c_int), ("n", C.c_int),
+                ("d_lm", C.c_void_p), ("d_lm_ptr", C.c_void_p), ("d_meas", C.c_void_p), ("d_info", C.c_void_p),
+                ("n_info", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int), ("delta", C.c_double)]
+
+
 class RelPoseEdges(C.Structure):
     """cugo_relpose_edges: relative-pose SE(3) edges with 6 x 6 information in the caller's order; the layout (who walks
     which edge, where the off-diagonal block goes) is the plan's (relpose_plan_create; cugo_hip.h)."""
@@ -141,6 +149,24 @@ def icp_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, 
 def prior_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
     """cugo_prior_construct_quadratic_form_schur: as icp_construct_quadratic_form_schur, for PriorEdges"""
     check(lib().cugo_prior_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def lm_prior_compute_errors(ctx, ev, d_lms, d_chi, d_edge_chi=None):
+    """cugo_lm_prior_compute_errors: the chi2 of the landmark priors `ev` (LmPriorEdges) to d_chi[0], and the term of
+    every prior to d_edge_chi [n] if given.  Handles and pointers as for icp_construct_quadratic_form_schur"""
+    check(lib().cugo_lm_prior_compute_errors(ctx, C.byref(ev), d_lms, d_chi, d_edge_chi))
+
+
+def lm_prior_construct_quadratic_form(ctx, ev, d_lms, d_Hll, d_bl, d_chi=None):
+    """cugo_lm_prior_construct_quadratic_form: the terms ADDED to d_Hll [Lfree][9] and d_bl [Lfree][3]"""
+    check(lib().cugo_lm_prior_construct_quadratic_form(ctx, C.byref(ev), d_lms, d_Hll, d_bl, d_chi))
+
+
+def construct_quadratic_form_lm_priors(ctx, ev, lp, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl, d_chi=None):
+    """cugo_construct_quadratic_form_lm_priors: the BA build pass of `ev` (Edges, rk: Robust) with the landmark priors
+    `lp` taken inside its edge kernel, the form the LM loop uses"""
+    check(lib().cugo_construct_quadratic_form_lm_priors(ctx, C.byref(ev), C.byref(lp), d_poses, d_lms, rk, d_Hpp, d_bp,
+                                                        d_Hll, d_bl, d_Hpl, d_chi))
 
 
 def _i32(a):
@@ -463,6 +489,33 @@ class Graph:
     def n_prior_edges(self):
         """active priors in the current flattening (priors on fixed poses are not counted)"""
         return lib().cugo_graph_n_prior_edges(self._g)
+
+    def add_landmark_priors(self, lm_ids, xyz3, info9=None):
+        """landmark position priors (an extension; LandmarkPriorEdgeSet): residual X - Z against the measured position
+        xyz3 [n, 3], cost r^T Omega r.  info9: [n, 3, 3] (or one 3 x 3 for all); None for the set's matrix
+        (set_landmark_prior_information).  An unknown landmark id refuses the whole call"""
+        n = len(lm_ids)
+        if n == 0:
+            return
+        li = np.ascontiguousarray(lm_ids, np.int32)
+        z = np.ascontiguousarray(np.asarray(xyz3, np.float64).reshape(n, 3))
+        w = None if info9 is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(info9, np.float64).reshape(-1, 9), (n, 9)))
+        check(lib().cugo_graph_add_landmark_priors(self._g, n, _p(li, _i32p), _p(z, _f64p),
+                                                   None if w is None else _p(w, _f64p)))
+
+    def set_landmark_prior_information(self, info9):
+        """the landmark-prior set's 3 x 3 information (used when per_edge_information is off, or for priors added
+        without one)"""
+        w = np.ascontiguousarray(np.asarray(info9, np.float64).reshape(9))
+        check(lib().cugo_graph_set_landmark_prior_information(self._g, _p(w, _f64p)))
+
+    def set_landmark_prior_robust_kernel(self, rk_type, delta):
+        check(lib().cugo_graph_set_landmark_prior_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
+
+    def n_landmark_prior_edges(self):
+        """landmark priors that count in the current flattening (priors on fixed landmarks are not counted)"""
+        return lib().cugo_graph_n_landmark_prior_edges(self._g)
 
     def add_relpose_edges(self, pose_ids_a, pose_ids_b, q_t7, info36=None):
         """relative-pose SE(3) edges (an extension; RelPoseEdgeSet): residual [Log_SO3(R_D); t_D] of D = T_a T_b^-1 Z^-1

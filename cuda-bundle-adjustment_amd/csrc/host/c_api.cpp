@@ -8,6 +8,7 @@
 #include "../../../include/cugo_hip.h"
 #include "../../include/cuda_graph_optimisation.h"
 #include "../../include/icp_types.h"
+#include "../../include/landmark_prior_types.h"
 #include "../../include/prior_types.h"
 #include "../../include/relpose_types.h"
 #include "../kernels/kernels.h"
@@ -332,6 +333,100 @@ int cugo_prior_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_prior_ed
         cugo_k::launch_prior_add_schur(ctx->stream, *ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, rs.d_partials);
         if (d_chi)
             cugo_k::launch_pose_chi_total(ctx->stream, "k_prior_chi_total", rs.d_partials, cugo_k::prior_workgroups(*ev), d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+} // extern "C"
+
+namespace
+{
+// Landmark position priors: as check_prior, with lm_ptr (n_landmarks_total + 1 entries) on the host and the landmark
+// index of every prior against it on the device.  `before`: doubles of the scratch in front of the workgroup totals
+// (what a BA build pass of the same call needs); the totals start there
+double* check_lm_prior(cugo_ctx* ctx, const cugo_lm_prior_edges* ev, size_t before = 0)
+{
+    const char* prefix = "cugo_lm_prior";
+    auto refuse = [&](const char* what) { throw std::runtime_error(std::string(prefix) + ": " + what); };
+    if (!ctx || !ev || ev->n_landmarks_total < 0 || ev->n_landmarks_free < 0 || ev->n_landmarks_free > ev->n_landmarks_total ||
+        ev->n < 0)
+        refuse("bad landmark or edge counts");
+    if (!ev->d_lm_ptr)
+        refuse("no lm_ptr");
+    if (ev->n > (1 << 26))
+        refuse("more than 2^26 edges (the kernel indexes the planar arrays with 32 bits)");
+    if (ev->rk < CUGO_RK_NONE || ev->rk > CUGO_RK_HUBER || (ev->rk != CUGO_RK_NONE && !(ev->delta > 0.0 && std::isfinite(ev->delta))))
+        refuse("unknown robust kernel or bad delta");
+    if (ev->n > 0 && (!ev->d_lm || !ev->d_meas || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
+        refuse("missing arrays");
+    const int L = ev->n_landmarks_total;
+    std::vector<int32_t> ptr((size_t)L + 1);
+    CUGO_HIP(hipMemcpyAsync(ptr.data(), ev->d_lm_ptr, sizeof(int32_t) * ((size_t)L + 1), hipMemcpyDeviceToHost, ctx->stream));
+    CUGO_HIP(hipStreamSynchronize(ctx->stream));
+    if (ptr[0] != 0 || ptr[L] != ev->n)
+        refuse("lm_ptr does not span the edges");
+    for (int l = 0; l < L; l++)
+        if (ptr[l + 1] < ptr[l])
+            refuse("lm_ptr not ascending");
+    const size_t need = before + (size_t)cugo_k::lm_prior_workgroups(*ev);
+    const cugo_k::ReduceScratch rs = pose_scratch_for(ctx, need);
+    const cugo_k::PoseIndexCheck kind{ev->d_lm, ev->d_lm_ptr, ev->n, "k_lm_prior_check"};
+    if (cugo_k::pose_check_indices(ctx->stream, "landmark prior", &kind, 1, L, reinterpret_cast<int*>(rs.d_partials + need)))
+        refuse("edges not sorted by landmark, or a landmark index disagrees with lm_ptr");
+    return rs.d_partials + before;
+}
+} // namespace
+
+extern "C" {
+
+int cugo_lm_prior_compute_errors(cugo_ctx* ctx, const cugo_lm_prior_edges* ev, const double* d_lms, double* d_chi,
+                                 double* d_edge_chi)
+{
+    return guarded([&] {
+        double* d_wg = check_lm_prior(ctx, ev);
+        if (d_edge_chi && ev->n > 0 && ev->n_landmarks_free < ev->n_landmarks_total) // (the kernel never visits a fixed landmark)
+            CUGO_HIP(hipMemsetAsync(d_edge_chi, 0, sizeof(double) * ev->n, ctx->stream));
+        cugo_k::launch_lm_prior_errors(ctx->stream, *ev, d_lms, d_wg, d_edge_chi);
+        if (d_chi)
+            cugo_k::launch_pose_chi_total(ctx->stream, "k_lm_prior_chi_total", d_wg, cugo_k::lm_prior_workgroups(*ev), d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_lm_prior_construct_quadratic_form(cugo_ctx* ctx, const cugo_lm_prior_edges* ev, const double* d_lms, double* d_Hll,
+                                           double* d_bl, double* d_chi)
+{
+    return guarded([&] {
+        double* d_wg = check_lm_prior(ctx, ev);
+        if (ev->n > 0 && ev->n_landmarks_free > 0 && (!d_Hll || !d_bl))
+            throw std::runtime_error("cugo_lm_prior: missing Hll or bl");
+        cugo_k::launch_lm_prior_add(ctx->stream, *ev, d_lms, d_Hll, d_bl, d_wg);
+        if (d_chi)
+            cugo_k::launch_pose_chi_total(ctx->stream, "k_lm_prior_chi_total", d_wg, cugo_k::lm_prior_workgroups(*ev), d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_construct_quadratic_form_lm_priors(cugo_ctx* ctx, const cugo_edges* ev, const cugo_lm_prior_edges* lp,
+                                            const double* d_poses, const double* d_lms, cugo_robust rk, double* d_Hpp,
+                                            double* d_bp, double* d_Hll, double* d_bl, void* d_Hpl, double* d_chi)
+{
+    return guarded([&] {
+        if (!ev || !lp)
+            throw std::runtime_error("cugo_lm_prior: no edges or no priors");
+        if (lp->n_landmarks_total != ev->n_landmarks_total || lp->n_landmarks_free != ev->n_landmarks_free)
+            throw std::runtime_error("cugo_lm_prior: the priors do not describe the landmarks of the edges");
+        // (the scratch of the BA pass in front, the priors' workgroup totals and the flag of the index check behind it)
+        const size_t ba = cugo_k::reduce_scratch_doubles(ev->n_edges, ev->n_poses_free, ev->n_landmarks_free);
+        double* d_wg = check_lm_prior(ctx, lp, ba);
+        cugo_k::launch_build(ctx->stream, *ev, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl,
+                             cugo_k::ReduceScratch{ctx->scratch.data(), ctx->scratch.size()}, d_chi, -1.0, nullptr, nullptr,
+                             nullptr, false, false, lp);
+        if (d_chi)
+        {
+            cugo_k::launch_lm_prior_errors(ctx->stream, *lp, d_lms, d_wg);
+            cugo_k::launch_pose_chi_total(ctx->stream, "k_lm_prior_chi_total", d_wg, cugo_k::lm_prior_workgroups(*lp), d_chi, true);
+        }
         CUGO_HIP(hipGetLastError());
     });
 }
@@ -827,6 +922,8 @@ struct cugo_graph
     std::deque<cugo::PosePriorEdge> prior_store;
     cugo::RelPoseEdgeSet relpose;
     std::deque<cugo::RelPoseEdge> relpose_store;
+    cugo::LandmarkPriorEdgeSet lm_prior;
+    std::deque<cugo::LandmarkPriorEdge> lm_prior_store;
     std::deque<cugo::PlaneEdge> plane_store;
     std::deque<cugo::LineEdge> line_store;
     std::deque<cugo::PoseVertex> pose_store;
@@ -846,6 +943,7 @@ struct cugo_graph
         opt->addEdgeSet(&line);
         opt->addEdgeSet(&prior);
         opt->addEdgeSet(&relpose);
+        opt->addEdgeSet(&lm_prior);
         attached = true;
     }
 };
@@ -1151,6 +1249,47 @@ int cugo_graph_set_relpose_active(cugo_graph* g, int first, int n, const uint8_t
     });
 }
 int cugo_graph_n_relpose_edges(cugo_graph* g) { return g->opt->nRelPoseEdges(); }
+int cugo_graph_add_landmark_priors(cugo_graph* g, int n, const int32_t* lm_ids, const double* xyz3, const double* info9)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!lm_ids || !xyz3)))
+            throw std::invalid_argument("cugo_graph_add_landmark_priors: missing arrays");
+        auto landmark = [&](int32_t id) {
+            try
+            {
+                return g->lms.getVertex(id);
+            }
+            catch (const std::out_of_range&)
+            {
+                throw std::invalid_argument("cugo_graph_add_landmark_priors: unknown landmark id " + std::to_string(id));
+            }
+        };
+        for (int i = 0; i < n; i++) // (all or nothing: an unknown id adds no edge)
+            (void)landmark(lm_ids[i]);
+        for (int i = 0; i < n; i++)
+        {
+            g->lm_prior_store.emplace_back();
+            cugo::LandmarkPriorEdge& e = g->lm_prior_store.back();
+            e.setVertex(landmark(lm_ids[i]), 0);
+            e.setMeasurement(cugo::LandmarkPriorMatch<double>(xyz3 + 3 * (size_t)i,
+                                                              info9 ? info9 + 9 * (size_t)i : g->lm_prior.informationMatrix()));
+            g->lm_prior.addEdge(&e);
+        }
+    });
+}
+int cugo_graph_set_landmark_prior_information(cugo_graph* g, const double* info9)
+{
+    return guarded([&] {
+        if (!info9)
+            throw std::invalid_argument("cugo_graph_set_landmark_prior_information: no matrix");
+        g->lm_prior.setInformationMatrix(info9);
+    });
+}
+int cugo_graph_set_landmark_prior_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    return guarded([&] { g->lm_prior.setRobustKernel(rk_type_of(type), delta); });
+}
+int cugo_graph_n_landmark_prior_edges(cugo_graph* g) { return g->opt->nLandmarkPriorEdges(); }
 int cugo_graph_set_camera(cugo_graph* g, int dim, const double* c)
 {
     const cugo::Camera cam(c[0], c[1], c[2], c[3], c[4]);

@@ -164,7 +164,11 @@ struct Engine::Impl : cugo_k::LaunchHook
     // sort; the views the kernels take; and a scratch of their own (the BA scratch holds live scale / chi2 partials and
     // records across the same span of the stream):
     //     [ICP partials | ICP chunk chi2 totals | prior workgroup chi2 totals | relative-pose workgroup chi2 totals |
-    //      16 doubles of slack]
+    //      landmark-prior workgroup chi2 totals | 16 doubles of slack]
+    // The landmark position priors (FlatGraph::lm_priors, lm_prior_kernels.hip) sit on landmarks, not poses, but their
+    // chi2 travels the same way, so they live here too: sorted by landmark (stable) with a CSR over all landmarks,
+    // planar on the device.  Their terms ride in the BA build pass (launch_build with the view); only the chi2 has
+    // launches of its own.
     // The runs of totals are adjacent, so that the launch ending a trial sums them as one array (chi_totals).  Every
     // launch of a kind sits under its count of totals: a graph without the kind queues what it always did.
     struct PoseEdges
@@ -181,7 +185,61 @@ struct Engine::Impl : cugo_k::LaunchHook
         // totals an ICP pass / a prior pass / a relative-pose pass leaves (0: the pass is not launched)
         int n_icp_chi = 0, n_prior_wg = 0, n_relpose_wg = 0;
         DevBuf<double> d_scratch;
-        size_t off_icp_chi = 0, off_prior_chi = 0, off_relpose_chi = 0; // the layout above, set by bind()
+        size_t off_icp_chi = 0, off_prior_chi = 0, off_relpose_chi = 0, off_lm_prior_chi = 0; // the layout above, set by bind()
+        // landmark position priors: sorted host copies (h_lmp_lm, h_lmp_ptr: what initialize() checks against the slot
+        // layout), the device arrays, the view
+        std::vector<int32_t> h_lmp_lm, h_lmp_ptr;
+        DevBuf<int32_t> d_lmp_lm, d_lmp_ptr;
+        DevBuf<double> d_lmp_meas, d_lmp_info;
+        cugo_lm_prior_edges lm_prior{};
+        int n_lm_prior = 0, n_lm_prior_wg = 0;
+        double* lm_prior_chi() { return d_scratch.data() + off_lm_prior_chi; }
+        // the view for the build pass; nullptr without priors (the pass is then queued as it always was)
+        const cugo_lm_prior_edges* lm_prior_view() const { return n_lm_prior_wg ? &lm_prior : nullptr; }
+        void bind_lm_priors(const FlatLmPriors& f, int Lall, int L, hipStream_t stream, bool plan_only)
+        {
+            const int n = n_lm_prior = f.n();
+            lm_prior = cugo_lm_prior_edges{};
+            lm_prior.n_landmarks_total = Lall, lm_prior.n_landmarks_free = L, lm_prior.n = n;
+            lm_prior.rk = f.rk, lm_prior.delta = f.delta;
+            h_lmp_lm.clear(), h_lmp_ptr.clear();
+            n_lm_prior_wg = 0;
+            if (!n)
+                return;
+            if (n > (1 << 26))
+                throw std::runtime_error("cugo: more than 2^26 landmark prior edges");
+            // counting sort by landmark: stable, container order inside a landmark
+            h_lmp_ptr.assign((size_t)Lall + 1, 0);
+            for (int e = 0; e < n; e++)
+                h_lmp_ptr[(size_t)f.lm[e] + 1]++;
+            for (int l = 0; l < Lall; l++)
+                h_lmp_ptr[l + 1] += h_lmp_ptr[l];
+            std::vector<int32_t> at(h_lmp_ptr.begin(), h_lmp_ptr.end() - 1);
+            const int n_info = f.info.size() == 6 ? 1 : n;
+            std::vector<double> meas(3 * (size_t)n), info(6 * (size_t)n_info);
+            h_lmp_lm.resize((size_t)n);
+            for (int e = 0; e < n; e++)
+            {
+                const int q = at[f.lm[e]]++;
+                h_lmp_lm[q] = f.lm[e];
+                for (int c = 0; c < 3; c++)
+                    meas[(size_t)c * n + q] = f.meas[3 * (size_t)e + c];
+                if (n_info > 1)
+                    for (int c = 0; c < 6; c++)
+                        info[(size_t)c * n + q] = f.info[6 * (size_t)e + c];
+            }
+            if (n_info == 1)
+                info = f.info;
+            lm_prior.n_info = n_info;
+            n_lm_prior_wg = cugo_k::lm_prior_workgroups(lm_prior);
+            if (plan_only)
+                return;
+            d_lmp_lm.upload(h_lmp_lm, stream), d_lmp_ptr.upload(h_lmp_ptr, stream);
+            d_lmp_meas.upload(meas, stream), d_lmp_info.upload(info, stream);
+            CUGO_HIP(hipStreamSynchronize(stream)); // (meas / info are locals)
+            lm_prior.d_lm = d_lmp_lm.data(), lm_prior.d_lm_ptr = d_lmp_ptr.data();
+            lm_prior.d_meas = d_lmp_meas.data(), lm_prior.d_info = d_lmp_info.data();
+        }
         struct RelPosePlan
         {
             DevBuf<int32_t> d_inc_ptr, d_inc, d_off_blk;
@@ -237,14 +295,15 @@ struct Engine::Impl : cugo_k::LaunchHook
         // the chi2 totals of the last ICP, prior and relative-pose pass, one array; nullptr / 0 without such edges
         const double* chi_totals(int* n)
         {
-            *n = n_icp_chi + n_prior_wg + n_relpose_wg;
+            *n = n_icp_chi + n_prior_wg + n_relpose_wg + n_lm_prior_wg;
             return *n ? d_scratch.data() + off_icp_chi : nullptr;
         }
 
         // planar copies (the unary kinds: sorted), upload by the calling thread (plan_only: no device), views and scratch
         // layout.  The relative-pose plan waits for the Hsc pattern (bind_relpose_plan)
-        void bind(const FlatGraph& g, int Pall, int P, hipStream_t stream, bool plan_only)
+        void bind(const FlatGraph& g, int Pall, int P, int Lall, int L, hipStream_t stream, bool plan_only)
         {
+            bind_lm_priors(g.lm_priors, Lall, L, stream, plan_only);
             n_icp = g.kinds[POSE_KIND_PLANE].n() + g.kinds[POSE_KIND_LINE].n();
             n_prior = g.kinds[POSE_KIND_PRIOR].n(), n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
             for (int k = 0; k < POSE_KIND_COUNT; k++)
@@ -300,8 +359,9 @@ struct Engine::Impl : cugo_k::LaunchHook
             n_prior_wg = cugo_k::prior_workgroups(prior), n_relpose_wg = cugo_k::relpose_workgroups(relpose);
             off_icp_chi = icp_doubles - n_icp_chi, off_prior_chi = icp_doubles;
             off_relpose_chi = off_prior_chi + (size_t)n_prior_wg;
-            if ((n_icp || n_prior_wg || n_relpose_wg) && !plan_only)
-                d_scratch.resize(icp_doubles + (size_t)n_prior_wg + (size_t)n_relpose_wg + 16);
+            off_lm_prior_chi = off_relpose_chi + (size_t)n_relpose_wg;
+            if ((n_icp || n_prior_wg || n_relpose_wg || n_lm_prior_wg) && !plan_only)
+                d_scratch.resize(icp_doubles + (size_t)n_prior_wg + (size_t)n_relpose_wg + (size_t)n_lm_prior_wg + 16);
         }
         // the plan against the Hsc pattern at hand (upper block CSR over the free poses): the engine made the pattern
         // from these very pairs, so a pair missing from it is a defect of the engine and throws
@@ -329,8 +389,10 @@ struct Engine::Impl : cugo_k::LaunchHook
         // written): the adds go behind k_pose_schur (queue_add_schur); the chunk pass still runs here, and the priors'
         // totals are computed here only where a chi2 is asked for (want_totals: iteration 0, or a trial that takes its
         // chi2 from this pass).  d_chi (once per call, iteration 0): the totals ADDED to it, ICP first
-        void queue_build(hipStream_t s, const double* poses, bool one_stream, double* Hpp, double* bp, bool want_totals,
-                         double* d_chi)
+        // The landmark priors' terms are in the BA build pass itself; their chi2 (at `lms`) has a launch here only where
+        // a chi2 is asked for (want_totals)
+        void queue_build(hipStream_t s, const double* poses, const double* lms, bool one_stream, double* Hpp, double* bp,
+                         bool want_totals, double* d_chi)
         {
             if (n_icp)
             {
@@ -358,6 +420,12 @@ struct Engine::Impl : cugo_k::LaunchHook
                 if (d_chi)
                     cugo_k::launch_pose_chi_total(s, "k_relpose_chi_total", relpose_chi(), n_relpose_wg, d_chi, true);
             }
+            if (n_lm_prior_wg && want_totals)
+            {
+                cugo_k::launch_lm_prior_errors(s, lm_prior, lms, lm_prior_chi());
+                if (d_chi)
+                    cugo_k::launch_pose_chi_total(s, "k_lm_prior_chi_total", lm_prior_chi(), n_lm_prior_wg, d_chi, true);
+            }
         }
         // two-stream form: the off-diagonal terms of the relative-pose edges ADDED to their blocks of Hsc behind a Schur
         // pass (which wrote every block), at the poses the build pass at hand linearised at
@@ -377,8 +445,8 @@ struct Engine::Impl : cugo_k::LaunchHook
             if (n_relpose_wg)
                 cugo_k::launch_relpose_add_schur(s, relpose, rp.dev, poses, rowptr, Hsc, bp, bsc, relpose_chi());
         }
-        // error pass: chi_totals() at `poses`
-        void queue_errors(hipStream_t s, const double* poses)
+        // error pass: chi_totals() at `poses` / `lms`
+        void queue_errors(hipStream_t s, const double* poses, const double* lms)
         {
             if (n_icp)
                 cugo_k::launch_icp_chunks(s, icp, poses, false, icp_rs());
@@ -386,6 +454,8 @@ struct Engine::Impl : cugo_k::LaunchHook
                 cugo_k::launch_prior_errors(s, prior, poses, prior_chi());
             if (n_relpose_wg)
                 cugo_k::launch_relpose_errors(s, relpose, rp.dev, poses, relpose_chi());
+            if (n_lm_prior_wg)
+                cugo_k::launch_lm_prior_errors(s, lm_prior, lms, lm_prior_chi());
         }
     } pe;
     cugo_hsc_struct hs{};
@@ -723,8 +793,9 @@ struct Engine::Impl : cugo_k::LaunchHook
             cugo_k::launch_build(ctx.stream, ev, d_poses[buf].data(), d_lms[buf].data(), rk, d_Hpp.data(), bp(),
                                  d_Hll.data(), bl(), d_Hpl.data(), rs(), d_chi, fuse ? fuse_lambda : -1.0,
                                  fuse ? d_invHll.data() : nullptr, fuse && !f.use_rows ? d_T.data() : nullptr,
-                                 one_stream ? d_lmrec.data() : nullptr, one_stream, chi_behind_scale);
-            pe.queue_build(ctx.stream, d_poses[buf].data(), one_stream, d_Hpp.data(), bp(), d_chi || chi_behind_scale, d_chi);
+                                 one_stream ? d_lmrec.data() : nullptr, one_stream, chi_behind_scale, pe.lm_prior_view());
+            pe.queue_build(ctx.stream, d_poses[buf].data(), d_lms[buf].data(), one_stream, d_Hpp.data(), bp(),
+                           d_chi || chi_behind_scale, d_chi);
         });
         st.hpp_valid = !one_stream;
         st.fused_lambda = fuse ? fuse_lambda : -1.0;
@@ -1113,7 +1184,10 @@ void Engine::initialize(FlatGraph& g)
     m.init_rank = m.rank, m.init_world = m.world;
     m.Etot = g.n_edges();
     const int n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
-    E_global_ = m.Etot + g.n_pose_edges() + n_relpose;
+    E_global_ = m.Etot + g.n_pose_edges() + n_relpose + g.lm_priors.n();
+    if (g.lm_priors.n() && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: landmark prior edge sets are not supported on a landmark-sharded (multi-GPU) "
+                                 "optimiser yet");
     if (n_relpose && (m.world > 1 || m.comm))
         throw std::runtime_error("cugo: relative-pose edge sets are not supported on a landmark-sharded (multi-GPU) "
                                  "optimiser yet");
@@ -1127,6 +1201,14 @@ void Engine::initialize(FlatGraph& g)
                                      " edge sets are not supported on a landmark-sharded (multi-GPU) optimiser yet");
     sort_landmark_major(g, m.st_lm_cnt, m.st_order);
     laps.lap("engine: landmark sort");
+    // (before anything is started or uploaded) a prior on a free landmark without any edge slot — lm_ptr[l] == lm_ptr[l + 1]
+    // in the slot layout, which gives a landmark slots iff it has flattened edges — would shape Hll and bl of a landmark nothing ever steps: the
+    // back-substitution walks the landmarks of the slots
+    for (int32_t l : g.lm_priors.lm)
+        if (m.st_lm_cnt[l] == m.st_lm_cnt[l + 1])
+            throw std::runtime_error("cugo: landmark prior edge set: a prior sits on free landmark " + std::to_string(l) +
+                                     " (flattened index), which no active BA edge observes; the back-substitution gives such "
+                                     "a landmark a zero step (not supported)");
     build_covisibility(g, m.st_lm_cnt, m.st_order, m.cov_ptr, m.cov_pose);
     m.build_pair_lists(g.kinds[POSE_KIND_RELPOSE]);
     laps.lap("engine: co-visibility");
@@ -1144,7 +1226,7 @@ void Engine::initialize(FlatGraph& g)
     Impl::SlotUpload upload(m, g);
     pose_major_view(m.Pall, m.slots.pose, m.st_slot_src, m.h_pose_ptr, m.h_pose_edge);
     laps.lap("engine: pose-major view");
-    m.pe.bind(g, m.Pall, m.P, s, m.plan_only);
+    m.pe.bind(g, m.Pall, m.P, m.Lall, m.L, s, m.plan_only);
     laps.lap("engine: ICP edge sort");
     // (a plan-only engine has no device: it skips to the topology compare)
     if (!m.plan_only)
@@ -1690,7 +1772,7 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
                 {
                     int n_icp_chi = 0;
                     const double* icp_chi = m.pe.chi_totals(&n_icp_chi);
-                    m.pe.queue_errors(s, m.d_poses[nxt].data());
+                    m.pe.queue_errors(s, m.d_poses[nxt].data(), m.d_lms[nxt].data());
                     cugo_k::launch_errors_tail(s, m.ev, m.d_poses[nxt].data(), m.d_lms[nxt].data(), m.rk, m.rs(),
                                                n_scale_part, m.d_scal.data() + 2, m.d_scal.data() + 4,
                                                m.h_scal.data() + 2, (double)++m.trial_seq,
@@ -1900,6 +1982,7 @@ const std::vector<int32_t>& Engine::icp_slot_source(int kind, bool set) const
 }
 int Engine::n_prior_edges() const { return impl_->pe.n_prior; }
 int Engine::n_relpose_edges() const { return impl_->pe.n_relpose; }
+int Engine::n_lm_prior_edges() const { return impl_->pe.n_lm_prior; }
 int Engine::n_poses_free() const { return impl_->P; }
 int Engine::n_landmarks_free() const { return impl_->L; }
 

@@ -77,6 +77,25 @@ inline void collapse_thresholds(std::vector<double>& t)
         t.resize(1);
 }
 
+// Landmark position priors (landmark_prior_types.h), flattened in container order: only priors that count get here
+// (active, on a free landmark of the optimiser, values checked by graph_optimisation.cpp).  The engine sorts them by
+// landmark (stable) and builds the CSR over all landmarks.
+struct FlatLmPriors
+{
+    std::vector<int32_t> lm;  // free-first landmark index per prior, always < L
+    std::vector<double> meas; // n x 3: Z
+    std::vector<double> info; // n x 6, or 1 x 6 when one matrix serves all: upper triangle, row-major packed
+    int rk = CUGO_RK_NONE;
+    double delta = 1.0;
+    bool rk_seen = false;
+    int n() const { return (int)lm.size(); }
+    void clear()
+    {
+        lm.clear(), meas.clear(), info.clear();
+        rk = CUGO_RK_NONE, delta = 1.0, rk_seen = false;
+    }
+};
+
 struct FlatGraph
 {
     int Pall = 0, Lall = 0, P = 0, L = 0;
@@ -94,6 +113,7 @@ struct FlatGraph
     // the chi2 threshold of its edge set, 0 = disabled; empty = disabled for all
     std::vector<double> e_outlier_threshold;
     FlatPoseKind kinds[POSE_KIND_COUNT]; // widths set by the constructor
+    FlatLmPriors lm_priors;
     FlatGraph()
     {
         const int w[POSE_KIND_COUNT][2] = {{7, 1}, {9, 1}, {7, 21}, {7, 21}};
@@ -210,10 +230,11 @@ public:
     const std::vector<double>& cov_lm() const { return cov_lm_; }
     int n_poses_free() const;
     int n_landmarks_free() const;
-    int n_active_edges() const { return E_global_; } // BA + ICP edges + priors + relative-pose edges of the current flattening
+    int n_active_edges() const { return E_global_; } // BA + ICP edges + priors (pose and landmark) + relative-pose edges of the current flattening
     int n_icp_edges(int kind) const;                  // 0 plane, 1 line
     int n_prior_edges() const;
     int n_relpose_edges() const;
+    int n_lm_prior_edges() const;
     // sorted slot of a kind -> {edge set, position in the set} as FlatPoseKind recorded them (kept for a later
     // outlier rejection on these sets)
     const std::vector<int32_t>& icp_slot_source(int kind, bool set) const;

@@ -3,6 +3,7 @@
 // (initialize), src/optimisable_graph.hpp:84-154, 474-572 (index / flag / activeness rules).
 #include "../../include/cuda_graph_optimisation.h"
 #include "../../include/icp_types.h"
+#include "../../include/landmark_prior_types.h"
 #include "../../include/prior_types.h"
 #include "../../include/relpose_types.h"
 
@@ -74,6 +75,7 @@ int CudaGraphOptimisationImpl::nActiveEdges() const { return engine_->n_active_e
 int CudaGraphOptimisationImpl::nIcpEdges(int kind) const { return engine_->n_icp_edges(kind); }
 int CudaGraphOptimisationImpl::nPriorEdges() const { return engine_->n_prior_edges(); }
 int CudaGraphOptimisationImpl::nRelPoseEdges() const { return engine_->n_relpose_edges(); }
+int CudaGraphOptimisationImpl::nLandmarkPriorEdges() const { return engine_->n_lm_prior_edges(); }
 
 std::vector<double> CudaGraphOptimisationImpl::structureStats() const
 {
@@ -131,35 +133,36 @@ static int rk_code(RobustKernelType t)
     }
 }
 
-// smallest and largest eigenvalue of a symmetric 6 x 6 matrix by cyclic Jacobi sweeps
-static void symEigenRange6(const double* A36, double& lo, double& hi)
+// smallest and largest eigenvalue of a symmetric N x N matrix by cyclic Jacobi sweeps
+template <int N>
+static void symEigenRange(const double* A, double& lo, double& hi)
 {
-    double a[6][6];
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++)
-            a[i][j] = 0.5 * (A36[6 * i + j] + A36[6 * j + i]);
+    double a[N][N];
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < N; j++)
+            a[i][j] = 0.5 * (A[N * i + j] + A[N * j + i]);
     for (int sweep = 0; sweep < 30; sweep++)
     {
         double off = 0.0, diag = 0.0;
-        for (int i = 0; i < 6; i++)
-            for (int j = 0; j < 6; j++)
+        for (int i = 0; i < N; i++)
+            for (int j = 0; j < N; j++)
                 (i == j ? diag : off) += a[i][j] * a[i][j];
         if (off <= 1e-32 * diag || off == 0.0)
             break;
-        for (int p = 0; p < 5; p++)
-            for (int q = p + 1; q < 6; q++)
+        for (int p = 0; p < N - 1; p++)
+            for (int q = p + 1; q < N; q++)
             {
                 if (a[p][q] == 0.0)
                     continue;
                 const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
                 const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
                 const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-                for (int k = 0; k < 6; k++)
+                for (int k = 0; k < N; k++)
                 {
                     const double akp = a[k][p], akq = a[k][q];
                     a[k][p] = c * akp - sn * akq, a[k][q] = sn * akp + c * akq;
                 }
-                for (int k = 0; k < 6; k++)
+                for (int k = 0; k < N; k++)
                 {
                     const double apk = a[p][k], aqk = a[q][k];
                     a[p][k] = c * apk - sn * aqk, a[q][k] = sn * apk + c * aqk;
@@ -167,30 +170,32 @@ static void symEigenRange6(const double* A36, double& lo, double& hi)
             }
     }
     lo = hi = a[0][0];
-    for (int i = 1; i < 6; i++)
+    for (int i = 1; i < N; i++)
         lo = std::min(lo, a[i][i]), hi = std::max(hi, a[i][i]);
 }
 
-// nullptr if Omega [36] can serve as an information matrix, else what is wrong with it
-static const char* checkInformation36(const double* A)
+// nullptr if Omega [N x N] can serve as an information matrix, else what is wrong with it
+template <int N>
+static const char* checkInformation(const double* A)
 {
     double mx = 0.0;
-    for (int i = 0; i < 36; i++)
+    for (int i = 0; i < N * N; i++)
     {
         if (!std::isfinite(A[i]))
             return "non-finite information";
         mx = std::max(mx, std::fabs(A[i]));
     }
-    for (int i = 0; i < 6; i++)
-        for (int j = i + 1; j < 6; j++)
-            if (std::fabs(A[6 * i + j] - A[6 * j + i]) > 1e-12 * mx)
+    for (int i = 0; i < N; i++)
+        for (int j = i + 1; j < N; j++)
+            if (std::fabs(A[N * i + j] - A[N * j + i]) > 1e-12 * mx)
                 return "the information matrix is not symmetric";
     double lo, hi;
-    symEigenRange6(A, lo, hi);
+    symEigenRange<N>(A, lo, hi);
     if (lo < -1e-12 * std::max(hi, 0.0) || hi < 0.0)
         return "the information matrix is not positive semi-definite";
     return nullptr;
 }
+static const char* checkInformation36(const double* A) { return checkInformation<6>(A); }
 
 // What the pose edge kinds, unary and binary, share per set: the outlier threshold (refused unless
 // GraphOptimisationOptions::poseEdgeOutlierRejection is on; returned: finite and > 0, or 0 = no rejection on this set), one
@@ -348,6 +353,56 @@ static void priorPayload(BaseEdge* e, const double* setInformation, Refuse& refu
             weight[t++] = 0.5 * (A[6 * r + c] + A[6 * c + r]);
 }
 
+// One LandmarkPriorEdgeSet (landmark_prior_types.h) into the flat arrays, in container order; the one place where these
+// edges are checked, as flattenPoseEdgeSet is for the pose kinds.  Every active edge must sit on a landmark vertex of one
+// of the optimiser's landmark sets and hold finite values and a symmetric positive semi-definite Omega (its own with
+// perEdgeInformation, else the set's).  Inactive priors and priors on fixed landmarks are dropped.  Several sets must
+// agree on the robust kernel.  Outlier rejection is not available on this kind.
+static void flattenLandmarkPriorSet(LandmarkPriorEdgeSet* es, int setIndex, const std::vector<BaseVertexSet*>& vertexSets,
+                                    bool perEdgeInformation, cugo_host::FlatLmPriors& out)
+{
+    const std::string name = "landmark prior";
+    const double* setInformation = perEdgeInformation ? nullptr : es->informationMatrix();
+    settlePoseEdgeSet(es, setIndex, name, false, out.rk, out.delta, out.rk_seen,
+                      [&] { return setInformation ? checkInformation<3>(setInformation) : nullptr; });
+    size_t at = 0, kept = 0;
+    for (BaseEdge* e : es->get())
+    {
+        const size_t i = at++;
+        if (!e->isActive())
+            continue;
+        auto refuse = [&](const char* what) {
+            throw std::runtime_error("cugo: " + name + " edge " + std::to_string(i) + " of edge set " +
+                                     std::to_string(setIndex) + ": " + what);
+        };
+        BaseVertex* v = e->getVertex(0);
+        bool known = false;
+        if (v && v->isMarginilised())
+            for (const BaseVertexSet* vs : vertexSets)
+                known = known || (vs == v->ownerSet() && vs->isMarginilised());
+        if (!known)
+            refuse("its landmark vertex is in no landmark vertex set of this optimiser");
+        const auto& mz = *static_cast<const LandmarkPriorMatch<double>*>(e->measurementData());
+        for (int c = 0; c < 3; c++)
+            if (!std::isfinite(mz.point[c]))
+                refuse("non-finite measured position");
+        const double* A = setInformation ? setInformation : mz.information;
+        if (!setInformation)
+            if (const char* bad = checkInformation<3>(A))
+                refuse(bad);
+        if (v->isFixed())
+            continue;
+        out.lm.push_back(v->getIndex());
+        out.meas.insert(out.meas.end(), mz.point, mz.point + 3);
+        for (int r = 0; r < 3; r++)
+            for (int c = r; c < 3; c++)
+                out.info.push_back(0.5 * (A[3 * r + c] + A[3 * c + r]));
+        kept++;
+    }
+    es->setActiveEdgeCount(kept);
+    es->setDirtyState(false);
+}
+
 void CudaGraphOptimisationImpl::initialize()
 {
     if (vertexSets.empty() || edgeSets.empty())
@@ -454,11 +509,12 @@ void CudaGraphOptimisationImpl::initialize()
     // pages is parallel too); chunks with skipped edges are compacted afterwards, in order, so
     // the flattened order is exactly the container order.
     size_t cap = 0;
-    for (BaseEdgeSet* es : edgeSets)
-        if (es->dim() != 1 && es->dim() != 6)
+    for (BaseEdgeSet* es : edgeSets) // (a LandmarkPriorEdgeSet is 3-d like a stereo set: the type tells them apart)
+        if (es->dim() != 1 && es->dim() != 6 && !dynamic_cast<LandmarkPriorEdgeSet*>(es))
             cap += es->nedges();
     for (cugo_host::FlatPoseKind& fk : g.kinds)
         fk.clear();
+    g.lm_priors.clear();
     poseSetEdges_.assign(edgeSets.size(), {});
     const bool rejection = options.poseEdgeOutlierRejection;
     g.e_pose.resize(cap), g.e_lm.resize(cap), g.e_flags.resize(cap);
@@ -481,6 +537,11 @@ void CudaGraphOptimisationImpl::initialize()
     {
         BaseEdgeSet* es = edgeSets[si];
         const int dim = es->dim();
+        if (auto* ls = dynamic_cast<LandmarkPriorEdgeSet*>(es))
+        { // landmark_prior_types.h, an extension: by type, before the dispatch on dim() (stereo BA sets are 3-d as well)
+            flattenLandmarkPriorSet(ls, (int)si, vertexSets, options.perEdgeInformation, g.lm_priors);
+            continue;
+        }
         if (dim == 1)
         { // PlaneEdgeSet / LineEdgeSet (icp_types.h): both have dim() 1, the type tells them apart
             const bool line = dynamic_cast<LineEdgeSet*>(es) != nullptr;
@@ -690,6 +751,14 @@ void CudaGraphOptimisationImpl::initialize()
         if (uniform)
             fk.weight.resize(fk.weight_w);
         cugo_host::collapse_thresholds(fk.threshold);
+    }
+    { // one matrix for all landmark priors: a single entry
+        std::vector<double>& w = g.lm_priors.info;
+        bool uniform = !w.empty();
+        for (size_t i = 6; uniform && i < w.size(); i++)
+            uniform = w[i] == w[i % 6];
+        if (uniform)
+            w.resize(6);
     }
     lap("graph: edge flatten");
 

@@ -13,6 +13,7 @@
 // 1223 (max diagonal), 1286-1345 (Schur), 1419-1490 (back-substitution, update, scale).
 #include "ba_math.h"
 #include "kernels.h"
+#include "lm_prior_term.h"
 
 using namespace cugo_dev;
 
@@ -338,9 +339,19 @@ __device__ __forceinline__ LmContrib lm_contrib(const double JL[3][3], const Edg
                      g.w * t0, g.w * t1, g.w * t2};
 }
 
+// the one element of a parameter pack (the view of the landmark priors below)
+template <typename T>
+__device__ __forceinline__ const T& first_of(const T& t)
+{
+    return t;
+}
+
 // (153 VGPRs, no private segment: three waves per SIMD — tools/kernel_resources.sh.  Capped at 128 — four waves — the kernel spills ~230 bytes per lane and takes
 // 75 instead of 56 us: 11.43 vs 11.17 ms per step, 38.9 vs 38.2 ms on the 10k-pose graph.)
-template <typename S>
+// LMP: landmark position priors (lm_prior_term.h) ride along: LP is then the one LmPriorView.  The
+// instantiation without them takes the arguments the kernel has always taken (an empty pack) and holds none of their
+// code; both have the register figures above.
+template <typename S, bool LMP, typename... LP>
 __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restrict__ poses,
                                                     const double* __restrict__ lms, Robust2 rk,
                                                     S* __restrict__ Hpl,
@@ -349,8 +360,9 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
                                                     double* __restrict__ rec,
                                                     double* __restrict__ partials,
                                                     double fuse_lambda, double* __restrict__ invHll,
-                                                    S* __restrict__ T, double* __restrict__ lmrec)
+                                                    S* __restrict__ T, double* __restrict__ lmrec, LP... lp)
 {
+    static_assert(sizeof...(LP) == (LMP ? 1 : 0), "the view of the landmark priors goes with LMP");
     // fuse_lambda >= 0 (the engine, whose slot layout keeps a landmark inside one workgroup, from the
     // second LM iteration on: the damping of the first trial is known when the build is queued): this
     // pass also leaves invHll = (Hll + lambda I)^-1 and T = Hpl invHll — exactly what k_schur_edges
@@ -474,6 +486,10 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             a[0] += c2.h00, a[1] += c2.h01, a[2] += c2.h02, a[3] += c2.h11, a[4] += c2.h12;
             a[5] += c2.h22, a[6] += c2.b0, a[7] += c2.b1, a[8] += c2.b2;
         }
+        // the landmark's priors behind ALL its edges, in sorted order: everything below — the stores, either fused form —
+        // carries them, and Hll / bl have the bits of the plain pass followed by k_lm_prior<1>
+        if constexpr (LMP)
+            lm_prior_accumulate(first_of(lp...), l, lms + 3 * (size_t)l, a);
         double* Hg = Hll + 9 * (size_t)l;
         const double h9[9] = {a[0], a[1], a[2], a[1], a[3], a[4], a[2], a[4], a[5]};
 #pragma unroll
@@ -517,10 +533,23 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
     if (e < ev.L && ev.lm_ptr[e] == ev.lm_ptr[e + 1])
     { // landmark without any edge
         double* H = Hll + 9 * (size_t)e;
+        if constexpr (LMP)
+        { // its priors added to the zeros (kernel level only: the engine refuses such a graph, nothing steps the landmark)
+            double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+            lm_prior_accumulate(first_of(lp...), e, lms + 3 * (size_t)e, a);
+            const double h9[9] = {a[0], a[1], a[2], a[1], a[3], a[4], a[2], a[4], a[5]};
 #pragma unroll
-        for (int i = 0; i < 9; i++)
-            H[i] = 0;
-        bl[3 * (size_t)e] = 0, bl[3 * (size_t)e + 1] = 0, bl[3 * (size_t)e + 2] = 0;
+            for (int i = 0; i < 9; i++)
+                H[i] = h9[i];
+            bl[3 * (size_t)e] = a[6], bl[3 * (size_t)e + 1] = a[7], bl[3 * (size_t)e + 2] = a[8];
+        }
+        else
+        {
+#pragma unroll
+            for (int i = 0; i < 9; i++)
+                H[i] = 0;
+            bl[3 * (size_t)e] = 0, bl[3 * (size_t)e + 1] = 0, bl[3 * (size_t)e + 2] = 0;
+        }
     }
     // ---- Hpl blocks of the block's 256 slots -> global through LDS: a lane storing its own
     // 144 bytes (9 stores at a 144-B stride) touches 64 cache lines per store instruction
@@ -2576,7 +2605,8 @@ template <typename S>
 static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                            cugo_robust rk, double* d_Hpp, double* d_bp, double* d_Hll, double* d_bl,
                            S* d_Hpl, ReduceScratch rs, double* d_chi, double fuse_lambda, double* d_invHll,
-                           S* d_T, double* d_lmrec, bool skip_poses, bool chi_behind_scale)
+                           S* d_T, double* d_lmrec, bool skip_poses, bool chi_behind_scale,
+                           const cugo_lm_prior_edges* lm_priors)
 {
     const EV ev = make_ev(e);
     const Robust2 r{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}};
@@ -2585,10 +2615,20 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
     // chi_behind_scale: this build pass ends a trial (launch_trial_tail_from_build sums its chi2 partials together with
     // the scale partials of the update pass, which sit at the start of the scratch)
     double* d_chi_part = rs.d_partials + (chi_behind_scale ? spec_chi_offset(ev.E, ev.P, ev.L) : 0);
-    if (nb > 0)
-        CUGO_LAUNCH_T(k_build_edges, S, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r, d_Hpl, d_Hll,
-                      d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
-                      d_invHll && d_T ? d_lmrec : nullptr);
+    if (nb > 0 && lm_priors && lm_priors->n > 0)
+    {
+        ::cugo_k::LaunchScope _scope("k_build_edges", s);
+        hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r, d_Hpl,
+                           d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
+                           d_invHll && d_T ? d_lmrec : nullptr, lm_prior_view(*lm_priors));
+    }
+    else if (nb > 0)
+    {
+        ::cugo_k::LaunchScope _scope("k_build_edges", s);
+        hipLaunchKernelGGL((k_build_edges<S, false>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r, d_Hpl, d_Hll,
+                           d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
+                           d_invHll && d_T ? d_lmrec : nullptr);
+    }
     if (d_chi)
         CUGO_LAUNCH(k_sum_partials, dim3(1), dim3(SP_BS), 0, s, d_chi_part, nb, d_chi);
     // skip_poses: the Schur complement of this lambda forms Hsc's diagonal blocks, bp and bsc from the records itself
@@ -2600,14 +2640,14 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
 void launch_build(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                   cugo_robust rk, double* d_Hpp, double* d_bp, double* d_Hll, double* d_bl,
                   void* d_Hpl, ReduceScratch rs, double* d_chi, double fuse_lambda, double* d_invHll, void* d_T,
-                  double* d_lmrec, bool skip_poses, bool chi_behind_scale)
+                  double* d_lmrec, bool skip_poses, bool chi_behind_scale, const cugo_lm_prior_edges* lm_priors)
 {
     if (e.block_f32)
         launch_build_t(s, e, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, static_cast<float*>(d_Hpl), rs, d_chi,
-                       fuse_lambda, d_invHll, static_cast<float*>(d_T), d_lmrec, skip_poses, chi_behind_scale);
+                       fuse_lambda, d_invHll, static_cast<float*>(d_T), d_lmrec, skip_poses, chi_behind_scale, lm_priors);
     else
         launch_build_t(s, e, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, static_cast<double*>(d_Hpl), rs, d_chi,
-                       fuse_lambda, d_invHll, static_cast<double*>(d_T), d_lmrec, skip_poses, chi_behind_scale);
+                       fuse_lambda, d_invHll, static_cast<double*>(d_T), d_lmrec, skip_poses, chi_behind_scale, lm_priors);
 }
 
 // The end of a trial whose chi2 comes out of the NEXT iteration's build pass (launch_build with chi_behind_scale, queued

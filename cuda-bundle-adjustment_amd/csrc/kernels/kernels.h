@@ -64,11 +64,15 @@ void launch_errors(hipStream_t s, const cugo_edges& ev, const double* d_poses, c
 // the same d_lmrec and d_T for that form (SchurRows::d_lmrec).
 // chi_behind_scale: the chi2 partials of the pass go behind the scale partials of the update pass in the scratch, for
 // launch_trial_tail_from_build.
+// lm_priors (optional; nullptr or n == 0: the pass as it is without them, the same instantiation with the same
+// arguments): landmark position priors (lm_prior_kernels.hip).  The owner lane of every free landmark adds the
+// landmark's priors, in sorted order, behind the landmark's edges and before Hll / bl are stored, factored or inverted:
+// Hll, bl, invHll, T, G and the landmarks' lines all carry them.  The chi2 of the pass stays that of the BA edges.
 void launch_build(hipStream_t s, const cugo_edges& ev, const double* d_poses, const double* d_lms,
                   cugo_robust rk, double* d_Hpp, double* d_bp, double* d_Hll, double* d_bl,
                   void* d_Hpl, ReduceScratch rs, double* d_chi, double fuse_lambda = -1.0,
                   double* d_invHll = nullptr, void* d_T = nullptr, double* d_lmrec = nullptr, bool skip_poses = false,
-                  bool chi_behind_scale = false);
+                  bool chi_behind_scale = false, const cugo_lm_prior_edges* lm_priors = nullptr);
 
 // the reductions that end a trial, with the chi2 partials of a build pass queued with chi_behind_scale (ba_kernels.hip)
 // d_icp_chi / n_icp_chi (both tails): chi2 totals of the chunks of an ICP pass at the trial's estimates (icp_chunk_count),
@@ -207,6 +211,18 @@ void launch_prior_add(hipStream_t s, const cugo_prior_edges& ev, const double* d
 // k_pose_schur, which writes the three in the one-stream form)
 void launch_prior_add_schur(hipStream_t s, const cugo_prior_edges& ev, const double* d_poses, const int32_t* d_rowptr,
                             double* d_Hsc, double* d_bp, double* d_bsc, double* d_wg_chi);
+
+// --- landmark position priors with 3 x 3 information (lm_prior_kernels.hip) -----------------
+// One lane per free landmark walks its priors in sorted order; every 256-lane workgroup leaves one chi2 total in
+// d_wg_chi [lm_prior_workgroups()], its lanes in order.  The LM loop places these totals behind the relative-pose
+// totals; the terms themselves it takes inside the build pass (launch_build with lm_priors).
+int lm_prior_workgroups(const cugo_lm_prior_edges& ev); // 0 without priors or free landmarks: nothing is launched
+// chi2 only; d_edge_chi [n] (sorted order, 0 for priors that do not count; priors on fixed landmarks are not written)
+void launch_lm_prior_errors(hipStream_t s, const cugo_lm_prior_edges& ev, const double* d_lms, double* d_wg_chi,
+                            double* d_edge_chi = nullptr);
+// the terms ADDED to d_Hll [Lfree][9] / d_bl [Lfree][3]; the same totals, bit for bit
+void launch_lm_prior_add(hipStream_t s, const cugo_lm_prior_edges& ev, const double* d_lms, double* d_Hll, double* d_bl,
+                         double* d_wg_chi);
 
 // --- relative-pose SE(3) edges (relpose_kernels.hip) ---------------------------------------
 // the device side of a cugo_relpose_plan (csrc/host/relpose_plan.h): index arrays and incidence lists

@@ -144,6 +144,9 @@ public:
     /** relative-pose edges of the current flattening that count: active, at least one free end (relpose_types.h, an
      *  extension; GraphOptimisationOptions::relativePoseEdges) */
     int nRelPoseEdges() const;
+    /** landmark position priors of the current flattening that count: active, on a free landmark
+     *  (landmark_prior_types.h, an extension) */
+    int nLandmarkPriorEdges() const;
     /** B, M, nnz(L), flops, supernodes, stages, front bytes, off-diagonal products, then per
      *  factorisation: potrf / trsm / syrk flops, extend-add bytes, backward bytes */
     std::vector<double> structureStats() const;

@@ -386,6 +386,53 @@ int cugo_prior_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_prior_ed
                                               const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi);
 
 /*
+ * Extension (the reference has no such edge; g2o: EdgeXYZPrior): landmark position priors, unary edges on a landmark
+ * with a measured position Z and a 3 x 3 information matrix Omega (symmetric, positive semi-definite):
+ *   r = X - Z,  J = I,  chi2 term rho(max(0, r^T Omega r)) with the set's robust kernel,  w = rho'
+ *   Hll += w Omega,  bl -= w Omega r          (sign and column-major blocks of cugo_construct_quadratic_form)
+ * The priors are SORTED by landmark index (ascending), structure of arrays; lm_ptr is the CSR over ALL landmarks (the
+ * priors of landmark l are [lm_ptr[l], lm_ptr[l+1])).  Priors on fixed landmarks (index >= n_landmarks_free) and priors
+ * flagged CUGO_EDGE_INACTIVE contribute nothing.
+ */
+typedef struct cugo_lm_prior_edges
+{
+    int n_landmarks_total, n_landmarks_free;
+    int n;
+    const int32_t* d_lm;     /* [n] ascending */
+    const int32_t* d_lm_ptr; /* [n_landmarks_total+1] */
+    const double* d_meas;    /* [3][n] x y z of Z */
+    const double* d_info;    /* [6][n] or [6][1]: upper triangle of Omega, row-major packed 00 01 02 11 12 22 */
+    int n_info;              /* n or 1 */
+    const uint8_t* d_flags;  /* [n] CUGO_EDGE_INACTIVE, or NULL: all active */
+    int rk;                  /* CUGO_RK_* */
+    double delta;
+} cugo_lm_prior_edges;
+
+/* Writes the chi2 total to d_chi[0]; with d_edge_chi (optional, [n], sorted order) also the chi2 term of every prior (0
+ * for priors that do not count).  d_lms [n_landmarks_total][3].  Checks lm_ptr on the host and the landmark index of
+ * every prior on the device before launching, and refuses a bad layout or an unknown kernel code with CUGO_ERR_INVALID
+ * (one flag is read back: the call synchronises once).  The values (finite, Omega symmetric positive semi-definite) are
+ * the caller's.  Deterministic. */
+int cugo_lm_prior_compute_errors(cugo_ctx* ctx, const cugo_lm_prior_edges* ev, const double* d_lms, double* d_chi,
+                                 double* d_edge_chi);
+
+/* ADDS sum w Omega to d_Hll [n_landmarks_free][9] and -sum w Omega r to d_bl [n_landmarks_free][3], one lane per
+ * landmark over its priors in sorted order.  Writes the chi2 total to d_chi[0] if d_chi != NULL (the bits of
+ * cugo_lm_prior_compute_errors).  A landmark none of whose priors counts keeps the bits of its blocks.  Checks as
+ * above.  No atomics. */
+int cugo_lm_prior_construct_quadratic_form(cugo_ctx* ctx, const cugo_lm_prior_edges* ev, const double* d_lms, double* d_Hll,
+                                           double* d_bl, double* d_chi);
+
+/* cugo_construct_quadratic_form with the priors taken INSIDE the edge kernel of the build pass, the form the LM loop
+ * uses: the lane that sums a landmark's Hll / bl adds the landmark's priors behind its edges, in sorted order.  d_Hll /
+ * d_bl receive the bits of cugo_construct_quadratic_form followed by cugo_lm_prior_construct_quadratic_form; d_Hpp,
+ * d_bp and d_Hpl those of cugo_construct_quadratic_form; d_chi[0], if given, the BA chi2 plus the priors' chi2.  lp must
+ * describe the landmarks of ev (the same totals).  Checks as above. */
+int cugo_construct_quadratic_form_lm_priors(cugo_ctx* ctx, const cugo_edges* ev, const cugo_lm_prior_edges* lp,
+                                            const double* d_poses, const double* d_lms, cugo_robust rk, double* d_Hpp,
+                                            double* d_bp, double* d_Hll, double* d_bl, void* d_Hpl, double* d_chi);
+
+/*
  * Extension (the reference has no such edge): relative-pose SE(3) edges, binary edges between poses a and b with a
  * measurement Z = (q_z, t_z) ~ T_a T_b^-1 and a full 6 x 6 information matrix Omega (relpose_types.h).  Conventions as
  * for cugo_prior_edges:
@@ -549,6 +596,21 @@ int cugo_graph_set_prior_robust_kernel(cugo_graph* g, int type, double delta);
 int cugo_graph_set_prior_outlier_threshold(cugo_graph* g, double threshold);
 /* active priors in the current flattening (priors on fixed poses are not counted) */
 int cugo_graph_n_prior_edges(cugo_graph* g);
+/* Extension: landmark position priors (LandmarkPriorEdgeSet, cuda-bundle-adjustment_amd/include/landmark_prior_types.h),
+ * next to the other sets; term and conventions as for cugo_lm_prior_edges above.  lm_ids [n]: ids given to
+ * cugo_graph_add_landmarks (an unknown id refuses the whole call: nothing is added); xyz3 [n][3]: the measured position
+ * Z; info9 [n][9]: Omega of every prior (symmetric, so row- and column-major agree), or NULL for the set's matrix
+ * (cugo_graph_set_landmark_prior_information; the identity until it is set), with the per_edge_information rule of the
+ * pose priors.  Several priors on one landmark are allowed.  cugo_graph_initialize() refuses non-finite values, an Omega
+ * that is asymmetric beyond 1e-12 max|Omega| or has an eigenvalue below -1e-12 lambda_max (semi-definite is allowed: a
+ * height-only prior), a landmark of no landmark set of the optimiser, a prior that counts on a free landmark without any
+ * BA edge (the back-substitution gives such a landmark a zero step), an outlier threshold on the set and a sharded
+ * optimiser; priors on fixed landmarks and inactive priors count for nothing. */
+int cugo_graph_add_landmark_priors(cugo_graph* g, int n, const int32_t* lm_ids, const double* xyz3, const double* info9);
+int cugo_graph_set_landmark_prior_information(cugo_graph* g, const double* info9);
+int cugo_graph_set_landmark_prior_robust_kernel(cugo_graph* g, int type, double delta);
+/* active landmark priors in the current flattening (priors on fixed landmarks are not counted) */
+int cugo_graph_n_landmark_prior_edges(cugo_graph* g);
 /* Extension: relative-pose SE(3) edges (RelPoseEdgeSet, cuda-bundle-adjustment_amd/include/relpose_types.h), next to or
  * instead of the other sets; term and conventions as for cugo_relpose_edges above (Z ~ T_a T_b^-1).  pose_ids_a /
  * pose_ids_b [n]: ids given to cugo_graph_add_poses; q_t7 [n][7] the measured relative pose; info36 [n][36] or NULL for
