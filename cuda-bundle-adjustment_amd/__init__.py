@@ -130,6 +130,24 @@ def lib():
         # (ctx, ev, hs, d_Hll, d_Hpl, d_sigma, d_cov9, d_fail): device pointers as c_void_p, None = NULL
         _lib.cugo_landmark_covariances.argtypes = [C.c_void_p, C.POINTER(Edges), C.POINTER(HscStruct)] + [C.c_void_p] * 5
         _lib.cugo_landmark_covariances.restype = C.c_int
+        # (ctx, ev, n, d_q_pose, d_q_lm, d_q_ptr, d_q_slot, d_Hll, d_Hpl, d_blocks, d_cov18, d_fail)
+        _lib.cugo_pose_landmark_cross_covariances.argtypes = [C.c_void_p, C.POINTER(Edges), C.c_int] + [C.c_void_p] * 9
+        _lib.cugo_pose_landmark_cross_covariances.restype = C.c_int
+        # (ctx, n, n_landmarks_free, d_q_pose, d_q_lm, d_q_dim, d_q_aa, d_cam5, d_poses, d_lms, d_blocks, d_cross18,
+        #  d_lmcov9, d_cov9)
+        _lib.cugo_reprojection_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11
+        _lib.cugo_reprojection_covariances.restype = C.c_int
+        _lib.cugo_plcov_plan_create.argtypes = [C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p,
+                                                C.POINTER(C.c_void_p)]
+        _lib.cugo_plcov_plan_create.restype = C.c_int
+        _lib.cugo_plcov_plan_array.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(_i32p)]
+        _lib.cugo_plcov_plan_array.restype = C.c_int
+        _lib.cugo_plcov_plan_destroy.argtypes = [C.c_void_p]
+        _lib.cugo_plcov_plan_destroy.restype = None
+        _lib.cugo_graph_compute_pose_landmark_cross_covariances.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f64p]
+        _lib.cugo_graph_compute_pose_landmark_cross_covariances.restype = C.c_int
+        _lib.cugo_graph_reprojection_covariances.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int, _f64p, _f64p]
+        _lib.cugo_graph_reprojection_covariances.restype = C.c_int
     return _lib
 
 
@@ -217,6 +235,49 @@ class RelPosePlan:
         if self._p:
             lib().cugo_relpose_plan_destroy(self._p)
             self._p = C.c_void_p()
+
+
+class PlCovPlan:
+    """cugo_plcov_plan: the plan of a batch of pose-landmark covariance queries (host only, no GPU): the pose pairs to
+    ask cugo_chol_inverse_blocks for and, per query, the block every slot of its landmark reads.  lm_ptr / slot_pose:
+    the flattened edges (landmark-major slots); q_pose / q_lm: free indices, -1 for a fixed vertex"""
+
+    def __init__(self, n_poses_free, lm_ptr, slot_pose, q_pose, q_lm):
+        lp, sp, qp, ql = _i32(lm_ptr), _i32(slot_pose), _i32(q_pose), _i32(q_lm)
+        if len(qp) != len(ql):
+            raise ValueError("q_pose and q_lm must have the same length")
+        self._p = C.c_void_p()
+        self.n = len(qp)
+        check(lib().cugo_plcov_plan_create(int(n_poses_free), max(len(lp) - 1, 0), _p(lp, _i32p), _p(sp, _i32p), self.n,
+                                           _p(qp, _i32p), _p(ql, _i32p), C.byref(self._p)))
+
+    def array(self, name):
+        """a copy of the plan array rows, cols, q_ptr, q_slot or q_aa"""
+        out = _i32p()
+        n = lib().cugo_plcov_plan_array(self._p, name.encode(), C.byref(out))
+        if n < 0:
+            raise CugoError("cugo error %d: %s" % (n, lib().cugo_last_error().decode()))
+        return np.array(out[:n], np.int32)
+
+    def close(self):
+        if self._p:
+            lib().cugo_plcov_plan_destroy(self._p)
+            self._p = C.c_void_p()
+
+
+def pose_landmark_cross_covariances(ctx, ev, n, d_q_pose, d_q_lm, d_q_ptr, d_q_slot, d_Hll, d_Hpl, d_blocks, d_cov18,
+                                    d_fail):
+    """cugo_pose_landmark_cross_covariances: Sigma_al [n][18] of n queries from the blocks of a PlCovPlan's pair list
+    (device pointers as ctypes.c_void_p; ev: Edges)"""
+    check(lib().cugo_pose_landmark_cross_covariances(ctx, C.byref(ev), int(n), d_q_pose, d_q_lm, d_q_ptr, d_q_slot, d_Hll,
+                                                     d_Hpl, d_blocks, d_cov18, d_fail))
+
+
+def reprojection_covariances(ctx, n, n_landmarks_free, d_q_pose, d_q_lm, d_q_dim, d_q_aa, d_cam5, d_poses, d_lms,
+                             d_blocks, d_cross18, d_lmcov9, d_cov9):
+    """cugo_reprojection_covariances: S = J Sigma J^T [n][9] of n queries (device pointers as ctypes.c_void_p)"""
+    check(lib().cugo_reprojection_covariances(ctx, int(n), int(n_landmarks_free), d_q_pose, d_q_lm, d_q_dim, d_q_aa,
+                                              d_cam5, d_poses, d_lms, d_blocks, d_cross18, d_lmcov9, d_cov9))
 
 
 def relpose_compute_errors(ctx, ev, d_poses, d_chi, d_edge_chi=None):
@@ -680,6 +741,37 @@ class Graph:
         """[n, 6, 6]: covariance of the relative pose T_a T_b^-1 in the tangent convention of the relative-pose edges;
         its inverse is the information of an edge that summarises the graph between a and b.  a == b is refused."""
         return self._pair_blocks(lib().cugo_graph_relative_pose_covariances, ids_a, ids_b)
+
+    def pose_landmark_cross_covariances(self, pose_ids, lm_ids):
+        """[n, 6, 3]: Sigma_al of the pairs (pose_ids[k], lm_ids[k]) at the current estimates — any pairs, with or
+        without an edge (rows in the tangent order of pose_covariances(); zeros where either vertex is fixed).  With
+        pose_covariances() and landmark_covariances() it completes the joint covariance of a camera and a map point.
+        Does not touch what compute_covariances() stored.  Raises CugoError (code -4) on a zero pivot or when a
+        queried landmark has no active edge."""
+        a = np.ascontiguousarray(pose_ids, np.int32).reshape(-1)
+        b = np.ascontiguousarray(lm_ids, np.int32).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("pose_ids and lm_ids must have the same length")
+        out = np.zeros((len(a), 18))
+        check(lib().cugo_graph_compute_pose_landmark_cross_covariances(self._g, len(a), _p(a, _i32p), _p(b, _i32p),
+                                                                       _p(out, _f64p)))
+        return out.reshape(-1, 3, 6).transpose(0, 2, 1).copy()  # (column-major blocks)
+
+    def reprojection_covariances(self, pose_ids, lm_ids, dim=2, cam=None):
+        """[n, dim, dim]: covariance S = J Sigma J^T of the predicted reprojection of landmark lm_ids[k] in pose
+        pose_ids[k] over their joint covariance (dim 2: u, v; dim 3: u, v, u_right).  cam: [5] or [n, 5] (fx, fy, cx,
+        cy, bf); None: the camera given to set_camera(dim, ...).  A fixed vertex contributes no terms."""
+        a = np.ascontiguousarray(pose_ids, np.int32).reshape(-1)
+        b = np.ascontiguousarray(lm_ids, np.int32).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("pose_ids and lm_ids must have the same length")
+        c = None if cam is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(cam, np.float64).reshape(-1, 5), (len(a), 5)))
+        dd = int(dim) * int(dim) if dim in (2, 3) else 9
+        out = np.zeros((len(a), dd))
+        check(lib().cugo_graph_reprojection_covariances(self._g, len(a), _p(a, _i32p), _p(b, _i32p), int(dim),
+                                                        None if c is None else _p(c, _f64p), _p(out, _f64p)))
+        return out.reshape(-1, int(dim), int(dim)).transpose(0, 2, 1).copy()
 
     def set_poses(self, ids, q_t7):
         ids = np.ascontiguousarray(ids, np.int32); q = np.ascontiguousarray(q_t7, np.float64)

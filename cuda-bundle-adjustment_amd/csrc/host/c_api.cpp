@@ -2,6 +2,7 @@
 #include <cmath>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <unordered_map>
 
@@ -17,6 +18,7 @@
 #include "engine.h"
 #include "hip_util.h"
 #include "rccl_comm.h"
+#include "plcov_plan.h"
 #include "relpose_plan.h"
 #include "schur_plan.h"
 
@@ -472,6 +474,12 @@ struct cugo_relpose_plan
     }
 };
 
+// the plan of a batch of pose-landmark covariance queries (plcov_plan.h): host arrays only, the caller uploads them
+struct cugo_plcov_plan
+{
+    cugo_host::PlCovPlanHost host;
+};
+
 namespace
 {
 // the layout is the plan's own, so nothing is checked on the device: counts against the plan, arrays, kernel code
@@ -756,6 +764,77 @@ int cugo_landmark_covariances(cugo_ctx* ctx, const cugo_edges* ev, const cugo_hs
         CUGO_HIP(hipMemsetAsync(d_fail, 0, sizeof(int32_t), ctx->stream));
         cugo_k::launch_lm_covariance(ctx->stream, ev->n_landmarks_free, ev->d_lm_ptr, ev->d_pose, ev->d_flags, d_Hll,
                                      d_Hpl, hs->d_rowptr, hs->d_colind, d_sigma, d_cov9, d_fail);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+int cugo_plcov_plan_create(int n_poses_free, int n_landmarks, const int32_t* h_lm_ptr, const int32_t* h_slot_pose, int n,
+                           const int32_t* h_q_pose, const int32_t* h_q_lm, cugo_plcov_plan** out)
+{
+    return guarded([&] {
+        if (!out)
+            throw std::invalid_argument("cugo_plcov_plan_create: null argument");
+        *out = nullptr;
+        auto p = std::make_unique<cugo_plcov_plan>();
+        cugo_host::build_plcov_plan(n_poses_free, n_landmarks, h_lm_ptr, h_slot_pose, n, h_q_pose, h_q_lm, p->host);
+        *out = p.release();
+    });
+}
+void cugo_plcov_plan_destroy(cugo_plcov_plan* plan) { delete plan; }
+int cugo_plcov_plan_array(const cugo_plcov_plan* plan, const char* name, const int32_t** out)
+{
+    if (!plan || !name || !out)
+        return CUGO_ERR_INVALID;
+    const std::string n = name;
+    const cugo_host::PlCovPlanHost& h = plan->host;
+    const std::vector<int32_t>* v = n == "rows" ? &h.rows : n == "cols" ? &h.cols : n == "q_ptr" ? &h.q_ptr
+                                    : n == "q_slot" ? &h.q_slot : n == "q_aa" ? &h.q_aa : nullptr;
+    if (!v)
+    {
+        set_last_error("cugo_plcov_plan_array: unknown array " + n);
+        return CUGO_ERR_INVALID;
+    }
+    *out = v->data();
+    return (int)v->size();
+}
+int cugo_pose_landmark_cross_covariances(cugo_ctx* ctx, const cugo_edges* ev, int n, const int32_t* d_q_pose,
+                                         const int32_t* d_q_lm, const int32_t* d_q_ptr, const int32_t* d_q_slot,
+                                         const double* d_Hll, const double* d_Hpl, const double* d_blocks,
+                                         double* d_cov18, int32_t* d_fail)
+{
+    return guarded([&] {
+        if (!ctx || !ev || !d_q_pose || !d_q_lm || !d_q_ptr || !d_q_slot || !d_Hll || !d_Hpl || !d_blocks || !d_cov18 ||
+            !d_fail)
+            throw std::invalid_argument("cugo_pose_landmark_cross_covariances: null argument");
+        if (n < 0)
+            throw std::invalid_argument("cugo_pose_landmark_cross_covariances: negative count");
+        if (ev->block_f32)
+            throw std::invalid_argument("cugo_pose_landmark_cross_covariances: the kernel reads Hpl as fp64 (ev->block_f32 "
+                                        "is set)");
+        if (n == 0)
+            return;
+        if (!ev->d_lm_ptr || !ev->d_flags)
+            throw std::invalid_argument("cugo_pose_landmark_cross_covariances: null array in ev");
+        CUGO_HIP(hipMemsetAsync(d_fail, 0, sizeof(int32_t), ctx->stream));
+        cugo_k::launch_pose_lm_cross(ctx->stream, n, d_q_pose, d_q_lm, d_q_ptr, d_q_slot, ev->d_lm_ptr, ev->d_flags, d_Hll,
+                                     d_Hpl, d_blocks, d_cov18, d_fail);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+int cugo_reprojection_covariances(cugo_ctx* ctx, int n, int n_landmarks_free, const int32_t* d_q_pose,
+                                  const int32_t* d_q_lm, const int32_t* d_q_dim, const int32_t* d_q_aa,
+                                  const double* d_cam5, const double* d_poses, const double* d_lms,
+                                  const double* d_blocks, const double* d_cross18, const double* d_lmcov9, double* d_cov9)
+{
+    return guarded([&] {
+        if (!ctx || !d_q_pose || !d_q_lm || !d_q_dim || !d_q_aa || !d_cam5 || !d_poses || !d_lms || !d_blocks ||
+            !d_cross18 || !d_lmcov9 || !d_cov9)
+            throw std::invalid_argument("cugo_reprojection_covariances: null argument");
+        if (n < 0 || n_landmarks_free < 0)
+            throw std::invalid_argument("cugo_reprojection_covariances: negative count");
+        if (n == 0)
+            return;
+        cugo_k::launch_reprojection_cov(ctx->stream, n, n_landmarks_free, d_q_pose, d_q_lm, d_q_dim, d_q_aa, d_cam5,
+                                        d_poses, d_lms, d_blocks, d_cross18, d_lmcov9, d_cov9);
         CUGO_HIP(hipGetLastError());
     });
 }
@@ -1585,6 +1664,64 @@ int cugo_graph_compute_pose_cross_covariances(cugo_graph* g, int n, const int32_
                                               double* cov36)
 {
     return pose_cross_blocks(g, "cugo_graph_compute_pose_cross_covariances", n, ids_a, ids_b, cov36);
+}
+
+namespace
+{
+// the two pose-landmark calls by caller id; CUGO_ERR_NUMERIC on a zero pivot or a queried landmark whose Hll fails
+using PoseLandmarkFn = std::function<bool(const cugo::BaseVertex* const*, const cugo::BaseVertex* const*)>;
+int pose_landmark_call(cugo_graph* g, const char* who, int n, const int32_t* pose_ids, const int32_t* lm_ids,
+                       const PoseLandmarkFn& call)
+{
+    bool ok = true;
+    const int rc = guarded([&] {
+        if (!g)
+            throw std::invalid_argument(std::string(who) + ": null argument");
+        if (n < 0)
+            throw std::invalid_argument(std::string(who) + ": negative count");
+        if (n > 0 && (!pose_ids || !lm_ids))
+            throw std::invalid_argument(std::string(who) + ": null argument");
+        std::vector<const cugo::BaseVertex*> p(n), l(n);
+        for (int i = 0; i < n; i++)
+            p[i] = g->poses.getVertex(pose_ids[i]), l[i] = g->lms.getVertex(lm_ids[i]);
+        ok = call(p.data(), l.data());
+    });
+    if (rc != CUGO_OK)
+        return rc;
+    if (!ok)
+    {
+        set_last_error(std::string(who) + ": zero pivot — H is singular at the current estimates, or a queried landmark "
+                                          "has no active edge");
+        return CUGO_ERR_NUMERIC;
+    }
+    return CUGO_OK;
+}
+} // namespace
+
+int cugo_graph_compute_pose_landmark_cross_covariances(cugo_graph* g, int n, const int32_t* pose_ids,
+                                                       const int32_t* lm_ids, double* cov18)
+{
+    return pose_landmark_call(g, "cugo_graph_compute_pose_landmark_cross_covariances", n, pose_ids, lm_ids,
+                              [&](const cugo::BaseVertex* const* p, const cugo::BaseVertex* const* l) {
+                                  return g->opt->poseLandmarkCrossCovariances(n, p, l, cov18);
+                              });
+}
+
+int cugo_graph_reprojection_covariances(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* lm_ids, int dim,
+                                        const double* cam5, double* cov)
+{
+    return pose_landmark_call(g, "cugo_graph_reprojection_covariances", n, pose_ids, lm_ids,
+                              [&](const cugo::BaseVertex* const* p, const cugo::BaseVertex* const* l) {
+                                  if (dim != 2 && dim != 3)
+                                      throw std::invalid_argument("cugo_graph_reprojection_covariances: dim must be 2 "
+                                                                  "(mono) or 3 (stereo)");
+                                  if (cam5)
+                                      return g->opt->reprojectionCovariances(n, p, l, dim, cam5, n, cov);
+                                  // the camera of the edge set of that dim (cugo_graph_set_camera)
+                                  const cugo::Camera& c = dim == 3 ? g->stereo.getCamera() : g->mono.getCamera();
+                                  const double set5[5] = {c.fx, c.fy, c.cx, c.cy, c.bf};
+                                  return g->opt->reprojectionCovariances(n, p, l, dim, set5, 1, cov);
+                              });
 }
 
 int cugo_graph_relative_pose_covariances(cugo_graph* g, int n, const int32_t* ids_a, const int32_t* ids_b, double* cov36)

@@ -20,6 +20,7 @@
 #include "hip_util.h"
 #include "options.h"
 #include "rccl_comm.h"
+#include "plcov_plan.h"
 #include "relpose_plan.h"
 #include "schur_plan.h"
 #include "structure_gpu.h"
@@ -149,7 +150,12 @@ struct Engine::Impl : cugo_k::LaunchHook
     // marginal covariances (Engine::compute_covariances; allocated by the first call only): the blocks of Sigma on
     // the Hsc pattern, the landmark blocks, their positive-definiteness flag
     DevBuf<double> d_cov_sigma, d_cov_pose, d_cov_lm, d_xcov; // (d_xcov: Engine::pose_cross_covariances)
-    DevBuf<int32_t> d_cov_fail;
+    DevBuf<int32_t> d_cov_fail; // [0] k_lm_covariance, [1] k_pose_lm_cross
+    // pose-landmark queries (Engine::queue_pose_lm_cross): the index arrays of a batch behind one another, the pose
+    // blocks of its plan, Sigma_al, the cameras and the result of k_reprojection_cov
+    std::vector<int32_t> h_pl_idx;
+    DevBuf<int32_t> d_pl_idx;
+    DevBuf<double> d_pl_blocks, d_pl_cross, d_pl_cam, d_pl_out;
     PinnedBuf<double> h_pin_poses, h_pin_lms; // refresh_estimates_pinned / download_pinned
     Clock::duration last_trial_wait{0};       // how long the host polled for the previous trial's result
     DevBuf<int32_t> d_hsc_rowptr, d_hsc_colind, d_off_ptr, d_off_ei, d_off_ej, d_fail;
@@ -2105,6 +2111,126 @@ bool Engine::pose_cross_covariances(int n, const int32_t* ia, const int32_t* ib,
     CUGO_HIP(hipStreamSynchronize(s));
     for (size_t q = 0; q < where.size(); q++)
         std::copy(h.begin() + 36 * q, h.begin() + 36 * q + 36, cov36 + 36 * (size_t)where[q]);
+    return true;
+}
+
+// The plan needs the pose of every slot on the host: the engine keeps the slot arrays of the flattening (slots.pose,
+// what d_e_pose was uploaded from; build_structure() reads it too), so nothing is downloaded.
+bool Engine::queue_pose_lm_cross(int n, const int32_t* qp, const int32_t* ql, const std::vector<int32_t>& extra,
+                                 size_t off[6])
+{
+    Impl& m = *impl_;
+    PlCovPlanHost plan;
+    build_plcov_plan(m.P, m.L, m.h_lm_ptr.data(), m.slots.pose.data(), n, qp, ql, plan);
+    queue_covariance_system();
+    hipStream_t s = m.ctx.stream;
+    m.d_pl_blocks.resize(36 * plan.rows.size() + 16);
+    if (!plan.rows.empty() &&
+        !m.chol.inverse_blocks((int)plan.rows.size(), plan.rows.data(), plan.cols.data(), m.d_pl_blocks.data()))
+        return false;
+    std::vector<int32_t>& h = m.h_pl_idx; // (pageable: it lives until the caller's synchronisation)
+    h.clear();
+    auto put = [&h](const int32_t* p, size_t k) {
+        const size_t at = h.size();
+        h.insert(h.end(), p, p + k);
+        return at;
+    };
+    off[0] = put(qp, (size_t)n), off[1] = put(ql, (size_t)n);
+    off[2] = put(plan.q_ptr.data(), plan.q_ptr.size()), off[3] = put(plan.q_slot.data(), plan.q_slot.size());
+    off[4] = put(plan.q_aa.data(), plan.q_aa.size()), off[5] = put(extra.data(), extra.size());
+    m.d_pl_idx.upload(h, s);
+    m.d_pl_cross.resize(18 * (size_t)n + 16);
+    m.d_cov_fail.resize(16);
+    m.d_cov_fail.zero(s);
+    const int32_t* ix = m.d_pl_idx.data();
+    cugo_k::launch_pose_lm_cross(s, n, ix + off[0], ix + off[1], ix + off[2], ix + off[3], m.ev.d_lm_ptr, m.ev.d_flags,
+                                 m.d_Hll.data(), reinterpret_cast<const double*>(m.d_Hpl.data()), m.d_pl_blocks.data(),
+                                 m.d_pl_cross.data(), m.d_cov_fail.data() + 1);
+    return true;
+}
+
+bool Engine::pose_landmark_cross_covariances(int n, const int32_t* ia, const int32_t* il, double* cov18)
+{
+    Impl& m = *impl_;
+    const char* who = "cugo_graph_compute_pose_landmark_cross_covariances";
+    check_covariance_call(who);
+    bool any = false;
+    for (int k = 0; k < n; k++)
+    {
+        if (ia[k] < -1 || ia[k] >= m.P || il[k] < -1 || il[k] >= m.L)
+            throw std::invalid_argument(std::string(who) + ": vertex index out of range");
+        any = any || il[k] >= 0; // (a free landmark is looked at under a fixed pose too: its Hll must factor)
+    }
+    std::fill(cov18, cov18 + 18 * (size_t)n, 0.0);
+    if (!any) // (every query holds a fixed landmark: nothing to factor)
+        return true;
+    size_t off[6];
+    if (!queue_pose_lm_cross(n, ia, il, {}, off))
+        return false;
+    hipStream_t s = m.ctx.stream;
+    int32_t fail = 0;
+    CUGO_HIP(hipMemcpyAsync(cov18, m.d_pl_cross.data(), 18 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    CUGO_HIP(hipMemcpyAsync(&fail, m.d_cov_fail.data() + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CUGO_HIP(hipStreamSynchronize(s));
+    if (fail)
+        std::fill(cov18, cov18 + 18 * (size_t)n, 0.0);
+    return !fail;
+}
+
+bool Engine::reprojection_covariances(int n, const int32_t* ia, const int32_t* il, int dim, const double* cam5, double* cov)
+{
+    Impl& m = *impl_;
+    const char* who = "cugo_graph_reprojection_covariances";
+    check_covariance_call(who);
+    if (dim != 2 && dim != 3)
+        throw std::invalid_argument(std::string(who) + ": dim must be 2 (mono) or 3 (stereo)");
+    std::vector<int32_t> qp((size_t)n), ql((size_t)n), extra(3 * (size_t)n);
+    bool any = false, any_lm = false;
+    for (int k = 0; k < n; k++)
+    {
+        if (ia[k] < 0 || ia[k] >= m.Pall || il[k] < 0 || il[k] >= m.Lall)
+            throw std::invalid_argument(std::string(who) + ": vertex index out of range");
+        qp[k] = ia[k] < m.P ? ia[k] : -1, ql[k] = il[k] < m.L ? il[k] : -1;
+        extra[k] = ia[k], extra[(size_t)n + k] = il[k], extra[2 * (size_t)n + k] = dim;
+        any = any || qp[k] >= 0 || ql[k] >= 0;
+        any_lm = any_lm || ql[k] >= 0;
+    }
+    const size_t dd = (size_t)dim * dim;
+    std::fill(cov, cov + dd * (size_t)n, 0.0);
+    if (!any) // (both vertices of every query are fixed)
+        return true;
+    size_t off[6];
+    if (!queue_pose_lm_cross(n, qp.data(), ql.data(), extra, off))
+        return false;
+    hipStream_t s = m.ctx.stream;
+    // Sigma_ll of every free landmark on the same factorisation; whether one of them fails is the first kernel's call
+    m.d_cov_lm.resize(9 * (size_t)m.L + 16);
+    if (any_lm)
+    {
+        m.d_cov_sigma.resize(36 * (size_t)m.hs.n_blocks + 16);
+        if (m.P > 0 && !m.chol.selected_inverse(m.d_cov_sigma.data()))
+            return false;
+        cugo_k::launch_lm_covariance(s, m.L, m.ev.d_lm_ptr, m.ev.d_pose, m.ev.d_flags, m.d_Hll.data(),
+                                     reinterpret_cast<const double*>(m.d_Hpl.data()), m.hs.d_rowptr, m.hs.d_colind,
+                                     m.d_cov_sigma.data(), m.d_cov_lm.data(), m.d_cov_fail.data());
+    }
+    m.d_pl_cam.upload(cam5, 5 * (size_t)n, s);
+    m.d_pl_out.resize(9 * (size_t)n + 16);
+    const int32_t* ix = m.d_pl_idx.data();
+    cugo_k::launch_reprojection_cov(s, n, m.L, ix + off[5], ix + off[5] + n, ix + off[5] + 2 * (size_t)n, ix + off[4],
+                                    m.d_pl_cam.data(), m.d_poses[m.cur].data(), m.d_lms[m.cur].data(), m.d_pl_blocks.data(),
+                                    m.d_pl_cross.data(), m.d_cov_lm.data(), m.d_pl_out.data());
+    std::vector<double> h(9 * (size_t)n);
+    int32_t fail = 0;
+    CUGO_HIP(hipMemcpyAsync(h.data(), m.d_pl_out.data(), h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    CUGO_HIP(hipMemcpyAsync(&fail, m.d_cov_fail.data() + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CUGO_HIP(hipStreamSynchronize(s));
+    if (fail)
+        return false;
+    for (int k = 0; k < n; k++)
+        for (int c = 0; c < dim; c++)
+            for (int r = 0; r < dim; r++)
+                cov[dd * (size_t)k + r + (size_t)dim * c] = h[9 * (size_t)k + r + 3 * c];
     return true;
 }
 

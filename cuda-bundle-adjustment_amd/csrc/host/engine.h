@@ -224,6 +224,18 @@ public:
     // into cov36 [n][36] (host, column-major, rows a).  The same build pass, Schur complement and factorisation, then
     // cugo_chol::inverse_blocks; the marginals kept by compute_covariances() are not touched.  false: a zero pivot.
     bool pose_cross_covariances(int n, const int32_t* ia, const int32_t* ib, double* cov36);
+    // Extension: the pose-landmark blocks Sigma_al of n queries, given by free pose index and free landmark index (-1: a
+    // fixed vertex, the block is zero), into cov18 [n][18] (host, 6x3 column-major, rows a).  One build pass, Schur
+    // complement and factorisation, the plan of the batch (plcov_plan.h, from the engine's host copy of the slot
+    // layout), cugo_chol::inverse_blocks for its pairs into a device buffer and k_pose_lm_cross; only the results
+    // travel to the host.  The same contract as pose_cross_covariances.  false: a zero pivot, or the Hll of a queried
+    // landmark is not positive definite.
+    bool pose_landmark_cross_covariances(int n, const int32_t* ia, const int32_t* il, double* cov18);
+    // Extension: S = J Sigma J^T of the reprojection of landmark il[k] in pose ia[k] (indices of the flattening, fixed
+    // vertices included: >= n_poses_free() / n_landmarks_free()) into cov [n][dim * dim] (host, column-major), dim 2 or
+    // 3, cam5 [n][5].  The above, plus the selected inverse and k_lm_covariance into a scratch buffer for Sigma_ll (its
+    // own fail flag is ignored: a singular Hll counts only when a query names the landmark), then k_reprojection_cov.
+    bool reprojection_covariances(int n, const int32_t* ia, const int32_t* il, int dim, const double* cam5, double* cov);
     void clear_covariances();
     int covariances_held() const { return cov_what_; } // bit 0 poses, bit 1 landmarks
     const std::vector<double>& cov_pose() const { return cov_pose_; }
@@ -258,6 +270,10 @@ public:
 private:
     void check_covariance_call(const char* who) const; // throws on plan-only, sharded and fp32-internal optimisers
     void queue_covariance_system();                    // build pass at lambda = 0, Schur complement, factorisation
+    // queue_covariance_system(), the plan of the queries (qp, ql: free indices or -1), its pose blocks and
+    // k_pose_lm_cross; `extra` rides behind the index arrays on the device.  off[6]: where q_pose, q_lm, q_ptr, q_slot,
+    // q_aa and extra start in the index buffer.  false: a zero pivot
+    bool queue_pose_lm_cross(int n, const int32_t* qp, const int32_t* ql, const std::vector<int32_t>& extra, size_t off[6]);
     void build_structure(); // by device_structure() or host_structure(); both end in adopt_structure()
     bool device_structure(InitLaps& laps);
     void host_structure(InitLaps& laps);

@@ -915,6 +915,73 @@ bool CudaGraphOptimisationImpl::poseCrossCovariances(int n, const BaseVertex* co
     return engine_->pose_cross_covariances(n, ia.data(), ib.data(), cov36);
 }
 
+// what the two pose-landmark calls refuse, and the indices of their vertices in the flattening (fixed vertices keep
+// theirs: behind the free ones)
+void CudaGraphOptimisationImpl::poseLandmarkIndices(const char* who, int n, const BaseVertex* const* poses,
+                                                    const BaseVertex* const* landmarks, std::vector<int32_t>& ia,
+                                                    std::vector<int32_t>& il) const
+{
+    const std::string w = std::string("cugo: ") + who;
+    if (!initialized_)
+        throw std::runtime_error(w + "() needs initialize() first");
+    if (options.planOnly)
+        throw std::runtime_error(w + "(): this optimiser is plan-only (no HIP device in use)");
+    if (options.useFloat32)
+        throw std::runtime_error(w + "() is not available in the fp32-internal mode");
+    if (n < 0)
+        throw std::invalid_argument(w + "(): negative count");
+    if (n > 0 && (!poses || !landmarks))
+        throw std::invalid_argument(w + "(): null argument");
+    for (BaseVertexSet* vs : vertexSets)
+        if (!flattenedUnchanged(vs))
+            throw std::runtime_error(w + "(): a vertex set changed since initialize() (vertex added, removed or fixed / "
+                                         "freed); call initialize() again");
+    ia.resize((size_t)n), il.resize((size_t)n);
+    for (int k = 0; k < n; k++)
+    {
+        const BaseVertex *p = poses[k], *l = landmarks[k];
+        if (!p || p->isMarginilised() || !flattenedUnchanged(p->ownerSet()) || p->getIndex() < 0)
+            throw std::invalid_argument(w + "(): a vertex is not a pose of the current flattening");
+        if (!l || !l->isMarginilised() || !flattenedUnchanged(l->ownerSet()) || l->getIndex() < 0)
+            throw std::invalid_argument(w + "(): a vertex is not a landmark of the current flattening");
+        ia[k] = p->getIndex(), il[k] = l->getIndex();
+    }
+}
+
+bool CudaGraphOptimisationImpl::poseLandmarkCrossCovariances(int n, const BaseVertex* const* poses,
+                                                             const BaseVertex* const* landmarks, double* cov18)
+{
+    std::vector<int32_t> ia, il;
+    poseLandmarkIndices("poseLandmarkCrossCovariances", n, poses, landmarks, ia, il);
+    if (n > 0 && !cov18)
+        throw std::invalid_argument("cugo: poseLandmarkCrossCovariances(): null argument");
+    // free index, -1 for a fixed vertex
+    for (int k = 0; k < n; k++)
+    {
+        if (poses[k]->isFixed() || ia[k] >= engine_->n_poses_free())
+            ia[k] = -1;
+        if (landmarks[k]->isFixed() || il[k] >= engine_->n_landmarks_free())
+            il[k] = -1;
+    }
+    return engine_->pose_landmark_cross_covariances(n, ia.data(), il.data(), cov18);
+}
+
+bool CudaGraphOptimisationImpl::reprojectionCovariances(int n, const BaseVertex* const* poses,
+                                                        const BaseVertex* const* landmarks, int dim, const double* cam5,
+                                                        int nCams, double* cov)
+{
+    std::vector<int32_t> ia, il;
+    poseLandmarkIndices("reprojectionCovariances", n, poses, landmarks, ia, il);
+    if (dim != 2 && dim != 3)
+        throw std::invalid_argument("cugo: reprojectionCovariances(): dim must be 2 (mono) or 3 (stereo)");
+    if (n > 0 && (!cam5 || !cov || (nCams != 1 && nCams != n)))
+        throw std::invalid_argument("cugo: reprojectionCovariances(): cam5 must hold one camera or one per query");
+    std::vector<double> cams(5 * (size_t)n);
+    for (int k = 0; k < n; k++)
+        std::copy(cam5 + 5 * (size_t)(nCams == 1 ? 0 : k), cam5 + 5 * (size_t)(nCams == 1 ? 0 : k) + 5, cams.begin() + 5 * (size_t)k);
+    return engine_->reprojection_covariances(n, ia.data(), il.data(), dim, cams.data(), cov);
+}
+
 bool CudaGraphOptimisationImpl::landmarkCovariance(const BaseVertex* v, double cov[9]) const
 {
     if (!(engine_->covariances_held() & 2) || !v || !v->isMarginilised() || !flattenedUnchanged(v->ownerSet()))

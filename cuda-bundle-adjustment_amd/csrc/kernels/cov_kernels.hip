@@ -27,8 +27,13 @@
 // Landmarks (k_lm_covariance): with Hll = L L^T and G_e = Hpl_e L^-T of the landmark's free-pose edges,
 //   Sigma_l = L^-T (I + sum_{e,f} G_e^T Sigma_{p(e) p(f)} G_f) L^-1,
 // one thread per landmark, the pose blocks looked up in the upper block CSR of Hsc.
+//
+// Pose-landmark blocks (k_pose_lm_cross), with the same L and G_e: Sigma_al = -(sum_e Sigma_{a p(e)} G_e) L^-1, and the
+// covariance of a reprojection from them (k_reprojection_cov): J Sigma J^T over the joint [a; l] block.  One thread per
+// query, the pose blocks handed in by index (csrc/host/plcov_plan.h).
 #include <algorithm>
 
+#include "ba_math.h"
 #include "kernels.h"
 
 namespace
@@ -458,6 +463,190 @@ __global__ __launch_bounds__(256) void k_lm_covariance(int L, const int32_t* __r
         }
 }
 
+// Pose-landmark blocks: Sigma_al = -(sum_e Sigma_{a p(e)} G_e) L^-1 over the counted slots e of landmark l in slot
+// order, one thread per query.  Query q: q_pose[q] / q_lm[q] are the free indices of a and l, -1 for a fixed vertex
+// (18 zeros; of a free landmark under a fixed pose Hll alone is read, for the flag); its slot k reads the block
+// blocks[q_slot[q_ptr[q] + k]] (6 x 6 column-major, rows a).
+// Every index into acc, g and li is a compile-time constant (the loops are unrolled), so all of it lives in registers.
+__global__ __launch_bounds__(256) void k_pose_lm_cross(int n, const int32_t* __restrict__ q_pose,
+                                                       const int32_t* __restrict__ q_lm, const int32_t* __restrict__ q_ptr,
+                                                       const int32_t* __restrict__ q_slot, const int32_t* __restrict__ lm_ptr,
+                                                       const uint8_t* __restrict__ flags, const double* __restrict__ Hll,
+                                                       const double* __restrict__ Hpl, const double* __restrict__ blocks,
+                                                       double* __restrict__ out, int32_t* __restrict__ fail)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n)
+        return;
+    double* o = out + 18L * q;
+    const int l = q_lm[q];
+    double li[3][3];
+    bool ok = l >= 0;
+    if (ok && !chol3_inv(Hll + 9L * l, li)) // (a free landmark is factored under a fixed pose too: the flag is about it)
+    {
+        *fail = 1; // (every writer stores the same value)
+        ok = false;
+    }
+    ok = ok && q_pose[q] >= 0;
+    if (!ok)
+    {
+#pragma unroll
+        for (int k = 0; k < 18; k++)
+            o[k] = 0.0;
+        return;
+    }
+    double acc[6][3];
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            acc[r][c] = 0.0;
+    const int s0 = q_ptr[q], ns = q_ptr[q + 1] - s0, e0 = lm_ptr[l];
+    for (int k = 0; k < ns; k++)
+    {
+        if (flags[e0 + k] & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P | CUGO_EDGE_INACTIVE))
+            continue;
+        double g[6][3];
+        lm_g(Hpl + 18L * (e0 + k), li, g);
+        const double* __restrict__ S = blocks + 36L * q_slot[s0 + k];
+#pragma unroll
+        for (int j = 0; j < 6; j++) // acc += S[:, j] g[j, :], column by column of the block
+#pragma unroll
+            for (int r = 0; r < 6; r++)
+            {
+                const double s = S[r + 6 * j];
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                    acc[r][c] += s * g[j][c];
+            }
+    }
+    // -(acc L^-1): [r][c] = -sum_{k >= c} acc[r][k] Linv[k][c]
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+        {
+            double s = acc[r][c] * li[c][c];
+#pragma unroll
+            for (int k = c + 1; k < 3; k++)
+                s += acc[r][k] * li[k][c];
+            o[r + 6 * c] = -s;
+        }
+}
+
+// Covariance of the reprojection of landmark l in pose a at the current estimates, S = J Sigma J^T over the joint
+// [a; l] block with J = [J_p J_l] of ba_math.h, one thread per query:
+//   S = J_p Sigma_aa J_p^T + X + X^T + J_l Sigma_ll J_l^T,   X = J_p Sigma_al J_l^T.
+// q_pose / q_lm: indices into poses [.][7] / lms [.][3] (fixed vertices included); q_aa: the block of Sigma_aa in
+// `blocks`, -1 for a fixed pose (the terms with J_p go); a landmark index >= Lfree is a fixed landmark (the terms with
+// J_l go).  cross [n][18] (k_pose_lm_cross), lmcov [Lfree][9] (k_lm_covariance).  out [n][9]: the lower triangle,
+// mirrored; the third row and column are zero for dim 2.
+__global__ __launch_bounds__(256) void k_reprojection_cov(int n, int Lfree, const int32_t* __restrict__ q_pose,
+                                                          const int32_t* __restrict__ q_lm, const int32_t* __restrict__ q_dim,
+                                                          const int32_t* __restrict__ q_aa, const double* __restrict__ cam5,
+                                                          const double* __restrict__ poses, const double* __restrict__ lms,
+                                                          const double* __restrict__ blocks, const double* __restrict__ cross,
+                                                          const double* __restrict__ lmcov, double* __restrict__ out)
+{
+    using namespace cugo_dev;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n)
+        return;
+    const double* __restrict__ pose = poses + 7L * q_pose[q];
+    const int l = q_lm[q], aa = q_aa[q];
+    const double* __restrict__ cam = cam5 + 5L * q;
+    const bool stereo = q_dim[q] == 3, free_p = aa >= 0, free_l = l < Lfree;
+    double Xc[3], JP[3][6], JL[3][3];
+    world_to_cam(pose, lms + 3L * l, Xc);
+    jac_pose(Xc, cam, stereo, JP);
+    jac_landmark(Xc, pose, cam, stereo, JL);
+    double S[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            S[i][j] = 0.0;
+    if (free_p)
+    {
+        // A = Sigma_aa J_p^T (6 x 3), then the lower triangle of J_p A
+        const double* __restrict__ Saa = blocks + 36L * aa;
+        double A[6][3];
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+            {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++)
+                    s += Saa[r + 6 * k] * JP[j][k];
+                A[r][j] = s;
+            }
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j <= i; j++)
+            {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++)
+                    s += JP[i][k] * A[k][j];
+                S[i][j] = s;
+            }
+    }
+    if (free_p && free_l)
+    {
+        // B = Sigma_al J_l^T (6 x 3), X = J_p B; S += X + X^T on the lower triangle
+        const double* __restrict__ Sal = cross + 18L * q;
+        double B[6][3], X[3][3];
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                B[r][j] = Sal[r] * JL[j][0] + Sal[r + 6] * JL[j][1] + Sal[r + 12] * JL[j][2];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+            {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++)
+                    s += JP[i][k] * B[k][j];
+                X[i][j] = s;
+            }
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j <= i; j++)
+                S[i][j] += X[i][j] + X[j][i];
+    }
+    if (free_l)
+    {
+        const double* __restrict__ Sll = lmcov + 9L * l;
+        double C[3][3]; // Sigma_ll J_l^T
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                C[r][j] = Sll[r] * JL[j][0] + Sll[r + 3] * JL[j][1] + Sll[r + 6] * JL[j][2];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j <= i; j++)
+                S[i][j] += JL[i][0] * C[0][j] + JL[i][1] * C[1][j] + JL[i][2] * C[2][j];
+    }
+    double* o = out + 9L * q;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+        {
+            const int rr = i > j ? i : j, cc = i > j ? j : i; // (the lower triangle, mirrored: exactly symmetric)
+            o[i + 3 * j] = (!stereo && rr == 2) ? 0.0 : S[rr][cc];
+        }
+}
+
 // out[p] = the diagonal block of pose p: the first block of row p of the upper block CSR
 __global__ __launch_bounds__(256) void k_cov_pose_diag(int P, const int32_t* __restrict__ rowptr,
                                                        const double* __restrict__ sigma, double* __restrict__ out)
@@ -651,6 +840,27 @@ void launch_lm_covariance(hipStream_t s, int L, const int32_t* d_lm_ptr, const i
         return;
     CUGO_LAUNCH(k_lm_covariance, dim3((L + 255) / 256), dim3(256), 0, s, L, d_lm_ptr, d_e_pose, d_flags, d_Hll, d_Hpl,
                 d_rowptr, d_colind, d_sigma, d_out, d_fail);
+}
+
+void launch_pose_lm_cross(hipStream_t s, int n, const int32_t* d_q_pose, const int32_t* d_q_lm, const int32_t* d_q_ptr,
+                          const int32_t* d_q_slot, const int32_t* d_lm_ptr, const uint8_t* d_flags, const double* d_Hll,
+                          const double* d_Hpl, const double* d_blocks, double* d_out, int32_t* d_fail)
+{
+    if (n <= 0)
+        return;
+    CUGO_LAUNCH(k_pose_lm_cross, dim3((n + 255) / 256), dim3(256), 0, s, n, d_q_pose, d_q_lm, d_q_ptr, d_q_slot, d_lm_ptr,
+                d_flags, d_Hll, d_Hpl, d_blocks, d_out, d_fail);
+}
+
+void launch_reprojection_cov(hipStream_t s, int n, int Lfree, const int32_t* d_q_pose, const int32_t* d_q_lm,
+                             const int32_t* d_q_dim, const int32_t* d_q_aa, const double* d_cam5, const double* d_poses,
+                             const double* d_lms, const double* d_blocks, const double* d_cross, const double* d_lmcov,
+                             double* d_out)
+{
+    if (n <= 0)
+        return;
+    CUGO_LAUNCH(k_reprojection_cov, dim3((n + 255) / 256), dim3(256), 0, s, n, Lfree, d_q_pose, d_q_lm, d_q_dim, d_q_aa,
+                d_cam5, d_poses, d_lms, d_blocks, d_cross, d_lmcov, d_out);
 }
 
 } // namespace cugo_k

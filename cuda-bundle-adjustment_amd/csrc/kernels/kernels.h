@@ -435,5 +435,18 @@ void launch_cov_pose_diag(hipStream_t s, int P, const int32_t* d_rowptr, const d
 void launch_lm_covariance(hipStream_t s, int L, const int32_t* d_lm_ptr, const int32_t* d_e_pose,
                           const uint8_t* d_flags, const double* d_Hll, const double* d_Hpl, const int32_t* d_rowptr,
                           const int32_t* d_colind, const double* d_sigma, double* d_out, int32_t* d_fail);
+// Sigma_al [n][18] (6 x 3 column-major, rows a) of n queries (d_q_pose / d_q_lm: free indices, -1 for a fixed vertex: 18
+// zeros): slot k of the query's landmark reads the block d_blocks[d_q_slot[d_q_ptr[q] + k]] ([.][36], column-major, rows
+// a; csrc/host/plcov_plan.h); *d_fail = 1 if the Hll of a queried landmark is not positive definite (18 zeros)
+void launch_pose_lm_cross(hipStream_t s, int n, const int32_t* d_q_pose, const int32_t* d_q_lm, const int32_t* d_q_ptr,
+                          const int32_t* d_q_slot, const int32_t* d_lm_ptr, const uint8_t* d_flags, const double* d_Hll,
+                          const double* d_Hpl, const double* d_blocks, double* d_out, int32_t* d_fail);
+// S [n][9] (3 x 3 column-major) = J Sigma J^T of the reprojection of landmark d_q_lm[q] in pose d_q_pose[q] (indices into
+// d_lms / d_poses, fixed vertices included; d_q_aa: the block of Sigma_aa in d_blocks, -1 for a fixed pose; a landmark
+// index >= Lfree is fixed); d_cross: what launch_pose_lm_cross wrote, d_lmcov: what launch_lm_covariance wrote
+void launch_reprojection_cov(hipStream_t s, int n, int Lfree, const int32_t* d_q_pose, const int32_t* d_q_lm,
+                             const int32_t* d_q_dim, const int32_t* d_q_aa, const double* d_cam5, const double* d_poses,
+                             const double* d_lms, const double* d_blocks, const double* d_cross, const double* d_lmcov,
+                             double* d_out);
 
 } // namespace cugo_k

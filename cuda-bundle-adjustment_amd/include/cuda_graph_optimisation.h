@@ -5,6 +5,7 @@
 #pragma once
 #include <cassert>
 #include <cmath>
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <string>
@@ -184,8 +185,26 @@ public:
      *  computeMarginals runs up to the factorisation and leaves the marginals stored by it untouched.  false: a zero
      *  pivot.  Throws as computeMarginals does, and for a vertex that is not a pose of the current flattening. */
     bool poseCrossCovariances(int n, const BaseVertex* const* a, const BaseVertex* const* b, double* cov36);
+    /** pose-landmark blocks of the covariance (g2o computeMarginals / Ceres Covariance with mixed pairs): cov18
+     *  [n][18], block k is Sigma_al of (poses[k], landmarks[k]) at the current estimates, 6x3 column-major with the rows
+     *  in the tangent order of poseCovariance; zero where either vertex is fixed.  The pair needs no edge.  With
+     *  poseCovariance and landmarkCovariance this gives the joint covariance of a camera and a map point.  The contract
+     *  of poseCrossCovariances; false also when the Hll of a QUERIED landmark is not positive definite (a free landmark
+     *  without an active edge) — other landmarks in that state do not matter. */
+    bool poseLandmarkCrossCovariances(int n, const BaseVertex* const* poses, const BaseVertex* const* landmarks,
+                                      double* cov18);
+    /** covariance of the predicted reprojection of landmarks[k] in poses[k]: S = J Sigma J^T over the joint [pose;
+     *  landmark] block with the Jacobians of the projection — the search ellipse of guided matching, the denominator
+     *  of a normalised-innovation test.  cov [n][dim * dim] column-major, dim 2 (mono: u, v) or 3 (stereo: u, v,
+     *  u_right); cam5 [nCams][5] = fx, fy, cx, cy, bf with nCams 1 (one camera for all) or n.  A fixed pose contributes
+     *  no pose terms, a fixed landmark no landmark terms.  Contract and return value as above; throws
+     *  std::invalid_argument for another dim or nCams. */
+    bool reprojectionCovariances(int n, const BaseVertex* const* poses, const BaseVertex* const* landmarks, int dim,
+                                 const double* cam5, int nCams, double* cov);
 
 private:
+    void poseLandmarkIndices(const char* who, int n, const BaseVertex* const* poses, const BaseVertex* const* landmarks,
+                             std::vector<int32_t>& ia, std::vector<int32_t>& il) const;
     bool verbose = false;
     bool shouldProfile_ = false;
     GraphOptimisationOptions options;

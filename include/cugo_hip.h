@@ -245,6 +245,60 @@ int cugo_chol_inverse_blocks(cugo_chol* s, int n_pairs, const int32_t* h_rows, c
 int cugo_landmark_covariances(cugo_ctx* ctx, const cugo_edges* ev, const cugo_hsc_struct* hs, const double* d_Hll,
                               const double* d_Hpl, const double* d_sigma, double* d_cov9 /* [9 * n_landmarks_free] */,
                               int32_t* d_fail);
+/* Extension (g2o computeMarginals(spinv, blockIndices) / Ceres Covariance with mixed pairs): the pose-landmark blocks
+ * of the covariance.  With Sigma_pp the pose covariance, Hll_l = L L^T and G_e = Hpl_e L^-T as above,
+ *   Sigma_al = -(sum_e Sigma_{a p(e)} G_e) L^-1                              (6x3, column-major, rows a),
+ * e over the counted slots of landmark l (as for cugo_landmark_covariances) in slot order.
+ *
+ * The plan of a batch of n queries (host only, no device needed).  h_lm_ptr [n_landmarks + 1] and h_slot_pose (the pose
+ * index of every edge slot, landmark-major slot order; an index >= n_poses_free is a fixed pose) are those of the
+ * flattened edges; query k is (h_q_pose[k], h_q_lm[k]): a free pose index, or -1 for a fixed pose, and a free landmark
+ * index, or -1.  Named int32 arrays of the plan (cugo_plcov_plan_array returns the length or a negative error; the
+ * pointer is valid until the plan is destroyed):
+ *   "rows", "cols"   the distinct pose pairs to hand to cugo_chol_inverse_blocks, in the order of their first use:
+ *                    (a, p(e)) for every slot of a query's landmark whose pose is free (whether or not the slot counts:
+ *                    the kernel decides by flag), and (a, a) once per distinct free a.  One pose against every landmark
+ *                    of a map gives at most n_poses_free + 1 pairs;
+ *   "q_ptr" [n + 1], "q_slot"   per query one entry per slot of its landmark, in slot order: the index of the block
+ *                    Sigma_{a p(e)} in that list, -1 for a slot on a fixed pose; an empty range for a query with a fixed
+ *                    pose or a fixed landmark;
+ *   "q_aa" [n]       the index of Sigma_aa, -1 for a fixed pose.
+ * CUGO_ERR_INVALID for a null argument that is needed, a negative count or an index out of range. */
+typedef struct cugo_plcov_plan cugo_plcov_plan;
+int cugo_plcov_plan_create(int n_poses_free, int n_landmarks, const int32_t* h_lm_ptr, const int32_t* h_slot_pose, int n,
+                           const int32_t* h_q_pose, const int32_t* h_q_lm, cugo_plcov_plan** out);
+int cugo_plcov_plan_array(const cugo_plcov_plan* plan, const char* name, const int32_t** out);
+void cugo_plcov_plan_destroy(cugo_plcov_plan* plan);
+/* d_cov18 [n][18] = Sigma_al of the n queries (d_q_pose, d_q_lm, d_q_ptr, d_q_slot: device copies of the query lists and
+ * of the plan's arrays).  d_blocks [.][36]: the blocks of the plan's pair list, each 6x6 column-major with rows a, as
+ * cugo_chol_inverse_blocks writes them; only the blocks that counted slots refer to are read.  d_Hll, d_Hpl, ev as for
+ * cugo_landmark_covariances (ev->d_lm_ptr and ev->d_flags are read; of a slot that does not count only the flag).
+ * A query with a fixed vertex (an index of -1) gets 18 zeros: its range in d_q_slot is empty and no block is read.
+ * d_fail[0] (int32, device) is zeroed here and set to 1 by every query whose free landmark's Hll has a pivot <= 0 or a
+ * NaN in its 3x3 Cholesky factorisation (under a fixed pose too: the flag is about the landmark): that query gets 18
+ * zeros, every other query is as without it.  A landmark that factors and has no counted slot gives zeros and no
+ * failure.  Asynchronous on the context's stream; one thread per query, no atomics:
+ * the same bits on every call.  CUGO_ERR_INVALID for a null argument, n < 0 or ev->block_f32; CUGO_OK with nothing
+ * launched (the flag untouched) when n == 0. */
+int cugo_pose_landmark_cross_covariances(cugo_ctx* ctx, const cugo_edges* ev, int n, const int32_t* d_q_pose,
+                                         const int32_t* d_q_lm, const int32_t* d_q_ptr, const int32_t* d_q_slot,
+                                         const double* d_Hll, const double* d_Hpl, const double* d_blocks,
+                                         double* d_cov18, int32_t* d_fail);
+/* Covariance of the predicted reprojection of landmark l in pose a at the estimates d_poses / d_lms:
+ *   S = J_p Sigma_aa J_p^T + J_p Sigma_al J_l^T + (J_p Sigma_al J_l^T)^T + J_l Sigma_ll J_l^T
+ * with the Jacobians of the projection as the build pass forms them (left update, tangent order [rotation,
+ * translation]); no edge between a and l is needed.  Per query: d_q_pose / d_q_lm index d_poses [.][7] / d_lms [.][3]
+ * (fixed vertices included); d_q_dim is 2 (mono) or 3 (stereo); d_cam5 [n][5] = fx, fy, cx, cy, bf; d_q_aa is the index
+ * of Sigma_aa in d_blocks (the plan's "q_aa"), -1 for a fixed pose: the three terms with J_p go; a landmark index
+ * >= n_landmarks_free is a fixed landmark: the terms with J_l go.  d_cross18 [n][18]: what
+ * cugo_pose_landmark_cross_covariances wrote for the same queries; d_lmcov9 [n_landmarks_free][9]: what
+ * cugo_landmark_covariances wrote.  d_cov9 [n][9]: 3x3 column-major, exactly symmetric (the lower triangle, mirrored);
+ * for dim 2 the third row and column are zero.  Asynchronous, one thread per query.  CUGO_ERR_INVALID for a null
+ * argument or a negative count; CUGO_OK with nothing launched when n == 0. */
+int cugo_reprojection_covariances(cugo_ctx* ctx, int n, int n_landmarks_free, const int32_t* d_q_pose,
+                                  const int32_t* d_q_lm, const int32_t* d_q_dim, const int32_t* d_q_aa,
+                                  const double* d_cam5, const double* d_poses, const double* d_lms,
+                                  const double* d_blocks, const double* d_cross18, const double* d_lmcov9, double* d_cov9);
 /* statistics of the analysis: nnz(L) in scalars, factorisation flops, #supernodes, #stages */
 int cugo_chol_stats(const cugo_chol* s, double* nnzL, double* flops, int* n_supernodes,
                     int* n_stages, double* front_bytes);
@@ -743,6 +797,24 @@ int cugo_graph_compute_pose_cross_covariances(cugo_graph* g, int n, const int32_
  * edge that summarises the graph between a and b.  CUGO_ERR_INVALID for a == b. */
 int cugo_graph_relative_pose_covariances(cugo_graph* g, int n, const int32_t* ids_a, const int32_t* ids_b,
                                          double* cov36);
+/* Extension: the pose-landmark blocks Sigma_al of the pairs (pose_ids[k], lm_ids[k]) — any pairs, with or without an
+ * edge — at the current estimates: cov18 [n][18] (host), 6x3 column-major, rows in the tangent order above; zeros where
+ * the pose or the landmark is fixed.  One build pass at lambda = 0, Schur complement and factorisation as above, then
+ * cugo_chol_inverse_blocks for the pose pairs the queries need and cugo_pose_landmark_cross_covariances; only the
+ * results travel to the host.  CUGO_ERR_NUMERIC on a zero pivot or when the Hll of a QUERIED landmark is not positive
+ * definite (a free landmark without an active edge); other landmarks in that state do not matter.  CUGO_ERR_INVALID for
+ * an id that is not a vertex of the current flattening, before initialize(), on plan-only, sharded or fp32-internal
+ * graphs.  Leaves the estimates, the LM state and the kept marginals alone. */
+int cugo_graph_compute_pose_landmark_cross_covariances(cugo_graph* g, int n, const int32_t* pose_ids,
+                                                       const int32_t* lm_ids, double* cov18);
+/* the covariance S = J Sigma J^T of the predicted reprojection of landmark lm_ids[k] in pose pose_ids[k] over the joint
+ * [pose; landmark] block (the search ellipse of guided matching, the denominator of a normalised-innovation test):
+ * cov [n][dim*dim] (host), column-major, dim = 2 (mono: u, v) or 3 (stereo: u, v, u_right).  cam5 [n][5] = fx, fy, cx,
+ * cy, bf per query, or NULL for the camera set with cugo_graph_set_camera(g, dim, ...).  A fixed pose contributes no
+ * pose terms, a fixed landmark no landmark terms; both fixed gives zeros.  Error codes as above; also CUGO_ERR_INVALID
+ * for dim outside {2, 3}. */
+int cugo_graph_reprojection_covariances(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* lm_ids, int dim,
+                                        const double* cam5, double* cov);
 /* per-phase milliseconds accumulated since initialize(): ref getTimeProfile
  * (block_solver.cpp:470-488).  names is a '\n' separated list written into buf. */
 int cugo_graph_time_profile(cugo_graph* g, char* names_buf, int buf_len, double* ms, int cap);
