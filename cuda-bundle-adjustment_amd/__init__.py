@@ -148,6 +148,21 @@ def lib():
         _lib.cugo_graph_compute_pose_landmark_cross_covariances.restype = C.c_int
         _lib.cugo_graph_reprojection_covariances.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int, _f64p, _f64p]
         _lib.cugo_graph_reprojection_covariances.restype = C.c_int
+        # the fused iteration at kernel level (cugo_hip.h); device pointers as c_void_p, None = NULL
+        # (ctx, ev, h_lm_ptr, d_poses, d_lms, rk, lambda, form, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl, d_invHll, d_T, d_lmrec, d_chi)
+        _lib.cugo_construct_quadratic_form_fused.argtypes = ([C.c_void_p, C.POINTER(Edges), _i32p, C.c_void_p, C.c_void_p,
+                                                              Robust, C.c_double, C.c_int] + [C.c_void_p] * 9)
+        _lib.cugo_construct_quadratic_form_fused.restype = C.c_int
+        # (ctx, ev, hs, lambda, damp_hsc_diag, form, d_poses, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl, d_invHll, d_T, d_lmrec,
+        #  d_bp_out, d_bsc, d_Hsc)
+        _lib.cugo_compute_schur_fused.argtypes = ([C.c_void_p, C.POINTER(Edges), C.POINTER(HscStruct), C.c_double, C.c_int,
+                                                   C.c_int] + [C.c_void_p] * 12)
+        _lib.cugo_compute_schur_fused.restype = C.c_int
+        # (ctx, ev, lambda, d_lmrec, d_bl, d_bp, d_G, d_xp, d_xl, d_poses_in, d_lms_in, d_poses_out, d_lms_out, d_scale,
+        #  from_records)
+        _lib.cugo_backsubst_update_fused.argtypes = ([C.c_void_p, C.POINTER(Edges), C.c_double] + [C.c_void_p] * 11 +
+                                                     [C.c_int])
+        _lib.cugo_backsubst_update_fused.restype = C.c_int
     return _lib
 
 

@@ -671,6 +671,108 @@ int cugo_backsubst_update(cugo_ctx* ctx, const cugo_edges* ev, double lambda,
     });
 }
 
+// ---------------------------------------------------------------- fused iteration ------
+// The forms of the three passes that the LM loop runs from its second iteration on (engine.cpp: queue_build, queue_schur
+// and the update of a trial), through the same launchers.  Every argument is checked before the context is touched.
+int cugo_construct_quadratic_form_fused(cugo_ctx* ctx, const cugo_edges* ev, const int32_t* h_lm_ptr, const double* d_poses,
+                                        const double* d_lms, cugo_robust rk, double lambda, int form, double* d_Hpp,
+                                        double* d_bp, double* d_Hll, double* d_bl, void* d_Hpl, double* d_invHll,
+                                        void* d_T, double* d_lmrec, double* d_chi)
+{
+    return guarded([&] {
+        const char* who = "cugo_construct_quadratic_form_fused: ";
+        auto refuse = [&](const char* what) { throw std::runtime_error(std::string(who) + what); };
+        if (!ev || !h_lm_ptr)
+            refuse("null ev or h_lm_ptr");
+        if (form != 1 && form != 2)
+            refuse("form must be 1 (two-stream) or 2 (one-stream)");
+        if (!(lambda >= 0.0) || !std::isfinite(lambda))
+            refuse("lambda must be finite and >= 0");
+        if (!d_invHll || !d_T || !d_Hll || !d_bl)
+            refuse("null d_invHll, d_T, d_Hll or d_bl (d_invHll is the launcher's fuse switch in either form)");
+        if (form == 2 && !d_lmrec)
+            refuse("form 2 needs d_lmrec");
+        if (form == 1 && (!d_Hpl || (ev->n_poses_free > 0 && (!d_Hpp || !d_bp))))
+            refuse("form 1 needs d_Hpl, d_Hpp and d_bp");
+        // what the engine's slot layout guarantees and the fused kernel relies on: a landmark's slots in one group
+        for (int l = 0; l < ev->n_landmarks_total; l++)
+        {
+            const int a = h_lm_ptr[l], b = h_lm_ptr[l + 1];
+            if (a < 0 || b < a || b > ev->n_edges)
+                refuse("h_lm_ptr is not a slot range list of ev");
+            if (b > a && a / 256 != (b - 1) / 256)
+                refuse("a landmark's edge slots lie in two 256-slot groups");
+        }
+        if (!ctx)
+            refuse("null context");
+        cugo_k::launch_build(ctx->stream, *ev, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl, scratch_for(ctx, ev),
+                             d_chi, lambda, d_invHll, d_T, form == 2 ? d_lmrec : nullptr, form == 2);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_compute_schur_fused(cugo_ctx* ctx, const cugo_edges* ev, const cugo_hsc_struct* hs, double lambda,
+                             int damp_hsc_diag, int form, const double* d_poses, const double* d_Hpp, const double* d_bp,
+                             const double* d_Hll, const double* d_bl, const void* d_Hpl, double* d_invHll, void* d_T,
+                             const double* d_lmrec, double* d_bp_out, double* d_bsc, double* d_Hsc)
+{
+    return guarded([&] {
+        const char* who = "cugo_compute_schur_fused: ";
+        auto refuse = [&](const char* what) { throw std::runtime_error(std::string(who) + what); };
+        if (!ev || !hs)
+            refuse("null ev or hs");
+        if (form != 1 && form != 2)
+            refuse("form must be 1 (two-stream) or 2 (one-stream)");
+        if (!(lambda >= 0.0) || !std::isfinite(lambda))
+            refuse("lambda must be finite and >= 0");
+        if (hs->d_grp_ptr)
+            refuse("hs carries a landmark-major plan: the fused forms run the gather kernels");
+        if (!d_T || !d_bsc || !d_Hsc)
+            refuse("null d_T, d_bsc or d_Hsc");
+        if (form == 2 && (!d_lmrec || !d_poses || !d_bp_out || !hs->d_rowptr))
+            refuse("form 2 needs d_lmrec, d_poses, d_bp_out and hs->d_rowptr");
+        if (form == 1 && (!d_Hpl || !d_bl || (ev->n_poses_free > 0 && (!d_Hpp || !d_bp))))
+            refuse("form 1 needs d_Hpl, d_bl, d_Hpp and d_bp");
+        if (!ctx)
+            refuse("null context");
+        cugo_k::SchurRows rows;
+        rows.mfma = ctx->opt.hsc_mfma, rows.xcd = ctx->opt.hsc_xcd;
+        if (form == 2)
+        {
+            rows.d_lmrec = d_lmrec, rows.d_poses = d_poses, rows.d_bp_out = d_bp_out;
+            rows.rs = scratch_for(ctx, ev); // the records of the fused build entry: same ev, same size, no resize
+        }
+        cugo_k::launch_schur(ctx->stream, *ev, *hs, lambda, damp_hsc_diag, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl, d_invHll, d_T,
+                             d_bsc, d_Hsc, true, rows);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_backsubst_update_fused(cugo_ctx* ctx, const cugo_edges* ev, double lambda, const double* d_lmrec,
+                                const double* d_bl, const double* d_bp, const void* d_G, const double* d_xp, double* d_xl,
+                                const double* d_poses_in, const double* d_lms_in, double* d_poses_out, double* d_lms_out,
+                                double* d_scale, int from_records)
+{
+    return guarded([&] {
+        const char* who = "cugo_backsubst_update_fused: ";
+        auto refuse = [&](const char* what) { throw std::runtime_error(std::string(who) + what); };
+        if (!ev)
+            refuse("null ev");
+        if (!(lambda >= 0.0) || !std::isfinite(lambda))
+            refuse("lambda must be finite and >= 0");
+        if (!d_lmrec)
+            refuse(from_records ? "from_records without the landmarks' lines (d_lmrec)" : "null d_lmrec");
+        if (!d_G || !d_bl || !d_bp || !d_xp || !d_xl || !d_poses_in || !d_lms_in || !d_poses_out || !d_lms_out)
+            refuse("null argument");
+        if (!ctx)
+            refuse("null context");
+        cugo_k::launch_backsubst_update(ctx->stream, *ev, lambda, lambda, nullptr, d_bl, d_bp, d_G, d_xp, d_xl, d_poses_in,
+                                        d_lms_in, d_poses_out, d_lms_out, scratch_for(ctx, ev), d_scale, d_lmrec,
+                                        from_records != 0);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
 // ---------------------------------------------------------------- sparse LL^T ----------
 int cugo_chol_create(cugo_ctx* ctx, cugo_chol** out)
 {

@@ -331,6 +331,50 @@ int cugo_backsubst_update(cugo_ctx* ctx, const cugo_edges* ev, double lambda,
                           const double* d_poses_in, const double* d_lms_in, double* d_poses_out,
                           double* d_lms_out, double* d_scale);
 
+/* ---- the fused iteration at kernel level (DESIGN.md sections 4c / 4d) -------------------
+ * The three passes in the forms the LM loop runs from its second iteration on, when the damping of the first trial is
+ * known before the build pass is queued.  Call them in this order with the same ctx, ev, lambda and arrays.
+ * form 1, two streams: the build pass also leaves d_invHll = (Hll + lambda I)^-1 and d_T = Hpl invHll, the bits
+ *   cugo_compute_schur would form from the Hll and Hpl written here; every output of cugo_construct_quadratic_form is
+ *   written as well.
+ * form 2, one stream: with Hll + lambda I = L L^T per free landmark (a pivot that is not positive gives NaNs),
+ *   d_Hll, d_bl, d_chi as in form 1;
+ *   d_lmrec [Lfree][16]: the landmark's line {L^-1 (0,0) (1,0) (1,1) (2,0) (2,1) (2,2), y = L^-1 bl (3), 7 unused},
+ *     written by the landmark's first edge slot: the line of a free landmark without any slot is left untouched;
+ *   d_T [E][18] = G = Hpl L^-T (zero blocks for slots that are inactive or have a fixed endpoint);
+ *   d_Hpp, d_bp, d_Hpl and d_invHll are NOT written (d_invHll must still be non-NULL; the others may be NULL).
+ * The build pass also leaves one 64-byte record per edge slot in the context's scratch.  cugo_compute_schur_fused
+ * (form 2) and cugo_backsubst_update_fused (from_records) read them: the records are valid from
+ * cugo_construct_quadratic_form_fused until the next call on this context that is not one of these three entries, and
+ * they belong to the ev, d_poses and lambda of that call; the caller vouches for this, nothing checks it.
+ * h_lm_ptr: HOST copy of ev->d_lm_ptr [n_landmarks_total + 1].  CUGO_ERR_INVALID, with nothing launched, for
+ * lambda < 0, an unknown form, a null array the form needs, or a landmark whose slots lie in two 256-slot groups (the
+ * fused kernel sums a landmark inside one workgroup; the engine pads its slot layout so that none does). */
+int cugo_construct_quadratic_form_fused(cugo_ctx* ctx, const cugo_edges* ev, const int32_t* h_lm_ptr,
+                                        const double* d_poses, const double* d_lms, cugo_robust rk, double lambda,
+                                        int form, double* d_Hpp, double* d_bp, double* d_Hll, double* d_bl, void* d_Hpl,
+                                        double* d_invHll, void* d_T, double* d_lmrec, double* d_chi);
+/* [Hsc | bsc] from what cugo_construct_quadratic_form_fused left for this lambda, by the gather kernels (CUGO_ERR_INVALID
+ * if *hs carries a landmark-major plan).  form 1: cugo_compute_schur without its edge pass (d_invHll and d_T are read,
+ * d_poses, d_lmrec and d_bp_out are not used).  form 2: the off-diagonal blocks are - sum G_i G_j^T with both operands
+ * from d_T; the diagonal blocks (+ lambda I with damp_hsc_diag), d_bp_out [Pfree][6] = bp and d_bsc come from the
+ * records, the lines d_lmrec and the poses d_poses the build pass linearised at; d_Hpp, d_bp, d_Hll, d_bl, d_Hpl and
+ * d_invHll are not read.  The off-diagonal kernel is the context's (CUGO_HSC_MFMA / CUGO_HSC_XCD when it was created).
+ * CUGO_ERR_INVALID, with nothing launched, for lambda < 0, an unknown form or a null array the form needs. */
+int cugo_compute_schur_fused(cugo_ctx* ctx, const cugo_edges* ev, const cugo_hsc_struct* hs, double lambda,
+                             int damp_hsc_diag, int form, const double* d_poses, const double* d_Hpp,
+                             const double* d_bp, const double* d_Hll, const double* d_bl, const void* d_Hpl,
+                             double* d_invHll, void* d_T, const double* d_lmrec, double* d_bp_out, double* d_bsc,
+                             double* d_Hsc);
+/* cugo_backsubst_update in the one-stream form: dx_l = L^-T (y - sum G_e^T dx_p) from the lines d_lmrec and d_G (what
+ * form 2 left in d_T); everything else as cugo_backsubst_update.  from_records != 0: G_e^T dx_p is re-formed from the
+ * records in the scratch, d_poses_in (which must be the poses of the build pass) and the lines instead of read from
+ * d_G — the same bits.  CUGO_ERR_INVALID, with nothing launched, for lambda < 0 or a null array (d_lmrec included). */
+int cugo_backsubst_update_fused(cugo_ctx* ctx, const cugo_edges* ev, double lambda, const double* d_lmrec,
+                                const double* d_bl, const double* d_bp, const void* d_G, const double* d_xp,
+                                double* d_xl, const double* d_poses_in, const double* d_lms_in, double* d_poses_out,
+                                double* d_lms_out, double* d_scale, int from_records);
+
 /*
  * Point-to-plane and point-to-line pose edges (the reference's include/icp_types.h: PlaneEdgeSet, LineEdgeSet):
  * unary edges on a pose.  With y = R(q) p + t (the pose read as the BA edges read it) and the left update in the

@@ -45,9 +45,10 @@ def _cameras(rng, n, n_small_w):
 
 
 def _assemble(rng, n_poses, n_landmarks, e_pose, e_lm, fixed_poses, fixed_landmarks, stereo_frac=0.5,
-              pix_noise=1.0, pose_noise=(0.01, 0.05), lm_noise=0.02):
+              pix_noise=1.0, pose_noise=(0.01, 0.05), lm_noise=0.02, cameras=None):
+    """cameras (optional): a function (rng, n, n_small_w) -> poses in place of _cameras"""
     n_small_w = max(2, n_poses // 8)
-    pose_gt = _cameras(rng, n_poses, n_small_w)
+    pose_gt = (cameras or _cameras)(rng, n_poses, n_small_w)
     lm_gt = rng.normal(0, 1.5, (n_landmarks, 3))
     nrm = np.linalg.norm(lm_gt, axis=1, keepdims=True)
     lm_gt *= np.minimum(1.0, 6.0 / np.maximum(nrm, 1e-30))   # inside a ball of radius 6: depth >= 15 - 6 - noise
@@ -321,6 +322,155 @@ def robust_kernels(name):
     import kernel_ref
     _, prob, f, _ = layout(name)
     x = np.asarray(kernel_ref.build(prob, (0, 1.0), f)["x"], np.float64)
+    delta = tukey_delta(x)
+    zero = float((x > delta * delta).mean())
+    assert zero >= 0.1 and 1 - zero >= 0.1, zero
+    return {"none": (0, 1.0), "huber": (3, 1.5), "tukey": (2, delta)}
+
+
+# ------------------------------------------------------------------ layouts of the fused iteration (test_fused_shapes.py)
+F_COND_LAMBDAS = (1e-6, 1e-3, 0.5)
+# landmark degrees of the fused tests' "B_plan" in free-index order: B_LM_DEGREES without the landmarks of more than 256
+# edges, and 2 + 100 + 153 = 255 slots in front of the degree-1 landmark, whose owner slot is then the LAST of its group;
+# the landmarks of 255 and 256 edges are owned by the FIRST slot of theirs (one padding slot between them)
+FUSED_B_LM_DEGREES = (2, 100, 153, 1, 255, 0, 256, 3, 0, 5, 4, 7, 0, 2, 0, 0)
+
+
+def deactivate(f, slots):
+    """a copy of the flattened dict with CUGO_EDGE_INACTIVE set on `slots`, as the engine's outlier rejection leaves
+    them: the flag is set, the slots STAY in the pose lists (pose_ptr / pose_edge) and keep their measurements"""
+    g = dict(f)
+    g["flags"] = f["flags"].copy()
+    g["flags"][np.asarray(slots, np.int64)] |= 8
+    return g
+
+
+def check_fused_layout(f):
+    """check_layout for a layout that may hold deactivated edges (deactivate(): INACTIVE slots that are not padding and
+    are still listed by their pose): legal with those flags cleared, the padding slots are the ones with src < 0, and no
+    landmark's slots lie in two 256-slot groups"""
+    g = dict(f)
+    g["flags"] = np.where(f["src"] >= 0, f["flags"] & 7, f["flags"]).astype(np.uint8)
+    check_layout(g)
+    assert np.all((f["flags"][f["src"] < 0] & 8) != 0)
+    assert straddlers(f) == []
+
+
+def _pairs_of_cameras(rng, n, n_small_w):
+    """_cameras, with every odd pose a near copy of the pose before it (rotation 2e-3, translation 0.02): a landmark seen
+    by such a pair only has small parallax"""
+    pose = _cameras(rng, n, n_small_w)
+    for i in range(1, n, 2):
+        q = synth.quat_mul(synth.quat_from_rotvec(rng.normal(0, 2e-3, 3)), pose[i - 1, :4])
+        pose[i, :4] = q / np.linalg.norm(q) * (1 if q[3] >= 0 else -1)
+        pose[i, 4:] = pose[i - 1, 4:] + rng.normal(0, 0.02, 3)
+    return pose
+
+
+@functools.lru_cache(maxsize=None)
+def fused_layout(name):
+    """(oracle.Problem, flattened dict in the engine's slot layout, hsc structure) of a layout of the fused-iteration
+    tests: "A", "C", "U" (layout()) and "B_plan" (FUSED_B_LM_DEGREES) padded (devmem.pad_to_groups), and
+    "F-dead": a free landmark all of whose slots are INACTIVE, a free pose all of whose edges are, edges whose only free
+              end is the pose and edges whose only free end is the landmark;
+    "F-allfixed": every landmark fixed (Lfree = 0), free poses;
+    "F-cond": monocular landmarks of degree 1 and 2, the pairs of poses close together (small parallax).
+    Built once per process and never modified; the census of each is asserted here, on the CPU."""
+    import devmem
+    import oracle
+    dead = None
+    if name in ("A", "C", "U"):
+        prob, f0 = layout(name)[1:3]
+    elif name == "B_plan":
+        # ids: two fixed landmarks (3 edges each) in front and in the middle, the free ones in FUSED_B_LM_DEGREES order
+        degs = list(FUSED_B_LM_DEGREES)
+        d = designed_by_landmark(degs[:2] + [3] + degs[2:9] + [3] + degs[9:], 304, fixed_poses=(1, 77, 150, 200),
+                                 fixed_landmarks=(2, 10), seed=1)
+        prob, f0 = _flat(d, oracle)
+    elif name == "F-dead":
+        # landmark ids: 3 is fixed; free landmark 6 (degree 3) and pose 7 are the dead ones; four poses are fixed
+        lmd = [100, 100, 100, 40, 5, 4, 3, 6, 5, 4, 6, 5]
+        d = designed_by_landmark(lmd, 130, fixed_poses=(2, 50, 90, 120), fixed_landmarks=(3,), seed=5)
+        prob, f0 = _flat(d, oracle)
+        dead = (int(prob.indices()[0][7]), int(prob.indices()[1][6]))
+    elif name == "F-allfixed":
+        d = designed_by_landmark([30] * 20, 40, seed=6)
+        d["lm_fixed"][:] = 1
+        prob, f0 = _flat(d, oracle)
+    elif name == "F-cond":
+        lmd = [2, 1] * 150            # 255 slots in front of a degree-2 landmark: one padding slot
+        rng = np.random.default_rng(7)
+        ep, el = [], []
+        for l, deg in enumerate(lmd):
+            a = 2 * int(rng.integers(0, 20))          # a pair (a, a + 1) of near-identical cameras
+            ep += [a, a + 1][:deg]
+            el += [l] * deg
+        d = _assemble(rng, 40, len(lmd), ep, el, (), (), stereo_frac=0.0, cameras=_pairs_of_cameras)
+        prob, f0 = _flat(d, oracle)
+    else:
+        raise KeyError(name)
+    f = devmem.pad_to_groups(f0)
+    P, L = f["P"], f["L"]
+    if dead:
+        p_dead, l_dead = dead
+        slots = np.flatnonzero(((f["pose"] == p_dead) | (f["lm"] == l_dead)) & (f["src"] >= 0))
+        f = deactivate(f, slots)
+    check_fused_layout(f)
+    hs = devmem.hsc_structure(f)
+    fl, lmdeg, deg = f["flags"], np.diff(f["lm_ptr"]), np.diff(f["pose_ptr"])
+    pad = f["src"] < 0
+    if name not in ("C", "U"):           # (these two have fewer than 256 slots: nothing to pad)
+        assert pad.any() and f["E"] > f0["E"], "no padding slot"
+    if name == "A":
+        assert sorted(deg[:P].tolist()) == sorted(A_FREE_DEGREES) and f["Pall"] - P == 2 and f["Lall"] - L == 5
+        rounds = sorted(set(-(-k // 256) for k in A_FREE_DEGREES))
+        assert rounds == [0, 1, 2, 3, 5]                      # rounds of k_pose_schur's 256 lanes
+        assert 256 in deg and 512 in deg and 257 in deg and 513 in deg and 1025 in deg   # last round full / 1 lane
+    elif name == "B_plan":
+        real_deg = np.bincount(f["lm"][~pad], minlength=f["Lall"])[:L]
+        for k in (1, 2, 255, 256):
+            assert k in real_deg
+        mid = [l for l in range(L) if lmdeg[l] == 0]
+        assert len(mid) >= 4 and mid[0] < L - 1 and lmdeg[mid[0] + 1] > 0 and mid[-1] == L - 1
+        own = f["lm_ptr"][:L][lmdeg[:L] > 0]
+        assert (own % 256 == 0).any() and (own % 256 == 255).any(), "no landmark owned by the first / last slot of a group"
+    elif name == "C":
+        assert L > 256 + f["E"] and f["E"] == 3                # back-substitution workgroups past the last slot
+    elif name == "U":
+        assert P == 64
+    elif name == "F-dead":
+        assert P == 126 and f["Pall"] == 130 and f["Lall"] - L == 1
+        sl = np.arange(f["lm_ptr"][l_dead], f["lm_ptr"][l_dead + 1])
+        assert len(sl) == 3 and np.all(fl[sl] & 8) and l_dead < L
+        pe = f["pose_edge"][f["pose_ptr"][p_dead]:f["pose_ptr"][p_dead + 1]]
+        assert len(pe) >= 2 and np.all(fl[pe] & 8) and p_dead < P
+        live = (fl & 8) == 0
+        assert (live & ((fl & 3) == 1)).sum() >= 10 and (live & ((fl & 3) == 2)).sum() >= 5
+        # the landmarks the dead pose saw keep other, live edges
+        assert all((live[f["lm_ptr"][l]:f["lm_ptr"][l + 1]]).any() for l in set(f["lm"][pe].tolist()) - {l_dead})
+    elif name == "F-allfixed":
+        assert L == 0 and P == 40 and np.all((fl[~pad] & 3) == 1) and len(hs[1]) == P and len(hs[3]) == 0
+    elif name == "F-cond":
+        assert not (fl & 4).any() and sorted(set(lmdeg[:L].tolist()) - {0}) >= [1, 2]
+        import kernel_ref
+        ref = kernel_ref.build(prob, (0, 1.0), f)
+        kap = []
+        for lam in F_COND_LAMBDAS:
+            ln = kernel_ref.fused_lines(ref["Hll"], ref["bl"], lam)
+            assert np.all(ln["piv"] > 0), "a non-positive pivot in the reference factorisation"
+            kap.append(ln["kappa"])
+        assert (kap[0] > 1e6).mean() >= 0.1 and kap[0].max() > 1e9 and kap[2].min() < 1e4, (kap[0].max(), kap[2].min())
+    return prob, f, hs
+
+
+@functools.lru_cache(maxsize=None)
+def fused_robust_kernels(name):
+    """robust_kernels for a layout of fused_layout (the Tukey delta from the layout's own kernel arguments)"""
+    if name in ("A", "C", "U"):
+        return robust_kernels(name)
+    import kernel_ref
+    prob, f, _ = fused_layout(name)
+    x = np.asarray(kernel_ref.build(prob, (0, 1.0), f)["x"], np.float64)[(f["flags"] & 8) == 0]
     delta = tukey_delta(x)
     zero = float((x > delta * delta).mean())
     assert zero >= 0.1 and 1 - zero >= 0.1, zero
