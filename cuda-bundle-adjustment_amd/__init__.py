@@ -25,7 +25,7 @@ ICP_PLANE, ICP_LINE = 0, 1
 POSE_KIND_PLANE, POSE_KIND_LINE, POSE_KIND_PRIOR, POSE_KIND_RELPOSE = 0, 1, 2, 3
 # pose_edges_reject: edges one trip of its grid covers (1024 workgroups of 256); beyond, a workgroup walks several runs
 POSE_REJECT_GRID_EDGES = 1024 * 256
-EDGE_FIXED_L, EDGE_FIXED_P, EDGE_STEREO, EDGE_INACTIVE = 1, 2, 4, 8
+EDGE_FIXED_L, EDGE_FIXED_P, EDGE_STEREO, EDGE_INACTIVE, EDGE_DEPTH = 1, 2, 4, 8, 16
 
 _i32p = C.POINTER(C.c_int32)
 _f64p = C.POINTER(C.c_double)
@@ -46,7 +46,10 @@ class Edges(C.Structure):
                 ("d_omega", C.c_void_p), ("n_omega", C.c_int), ("d_flags", C.c_void_p),
                 ("d_cam", C.c_void_p), ("d_cams", C.c_void_p), ("n_cams", C.c_int),
                 ("d_lm_ptr", C.c_void_p), ("d_pose_ptr", C.c_void_p), ("d_pose_edge", C.c_void_p),
-                ("block_f32", C.c_int)]
+                ("block_f32", C.c_int),
+                # depth slots (EDGE_DEPTH): nothing behind has_depth is read while it is 0
+                ("has_depth", C.c_int), ("rk_type_depth", C.c_int), ("rk_delta_depth", C.c_double),
+                ("depth_weight", C.c_double)]
 
 
 class Robust(C.Structure):
@@ -163,6 +166,8 @@ def lib():
         _lib.cugo_backsubst_update_fused.argtypes = ([C.c_void_p, C.POINTER(Edges), C.c_double] + [C.c_void_p] * 11 +
                                                      [C.c_int])
         _lib.cugo_backsubst_update_fused.restype = C.c_int
+        _lib.cugo_compute_edge_chi.argtypes = [C.c_void_p, C.POINTER(Edges), C.c_void_p, C.c_void_p, Robust, C.c_void_p]
+        _lib.cugo_compute_edge_chi.restype = C.c_int
     return _lib
 
 
@@ -630,6 +635,62 @@ class Graph:
     def n_relpose_edges(self):
         """relative-pose edges that count in the current flattening (edges between two fixed poses do not)"""
         return lib().cugo_graph_n_relpose_edges(self._g)
+
+    def add_depth_edges(self, pose_ids, lm_ids, meas3, info, cam5=None):
+        """depth edges (ref: DepthEdgeSet): observations (u, v, 1/Z) with the residual
+        (pu - u, pv - v, sqrt(k) (1/Z - m_d)), k the set's inverse-depth weight (set_depth_weight).  info: per edge, or
+        None for the set's value; cam5 [n][5] or None for the set's camera (bf is not used)"""
+        n = len(pose_ids)
+        if n == 0:
+            return
+        pi = np.ascontiguousarray(pose_ids, np.int32); li = np.ascontiguousarray(lm_ids, np.int32)
+        m = np.ascontiguousarray(np.asarray(meas3, np.float64)[:, :3])
+        w = None if info is None else np.ascontiguousarray(info, np.float64)
+        cam = None if cam5 is None else np.ascontiguousarray(cam5, np.float64)
+        check(lib().cugo_graph_add_depth_edges(self._g, n, _p(pi, _i32p), _p(li, _i32p), _p(m, _f64p),
+                                               None if w is None else _p(w, _f64p),
+                                               None if cam is None else _p(cam, _f64p)))
+
+    def set_depth_camera(self, cam5):
+        c = np.ascontiguousarray(cam5, np.float64)
+        check(lib().cugo_graph_set_depth_camera(self._g, _p(c, _f64p)))
+
+    def set_depth_information(self, info):
+        check(lib().cugo_graph_set_depth_information(self._g, C.c_double(info)))
+
+    def set_depth_robust_kernel(self, rk_type, delta):
+        check(lib().cugo_graph_set_depth_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
+
+    def set_depth_outlier_threshold(self, threshold):
+        """as set_outlier_threshold, for the depth edge set"""
+        check(lib().cugo_graph_set_depth_outlier_threshold(self._g, C.c_double(threshold)))
+
+    def set_depth_weight(self, weight):
+        """k, the inverse-depth weight of the depth edge set (default 1); initialize() refuses a value that is not
+        finite and > 0.  Changing it counts as a change of the set"""
+        check(lib().cugo_graph_set_depth_weight(self._g, C.c_double(weight)))
+
+    def n_depth_outliers(self):
+        return lib().cugo_graph_n_depth_outliers(self._g)
+
+    def depth_edge_active(self, n):
+        out = np.zeros(n, np.uint8)
+        check(lib().cugo_graph_get_depth_edge_active(self._g, n, _p(out, _u8p)))
+        return out.astype(bool)
+
+    def flat_edges(self):
+        """the pose-landmark edges of the current flattening, in flattening order: dict(pose, lm, flags, meas [n][3],
+        has_depth, depth_weight) — mono, stereo and depth edges share the array (flag bits EDGE_*)"""
+        n = lib().cugo_graph_get_flat_edges(self._g, 0, None, None, None, None, None, None)
+        if n < 0:
+            check(n)
+        pose = np.zeros(n, np.int32); lm = np.zeros(n, np.int32); fl = np.zeros(n, np.uint8)
+        meas = np.zeros((n, 3)); hd = C.c_int(0); w = C.c_double(0.0)
+        rc = lib().cugo_graph_get_flat_edges(self._g, n, _p(pose, _i32p), _p(lm, _i32p), _p(fl, _u8p), _p(meas, _f64p),
+                                             C.byref(hd), C.byref(w))
+        if rc < 0:
+            check(rc)
+        return dict(pose=pose, lm=lm, flags=fl, meas=meas, has_depth=bool(hd.value), depth_weight=w.value)
 
     def set_outlier_threshold(self, dim, threshold):
         """edges of the set (dim 2 mono / 3 stereo) with chi2 > threshold are inactivated at the

@@ -58,6 +58,20 @@ cugo_k::ReduceScratch scratch_for(cugo_ctx* ctx, const cugo_edges* ev)
     }
     return {ctx->scratch.data(), ctx->scratch.size()};
 }
+
+// the depth members of an edge view (cugo_edges.has_depth != 0; nothing is read otherwise) are checked before anything
+// is launched: the kernels take sqrt(depth_weight)
+void check_depth(const cugo_edges* ev, const char* who)
+{
+    if (!ev || !ev->has_depth)
+        return;
+    if (!(ev->depth_weight > 0.0) || !std::isfinite(ev->depth_weight))
+        throw std::runtime_error(std::string(who) + ": depth_weight must be finite and > 0 with has_depth");
+    const int rk = ev->rk_type_depth;
+    if (rk < CUGO_RK_NONE || rk > CUGO_RK_HUBER ||
+        (rk != CUGO_RK_NONE && !(ev->rk_delta_depth > 0.0 && std::isfinite(ev->rk_delta_depth))))
+        throw std::runtime_error(std::string(who) + ": unknown robust kernel or bad delta of the depth kind");
+}
 } // namespace
 
 extern "C" {
@@ -134,7 +148,20 @@ int cugo_compute_active_errors(cugo_ctx* ctx, const cugo_edges* ev, const double
                                const double* d_lms, cugo_robust rk, double* d_chi)
 {
     return guarded([&] {
+        check_depth(ev, "cugo_compute_active_errors");
         cugo_k::launch_errors(ctx->stream, *ev, d_poses, d_lms, rk, scratch_for(ctx, ev), d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_compute_edge_chi(cugo_ctx* ctx, const cugo_edges* ev, const double* d_poses, const double* d_lms,
+                          cugo_robust rk, double* d_edge_chi)
+{
+    return guarded([&] {
+        if (!ctx || !ev || !d_edge_chi)
+            throw std::runtime_error("cugo_compute_edge_chi: null argument");
+        check_depth(ev, "cugo_compute_edge_chi");
+        cugo_k::launch_edge_chi(ctx->stream, *ev, d_poses, d_lms, rk, d_edge_chi);
         CUGO_HIP(hipGetLastError());
     });
 }
@@ -144,6 +171,7 @@ int cugo_construct_quadratic_form(cugo_ctx* ctx, const cugo_edges* ev, const dou
                                   double* d_Hll, double* d_bl, void* d_Hpl, double* d_chi)
 {
     return guarded([&] {
+        check_depth(ev, "cugo_construct_quadratic_form");
         cugo_k::launch_build(ctx->stream, *ev, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl,
                              scratch_for(ctx, ev), d_chi);
         CUGO_HIP(hipGetLastError());
@@ -418,6 +446,7 @@ int cugo_construct_quadratic_form_lm_priors(cugo_ctx* ctx, const cugo_edges* ev,
             throw std::runtime_error("cugo_lm_prior: no edges or no priors");
         if (lp->n_landmarks_total != ev->n_landmarks_total || lp->n_landmarks_free != ev->n_landmarks_free)
             throw std::runtime_error("cugo_lm_prior: the priors do not describe the landmarks of the edges");
+        check_depth(ev, "cugo_construct_quadratic_form_lm_priors");
         // (the scratch of the BA pass in front, the priors' workgroup totals and the flag of the index check behind it)
         const size_t ba = cugo_k::reduce_scratch_doubles(ev->n_edges, ev->n_poses_free, ev->n_landmarks_free);
         double* d_wg = check_lm_prior(ctx, lp, ba);
@@ -694,6 +723,7 @@ int cugo_construct_quadratic_form_fused(cugo_ctx* ctx, const cugo_edges* ev, con
             refuse("form 2 needs d_lmrec");
         if (form == 1 && (!d_Hpl || (ev->n_poses_free > 0 && (!d_Hpp || !d_bp))))
             refuse("form 1 needs d_Hpl, d_Hpp and d_bp");
+        check_depth(ev, "cugo_construct_quadratic_form_fused");
         // what the engine's slot layout guarantees and the fused kernel relies on: a landmark's slots in one group
         for (int l = 0; l < ev->n_landmarks_total; l++)
         {
@@ -733,6 +763,7 @@ int cugo_compute_schur_fused(cugo_ctx* ctx, const cugo_edges* ev, const cugo_hsc
             refuse("form 2 needs d_lmrec, d_poses, d_bp_out and hs->d_rowptr");
         if (form == 1 && (!d_Hpl || !d_bl || (ev->n_poses_free > 0 && (!d_Hpp || !d_bp))))
             refuse("form 1 needs d_Hpl, d_bl, d_Hpp and d_bp");
+        check_depth(ev, "cugo_compute_schur_fused");
         if (!ctx)
             refuse("null context");
         cugo_k::SchurRows rows;
@@ -764,6 +795,7 @@ int cugo_backsubst_update_fused(cugo_ctx* ctx, const cugo_edges* ev, double lamb
             refuse(from_records ? "from_records without the landmarks' lines (d_lmrec)" : "null d_lmrec");
         if (!d_G || !d_bl || !d_bp || !d_xp || !d_xl || !d_poses_in || !d_lms_in || !d_poses_out || !d_lms_out)
             refuse("null argument");
+        check_depth(ev, "cugo_backsubst_update_fused");
         if (!ctx)
             refuse("null context");
         cugo_k::launch_backsubst_update(ctx->stream, *ev, lambda, lambda, nullptr, d_bl, d_bp, d_G, d_xp, d_xl, d_poses_in,
@@ -1111,6 +1143,8 @@ struct cugo_graph
     std::deque<cugo::LandmarkVertex> lm_store;
     std::deque<cugo::MonoEdge> mono_store;
     std::deque<cugo::StereoEdge> stereo_store;
+    cugo::DepthEdgeSet depth;
+    std::deque<cugo::DepthEdge> depth_store;
     bool attached = false;
     void attach()
     {
@@ -1125,6 +1159,7 @@ struct cugo_graph
         opt->addEdgeSet(&prior);
         opt->addEdgeSet(&relpose);
         opt->addEdgeSet(&lm_prior);
+        opt->addEdgeSet(&depth); // (last: the indices of the other sets in messages stay what they were)
         attached = true;
     }
 };
@@ -1238,6 +1273,28 @@ int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids,
                     e.setCamera(cam);
                 g->stereo.addEdge(&e);
             }
+        }
+    });
+}
+int cugo_graph_add_depth_edges(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* lm_ids, const double* meas3,
+                               const double* info, const double* cam5)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids || !lm_ids || !meas3)))
+            throw std::invalid_argument("cugo_graph_add_depth_edges: missing arrays");
+        for (int i = 0; i < n; i++)
+        {
+            cugo::PoseVertex* vp = g->poses.getVertex(pose_ids[i]);
+            cugo::LandmarkVertex* vl = g->lms.getVertex(lm_ids[i]);
+            g->depth_store.emplace_back();
+            cugo::DepthEdge& e = g->depth_store.back();
+            e.setVertex(vp, 0), e.setVertex(vl, 1);
+            e.setMeasurement(cugo::Vec3d(meas3 + 3 * (size_t)i));
+            e.setInformation(info ? info[i] : 0.0);
+            if (cam5)
+                e.setCamera(cugo::Camera(cam5[5 * (size_t)i], cam5[5 * (size_t)i + 1], cam5[5 * (size_t)i + 2],
+                                         cam5[5 * (size_t)i + 3], cam5[5 * (size_t)i + 4]));
+            g->depth.addEdge(&e);
         }
     });
 }
@@ -1518,6 +1575,70 @@ int cugo_graph_get_edge_active(cugo_graph* g, int dim, int n, uint8_t* active)
             for (int i = 0; i < n && i < (int)g->mono_store.size(); i++)
                 active[i] = g->mono_store[i].isActive() ? 1 : 0;
     });
+}
+// the depth edge set: the dim-keyed functions above keep meaning mono (2) and stereo (3)
+int cugo_graph_set_depth_camera(cugo_graph* g, const double* c)
+{
+    g->depth.setCamera(cugo::Camera(c[0], c[1], c[2], c[3], c[4]));
+    return CUGO_OK;
+}
+int cugo_graph_set_depth_information(cugo_graph* g, double info)
+{
+    g->depth.setInformation(info);
+    return CUGO_OK;
+}
+int cugo_graph_set_depth_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    g->depth.setRobustKernel(rk_type_of(type), delta);
+    return CUGO_OK;
+}
+int cugo_graph_set_depth_outlier_threshold(cugo_graph* g, double threshold)
+{
+    g->depth.setOutlierThreshold(threshold);
+    return CUGO_OK;
+}
+int cugo_graph_set_depth_weight(cugo_graph* g, double weight)
+{
+    g->depth.setInverseDepthWeight(weight); // (checked by initialize())
+    return CUGO_OK;
+}
+int cugo_graph_n_depth_outliers(cugo_graph* g) { return (int)g->depth.getOutlierCount(); }
+int cugo_graph_get_depth_edge_active(cugo_graph* g, int n, uint8_t* active)
+{
+    return guarded([&] {
+        for (int i = 0; i < n && i < (int)g->depth_store.size(); i++)
+            active[i] = g->depth_store[i].isActive() ? 1 : 0;
+    });
+}
+int cugo_graph_get_flat_edges(cugo_graph* g, int cap, int32_t* pose, int32_t* landmark, uint8_t* flags, double* meas3,
+                              int* has_depth, double* depth_weight)
+{
+    int n = -1;
+    const int rc = guarded([&] {
+        std::vector<int> p, l;
+        std::vector<unsigned char> f;
+        std::vector<double> m;
+        g->opt->flatEdges(p, l, f, m);
+        n = (int)p.size();
+        for (int i = 0; i < n && i < cap; i++)
+        {
+            if (pose)
+                pose[i] = p[i];
+            if (landmark)
+                landmark[i] = l[i];
+            if (flags)
+                flags[i] = f[i];
+            if (meas3)
+                std::copy(m.begin() + 3 * (size_t)i, m.begin() + 3 * (size_t)i + 3, meas3 + 3 * (size_t)i);
+        }
+        double w = 1.0;
+        const bool d = g->opt->flatDepth(w);
+        if (has_depth)
+            *has_depth = d ? 1 : 0;
+        if (depth_weight)
+            *depth_weight = w;
+    });
+    return rc == CUGO_OK ? n : rc;
 }
 int cugo_graph_n_pose_edge_outliers(cugo_graph* g, int kind)
 {

@@ -1187,6 +1187,8 @@ void Engine::initialize(FlatGraph& g)
     hipStream_t s = m.ctx.stream;
     m.Pall = g.Pall, m.Lall = g.Lall, m.P = g.P, m.L = g.L;
     m.rk = g.rk;
+    m.ev.has_depth = g.has_depth ? 1 : 0, m.ev.rk_type_depth = g.rk_type_depth;
+    m.ev.rk_delta_depth = g.rk_delta_depth, m.ev.depth_weight = g.depth_weight;
     m.init_rank = m.rank, m.init_world = m.world;
     m.Etot = g.n_edges();
     const int n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
@@ -1196,6 +1198,9 @@ void Engine::initialize(FlatGraph& g)
                                  "optimiser yet");
     if (n_relpose && (m.world > 1 || m.comm))
         throw std::runtime_error("cugo: relative-pose edge sets are not supported on a landmark-sharded (multi-GPU) "
+                                 "optimiser yet");
+    if (g.has_depth && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: depth edge sets are not supported on a landmark-sharded (multi-GPU) "
                                  "optimiser yet");
     // (k_hsc_offdiag_strip reads the list entry before a block's range: a pair block without products has none)
     if (n_relpose && m.opt.hsc_strip)

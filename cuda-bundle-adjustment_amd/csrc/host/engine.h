@@ -109,6 +109,11 @@ struct FlatGraph
     std::vector<uint16_t> e_cam; // E or empty
     std::vector<double> cams;    // n_cams x 5
     cugo_robust rk{CUGO_RK_NONE, 1.0, CUGO_RK_NONE, 1.0};
+    // depth edge sets (flag bit CUGO_EDGE_DEPTH; cugo_edges.has_depth and the members behind it): whether the graph has
+    // any, their robust kernel and their inverse-depth weight
+    bool has_depth = false;
+    int rk_type_depth = CUGO_RK_NONE;
+    double rk_delta_depth = 1.0, depth_weight = 1.0;
     // outlier rejection (ref: EdgeSet::updateEdges, optimisable_graph.hpp:603-640): per edge
     // the chi2 threshold of its edge set, 0 = disabled; empty = disabled for all
     std::vector<double> e_outlier_threshold;

@@ -76,6 +76,21 @@ int CudaGraphOptimisationImpl::nIcpEdges(int kind) const { return engine_->n_icp
 int CudaGraphOptimisationImpl::nPriorEdges() const { return engine_->n_prior_edges(); }
 int CudaGraphOptimisationImpl::nRelPoseEdges() const { return engine_->n_relpose_edges(); }
 int CudaGraphOptimisationImpl::nLandmarkPriorEdges() const { return engine_->n_lm_prior_edges(); }
+void CudaGraphOptimisationImpl::flatEdges(std::vector<int>& pose, std::vector<int>& landmark,
+                                          std::vector<unsigned char>& flags, std::vector<double>& meas3) const
+{
+    const FlatGraph& g = engine_->staging();
+    pose.assign(g.e_pose.begin(), g.e_pose.end());
+    landmark.assign(g.e_lm.begin(), g.e_lm.end());
+    flags.assign(g.e_flags.begin(), g.e_flags.end());
+    meas3 = g.e_meas;
+}
+bool CudaGraphOptimisationImpl::flatDepth(double& weight) const
+{
+    const FlatGraph& g = engine_->staging();
+    weight = g.depth_weight;
+    return g.has_depth;
+}
 
 std::vector<double> CudaGraphOptimisationImpl::structureStats() const
 {
@@ -509,6 +524,7 @@ void CudaGraphOptimisationImpl::initialize()
     // pages is parallel too); chunks with skipped edges are compacted afterwards, in order, so
     // the flattened order is exactly the container order.
     size_t cap = 0;
+    g.has_depth = false, g.rk_type_depth = CUGO_RK_NONE, g.rk_delta_depth = 1.0, g.depth_weight = 1.0;
     for (BaseEdgeSet* es : edgeSets) // (a LandmarkPriorEdgeSet is 3-d like a stereo set: the type tells them apart)
         if (es->dim() != 1 && es->dim() != 6 && !dynamic_cast<LandmarkPriorEdgeSet*>(es))
             cap += es->nedges();
@@ -581,10 +597,26 @@ void CudaGraphOptimisationImpl::initialize()
             continue;
         }
         if (dim != 2 && dim != 3)
-            throw std::runtime_error("cugo: only 2-d (mono) and 3-d (stereo) BA edge sets are supported");
-        const uint8_t stereo_bit = dim == 3 ? CUGO_EDGE_STEREO : 0;
+            throw std::runtime_error("cugo: only 2-d (mono) and 3-d (stereo, depth) BA edge sets are supported");
+        // DepthEdgeSet (ba_types.h): by type — a stereo set is 3-d as well.  Same array, flag bit of its own
+        auto* ds = dynamic_cast<DepthEdgeSet*>(es);
+        if (ds && ds->nedges() == 0)
+            continue; // (an empty depth set leaves the graph one without depth edges)
+        const uint8_t stereo_bit = ds ? CUGO_EDGE_DEPTH : dim == 3 ? CUGO_EDGE_STEREO : 0;
         const RobustKernel& k = es->robustKernelData();
-        if (dim == 3)
+        if (ds)
+        {
+            const double w = ds->inverseDepthWeight();
+            if (!(w > 0.0) || !std::isfinite(w))
+                throw std::runtime_error("cugo: depth edge set: the inverse-depth weight must be finite and > 0 (edge set " +
+                                         std::to_string(si) + ")");
+            if (g.has_depth && w != g.depth_weight)
+                throw std::runtime_error("cugo: depth edge sets disagree on the inverse-depth weight (edge set " +
+                                         std::to_string(si) + "): one weight per optimiser");
+            g.has_depth = true, g.depth_weight = w;
+            g.rk_type_depth = rk_code(k.type()), g.rk_delta_depth = k.delta();
+        }
+        else if (dim == 3)
             rk.type_stereo = rk_code(k.type()), rk.delta_stereo = k.delta();
         else
             rk.type = rk_code(k.type()), rk.delta = k.delta();

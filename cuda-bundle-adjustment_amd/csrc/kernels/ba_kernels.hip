@@ -1,7 +1,7 @@
 // Edge / landmark / pose kernels of the BA hot path for gfx950 (wave64, fp64).
 //
 // Design:
-//  * edges are landmark-major, mono+stereo merged, streamed with lane <-> edge so every
+//  * edges are landmark-major, mono+stereo(+depth) merged, streamed with lane <-> edge so every
 //    per-edge array is read/written fully coalesced;
 //  * no floating-point atomics anywhere: Hll/bl are summed per landmark, Hpp/bp and the
 //    diagonal Schur blocks per pose by one workgroup each, off-diagonal Schur blocks by one
@@ -11,6 +11,8 @@
 //
 // ref: src/cuda/cuda_block_solver.cu — kernels at 1060 (errors), 1152 (quadratic form),
 // 1223 (max diagonal), 1286-1345 (Schur), 1419-1490 (back-substitution, update, scale).
+#include <cmath>
+
 #include "ba_math.h"
 #include "kernels.h"
 #include "lm_prior_term.h"
@@ -133,6 +135,16 @@ struct Robust2
     Robust m, s; // mono / stereo edge sets
 };
 
+// The inverse-depth kind (DepthEdge) rides in the edge passes as a trailing parameter pack DP: empty
+// for an edge array without depth slots (cugo_edges.has_depth == 0) — those instantiations take the arguments the kernels
+// have always taken, never look at CUGO_EDGE_DEPTH and hold none of the depth code — or the one DepthPar.  A depth-aware
+// instantiation computes its mono and stereo slots with the same operations in the same order.
+struct DepthPar
+{
+    Robust rk; // robust kernel of the depth edge sets
+    double s;  // sqrt(inverse-depth weight)
+};
+
 struct EdgeIn
 {
     int ip, il;
@@ -141,6 +153,14 @@ struct EdgeIn
     const double* cam;
 };
 
+// a slot of the depth kind: only a depth-aware instantiation (DEP) looks at the bit
+template <bool DEP>
+__device__ __forceinline__ bool is_depth(uint8_t fl)
+{
+    return DEP && (fl & CUGO_EDGE_DEPTH) != 0;
+}
+
+template <bool DEP = false>
 __device__ __forceinline__ EdgeIn load_edge(const EV& ev, int e, uint8_t fl)
 {
     EdgeIn in;
@@ -149,10 +169,39 @@ __device__ __forceinline__ EdgeIn load_edge(const EV& ev, int e, uint8_t fl)
     in.stereo = (fl & CUGO_EDGE_STEREO) != 0;
     in.mu = ev.meas[e];
     in.mv = ev.meas[(size_t)ev.E + e];
-    in.mr = in.stereo ? ev.meas[2 * (size_t)ev.E + e] : 0.0;
+    in.mr = (in.stereo || is_depth<DEP>(fl)) ? ev.meas[2 * (size_t)ev.E + e] : 0.0;
     in.omega = ev.n_omega > 1 ? ev.omega[e] : ev.omega[0];
     in.cam = ev.n_cams > 1 ? ev.cams + 5 * (int)ev.cam[e] : ev.cams;
     return in;
+}
+
+// sqrt(inverse-depth weight), without / with the depth kind
+__device__ __forceinline__ double depth_scale_of() { return 0.0; }
+__device__ __forceinline__ double depth_scale_of(double s) { return s; }
+__device__ __forceinline__ double depth_scale_of(const DepthPar dp) { return dp.s; }
+// the kind bits of the meta word of a slot's 64-byte record (k_build_edges): stereo bit 16, depth bit 18
+__device__ __forceinline__ bool record_stereo(long long meta) { return ((meta >> 16) & 1) != 0; }
+template <bool DEP>
+__device__ __forceinline__ bool record_depth(long long meta)
+{
+    return DEP && ((meta >> 18) & 1) != 0;
+}
+// the first element of a parameter pack (k_build_edges: the view of the landmark priors)
+template <typename T, typename... R>
+__device__ __forceinline__ const T& first_of(const T& t, const R&...)
+{
+    return t;
+}
+// the last element of a parameter pack
+template <typename T>
+__device__ __forceinline__ const T& last_of(const T& t)
+{
+    return t;
+}
+template <typename T, typename U, typename... R>
+__device__ __forceinline__ decltype(auto) last_of(const T&, const U& u, const R&... r)
+{
+    return last_of(u, r...);
 }
 
 // ---------------------------------------------------------------- reductions -----------
@@ -253,9 +302,10 @@ __global__ __launch_bounds__(BS) void k_max_partials(const double* __restrict__ 
 // ---------------------------------------------------------------- errors ---------------
 // one lane per edge; chi2 partial per workgroup (ref: computeActiveErrorsKernel .cu:1060 +
 // computeChiValueKernel .cu:1112, fused; errors/Xc are not materialised)
+template <typename... DP>
 __global__ __launch_bounds__(BS) void k_errors(EV ev, const double* __restrict__ poses,
                                                const double* __restrict__ lms, Robust2 rk,
-                                               double* __restrict__ partials)
+                                               double* __restrict__ partials, DP... dp)
 {
     __shared__ double sm[BS / 64];
     const int e = blockIdx.x * BS + threadIdx.x;
@@ -265,10 +315,20 @@ __global__ __launch_bounds__(BS) void k_errors(EV ev, const double* __restrict__
         const uint8_t fl = ev.flags[e];
         if (!(fl & CUGO_EDGE_INACTIVE))
         {
-            const EdgeIn in = load_edge(ev, e, fl);
+            constexpr bool DEP = sizeof...(DP) != 0;
+            const EdgeIn in = load_edge<DEP>(ev, e, fl);
+            const bool depth = is_depth<DEP>(fl);
             EdgeGeom g;
-            edge_residual(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr,
-                          in.stereo, in.omega, in.cam, in.stereo ? rk.s : rk.m, g);
+            // (two calls, here and in the kernels below: the one without the depth kind is written as it always was.
+            // Routing it through the template with a helper that picks the robust kernel gave the same arithmetic but
+            // other register figures for the instantiations that existed before — tools/kernel_resources.sh)
+            if constexpr (DEP)
+                edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
+                                      depth, depth_scale_of(dp...), in.omega, in.cam,
+                                      in.stereo ? rk.s : (depth ? first_of(dp...).rk : rk.m), g);
+            else
+                edge_residual(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr,
+                              in.stereo, in.omega, in.cam, in.stereo ? rk.s : rk.m, g);
             chi = g.chi;
         }
     }
@@ -279,9 +339,10 @@ __global__ __launch_bounds__(BS) void k_errors(EV ev, const double* __restrict__
 
 // chi_e = rho(omega |e|^2) per edge slot (0 for inactive slots): only used by the outlier
 // rejection at the end of optimize() (ref: d_chiValues read by computeOutliersKernel .cu:1135)
+template <typename... DP>
 __global__ __launch_bounds__(BS) void k_edge_chi(EV ev, const double* __restrict__ poses,
                                                  const double* __restrict__ lms, Robust2 rk,
-                                                 double* __restrict__ chi_out)
+                                                 double* __restrict__ chi_out, DP... dp)
 {
     const int e = blockIdx.x * BS + threadIdx.x;
     if (e >= ev.E)
@@ -290,10 +351,17 @@ __global__ __launch_bounds__(BS) void k_edge_chi(EV ev, const double* __restrict
     double chi = 0;
     if (!(fl & CUGO_EDGE_INACTIVE))
     {
-        const EdgeIn in = load_edge(ev, e, fl);
+        constexpr bool DEP = sizeof...(DP) != 0;
+        const EdgeIn in = load_edge<DEP>(ev, e, fl);
+        const bool depth = is_depth<DEP>(fl);
         EdgeGeom g;
-        edge_residual(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr,
-                      in.stereo, in.omega, in.cam, in.stereo ? rk.s : rk.m, g);
+        if constexpr (DEP)
+            edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth,
+                                  depth_scale_of(dp...), in.omega, in.cam,
+                                  in.stereo ? rk.s : (depth ? first_of(dp...).rk : rk.m), g);
+        else
+            edge_residual(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr,
+                          in.stereo, in.omega, in.cam, in.stereo ? rk.s : rk.m, g);
         chi = g.chi;
     }
     chi_out[e] = chi;
@@ -313,9 +381,10 @@ struct LmContrib
 {
     double h00, h01, h02, h11, h12, h22, b0, b1, b2;
 };
-__device__ __forceinline__ LmContrib lm_contrib(const double JL[3][3], const EdgeGeom& g, bool stereo)
+// (three: a stereo or a depth slot)
+__device__ __forceinline__ LmContrib lm_contrib(const double JL[3][3], const EdgeGeom& g, bool three)
 {
-    const int dim = stereo ? 3 : 2;
+    const int dim = three ? 3 : 2;
     double s00 = 0, s01 = 0, s02 = 0, s11 = 0, s12 = 0, s22 = 0, t0 = 0, t1 = 0, t2 = 0;
     // three rows unrolled, the third skipped for a monocular edge: with the run-time bound `m < dim` the loop stays a
     // loop, JL[m][.] is indexed at run time and all nine doubles of JL live in private memory (72 bytes per lane
@@ -339,11 +408,15 @@ __device__ __forceinline__ LmContrib lm_contrib(const double JL[3][3], const Edg
                      g.w * t0, g.w * t1, g.w * t2};
 }
 
-// the one element of a parameter pack (the view of the landmark priors below)
-template <typename T>
-__device__ __forceinline__ const T& first_of(const T& t)
+
+// sqrt(inverse-depth weight) where the DepthPar, if any (DEP), is the last element of a pack
+template <bool DEP, typename... LP>
+__device__ __forceinline__ double depth_scale_in(const LP&... lp)
 {
-    return t;
+    if constexpr (DEP)
+        return last_of(lp...).s;
+    else
+        return 0.0;
 }
 
 // (153 VGPRs, no private segment: three waves per SIMD — tools/kernel_resources.sh.  Capped at 128 — four waves — the kernel spills ~230 bytes per lane and takes
@@ -351,6 +424,7 @@ __device__ __forceinline__ const T& first_of(const T& t)
 // LMP: landmark position priors (lm_prior_term.h) ride along: LP is then the one LmPriorView.  The
 // instantiation without them takes the arguments the kernel has always taken (an empty pack) and holds none of their
 // code; both have the register figures above.
+// The pack ends with the one DepthPar where the edge array may hold depth slots (see DepthPar above).
 template <typename S, bool LMP, typename... LP>
 __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restrict__ poses,
                                                     const double* __restrict__ lms, Robust2 rk,
@@ -362,7 +436,9 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
                                                     double fuse_lambda, double* __restrict__ invHll,
                                                     S* __restrict__ T, double* __restrict__ lmrec, LP... lp)
 {
-    static_assert(sizeof...(LP) == (LMP ? 1 : 0), "the view of the landmark priors goes with LMP");
+    static_assert(sizeof...(LP) == (LMP ? 1 : 0) || sizeof...(LP) == (LMP ? 2 : 1),
+                  "the view of the landmark priors goes with LMP, the DepthPar behind it");
+    constexpr bool DEP = sizeof...(LP) == (LMP ? 2 : 1);
     // fuse_lambda >= 0 (the engine, whose slot layout keeps a landmark inside one workgroup, from the
     // second LM iteration on: the damping of the first trial is known when the build is queued): this
     // pass also leaves invHll = (Hll + lambda I)^-1 and T = Hpl invHll — exactly what k_schur_edges
@@ -400,26 +476,35 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
         l = ev.lm[e];
         if (!(fl & CUGO_EDGE_INACTIVE))
         {
-            const EdgeIn in = load_edge(ev, e, fl);
+            const EdgeIn in = load_edge<DEP>(ev, e, fl);
+            const bool depth = is_depth<DEP>(fl);
+            const double sd = depth_scale_in<DEP>(lp...);
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
-            edge_residual(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega,
-                          in.cam, in.stereo ? rk.s : rk.m, g);
+            if constexpr (DEP)
+                edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
+                                      in.cam, in.stereo ? rk.s : (depth ? last_of(lp...).rk : rk.m), g);
+            else
+                edge_residual(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega,
+                              in.cam, in.stereo ? rk.s : rk.m, g);
             chi = g.chi;
             r8[0] = g.Xc[0], r8[1] = g.Xc[1], r8[2] = g.Xc[2];
             r8[3] = g.e[0], r8[4] = g.e[1], r8[5] = g.e[2], r8[6] = g.w;
-            // {camera index, stereo bit, "takes part in the Schur complement" bit, landmark} (k_pose_schur)
+            // {camera index, stereo bit, "takes part in the Schur complement" bit, depth bit, landmark} (k_pose_schur)
             const bool schur_act = !(fl & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P)) && l < ev.L;
-            r8[7] = __longlong_as_double((long long)(ev.n_cams > 1 ? (int)ev.cam[e] : 0) |
-                                         ((long long)(in.stereo ? 1 : 0) << 16) | ((long long)(schur_act ? 1 : 0) << 17) |
-                                         ((long long)(schur_act ? l : 0) << 32));
+            long long meta = (long long)(ev.n_cams > 1 ? (int)ev.cam[e] : 0) |
+                             ((long long)(in.stereo ? 1 : 0) << 16) | ((long long)(schur_act ? 1 : 0) << 17) |
+                             ((long long)(schur_act ? l : 0) << 32);
+            if constexpr (DEP)
+                meta |= (long long)(depth ? 1 : 0) << 18;
+            r8[7] = __longlong_as_double(meta);
             double JL[3][3];
-            jac_landmark(g.Xc, pose, in.cam, in.stereo, JL);
-            lc = lm_contrib(JL, g, in.stereo);
+            jac_landmark_k<DEP>(g.Xc, pose, in.cam, in.stereo, depth, sd, JL);
+            lc = lm_contrib(JL, g, in.stereo || depth);
             if (!(fl & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P)))
             {
                 double JP[3][6];
-                jac_pose(g.Xc, in.cam, in.stereo, JP);
+                jac_pose_k<DEP>(g.Xc, in.cam, in.stereo, depth, sd, JP);
 #pragma unroll
                 for (int c = 0; c < 3; c++)
 #pragma unroll
@@ -475,14 +560,20 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             const uint8_t fl = ev.flags[ee];
             if (fl & CUGO_EDGE_INACTIVE)
                 continue;
-            const EdgeIn in = load_edge(ev, ee, fl);
+            const EdgeIn in = load_edge<DEP>(ev, ee, fl);
+            const bool depth = is_depth<DEP>(fl);
+            const double sd = depth_scale_in<DEP>(lp...);
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
-            edge_residual(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega,
-                          in.cam, in.stereo ? rk.s : rk.m, g);
+            if constexpr (DEP)
+                edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
+                                      in.cam, in.stereo ? rk.s : (depth ? last_of(lp...).rk : rk.m), g);
+            else
+                edge_residual(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega,
+                              in.cam, in.stereo ? rk.s : rk.m, g);
             double JL[3][3];
-            jac_landmark(g.Xc, pose, in.cam, in.stereo, JL);
-            const LmContrib c2 = lm_contrib(JL, g, in.stereo);
+            jac_landmark_k<DEP>(g.Xc, pose, in.cam, in.stereo, depth, sd, JL);
+            const LmContrib c2 = lm_contrib(JL, g, in.stereo || depth);
             a[0] += c2.h00, a[1] += c2.h01, a[2] += c2.h02, a[3] += c2.h11, a[4] += c2.h12;
             a[5] += c2.h22, a[6] += c2.b0, a[7] += c2.b1, a[8] += c2.b2;
         }
@@ -668,9 +759,11 @@ __device__ __forceinline__ void wave_reduce32(double (&a)[32])
 // The 27 sums of a wave are formed in registers (wave_reduce32), the four waves' partial sums meet in 1 KB of LDS:
 // 19 KB of LDS per workgroup, so that every pose of a kitti_00-sized graph is resident at once.
 constexpr int BP_W = BS / 64;
+// DS: empty, or sqrt(inverse-depth weight) where the records may carry the depth bit (see DepthPar)
+template <typename... DS>
 __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restrict__ rec,
                                                     double* __restrict__ Hpp,
-                                                    double* __restrict__ bp)
+                                                    double* __restrict__ bp, DS... ds)
 {
     __shared__ double stage_all[BP_W][64 * 9]; // per wave: 64 records x 9 doubles
     __shared__ double wsum[BP_W][32];
@@ -712,10 +805,10 @@ __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restr
             const double ee[3] = {r[3], r[4], r[5]};
             const double w = r[6];
             const long long meta = __double_as_longlong(r[7]);
-            const bool stereo = ((meta >> 16) & 1) != 0;
+            const bool stereo = record_stereo(meta);
             const double* cam = ev.cams + 5 * (int)(meta & 0xFFFF);
             double JP[3][6];
-            jac_pose(Xc, cam, stereo, JP);
+            jac_pose_k<sizeof...(DS) != 0>(Xc, cam, stereo, record_depth<sizeof...(DS) != 0>(meta), depth_scale_of(ds...), JP);
             int k = 0;
 #pragma unroll
             for (int rr = 0; rr < 6; rr++)
@@ -792,12 +885,14 @@ __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restr
 // (In the float mode the stored T / Hpl blocks are rounded to float and the off-diagonal blocks are formed from
 // those; the diagonal blocks formed here never see a stored block and come out in full precision.)
 constexpr int PS_W = 4, PS_BS = 64 * PS_W;
+// DS: as for k_build_poses
+template <typename... DS>
 __global__ __launch_bounds__(PS_BS, 3) void k_pose_schur(EV ev, const double* __restrict__ rec,
                                                       const double* __restrict__ lmrec,
                                                       const double* __restrict__ poses,
                                                       const int32_t* __restrict__ rowptr, double lambda_diag,
                                                       double* __restrict__ Hsc, double* __restrict__ bp,
-                                                      double* __restrict__ bsc)
+                                                      double* __restrict__ bsc, DS... ds)
 {
     __shared__ double stage_all[PS_W][64 * 9]; // per wave: 64 records x 9 doubles
     __shared__ double wsum[PS_W][34];
@@ -850,7 +945,9 @@ __global__ __launch_bounds__(PS_BS, 3) void k_pose_schur(EV ev, const double* __
         const double we[3] = {wgt * r[3], wgt * r[4], wgt * r[5]};
         const long long meta = __double_as_longlong(r[7]);
         wave_sync_lds(); // (the slot is refilled by the next round)
-        const bool stereo = ((meta >> 16) & 1) != 0;
+        constexpr bool DEP = sizeof...(DS) != 0;
+        const bool stereo = record_stereo(meta);
+        const bool depth = record_depth<DEP>(meta);
         const bool act = i < i1 && ((meta >> 17) & 1) != 0;
         const double* cam = ev.cams + 5 * (int)(meta & 0xFFFF);
         // the landmark's line (an inactive edge reads slot 0 and never uses it).  (Measured: a pose-major copy of the
@@ -868,7 +965,7 @@ __global__ __launch_bounds__(PS_BS, 3) void k_pose_schur(EV ev, const double* __
             for (int a = 0; a < 9; a++)
                 R[a / 3][a % 3] = Rs[a + zero];
             double JL[3][3];
-            jac_landmark_R(Xc, R, cam, stereo, JL);
+            jac_landmark_R_k<DEP>(Xc, R, cam, stereo, depth, depth_scale_of(ds...), JL);
             double K[3][3]; // A = JL L^-T:  A[m][j] = sum_{i <= j} JL[m][i] L^-1[j][i]
 #pragma unroll
             for (int m = 0; m < 3; m++)
@@ -898,7 +995,7 @@ __global__ __launch_bounds__(PS_BS, 3) void k_pose_schur(EV ev, const double* __
         }
         __builtin_amdgcn_sched_barrier(0); // (JL, K and the landmark's line are dead before JP exists: registers)
         double JP[3][6];
-        jac_pose(Xc, cam, stereo, JP);
+        jac_pose_k<DEP>(Xc, cam, stereo, depth, depth_scale_of(ds...), JP);
         // (the right-hand sides first: we and u are dead before the 21 block entries are formed)
 #pragma unroll
         for (int rr = 0; rr < 6; rr++)
@@ -2341,19 +2438,21 @@ __device__ __forceinline__ void dev_update_poses(int blk, int nP, double lambda,
 // q = L^-1 of the landmark's line.  H = w (JP^T JL) and G = H L^-T are the build pass's own expressions in its
 // association (the translation unit is compiled with -ffp-contract=off), every entry of G goes through S as its
 // store does, and the three sums run in hplT_x's order: the same bits as hplT_x on the stored block.
-template <typename S>
+template <typename S, typename... DS>
 __device__ __forceinline__ void gT_x_from_record(const double* r8, const double* __restrict__ pose,
                                                  const double* __restrict__ cams, const double* __restrict__ q,
-                                                 const double* x, double& s0, double& s1, double& s2)
+                                                 const double* x, double& s0, double& s1, double& s2, DS... ds)
 {
     const double Xc[3] = {r8[0], r8[1], r8[2]};
     const double w = r8[6];
     const long long bits = __double_as_longlong(r8[7]);
     const double* cam = cams + 5 * (int)(bits & 0xffff);
-    const bool stereo = ((bits >> 16) & 1) != 0;
+    constexpr bool DEP = sizeof...(DS) != 0;
+    const bool stereo = record_stereo(bits);
+    const bool depth = record_depth<DEP>(bits);
     double JL[3][3], JP[3][6];
-    jac_landmark(Xc, pose, cam, stereo, JL);
-    jac_pose(Xc, cam, stereo, JP);
+    jac_landmark_k<DEP>(Xc, pose, cam, stereo, depth, depth_scale_of(ds...), JL);
+    jac_pose_k<DEP>(Xc, cam, stereo, depth, depth_scale_of(ds...), JP);
     const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
     s0 = 0, s1 = 0, s2 = 0;
 #pragma unroll
@@ -2381,15 +2480,17 @@ __device__ __forceinline__ void gT_x_from_record(const double* r8, const double*
 // k_build_edges wrote and k_pose_schur reads) instead of the 144-byte G blocks and every lane re-forms its G^T x
 // (gT_x_from_record): 64 + 0 instead of 144 bytes per slot from memory, 24.6 instead of 36.9 KB of LDS.  The records
 // must be those of the build pass that wrote lmrec and G, at poses_in (see the call in engine.cpp).
-template <typename S, bool REC>
+// DS (only with REC): as for k_build_poses
+template <typename S, bool REC, typename... DS>
 __global__ __launch_bounds__(BS) void k_backsubst_landmarks(
     EV ev, double lambda, const double* __restrict__ invHll, const double* __restrict__ bl,
     const S* __restrict__ Hpl, const double* __restrict__ xp, double* __restrict__ xl,
     const double* __restrict__ lms_in, double* __restrict__ lms_out,
     double* __restrict__ partials, int nbl, double lambda_pose, const double* __restrict__ bp,
     const double* __restrict__ poses_in, double* __restrict__ poses_out, const double* __restrict__ lmrec,
-    const double* __restrict__ rec)
+    const double* __restrict__ rec, DS... ds)
 {
+    static_assert(REC || sizeof...(DS) == 0, "only the record form re-forms Jacobians");
     // lmrec != nullptr: the one-stream form of the fused iteration (k_build_edges): `Hpl` holds G = Hpl L^-T and the
     // landmark's line {L^-1, y = L^-1 bl}:  dx_l = L^-T (y - sum G_e^T dx_p)  in place of  invHll (bl - sum Hpl_e^T dx_p)
     __shared__ double sm[BS / 64];
@@ -2463,7 +2564,7 @@ __global__ __launch_bounds__(BS) void k_backsubst_landmarks(
         double s0 = 0, s1 = 0, s2 = 0;
         if (act && l < ev.L)
             gT_x_from_record<S>(reinterpret_cast<const double*>(hs) + 9 * t, poses_in + 7 * (size_t)ev.pose[e], ev.cams,
-                                lmrec + 16 * (size_t)l, x, s0, s1, s2);
+                                lmrec + 16 * (size_t)l, x, s0, s1, s2, ds...);
         cs[0][t] = s0, cs[1][t] = s1, cs[2][t] = s2;
     }
     else
@@ -2555,12 +2656,21 @@ size_t reduce_scratch_doubles(int n_edges, int n_poses, int n_landmarks)
     return scratch_partials(n_edges, n_poses, n_landmarks) + 8 * ((size_t)n_edges + BS);
 }
 
+// the depth kind of an edge view (cugo_edges.has_depth != 0): its robust kernel and s = sqrt(weight), formed once here
+static DepthPar depth_par(const cugo_edges& e)
+{
+    return DepthPar{{e.rk_type_depth, e.rk_delta_depth}, std::sqrt(e.depth_weight)};
+}
+
 void launch_errors(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                    cugo_robust rk, ReduceScratch rs, double* d_chi)
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E, BS);
-    if (nb > 0)
+    if (nb > 0 && e.has_depth)
+        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials, depth_par(e));
+    else if (nb > 0)
         CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials);
     CUGO_LAUNCH(k_sum_partials, dim3(1), dim3(SP_BS), 0, s, rs.d_partials, nb, d_chi);
@@ -2576,7 +2686,10 @@ void launch_errors_tail(hipStream_t s, const cugo_edges& e, const double* d_pose
     // the scale partials of the update pass sit at the start of the scratch: the error pass uses the
     // record area behind the partial slots (free between two build passes)
     double* d_chi_part = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-    if (nb > 0)
+    if (nb > 0 && e.has_depth)
+        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, depth_par(e));
+    else if (nb > 0)
         CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part);
     CUGO_LAUNCH(k_sum_partials2, dim3(2), dim3(SP_BS), 0, s, d_chi_part, nb, rs.d_partials, n_scale_partials,
@@ -2588,7 +2701,10 @@ void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, 
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E, BS);
-    if (nb > 0)
+    if (nb > 0 && e.has_depth)
+        CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, depth_par(e));
+    else if (nb > 0)
         CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e);
 }
@@ -2615,7 +2731,20 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
     // chi_behind_scale: this build pass ends a trial (launch_trial_tail_from_build sums its chi2 partials together with
     // the scale partials of the update pass, which sit at the start of the scratch)
     double* d_chi_part = rs.d_partials + (chi_behind_scale ? spec_chi_offset(ev.E, ev.P, ev.L) : 0);
-    if (nb > 0 && lm_priors && lm_priors->n > 0)
+    const bool lmp = lm_priors && lm_priors->n > 0;
+    if (nb > 0 && e.has_depth)
+    { // the depth-aware instantiations: only for an edge view that says depth slots may be present
+        ::cugo_k::LaunchScope _scope("k_build_edges", s);
+        if (lmp)
+            hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView, DepthPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses,
+                               d_lms, r, d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll,
+                               d_T, d_invHll && d_T ? d_lmrec : nullptr, lm_prior_view(*lm_priors), depth_par(e));
+        else
+            hipLaunchKernelGGL((k_build_edges<S, false, DepthPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r,
+                               d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
+                               d_invHll && d_T ? d_lmrec : nullptr, depth_par(e));
+    }
+    else if (nb > 0 && lmp)
     {
         ::cugo_k::LaunchScope _scope("k_build_edges", s);
         hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r, d_Hpl,
@@ -2634,7 +2763,12 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
     // skip_poses: the Schur complement of this lambda forms Hsc's diagonal blocks, bp and bsc from the records itself
     // (launch_schur with SchurRows::d_lmrec); Hpp is then not written
     if (ev.P > 0 && !(skip_poses && d_invHll && d_T && d_lmrec))
-        CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp);
+    {
+        if (e.has_depth)
+            CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, depth_par(e).s);
+        else
+            CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp);
+    }
 }
 
 void launch_build(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
@@ -2757,8 +2891,12 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
     if (ev.P > 0 && have_T && rows.d_lmrec)
     { // fused iteration: diagonal blocks, bp and bsc from the build pass's records (its pose pass was skipped)
         const double* d_rec = rows.rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-        CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
-                      hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc);
+        if (e.has_depth)
+            CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
+                        hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc, depth_par(e).s);
+        else
+            CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
+                        hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc);
     }
     else if (ev.P > 0 && rows.mfma == 1)
         CUGO_LAUNCH_T(k_hsc_diag_mfma, S, dim3(xcd_grid(ev.P)), dim3(HM_BS), 0, s, ev,
@@ -2822,7 +2960,11 @@ static int launch_backsubst_update_t(hipStream_t s, const cugo_edges& e, double 
         ::cugo_k::LaunchScope _scope("k_backsubst_landmarks", s);
         // from_records: G^T dx_p from the build pass's records in the scratch instead of the G stream
         const double* d_rec = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-        if (from_records && d_lmrec)
+        if (from_records && d_lmrec && e.has_depth)
+            hipLaunchKernelGGL((k_backsubst_landmarks<S, true, double>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda,
+                               d_invHll, d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
+                               d_poses_in, d_poses_out, d_lmrec, d_rec, depth_par(e).s);
+        else if (from_records && d_lmrec)
             hipLaunchKernelGGL((k_backsubst_landmarks<S, true>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda, d_invHll,
                                d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
                                d_poses_in, d_poses_out, d_lmrec, d_rec);

@@ -71,12 +71,20 @@ __device__ __forceinline__ void world_to_cam(const double* __restrict__ pose,
     Xc[2] = Xw[2] + qw * t1z + t2z + pose[6];
 }
 
-// residual (proj - meas), weight and chi for one edge (ref: .cu:410-424, 1100-1109, 1190-1192)
-__device__ __forceinline__ void edge_residual(const double* __restrict__ pose,
-                                              const double* __restrict__ Xw, double mu, double mv,
-                                              double mr, bool stereo, double omega,
-                                              const double* __restrict__ cam, const Robust rk,
-                                              EdgeGeom& g)
+// The kind of a pose-landmark slot: mono, stereo, or (DEP only) inverse depth (DepthEdge) with the
+// third residual sd (1/Z - m_d), sd = sqrt(inverse-depth weight); at most one of stereo and depth is set.  DEP = false
+// is what `bool stereo` has always said: those instantiations hold the code of the overloads that take the bool alone,
+// operation by operation, and never read depth or sd.  Only the kernels for edge arrays that may hold depth slots are
+// built with DEP.  (The kind travels as scalars: a one-byte struct handed through these functions ends up in LDS.)
+
+// residual (proj - meas), weight and chi for one edge (ref: .cu:410-424, 1100-1109, 1190-1192); mr is the third
+// measurement: u_right of a stereo slot, 1/Z of a depth slot
+template <bool DEP>
+__device__ __forceinline__ void edge_residual_k(const double* __restrict__ pose,
+                                                const double* __restrict__ Xw, double mu, double mv,
+                                                double mr, bool stereo, bool depth, double sd, double omega,
+                                                const double* __restrict__ cam, const Robust rk,
+                                                EdgeGeom& g)
 {
     world_to_cam(pose, Xw, g.Xc);
     const double invZ = 1.0 / g.Xc[2];
@@ -91,10 +99,26 @@ __device__ __forceinline__ void edge_residual(const double* __restrict__ pose,
         sq += g.e[2] * g.e[2];
     }
     else
+    {
         g.e[2] = 0.0;
+        if constexpr (DEP)
+            if (depth)
+            {
+                g.e[2] = sd * (invZ - mr);
+                sq += g.e[2] * g.e[2];
+            }
+    }
     const double x = omega * sq;
     g.chi = rk_rho(rk, x);
     g.w = omega * rk_drho(rk, x);
+}
+__device__ __forceinline__ void edge_residual(const double* __restrict__ pose,
+                                              const double* __restrict__ Xw, double mu, double mv,
+                                              double mr, bool stereo, double omega,
+                                              const double* __restrict__ cam, const Robust rk,
+                                              EdgeGeom& g)
+{
+    edge_residual_k<false>(pose, Xw, mu, mv, mr, stereo, false, 0.0, omega, cam, rk, g);
 }
 
 // rotation matrix rows from quaternion (ref: .cu:449-478). R[r][c]
@@ -117,8 +141,11 @@ __device__ __forceinline__ void quat_to_rot(const double* __restrict__ q, double
 }
 
 // Pose Jacobian rows JP[m][6] (m < dim); third row zero for mono. ref: .cu:491-578
-__device__ __forceinline__ void jac_pose(const double* Xc, const double* __restrict__ cam,
-                                         bool stereo, double JP[3][6])
+// Depth: rows 0 and 1 are the mono rows, JP[2] = s/Z^2 (Y, -X, 0, 0, 0, 1) — minus the derivative of s/Z, as the
+// stereo row is JP[0] - bf/Z^2 dZ/dxi with dZ/dxi = (Y, -X, 0, 0, 0, 1)
+template <bool DEP>
+__device__ __forceinline__ void jac_pose_k(const double* Xc, const double* __restrict__ cam,
+                                           bool stereo, bool depth, double sd, double JP[3][6])
 {
     const double X = Xc[0], Y = Xc[1], Z = Xc[2];
     const double invZ = 1.0 / Z;
@@ -142,6 +169,14 @@ __device__ __forceinline__ void jac_pose(const double* Xc, const double* __restr
 #pragma unroll
         for (int c = 0; c < 6; c++)
             JP[2][c] = 0;
+        if constexpr (DEP)
+            if (depth)
+            {
+                const double sZZ = sd * (invZ * invZ);
+                JP[2][0] = sZZ * Y;
+                JP[2][1] = -(sZZ * X);
+                JP[2][5] = sZZ;
+            }
     }
     else
     {
@@ -166,11 +201,18 @@ __device__ __forceinline__ void jac_pose(const double* Xc, const double* __restr
         JP[2][5] = JP[0][5] - bf * iZZ;
     }
 }
+__device__ __forceinline__ void jac_pose(const double* Xc, const double* __restrict__ cam,
+                                         bool stereo, double JP[3][6])
+{
+    jac_pose_k<false>(Xc, cam, stereo, false, 0.0, JP);
+}
 
 // Landmark Jacobian rows JL[m][3] from the rotation matrix of the pose. ref: .cu:508-513, 546-556
-__device__ __forceinline__ void jac_landmark_R(const double* Xc, const double R[3][3],
-                                               const double* __restrict__ cam, bool stereo,
-                                               double JL[3][3])
+// Depth: JL[2][j] = s/Z^2 R[2][j]
+template <bool DEP>
+__device__ __forceinline__ void jac_landmark_R_k(const double* Xc, const double R[3][3],
+                                                 const double* __restrict__ cam, bool stereo, bool depth, double sd,
+                                                 double JL[3][3])
 {
     const double X = Xc[0], Y = Xc[1], Z = Xc[2];
     const double invZ = 1.0 / Z;
@@ -186,6 +228,14 @@ __device__ __forceinline__ void jac_landmark_R(const double* Xc, const double R[
             JL[1][j] = -fv_iz * (R[1][j] - y * R[2][j]);
             JL[2][j] = 0;
         }
+        if constexpr (DEP)
+            if (depth)
+            {
+                const double sZZ = sd * (invZ * invZ);
+#pragma unroll
+                for (int j = 0; j < 3; j++)
+                    JL[2][j] = sZZ * R[2][j];
+            }
     }
     else
     {
@@ -199,13 +249,26 @@ __device__ __forceinline__ void jac_landmark_R(const double* Xc, const double R[
         }
     }
 }
+__device__ __forceinline__ void jac_landmark_R(const double* Xc, const double R[3][3],
+                                               const double* __restrict__ cam, bool stereo,
+                                               double JL[3][3])
+{
+    jac_landmark_R_k<false>(Xc, R, cam, stereo, false, 0.0, JL);
+}
+template <bool DEP>
+__device__ __forceinline__ void jac_landmark_k(const double* Xc, const double* __restrict__ q,
+                                               const double* __restrict__ cam, bool stereo, bool depth, double sd,
+                                               double JL[3][3])
+{
+    double R[3][3];
+    quat_to_rot(q, R);
+    jac_landmark_R_k<DEP>(Xc, R, cam, stereo, depth, sd, JL);
+}
 __device__ __forceinline__ void jac_landmark(const double* Xc, const double* __restrict__ q,
                                              const double* __restrict__ cam, bool stereo,
                                              double JL[3][3])
 {
-    double R[3][3];
-    quat_to_rot(q, R);
-    jac_landmark_R(Xc, R, cam, stereo, JL);
+    jac_landmark_k<false>(Xc, q, cam, stereo, false, 0.0, JL);
 }
 
 // symmetric 3x3 inverse by adjugate, A column-major 9 with lambda added to the diagonal.

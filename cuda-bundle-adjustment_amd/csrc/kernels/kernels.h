@@ -51,6 +51,11 @@ struct ReduceScratch
 };
 
 // --- edge / landmark / pose passes (ba_kernels.hip) ---------------------------------------
+// Depth slots (CUGO_EDGE_DEPTH): every launcher below that forms residuals or Jacobians
+// (launch_errors*, launch_edge_chi, launch_build, launch_schur's pose pass, launch_backsubst_update from records) picks
+// the depth-aware instantiation of its kernel iff ev.has_depth != 0 and takes the depth kind's robust kernel and
+// sqrt(ev.depth_weight) from ev; with ev.has_depth == 0 the kernels, and their arguments, are the ones there have
+// always been.  The caller has checked the members (c_api.cpp: check_depth; the engine's come from initialize()).
 void launch_errors(hipStream_t s, const cugo_edges& ev, const double* d_poses, const double* d_lms,
                    cugo_robust rk, ReduceScratch rs, double* d_chi);
 

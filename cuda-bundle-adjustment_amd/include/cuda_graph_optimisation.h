@@ -148,6 +148,13 @@ public:
     /** landmark position priors of the current flattening that count: active, on a free landmark
      *  (landmark_prior_types.h, an extension) */
     int nLandmarkPriorEdges() const;
+    /** the pose-landmark edges of the current flattening in flattening order (set by set, container order; mono,
+     *  stereo and depth edges share the array): flattened pose and landmark index, CUGO_EDGE_* flags, measurement
+     *  (3 per edge, the third 0 for a mono edge).  Diagnostic */
+    void flatEdges(std::vector<int>& pose, std::vector<int>& landmark, std::vector<unsigned char>& flags,
+                   std::vector<double>& meas3) const;
+    /** whether the current flattening holds depth edges, and their inverse-depth weight */
+    bool flatDepth(double& weight) const;
     /** B, M, nnz(L), flops, supernodes, stages, front bytes, off-diagonal products, then per
      *  factorisation: potrf / trsm / syrk flops, extend-add bytes, backward bytes */
     std::vector<double> structureStats() const;

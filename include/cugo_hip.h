@@ -43,7 +43,9 @@ enum
     CUGO_EDGE_FIXED_L = 1,
     CUGO_EDGE_FIXED_P = 2,
     CUGO_EDGE_STEREO = 4,  /* 3-d measurement (StereoEdge) instead of 2-d (MonoEdge) */
-    CUGO_EDGE_INACTIVE = 8 /* outlier / removed: contributes nothing (ref: outliers[e]!=0) */
+    CUGO_EDGE_INACTIVE = 8, /* outlier / removed: contributes nothing (ref: outliers[e]!=0) */
+    CUGO_EDGE_DEPTH = 16    /* extension: 3-d measurement (u, v, 1/Z) of a DepthEdge; never together with STEREO.
+                             * Looked at only when cugo_edges.has_depth != 0 */
 };
 
 typedef struct cugo_ctx cugo_ctx; /* device + stream + scratch; replaces CudaDevice */
@@ -79,7 +81,7 @@ typedef struct cugo_edges
     int n_poses_free, n_landmarks_free;
     const int32_t* d_pose;   /* [E] pose index      (ref edge2PL[e][0]) */
     const int32_t* d_lm;     /* [E] landmark index  (ref edge2PL[e][1]) */
-    const double* d_meas;    /* [3][E] planar: u, v, u_right */
+    const double* d_meas;    /* [3][E] planar: u, v, u_right (stereo slot) or 1/Z (depth slot) */
     const double* d_omega;   /* [E] or [1] information (ref omegas) */
     int n_omega;             /* E or 1  (ref: perEdgeInformation) */
     const uint8_t* d_flags;  /* [E] CUGO_EDGE_* */
@@ -95,6 +97,17 @@ typedef struct cugo_edges
      * CMakeLists.txt:8, src/scalar.h:24-28).  Only the storage of these two streams changes:
      * every value is widened on load, all arithmetic and every other array stay fp64. */
     int block_f32;
+    /* Extension: inverse-depth slots (CUGO_EDGE_DEPTH, ref: DepthEdge include/ba_types.h:171-260).  Residual
+     *   e = (pu - m_u, pv - m_v, s (1/Z - m_d)),  s = sqrt(depth_weight);  bf of the camera is not used.
+     * has_depth == 0 (every zero-initialised struct): none of the members below is read, the DEPTH bit of d_flags is
+     * not looked at and every entry point runs the kernels it has always run.  has_depth != 0: slots with the DEPTH
+     * bit are depth slots (there may be none: the results then have the bits of has_depth == 0), their robust kernel is
+     * (rk_type_depth, rk_delta_depth) — cugo_robust keeps describing the mono and stereo kinds — and depth_weight must
+     * be finite and > 0 (CUGO_ERR_INVALID otherwise).  Mono and stereo slots come out with the same bits either way. */
+    int has_depth;
+    int rk_type_depth;     /* CUGO_RK_* */
+    double rk_delta_depth;
+    double depth_weight;   /* k: the set's inverse-depth weight (1: chi2 of the reference's computeActiveErrors_DepthBa) */
 } cugo_edges;
 
 typedef struct cugo_robust
@@ -112,6 +125,11 @@ typedef struct cugo_robust
  * Writes the total chi2 to d_chi[0] (device).  Deterministic (fixed reduction order). */
 int cugo_compute_active_errors(cugo_ctx* ctx, const cugo_edges* ev, const double* d_poses,
                                const double* d_lms, cugo_robust rk, double* d_chi);
+
+/* Extension: d_edge_chi[e] = rho(omega |e|^2) of every edge slot, 0 for an inactive slot ([n_edges], device): what the
+ * outlier rejection compares with the set's threshold (ref: d_chiValues, computeOutliersKernel .cu:1135).  Asynchronous. */
+int cugo_compute_edge_chi(cugo_ctx* ctx, const cugo_edges* ev, const double* d_poses, const double* d_lms,
+                          cugo_robust rk, double* d_edge_chi);
 
 /* ref: gpu::constructQuadraticForm_<2|3> (cuda_block_solver.h:159-176; .cu:1152-1220) plus
  * the four fillZero calls of BlockSolver::buildSystem (block_solver.cpp:287-294).
@@ -749,6 +767,28 @@ int cugo_graph_set_outlier_threshold(cugo_graph* g, int dim, double threshold);
 int cugo_graph_n_outliers(cugo_graph* g, int dim);
 /* active flag of the first n edges of the set, in insertion order */
 int cugo_graph_get_edge_active(cugo_graph* g, int dim, int n, uint8_t* active);
+/* Extension: depth edges (DepthEdgeSet, ref: include/ba_types.h:171-260): observations (u, v, 1/Z) with the residual
+ * (pu - u, pv - v, sqrt(k) (1/Z - m_d)); k is the set's inverse-depth weight (default 1, the reference's chi2).  They
+ * share the landmark-major array, the Schur complement and the covariance entry points with the mono and stereo edges;
+ * the dim-keyed functions above keep meaning mono (2) and stereo (3), these are their counterparts for the depth set.
+ * meas3 [n][3]; info [n] (with per-edge information) or NULL; cam5 [n][5] or NULL for the set's camera (bf unused).
+ * cugo_graph_initialize refuses a weight that is not finite and > 0, and a depth set on a landmark-sharded (multi-GPU)
+ * graph.  cugo_graph_reprojection_covariances keeps its two kinds (2, 3). */
+int cugo_graph_add_depth_edges(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* landmark_ids,
+                               const double* meas3, const double* info, const double* cam5);
+int cugo_graph_set_depth_camera(cugo_graph* g, const double* cam5);
+int cugo_graph_set_depth_information(cugo_graph* g, double info);
+int cugo_graph_set_depth_robust_kernel(cugo_graph* g, int type, double delta);
+int cugo_graph_set_depth_outlier_threshold(cugo_graph* g, double threshold);
+int cugo_graph_set_depth_weight(cugo_graph* g, double weight);
+int cugo_graph_n_depth_outliers(cugo_graph* g);
+int cugo_graph_get_depth_edge_active(cugo_graph* g, int n, uint8_t* active);
+/* Diagnostic: the pose-landmark edges of the current flattening in flattening order (set by set, insertion order; mono,
+ * stereo and depth edges share the array).  Returns their number (or a negative error) and fills the first `cap`
+ * entries of the arrays that are not NULL: flattened pose and landmark index, CUGO_EDGE_* flags, meas3 [cap][3] (the
+ * third 0 for a mono edge); *has_depth / *depth_weight: what the edge kernels get in cugo_edges. */
+int cugo_graph_get_flat_edges(cugo_graph* g, int cap, int32_t* pose, int32_t* landmark, uint8_t* flags, double* meas3,
+                              int* has_depth, double* depth_weight);
 /* The same for the four pose edge kinds: CUGO_ICP_PLANE / CUGO_ICP_LINE under their other names, the priors and the
  * relative-pose edges.  Outliers found in the kind's set since the last initialize (a negative error code for an
  * unknown kind), and the active flag of its first n edges in insertion order (CUGO_ERR_INVALID: unknown kind, n
