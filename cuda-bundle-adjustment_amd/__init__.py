@@ -40,6 +40,11 @@ class CugoError(RuntimeError):
 
 
 class Edges(C.Structure):
+    """The HEAD of cugo_edges: every member up to depth_weight.  The C struct has since grown (RigEdges, below) and
+    the library reads has_rig behind depth_weight of every edge view it is given, so sizeof(Edges) != sizeof(cugo_edges).
+    Edges() — the constructor — is safe: it hands out the head of a zeroed full-size struct (has_rig = 0).  An Edges
+    made any other way (from_buffer_copy, copy.copy, (Edges * n)(), a member of another Structure) has nothing behind
+    it and must NOT be passed to the library: build a RigEdges for those, which is the struct in full."""
     _fields_ = [("n_edges", C.c_int), ("n_poses_total", C.c_int), ("n_landmarks_total", C.c_int),
                 ("n_poses_free", C.c_int), ("n_landmarks_free", C.c_int),
                 ("d_pose", C.c_void_p), ("d_lm", C.c_void_p), ("d_meas", C.c_void_p),
@@ -50,6 +55,19 @@ class Edges(C.Structure):
                 # depth slots (EDGE_DEPTH): nothing behind has_depth is read while it is 0
                 ("has_depth", C.c_int), ("rk_type_depth", C.c_int), ("rk_delta_depth", C.c_double),
                 ("depth_weight", C.c_double)]
+
+    def __new__(cls, *args, **kwargs):
+        # cugo_edges has grown behind depth_weight (RigEdges below) and the library reads has_rig of every edge view it
+        # is given: an Edges() is the head of a zeroed full-size struct, so has_rig is 0 for it
+        if cls is Edges:
+            return cls.from_buffer(RigEdges())
+        return super().__new__(cls)
+
+
+class RigEdges(Edges):
+    """cugo_edges in full: Edges plus the members appended for camera extrinsics (a rig).  has_rig != 0: d_cam_ext
+    [n_cams][12] = {M row-major, t_s} per camera-table entry, body -> sensor; d_cam_ext is not read while has_rig is 0"""
+    _fields_ = [("has_rig", C.c_int), ("d_cam_ext", C.c_void_p)]
 
 
 class Robust(C.Structure):
@@ -476,7 +494,9 @@ class Graph:
         check(lib().cugo_graph_add_landmarks(self._g, len(ids), _p(ids, _i32p), _p(x, _f64p), _p(f, _u8p)))
         self.lm_ids = np.concatenate([self.lm_ids, ids])
 
-    def add_edges(self, dim, pose_ids, lm_ids, meas, info, cam5=None):
+    def add_edges(self, dim, pose_ids, lm_ids, meas, info, cam5=None, sensor=None):
+        """sensor: a sensor pose (q, t) body -> sensor per edge, [n][7] (a rig: the poses are then world -> body); it
+        follows the camera, so it counts on a graph with per_edge_camera, like cam5.  None: the set's (set_sensor_pose)"""
         n = len(pose_ids)
         if n == 0:
             return
@@ -484,8 +504,40 @@ class Graph:
         m = np.ascontiguousarray(np.asarray(meas, np.float64)[:, :dim])
         w = np.ascontiguousarray(info, np.float64)
         cam = None if cam5 is None else np.ascontiguousarray(cam5, np.float64)
-        check(lib().cugo_graph_add_edges(self._g, dim, n, _p(pi, _i32p), _p(li, _i32p), _p(m, _f64p),
-                                         _p(w, _f64p), None if cam is None else _p(cam, _f64p)))
+        if sensor is None:
+            check(lib().cugo_graph_add_edges(self._g, dim, n, _p(pi, _i32p), _p(li, _i32p), _p(m, _f64p),
+                                             _p(w, _f64p), None if cam is None else _p(cam, _f64p)))
+            return
+        sx = np.ascontiguousarray(sensor, np.float64)
+        if sx.shape != (n, 7):
+            raise CugoError("add_edges: sensor must be [n][7] (qx, qy, qz, qw, tx, ty, tz)")
+        check(lib().cugo_graph_add_edges_rig(self._g, dim, n, _p(pi, _i32p), _p(li, _i32p), _p(m, _f64p), _p(w, _f64p),
+                                             None if cam is None else _p(cam, _f64p), _p(sx, _f64p)))
+
+    def set_sensor_pose(self, dim, q_t7):
+        """the sensor pose body -> sensor (qx, qy, qz, qw, tx, ty, tz) of the mono (dim 2) or stereo (dim 3) set"""
+        q = np.ascontiguousarray(q_t7, np.float64)
+        if q.shape != (7,):
+            raise CugoError("set_sensor_pose: q_t7 must hold 7 numbers")
+        check(lib().cugo_graph_set_sensor_pose(self._g, dim, _p(q, _f64p)))
+
+    def n_rig_cameras(self):
+        """camera-table entries of the current flattening whose sensor pose is not the identity"""
+        n = lib().cugo_graph_n_rig_cameras(self._g)
+        if n < 0:
+            check(n)
+        return n
+
+    def flat_cameras(self):
+        """the camera table of the current flattening: dict(cams [n][5], ext [n][12] = {M row-major, t_s}, has_rig)"""
+        n = lib().cugo_graph_get_flat_cameras(self._g, 0, None, None, None)
+        if n < 0:
+            check(n)
+        cams = np.zeros((n, 5)); ext = np.zeros((n, 12)); hr = C.c_int(0)
+        rc = lib().cugo_graph_get_flat_cameras(self._g, n, _p(cams, _f64p), _p(ext, _f64p), C.byref(hr))
+        if rc < 0:
+            check(rc)
+        return dict(cams=cams, ext=ext, has_rig=bool(hr.value))
 
     def set_camera(self, dim, cam5):
         c = np.ascontiguousarray(cam5, np.float64)

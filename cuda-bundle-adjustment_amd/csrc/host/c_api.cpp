@@ -61,8 +61,18 @@ cugo_k::ReduceScratch scratch_for(cugo_ctx* ctx, const cugo_edges* ev)
 
 // the depth members of an edge view (cugo_edges.has_depth != 0; nothing is read otherwise) are checked before anything
 // is launched: the kernels take sqrt(depth_weight)
+// The rig members (cugo_edges.has_rig != 0; d_cam_ext is not read otherwise) likewise: a table must be there, and the
+// rig-aware kernels hold no depth code yet.
 void check_depth(const cugo_edges* ev, const char* who)
 {
+    if (ev && ev->has_rig)
+    {
+        if (!ev->d_cam_ext)
+            throw std::runtime_error(std::string(who) + ": has_rig needs the extrinsics table d_cam_ext");
+        if (ev->has_depth)
+            throw std::runtime_error(std::string(who) + ": camera extrinsics (has_rig) together with depth slots "
+                                                        "(has_depth) are not supported yet");
+    }
     if (!ev || !ev->has_depth)
         return;
     if (!(ev->depth_weight > 0.0) || !std::isfinite(ev->depth_weight))
@@ -1237,16 +1247,20 @@ int cugo_graph_add_landmarks(cugo_graph* g, int n, const int32_t* ids, const dou
         }
     });
 }
-int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids, const int32_t* lm_ids,
-                         const double* meas, const double* info, const double* cam5)
+// mono / stereo edges; ext7 [n][7]: a sensor pose (q, t) per edge, or NULL (the set's applies)
+static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const int32_t* pose_ids, const int32_t* lm_ids,
+                        const double* meas, const double* info, const double* cam5, const double* ext7)
 {
     return guarded([&] {
         if (dim != 2 && dim != 3)
-            throw std::runtime_error("cugo_graph_add_edges: dim must be 2 or 3");
+            throw std::runtime_error(std::string(who) + ": dim must be 2 or 3");
         for (int i = 0; i < n; i++)
         {
             cugo::PoseVertex* vp = g->poses.getVertex(pose_ids[i]);
             cugo::LandmarkVertex* vl = g->lms.getVertex(lm_ids[i]);
+            cugo::Se3D ext;
+            if (ext7)
+                ext = cugo::Se3D(ext7 + 7 * (size_t)i, ext7 + 7 * (size_t)i + 4);
             cugo::Camera cam;
             if (cam5)
                 cam = cugo::Camera(cam5[5 * (size_t)i], cam5[5 * (size_t)i + 1], cam5[5 * (size_t)i + 2],
@@ -1260,6 +1274,8 @@ int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids,
                 e.setInformation(info ? info[i] : 0.0);
                 if (cam5)
                     e.setCamera(cam);
+                if (ext7)
+                    e.setSensorPose(ext);
                 g->mono.addEdge(&e);
             }
             else
@@ -1271,10 +1287,59 @@ int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids,
                 e.setInformation(info ? info[i] : 0.0);
                 if (cam5)
                     e.setCamera(cam);
+                if (ext7)
+                    e.setSensorPose(ext);
                 g->stereo.addEdge(&e);
             }
         }
     });
+}
+int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids, const int32_t* lm_ids,
+                         const double* meas, const double* info, const double* cam5)
+{
+    return add_ba_edges(g, "cugo_graph_add_edges", dim, n, pose_ids, lm_ids, meas, info, cam5, nullptr);
+}
+int cugo_graph_add_edges_rig(cugo_graph* g, int dim, int n, const int32_t* pose_ids, const int32_t* lm_ids,
+                             const double* meas, const double* info, const double* cam5, const double* sensor_q_t7)
+{
+    return add_ba_edges(g, "cugo_graph_add_edges_rig", dim, n, pose_ids, lm_ids, meas, info, cam5, sensor_q_t7);
+}
+int cugo_graph_set_sensor_pose(cugo_graph* g, int dim, const double* q_t7)
+{
+    return guarded([&] {
+        if ((dim != 2 && dim != 3) || !q_t7)
+            throw std::runtime_error("cugo_graph_set_sensor_pose: dim must be 2 or 3 and q_t7 not NULL");
+        const cugo::Se3D T(q_t7, q_t7 + 4);
+        if (dim == 3)
+            g->stereo.setSensorPose(T);
+        else
+            g->mono.setSensorPose(T);
+    });
+}
+int cugo_graph_n_rig_cameras(cugo_graph* g)
+{
+    int n = -1;
+    const int rc = guarded([&] { n = g->opt->nRigCameras(); });
+    return rc == CUGO_OK ? n : rc;
+}
+int cugo_graph_get_flat_cameras(cugo_graph* g, int cap, double* cam5, double* ext12, int* has_rig)
+{
+    int n = -1;
+    const int rc = guarded([&] {
+        std::vector<double> c, x;
+        const bool rig = g->opt->flatCameras(c, x);
+        n = (int)(c.size() / 5);
+        for (int i = 0; i < n && i < cap; i++)
+        {
+            if (cam5)
+                std::copy(c.begin() + 5 * (size_t)i, c.begin() + 5 * (size_t)i + 5, cam5 + 5 * (size_t)i);
+            if (ext12)
+                std::copy(x.begin() + 12 * (size_t)i, x.begin() + 12 * (size_t)i + 12, ext12 + 12 * (size_t)i);
+        }
+        if (has_rig)
+            *has_rig = rig ? 1 : 0;
+    });
+    return rc == CUGO_OK ? n : rc;
 }
 int cugo_graph_add_depth_edges(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* lm_ids, const double* meas3,
                                const double* info, const double* cam5)

@@ -138,7 +138,8 @@ struct Engine::Impl : cugo_k::LaunchHook
     DevBuf<int32_t> d_pose_pos, d_off_pi; // row-strip form of the off-diagonal gather (k_hsc_offdiag_strip)
     bool strip_on = false;
     int max_row_nnz = 0;
-    DevBuf<double> d_meas, d_omega, d_cams;
+    DevBuf<double> d_meas, d_omega, d_cams, d_cam_ext; // (d_cam_ext: FlatGraph::cam_ext, only with has_rig)
+    bool has_rig = false;
     DevBuf<uint8_t> d_flags;
     DevBuf<uint16_t> d_cam;
     DevBuf<double> d_poses[2], d_lms[2];
@@ -1146,6 +1147,8 @@ struct Engine::Impl::SlotUpload
         const SlotArrays& sl = m.slots;
         f(m.d_e_pose, sl.pose), f(m.d_e_lm, sl.lm), f(m.d_flags, sl.flags), f(m.d_lm_ptr, m.h_lm_ptr);
         f(m.d_meas, sl.meas), f(m.d_omega, sl.omega), f(m.d_cams, g.cams);
+        if (g.has_rig) // the extrinsics go up with the cameras (a table parallel to them)
+            f(m.d_cam_ext, g.cam_ext);
         if (sl.n_cams > 1)
             f(m.d_cam, sl.cam);
         for (int k = 0; k < 2; k++)
@@ -1202,6 +1205,15 @@ void Engine::initialize(FlatGraph& g)
     if (g.has_depth && (m.world > 1 || m.comm))
         throw std::runtime_error("cugo: depth edge sets are not supported on a landmark-sharded (multi-GPU) "
                                  "optimiser yet");
+    if (g.has_rig && g.cam_ext.size() != 12 * (g.cams.size() / 5))
+        throw std::runtime_error("cugo: camera extrinsics (sensor poses): the table must hold 12 numbers per camera");
+    if (g.has_rig && g.has_depth)
+        throw std::runtime_error("cugo: camera extrinsics (sensor poses) together with depth edge sets are not "
+                                 "supported yet");
+    if (g.has_rig && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: camera extrinsics (sensor poses) are not supported on a landmark-sharded "
+                                 "(multi-GPU) optimiser yet");
+    m.has_rig = g.has_rig;
     // (k_hsc_offdiag_strip reads the list entry before a block's range: a pair block without products has none)
     if (n_relpose && m.opt.hsc_strip)
         throw std::runtime_error("cugo: relative-pose edge sets cannot be combined with CUGO_HSC_STRIP=1: the row-strip "
@@ -1268,6 +1280,8 @@ void Engine::initialize(FlatGraph& g)
     ev.d_cam = m.slots.n_cams > 1 ? m.d_cam.data() : nullptr, ev.d_cams = m.d_cams.data();
     ev.n_cams = m.slots.n_cams, ev.d_lm_ptr = m.d_lm_ptr.data(), ev.d_pose_ptr = m.d_pose_ptr.data();
     ev.d_pose_edge = m.d_pose_edge.data();
+    // (every launcher of an edge pass picks its rig-aware instantiation from this)
+    ev.has_rig = m.has_rig ? 1 : 0, ev.d_cam_ext = m.has_rig ? m.d_cam_ext.data() : nullptr;
     // opt-in (CUGO_HSC_ROWS=1): the Schur complement by whole block rows (k_hsc_rows; slower)
     m.rows_on = !m.plan_only && m.opt.hsc_rows && !m.opt.schur_plan;
     if (m.rows_on)

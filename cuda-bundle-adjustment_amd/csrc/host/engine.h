@@ -108,6 +108,10 @@ struct FlatGraph
     std::vector<uint8_t> e_flags;
     std::vector<uint16_t> e_cam; // E or empty
     std::vector<double> cams;    // n_cams x 5
+    // camera extrinsics (a rig; cugo_edges.has_rig / d_cam_ext): per camera-table entry the sensor pose body -> sensor
+    // as {M row-major, t_s}, n_cams x 12 (or empty: all identity); has_rig iff one of them is not exactly identity
+    std::vector<double> cam_ext;
+    bool has_rig = false;
     cugo_robust rk{CUGO_RK_NONE, 1.0, CUGO_RK_NONE, 1.0};
     // depth edge sets (flag bit CUGO_EDGE_DEPTH; cugo_edges.has_depth and the members behind it): whether the graph has
     // any, their robust kernel and their inverse-depth weight

@@ -92,6 +92,34 @@ bool CudaGraphOptimisationImpl::flatDepth(double& weight) const
     return g.has_depth;
 }
 
+bool CudaGraphOptimisationImpl::flatCameras(std::vector<double>& cam5, std::vector<double>& ext12) const
+{
+    const FlatGraph& g = engine_->staging();
+    static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    cam5 = g.cams;
+    ext12 = g.cam_ext;
+    if (!g.has_rig)
+        for (size_t k = 0; k < g.cams.size() / 5; k++)
+            ext12.insert(ext12.end(), I12, I12 + 12);
+    return g.has_rig;
+}
+int CudaGraphOptimisationImpl::nRigCameras() const
+{
+    std::vector<double> cams, x;
+    if (!flatCameras(cams, x))
+        return 0;
+    static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    int n = 0;
+    for (size_t k = 0; k < x.size() / 12; k++)
+    {
+        bool identity = true;
+        for (int c = 0; c < 12; c++)
+            identity = identity && x[12 * k + c] == I12[c];
+        n += identity ? 0 : 1;
+    }
+    return n;
+}
+
 std::vector<double> CudaGraphOptimisationImpl::structureStats() const
 {
     const auto& s = engine_->structure_stats();
@@ -481,6 +509,7 @@ void CudaGraphOptimisationImpl::initialize()
         flattenValid_ = false;
     }
     g.cams.clear();
+    g.cam_ext.clear(), g.has_rig = false;
     // ---- vertex indices: free first (ascending id), fixed after -------------------------
     int nPfree = 0, nLfree = 0, nP = 0, nL = 0;
     for (BaseVertexSet* vs : vertexSets)
@@ -542,10 +571,15 @@ void CudaGraphOptimisationImpl::initialize()
     struct Chunk
     {
         size_t begin = 0, count = 0;  // slot range written: [begin, begin + count)
-        std::vector<double> cams;     // distinct cameras of this chunk (5 each), first-seen order
+        std::vector<double> cams;     // distinct cameras of this chunk (CK each: see below), first-seen order
         bool uniform = true;
         bool too_many_cams = false;
     };
+    // A camera-table entry is keyed on CK = 5 + 7 numbers: the intrinsics and the sensor pose (q, t) as the caller gave
+    // it.  Two entries with the same intrinsics and different extrinsics are different entries; the key table is split
+    // into g.cams and g.cam_ext behind the walk.
+    constexpr size_t CK = 12;
+    std::vector<double> camKeys;
     const unsigned hw = cugo_host::pool_threads();
     lap("graph: edge array alloc");
     size_t out = 0; // slots filled so far (compacted)
@@ -625,6 +659,7 @@ void CudaGraphOptimisationImpl::initialize()
         es->setOutlierCount(0);
         const double set_info = es->informationValue();
         const Camera set_cam = es->cameraData();
+        const Se3D set_ext = es->sensorPoseData();
         const EdgeContainer& ec = es->get();
         const size_t n = ec.size();
         const unsigned nthreads = n < 20000 ? 1u : hw;
@@ -672,15 +707,17 @@ void CudaGraphOptimisationImpl::initialize()
                     c.uniform = false;
                 g.e_omega[o] = w;
                 const Camera& cm = perCam ? e->cameraData() : set_cam;
-                const double cv[5] = {cm.fx, cm.fy, cm.cx, cm.cy, cm.bf};
+                const Se3D& sx = perCam ? e->sensorPoseData() : set_ext;
+                const double cv[CK] = {cm.fx,        cm.fy,        cm.cx,        cm.cy,        cm.bf,        sx.r.data[0],
+                                       sx.r.data[1], sx.r.data[2], sx.r.data[3], sx.t.data[0], sx.t.data[1], sx.t.data[2]};
                 // deduplicate cameras: last-hit fast path, then a short linear scan
                 int ci = -1;
-                const size_t ncam = c.cams.size() / 5;
-                if (ncam > 0 && std::memcmp(&c.cams[5 * (size_t)last_cam], cv, sizeof cv) == 0)
+                const size_t ncam = c.cams.size() / CK;
+                if (ncam > 0 && std::memcmp(&c.cams[CK * (size_t)last_cam], cv, sizeof cv) == 0)
                     ci = last_cam;
                 else
                     for (size_t k2 = 0; k2 < ncam; k2++)
-                        if (std::memcmp(&c.cams[5 * k2], cv, sizeof cv) == 0)
+                        if (std::memcmp(&c.cams[CK * k2], cv, sizeof cv) == 0)
                         {
                             ci = (int)k2;
                             break;
@@ -695,7 +732,7 @@ void CudaGraphOptimisationImpl::initialize()
                     else
                     {
                         ci = (int)ncam;
-                        c.cams.insert(c.cams.end(), cv, cv + 5);
+                        c.cams.insert(c.cams.end(), cv, cv + CK);
                     }
                 }
                 last_cam = (uint16_t)ci;
@@ -716,14 +753,14 @@ void CudaGraphOptimisationImpl::initialize()
             if (c.too_many_cams)
                 throw std::runtime_error("cugo: more than 65535 distinct cameras");
             // merge this chunk's cameras into the global table (first-seen order is kept)
-            std::vector<uint16_t> remap(c.cams.size() / 5);
+            std::vector<uint16_t> remap(c.cams.size() / CK);
             bool identity = true;
             for (size_t q = 0; q < remap.size(); q++)
             {
                 int ci = -1;
-                const size_t ncam = g.cams.size() / 5;
+                const size_t ncam = camKeys.size() / CK;
                 for (size_t k2 = 0; k2 < ncam; k2++)
-                    if (std::memcmp(&g.cams[5 * k2], &c.cams[5 * q], 5 * sizeof(double)) == 0)
+                    if (std::memcmp(&camKeys[CK * k2], &c.cams[CK * q], CK * sizeof(double)) == 0)
                     {
                         ci = (int)k2;
                         break;
@@ -733,7 +770,7 @@ void CudaGraphOptimisationImpl::initialize()
                     if (ncam >= 65535)
                         throw std::runtime_error("cugo: more than 65535 distinct cameras");
                     ci = (int)ncam;
-                    g.cams.insert(g.cams.end(), c.cams.begin() + 5 * q, c.cams.begin() + 5 * q + 5);
+                    camKeys.insert(camKeys.end(), c.cams.begin() + CK * q, c.cams.begin() + CK * q + CK);
                 }
                 remap[q] = (uint16_t)ci;
                 identity = identity && ci == (int)q;
@@ -769,6 +806,31 @@ void CudaGraphOptimisationImpl::initialize()
         g.e_omega.resize(1);
     if (!any_threshold)
         g.e_outlier_threshold.clear();
+    // the key table -> cameras and extrinsics: the quaternion normalised and expanded to M here, in fp64
+    for (size_t k = 0; k < camKeys.size() / CK; k++)
+    {
+        const double* key = &camKeys[CK * k];
+        g.cams.insert(g.cams.end(), key, key + 5);
+        const double n2 = key[5] * key[5] + key[6] * key[6] + key[7] * key[7] + key[8] * key[8];
+        bool finite = std::isfinite(n2) && n2 > 0.0;
+        for (int c = 9; c < 12; c++)
+            finite = finite && std::isfinite(key[c]);
+        if (!finite)
+            throw std::runtime_error("cugo: camera extrinsics (sensor pose) of camera-table entry " + std::to_string(k) +
+                                     ": the quaternion must be finite with a norm > 0, the translation finite");
+        const double in = 1.0 / std::sqrt(n2);
+        const double x = key[5] * in, y = key[6] * in, z = key[7] * in, w = key[8] * in;
+        const double M[12] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w),     2 * (x * z + y * w),
+                              2 * (x * y + z * w),     1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                              2 * (x * z - y * w),     2 * (y * z + x * w),     1 - 2 * (x * x + y * y),
+                              key[9],                  key[10],                 key[11]};
+        static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+        for (int c = 0; c < 12; c++)
+            g.has_rig = g.has_rig || M[c] != I12[c];
+        g.cam_ext.insert(g.cam_ext.end(), M, M + 12);
+    }
+    if (!g.has_rig)
+        g.cam_ext.clear(); // (identities only: the graph runs the kernels it has always run)
     if (g.cams.empty())
     {
         const double z[5] = {1, 1, 0, 0, 0};

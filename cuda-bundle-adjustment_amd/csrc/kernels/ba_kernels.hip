@@ -12,6 +12,7 @@
 // ref: src/cuda/cuda_block_solver.cu — kernels at 1060 (errors), 1152 (quadratic form),
 // 1223 (max diagonal), 1286-1345 (Schur), 1419-1490 (back-substitution, update, scale).
 #include <cmath>
+#include <type_traits>
 
 #include "ba_math.h"
 #include "kernels.h"
@@ -144,6 +145,26 @@ struct DepthPar
     Robust rk; // robust kernel of the depth edge sets
     double s;  // sqrt(inverse-depth weight)
 };
+
+// Camera extrinsics (a rig) ride the same way: the pack is then the one RigPar (behind the view of
+// the landmark priors in k_build_edges), never together with a DepthPar.  cam_ext [n_cams][12] is parallel to the camera
+// table and the slot's camera index (cam[e], the record's meta word) selects the entry.  Instantiations without it hold
+// none of the rig code.
+struct RigPar
+{
+    const double* cam_ext;
+};
+template <typename... P>
+constexpr bool pack_has_rig = (false || ... || std::is_same_v<P, RigPar>);
+// the extrinsic of slot e / of a record's meta word
+__device__ __forceinline__ const double* ext_of_slot(const EV& ev, const RigPar& rp, int e)
+{
+    return ev.n_cams > 1 ? rp.cam_ext + 12 * (int)ev.cam[e] : rp.cam_ext;
+}
+__device__ __forceinline__ const double* ext_of_record(const RigPar& rp, long long meta)
+{
+    return rp.cam_ext + 12 * (int)(meta & 0xFFFF);
+}
 
 struct EdgeIn
 {
@@ -315,14 +336,18 @@ __global__ __launch_bounds__(BS) void k_errors(EV ev, const double* __restrict__
         const uint8_t fl = ev.flags[e];
         if (!(fl & CUGO_EDGE_INACTIVE))
         {
-            constexpr bool DEP = sizeof...(DP) != 0;
+            constexpr bool RIG = pack_has_rig<DP...>;
+            constexpr bool DEP = sizeof...(DP) != 0 && !RIG;
             const EdgeIn in = load_edge<DEP>(ev, e, fl);
             const bool depth = is_depth<DEP>(fl);
             EdgeGeom g;
             // (two calls, here and in the kernels below: the one without the depth kind is written as it always was.
             // Routing it through the template with a helper that picks the robust kernel gave the same arithmetic but
             // other register figures for the instantiations that existed before — tools/kernel_resources.sh)
-            if constexpr (DEP)
+            if constexpr (RIG)
+                edge_residual_rig(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
+                                  in.omega, in.cam, ext_of_slot(ev, first_of(dp...), e), in.stereo ? rk.s : rk.m, g);
+            else if constexpr (DEP)
                 edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
                                       depth, depth_scale_of(dp...), in.omega, in.cam,
                                       in.stereo ? rk.s : (depth ? first_of(dp...).rk : rk.m), g);
@@ -351,11 +376,15 @@ __global__ __launch_bounds__(BS) void k_edge_chi(EV ev, const double* __restrict
     double chi = 0;
     if (!(fl & CUGO_EDGE_INACTIVE))
     {
-        constexpr bool DEP = sizeof...(DP) != 0;
+        constexpr bool RIG = pack_has_rig<DP...>;
+        constexpr bool DEP = sizeof...(DP) != 0 && !RIG;
         const EdgeIn in = load_edge<DEP>(ev, e, fl);
         const bool depth = is_depth<DEP>(fl);
         EdgeGeom g;
-        if constexpr (DEP)
+        if constexpr (RIG)
+            edge_residual_rig(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
+                              in.omega, in.cam, ext_of_slot(ev, first_of(dp...), e), in.stereo ? rk.s : rk.m, g);
+        else if constexpr (DEP)
             edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth,
                                   depth_scale_of(dp...), in.omega, in.cam,
                                   in.stereo ? rk.s : (depth ? first_of(dp...).rk : rk.m), g);
@@ -424,7 +453,8 @@ __device__ __forceinline__ double depth_scale_in(const LP&... lp)
 // LMP: landmark position priors (lm_prior_term.h) ride along: LP is then the one LmPriorView.  The
 // instantiation without them takes the arguments the kernel has always taken (an empty pack) and holds none of their
 // code; both have the register figures above.
-// The pack ends with the one DepthPar where the edge array may hold depth slots (see DepthPar above).
+// The pack ends with the one DepthPar where the edge array may hold depth slots (see DepthPar above), or with the one
+// RigPar where the camera table carries extrinsics (see RigPar above).
 template <typename S, bool LMP, typename... LP>
 __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restrict__ poses,
                                                     const double* __restrict__ lms, Robust2 rk,
@@ -437,8 +467,9 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
                                                     S* __restrict__ T, double* __restrict__ lmrec, LP... lp)
 {
     static_assert(sizeof...(LP) == (LMP ? 1 : 0) || sizeof...(LP) == (LMP ? 2 : 1),
-                  "the view of the landmark priors goes with LMP, the DepthPar behind it");
-    constexpr bool DEP = sizeof...(LP) == (LMP ? 2 : 1);
+                  "the view of the landmark priors goes with LMP, the DepthPar or RigPar behind it");
+    constexpr bool RIG = pack_has_rig<LP...>;
+    constexpr bool DEP = sizeof...(LP) == (LMP ? 2 : 1) && !RIG;
     // fuse_lambda >= 0 (the engine, whose slot layout keeps a landmark inside one workgroup, from the
     // second LM iteration on: the damping of the first trial is known when the build is queued): this
     // pass also leaves invHll = (Hll + lambda I)^-1 and T = Hpl invHll — exactly what k_schur_edges
@@ -481,7 +512,10 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             const double sd = depth_scale_in<DEP>(lp...);
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
-            if constexpr (DEP)
+            if constexpr (RIG)
+                edge_residual_rig(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
+                                  ext_of_slot(ev, last_of(lp...), e), in.stereo ? rk.s : rk.m, g);
+            else if constexpr (DEP)
                 edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
                                       in.cam, in.stereo ? rk.s : (depth ? last_of(lp...).rk : rk.m), g);
             else
@@ -499,12 +533,24 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
                 meta |= (long long)(depth ? 1 : 0) << 18;
             r8[7] = __longlong_as_double(meta);
             double JL[3][3];
-            jac_landmark_k<DEP>(g.Xc, pose, in.cam, in.stereo, depth, sd, JL);
+            double B[RIG ? 3 : 1][3]; // (rig: B = A M, shared by JL and JP)
+            if constexpr (RIG)
+            {
+                double R[3][3];
+                quat_to_rot(pose, R);
+                rig_B(g.Xc, in.cam, ext_of_slot(ev, last_of(lp...), e), in.stereo, true, B);
+                jac_landmark_rig(B, R, JL);
+            }
+            else
+                jac_landmark_k<DEP>(g.Xc, pose, in.cam, in.stereo, depth, sd, JL);
             lc = lm_contrib(JL, g, in.stereo || depth);
             if (!(fl & (CUGO_EDGE_FIXED_L | CUGO_EDGE_FIXED_P)))
             {
                 double JP[3][6];
-                jac_pose_k<DEP>(g.Xc, in.cam, in.stereo, depth, sd, JP);
+                if constexpr (RIG)
+                    jac_pose_rig(g.Xc, B, JP);
+                else
+                    jac_pose_k<DEP>(g.Xc, in.cam, in.stereo, depth, sd, JP);
 #pragma unroll
                 for (int c = 0; c < 3; c++)
 #pragma unroll
@@ -565,14 +611,25 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             const double sd = depth_scale_in<DEP>(lp...);
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
-            if constexpr (DEP)
+            if constexpr (RIG)
+                edge_residual_rig(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
+                                  ext_of_slot(ev, last_of(lp...), ee), in.stereo ? rk.s : rk.m, g);
+            else if constexpr (DEP)
                 edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
                                       in.cam, in.stereo ? rk.s : (depth ? last_of(lp...).rk : rk.m), g);
             else
                 edge_residual(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega,
                               in.cam, in.stereo ? rk.s : rk.m, g);
             double JL[3][3];
-            jac_landmark_k<DEP>(g.Xc, pose, in.cam, in.stereo, depth, sd, JL);
+            if constexpr (RIG)
+            {
+                double R[3][3], B[3][3];
+                quat_to_rot(pose, R);
+                rig_B(g.Xc, in.cam, ext_of_slot(ev, last_of(lp...), ee), in.stereo, true, B);
+                jac_landmark_rig(B, R, JL);
+            }
+            else
+                jac_landmark_k<DEP>(g.Xc, pose, in.cam, in.stereo, depth, sd, JL);
             const LmContrib c2 = lm_contrib(JL, g, in.stereo || depth);
             a[0] += c2.h00, a[1] += c2.h01, a[2] += c2.h02, a[3] += c2.h11, a[4] += c2.h12;
             a[5] += c2.h22, a[6] += c2.b0, a[7] += c2.b1, a[8] += c2.b2;
@@ -759,7 +816,7 @@ __device__ __forceinline__ void wave_reduce32(double (&a)[32])
 // The 27 sums of a wave are formed in registers (wave_reduce32), the four waves' partial sums meet in 1 KB of LDS:
 // 19 KB of LDS per workgroup, so that every pose of a kitti_00-sized graph is resident at once.
 constexpr int BP_W = BS / 64;
-// DS: empty, or sqrt(inverse-depth weight) where the records may carry the depth bit (see DepthPar)
+// DS: empty, sqrt(inverse-depth weight) where the records may carry the depth bit (see DepthPar), or the one RigPar
 template <typename... DS>
 __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restrict__ rec,
                                                     double* __restrict__ Hpp,
@@ -808,7 +865,14 @@ __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restr
             const bool stereo = record_stereo(meta);
             const double* cam = ev.cams + 5 * (int)(meta & 0xFFFF);
             double JP[3][6];
-            jac_pose_k<sizeof...(DS) != 0>(Xc, cam, stereo, record_depth<sizeof...(DS) != 0>(meta), depth_scale_of(ds...), JP);
+            if constexpr (pack_has_rig<DS...>)
+            {
+                double B[3][3];
+                rig_B(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, w != 0.0, B);
+                jac_pose_rig(Xc, B, JP);
+            }
+            else
+                jac_pose_k<sizeof...(DS) != 0>(Xc, cam, stereo, record_depth<sizeof...(DS) != 0>(meta), depth_scale_of(ds...), JP);
             int k = 0;
 #pragma unroll
             for (int rr = 0; rr < 6; rr++)
@@ -885,9 +949,13 @@ __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restr
 // (In the float mode the stored T / Hpl blocks are rounded to float and the off-diagonal blocks are formed from
 // those; the diagonal blocks formed here never see a stored block and come out in full precision.)
 constexpr int PS_W = 4, PS_BS = 64 * PS_W;
-// DS: as for k_build_poses
+// DS: as for k_build_poses.  The rig-aware instantiation holds the entry's twelve doubles and B (nine) while the 33
+// accumulators are live: under (PS_BS, 3) it is capped at 168 registers and spills 140 bytes per lane into a private
+// segment, so it asks for two waves per SIMD (212 registers, no private segment)
 template <typename... DS>
-__global__ __launch_bounds__(PS_BS, 3) void k_pose_schur(EV ev, const double* __restrict__ rec,
+constexpr int PS_WAVES = pack_has_rig<DS...> ? 2 : 3;
+template <typename... DS>
+__global__ __launch_bounds__(PS_BS, PS_WAVES<DS...>) void k_pose_schur(EV ev, const double* __restrict__ rec,
                                                       const double* __restrict__ lmrec,
                                                       const double* __restrict__ poses,
                                                       const int32_t* __restrict__ rowptr, double lambda_diag,
@@ -945,7 +1013,8 @@ __global__ __launch_bounds__(PS_BS, 3) void k_pose_schur(EV ev, const double* __
         const double we[3] = {wgt * r[3], wgt * r[4], wgt * r[5]};
         const long long meta = __double_as_longlong(r[7]);
         wave_sync_lds(); // (the slot is refilled by the next round)
-        constexpr bool DEP = sizeof...(DS) != 0;
+        constexpr bool RIG = pack_has_rig<DS...>;
+        constexpr bool DEP = sizeof...(DS) != 0 && !RIG;
         const bool stereo = record_stereo(meta);
         const bool depth = record_depth<DEP>(meta);
         const bool act = i < i1 && ((meta >> 17) & 1) != 0;
@@ -965,7 +1034,14 @@ __global__ __launch_bounds__(PS_BS, 3) void k_pose_schur(EV ev, const double* __
             for (int a = 0; a < 9; a++)
                 R[a / 3][a % 3] = Rs[a + zero];
             double JL[3][3];
-            jac_landmark_R_k<DEP>(Xc, R, cam, stereo, depth, depth_scale_of(ds...), JL);
+            if constexpr (RIG)
+            {
+                double B[3][3];
+                rig_B(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, wgt != 0.0, B);
+                jac_landmark_rig(B, R, JL);
+            }
+            else
+                jac_landmark_R_k<DEP>(Xc, R, cam, stereo, depth, depth_scale_of(ds...), JL);
             double K[3][3]; // A = JL L^-T:  A[m][j] = sum_{i <= j} JL[m][i] L^-1[j][i]
 #pragma unroll
             for (int m = 0; m < 3; m++)
@@ -995,7 +1071,14 @@ __global__ __launch_bounds__(PS_BS, 3) void k_pose_schur(EV ev, const double* __
         }
         __builtin_amdgcn_sched_barrier(0); // (JL, K and the landmark's line are dead before JP exists: registers)
         double JP[3][6];
-        jac_pose_k<DEP>(Xc, cam, stereo, depth, depth_scale_of(ds...), JP);
+        if constexpr (RIG)
+        { // (B formed again: the same function on the same inputs, and nothing of it lives across the barrier above)
+            double B[3][3];
+            rig_B(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, wgt != 0.0, B);
+            jac_pose_rig(Xc, B, JP);
+        }
+        else
+            jac_pose_k<DEP>(Xc, cam, stereo, depth, depth_scale_of(ds...), JP);
         // (the right-hand sides first: we and u are dead before the 21 block entries are formed)
 #pragma unroll
         for (int rr = 0; rr < 6; rr++)
@@ -2447,12 +2530,24 @@ __device__ __forceinline__ void gT_x_from_record(const double* r8, const double*
     const double w = r8[6];
     const long long bits = __double_as_longlong(r8[7]);
     const double* cam = cams + 5 * (int)(bits & 0xffff);
-    constexpr bool DEP = sizeof...(DS) != 0;
+    constexpr bool RIG = pack_has_rig<DS...>;
+    constexpr bool DEP = sizeof...(DS) != 0 && !RIG;
     const bool stereo = record_stereo(bits);
     const bool depth = record_depth<DEP>(bits);
     double JL[3][3], JP[3][6];
-    jac_landmark_k<DEP>(Xc, pose, cam, stereo, depth, depth_scale_of(ds...), JL);
-    jac_pose_k<DEP>(Xc, cam, stereo, depth, depth_scale_of(ds...), JP);
+    if constexpr (RIG)
+    {
+        double R[3][3], B[3][3];
+        quat_to_rot(pose, R);
+        rig_B(Xc, cam, ext_of_record(first_of(ds...), bits), stereo, w != 0.0, B);
+        jac_landmark_rig(B, R, JL);
+        jac_pose_rig(Xc, B, JP);
+    }
+    else
+    {
+        jac_landmark_k<DEP>(Xc, pose, cam, stereo, depth, depth_scale_of(ds...), JL);
+        jac_pose_k<DEP>(Xc, cam, stereo, depth, depth_scale_of(ds...), JP);
+    }
     const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
     s0 = 0, s1 = 0, s2 = 0;
 #pragma unroll
@@ -2661,13 +2756,18 @@ static DepthPar depth_par(const cugo_edges& e)
 {
     return DepthPar{{e.rk_type_depth, e.rk_delta_depth}, std::sqrt(e.depth_weight)};
 }
+// the extrinsics of an edge view (cugo_edges.has_rig != 0, never together with has_depth: the callers have checked)
+static RigPar rig_par(const cugo_edges& e) { return RigPar{e.d_cam_ext}; }
 
 void launch_errors(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                    cugo_robust rk, ReduceScratch rs, double* d_chi)
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E, BS);
-    if (nb > 0 && e.has_depth)
+    if (nb > 0 && e.has_rig)
+        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials, rig_par(e));
+    else if (nb > 0 && e.has_depth)
         CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials, depth_par(e));
     else if (nb > 0)
@@ -2686,7 +2786,10 @@ void launch_errors_tail(hipStream_t s, const cugo_edges& e, const double* d_pose
     // the scale partials of the update pass sit at the start of the scratch: the error pass uses the
     // record area behind the partial slots (free between two build passes)
     double* d_chi_part = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-    if (nb > 0 && e.has_depth)
+    if (nb > 0 && e.has_rig)
+        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, rig_par(e));
+    else if (nb > 0 && e.has_depth)
         CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, depth_par(e));
     else if (nb > 0)
@@ -2701,7 +2804,10 @@ void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, 
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E, BS);
-    if (nb > 0 && e.has_depth)
+    if (nb > 0 && e.has_rig)
+        CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, rig_par(e));
+    else if (nb > 0 && e.has_depth)
         CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, depth_par(e));
     else if (nb > 0)
@@ -2732,7 +2838,19 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
     // the scale partials of the update pass, which sit at the start of the scratch)
     double* d_chi_part = rs.d_partials + (chi_behind_scale ? spec_chi_offset(ev.E, ev.P, ev.L) : 0);
     const bool lmp = lm_priors && lm_priors->n > 0;
-    if (nb > 0 && e.has_depth)
+    if (nb > 0 && e.has_rig)
+    { // the rig-aware instantiations: only for an edge view whose camera table carries extrinsics
+        ::cugo_k::LaunchScope _scope("k_build_edges", s);
+        if (lmp)
+            hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView, RigPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses,
+                               d_lms, r, d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll,
+                               d_T, d_invHll && d_T ? d_lmrec : nullptr, lm_prior_view(*lm_priors), rig_par(e));
+        else
+            hipLaunchKernelGGL((k_build_edges<S, false, RigPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r,
+                               d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
+                               d_invHll && d_T ? d_lmrec : nullptr, rig_par(e));
+    }
+    else if (nb > 0 && e.has_depth)
     { // the depth-aware instantiations: only for an edge view that says depth slots may be present
         ::cugo_k::LaunchScope _scope("k_build_edges", s);
         if (lmp)
@@ -2764,7 +2882,9 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
     // (launch_schur with SchurRows::d_lmrec); Hpp is then not written
     if (ev.P > 0 && !(skip_poses && d_invHll && d_T && d_lmrec))
     {
-        if (e.has_depth)
+        if (e.has_rig)
+            CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, rig_par(e));
+        else if (e.has_depth)
             CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, depth_par(e).s);
         else
             CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp);
@@ -2891,7 +3011,10 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
     if (ev.P > 0 && have_T && rows.d_lmrec)
     { // fused iteration: diagonal blocks, bp and bsc from the build pass's records (its pose pass was skipped)
         const double* d_rec = rows.rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-        if (e.has_depth)
+        if (e.has_rig)
+            CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
+                        hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc, rig_par(e));
+        else if (e.has_depth)
             CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
                         hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc, depth_par(e).s);
         else
@@ -2960,7 +3083,11 @@ static int launch_backsubst_update_t(hipStream_t s, const cugo_edges& e, double 
         ::cugo_k::LaunchScope _scope("k_backsubst_landmarks", s);
         // from_records: G^T dx_p from the build pass's records in the scratch instead of the G stream
         const double* d_rec = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-        if (from_records && d_lmrec && e.has_depth)
+        if (from_records && d_lmrec && e.has_rig)
+            hipLaunchKernelGGL((k_backsubst_landmarks<S, true, RigPar>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda,
+                               d_invHll, d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
+                               d_poses_in, d_poses_out, d_lmrec, d_rec, rig_par(e));
+        else if (from_records && d_lmrec && e.has_depth)
             hipLaunchKernelGGL((k_backsubst_landmarks<S, true, double>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda,
                                d_invHll, d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
                                d_poses_in, d_poses_out, d_lmrec, d_rec, depth_par(e).s);

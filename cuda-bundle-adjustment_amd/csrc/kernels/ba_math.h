@@ -271,6 +271,90 @@ __device__ __forceinline__ void jac_landmark(const double* Xc, const double* __r
     jac_landmark_k<false>(Xc, q, cam, stereo, false, 0.0, JL);
 }
 
+// ---- camera extrinsics (rig) ---------------------------------------------------------------
+// The pose vertex is world -> body; a camera-table entry carries a fixed sensor pose T_sb = (M, t_s), body -> sensor,
+// as 12 doubles {M row-major, t_s}:  Xb = R(q) Xw + t (world_to_cam, unchanged),  Xs = M Xb + t_s.  The residual is the
+// one above evaluated at Xs; EdgeGeom::Xc (and with it the 64-byte record) keeps holding Xb.  With
+//   A = JP[:, 3:6] of jac_pose at Xs  (= -de/dXs),   B = A M:
+//   JP[:, 3:6] = B,   JP[:, 0:3] = -B [Xb]x   (left update T_b <- exp([w, v]) T_b),   JL = B R(q).
+// Only the rig-aware instantiations of the kernels (cugo_edges.has_rig != 0) hold this code; every pass that needs
+// Xs or B forms them with the functions below, so the record forms repeat the build pass's bits.
+__device__ __forceinline__ void body_to_sensor(const double* __restrict__ ext, const double* Xb, double Xs[3])
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        Xs[r] = ext[3 * r] * Xb[0] + ext[3 * r + 1] * Xb[1] + ext[3 * r + 2] * Xb[2] + ext[9 + r];
+}
+
+// residual, weight and chi of a mono or stereo slot seen through the extrinsic; g.Xc = Xb
+__device__ __forceinline__ void edge_residual_rig(const double* __restrict__ pose, const double* __restrict__ Xw,
+                                                  double mu, double mv, double mr, bool stereo, double omega,
+                                                  const double* __restrict__ cam, const double* __restrict__ ext,
+                                                  const Robust rk, EdgeGeom& g)
+{
+    world_to_cam(pose, Xw, g.Xc);
+    double Xs[3];
+    body_to_sensor(ext, g.Xc, Xs);
+    const double invZ = 1.0 / Xs[2];
+    const double pu = cam[0] * invZ * Xs[0] + cam[2];
+    const double pv = cam[1] * invZ * Xs[1] + cam[3];
+    g.e[0] = pu - mu;
+    g.e[1] = pv - mv;
+    double sq = g.e[0] * g.e[0] + g.e[1] * g.e[1];
+    if (stereo)
+    {
+        g.e[2] = (pu - cam[4] * invZ) - mr;
+        sq += g.e[2] * g.e[2];
+    }
+    else
+        g.e[2] = 0.0;
+    const double x = omega * sq;
+    g.chi = rk_rho(rk, x);
+    g.w = omega * rk_drho(rk, x);
+}
+
+// B = A M from the body-frame point (third row zero for mono).  live = false: zeros, SELECTED — the record of an
+// inactive slot holds Xb = (0, 0, 1) and weight 0, which is a finite point for the plain Jacobians but may have
+// Z_s = 0 behind a sensor pose, and 0 x inf would not do
+__device__ __forceinline__ void rig_B(const double* Xb, const double* __restrict__ cam,
+                                      const double* __restrict__ ext, bool stereo, bool live, double B[3][3])
+{
+    double Xs[3];
+    body_to_sensor(ext, Xb, Xs);
+    double JPs[3][6]; // (only the translation columns are used: the others are never formed)
+    jac_pose(Xs, cam, stereo, JPs);
+#pragma unroll
+    for (int m = 0; m < 3; m++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+        {
+            const double b = JPs[m][3] * ext[j] + JPs[m][4] * ext[3 + j] + JPs[m][5] * ext[6 + j];
+            B[m][j] = live ? b : 0.0;
+        }
+}
+__device__ __forceinline__ void jac_pose_rig(const double* Xb, const double B[3][3], double JP[3][6])
+{
+    const double X = Xb[0], Y = Xb[1], Z = Xb[2];
+#pragma unroll
+    for (int m = 0; m < 3; m++)
+    {
+        JP[m][0] = B[m][2] * Y - B[m][1] * Z;
+        JP[m][1] = B[m][0] * Z - B[m][2] * X;
+        JP[m][2] = B[m][1] * X - B[m][0] * Y;
+        JP[m][3] = B[m][0];
+        JP[m][4] = B[m][1];
+        JP[m][5] = B[m][2];
+    }
+}
+__device__ __forceinline__ void jac_landmark_rig(const double B[3][3], const double R[3][3], double JL[3][3])
+{
+#pragma unroll
+    for (int m = 0; m < 3; m++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            JL[m][j] = B[m][0] * R[0][j] + B[m][1] * R[1][j] + B[m][2] * R[2][j];
+}
+
 // symmetric 3x3 inverse by adjugate, A column-major 9 with lambda added to the diagonal.
 // ref: .cu:639-669 (no pivot / SPD check there either). Returns the 6 unique entries.
 struct Sym3

@@ -56,6 +56,9 @@ struct ReduceScratch
 // the depth-aware instantiation of its kernel iff ev.has_depth != 0 and takes the depth kind's robust kernel and
 // sqrt(ev.depth_weight) from ev; with ev.has_depth == 0 the kernels, and their arguments, are the ones there have
 // always been.  The caller has checked the members (c_api.cpp: check_depth; the engine's come from initialize()).
+// Camera extrinsics the same way: the same launchers pick the rig-aware instantiation iff
+// ev.has_rig != 0 and hand it ev.d_cam_ext ([n_cams][12], parallel to ev.d_cams); never together with ev.has_depth
+// (c_api.cpp: check_depth; the engine's initialize() refuses such a graph).
 void launch_errors(hipStream_t s, const cugo_edges& ev, const double* d_poses, const double* d_lms,
                    cugo_robust rk, ReduceScratch rs, double* d_chi);
 

@@ -51,6 +51,9 @@ public:
     const void* measurementData() const noexcept override { return static_cast<const void*>(measurement.data); }
 };
 
+/** Extension, for both sets below: setSensorPose(T_sb) gives the set's camera a fixed pose body -> sensor and makes the
+ *  pose vertices body poses — one MonoEdgeSet per physical camera is a rig (optimisable_graph.h, BaseEdge::setSensorPose).
+ *  A DepthEdgeSet with a sensor pose other than the identity is refused by initialize() (not yet) */
 class CUGO_API MonoEdgeSet : public EdgeSet<2, Vec2d, PoseVertex, LandmarkVertex>
 {
 };

@@ -155,6 +155,12 @@ public:
                    std::vector<double>& meas3) const;
     /** whether the current flattening holds depth edges, and their inverse-depth weight */
     bool flatDepth(double& weight) const;
+    /** the camera table of the current flattening: 5 intrinsics per entry, and the sensor pose body -> sensor of each
+     *  entry as {M row-major, t_s} (12 per entry; identities where no sensor pose was set).  Returns whether any entry
+     *  is not the identity: only then do the edge kernels see the extrinsics at all.  Diagnostic */
+    bool flatCameras(std::vector<double>& cam5, std::vector<double>& ext12) const;
+    /** entries of that table whose sensor pose is not the identity */
+    int nRigCameras() const;
     /** B, M, nnz(L), flops, supernodes, stages, front bytes, off-diagonal products, then per
      *  factorisation: potrf / trsm / syrk flops, extend-add bytes, backward bytes */
     std::vector<double> structureStats() const;
@@ -205,7 +211,9 @@ public:
      *  of a normalised-innovation test.  cov [n][dim * dim] column-major, dim 2 (mono: u, v) or 3 (stereo: u, v,
      *  u_right); cam5 [nCams][5] = fx, fy, cx, cy, bf with nCams 1 (one camera for all) or n.  A fixed pose contributes
      *  no pose terms, a fixed landmark no landmark terms.  Contract and return value as above; throws
-     *  std::invalid_argument for another dim or nCams. */
+     *  std::invalid_argument for another dim or nCams.  cam5 describes a camera AT THE POSE: on a graph with sensor
+     *  poses (setSensorPose: the pose vertex is then the body) this is the reprojection into a camera whose sensor
+     *  pose is the identity; a rig kind here is a later step. */
     bool reprojectionCovariances(int n, const BaseVertex* const* poses, const BaseVertex* const* landmarks, int dim,
                                  const double* cam5, int nCams, double* cov);
 

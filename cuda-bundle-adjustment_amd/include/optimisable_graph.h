@@ -485,6 +485,12 @@ public:
     virtual void inactivate() noexcept = 0;
     virtual void setActive() noexcept = 0;
     virtual bool isActive() const noexcept = 0;
+    // Extension: the camera's fixed sensor pose T_sb, body -> sensor (Xs = R(q_s) Xb + t_s), for an optimiser whose pose
+    // vertices are world -> body (a multi-camera rig).  It follows the camera: used when
+    // GraphOptimisationOptions::perEdgeCamera is on, otherwise the edge set's.  Default: identity
+    virtual void setSensorPose(const Se3D& T_sb) noexcept = 0;
+    virtual const Se3D& sensorPoseData() const noexcept = 0;
+    virtual Se3D& getSensorPose() noexcept = 0;
 };
 
 // ref: Edge<DIM, E, VertexTypes...> src/optimisable_graph.h:416-503
@@ -546,6 +552,17 @@ public:
         return camera_;
     }
     const Camera& cameraData() const noexcept override { return camera_; }
+    void setSensorPose(const Se3D& T_sb) noexcept override
+    {
+        touchOwner();
+        sensorPose_ = T_sb;
+    }
+    Se3D& getSensorPose() noexcept override
+    {
+        touchOwner();
+        return sensorPose_;
+    }
+    const Se3D& sensorPoseData() const noexcept override { return sensorPose_; }
     void inactivate() noexcept override
     {
         touchOwner();
@@ -562,6 +579,7 @@ protected:
     Measurement measurement;
     Information info_;
     Camera camera_;
+    Se3D sensorPose_; // identity
     BaseVertex* vertices[VertexSize];
     bool isActive_;
 };
@@ -598,6 +616,11 @@ public:
     virtual void setActiveEdgeCount(size_t n) noexcept = 0;
     // set by the optimiser: outliers found since initialize() (ref: currOutlierCount_)
     virtual void setOutlierCount(uint32_t n) noexcept = 0;
+    // Extension: the set's sensor pose T_sb, body -> sensor (see BaseEdge::setSensorPose); default identity.  One
+    // MonoEdgeSet per physical camera, each with its own, is a rig
+    virtual void setSensorPose(const Se3D& T_sb) noexcept = 0;
+    virtual const Se3D& sensorPoseData() const noexcept = 0;
+    virtual Se3D& getSensorPose() noexcept = 0;
 };
 
 inline void BaseEdge::touchOwner() noexcept
@@ -674,6 +697,17 @@ public:
         touch();
         return camera_;
     }
+    void setSensorPose(const Se3D& T_sb) noexcept override
+    {
+        touch();
+        sensorPose_ = T_sb;
+    }
+    Se3D& getSensorPose() noexcept override
+    {
+        touch();
+        return sensorPose_;
+    }
+    const Se3D& sensorPoseData() const noexcept override { return sensorPose_; }
     void setOutlierThreshold(const Scalar t) noexcept
     {
         touch();
@@ -697,6 +731,7 @@ protected:
     uint32_t currOutlierCount_ = 0;
     Information info_ = 0.0;
     Camera camera_;
+    Se3D sensorPose_; // identity
     bool isDirty_ = true;
 };
 

@@ -108,6 +108,15 @@ typedef struct cugo_edges
     int rk_type_depth;     /* CUGO_RK_* */
     double rk_delta_depth;
     double depth_weight;   /* k: the set's inverse-depth weight (1: chi2 of the reference's computeActiveErrors_DepthBa) */
+    /* Extension: camera extrinsics (a multi-camera rig).  The pose is world -> body, and camera-table entry k carries a
+     * fixed sensor pose body -> sensor, d_cam_ext[12 k] = {M row-major (9), t_s (3)}:
+     *   Xb = R(q) Xw + t,  Xs = M Xb + t_s,  residual and robust kernel as always, evaluated at Xs;
+     * the Jacobians are those of the left update on the body pose.  The slot's camera index (d_cam, 16 bits) selects
+     * the entry; with n_cams == 1 entry 0 serves every slot.  has_rig == 0 (every zero-initialised struct): d_cam_ext
+     * is not read and every entry point runs the kernels it has always run.  has_rig != 0 with d_cam_ext == NULL, or
+     * together with has_depth != 0 (not yet), is CUGO_ERR_INVALID before anything is launched. */
+    int has_rig;
+    const double* d_cam_ext; /* [n_cams][12] */
 } cugo_edges;
 
 typedef struct cugo_robust
@@ -673,6 +682,24 @@ int cugo_graph_add_edges(cugo_graph* g, int dim, int n, const int32_t* pose_ids,
 int cugo_graph_set_camera(cugo_graph* g, int dim, const double* cam5);
 int cugo_graph_set_information(cugo_graph* g, int dim, double info);
 int cugo_graph_set_robust_kernel(cugo_graph* g, int dim, int type, double delta);
+/* Extension: camera extrinsics (a multi-camera rig; cugo_edges.has_rig).  The poses are then world -> body, and a
+ * camera carries a fixed sensor pose body -> sensor, q_t7 = (qx, qy, qz, qw, tx, ty, tz): Xs = R(q) Xb + t.  The
+ * extrinsic follows the camera: cugo_graph_set_sensor_pose sets that of the mono (dim 2) or stereo (dim 3) set;
+ * cugo_graph_add_edges_rig is cugo_graph_add_edges with a sensor pose per edge, sensor_q_t7 [n][7].  Like cam5 it
+ * counts on a graph created with per_edge_camera (NULL: these edges keep the identity) and is not looked at on a
+ * graph without, where the set's applies.  The default is the identity, and a graph whose sensor
+ * poses are all identities runs the kernels it has always run.  cugo_graph_initialize normalises the quaternion and
+ * refuses one that is not finite or has norm 0, sensor poses together with depth edges (not yet) and on a
+ * landmark-sharded graph (not yet).  Pose priors, relative-pose and ICP edges act on the pose vertex: the body.
+ * cugo_graph_reprojection_covariances keeps describing a camera at the pose.
+ * cugo_graph_n_rig_cameras: entries of the camera table of the current flattening whose sensor pose is not the
+ * identity.  cugo_graph_get_flat_cameras (diagnostic): that table — returns the number of entries and fills the first
+ * `cap` of cam5 [cap][5] and ext12 [cap][12] = {M row-major, t} where not NULL; *has_rig: what the edge kernels get. */
+int cugo_graph_set_sensor_pose(cugo_graph* g, int dim, const double* q_t7);
+int cugo_graph_add_edges_rig(cugo_graph* g, int dim, int n, const int32_t* pose_ids, const int32_t* landmark_ids,
+                             const double* meas, const double* info, const double* cam5, const double* sensor_q_t7);
+int cugo_graph_n_rig_cameras(cugo_graph* g);
+int cugo_graph_get_flat_cameras(cugo_graph* g, int cap, double* cam5, double* ext12, int* has_rig);
 /* Point-to-plane / point-to-line pose edges (the reference's PlaneEdgeSet / LineEdgeSet, include/icp_types.h), next to
  * or instead of the BA edges; residuals and conventions as for cugo_icp_edges above.  pointP [n][3]; plane: unit normal
  * [n][3] (used as given) and origin_distance [n]; line: two distinct points a, b [n][3]; info [n] or NULL (the set's
