@@ -70,6 +70,24 @@ class RigEdges(Edges):
     _fields_ = [("has_rig", C.c_int), ("d_cam_ext", C.c_void_p)]
 
 
+RIG_NONE, RIG_EXTRINSICS, RIG_MODELS = 0, 1, 2   # cugo_edges.has_rig (CUGO_RIG_*)
+CAM_TAB_STRIDE = 17
+
+
+def camera_model_table(ext12=None, model_k5=None, n=None):
+    """the table d_cam_ext points to under has_rig = RIG_MODELS: [n][17] = {M row-major (9), t_s (3), k1, k2, k3, k4,
+    model}, from ext12 [n][12] (None: identities) and model_k5 [n][5] = (k1, k2, k3, k4, model) (None: pinholes)"""
+    if n is None:
+        n = len(ext12) if ext12 is not None else len(model_k5)
+    tab = np.zeros((n, CAM_TAB_STRIDE))
+    tab[:, :12] = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0.0]) if ext12 is None else np.asarray(ext12, np.float64).reshape(n, 12)
+    if model_k5 is not None:
+        tab[:, 12:] = np.asarray(model_k5, np.float64).reshape(n, 5)
+    if not np.all((tab[:, 16] == 0.0) | (tab[:, 16] == 1.0)):
+        raise CugoError("camera_model_table: model must be 0 (pinhole) or 1 (Kannala-Brandt)")
+    return tab
+
+
 class Robust(C.Structure):
     _fields_ = [("type", C.c_int), ("delta", C.c_double), ("type_stereo", C.c_int),
                 ("delta_stereo", C.c_double)]
@@ -494,8 +512,10 @@ class Graph:
         check(lib().cugo_graph_add_landmarks(self._g, len(ids), _p(ids, _i32p), _p(x, _f64p), _p(f, _u8p)))
         self.lm_ids = np.concatenate([self.lm_ids, ids])
 
-    def add_edges(self, dim, pose_ids, lm_ids, meas, info, cam5=None, sensor=None):
-        """sensor: a sensor pose (q, t) body -> sensor per edge, [n][7] (a rig: the poses are then world -> body); it
+    def add_edges(self, dim, pose_ids, lm_ids, meas, info, cam5=None, sensor=None, model=None):
+        """model: a projection model per edge, [n][5] = (k1, k2, k3, k4, type) with type 0 pinhole / 1 Kannala-Brandt; like
+        cam5 and sensor it follows the camera (per_edge_camera).  None: the set's (set_camera_model).
+        sensor: a sensor pose (q, t) body -> sensor per edge, [n][7] (a rig: the poses are then world -> body); it
         follows the camera, so it counts on a graph with per_edge_camera, like cam5.  None: the set's (set_sensor_pose)"""
         n = len(pose_ids)
         if n == 0:
@@ -504,6 +524,17 @@ class Graph:
         m = np.ascontiguousarray(np.asarray(meas, np.float64)[:, :dim])
         w = np.ascontiguousarray(info, np.float64)
         cam = None if cam5 is None else np.ascontiguousarray(cam5, np.float64)
+        if model is not None:
+            mk = np.ascontiguousarray(model, np.float64)
+            if mk.shape != (n, 5):
+                raise CugoError("add_edges: model must be [n][5] (k1, k2, k3, k4, type)")
+            sx = None if sensor is None else np.ascontiguousarray(sensor, np.float64)
+            if sx is not None and sx.shape != (n, 7):
+                raise CugoError("add_edges: sensor must be [n][7] (qx, qy, qz, qw, tx, ty, tz)")
+            check(lib().cugo_graph_add_edges_model(self._g, dim, n, _p(pi, _i32p), _p(li, _i32p), _p(m, _f64p),
+                                                   _p(w, _f64p), None if cam is None else _p(cam, _f64p),
+                                                   None if sx is None else _p(sx, _f64p), _p(mk, _f64p)))
+            return
         if sensor is None:
             check(lib().cugo_graph_add_edges(self._g, dim, n, _p(pi, _i32p), _p(li, _i32p), _p(m, _f64p),
                                              _p(w, _f64p), None if cam is None else _p(cam, _f64p)))
@@ -520,6 +551,33 @@ class Graph:
         if q.shape != (7,):
             raise CugoError("set_sensor_pose: q_t7 must hold 7 numbers")
         check(lib().cugo_graph_set_sensor_pose(self._g, dim, _p(q, _f64p)))
+
+    def set_camera_model(self, dim, model, k4=None):
+        """the projection model of the mono (dim 2) or stereo (dim 3) set: model 0 pinhole, 1 Kannala-Brandt with the
+        coefficients k4 = (k1, k2, k3, k4) (None: zeros, the equidistant model)"""
+        k = np.zeros(4) if k4 is None else np.ascontiguousarray(k4, np.float64)
+        if k.shape != (4,):
+            raise CugoError("set_camera_model: k4 must hold 4 numbers")
+        check(lib().cugo_graph_set_camera_model(self._g, dim, int(model), _p(k, _f64p)))
+
+    def n_fisheye_cameras(self):
+        """camera-table entries of the current flattening whose model is Kannala-Brandt"""
+        n = lib().cugo_graph_n_fisheye_cameras(self._g)
+        if n < 0:
+            check(n)
+        return n
+
+    def flat_camera_models(self):
+        """the projection models of the camera table of the current flattening, [n][5] = (k1, k2, k3, k4, type),
+        parallel to flat_cameras()"""
+        n = lib().cugo_graph_get_flat_camera_models(self._g, 0, None)
+        if n < 0:
+            check(n)
+        mk = np.zeros((n, 5))
+        rc = lib().cugo_graph_get_flat_camera_models(self._g, n, _p(mk, _f64p))
+        if rc < 0:
+            check(rc)
+        return mk
 
     def n_rig_cameras(self):
         """camera-table entries of the current flattening whose sensor pose is not the identity"""

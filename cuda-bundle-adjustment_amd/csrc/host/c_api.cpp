@@ -1247,9 +1247,22 @@ int cugo_graph_add_landmarks(cugo_graph* g, int n, const int32_t* ids, const dou
         }
     });
 }
-// mono / stereo edges; ext7 [n][7]: a sensor pose (q, t) per edge, or NULL (the set's applies)
+// (k1, k2, k3, k4, model) -> CameraModel; who names the entry point in the message
+static cugo::CameraModel camera_model_of(const char* who, const double* k4, double model)
+{
+    if (model != 0.0 && model != 1.0)
+        throw std::runtime_error(std::string(who) + ": model must be 0 (pinhole) or 1 (Kannala-Brandt)");
+    cugo::CameraModel m;
+    m.type = model != 0.0 ? cugo::KannalaBrandt : cugo::Pinhole;
+    for (int c = 0; c < 4; c++)
+        m.k[c] = k4 ? k4[c] : 0.0;
+    return m;
+}
+// mono / stereo edges; ext7 [n][7]: a sensor pose (q, t) per edge, or NULL (the set's applies); model5 [n][5]: a
+// projection model (k1..k4, type) per edge, or NULL (likewise)
 static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const int32_t* pose_ids, const int32_t* lm_ids,
-                        const double* meas, const double* info, const double* cam5, const double* ext7)
+                        const double* meas, const double* info, const double* cam5, const double* ext7,
+                        const double* model5 = nullptr)
 {
     return guarded([&] {
         if (dim != 2 && dim != 3)
@@ -1261,6 +1274,9 @@ static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const in
             cugo::Se3D ext;
             if (ext7)
                 ext = cugo::Se3D(ext7 + 7 * (size_t)i, ext7 + 7 * (size_t)i + 4);
+            cugo::CameraModel model;
+            if (model5)
+                model = camera_model_of(who, model5 + 5 * (size_t)i, model5[5 * (size_t)i + 4]);
             cugo::Camera cam;
             if (cam5)
                 cam = cugo::Camera(cam5[5 * (size_t)i], cam5[5 * (size_t)i + 1], cam5[5 * (size_t)i + 2],
@@ -1276,6 +1292,8 @@ static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const in
                     e.setCamera(cam);
                 if (ext7)
                     e.setSensorPose(ext);
+                if (model5)
+                    e.setCameraModel(model);
                 g->mono.addEdge(&e);
             }
             else
@@ -1289,6 +1307,8 @@ static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const in
                     e.setCamera(cam);
                 if (ext7)
                     e.setSensorPose(ext);
+                if (model5)
+                    e.setCameraModel(model);
                 g->stereo.addEdge(&e);
             }
         }
@@ -1315,6 +1335,42 @@ int cugo_graph_set_sensor_pose(cugo_graph* g, int dim, const double* q_t7)
         else
             g->mono.setSensorPose(T);
     });
+}
+int cugo_graph_add_edges_model(cugo_graph* g, int dim, int n, const int32_t* pose_ids, const int32_t* lm_ids,
+                               const double* meas, const double* info, const double* cam5, const double* sensor_q_t7,
+                               const double* model_k5)
+{
+    return add_ba_edges(g, "cugo_graph_add_edges_model", dim, n, pose_ids, lm_ids, meas, info, cam5, sensor_q_t7, model_k5);
+}
+int cugo_graph_set_camera_model(cugo_graph* g, int dim, int model, const double* k4)
+{
+    return guarded([&] {
+        if (dim != 2 && dim != 3)
+            throw std::runtime_error("cugo_graph_set_camera_model: dim must be 2 or 3");
+        const cugo::CameraModel m = camera_model_of("cugo_graph_set_camera_model", k4, (double)model);
+        if (dim == 3)
+            g->stereo.setCameraModel(m);
+        else
+            g->mono.setCameraModel(m);
+    });
+}
+int cugo_graph_n_fisheye_cameras(cugo_graph* g)
+{
+    int n = -1;
+    const int rc = guarded([&] { n = g->opt->nFisheyeCameras(); });
+    return rc == CUGO_OK ? n : rc;
+}
+int cugo_graph_get_flat_camera_models(cugo_graph* g, int cap, double* model_k5)
+{
+    int n = -1;
+    const int rc = guarded([&] {
+        std::vector<double> m;
+        g->opt->flatCameraModels(m);
+        n = (int)(m.size() / 5);
+        if (model_k5)
+            std::copy(m.begin(), m.begin() + 5 * (size_t)std::min(n, std::max(cap, 0)), model_k5);
+    });
+    return rc == CUGO_OK ? n : rc;
 }
 int cugo_graph_n_rig_cameras(cugo_graph* g)
 {

@@ -140,6 +140,8 @@ struct Engine::Impl : cugo_k::LaunchHook
     int max_row_nnz = 0;
     DevBuf<double> d_meas, d_omega, d_cams, d_cam_ext; // (d_cam_ext: FlatGraph::cam_ext, only with has_rig)
     bool has_rig = false;
+    bool has_models = false;         // d_cam_ext then holds the model table (stride 17) assembled below
+    std::vector<double> h_cam_tab;
     DevBuf<uint8_t> d_flags;
     DevBuf<uint16_t> d_cam;
     DevBuf<double> d_poses[2], d_lms[2];
@@ -1147,7 +1149,9 @@ struct Engine::Impl::SlotUpload
         const SlotArrays& sl = m.slots;
         f(m.d_e_pose, sl.pose), f(m.d_e_lm, sl.lm), f(m.d_flags, sl.flags), f(m.d_lm_ptr, m.h_lm_ptr);
         f(m.d_meas, sl.meas), f(m.d_omega, sl.omega), f(m.d_cams, g.cams);
-        if (g.has_rig) // the extrinsics go up with the cameras (a table parallel to them)
+        if (g.has_models) // the model table takes the extrinsics' place
+            f(m.d_cam_ext, m.h_cam_tab);
+        else if (g.has_rig) // the extrinsics go up with the cameras (a table parallel to them)
             f(m.d_cam_ext, g.cam_ext);
         if (sl.n_cams > 1)
             f(m.d_cam, sl.cam);
@@ -1214,6 +1218,28 @@ void Engine::initialize(FlatGraph& g)
         throw std::runtime_error("cugo: camera extrinsics (sensor poses) are not supported on a landmark-sharded "
                                  "(multi-GPU) optimiser yet");
     m.has_rig = g.has_rig;
+    if (g.has_models && g.cam_model.size() != 5 * (g.cams.size() / 5))
+        throw std::runtime_error("cugo: camera models: the table must hold 5 numbers per camera");
+    if (g.has_models && g.has_depth)
+        throw std::runtime_error("cugo: camera models (Kannala-Brandt) together with depth edge sets are not supported "
+                                 "yet");
+    if (g.has_models && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: camera models (Kannala-Brandt) are not supported on a landmark-sharded "
+                                 "(multi-GPU) optimiser yet");
+    m.has_models = g.has_models;
+    m.h_cam_tab.clear();
+    if (g.has_models)
+    { // {M, t_s, k1..k4, type} per entry; a graph whose sensor poses are all identities has no cam_ext
+        static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+        const size_t n = g.cams.size() / 5;
+        m.h_cam_tab.resize(CUGO_CAM_TAB_STRIDE * n);
+        for (size_t k = 0; k < n; k++)
+        {
+            const double* x = g.has_rig ? &g.cam_ext[12 * k] : I12;
+            std::copy(x, x + 12, &m.h_cam_tab[CUGO_CAM_TAB_STRIDE * k]);
+            std::copy(&g.cam_model[5 * k], &g.cam_model[5 * k] + 5, &m.h_cam_tab[CUGO_CAM_TAB_STRIDE * k + 12]);
+        }
+    }
     // (k_hsc_offdiag_strip reads the list entry before a block's range: a pair block without products has none)
     if (n_relpose && m.opt.hsc_strip)
         throw std::runtime_error("cugo: relative-pose edge sets cannot be combined with CUGO_HSC_STRIP=1: the row-strip "
@@ -1281,7 +1307,8 @@ void Engine::initialize(FlatGraph& g)
     ev.n_cams = m.slots.n_cams, ev.d_lm_ptr = m.d_lm_ptr.data(), ev.d_pose_ptr = m.d_pose_ptr.data();
     ev.d_pose_edge = m.d_pose_edge.data();
     // (every launcher of an edge pass picks its rig-aware instantiation from this)
-    ev.has_rig = m.has_rig ? 1 : 0, ev.d_cam_ext = m.has_rig ? m.d_cam_ext.data() : nullptr;
+    ev.has_rig = m.has_models ? CUGO_RIG_MODELS : m.has_rig ? CUGO_RIG_EXTRINSICS : CUGO_RIG_NONE;
+    ev.d_cam_ext = m.has_models || m.has_rig ? m.d_cam_ext.data() : nullptr;
     // opt-in (CUGO_HSC_ROWS=1): the Schur complement by whole block rows (k_hsc_rows; slower)
     m.rows_on = !m.plan_only && m.opt.hsc_rows && !m.opt.schur_plan;
     if (m.rows_on)

@@ -112,6 +112,11 @@ struct FlatGraph
     // as {M row-major, t_s}, n_cams x 12 (or empty: all identity); has_rig iff one of them is not exactly identity
     std::vector<double> cam_ext;
     bool has_rig = false;
+    // camera models (Kannala-Brandt; cugo_edges.has_rig == CUGO_RIG_MODELS): per camera-table entry (k1, k2, k3, k4,
+    // type), n_cams x 5 (or empty: all pinhole); has_models iff one of them is not a pinhole.  The engine then hands the
+    // kernels ONE table of stride 17 assembled from cam_ext (identities where that is empty) and this
+    std::vector<double> cam_model;
+    bool has_models = false;
     cugo_robust rk{CUGO_RK_NONE, 1.0, CUGO_RK_NONE, 1.0};
     // depth edge sets (flag bit CUGO_EDGE_DEPTH; cugo_edges.has_depth and the members behind it): whether the graph has
     // any, their robust kernel and their inverse-depth weight

@@ -103,6 +103,23 @@ bool CudaGraphOptimisationImpl::flatCameras(std::vector<double>& cam5, std::vect
             ext12.insert(ext12.end(), I12, I12 + 12);
     return g.has_rig;
 }
+bool CudaGraphOptimisationImpl::flatCameraModels(std::vector<double>& model_k5) const
+{
+    const FlatGraph& g = engine_->staging();
+    model_k5 = g.cam_model;
+    if (!g.has_models)
+        model_k5.assign(5 * (g.cams.size() / 5), 0.0); // (k = 0, type Pinhole)
+    return g.has_models;
+}
+int CudaGraphOptimisationImpl::nFisheyeCameras() const
+{
+    const FlatGraph& g = engine_->staging();
+    int n = 0;
+    if (g.has_models)
+        for (size_t k = 0; k < g.cam_model.size() / 5; k++)
+            n += g.cam_model[5 * k + 4] != 0.0 ? 1 : 0;
+    return n;
+}
 int CudaGraphOptimisationImpl::nRigCameras() const
 {
     std::vector<double> cams, x;
@@ -510,6 +527,7 @@ void CudaGraphOptimisationImpl::initialize()
     }
     g.cams.clear();
     g.cam_ext.clear(), g.has_rig = false;
+    g.cam_model.clear(), g.has_models = false;
     // ---- vertex indices: free first (ascending id), fixed after -------------------------
     int nPfree = 0, nLfree = 0, nP = 0, nL = 0;
     for (BaseVertexSet* vs : vertexSets)
@@ -574,11 +592,13 @@ void CudaGraphOptimisationImpl::initialize()
         std::vector<double> cams;     // distinct cameras of this chunk (CK each: see below), first-seen order
         bool uniform = true;
         bool too_many_cams = false;
+        bool fisheye_3d = false;      // a Kannala-Brandt model met on a 3-d (stereo or depth) edge
     };
-    // A camera-table entry is keyed on CK = 5 + 7 numbers: the intrinsics and the sensor pose (q, t) as the caller gave
-    // it.  Two entries with the same intrinsics and different extrinsics are different entries; the key table is split
-    // into g.cams and g.cam_ext behind the walk.
-    constexpr size_t CK = 12;
+    // A camera-table entry is keyed on CK = 5 + 7 + 5 numbers: the intrinsics, the sensor pose (q, t) as the caller gave
+    // it, and the projection model (k1..k4, type; a pinhole's coefficients are not looked at and count as zeros).  Two
+    // entries that differ in any of them are different entries; the key table is split into g.cams, g.cam_ext and
+    // g.cam_model behind the walk.
+    constexpr size_t CK = 17;
     std::vector<double> camKeys;
     const unsigned hw = cugo_host::pool_threads();
     lap("graph: edge array alloc");
@@ -660,6 +680,7 @@ void CudaGraphOptimisationImpl::initialize()
         const double set_info = es->informationValue();
         const Camera set_cam = es->cameraData();
         const Se3D set_ext = es->sensorPoseData();
+        const CameraModel set_model = es->cameraModelData();
         const EdgeContainer& ec = es->get();
         const size_t n = ec.size();
         const unsigned nthreads = n < 20000 ? 1u : hw;
@@ -708,8 +729,14 @@ void CudaGraphOptimisationImpl::initialize()
                 g.e_omega[o] = w;
                 const Camera& cm = perCam ? e->cameraData() : set_cam;
                 const Se3D& sx = perCam ? e->sensorPoseData() : set_ext;
+                const CameraModel& md = perCam ? e->cameraModelData() : set_model;
+                const bool kb = md.type != Pinhole;
+                if (kb && dim == 3)
+                    c.fisheye_3d = true;
                 const double cv[CK] = {cm.fx,        cm.fy,        cm.cx,        cm.cy,        cm.bf,        sx.r.data[0],
-                                       sx.r.data[1], sx.r.data[2], sx.r.data[3], sx.t.data[0], sx.t.data[1], sx.t.data[2]};
+                                       sx.r.data[1], sx.r.data[2], sx.r.data[3], sx.t.data[0], sx.t.data[1], sx.t.data[2],
+                                       kb ? md.k[0] : 0.0, kb ? md.k[1] : 0.0, kb ? md.k[2] : 0.0, kb ? md.k[3] : 0.0,
+                                       (double)(int)md.type};
                 // deduplicate cameras: last-hit fast path, then a short linear scan
                 int ci = -1;
                 const size_t ncam = c.cams.size() / CK;
@@ -752,6 +779,12 @@ void CudaGraphOptimisationImpl::initialize()
         {
             if (c.too_many_cams)
                 throw std::runtime_error("cugo: more than 65535 distinct cameras");
+            if (c.fisheye_3d)
+                throw std::runtime_error(
+                    ds ? "cugo: camera models (Kannala-Brandt) together with depth edge sets are not supported yet (edge set " +
+                             std::to_string(si) + ")"
+                       : "cugo: a Kannala-Brandt camera model on a stereo edge set is not defined: bf has no meaning there "
+                         "(edge set " + std::to_string(si) + ")");
             // merge this chunk's cameras into the global table (first-seen order is kept)
             std::vector<uint16_t> remap(c.cams.size() / CK);
             bool identity = true;
@@ -828,7 +861,23 @@ void CudaGraphOptimisationImpl::initialize()
         for (int c = 0; c < 12; c++)
             g.has_rig = g.has_rig || M[c] != I12[c];
         g.cam_ext.insert(g.cam_ext.end(), M, M + 12);
+        // the model: (k1, k2, k3, k4, type); has_models iff some entry is not a pinhole
+        const int type = (int)key[16];
+        if (type != (int)Pinhole && type != (int)KannalaBrandt)
+            throw std::runtime_error("cugo: camera model of camera-table entry " + std::to_string(k) +
+                                     ": unknown model type " + std::to_string(type));
+        for (int c = 12; c < 16; c++)
+            if (!std::isfinite(key[c]))
+                throw std::runtime_error("cugo: camera model (Kannala-Brandt) of camera-table entry " + std::to_string(k) +
+                                         ": the coefficients k1..k4 must be finite");
+        g.has_models = g.has_models || type != (int)Pinhole;
+        g.cam_model.insert(g.cam_model.end(), key + 12, key + 17);
     }
+    if (g.has_models && g.has_depth)
+        throw std::runtime_error("cugo: camera models (Kannala-Brandt) together with depth edge sets are not supported "
+                                 "yet");
+    if (!g.has_models)
+        g.cam_model.clear(); // (pinholes only: the graph runs the kernels it has always run)
     if (!g.has_rig)
         g.cam_ext.clear(); // (identities only: the graph runs the kernels it has always run)
     if (g.cams.empty())

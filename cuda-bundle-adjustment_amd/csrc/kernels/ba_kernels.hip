@@ -154,8 +154,18 @@ struct RigPar
 {
     const double* cam_ext;
 };
+// A MODEL table (cugo_edges.has_rig == CUGO_RIG_MODELS) takes RigPar's place: cam_tab
+// [n_cams][17] = {the entry's 12 numbers, k1..k4, model flag}.  It carries the extrinsic as well, so a fisheye rig is
+// one instantiation.  An entry whose flag is 0 runs RigPar's operations in RigPar's order.
+struct CamModelPar
+{
+    const double* cam_tab;
+};
 template <typename... P>
-constexpr bool pack_has_rig = (false || ... || std::is_same_v<P, RigPar>);
+constexpr bool pack_has_model = (false || ... || std::is_same_v<P, CamModelPar>);
+// (the rig code below serves both packs: what differs is the stride and what edge_residual_rig / rig_B do with the entry)
+template <typename... P>
+constexpr bool pack_has_rig = (false || ... || (std::is_same_v<P, RigPar> || std::is_same_v<P, CamModelPar>));
 // the extrinsic of slot e / of a record's meta word
 __device__ __forceinline__ const double* ext_of_slot(const EV& ev, const RigPar& rp, int e)
 {
@@ -164,6 +174,14 @@ __device__ __forceinline__ const double* ext_of_slot(const EV& ev, const RigPar&
 __device__ __forceinline__ const double* ext_of_record(const RigPar& rp, long long meta)
 {
     return rp.cam_ext + 12 * (int)(meta & 0xFFFF);
+}
+__device__ __forceinline__ const double* ext_of_slot(const EV& ev, const CamModelPar& mp, int e)
+{
+    return ev.n_cams > 1 ? mp.cam_tab + 17 * (int)ev.cam[e] : mp.cam_tab;
+}
+__device__ __forceinline__ const double* ext_of_record(const CamModelPar& mp, long long meta)
+{
+    return mp.cam_tab + 17 * (int)(meta & 0xFFFF);
 }
 
 struct EdgeIn
@@ -345,7 +363,7 @@ __global__ __launch_bounds__(BS) void k_errors(EV ev, const double* __restrict__
             // Routing it through the template with a helper that picks the robust kernel gave the same arithmetic but
             // other register figures for the instantiations that existed before — tools/kernel_resources.sh)
             if constexpr (RIG)
-                edge_residual_rig(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
+                edge_residual_rig<pack_has_model<DP...>>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
                                   in.omega, in.cam, ext_of_slot(ev, first_of(dp...), e), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
@@ -382,7 +400,7 @@ __global__ __launch_bounds__(BS) void k_edge_chi(EV ev, const double* __restrict
         const bool depth = is_depth<DEP>(fl);
         EdgeGeom g;
         if constexpr (RIG)
-            edge_residual_rig(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
+            edge_residual_rig<pack_has_model<DP...>>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
                               in.omega, in.cam, ext_of_slot(ev, first_of(dp...), e), in.stereo ? rk.s : rk.m, g);
         else if constexpr (DEP)
             edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth,
@@ -513,7 +531,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
             if constexpr (RIG)
-                edge_residual_rig(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
+                edge_residual_rig<pack_has_model<LP...>>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
                                   ext_of_slot(ev, last_of(lp...), e), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
@@ -538,7 +556,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             {
                 double R[3][3];
                 quat_to_rot(pose, R);
-                rig_B(g.Xc, in.cam, ext_of_slot(ev, last_of(lp...), e), in.stereo, true, B);
+                rig_B<pack_has_model<LP...>>(g.Xc, in.cam, ext_of_slot(ev, last_of(lp...), e), in.stereo, true, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -612,7 +630,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
             if constexpr (RIG)
-                edge_residual_rig(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
+                edge_residual_rig<pack_has_model<LP...>>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
                                   ext_of_slot(ev, last_of(lp...), ee), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
@@ -625,7 +643,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             {
                 double R[3][3], B[3][3];
                 quat_to_rot(pose, R);
-                rig_B(g.Xc, in.cam, ext_of_slot(ev, last_of(lp...), ee), in.stereo, true, B);
+                rig_B<pack_has_model<LP...>>(g.Xc, in.cam, ext_of_slot(ev, last_of(lp...), ee), in.stereo, true, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -868,7 +886,7 @@ __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restr
             if constexpr (pack_has_rig<DS...>)
             {
                 double B[3][3];
-                rig_B(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, w != 0.0, B);
+                rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, w != 0.0, B);
                 jac_pose_rig(Xc, B, JP);
             }
             else
@@ -1037,7 +1055,7 @@ __global__ __launch_bounds__(PS_BS, PS_WAVES<DS...>) void k_pose_schur(EV ev, co
             if constexpr (RIG)
             {
                 double B[3][3];
-                rig_B(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, wgt != 0.0, B);
+                rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, wgt != 0.0, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -1074,7 +1092,7 @@ __global__ __launch_bounds__(PS_BS, PS_WAVES<DS...>) void k_pose_schur(EV ev, co
         if constexpr (RIG)
         { // (B formed again: the same function on the same inputs, and nothing of it lives across the barrier above)
             double B[3][3];
-            rig_B(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, wgt != 0.0, B);
+            rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, wgt != 0.0, B);
             jac_pose_rig(Xc, B, JP);
         }
         else
@@ -2539,7 +2557,7 @@ __device__ __forceinline__ void gT_x_from_record(const double* r8, const double*
     {
         double R[3][3], B[3][3];
         quat_to_rot(pose, R);
-        rig_B(Xc, cam, ext_of_record(first_of(ds...), bits), stereo, w != 0.0, B);
+        rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(first_of(ds...), bits), stereo, w != 0.0, B);
         jac_landmark_rig(B, R, JL);
         jac_pose_rig(Xc, B, JP);
     }
@@ -2758,13 +2776,19 @@ static DepthPar depth_par(const cugo_edges& e)
 }
 // the extrinsics of an edge view (cugo_edges.has_rig != 0, never together with has_depth: the callers have checked)
 static RigPar rig_par(const cugo_edges& e) { return RigPar{e.d_cam_ext}; }
+// has_rig == CUGO_RIG_MODELS: d_cam_ext is a model table, stride 17 (the launchers below pick CamModelPar iff so)
+static CamModelPar model_par(const cugo_edges& e) { return CamModelPar{e.d_cam_ext}; }
+static bool has_models(const cugo_edges& e) { return e.has_rig == CUGO_RIG_MODELS; }
 
 void launch_errors(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                    cugo_robust rk, ReduceScratch rs, double* d_chi)
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E, BS);
-    if (nb > 0 && e.has_rig)
+    if (nb > 0 && has_models(e))
+        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials, model_par(e));
+    else if (nb > 0 && e.has_rig)
         CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials, rig_par(e));
     else if (nb > 0 && e.has_depth)
@@ -2786,7 +2810,10 @@ void launch_errors_tail(hipStream_t s, const cugo_edges& e, const double* d_pose
     // the scale partials of the update pass sit at the start of the scratch: the error pass uses the
     // record area behind the partial slots (free between two build passes)
     double* d_chi_part = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-    if (nb > 0 && e.has_rig)
+    if (nb > 0 && has_models(e))
+        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, model_par(e));
+    else if (nb > 0 && e.has_rig)
         CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, rig_par(e));
     else if (nb > 0 && e.has_depth)
@@ -2804,7 +2831,10 @@ void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, 
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E, BS);
-    if (nb > 0 && e.has_rig)
+    if (nb > 0 && has_models(e))
+        CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, model_par(e));
+    else if (nb > 0 && e.has_rig)
         CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
                            Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, rig_par(e));
     else if (nb > 0 && e.has_depth)
@@ -2838,7 +2868,19 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
     // the scale partials of the update pass, which sit at the start of the scratch)
     double* d_chi_part = rs.d_partials + (chi_behind_scale ? spec_chi_offset(ev.E, ev.P, ev.L) : 0);
     const bool lmp = lm_priors && lm_priors->n > 0;
-    if (nb > 0 && e.has_rig)
+    if (nb > 0 && has_models(e))
+    { // the same with a model table (Kannala-Brandt entries)
+        ::cugo_k::LaunchScope _scope("k_build_edges", s);
+        if (lmp)
+            hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView, CamModelPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses,
+                               d_lms, r, d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll,
+                               d_T, d_invHll && d_T ? d_lmrec : nullptr, lm_prior_view(*lm_priors), model_par(e));
+        else
+            hipLaunchKernelGGL((k_build_edges<S, false, CamModelPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r,
+                               d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
+                               d_invHll && d_T ? d_lmrec : nullptr, model_par(e));
+    }
+    else if (nb > 0 && e.has_rig)
     { // the rig-aware instantiations: only for an edge view whose camera table carries extrinsics
         ::cugo_k::LaunchScope _scope("k_build_edges", s);
         if (lmp)
@@ -2882,7 +2924,9 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
     // (launch_schur with SchurRows::d_lmrec); Hpp is then not written
     if (ev.P > 0 && !(skip_poses && d_invHll && d_T && d_lmrec))
     {
-        if (e.has_rig)
+        if (has_models(e))
+            CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, model_par(e));
+        else if (e.has_rig)
             CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, rig_par(e));
         else if (e.has_depth)
             CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, depth_par(e).s);
@@ -3011,7 +3055,10 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
     if (ev.P > 0 && have_T && rows.d_lmrec)
     { // fused iteration: diagonal blocks, bp and bsc from the build pass's records (its pose pass was skipped)
         const double* d_rec = rows.rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-        if (e.has_rig)
+        if (has_models(e))
+            CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
+                        hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc, model_par(e));
+        else if (e.has_rig)
             CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
                         hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc, rig_par(e));
         else if (e.has_depth)
@@ -3083,7 +3130,11 @@ static int launch_backsubst_update_t(hipStream_t s, const cugo_edges& e, double 
         ::cugo_k::LaunchScope _scope("k_backsubst_landmarks", s);
         // from_records: G^T dx_p from the build pass's records in the scratch instead of the G stream
         const double* d_rec = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-        if (from_records && d_lmrec && e.has_rig)
+        if (from_records && d_lmrec && has_models(e))
+            hipLaunchKernelGGL((k_backsubst_landmarks<S, true, CamModelPar>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda,
+                               d_invHll, d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
+                               d_poses_in, d_poses_out, d_lmrec, d_rec, model_par(e));
+        else if (from_records && d_lmrec && e.has_rig)
             hipLaunchKernelGGL((k_backsubst_landmarks<S, true, RigPar>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda,
                                d_invHll, d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
                                d_poses_in, d_poses_out, d_lmrec, d_rec, rig_par(e));

@@ -286,7 +286,62 @@ __device__ __forceinline__ void body_to_sensor(const double* __restrict__ ext, c
         Xs[r] = ext[3 * r] * Xb[0] + ext[3 * r + 1] * Xb[1] + ext[3 * r + 2] * Xb[2] + ext[9 + r];
 }
 
-// residual, weight and chi of a mono or stereo slot seen through the extrinsic; g.Xc = Xb
+// ---- Kannala-Brandt fisheye entries ---------------------------------------------------------
+// A camera-table entry of a MODEL table (cugo_edges.has_rig == CUGO_RIG_MODELS) is 17 doubles: the 12 above, then
+// k1..k4 and the model flag (0.0 pinhole, 1.0 Kannala-Brandt).  For a Kannala-Brandt entry, at Xs = (x, y, z):
+//   r2 = x^2 + y^2,  R2 = r2 + z^2,  th = atan2(r, z),  t2 = th^2
+//   P = 1 + k1 t2 + k2 t2^2 + k3 t2^3 + k4 t2^4          (theta_d = th P)
+//   Q = dP/dt2 = k1 + 2 k2 t2 + 3 k3 t2^2 + 4 k4 t2^3,   D = d theta_d / d th = P + 2 t2 Q
+//   g = th / r  (1 / z at r == 0),   rho = g P,   pu = fx rho x + cx,   pv = fy rho y + cy
+//   c = (D z / R2 - rho) / r2                                                   th >= KB_NEAR_AXIS
+//   c = g^2 (4 g P S(4 t2) + 2 Q z / R2),  S(w) = sum_{n>=1} (-1)^n w^(n-1) / (2n+1)!   th <  KB_NEAR_AXIS
+// The second form is the first with  z / R2 - th / r = (sin 2th - 2th) / (2 r)  expanded: no difference of nearly equal
+// terms and no division by r, so it holds at r == 0 (c = -2 / (3 z^3) for k = 0).  Below the switch z > 0; above it
+// nothing divides by z.  The switch and the nine terms of S: DESIGN.md section 19.
+constexpr double KB_NEAR_AXIS = 0.5; // rad
+struct KbTerms
+{
+    double rho, c, dR; // dR = D / R2
+};
+__device__ __forceinline__ KbTerms kb_terms(const double* Xs, const double* __restrict__ k)
+{
+    const double x = Xs[0], y = Xs[1], z = Xs[2];
+    const double r2 = x * x + y * y;
+    const double r = sqrt(r2);
+    const double R2 = r2 + z * z;
+    const double th = atan2(r, z);
+    const double t2 = th * th;
+    const double P = 1.0 + t2 * (k[0] + t2 * (k[1] + t2 * (k[2] + t2 * k[3])));
+    const double Q = k[0] + t2 * (2.0 * k[1] + t2 * (3.0 * k[2] + t2 * (4.0 * k[3])));
+    const double D = P + 2.0 * t2 * Q;
+    const double g = r > 0.0 ? th / r : 1.0 / z;
+    KbTerms o;
+    o.rho = g * P;
+    o.dR = D / R2;
+    if (th < KB_NEAR_AXIS)
+    {
+        const double w = 4.0 * t2;
+        // S(w), n = 9 down to 1: (-1)^n / (2n+1)!
+        double S = -1.0 / 121645100408832000.0;
+        S = S * w + 1.0 / 355687428096000.0;
+        S = S * w - 1.0 / 1307674368000.0;
+        S = S * w + 1.0 / 6227020800.0;
+        S = S * w - 1.0 / 39916800.0;
+        S = S * w + 1.0 / 362880.0;
+        S = S * w - 1.0 / 5040.0;
+        S = S * w + 1.0 / 120.0;
+        S = S * w - 1.0 / 6.0;
+        o.c = (g * g) * (4.0 * g * P * S + 2.0 * Q * (z / R2));
+    }
+    else
+        o.c = (o.dR * z - o.rho) / r2;
+    return o;
+}
+
+// residual, weight and chi of a mono or stereo slot seen through the extrinsic; g.Xc = Xb.
+// KB: ext is an entry of a model table (17 doubles); an entry whose flag is 0 takes the path below, operation for
+// operation.  A Kannala-Brandt entry has no third row: bf means nothing there and the stereo bit is not looked at.
+template <bool KB = false>
 __device__ __forceinline__ void edge_residual_rig(const double* __restrict__ pose, const double* __restrict__ Xw,
                                                   double mu, double mv, double mr, bool stereo, double omega,
                                                   const double* __restrict__ cam, const double* __restrict__ ext,
@@ -295,6 +350,18 @@ __device__ __forceinline__ void edge_residual_rig(const double* __restrict__ pos
     world_to_cam(pose, Xw, g.Xc);
     double Xs[3];
     body_to_sensor(ext, g.Xc, Xs);
+    if constexpr (KB)
+        if (ext[16] != 0.0)
+        {
+            const KbTerms kt = kb_terms(Xs, ext + 12);
+            g.e[0] = (cam[0] * kt.rho * Xs[0] + cam[2]) - mu;
+            g.e[1] = (cam[1] * kt.rho * Xs[1] + cam[3]) - mv;
+            g.e[2] = 0.0;
+            const double xk = omega * (g.e[0] * g.e[0] + g.e[1] * g.e[1]);
+            g.chi = rk_rho(rk, xk);
+            g.w = omega * rk_drho(rk, xk);
+            return;
+        }
     const double invZ = 1.0 / Xs[2];
     const double pu = cam[0] * invZ * Xs[0] + cam[2];
     const double pv = cam[1] * invZ * Xs[1] + cam[3];
@@ -316,11 +383,37 @@ __device__ __forceinline__ void edge_residual_rig(const double* __restrict__ pos
 // B = A M from the body-frame point (third row zero for mono).  live = false: zeros, SELECTED — the record of an
 // inactive slot holds Xb = (0, 0, 1) and weight 0, which is a finite point for the plain Jacobians but may have
 // Z_s = 0 behind a sensor pose, and 0 x inf would not do
+// KB: as for edge_residual_rig; for a Kannala-Brandt entry A = -d(pu, pv)/dXs, third row zero:
+//   A[0] = -fx (rho + x^2 c,  x y c,  -x D / R2),   A[1] = -fy (x y c,  rho + y^2 c,  -y D / R2)
+template <bool KB = false>
 __device__ __forceinline__ void rig_B(const double* Xb, const double* __restrict__ cam,
                                       const double* __restrict__ ext, bool stereo, bool live, double B[3][3])
 {
     double Xs[3];
     body_to_sensor(ext, Xb, Xs);
+    if constexpr (KB)
+        if (ext[16] != 0.0)
+        {
+            const KbTerms kt = kb_terms(Xs, ext + 12);
+            const double xc = Xs[0] * kt.c, yc = Xs[1] * kt.c;
+            double A[2][3];
+            A[0][0] = -(cam[0] * (kt.rho + Xs[0] * xc));
+            A[0][1] = -(cam[0] * (Xs[1] * xc));
+            A[0][2] = cam[0] * (Xs[0] * kt.dR);
+            A[1][0] = -(cam[1] * (Xs[0] * yc));
+            A[1][1] = -(cam[1] * (kt.rho + Xs[1] * yc));
+            A[1][2] = cam[1] * (Xs[1] * kt.dR);
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+            {
+                const double b0 = A[0][0] * ext[j] + A[0][1] * ext[3 + j] + A[0][2] * ext[6 + j];
+                const double b1 = A[1][0] * ext[j] + A[1][1] * ext[3 + j] + A[1][2] * ext[6 + j];
+                B[0][j] = live ? b0 : 0.0;
+                B[1][j] = live ? b1 : 0.0;
+                B[2][j] = 0.0;
+            }
+            return;
+        }
     double JPs[3][6]; // (only the translation columns are used: the others are never formed)
     jac_pose(Xs, cam, stereo, JPs);
 #pragma unroll

@@ -59,6 +59,8 @@ struct ReduceScratch
 // Camera extrinsics the same way: the same launchers pick the rig-aware instantiation iff
 // ev.has_rig != 0 and hand it ev.d_cam_ext ([n_cams][12], parallel to ev.d_cams); never together with ev.has_depth
 // (c_api.cpp: check_depth; the engine's initialize() refuses such a graph).
+// Camera models: iff ev.has_rig == CUGO_RIG_MODELS the same launchers pick the instantiation
+// with CamModelPar instead, and ev.d_cam_ext is then the model table [n_cams][17].
 void launch_errors(hipStream_t s, const cugo_edges& ev, const double* d_poses, const double* d_lms,
                    cugo_robust rk, ReduceScratch rs, double* d_chi);
 

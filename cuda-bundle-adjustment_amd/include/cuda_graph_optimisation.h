@@ -161,6 +161,12 @@ public:
     bool flatCameras(std::vector<double>& cam5, std::vector<double>& ext12) const;
     /** entries of that table whose sensor pose is not the identity */
     int nRigCameras() const;
+    /** the projection models of that table (camera_model.h), parallel to flatCameras(): (k1, k2, k3, k4, type) per entry,
+     *  type 0 Pinhole / 1 KannalaBrandt.  Returns whether any entry is not a pinhole: only then do the edge kernels get
+     *  the model table (cugo_edges.has_rig == CUGO_RIG_MODELS), sensor poses included even if all are identities */
+    bool flatCameraModels(std::vector<double>& model_k5) const;
+    /** entries of that table whose model is KannalaBrandt */
+    int nFisheyeCameras() const;
     /** B, M, nnz(L), flops, supernodes, stages, front bytes, off-diagonal products, then per
      *  factorisation: potrf / trsm / syrk flops, extend-add bytes, backward bytes */
     std::vector<double> structureStats() const;
@@ -213,7 +219,9 @@ public:
      *  no pose terms, a fixed landmark no landmark terms.  Contract and return value as above; throws
      *  std::invalid_argument for another dim or nCams.  cam5 describes a camera AT THE POSE: on a graph with sensor
      *  poses (setSensorPose: the pose vertex is then the body) this is the reprojection into a camera whose sensor
-     *  pose is the identity; a rig kind here is a later step. */
+     *  pose is the identity; a rig kind here is a later step.  Likewise it is a PINHOLE: on a graph with
+     *  Kannala-Brandt models (setCameraModel) cam5 is still read as fx, fy, cx, cy, bf of X / Z; a fisheye kind is a
+     *  later step. */
     bool reprojectionCovariances(int n, const BaseVertex* const* poses, const BaseVertex* const* landmarks, int dim,
                                  const double* cam5, int nCams, double* cov);
 

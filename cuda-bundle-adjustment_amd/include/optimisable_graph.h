@@ -19,6 +19,7 @@
 #include <utility>
 #include <vector>
 
+#include "camera_model.h"
 #include "cugo_types.h"
 
 namespace cugo
@@ -491,6 +492,12 @@ public:
     virtual void setSensorPose(const Se3D& T_sb) noexcept = 0;
     virtual const Se3D& sensorPoseData() const noexcept = 0;
     virtual Se3D& getSensorPose() noexcept = 0;
+    // Extension: the camera's projection model (camera_model.h; default Pinhole).  Like the sensor pose it follows the
+    // camera: used when GraphOptimisationOptions::perEdgeCamera is on, otherwise the edge set's.  KannalaBrandt is for
+    // mono edges; initialize() refuses it on stereo and depth edges
+    virtual void setCameraModel(const CameraModel& model) noexcept = 0;
+    virtual const CameraModel& cameraModelData() const noexcept = 0;
+    virtual CameraModel& getCameraModel() noexcept = 0;
 };
 
 // ref: Edge<DIM, E, VertexTypes...> src/optimisable_graph.h:416-503
@@ -563,6 +570,17 @@ public:
         return sensorPose_;
     }
     const Se3D& sensorPoseData() const noexcept override { return sensorPose_; }
+    void setCameraModel(const CameraModel& model) noexcept override
+    {
+        touchOwner();
+        cameraModel_ = model;
+    }
+    CameraModel& getCameraModel() noexcept override
+    {
+        touchOwner();
+        return cameraModel_;
+    }
+    const CameraModel& cameraModelData() const noexcept override { return cameraModel_; }
     void inactivate() noexcept override
     {
         touchOwner();
@@ -580,6 +598,7 @@ protected:
     Information info_;
     Camera camera_;
     Se3D sensorPose_; // identity
+    CameraModel cameraModel_; // Pinhole
     BaseVertex* vertices[VertexSize];
     bool isActive_;
 };
@@ -621,6 +640,11 @@ public:
     virtual void setSensorPose(const Se3D& T_sb) noexcept = 0;
     virtual const Se3D& sensorPoseData() const noexcept = 0;
     virtual Se3D& getSensorPose() noexcept = 0;
+    // Extension: the set's projection model (see BaseEdge::setCameraModel); default Pinhole.  One MonoEdgeSet per
+    // fisheye camera, each with its sensor pose and its coefficients, is a fisheye rig
+    virtual void setCameraModel(const CameraModel& model) noexcept = 0;
+    virtual const CameraModel& cameraModelData() const noexcept = 0;
+    virtual CameraModel& getCameraModel() noexcept = 0;
 };
 
 inline void BaseEdge::touchOwner() noexcept
@@ -708,6 +732,17 @@ public:
         return sensorPose_;
     }
     const Se3D& sensorPoseData() const noexcept override { return sensorPose_; }
+    void setCameraModel(const CameraModel& model) noexcept override
+    {
+        touch();
+        cameraModel_ = model;
+    }
+    CameraModel& getCameraModel() noexcept override
+    {
+        touch();
+        return cameraModel_;
+    }
+    const CameraModel& cameraModelData() const noexcept override { return cameraModel_; }
     void setOutlierThreshold(const Scalar t) noexcept
     {
         touch();
@@ -732,6 +767,7 @@ protected:
     Information info_ = 0.0;
     Camera camera_;
     Se3D sensorPose_; // identity
+    CameraModel cameraModel_; // Pinhole
     bool isDirty_ = true;
 };
 

@@ -114,10 +114,26 @@ typedef struct cugo_edges
      * the Jacobians are those of the left update on the body pose.  The slot's camera index (d_cam, 16 bits) selects
      * the entry; with n_cams == 1 entry 0 serves every slot.  has_rig == 0 (every zero-initialised struct): d_cam_ext
      * is not read and every entry point runs the kernels it has always run.  has_rig != 0 with d_cam_ext == NULL, or
-     * together with has_depth != 0 (not yet), is CUGO_ERR_INVALID before anything is launched. */
+     * together with has_depth != 0 (not yet), is CUGO_ERR_INVALID before anything is launched.
+     * Extension: camera models (Kannala-Brandt fisheye).  has_rig takes one of the CUGO_RIG_* values below; any other
+     * non-zero value means CUGO_RIG_EXTRINSICS, as it always did.  With has_rig == CUGO_RIG_MODELS d_cam_ext is a MODEL
+     * table of stride 17, d_cam_ext[17 k] = {M row-major (9), t_s (3), k1, k2, k3, k4, model}, model 0.0 (pinhole) or
+     * 1.0 (Kannala-Brandt):
+     *   theta = atan2(sqrt(x^2 + y^2), z),  theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+     *   pu = fx theta_d x / r + cx,  pv = fy theta_d y / r + cy          at Xs = (x, y, z);  z <= 0 is a legal point.
+     * A pinhole entry of a model table gives the bits of the same entry under CUGO_RIG_EXTRINSICS.  A Kannala-Brandt
+     * entry has two rows: bf has no meaning there, and a stereo slot on such an entry is NOT DEFINED at this level (the
+     * graph level refuses it).  CUGO_RIG_MODELS with d_cam_ext == NULL or together with has_depth != 0 is
+     * CUGO_ERR_INVALID before anything is launched. */
     int has_rig;
-    const double* d_cam_ext; /* [n_cams][12] */
+    const double* d_cam_ext; /* [n_cams][12], or [n_cams][17] with CUGO_RIG_MODELS */
 } cugo_edges;
+
+/* cugo_edges.has_rig */
+#define CUGO_RIG_NONE 0       /* d_cam_ext is not read */
+#define CUGO_RIG_EXTRINSICS 1 /* d_cam_ext [n_cams][12]: sensor poses */
+#define CUGO_RIG_MODELS 2     /* d_cam_ext [n_cams][17]: sensor poses, Kannala-Brandt coefficients, model flag */
+#define CUGO_CAM_TAB_STRIDE 17
 
 typedef struct cugo_robust
 {
@@ -700,6 +716,24 @@ int cugo_graph_add_edges_rig(cugo_graph* g, int dim, int n, const int32_t* pose_
                              const double* meas, const double* info, const double* cam5, const double* sensor_q_t7);
 int cugo_graph_n_rig_cameras(cugo_graph* g);
 int cugo_graph_get_flat_cameras(cugo_graph* g, int cap, double* cam5, double* ext12, int* has_rig);
+/* Extension: camera models (Kannala-Brandt fisheye; cugo_edges.has_rig == CUGO_RIG_MODELS).  model: 0 pinhole (the
+ * default), 1 Kannala-Brandt with coefficients k4 = (k1, k2, k3, k4) (NULL: zeros, the equidistant model).  Like the
+ * sensor pose the model follows the camera: cugo_graph_set_camera_model sets that of the mono (dim 2) or stereo (dim 3)
+ * set; cugo_graph_add_edges_model is cugo_graph_add_edges with, per edge, a camera cam5 [n][5], a sensor pose
+ * sensor_q_t7 [n][7] and a model model_k5 [n][5] = (k1, k2, k3, k4, model) — each of the three may be NULL and counts
+ * on a graph created with per_edge_camera only.  A graph whose models are all pinhole runs the kernels it ran before.
+ * cugo_graph_initialize refuses a Kannala-Brandt model on stereo edges, together with depth edges (not yet), on a
+ * landmark-sharded graph (not yet), and coefficients that are not finite.
+ * cugo_graph_reprojection_covariances keeps describing a pinhole camera at the pose.
+ * cugo_graph_n_fisheye_cameras: entries of the camera table of the current flattening whose model is Kannala-Brandt.
+ * cugo_graph_get_flat_camera_models (diagnostic): returns the number of entries of that table and fills the first
+ * `cap` of model_k5 [cap][5] = (k1, k2, k3, k4, model) where not NULL; parallel to cugo_graph_get_flat_cameras. */
+int cugo_graph_set_camera_model(cugo_graph* g, int dim, int model, const double* k4);
+int cugo_graph_add_edges_model(cugo_graph* g, int dim, int n, const int32_t* pose_ids, const int32_t* landmark_ids,
+                               const double* meas, const double* info, const double* cam5, const double* sensor_q_t7,
+                               const double* model_k5);
+int cugo_graph_n_fisheye_cameras(cugo_graph* g);
+int cugo_graph_get_flat_camera_models(cugo_graph* g, int cap, double* model_k5);
 /* Point-to-plane / point-to-line pose edges (the reference's PlaneEdgeSet / LineEdgeSet, include/icp_types.h), next to
  * or instead of the BA edges; residuals and conventions as for cugo_icp_edges above.  pointP [n][3]; plane: unit normal
  * [n][3] (used as given) and origin_distance [n]; line: two distinct points a, b [n][3]; info [n] or NULL (the set's
