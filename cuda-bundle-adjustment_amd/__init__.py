@@ -71,6 +71,7 @@ class RigEdges(Edges):
 
 
 RIG_NONE, RIG_EXTRINSICS, RIG_MODELS = 0, 1, 2   # cugo_edges.has_rig (CUGO_RIG_*)
+OBS_MONO, OBS_STEREO, OBS_DEPTH = 2, 3, 4        # kind of a predicted observation (CUGO_OBS_*)
 CAM_TAB_STRIDE = 17
 
 
@@ -176,6 +177,13 @@ def lib():
         #  d_lmcov9, d_cov9)
         _lib.cugo_reprojection_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11
         _lib.cugo_reprojection_covariances.restype = C.c_int
+        # (ctx, n, n_landmarks_free, d_q_pose, d_q_lm, d_q_kind, d_q_aa, d_cam5, d_cam_tab, d_poses, d_lms, d_blocks,
+        #  d_cross18, d_lmcov9, d_z3, d_cov9)
+        _lib.cugo_predict_observations.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 13
+        _lib.cugo_predict_observations.restype = C.c_int
+        _lib.cugo_graph_predict_observations.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int, _f64p, _f64p, _f64p,
+                                                         _f64p, _f64p]
+        _lib.cugo_graph_predict_observations.restype = C.c_int
         _lib.cugo_plcov_plan_create.argtypes = [C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p,
                                                 C.POINTER(C.c_void_p)]
         _lib.cugo_plcov_plan_create.restype = C.c_int
@@ -334,6 +342,15 @@ def reprojection_covariances(ctx, n, n_landmarks_free, d_q_pose, d_q_lm, d_q_dim
     """cugo_reprojection_covariances: S = J Sigma J^T [n][9] of n queries (device pointers as ctypes.c_void_p)"""
     check(lib().cugo_reprojection_covariances(ctx, int(n), int(n_landmarks_free), d_q_pose, d_q_lm, d_q_dim, d_q_aa,
                                               d_cam5, d_poses, d_lms, d_blocks, d_cross18, d_lmcov9, d_cov9))
+
+
+def predict_observations(ctx, n, n_landmarks_free, d_q_pose, d_q_lm, d_q_kind, d_q_aa, d_cam5, d_cam_tab, d_poses, d_lms,
+                         d_blocks, d_cross18, d_lmcov9, d_z3, d_cov9):
+    """cugo_predict_observations: the predicted observation z [n][3] and S = J Sigma J^T [n][9] of n queries of kind
+    OBS_MONO / OBS_STEREO / OBS_DEPTH; d_cam_tab [n][17] (camera_model_table) or None for pinholes at the pose (device
+    pointers as ctypes.c_void_p)"""
+    check(lib().cugo_predict_observations(ctx, int(n), int(n_landmarks_free), d_q_pose, d_q_lm, d_q_kind, d_q_aa, d_cam5,
+                                          d_cam_tab, d_poses, d_lms, d_blocks, d_cross18, d_lmcov9, d_z3, d_cov9))
 
 
 def relpose_compute_errors(ctx, ev, d_poses, d_chi, d_edge_chi=None):
@@ -958,6 +975,29 @@ class Graph:
         check(lib().cugo_graph_reprojection_covariances(self._g, len(a), _p(a, _i32p), _p(b, _i32p), int(dim),
                                                         None if c is None else _p(c, _f64p), _p(out, _f64p)))
         return out.reshape(-1, int(dim), int(dim)).transpose(0, 2, 1).copy()
+
+    def predict_observations(self, pose_ids, lm_ids, kind=OBS_MONO, cam=None, sensor=None, model=None):
+        """(z [n, dim], cov [n, dim, dim]): the predicted observation of landmark lm_ids[k] seen from pose pose_ids[k] and
+        its covariance S = J Sigma J^T, for every camera kind.  kind: OBS_MONO (u, v), OBS_STEREO (u, v, u_right),
+        OBS_DEPTH (u, v, 1/Z_s; S in measurement units, the set's inverse-depth weight not applied).  cam: [5] or [n, 5]
+        (fx, fy, cx, cy, bf); sensor: [7] or [n, 7] (q, t) body -> sensor, None: the identity; model: [5] or [n, 5]
+        (k1, k2, k3, k4, type), type 0 pinhole / 1 Kannala-Brandt, None: a pinhole.  cam=None: the camera, sensor pose
+        and model of the graph's mono / stereo / depth set for that kind (sensor and model must then be None)."""
+        a = np.ascontiguousarray(pose_ids, np.int32).reshape(-1)
+        b = np.ascontiguousarray(lm_ids, np.int32).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("pose_ids and lm_ids must have the same length")
+        n = len(a)
+
+        def per_query(v, w):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64).reshape(-1, w), (n, w)))
+        c, s, m = per_query(cam, 5), per_query(sensor, 7), per_query(model, 5)
+        dim = 2 if kind == OBS_MONO else 3
+        z, out = np.zeros((n, dim)), np.zeros((n, dim * dim))
+        check(lib().cugo_graph_predict_observations(self._g, n, _p(a, _i32p), _p(b, _i32p), int(kind),
+                                                    None if c is None else _p(c, _f64p), None if s is None else _p(s, _f64p),
+                                                    None if m is None else _p(m, _f64p), _p(z, _f64p), _p(out, _f64p)))
+        return z, out.reshape(-1, dim, dim).transpose(0, 2, 1).copy()
 
     def set_poses(self, ids, q_t7):
         ids = np.ascontiguousarray(ids, np.int32); q = np.ascontiguousarray(q_t7, np.float64)

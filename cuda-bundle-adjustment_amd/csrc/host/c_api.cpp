@@ -982,6 +982,24 @@ int cugo_reprojection_covariances(cugo_ctx* ctx, int n, int n_landmarks_free, co
         CUGO_HIP(hipGetLastError());
     });
 }
+int cugo_predict_observations(cugo_ctx* ctx, int n, int n_landmarks_free, const int32_t* d_q_pose, const int32_t* d_q_lm,
+                              const int32_t* d_q_kind, const int32_t* d_q_aa, const double* d_cam5, const double* d_cam_tab,
+                              const double* d_poses, const double* d_lms, const double* d_blocks, const double* d_cross18,
+                              const double* d_lmcov9, double* d_z3, double* d_cov9)
+{
+    return guarded([&] {
+        if (!ctx || !d_q_pose || !d_q_lm || !d_q_kind || !d_q_aa || !d_cam5 || !d_poses || !d_lms || !d_blocks ||
+            !d_cross18 || !d_lmcov9 || !d_z3 || !d_cov9)
+            throw std::invalid_argument("cugo_predict_observations: null argument");
+        if (n < 0 || n_landmarks_free < 0)
+            throw std::invalid_argument("cugo_predict_observations: negative count");
+        if (n == 0)
+            return;
+        cugo_k::launch_predict_obs(ctx->stream, n, n_landmarks_free, d_q_pose, d_q_lm, d_q_kind, d_q_aa, d_cam5, d_cam_tab,
+                                   d_poses, d_lms, d_blocks, d_cross18, d_lmcov9, d_z3, d_cov9);
+        CUGO_HIP(hipGetLastError());
+    });
+}
 #ifdef CUGO_DEBUG_HOOKS // diagnosis entry points: only libcugo_hip_hooks.so exports them (csrc/host/cugo_debug.h)
 int cugo_debug_pin_reference(void)
 {
@@ -2066,6 +2084,51 @@ int cugo_graph_reprojection_covariances(cugo_graph* g, int n, const int32_t* pos
                                   const double set5[5] = {c.fx, c.fy, c.cx, c.cy, c.bf};
                                   return g->opt->reprojectionCovariances(n, p, l, dim, set5, 1, cov);
                               });
+}
+
+int cugo_graph_predict_observations(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* lm_ids, int kind,
+                                    const double* cam5, const double* sensor_q_t7, const double* model_k5, double* z,
+                                    double* cov)
+{
+    const char* who = "cugo_graph_predict_observations";
+    return pose_landmark_call(g, who, n, pose_ids, lm_ids,
+                              [&](const cugo::BaseVertex* const* p, const cugo::BaseVertex* const* l) {
+        if (kind != CUGO_OBS_MONO && kind != CUGO_OBS_STEREO && kind != CUGO_OBS_DEPTH)
+            throw std::invalid_argument(std::string(who) + ": kind must be 2 (mono), 3 (stereo) or 4 (depth)");
+        if (!cam5)
+        {
+            // the camera, sensor pose and model of the edge set of that kind
+            if (sensor_q_t7 || model_k5)
+                throw std::invalid_argument(std::string(who) + ": sensor_q_t7 and model_k5 must be NULL where cam5 is "
+                                                               "(the set's camera brings its own)");
+            const cugo::BaseEdgeSet& es = kind == CUGO_OBS_DEPTH    ? static_cast<const cugo::BaseEdgeSet&>(g->depth)
+                                          : kind == CUGO_OBS_STEREO ? static_cast<const cugo::BaseEdgeSet&>(g->stereo)
+                                                                    : static_cast<const cugo::BaseEdgeSet&>(g->mono);
+            const cugo::Camera& c = es.cameraData();
+            const double set5[5] = {c.fx, c.fy, c.cx, c.cy, c.bf};
+            const cugo::Se3D T = es.sensorPoseData();
+            const cugo::CameraModel m = es.cameraModelData();
+            return g->opt->predictObservations(n, p, l, kind, set5, 1, &T, &m, z, cov);
+        }
+        std::vector<cugo::Se3D> T;
+        std::vector<cugo::CameraModel> m;
+        for (int i = 0; sensor_q_t7 && i < n; i++)
+            T.emplace_back(sensor_q_t7 + 7 * (size_t)i, sensor_q_t7 + 7 * (size_t)i + 4);
+        for (int i = 0; model_k5 && i < n; i++)
+        {
+            // (the type travels as a double and is judged by predictObservations; the enum holds what it says)
+            const double ty = model_k5[5 * (size_t)i + 4];
+            if (ty != 0.0 && ty != 1.0)
+                throw std::invalid_argument(std::string(who) + ": unknown model type (0 pinhole, 1 Kannala-Brandt)");
+            cugo::CameraModel cm;
+            cm.type = ty != 0.0 ? cugo::KannalaBrandt : cugo::Pinhole;
+            for (int c = 0; c < 4; c++)
+                cm.k[c] = model_k5[5 * (size_t)i + c];
+            m.push_back(cm);
+        }
+        return g->opt->predictObservations(n, p, l, kind, cam5, n, sensor_q_t7 ? T.data() : nullptr,
+                                           model_k5 ? m.data() : nullptr, z, cov);
+    });
 }
 
 int cugo_graph_relative_pose_covariances(cugo_graph* g, int n, const int32_t* ids_a, const int32_t* ids_b, double* cov36)

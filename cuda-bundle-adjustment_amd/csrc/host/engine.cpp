@@ -158,7 +158,7 @@ struct Engine::Impl : cugo_k::LaunchHook
     // blocks of its plan, Sigma_al, the cameras and the result of k_reprojection_cov
     std::vector<int32_t> h_pl_idx;
     DevBuf<int32_t> d_pl_idx;
-    DevBuf<double> d_pl_blocks, d_pl_cross, d_pl_cam, d_pl_out;
+    DevBuf<double> d_pl_blocks, d_pl_cross, d_pl_cam, d_pl_out, d_pl_tab, d_pl_z; // (tab, z: k_predict_obs)
     PinnedBuf<double> h_pin_poses, h_pin_lms; // refresh_estimates_pinned / download_pinned
     Clock::duration last_trial_wait{0};       // how long the host polled for the previous trial's result
     DevBuf<int32_t> d_hsc_rowptr, d_hsc_colind, d_off_ptr, d_off_ei, d_off_ej, d_fail;
@@ -2223,13 +2223,13 @@ bool Engine::pose_landmark_cross_covariances(int n, const int32_t* ia, const int
     return !fail;
 }
 
-bool Engine::reprojection_covariances(int n, const int32_t* ia, const int32_t* il, int dim, const double* cam5, double* cov)
+// What reprojection_covariances and predict_observations queue before their own kernel: the vertex indices of the
+// flattening as the kernel reads them, with `third` (a dim or a kind) per query behind them, Sigma_aa and Sigma_al
+// (queue_pose_lm_cross) and Sigma_ll of every free landmark on the same factorisation.  1: queued; 0: both vertices of
+// every query are fixed, nothing was queued; -1: a zero pivot
+int Engine::queue_joint_covariances(const char* who, int n, const int32_t* ia, const int32_t* il, int third, size_t off[6])
 {
     Impl& m = *impl_;
-    const char* who = "cugo_graph_reprojection_covariances";
-    check_covariance_call(who);
-    if (dim != 2 && dim != 3)
-        throw std::invalid_argument(std::string(who) + ": dim must be 2 (mono) or 3 (stereo)");
     std::vector<int32_t> qp((size_t)n), ql((size_t)n), extra(3 * (size_t)n);
     bool any = false, any_lm = false;
     for (int k = 0; k < n; k++)
@@ -2237,17 +2237,14 @@ bool Engine::reprojection_covariances(int n, const int32_t* ia, const int32_t* i
         if (ia[k] < 0 || ia[k] >= m.Pall || il[k] < 0 || il[k] >= m.Lall)
             throw std::invalid_argument(std::string(who) + ": vertex index out of range");
         qp[k] = ia[k] < m.P ? ia[k] : -1, ql[k] = il[k] < m.L ? il[k] : -1;
-        extra[k] = ia[k], extra[(size_t)n + k] = il[k], extra[2 * (size_t)n + k] = dim;
+        extra[k] = ia[k], extra[(size_t)n + k] = il[k], extra[2 * (size_t)n + k] = third;
         any = any || qp[k] >= 0 || ql[k] >= 0;
         any_lm = any_lm || ql[k] >= 0;
     }
-    const size_t dd = (size_t)dim * dim;
-    std::fill(cov, cov + dd * (size_t)n, 0.0);
-    if (!any) // (both vertices of every query are fixed)
-        return true;
-    size_t off[6];
+    if (!any)
+        return 0;
     if (!queue_pose_lm_cross(n, qp.data(), ql.data(), extra, off))
-        return false;
+        return -1;
     hipStream_t s = m.ctx.stream;
     // Sigma_ll of every free landmark on the same factorisation; whether one of them fails is the first kernel's call
     m.d_cov_lm.resize(9 * (size_t)m.L + 16);
@@ -2255,28 +2252,113 @@ bool Engine::reprojection_covariances(int n, const int32_t* ia, const int32_t* i
     {
         m.d_cov_sigma.resize(36 * (size_t)m.hs.n_blocks + 16);
         if (m.P > 0 && !m.chol.selected_inverse(m.d_cov_sigma.data()))
-            return false;
+            return -1;
         cugo_k::launch_lm_covariance(s, m.L, m.ev.d_lm_ptr, m.ev.d_pose, m.ev.d_flags, m.d_Hll.data(),
                                      reinterpret_cast<const double*>(m.d_Hpl.data()), m.hs.d_rowptr, m.hs.d_colind,
                                      m.d_cov_sigma.data(), m.d_cov_lm.data(), m.d_cov_fail.data());
     }
+    return 1;
+}
+
+// the 3 x 3 blocks of m.d_pl_out to the host with the fail flag of k_pose_lm_cross (read only where one was queued);
+// false, nothing copied: the flag is set
+bool Engine::fetch_joint_covariances(int n, bool flagged, std::vector<double>& h)
+{
+    Impl& m = *impl_;
+    hipStream_t s = m.ctx.stream;
+    h.resize(9 * (size_t)n);
+    int32_t fail = 0;
+    CUGO_HIP(hipMemcpyAsync(h.data(), m.d_pl_out.data(), h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (flagged)
+        CUGO_HIP(hipMemcpyAsync(&fail, m.d_cov_fail.data() + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CUGO_HIP(hipStreamSynchronize(s));
+    return !fail;
+}
+
+bool Engine::reprojection_covariances(int n, const int32_t* ia, const int32_t* il, int dim, const double* cam5, double* cov)
+{
+    Impl& m = *impl_;
+    const char* who = "cugo_graph_reprojection_covariances";
+    check_covariance_call(who);
+    if (dim != 2 && dim != 3)
+        throw std::invalid_argument(std::string(who) + ": dim must be 2 (mono) or 3 (stereo)");
+    const size_t dd = (size_t)dim * dim;
+    std::fill(cov, cov + dd * (size_t)n, 0.0);
+    size_t off[6];
+    const int queued = queue_joint_covariances(who, n, ia, il, dim, off);
+    if (queued <= 0) // (both vertices of every query are fixed, or a zero pivot)
+        return queued == 0;
+    hipStream_t s = m.ctx.stream;
     m.d_pl_cam.upload(cam5, 5 * (size_t)n, s);
     m.d_pl_out.resize(9 * (size_t)n + 16);
     const int32_t* ix = m.d_pl_idx.data();
     cugo_k::launch_reprojection_cov(s, n, m.L, ix + off[5], ix + off[5] + n, ix + off[5] + 2 * (size_t)n, ix + off[4],
                                     m.d_pl_cam.data(), m.d_poses[m.cur].data(), m.d_lms[m.cur].data(), m.d_pl_blocks.data(),
                                     m.d_pl_cross.data(), m.d_cov_lm.data(), m.d_pl_out.data());
-    std::vector<double> h(9 * (size_t)n);
-    int32_t fail = 0;
-    CUGO_HIP(hipMemcpyAsync(h.data(), m.d_pl_out.data(), h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    CUGO_HIP(hipMemcpyAsync(&fail, m.d_cov_fail.data() + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CUGO_HIP(hipStreamSynchronize(s));
-    if (fail)
+    std::vector<double> h;
+    if (!fetch_joint_covariances(n, true, h))
         return false;
     for (int k = 0; k < n; k++)
         for (int c = 0; c < dim; c++)
             for (int r = 0; r < dim; r++)
                 cov[dd * (size_t)k + r + (size_t)dim * c] = h[9 * (size_t)k + r + 3 * c];
+    return true;
+}
+
+bool Engine::predict_observations(int n, const int32_t* ia, const int32_t* il, int kind, const double* cam5,
+                                  const double* cam_tab, double* z, double* cov)
+{
+    Impl& m = *impl_;
+    const char* who = "cugo_graph_predict_observations";
+    check_covariance_call(who);
+    if (kind != CUGO_OBS_MONO && kind != CUGO_OBS_STEREO && kind != CUGO_OBS_DEPTH)
+        throw std::invalid_argument(std::string(who) + ": kind must be 2 (mono), 3 (stereo) or 4 (depth)");
+    const int dim = kind == CUGO_OBS_MONO ? 2 : 3;
+    const size_t dd = (size_t)dim * dim;
+    std::fill(z, z + (size_t)dim * n, 0.0);
+    std::fill(cov, cov + dd * (size_t)n, 0.0);
+    if (n == 0)
+        return true;
+    size_t off[6];
+    const int queued = queue_joint_covariances(who, n, ia, il, kind, off);
+    if (queued < 0)
+        return false;
+    hipStream_t s = m.ctx.stream;
+    if (queued == 0)
+    {
+        // both vertices of every query are fixed: no system is built, and of the covariance inputs the kernel reads none
+        // (q_aa = -1, every landmark index >= L) — z still needs the indices on the device
+        std::vector<int32_t>& h = m.h_pl_idx;
+        h.assign(ia, ia + n);
+        h.insert(h.end(), il, il + n);
+        h.insert(h.end(), (size_t)n, kind);
+        h.insert(h.end(), (size_t)n, -1);
+        m.d_pl_idx.upload(h, s);
+        off[5] = 0, off[4] = 3 * (size_t)n;
+        m.d_pl_blocks.resize(16), m.d_pl_cross.resize(16), m.d_cov_lm.resize(16);
+    }
+    m.d_pl_cam.upload(cam5, 5 * (size_t)n, s);
+    if (cam_tab)
+        m.d_pl_tab.upload(cam_tab, 17 * (size_t)n, s);
+    m.d_pl_out.resize(9 * (size_t)n + 16);
+    m.d_pl_z.resize(3 * (size_t)n + 16);
+    const int32_t* ix = m.d_pl_idx.data();
+    cugo_k::launch_predict_obs(s, n, m.L, ix + off[5], ix + off[5] + n, ix + off[5] + 2 * (size_t)n, ix + off[4],
+                               m.d_pl_cam.data(), cam_tab ? m.d_pl_tab.data() : nullptr, m.d_poses[m.cur].data(),
+                               m.d_lms[m.cur].data(), m.d_pl_blocks.data(), m.d_pl_cross.data(), m.d_cov_lm.data(),
+                               m.d_pl_z.data(), m.d_pl_out.data());
+    std::vector<double> hz(3 * (size_t)n), h;
+    CUGO_HIP(hipMemcpyAsync(hz.data(), m.d_pl_z.data(), hz.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (!fetch_joint_covariances(n, queued > 0, h))
+        return false;
+    for (int k = 0; k < n; k++)
+    {
+        for (int r = 0; r < dim; r++)
+            z[(size_t)dim * k + r] = hz[3 * (size_t)k + r];
+        for (int c = 0; c < dim; c++)
+            for (int r = 0; r < dim; r++)
+                cov[dd * (size_t)k + r + (size_t)dim * c] = h[9 * (size_t)k + r + 3 * c];
+    }
     return true;
 }
 

@@ -250,6 +250,12 @@ public:
     // 3, cam5 [n][5].  The above, plus the selected inverse and k_lm_covariance into a scratch buffer for Sigma_ll (its
     // own fail flag is ignored: a singular Hll counts only when a query names the landmark), then k_reprojection_cov.
     bool reprojection_covariances(int n, const int32_t* ia, const int32_t* il, int dim, const double* cam5, double* cov);
+    // Extension: the predicted observation z [n][dim] and S [n][dim * dim] of the same queries for every camera kind
+    // (k_predict_obs): kind CUGO_OBS_MONO / _STEREO / _DEPTH (dim 2 / 3 / 3), cam5 [n][5], cam_tab [n][17] = {M row-major,
+    // t_s, k1..k4, model} or NULL (pinholes at the pose).  The path of reprojection_covariances; z is computed where both
+    // vertices are fixed too.  false: both outputs zero-filled.
+    bool predict_observations(int n, const int32_t* ia, const int32_t* il, int kind, const double* cam5,
+                              const double* cam_tab, double* z, double* cov);
     void clear_covariances();
     int covariances_held() const { return cov_what_; } // bit 0 poses, bit 1 landmarks
     const std::vector<double>& cov_pose() const { return cov_pose_; }
@@ -288,6 +294,9 @@ private:
     // k_pose_lm_cross; `extra` rides behind the index arrays on the device.  off[6]: where q_pose, q_lm, q_ptr, q_slot,
     // q_aa and extra start in the index buffer.  false: a zero pivot
     bool queue_pose_lm_cross(int n, const int32_t* qp, const int32_t* ql, const std::vector<int32_t>& extra, size_t off[6]);
+    // what reprojection_covariances() and predict_observations() share (engine.cpp)
+    int queue_joint_covariances(const char* who, int n, const int32_t* ia, const int32_t* il, int third, size_t off[6]);
+    bool fetch_joint_covariances(int n, bool flagged, std::vector<double>& h);
     void build_structure(); // by device_structure() or host_structure(); both end in adopt_structure()
     bool device_structure(InitLaps& laps);
     void host_structure(InitLaps& laps);

@@ -1125,6 +1125,73 @@ bool CudaGraphOptimisationImpl::reprojectionCovariances(int n, const BaseVertex*
     return engine_->reprojection_covariances(n, ia.data(), il.data(), dim, cams.data(), cov);
 }
 
+bool CudaGraphOptimisationImpl::predictObservations(int n, const BaseVertex* const* poses,
+                                                    const BaseVertex* const* landmarks, int kind, const double* cam5,
+                                                    int nCams, const Se3D* sensorPoses, const CameraModel* models,
+                                                    double* z, double* cov)
+{
+    const std::string w = "cugo: predictObservations(): ";
+    std::vector<int32_t> ia, il;
+    poseLandmarkIndices("predictObservations", n, poses, landmarks, ia, il);
+    if (kind != CUGO_OBS_MONO && kind != CUGO_OBS_STEREO && kind != CUGO_OBS_DEPTH)
+        throw std::invalid_argument(w + "kind must be 2 (mono), 3 (stereo) or 4 (depth)");
+    if (n > 0 && (!cam5 || !z || !cov || (nCams != 1 && nCams != n)))
+        throw std::invalid_argument(w + "cam5 must hold one camera or one per query (nCams 1 or n), z and cov not null");
+    // the camera table of the batch, one entry per query: the quaternion normalised and expanded to M in fp64, as
+    // initialize() does for the table of the graph
+    // (neither sensor poses nor models: nothing to check and no table to form)
+    const bool tabled = sensorPoses || models;
+    std::vector<double> cams(5 * (size_t)n), tab(tabled ? 17 * (size_t)n : 0);
+    bool plain = true; // every entry a pinhole at the pose: the kernel then runs without the table
+    for (int k = 0; k < n; k++)
+    {
+        const size_t c = nCams == 1 ? 0 : (size_t)k;
+        std::copy(cam5 + 5 * c, cam5 + 5 * c + 5, cams.begin() + 5 * (size_t)k);
+        if (!tabled)
+            continue;
+        double* e = &tab[17 * (size_t)k];
+        if (k > 0 && nCams == 1)
+        {
+            std::copy(tab.begin(), tab.begin() + 17, e);
+            continue;
+        }
+        double q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0};
+        if (sensorPoses)
+            sensorPoses[c].copyTo(q, t);
+        const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+        if (!std::isfinite(n2) || !(n2 > 0.0) || !std::isfinite(t[0]) || !std::isfinite(t[1]) || !std::isfinite(t[2]))
+            throw std::invalid_argument(w + "sensor pose of query " + std::to_string(k) +
+                                        ": the quaternion must be finite with a norm > 0, the translation finite");
+        const double in = 1.0 / std::sqrt(n2);
+        const double x = q[0] * in, y = q[1] * in, zq = q[2] * in, qw = q[3] * in;
+        const double M[12] = {1 - 2 * (y * y + zq * zq), 2 * (x * y - zq * qw),     2 * (x * zq + y * qw),
+                              2 * (x * y + zq * qw),     1 - 2 * (x * x + zq * zq), 2 * (y * zq - x * qw),
+                              2 * (x * zq - y * qw),     2 * (y * zq + x * qw),     1 - 2 * (x * x + y * y),
+                              t[0],                      t[1],                      t[2]};
+        std::copy(M, M + 12, e);
+        const CameraModel md = models ? models[c] : CameraModel();
+        if ((int)md.type != (int)Pinhole && (int)md.type != (int)KannalaBrandt)
+            throw std::invalid_argument(w + "camera model of query " + std::to_string(k) + ": unknown model type " +
+                                        std::to_string((int)md.type));
+        for (int j = 0; j < 4; j++)
+        {
+            if (!std::isfinite((double)md.k[j]))
+                throw std::invalid_argument(w + "camera model of query " + std::to_string(k) +
+                                            ": the coefficients k1..k4 must be finite");
+            e[12 + j] = (double)md.k[j];
+        }
+        e[16] = md.type == KannalaBrandt ? 1.0 : 0.0;
+        if (md.type == KannalaBrandt && kind != CUGO_OBS_MONO)
+            throw std::invalid_argument(w + "a Kannala-Brandt camera has the rows (u, v) only: kind must be 2 (mono), "
+                                            "query " + std::to_string(k));
+        static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+        for (int j = 0; j < 12; j++)
+            plain = plain && M[j] == I12[j];
+        plain = plain && md.type == Pinhole;
+    }
+    return engine_->predict_observations(n, ia.data(), il.data(), kind, cams.data(), plain ? nullptr : tab.data(), z, cov);
+}
+
 bool CudaGraphOptimisationImpl::landmarkCovariance(const BaseVertex* v, double cov[9]) const
 {
     if (!(engine_->covariances_held() & 2) || !v || !v->isMarginilised() || !flattenedUnchanged(v->ownerSet()))

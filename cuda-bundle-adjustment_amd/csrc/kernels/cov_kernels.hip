@@ -30,7 +30,8 @@
 //
 // Pose-landmark blocks (k_pose_lm_cross), with the same L and G_e: Sigma_al = -(sum_e Sigma_{a p(e)} G_e) L^-1, and the
 // covariance of a reprojection from them (k_reprojection_cov): J Sigma J^T over the joint [a; l] block.  One thread per
-// query, the pose blocks handed in by index (csrc/host/plcov_plan.h).
+// query, the pose blocks handed in by index (csrc/host/plcov_plan.h).  k_predict_obs: the same for a camera behind a
+// sensor pose, a Kannala-Brandt camera and the depth kind, with the predicted observation itself.
 #include <algorithm>
 
 #include "ba_math.h"
@@ -534,33 +535,13 @@ __global__ __launch_bounds__(256) void k_pose_lm_cross(int n, const int32_t* __r
         }
 }
 
-// Covariance of the reprojection of landmark l in pose a at the current estimates, S = J Sigma J^T over the joint
-// [a; l] block with J = [J_p J_l] of ba_math.h, one thread per query:
-//   S = J_p Sigma_aa J_p^T + X + X^T + J_l Sigma_ll J_l^T,   X = J_p Sigma_al J_l^T.
-// q_pose / q_lm: indices into poses [.][7] / lms [.][3] (fixed vertices included); q_aa: the block of Sigma_aa in
-// `blocks`, -1 for a fixed pose (the terms with J_p go); a landmark index >= Lfree is a fixed landmark (the terms with
-// J_l go).  cross [n][18] (k_pose_lm_cross), lmcov [Lfree][9] (k_lm_covariance).  out [n][9]: the lower triangle,
-// mirrored; the third row and column are zero for dim 2.
-__global__ __launch_bounds__(256) void k_reprojection_cov(int n, int Lfree, const int32_t* __restrict__ q_pose,
-                                                          const int32_t* __restrict__ q_lm, const int32_t* __restrict__ q_dim,
-                                                          const int32_t* __restrict__ q_aa, const double* __restrict__ cam5,
-                                                          const double* __restrict__ poses, const double* __restrict__ lms,
-                                                          const double* __restrict__ blocks, const double* __restrict__ cross,
-                                                          const double* __restrict__ lmcov, double* __restrict__ out)
+// The lower triangle of S = J_p Sigma_aa J_p^T + X + X^T + J_l Sigma_ll J_l^T, X = J_p Sigma_al J_l^T, for both kernels
+// below: the terms in this order, every sum in index order.  Saa [36] / Sal [18] / Sll [9] column-major; each is read only
+// where its vertices are free
+__device__ __forceinline__ void joint_cov_lower(const double JP[3][6], const double JL[3][3], bool free_p, bool free_l,
+                                                const double* __restrict__ Saa, const double* __restrict__ Sal,
+                                                const double* __restrict__ Sll, double S[3][3])
 {
-    using namespace cugo_dev;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n)
-        return;
-    const double* __restrict__ pose = poses + 7L * q_pose[q];
-    const int l = q_lm[q], aa = q_aa[q];
-    const double* __restrict__ cam = cam5 + 5L * q;
-    const bool stereo = q_dim[q] == 3, free_p = aa >= 0, free_l = l < Lfree;
-    double Xc[3], JP[3][6], JL[3][3];
-    world_to_cam(pose, lms + 3L * l, Xc);
-    jac_pose(Xc, cam, stereo, JP);
-    jac_landmark(Xc, pose, cam, stereo, JL);
-    double S[3][3];
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -569,7 +550,6 @@ __global__ __launch_bounds__(256) void k_reprojection_cov(int n, int Lfree, cons
     if (free_p)
     {
         // A = Sigma_aa J_p^T (6 x 3), then the lower triangle of J_p A
-        const double* __restrict__ Saa = blocks + 36L * aa;
         double A[6][3];
 #pragma unroll
         for (int r = 0; r < 6; r++)
@@ -597,7 +577,6 @@ __global__ __launch_bounds__(256) void k_reprojection_cov(int n, int Lfree, cons
     if (free_p && free_l)
     {
         // B = Sigma_al J_l^T (6 x 3), X = J_p B; S += X + X^T on the lower triangle
-        const double* __restrict__ Sal = cross + 18L * q;
         double B[6][3], X[3][3];
 #pragma unroll
         for (int r = 0; r < 6; r++)
@@ -623,7 +602,6 @@ __global__ __launch_bounds__(256) void k_reprojection_cov(int n, int Lfree, cons
     }
     if (free_l)
     {
-        const double* __restrict__ Sll = lmcov + 9L * l;
         double C[3][3]; // Sigma_ll J_l^T
 #pragma unroll
         for (int r = 0; r < 3; r++)
@@ -636,6 +614,36 @@ __global__ __launch_bounds__(256) void k_reprojection_cov(int n, int Lfree, cons
             for (int j = 0; j <= i; j++)
                 S[i][j] += JL[i][0] * C[0][j] + JL[i][1] * C[1][j] + JL[i][2] * C[2][j];
     }
+}
+
+// Covariance of the reprojection of landmark l in pose a at the current estimates, S = J Sigma J^T over the joint
+// [a; l] block with J = [J_p J_l] of ba_math.h, one thread per query:
+//   S = J_p Sigma_aa J_p^T + X + X^T + J_l Sigma_ll J_l^T,   X = J_p Sigma_al J_l^T.
+// q_pose / q_lm: indices into poses [.][7] / lms [.][3] (fixed vertices included); q_aa: the block of Sigma_aa in
+// `blocks`, -1 for a fixed pose (the terms with J_p go); a landmark index >= Lfree is a fixed landmark (the terms with
+// J_l go).  cross [n][18] (k_pose_lm_cross), lmcov [Lfree][9] (k_lm_covariance).  out [n][9]: the lower triangle,
+// mirrored; the third row and column are zero for dim 2.
+__global__ __launch_bounds__(256) void k_reprojection_cov(int n, int Lfree, const int32_t* __restrict__ q_pose,
+                                                          const int32_t* __restrict__ q_lm, const int32_t* __restrict__ q_dim,
+                                                          const int32_t* __restrict__ q_aa, const double* __restrict__ cam5,
+                                                          const double* __restrict__ poses, const double* __restrict__ lms,
+                                                          const double* __restrict__ blocks, const double* __restrict__ cross,
+                                                          const double* __restrict__ lmcov, double* __restrict__ out)
+{
+    using namespace cugo_dev;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n)
+        return;
+    const double* __restrict__ pose = poses + 7L * q_pose[q];
+    const int l = q_lm[q], aa = q_aa[q];
+    const double* __restrict__ cam = cam5 + 5L * q;
+    const bool stereo = q_dim[q] == 3, free_p = aa >= 0, free_l = l < Lfree;
+    double Xc[3], JP[3][6], JL[3][3];
+    world_to_cam(pose, lms + 3L * l, Xc);
+    jac_pose(Xc, cam, stereo, JP);
+    jac_landmark(Xc, pose, cam, stereo, JL);
+    double S[3][3];
+    joint_cov_lower(JP, JL, free_p, free_l, blocks + 36L * aa, cross + 18L * q, lmcov + 9L * l, S);
     double* o = out + 9L * q;
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -644,6 +652,88 @@ __global__ __launch_bounds__(256) void k_reprojection_cov(int n, int Lfree, cons
         {
             const int rr = i > j ? i : j, cc = i > j ? j : i; // (the lower triangle, mirrored: exactly symmetric)
             o[i + 3 * j] = (!stereo && rr == 2) ? 0.0 : S[rr][cc];
+        }
+}
+
+// Predicted observation and its covariance for every camera kind, one thread per query:
+// z = the projection of Xs = M Xb + t_s, Xb = R(q_a) X_l + t_a, and S = J Sigma J^T with the build pass's Jacobians
+// of z - m.  q_kind: CUGO_OBS_MONO (u, v), CUGO_OBS_STEREO (u, v, u_right), CUGO_OBS_DEPTH (u, v, 1 / Z_s; the row of
+// DepthEdge with sd = 1, so S is in measurement units).  cam_tab [n][17] = {M row-major, t_s, k1..k4, model} per query,
+// or NULL: every camera a pinhole at the pose, and for the kinds MONO / STEREO the operations of k_reprojection_cov
+// in their order (the same bits).  A Kannala-Brandt entry has two rows whatever the kind (the edge kernels ignore
+// the stereo bit there).  z is the residual of ba_math.h against a zero measurement under unit weight: e - 0 is e.
+// The rest as k_reprojection_cov; z3 [n][3] holds 0 where a kind has no third row.
+__global__ __launch_bounds__(256) void k_predict_obs(int n, int Lfree, const int32_t* __restrict__ q_pose,
+                                                     const int32_t* __restrict__ q_lm, const int32_t* __restrict__ q_kind,
+                                                     const int32_t* __restrict__ q_aa, const double* __restrict__ cam5,
+                                                     const double* __restrict__ cam_tab, const double* __restrict__ poses,
+                                                     const double* __restrict__ lms, const double* __restrict__ blocks,
+                                                     const double* __restrict__ cross, const double* __restrict__ lmcov,
+                                                     double* __restrict__ z3, double* __restrict__ out)
+{
+    using namespace cugo_dev;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n)
+        return;
+    const double* __restrict__ pose = poses + 7L * q_pose[q];
+    const int l = q_lm[q], aa = q_aa[q], kind = q_kind[q];
+    const double* __restrict__ cam = cam5 + 5L * q;
+    const double* __restrict__ Xw = lms + 3L * l;
+    const bool stereo = kind == CUGO_OBS_STEREO, depth = kind == CUGO_OBS_DEPTH;
+    const bool free_p = aa >= 0, free_l = l < Lfree;
+    const Robust none = {0, 1.0};
+    bool rows3 = stereo || depth;
+    EdgeGeom g;
+    double JP[3][6], JL[3][3];
+    if (!cam_tab)
+    {
+        edge_residual_k<true>(pose, Xw, 0.0, 0.0, 0.0, stereo, depth, 1.0, 1.0, cam, none, g);
+        jac_pose_k<true>(g.Xc, cam, stereo, depth, 1.0, JP);
+        jac_landmark_k<true>(g.Xc, pose, cam, stereo, depth, 1.0, JL);
+    }
+    else
+    {
+        const double* __restrict__ ext = cam_tab + 17L * q;
+        double B[3][3], R[3][3];
+        if (ext[16] != 0.0)
+        {
+            // (kb_terms is formed in edge_residual_rig and in rig_B from the same Xs, side by side in this branch: one
+            // evaluation after inlining)
+            edge_residual_rig<true>(pose, Xw, 0.0, 0.0, 0.0, false, 1.0, cam, ext, none, g);
+            rig_B<true>(g.Xc, cam, ext, false, true, B);
+            rows3 = false;
+        }
+        else
+        {
+            // A = JP[:, 3:6] of the pinhole at Xs, the depth row included (rig_B knows mono and stereo only); B = A M
+            edge_residual_rig<true>(pose, Xw, 0.0, 0.0, 0.0, stereo, 1.0, cam, ext, none, g);
+            double Xs[3], JPs[3][6];
+            body_to_sensor(ext, g.Xc, Xs);
+            jac_pose_k<true>(Xs, cam, stereo, depth, 1.0, JPs);
+#pragma unroll
+            for (int m = 0; m < 3; m++)
+#pragma unroll
+                for (int j = 0; j < 3; j++)
+                    B[m][j] = JPs[m][3] * ext[j] + JPs[m][4] * ext[3 + j] + JPs[m][5] * ext[6 + j];
+            if (depth)
+                g.e[2] = 1.0 / Xs[2]; // (the third residual of edge_residual_k at sd = 1 against 0, taken at Xs)
+        }
+        quat_to_rot(pose, R);
+        jac_pose_rig(g.Xc, B, JP);
+        jac_landmark_rig(B, R, JL);
+    }
+    double S[3][3];
+    joint_cov_lower(JP, JL, free_p, free_l, blocks + 36L * aa, cross + 18L * q, lmcov + 9L * l, S);
+    double* oz = z3 + 3L * q;
+    oz[0] = g.e[0], oz[1] = g.e[1], oz[2] = rows3 ? g.e[2] : 0.0;
+    double* o = out + 9L * q;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+        {
+            const int rr = i > j ? i : j, cc = i > j ? j : i; // (the lower triangle, mirrored: exactly symmetric)
+            o[i + 3 * j] = (!rows3 && rr == 2) ? 0.0 : S[rr][cc];
         }
 }
 
@@ -861,6 +951,17 @@ void launch_reprojection_cov(hipStream_t s, int n, int Lfree, const int32_t* d_q
         return;
     CUGO_LAUNCH(k_reprojection_cov, dim3((n + 255) / 256), dim3(256), 0, s, n, Lfree, d_q_pose, d_q_lm, d_q_dim, d_q_aa,
                 d_cam5, d_poses, d_lms, d_blocks, d_cross, d_lmcov, d_out);
+}
+
+void launch_predict_obs(hipStream_t s, int n, int Lfree, const int32_t* d_q_pose, const int32_t* d_q_lm,
+                        const int32_t* d_q_kind, const int32_t* d_q_aa, const double* d_cam5, const double* d_cam_tab,
+                        const double* d_poses, const double* d_lms, const double* d_blocks, const double* d_cross,
+                        const double* d_lmcov, double* d_z3, double* d_out)
+{
+    if (n <= 0)
+        return;
+    CUGO_LAUNCH(k_predict_obs, dim3((n + 255) / 256), dim3(256), 0, s, n, Lfree, d_q_pose, d_q_lm, d_q_kind, d_q_aa, d_cam5,
+                d_cam_tab, d_poses, d_lms, d_blocks, d_cross, d_lmcov, d_z3, d_out);
 }
 
 } // namespace cugo_k

@@ -458,5 +458,12 @@ void launch_reprojection_cov(hipStream_t s, int n, int Lfree, const int32_t* d_q
                              const int32_t* d_q_dim, const int32_t* d_q_aa, const double* d_cam5, const double* d_poses,
                              const double* d_lms, const double* d_blocks, const double* d_cross, const double* d_lmcov,
                              double* d_out);
+// z3 [n][3] and S [n][9] of n predicted observations (k_predict_obs): as launch_reprojection_cov with a kind per query
+// (CUGO_OBS_*) instead of a dim and d_cam_tab [n][17] = {M row-major, t_s, k1..k4, model} per query, or NULL (pinholes
+// at the pose; kinds 2 / 3 then give the bits of launch_reprojection_cov)
+void launch_predict_obs(hipStream_t s, int n, int Lfree, const int32_t* d_q_pose, const int32_t* d_q_lm,
+                        const int32_t* d_q_kind, const int32_t* d_q_aa, const double* d_cam5, const double* d_cam_tab,
+                        const double* d_poses, const double* d_lms, const double* d_blocks, const double* d_cross,
+                        const double* d_lmcov, double* d_z3, double* d_out);
 
 } // namespace cugo_k

@@ -219,11 +219,30 @@ public:
      *  no pose terms, a fixed landmark no landmark terms.  Contract and return value as above; throws
      *  std::invalid_argument for another dim or nCams.  cam5 describes a camera AT THE POSE: on a graph with sensor
      *  poses (setSensorPose: the pose vertex is then the body) this is the reprojection into a camera whose sensor
-     *  pose is the identity; a rig kind here is a later step.  Likewise it is a PINHOLE: on a graph with
-     *  Kannala-Brandt models (setCameraModel) cam5 is still read as fx, fy, cx, cy, bf of X / Z; a fisheye kind is a
-     *  later step. */
+     *  pose is the identity.  Likewise it is a PINHOLE: on a graph with Kannala-Brandt models (setCameraModel) cam5
+     *  is still read as fx, fy, cx, cy, bf of X / Z.  For a camera of a rig, a fisheye camera or a depth observation:
+     *  predictObservations below. */
     bool reprojectionCovariances(int n, const BaseVertex* const* poses, const BaseVertex* const* landmarks, int dim,
                                  const double* cam5, int nCams, double* cov);
+    /** the predicted observation z of landmarks[k] seen from poses[k] and its covariance S = J Sigma J^T, for every
+     *  camera kind the optimiser accepts.  kind: 2 (mono, z = (u, v)), 3 (stereo, (u, v, u_right)) or 4 (depth,
+     *  (u, v, 1 / Z_s)) — CUGO_OBS_MONO / _STEREO / _DEPTH of cugo_hip.h; dim = 2, 3, 3.  Camera of a query: cam5 as
+     *  above; sensorPoses (null: identities) the pose body -> sensor in the convention of setSensorPose, its
+     *  quaternion normalised in fp64 as initialize() does; models (null: pinholes) as setCameraModel.  nCams is 1 or
+     *  n and counts for all three.  With Xb = R(q_a) X_l + t_a and Xs = M Xb + t_s, z is the projection of Xs and J
+     *  the build pass's Jacobians of z - m.  The depth row is that of 1 / Z_s under unit weight: S is in measurement
+     *  units, the inverse-depth weight of a DepthEdgeSet belongs to the caller's noise term.  A depth kind behind a
+     *  sensor pose is defined here (the optimiser refuses such graphs; a query is not a graph).  z [n][dim] is
+     *  computed for fixed vertices too; cov [n][dim * dim] column-major, exactly symmetric, fixed vertices as above.
+     *  With identity sensor poses and pinhole models the kinds 2 / 3 give the bits of reprojectionCovariances.
+     *  false (a zero pivot, or a queried free landmark whose Hll does not factor): z and cov zero-filled.  Throws as
+     *  reprojectionCovariances does, and std::invalid_argument for another kind, a quaternion that is not finite or
+     *  has norm 0, coefficients that are not finite, an unknown model type and a Kannala-Brandt model with kind 3 or
+     *  4.  Nothing guards the projection itself: a pinhole query with Z_s = 0, or a Kannala-Brandt query on the
+     *  negative optical axis, gives inf / NaN in its own z and S. */
+    bool predictObservations(int n, const BaseVertex* const* poses, const BaseVertex* const* landmarks, int kind,
+                             const double* cam5, int nCams, const Se3D* sensorPoses, const CameraModel* models, double* z,
+                             double* cov);
 
 private:
     void poseLandmarkIndices(const char* who, int n, const BaseVertex* const* poses, const BaseVertex* const* landmarks,

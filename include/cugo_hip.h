@@ -342,6 +342,30 @@ int cugo_reprojection_covariances(cugo_ctx* ctx, int n, int n_landmarks_free, co
                                   const int32_t* d_q_lm, const int32_t* d_q_dim, const int32_t* d_q_aa,
                                   const double* d_cam5, const double* d_poses, const double* d_lms,
                                   const double* d_blocks, const double* d_cross18, const double* d_lmcov9, double* d_cov9);
+/* Predicted observation z and its covariance S = J Sigma J^T (the sum above) for every camera kind the optimiser accepts.
+ * Kind of a query, d_q_kind: */
+#define CUGO_OBS_MONO 2   /* z = (u, v) */
+#define CUGO_OBS_STEREO 3 /* z = (u, v, u_right) */
+#define CUGO_OBS_DEPTH 4  /* z = (u, v, 1 / Z_s) */
+/* Camera of a query: d_cam5 [n][5] = fx, fy, cx, cy, bf and, where d_cam_tab is not NULL, d_cam_tab [n][17] = {M row-major
+ * (9), t_s (3), k1..k4, model}: the sensor pose body -> sensor and the projection model (0.0 pinhole, 1.0 Kannala-Brandt)
+ * — the layout of a CUGO_RIG_MODELS camera table, one entry per query.  Geometry: Xb = R(q_a) X_l + t_a,
+ * Xs = M Xb + t_s, z = the projection of Xs; J_p and J_l are the build pass's Jacobians of z - m: with A = -dz/dXs and
+ * B = A M, J_p = [-B [Xb]x, B] and J_l = B R(q_a).  The depth row is that of 1 / Z_s with unit weight: S is in
+ * measurement units, and the inverse-depth weight of a DepthEdgeSet belongs to the caller's noise term.  A depth kind
+ * behind a sensor pose is defined here although the optimiser refuses such graphs.  A Kannala-Brandt entry has two
+ * rows: with kind 3 or 4 it gives those and a zero third row and column (the edge kernels ignore the stereo bit
+ * there).  d_z3 [n][3] (the third 0 where there is no third row) is written for every query, fixed vertices included;
+ * d_cov9 [n][9] and every other argument as for cugo_reprojection_covariances.  With d_cam_tab == NULL and kinds 2 / 3
+ * d_cov9 has the bits of cugo_reprojection_covariances.  Nothing is checked on the device: the caller keeps Z_s != 0
+ * for pinhole entries and the point off the negative optical axis for Kannala-Brandt entries, or reads inf / NaN.
+ * Asynchronous, one thread per query, the same bits on every call.  CUGO_ERR_INVALID for a null required argument or a
+ * negative count; CUGO_OK with nothing launched when n == 0. */
+int cugo_predict_observations(cugo_ctx* ctx, int n, int n_landmarks_free, const int32_t* d_q_pose, const int32_t* d_q_lm,
+                              const int32_t* d_q_kind, const int32_t* d_q_aa, const double* d_cam5,
+                              const double* d_cam_tab /* may be NULL */, const double* d_poses, const double* d_lms,
+                              const double* d_blocks, const double* d_cross18, const double* d_lmcov9, double* d_z3,
+                              double* d_cov9);
 /* statistics of the analysis: nnz(L) in scalars, factorisation flops, #supernodes, #stages */
 int cugo_chol_stats(const cugo_chol* s, double* nnzL, double* flops, int* n_supernodes,
                     int* n_stages, double* front_bytes);
@@ -707,7 +731,8 @@ int cugo_graph_set_robust_kernel(cugo_graph* g, int dim, int type, double delta)
  * poses are all identities runs the kernels it has always run.  cugo_graph_initialize normalises the quaternion and
  * refuses one that is not finite or has norm 0, sensor poses together with depth edges (not yet) and on a
  * landmark-sharded graph (not yet).  Pose priors, relative-pose and ICP edges act on the pose vertex: the body.
- * cugo_graph_reprojection_covariances keeps describing a camera at the pose.
+ * cugo_graph_reprojection_covariances keeps describing a camera at the pose; cugo_graph_predict_observations answers
+ * for the camera behind its sensor pose.
  * cugo_graph_n_rig_cameras: entries of the camera table of the current flattening whose sensor pose is not the
  * identity.  cugo_graph_get_flat_cameras (diagnostic): that table — returns the number of entries and fills the first
  * `cap` of cam5 [cap][5] and ext12 [cap][12] = {M row-major, t} where not NULL; *has_rig: what the edge kernels get. */
@@ -724,7 +749,8 @@ int cugo_graph_get_flat_cameras(cugo_graph* g, int cap, double* cam5, double* ex
  * on a graph created with per_edge_camera only.  A graph whose models are all pinhole runs the kernels it ran before.
  * cugo_graph_initialize refuses a Kannala-Brandt model on stereo edges, together with depth edges (not yet), on a
  * landmark-sharded graph (not yet), and coefficients that are not finite.
- * cugo_graph_reprojection_covariances keeps describing a pinhole camera at the pose.
+ * cugo_graph_reprojection_covariances keeps describing a pinhole camera at the pose; cugo_graph_predict_observations
+ * answers for a Kannala-Brandt camera.
  * cugo_graph_n_fisheye_cameras: entries of the camera table of the current flattening whose model is Kannala-Brandt.
  * cugo_graph_get_flat_camera_models (diagnostic): returns the number of entries of that table and fills the first
  * `cap` of model_k5 [cap][5] = (k1, k2, k3, k4, model) where not NULL; parallel to cugo_graph_get_flat_cameras. */
@@ -834,7 +860,8 @@ int cugo_graph_get_edge_active(cugo_graph* g, int dim, int n, uint8_t* active);
  * the dim-keyed functions above keep meaning mono (2) and stereo (3), these are their counterparts for the depth set.
  * meas3 [n][3]; info [n] (with per-edge information) or NULL; cam5 [n][5] or NULL for the set's camera (bf unused).
  * cugo_graph_initialize refuses a weight that is not finite and > 0, and a depth set on a landmark-sharded (multi-GPU)
- * graph.  cugo_graph_reprojection_covariances keeps its two kinds (2, 3). */
+ * graph.  cugo_graph_reprojection_covariances keeps its two kinds (2, 3); cugo_graph_predict_observations has the
+ * depth kind (CUGO_OBS_DEPTH). */
 int cugo_graph_add_depth_edges(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* landmark_ids,
                                const double* meas3, const double* info, const double* cam5);
 int cugo_graph_set_depth_camera(cugo_graph* g, const double* cam5);
@@ -960,6 +987,19 @@ int cugo_graph_compute_pose_landmark_cross_covariances(cugo_graph* g, int n, con
  * for dim outside {2, 3}. */
 int cugo_graph_reprojection_covariances(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* lm_ids, int dim,
                                         const double* cam5, double* cov);
+/* the predicted observation z of landmark lm_ids[k] seen from pose pose_ids[k] and its covariance S = J Sigma J^T over
+ * the joint [pose; landmark] block, for every camera kind (cugo_predict_observations above: kinds, geometry, the depth
+ * row in measurement units).  kind: CUGO_OBS_MONO / _STEREO / _DEPTH, dim = 2 / 3 / 3; z [n][dim], cov [n][dim*dim]
+ * column-major (host).  cam5 [n][5] per query, with sensor_q_t7 [n][7] = (qx, qy, qz, qw, tx, ty, tz) body -> sensor
+ * (NULL: the identity; the quaternion is normalised in fp64) and model_k5 [n][5] = (k1, k2, k3, k4, model) (NULL: a
+ * pinhole).  cam5 == NULL takes the camera, sensor pose and model of the graph's mono / stereo / depth set for kind
+ * 2 / 3 / 4; the other two must then be NULL too.  Fixed vertices as for cugo_graph_reprojection_covariances; z is
+ * computed for them too.  Error codes as above (CUGO_ERR_NUMERIC: both outputs zero-filled); also CUGO_ERR_INVALID for
+ * a kind outside {2, 3, 4}, a quaternion that is not finite or has norm 0, coefficients that are not finite, an
+ * unknown model and a Kannala-Brandt model with kind 3 or 4. */
+int cugo_graph_predict_observations(cugo_graph* g, int n, const int32_t* pose_ids, const int32_t* lm_ids, int kind,
+                                    const double* cam5, const double* sensor_q_t7, const double* model_k5, double* z,
+                                    double* cov);
 /* per-phase milliseconds accumulated since initialize(): ref getTimeProfile
  * (block_solver.cpp:470-488).  names is a '\n' separated list written into buf. */
 int cugo_graph_time_profile(cugo_graph* g, char* names_buf, int buf_len, double* ms, int cap);
