@@ -59,13 +59,20 @@ cugo_k::ReduceScratch scratch_for(cugo_ctx* ctx, const cugo_edges* ev)
     return {ctx->scratch.data(), ctx->scratch.size()};
 }
 
-// the depth members of an edge view (cugo_edges.has_depth != 0; nothing is read otherwise) are checked before anything
-// is launched: the kernels take sqrt(depth_weight)
-// The rig members (cugo_edges.has_rig != 0; d_cam_ext is not read otherwise) likewise: a table must be there, and the
-// rig-aware kernels hold no depth code yet.
-void check_depth(const cugo_edges* ev, const char* who)
+} // namespace
+
+namespace cugo_host
 {
-    if (ev && ev->has_rig)
+// The members of an edge view that go with its form (cugo_k::edge_form) are checked before anything is launched: with a
+// table (Rig, Models) d_cam_ext must be there, and the kernels that read one hold no depth code yet; with depth slots the
+// kernels take sqrt(depth_weight) and the depth kind's robust kernel.  Nothing of either is read otherwise.
+// (not in the unnamed namespace: tests/test_edge_form_host.py links against it)
+void check_edge_form(const cugo_edges* ev, const char* who)
+{
+    if (!ev)
+        return;
+    const cugo_k::EdgeForm form = cugo_k::edge_form(*ev);
+    if (form == cugo_k::EdgeForm::Rig || form == cugo_k::EdgeForm::Models)
     {
         if (!ev->d_cam_ext)
             throw std::runtime_error(std::string(who) + ": has_rig needs the extrinsics table d_cam_ext");
@@ -73,7 +80,7 @@ void check_depth(const cugo_edges* ev, const char* who)
             throw std::runtime_error(std::string(who) + ": camera extrinsics (has_rig) together with depth slots "
                                                         "(has_depth) are not supported yet");
     }
-    if (!ev || !ev->has_depth)
+    if (!ev->has_depth)
         return;
     if (!(ev->depth_weight > 0.0) || !std::isfinite(ev->depth_weight))
         throw std::runtime_error(std::string(who) + ": depth_weight must be finite and > 0 with has_depth");
@@ -82,7 +89,7 @@ void check_depth(const cugo_edges* ev, const char* who)
         (rk != CUGO_RK_NONE && !(ev->rk_delta_depth > 0.0 && std::isfinite(ev->rk_delta_depth))))
         throw std::runtime_error(std::string(who) + ": unknown robust kernel or bad delta of the depth kind");
 }
-} // namespace
+} // namespace cugo_host
 
 extern "C" {
 
@@ -158,7 +165,7 @@ int cugo_compute_active_errors(cugo_ctx* ctx, const cugo_edges* ev, const double
                                const double* d_lms, cugo_robust rk, double* d_chi)
 {
     return guarded([&] {
-        check_depth(ev, "cugo_compute_active_errors");
+        check_edge_form(ev, "cugo_compute_active_errors");
         cugo_k::launch_errors(ctx->stream, *ev, d_poses, d_lms, rk, scratch_for(ctx, ev), d_chi);
         CUGO_HIP(hipGetLastError());
     });
@@ -170,7 +177,7 @@ int cugo_compute_edge_chi(cugo_ctx* ctx, const cugo_edges* ev, const double* d_p
     return guarded([&] {
         if (!ctx || !ev || !d_edge_chi)
             throw std::runtime_error("cugo_compute_edge_chi: null argument");
-        check_depth(ev, "cugo_compute_edge_chi");
+        check_edge_form(ev, "cugo_compute_edge_chi");
         cugo_k::launch_edge_chi(ctx->stream, *ev, d_poses, d_lms, rk, d_edge_chi);
         CUGO_HIP(hipGetLastError());
     });
@@ -181,7 +188,7 @@ int cugo_construct_quadratic_form(cugo_ctx* ctx, const cugo_edges* ev, const dou
                                   double* d_Hll, double* d_bl, void* d_Hpl, double* d_chi)
 {
     return guarded([&] {
-        check_depth(ev, "cugo_construct_quadratic_form");
+        check_edge_form(ev, "cugo_construct_quadratic_form");
         cugo_k::launch_build(ctx->stream, *ev, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl,
                              scratch_for(ctx, ev), d_chi);
         CUGO_HIP(hipGetLastError());
@@ -456,7 +463,7 @@ int cugo_construct_quadratic_form_lm_priors(cugo_ctx* ctx, const cugo_edges* ev,
             throw std::runtime_error("cugo_lm_prior: no edges or no priors");
         if (lp->n_landmarks_total != ev->n_landmarks_total || lp->n_landmarks_free != ev->n_landmarks_free)
             throw std::runtime_error("cugo_lm_prior: the priors do not describe the landmarks of the edges");
-        check_depth(ev, "cugo_construct_quadratic_form_lm_priors");
+        check_edge_form(ev, "cugo_construct_quadratic_form_lm_priors");
         // (the scratch of the BA pass in front, the priors' workgroup totals and the flag of the index check behind it)
         const size_t ba = cugo_k::reduce_scratch_doubles(ev->n_edges, ev->n_poses_free, ev->n_landmarks_free);
         double* d_wg = check_lm_prior(ctx, lp, ba);
@@ -733,7 +740,7 @@ int cugo_construct_quadratic_form_fused(cugo_ctx* ctx, const cugo_edges* ev, con
             refuse("form 2 needs d_lmrec");
         if (form == 1 && (!d_Hpl || (ev->n_poses_free > 0 && (!d_Hpp || !d_bp))))
             refuse("form 1 needs d_Hpl, d_Hpp and d_bp");
-        check_depth(ev, "cugo_construct_quadratic_form_fused");
+        check_edge_form(ev, "cugo_construct_quadratic_form_fused");
         // what the engine's slot layout guarantees and the fused kernel relies on: a landmark's slots in one group
         for (int l = 0; l < ev->n_landmarks_total; l++)
         {
@@ -773,7 +780,7 @@ int cugo_compute_schur_fused(cugo_ctx* ctx, const cugo_edges* ev, const cugo_hsc
             refuse("form 2 needs d_lmrec, d_poses, d_bp_out and hs->d_rowptr");
         if (form == 1 && (!d_Hpl || !d_bl || (ev->n_poses_free > 0 && (!d_Hpp || !d_bp))))
             refuse("form 1 needs d_Hpl, d_bl, d_Hpp and d_bp");
-        check_depth(ev, "cugo_compute_schur_fused");
+        check_edge_form(ev, "cugo_compute_schur_fused");
         if (!ctx)
             refuse("null context");
         cugo_k::SchurRows rows;
@@ -805,7 +812,7 @@ int cugo_backsubst_update_fused(cugo_ctx* ctx, const cugo_edges* ev, double lamb
             refuse(from_records ? "from_records without the landmarks' lines (d_lmrec)" : "null d_lmrec");
         if (!d_G || !d_bl || !d_bp || !d_xp || !d_xl || !d_poses_in || !d_lms_in || !d_poses_out || !d_lms_out)
             refuse("null argument");
-        check_depth(ev, "cugo_backsubst_update_fused");
+        check_edge_form(ev, "cugo_backsubst_update_fused");
         if (!ctx)
             refuse("null context");
         cugo_k::launch_backsubst_update(ctx->stream, *ev, lambda, lambda, nullptr, d_bl, d_bp, d_G, d_xp, d_xl, d_poses_in,

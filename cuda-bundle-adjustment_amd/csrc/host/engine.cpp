@@ -139,8 +139,6 @@ struct Engine::Impl : cugo_k::LaunchHook
     bool strip_on = false;
     int max_row_nnz = 0;
     DevBuf<double> d_meas, d_omega, d_cams, d_cam_ext; // (d_cam_ext: FlatGraph::cam_ext, only with has_rig)
-    bool has_rig = false;
-    bool has_models = false;         // d_cam_ext then holds the model table (stride 17) assembled below
     std::vector<double> h_cam_tab;
     DevBuf<uint8_t> d_flags;
     DevBuf<uint16_t> d_cam;
@@ -1183,6 +1181,52 @@ struct Engine::Impl::SlotUpload
     }
 };
 
+// What initialize() refuses of a graph's edge and camera kinds, first hit first: a kind on a landmark-sharded optimiser,
+// a camera table of the wrong size, a camera table together with depth edge sets.
+static void refuse_unsupported(const FlatGraph& g, int n_relpose, bool sharded)
+{
+    const size_t n_cams = g.cams.size() / 5;
+    const struct
+    {
+        bool hit;
+        const char* what;
+    } refusals[] = {
+        {g.lm_priors.n() && sharded, "landmark prior edge sets are not supported on a landmark-sharded (multi-GPU) optimiser yet"},
+        {n_relpose && sharded, "relative-pose edge sets are not supported on a landmark-sharded (multi-GPU) optimiser yet"},
+        {g.has_depth && sharded, "depth edge sets are not supported on a landmark-sharded (multi-GPU) optimiser yet"},
+        {g.has_rig && g.cam_ext.size() != 12 * n_cams,
+         "camera extrinsics (sensor poses): the table must hold 12 numbers per camera"},
+        {g.has_rig && g.has_depth, "camera extrinsics (sensor poses) together with depth edge sets are not supported yet"},
+        {g.has_rig && sharded,
+         "camera extrinsics (sensor poses) are not supported on a landmark-sharded (multi-GPU) optimiser yet"},
+        {g.has_models && g.cam_model.size() != 5 * n_cams, "camera models: the table must hold 5 numbers per camera"},
+        {g.has_models && g.has_depth, "camera models (Kannala-Brandt) together with depth edge sets are not supported yet"},
+        {g.has_models && sharded,
+         "camera models (Kannala-Brandt) are not supported on a landmark-sharded (multi-GPU) optimiser yet"},
+    };
+    for (const auto& r : refusals)
+        if (r.hit)
+            throw std::runtime_error(std::string("cugo: ") + r.what);
+}
+
+// The model table of a graph with camera models, which takes the extrinsics' place on the device: {M, t_s, k1..k4, type}
+// per entry; a graph whose sensor poses are all identities has no cam_ext.  Empty without models.
+static void assemble_cam_table(const FlatGraph& g, std::vector<double>& tab)
+{
+    static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    tab.clear();
+    if (!g.has_models)
+        return;
+    const size_t n = g.cams.size() / 5;
+    tab.resize(CUGO_CAM_TAB_STRIDE * n);
+    for (size_t k = 0; k < n; k++)
+    {
+        const double* x = g.has_rig ? &g.cam_ext[12 * k] : I12;
+        std::copy(x, x + 12, &tab[CUGO_CAM_TAB_STRIDE * k]);
+        std::copy(&g.cam_model[5 * k], &g.cam_model[5 * k] + 5, &tab[CUGO_CAM_TAB_STRIDE * k + 12]);
+    }
+}
+
 void Engine::initialize(FlatGraph& g)
 {
     const auto t0 = Clock::now();
@@ -1200,46 +1244,10 @@ void Engine::initialize(FlatGraph& g)
     m.Etot = g.n_edges();
     const int n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
     E_global_ = m.Etot + g.n_pose_edges() + n_relpose + g.lm_priors.n();
-    if (g.lm_priors.n() && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: landmark prior edge sets are not supported on a landmark-sharded (multi-GPU) "
-                                 "optimiser yet");
-    if (n_relpose && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: relative-pose edge sets are not supported on a landmark-sharded (multi-GPU) "
-                                 "optimiser yet");
-    if (g.has_depth && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: depth edge sets are not supported on a landmark-sharded (multi-GPU) "
-                                 "optimiser yet");
-    if (g.has_rig && g.cam_ext.size() != 12 * (g.cams.size() / 5))
-        throw std::runtime_error("cugo: camera extrinsics (sensor poses): the table must hold 12 numbers per camera");
-    if (g.has_rig && g.has_depth)
-        throw std::runtime_error("cugo: camera extrinsics (sensor poses) together with depth edge sets are not "
-                                 "supported yet");
-    if (g.has_rig && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: camera extrinsics (sensor poses) are not supported on a landmark-sharded "
-                                 "(multi-GPU) optimiser yet");
-    m.has_rig = g.has_rig;
-    if (g.has_models && g.cam_model.size() != 5 * (g.cams.size() / 5))
-        throw std::runtime_error("cugo: camera models: the table must hold 5 numbers per camera");
-    if (g.has_models && g.has_depth)
-        throw std::runtime_error("cugo: camera models (Kannala-Brandt) together with depth edge sets are not supported "
-                                 "yet");
-    if (g.has_models && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: camera models (Kannala-Brandt) are not supported on a landmark-sharded "
-                                 "(multi-GPU) optimiser yet");
-    m.has_models = g.has_models;
-    m.h_cam_tab.clear();
-    if (g.has_models)
-    { // {M, t_s, k1..k4, type} per entry; a graph whose sensor poses are all identities has no cam_ext
-        static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-        const size_t n = g.cams.size() / 5;
-        m.h_cam_tab.resize(CUGO_CAM_TAB_STRIDE * n);
-        for (size_t k = 0; k < n; k++)
-        {
-            const double* x = g.has_rig ? &g.cam_ext[12 * k] : I12;
-            std::copy(x, x + 12, &m.h_cam_tab[CUGO_CAM_TAB_STRIDE * k]);
-            std::copy(&g.cam_model[5 * k], &g.cam_model[5 * k] + 5, &m.h_cam_tab[CUGO_CAM_TAB_STRIDE * k + 12]);
-        }
-    }
+    refuse_unsupported(g, n_relpose, m.world > 1 || m.comm);
+    // (every launcher of an edge pass picks its instantiation from this: cugo_k::edge_form)
+    m.ev.has_rig = g.has_models ? CUGO_RIG_MODELS : g.has_rig ? CUGO_RIG_EXTRINSICS : CUGO_RIG_NONE;
+    assemble_cam_table(g, m.h_cam_tab);
     // (k_hsc_offdiag_strip reads the list entry before a block's range: a pair block without products has none)
     if (n_relpose && m.opt.hsc_strip)
         throw std::runtime_error("cugo: relative-pose edge sets cannot be combined with CUGO_HSC_STRIP=1: the row-strip "
@@ -1306,9 +1314,7 @@ void Engine::initialize(FlatGraph& g)
     ev.d_cam = m.slots.n_cams > 1 ? m.d_cam.data() : nullptr, ev.d_cams = m.d_cams.data();
     ev.n_cams = m.slots.n_cams, ev.d_lm_ptr = m.d_lm_ptr.data(), ev.d_pose_ptr = m.d_pose_ptr.data();
     ev.d_pose_edge = m.d_pose_edge.data();
-    // (every launcher of an edge pass picks its rig-aware instantiation from this)
-    ev.has_rig = m.has_models ? CUGO_RIG_MODELS : m.has_rig ? CUGO_RIG_EXTRINSICS : CUGO_RIG_NONE;
-    ev.d_cam_ext = m.has_models || m.has_rig ? m.d_cam_ext.data() : nullptr;
+    ev.d_cam_ext = ev.has_rig ? m.d_cam_ext.data() : nullptr;
     // opt-in (CUGO_HSC_ROWS=1): the Schur complement by whole block rows (k_hsc_rows; slower)
     m.rows_on = !m.plan_only && m.opt.hsc_rows && !m.opt.schur_plan;
     if (m.rows_on)

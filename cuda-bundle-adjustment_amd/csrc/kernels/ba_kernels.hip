@@ -166,6 +166,18 @@ constexpr bool pack_has_model = (false || ... || std::is_same_v<P, CamModelPar>)
 // (the rig code below serves both packs: what differs is the stride and what edge_residual_rig / rig_B do with the entry)
 template <typename... P>
 constexpr bool pack_has_rig = (false || ... || (std::is_same_v<P, RigPar> || std::is_same_v<P, CamModelPar>));
+// (the kernels that read records take the depth kind as its one number, sqrt(weight): record_par below)
+template <typename... P>
+constexpr bool pack_has_depth = (false || ... || (std::is_same_v<P, DepthPar> || std::is_same_v<P, double>));
+// the camera-kind element of a pack (DepthPar or its double, RigPar, CamModelPar), whatever stands in front of it
+template <typename T, typename... R>
+__device__ __forceinline__ decltype(auto) kind_of(const T& t, const R&... r)
+{
+    if constexpr (pack_has_depth<T> || pack_has_rig<T>)
+        return (t);
+    else
+        return kind_of(r...);
+}
 // the extrinsic of slot e / of a record's meta word
 __device__ __forceinline__ const double* ext_of_slot(const EV& ev, const RigPar& rp, int e)
 {
@@ -214,10 +226,17 @@ __device__ __forceinline__ EdgeIn load_edge(const EV& ev, int e, uint8_t fl)
     return in;
 }
 
-// sqrt(inverse-depth weight), without / with the depth kind
-__device__ __forceinline__ double depth_scale_of() { return 0.0; }
-__device__ __forceinline__ double depth_scale_of(double s) { return s; }
-__device__ __forceinline__ double depth_scale_of(const DepthPar dp) { return dp.s; }
+// sqrt(inverse-depth weight) of a pack: 0 without the depth kind
+__device__ __forceinline__ double depth_scale(double s) { return s; }
+__device__ __forceinline__ double depth_scale(const DepthPar& dp) { return dp.s; }
+template <typename... P>
+__device__ __forceinline__ double depth_scale_of(const P&... p)
+{
+    if constexpr (pack_has_depth<P...>)
+        return depth_scale(kind_of(p...));
+    else
+        return 0.0;
+}
 // the kind bits of the meta word of a slot's 64-byte record (k_build_edges): stereo bit 16, depth bit 18
 __device__ __forceinline__ bool record_stereo(long long meta) { return ((meta >> 16) & 1) != 0; }
 template <bool DEP>
@@ -230,17 +249,6 @@ template <typename T, typename... R>
 __device__ __forceinline__ const T& first_of(const T& t, const R&...)
 {
     return t;
-}
-// the last element of a parameter pack
-template <typename T>
-__device__ __forceinline__ const T& last_of(const T& t)
-{
-    return t;
-}
-template <typename T, typename U, typename... R>
-__device__ __forceinline__ decltype(auto) last_of(const T&, const U& u, const R&... r)
-{
-    return last_of(u, r...);
 }
 
 // ---------------------------------------------------------------- reductions -----------
@@ -355,7 +363,7 @@ __global__ __launch_bounds__(BS) void k_errors(EV ev, const double* __restrict__
         if (!(fl & CUGO_EDGE_INACTIVE))
         {
             constexpr bool RIG = pack_has_rig<DP...>;
-            constexpr bool DEP = sizeof...(DP) != 0 && !RIG;
+            constexpr bool DEP = pack_has_depth<DP...>;
             const EdgeIn in = load_edge<DEP>(ev, e, fl);
             const bool depth = is_depth<DEP>(fl);
             EdgeGeom g;
@@ -364,11 +372,11 @@ __global__ __launch_bounds__(BS) void k_errors(EV ev, const double* __restrict__
             // other register figures for the instantiations that existed before — tools/kernel_resources.sh)
             if constexpr (RIG)
                 edge_residual_rig<pack_has_model<DP...>>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
-                                  in.omega, in.cam, ext_of_slot(ev, first_of(dp...), e), in.stereo ? rk.s : rk.m, g);
+                                  in.omega, in.cam, ext_of_slot(ev, kind_of(dp...), e), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
                                       depth, depth_scale_of(dp...), in.omega, in.cam,
-                                      in.stereo ? rk.s : (depth ? first_of(dp...).rk : rk.m), g);
+                                      in.stereo ? rk.s : (depth ? kind_of(dp...).rk : rk.m), g);
             else
                 edge_residual(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr,
                               in.stereo, in.omega, in.cam, in.stereo ? rk.s : rk.m, g);
@@ -395,17 +403,17 @@ __global__ __launch_bounds__(BS) void k_edge_chi(EV ev, const double* __restrict
     if (!(fl & CUGO_EDGE_INACTIVE))
     {
         constexpr bool RIG = pack_has_rig<DP...>;
-        constexpr bool DEP = sizeof...(DP) != 0 && !RIG;
+        constexpr bool DEP = pack_has_depth<DP...>;
         const EdgeIn in = load_edge<DEP>(ev, e, fl);
         const bool depth = is_depth<DEP>(fl);
         EdgeGeom g;
         if constexpr (RIG)
             edge_residual_rig<pack_has_model<DP...>>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
-                              in.omega, in.cam, ext_of_slot(ev, first_of(dp...), e), in.stereo ? rk.s : rk.m, g);
+                              in.omega, in.cam, ext_of_slot(ev, kind_of(dp...), e), in.stereo ? rk.s : rk.m, g);
         else if constexpr (DEP)
             edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth,
                                   depth_scale_of(dp...), in.omega, in.cam,
-                                  in.stereo ? rk.s : (depth ? first_of(dp...).rk : rk.m), g);
+                                  in.stereo ? rk.s : (depth ? kind_of(dp...).rk : rk.m), g);
         else
             edge_residual(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr,
                           in.stereo, in.omega, in.cam, in.stereo ? rk.s : rk.m, g);
@@ -456,16 +464,6 @@ __device__ __forceinline__ LmContrib lm_contrib(const double JL[3][3], const Edg
 }
 
 
-// sqrt(inverse-depth weight) where the DepthPar, if any (DEP), is the last element of a pack
-template <bool DEP, typename... LP>
-__device__ __forceinline__ double depth_scale_in(const LP&... lp)
-{
-    if constexpr (DEP)
-        return last_of(lp...).s;
-    else
-        return 0.0;
-}
-
 // (153 VGPRs, no private segment: three waves per SIMD — tools/kernel_resources.sh.  Capped at 128 — four waves — the kernel spills ~230 bytes per lane and takes
 // 75 instead of 56 us: 11.43 vs 11.17 ms per step, 38.9 vs 38.2 ms on the 10k-pose graph.)
 // LMP: landmark position priors (lm_prior_term.h) ride along: LP is then the one LmPriorView.  The
@@ -484,10 +482,10 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
                                                     double fuse_lambda, double* __restrict__ invHll,
                                                     S* __restrict__ T, double* __restrict__ lmrec, LP... lp)
 {
-    static_assert(sizeof...(LP) == (LMP ? 1 : 0) || sizeof...(LP) == (LMP ? 2 : 1),
-                  "the view of the landmark priors goes with LMP, the DepthPar or RigPar behind it");
     constexpr bool RIG = pack_has_rig<LP...>;
-    constexpr bool DEP = sizeof...(LP) == (LMP ? 2 : 1) && !RIG;
+    constexpr bool DEP = pack_has_depth<LP...>;
+    static_assert(sizeof...(LP) == (LMP ? 1 : 0) + (RIG || DEP ? 1 : 0),
+                  "the view of the landmark priors goes with LMP, the one camera-kind element behind it");
     // fuse_lambda >= 0 (the engine, whose slot layout keeps a landmark inside one workgroup, from the
     // second LM iteration on: the damping of the first trial is known when the build is queued): this
     // pass also leaves invHll = (Hll + lambda I)^-1 and T = Hpl invHll — exactly what k_schur_edges
@@ -527,15 +525,15 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
         {
             const EdgeIn in = load_edge<DEP>(ev, e, fl);
             const bool depth = is_depth<DEP>(fl);
-            const double sd = depth_scale_in<DEP>(lp...);
+            const double sd = depth_scale_of(lp...);
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
             if constexpr (RIG)
                 edge_residual_rig<pack_has_model<LP...>>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
-                                  ext_of_slot(ev, last_of(lp...), e), in.stereo ? rk.s : rk.m, g);
+                                  ext_of_slot(ev, kind_of(lp...), e), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
-                                      in.cam, in.stereo ? rk.s : (depth ? last_of(lp...).rk : rk.m), g);
+                                      in.cam, in.stereo ? rk.s : (depth ? kind_of(lp...).rk : rk.m), g);
             else
                 edge_residual(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega,
                               in.cam, in.stereo ? rk.s : rk.m, g);
@@ -556,7 +554,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             {
                 double R[3][3];
                 quat_to_rot(pose, R);
-                rig_B<pack_has_model<LP...>>(g.Xc, in.cam, ext_of_slot(ev, last_of(lp...), e), in.stereo, true, B);
+                rig_B<pack_has_model<LP...>>(g.Xc, in.cam, ext_of_slot(ev, kind_of(lp...), e), in.stereo, true, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -626,15 +624,15 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
                 continue;
             const EdgeIn in = load_edge<DEP>(ev, ee, fl);
             const bool depth = is_depth<DEP>(fl);
-            const double sd = depth_scale_in<DEP>(lp...);
+            const double sd = depth_scale_of(lp...);
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
             if constexpr (RIG)
                 edge_residual_rig<pack_has_model<LP...>>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
-                                  ext_of_slot(ev, last_of(lp...), ee), in.stereo ? rk.s : rk.m, g);
+                                  ext_of_slot(ev, kind_of(lp...), ee), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
-                                      in.cam, in.stereo ? rk.s : (depth ? last_of(lp...).rk : rk.m), g);
+                                      in.cam, in.stereo ? rk.s : (depth ? kind_of(lp...).rk : rk.m), g);
             else
                 edge_residual(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega,
                               in.cam, in.stereo ? rk.s : rk.m, g);
@@ -643,7 +641,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             {
                 double R[3][3], B[3][3];
                 quat_to_rot(pose, R);
-                rig_B<pack_has_model<LP...>>(g.Xc, in.cam, ext_of_slot(ev, last_of(lp...), ee), in.stereo, true, B);
+                rig_B<pack_has_model<LP...>>(g.Xc, in.cam, ext_of_slot(ev, kind_of(lp...), ee), in.stereo, true, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -886,11 +884,11 @@ __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restr
             if constexpr (pack_has_rig<DS...>)
             {
                 double B[3][3];
-                rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, w != 0.0, B);
+                rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, w != 0.0, B);
                 jac_pose_rig(Xc, B, JP);
             }
             else
-                jac_pose_k<sizeof...(DS) != 0>(Xc, cam, stereo, record_depth<sizeof...(DS) != 0>(meta), depth_scale_of(ds...), JP);
+                jac_pose_k<pack_has_depth<DS...>>(Xc, cam, stereo, record_depth<pack_has_depth<DS...>>(meta), depth_scale_of(ds...), JP);
             int k = 0;
 #pragma unroll
             for (int rr = 0; rr < 6; rr++)
@@ -1032,7 +1030,7 @@ __global__ __launch_bounds__(PS_BS, PS_WAVES<DS...>) void k_pose_schur(EV ev, co
         const long long meta = __double_as_longlong(r[7]);
         wave_sync_lds(); // (the slot is refilled by the next round)
         constexpr bool RIG = pack_has_rig<DS...>;
-        constexpr bool DEP = sizeof...(DS) != 0 && !RIG;
+        constexpr bool DEP = pack_has_depth<DS...>;
         const bool stereo = record_stereo(meta);
         const bool depth = record_depth<DEP>(meta);
         const bool act = i < i1 && ((meta >> 17) & 1) != 0;
@@ -1055,7 +1053,7 @@ __global__ __launch_bounds__(PS_BS, PS_WAVES<DS...>) void k_pose_schur(EV ev, co
             if constexpr (RIG)
             {
                 double B[3][3];
-                rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, wgt != 0.0, B);
+                rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, wgt != 0.0, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -1092,7 +1090,7 @@ __global__ __launch_bounds__(PS_BS, PS_WAVES<DS...>) void k_pose_schur(EV ev, co
         if constexpr (RIG)
         { // (B formed again: the same function on the same inputs, and nothing of it lives across the barrier above)
             double B[3][3];
-            rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(first_of(ds...), meta), stereo, wgt != 0.0, B);
+            rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, wgt != 0.0, B);
             jac_pose_rig(Xc, B, JP);
         }
         else
@@ -2549,7 +2547,7 @@ __device__ __forceinline__ void gT_x_from_record(const double* r8, const double*
     const long long bits = __double_as_longlong(r8[7]);
     const double* cam = cams + 5 * (int)(bits & 0xffff);
     constexpr bool RIG = pack_has_rig<DS...>;
-    constexpr bool DEP = sizeof...(DS) != 0 && !RIG;
+    constexpr bool DEP = pack_has_depth<DS...>;
     const bool stereo = record_stereo(bits);
     const bool depth = record_depth<DEP>(bits);
     double JL[3][3], JP[3][6];
@@ -2557,7 +2555,7 @@ __device__ __forceinline__ void gT_x_from_record(const double* r8, const double*
     {
         double R[3][3], B[3][3];
         quat_to_rot(pose, R);
-        rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(first_of(ds...), bits), stereo, w != 0.0, B);
+        rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), bits), stereo, w != 0.0, B);
         jac_landmark_rig(B, R, JL);
         jac_pose_rig(Xc, B, JP);
     }
@@ -2769,34 +2767,67 @@ size_t reduce_scratch_doubles(int n_edges, int n_poses, int n_landmarks)
     return scratch_partials(n_edges, n_poses, n_landmarks) + 8 * ((size_t)n_edges + BS);
 }
 
-// the depth kind of an edge view (cugo_edges.has_depth != 0): its robust kernel and s = sqrt(weight), formed once here
-static DepthPar depth_par(const cugo_edges& e)
+// launch + per-kernel timing scope for a kernel template: the launch hook sees `name`, the plain kernel name
+template <typename... KA, typename... A>
+static void launch_as(const char* name, void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args)
 {
-    return DepthPar{{e.rk_type_depth, e.rk_delta_depth}, std::sqrt(e.depth_weight)};
+    LaunchScope scope(name, s);
+    kernel<<<grid, block, lds, s>>>(args...);
 }
-// the extrinsics of an edge view (cugo_edges.has_rig != 0, never together with has_depth: the callers have checked)
-static RigPar rig_par(const cugo_edges& e) { return RigPar{e.d_cam_ext}; }
-// has_rig == CUGO_RIG_MODELS: d_cam_ext is a model table, stride 17 (the launchers below pick CamModelPar iff so)
-static CamModelPar model_par(const cugo_edges& e) { return CamModelPar{e.d_cam_ext}; }
-static bool has_models(const cugo_edges& e) { return e.has_rig == CUGO_RIG_MODELS; }
+
+EdgeForm edge_form(const cugo_edges& e)
+{
+    if (e.has_rig)
+        return e.has_rig == CUGO_RIG_MODELS ? EdgeForm::Models : EdgeForm::Rig;
+    return e.has_depth ? EdgeForm::Depth : EdgeForm::Plain;
+}
+// THE place where the instantiation of an edge view is picked (edge_form, kernels.h): f is called with the parameter
+// object of the view's form — nothing, the DepthPar (robust kernel of the depth kind and s = sqrt(weight), formed once
+// here), the RigPar, or the CamModelPar (d_cam_ext is then the model table, stride 17) — and passes it on as the trailing
+// pack of its kernel: kernel<decltype(par)...>(..., par...)
+template <typename F>
+static void with_form(const cugo_edges& e, F&& f)
+{
+    switch (edge_form(e))
+    {
+    case EdgeForm::Models: return f(CamModelPar{e.d_cam_ext});
+    case EdgeForm::Rig: return f(RigPar{e.d_cam_ext});
+    case EdgeForm::Depth: return f(DepthPar{{e.rk_type_depth, e.rk_delta_depth}, std::sqrt(e.depth_weight)});
+    case EdgeForm::Plain: return f();
+    }
+}
+// ... and what the kernels that read the build pass's records (k_build_poses, k_pose_schur, k_backsubst_landmarks) take
+// of it: of the depth kind only s, the others as they are
+static double record_par(const DepthPar& dp) { return dp.s; }
+static RigPar record_par(const RigPar& rp) { return rp; }
+static CamModelPar record_par(const CamModelPar& mp) { return mp; }
+// the block storage type S of an edge view (cugo_edges.block_f32): f is called with a float or a double
+template <typename F>
+static auto with_storage(const cugo_edges& e, F&& f)
+{
+    if (e.block_f32)
+        return f(float());
+    return f(double());
+}
+
+// the error pass: one chi2 partial per 256 slots to d_chi_part; returns their number
+static int launch_k_errors(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms, cugo_robust rk,
+                           double* d_chi_part)
+{
+    const EV ev = make_ev(e);
+    const int nb = div_up(ev.E, BS);
+    if (nb > 0)
+        with_form(e, [&](auto... par) {
+            launch_as("k_errors", k_errors<decltype(par)...>, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                      Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, par...);
+        });
+    return nb;
+}
 
 void launch_errors(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                    cugo_robust rk, ReduceScratch rs, double* d_chi)
 {
-    const EV ev = make_ev(e);
-    const int nb = div_up(ev.E, BS);
-    if (nb > 0 && has_models(e))
-        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials, model_par(e));
-    else if (nb > 0 && e.has_rig)
-        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials, rig_par(e));
-    else if (nb > 0 && e.has_depth)
-        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials, depth_par(e));
-    else if (nb > 0)
-        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, rs.d_partials);
+    const int nb = launch_k_errors(s, e, d_poses, d_lms, rk, rs.d_partials);
     CUGO_LAUNCH(k_sum_partials, dim3(1), dim3(SP_BS), 0, s, rs.d_partials, nb, d_chi);
 }
 
@@ -2806,22 +2837,10 @@ void launch_errors_tail(hipStream_t s, const cugo_edges& e, const double* d_pose
                         int n_icp_chi)
 {
     const EV ev = make_ev(e);
-    const int nb = div_up(ev.E, BS);
     // the scale partials of the update pass sit at the start of the scratch: the error pass uses the
     // record area behind the partial slots (free between two build passes)
     double* d_chi_part = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-    if (nb > 0 && has_models(e))
-        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, model_par(e));
-    else if (nb > 0 && e.has_rig)
-        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, rig_par(e));
-    else if (nb > 0 && e.has_depth)
-        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part, depth_par(e));
-    else if (nb > 0)
-        CUGO_LAUNCH(k_errors, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_part);
+    const int nb = launch_k_errors(s, e, d_poses, d_lms, rk, d_chi_part);
     CUGO_LAUNCH(k_sum_partials2, dim3(2), dim3(SP_BS), 0, s, d_chi_part, nb, rs.d_partials, n_scale_partials,
                 d_out, d_flag, h_out, seq, d_done, d_icp_chi, n_icp_chi);
 }
@@ -2831,34 +2850,17 @@ void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, 
 {
     const EV ev = make_ev(e);
     const int nb = div_up(ev.E, BS);
-    if (nb > 0 && has_models(e))
-        CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, model_par(e));
-    else if (nb > 0 && e.has_rig)
-        CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, rig_par(e));
-    else if (nb > 0 && e.has_depth)
-        CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, depth_par(e));
-    else if (nb > 0)
-        CUGO_LAUNCH(k_edge_chi, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
-                           Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e);
+    if (nb > 0)
+        with_form(e, [&](auto... par) {
+            launch_as("k_edge_chi", k_edge_chi<decltype(par)...>, dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms,
+                      Robust2{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}}, d_chi_e, par...);
+        });
 }
 
-// kernel templated on the block storage type S: the launch hook sees the plain kernel name
-#define CUGO_LAUNCH_T(kernel, S, grid, block, lds, stream, ...)                     \
-    do                                                                              \
-    {                                                                               \
-        ::cugo_k::LaunchScope _scope(#kernel, stream);                              \
-        hipLaunchKernelGGL(kernel<S>, grid, block, lds, stream, __VA_ARGS__);       \
-    } while (0)
-
-template <typename S>
-static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
-                           cugo_robust rk, double* d_Hpp, double* d_bp, double* d_Hll, double* d_bl,
-                           S* d_Hpl, ReduceScratch rs, double* d_chi, double fuse_lambda, double* d_invHll,
-                           S* d_T, double* d_lmrec, bool skip_poses, bool chi_behind_scale,
-                           const cugo_lm_prior_edges* lm_priors)
+void launch_build(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
+                  cugo_robust rk, double* d_Hpp, double* d_bp, double* d_Hll, double* d_bl,
+                  void* d_Hpl, ReduceScratch rs, double* d_chi, double fuse_lambda, double* d_invHll, void* d_T,
+                  double* d_lmrec, bool skip_poses, bool chi_behind_scale, const cugo_lm_prior_edges* lm_priors)
 {
     const EV ev = make_ev(e);
     const Robust2 r{{rk.type, rk.delta}, {rk.type_stereo, rk.delta_stereo}};
@@ -2867,85 +2869,32 @@ static void launch_build_t(hipStream_t s, const cugo_edges& e, const double* d_p
     // chi_behind_scale: this build pass ends a trial (launch_trial_tail_from_build sums its chi2 partials together with
     // the scale partials of the update pass, which sit at the start of the scratch)
     double* d_chi_part = rs.d_partials + (chi_behind_scale ? spec_chi_offset(ev.E, ev.P, ev.L) : 0);
-    const bool lmp = lm_priors && lm_priors->n > 0;
-    if (nb > 0 && has_models(e))
-    { // the same with a model table (Kannala-Brandt entries)
-        ::cugo_k::LaunchScope _scope("k_build_edges", s);
-        if (lmp)
-            hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView, CamModelPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses,
-                               d_lms, r, d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll,
-                               d_T, d_invHll && d_T ? d_lmrec : nullptr, lm_prior_view(*lm_priors), model_par(e));
-        else
-            hipLaunchKernelGGL((k_build_edges<S, false, CamModelPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r,
-                               d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
-                               d_invHll && d_T ? d_lmrec : nullptr, model_par(e));
-    }
-    else if (nb > 0 && e.has_rig)
-    { // the rig-aware instantiations: only for an edge view whose camera table carries extrinsics
-        ::cugo_k::LaunchScope _scope("k_build_edges", s);
-        if (lmp)
-            hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView, RigPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses,
-                               d_lms, r, d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll,
-                               d_T, d_invHll && d_T ? d_lmrec : nullptr, lm_prior_view(*lm_priors), rig_par(e));
-        else
-            hipLaunchKernelGGL((k_build_edges<S, false, RigPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r,
-                               d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
-                               d_invHll && d_T ? d_lmrec : nullptr, rig_par(e));
-    }
-    else if (nb > 0 && e.has_depth)
-    { // the depth-aware instantiations: only for an edge view that says depth slots may be present
-        ::cugo_k::LaunchScope _scope("k_build_edges", s);
-        if (lmp)
-            hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView, DepthPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses,
-                               d_lms, r, d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll,
-                               d_T, d_invHll && d_T ? d_lmrec : nullptr, lm_prior_view(*lm_priors), depth_par(e));
-        else
-            hipLaunchKernelGGL((k_build_edges<S, false, DepthPar>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r,
-                               d_Hpl, d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
-                               d_invHll && d_T ? d_lmrec : nullptr, depth_par(e));
-    }
-    else if (nb > 0 && lmp)
-    {
-        ::cugo_k::LaunchScope _scope("k_build_edges", s);
-        hipLaunchKernelGGL((k_build_edges<S, true, LmPriorView>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r, d_Hpl,
-                           d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
-                           d_invHll && d_T ? d_lmrec : nullptr, lm_prior_view(*lm_priors));
-    }
-    else if (nb > 0)
-    {
-        ::cugo_k::LaunchScope _scope("k_build_edges", s);
-        hipLaunchKernelGGL((k_build_edges<S, false>), dim3(nb), dim3(BS), 0, s, ev, d_poses, d_lms, r, d_Hpl, d_Hll,
-                           d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0, d_invHll, d_T,
-                           d_invHll && d_T ? d_lmrec : nullptr);
-    }
+    if (nb > 0)
+        with_storage(e, [&](auto S0) {
+            using S = decltype(S0);
+            // lp: the view of the landmark priors, if any, then the parameter object of the form, if any
+            auto edges = [&](auto... lp) {
+                constexpr bool LMP = (false || ... || std::is_same_v<decltype(lp), LmPriorView>);
+                launch_as("k_build_edges", k_build_edges<S, LMP, decltype(lp)...>, dim3(nb), dim3(BS), 0, s, ev, d_poses,
+                          d_lms, r, static_cast<S*>(d_Hpl), d_Hll, d_bl, d_rec, d_chi_part, d_invHll ? fuse_lambda : -1.0,
+                          d_invHll, static_cast<S*>(d_T), d_invHll && d_T ? d_lmrec : nullptr, lp...);
+            };
+            with_form(e, [&](auto... par) {
+                if (lm_priors && lm_priors->n > 0)
+                    edges(lm_prior_view(*lm_priors), par...);
+                else
+                    edges(par...);
+            });
+        });
     if (d_chi)
         CUGO_LAUNCH(k_sum_partials, dim3(1), dim3(SP_BS), 0, s, d_chi_part, nb, d_chi);
     // skip_poses: the Schur complement of this lambda forms Hsc's diagonal blocks, bp and bsc from the records itself
     // (launch_schur with SchurRows::d_lmrec); Hpp is then not written
     if (ev.P > 0 && !(skip_poses && d_invHll && d_T && d_lmrec))
-    {
-        if (has_models(e))
-            CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, model_par(e));
-        else if (e.has_rig)
-            CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, rig_par(e));
-        else if (e.has_depth)
-            CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp, depth_par(e).s);
-        else
-            CUGO_LAUNCH(k_build_poses, dim3(ev.P), dim3(BS), 0, s, ev, d_rec, d_Hpp, d_bp);
-    }
-}
-
-void launch_build(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
-                  cugo_robust rk, double* d_Hpp, double* d_bp, double* d_Hll, double* d_bl,
-                  void* d_Hpl, ReduceScratch rs, double* d_chi, double fuse_lambda, double* d_invHll, void* d_T,
-                  double* d_lmrec, bool skip_poses, bool chi_behind_scale, const cugo_lm_prior_edges* lm_priors)
-{
-    if (e.block_f32)
-        launch_build_t(s, e, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, static_cast<float*>(d_Hpl), rs, d_chi,
-                       fuse_lambda, d_invHll, static_cast<float*>(d_T), d_lmrec, skip_poses, chi_behind_scale, lm_priors);
-    else
-        launch_build_t(s, e, d_poses, d_lms, rk, d_Hpp, d_bp, d_Hll, d_bl, static_cast<double*>(d_Hpl), rs, d_chi,
-                       fuse_lambda, d_invHll, static_cast<double*>(d_T), d_lmrec, skip_poses, chi_behind_scale, lm_priors);
+        with_form(e, [&](auto... par) {
+            launch_as("k_build_poses", k_build_poses<decltype(record_par(par))...>, dim3(ev.P), dim3(BS), 0, s, ev, d_rec,
+                      d_Hpp, d_bp, record_par(par)...);
+        });
 }
 
 // The end of a trial whose chi2 comes out of the NEXT iteration's build pass (launch_build with chi_behind_scale, queued
@@ -2986,8 +2935,8 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
     {
         const SchurPlanDev pl{hs.d_grp_ptr, hs.d_grp_nwave, hs.d_slot_rhs, hs.d_slot_ptr, hs.d_prod, hs.d_part_H, hs.d_part_b};
         if (ev.E > 0)
-            CUGO_LAUNCH_T(k_schur_fused, S, dim3(hs.n_groups), dim3(SF_BS), 0, s, ev, lambda, d_Hll, d_bl, d_Hpl,
-                          d_invHll, d_T, pl);
+            launch_as("k_schur_fused", k_schur_fused<S>, dim3(hs.n_groups), dim3(SF_BS), 0, s, ev, lambda, d_Hll, d_bl, d_Hpl,
+                      d_invHll, d_T, pl);
         if (hs.n_blocks > 0)
             CUGO_LAUNCH(k_hsc_reduce, dim3(div_up(hs.n_blocks, BS / 64)), dim3(BS), 0, s, hs.n_blocks, hs.d_red_ptr,
                         hs.d_red_slot, hs.d_slot_rhs, hs.d_blk_pose, hs.d_part_H, hs.d_part_b,
@@ -3009,17 +2958,17 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
                                               hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
                     attr_set[sizeof(S) == 4] = true;
                 }
-                CUGO_LAUNCH_T(k_hsc_rows, S, dim3(xcd_grid(ev.P)), dim3(HR_BS), lds, s, ev,
-                              reinterpret_cast<const int4*>(rows.d_pose_rec), hs.d_rowptr, hs.d_colind,
-                              damp_hsc_diag ? lambda : 0.0, d_Hpp, d_bp, d_bl, (const double*)d_invHll, d_Hpl, d_Hsc,
-                              d_bsc, std::max(rows.max_row_nnz, 1));
+                launch_as("k_hsc_rows", k_hsc_rows<S>, dim3(xcd_grid(ev.P)), dim3(HR_BS), lds, s, ev,
+                          reinterpret_cast<const int4*>(rows.d_pose_rec), hs.d_rowptr, hs.d_colind,
+                          damp_hsc_diag ? lambda : 0.0, d_Hpp, d_bp, d_bl, (const double*)d_invHll, d_Hpl, d_Hsc,
+                          d_bsc, std::max(rows.max_row_nnz, 1));
             }
             return;
         }
     }
     if (ev.E > 0 && !have_T) // have_T: the build pass left invHll and T for this lambda (launch_build)
-        CUGO_LAUNCH_T(k_schur_edges, S, dim3(div_up(ev.E, BS)), dim3(BS), 0, s, ev, lambda, d_Hll,
-                      d_Hpl, d_invHll, d_T);
+        launch_as("k_schur_edges", k_schur_edges<S>, dim3(div_up(ev.E, BS)), dim3(BS), 0, s, ev, lambda, d_Hll,
+                  d_Hpl, d_invHll, d_T);
     // one-stream form (k_build_edges with lmrec): T holds G and Hpl was not written, Hsc_ij = - sum G_i G_j^T — for the
     // off-diagonal kernel on the matrix cores and for the one on the vector lanes (CUGO_HSC_MFMA=0) alike
     const S* d_Hpl_off = (have_T && rows.d_lmrec) ? (const S*)d_T : d_Hpl;
@@ -3032,8 +2981,8 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)hs_lds_bytes());
             attr_set[sizeof(S) == 4] = true;
         }
-        CUGO_LAUNCH_T(k_hsc_offdiag_strip, S, dim3(xcd_grid(ev.P)), dim3(HS_BS), hs_lds_bytes(), s, ev, hs.d_rowptr,
-                      hs.d_off_ptr, hs.d_off_ei, rows.d_off_pi, hs.d_off_ej, d_Hpl, (const S*)d_T, d_Hsc);
+        launch_as("k_hsc_offdiag_strip", k_hsc_offdiag_strip<S>, dim3(xcd_grid(ev.P)), dim3(HS_BS), hs_lds_bytes(), s, ev,
+                  hs.d_rowptr, hs.d_off_ptr, hs.d_off_ei, rows.d_off_pi, hs.d_off_ej, d_Hpl, (const S*)d_T, d_Hsc);
     }
     else if (hs.n_blocks > 0 && rows.mfma)
     { // (rows.mfma == 0, CUGO_HSC_MFMA=0: the vector-lane kernels below; 2: only the off-diagonal kernel here)
@@ -3041,54 +2990,44 @@ static void launch_schur_t(hipStream_t s, const cugo_edges& e, const cugo_hsc_st
         // per step on the 10k-pose graph, 11.38 vs 11.36 ms on the kitti_00 shape — with the LDS port out of the
         // way the kernel is bound by its L2 misses, and rows that share T operands now meet in one L2 (the
         // vector-lane kernel, bound by LDS reads, was slower with this mapping: 123 vs 112 us)
-        ::cugo_k::LaunchScope _scope("k_hsc_offdiag_mfma", s);
-        if (rows.xcd)
-            hipLaunchKernelGGL((k_hsc_offdiag_mfma<S, true>), dim3(xcd_grid(div_up(hs.n_blocks, BS / 64))), dim3(BS), 0, s,
-                               hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl_off, (const S*)d_T, d_Hsc);
-        else
-            hipLaunchKernelGGL((k_hsc_offdiag_mfma<S, false>), dim3(div_up(hs.n_blocks, BS / 64)), dim3(BS), 0, s,
-                               hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl_off, (const S*)d_T, d_Hsc);
+        const int nwg = div_up(hs.n_blocks, BS / 64);
+        launch_as("k_hsc_offdiag_mfma", rows.xcd ? k_hsc_offdiag_mfma<S, true> : k_hsc_offdiag_mfma<S, false>,
+                  dim3(rows.xcd ? xcd_grid(nwg) : nwg), dim3(BS), 0, s, hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej,
+                  d_Hpl_off, (const S*)d_T, d_Hsc);
     }
     else if (hs.n_blocks > 0)
-        CUGO_LAUNCH_T(k_hsc_offdiag, S, dim3(div_up(hs.n_blocks, BS / 64)), dim3(BS), 0, s,
-                      hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl_off, (const S*)d_T, d_Hsc);
+        launch_as("k_hsc_offdiag", k_hsc_offdiag<S>, dim3(div_up(hs.n_blocks, BS / 64)), dim3(BS), 0, s,
+                  hs.n_blocks, hs.d_off_ptr, hs.d_off_ei, hs.d_off_ej, d_Hpl_off, (const S*)d_T, d_Hsc);
     if (ev.P > 0 && have_T && rows.d_lmrec)
     { // fused iteration: diagonal blocks, bp and bsc from the build pass's records (its pose pass was skipped)
         const double* d_rec = rows.rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-        if (has_models(e))
-            CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
-                        hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc, model_par(e));
-        else if (e.has_rig)
-            CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
-                        hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc, rig_par(e));
-        else if (e.has_depth)
-            CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
-                        hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc, depth_par(e).s);
-        else
-            CUGO_LAUNCH(k_pose_schur, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s, ev, d_rec, rows.d_lmrec, rows.d_poses,
-                        hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc, rows.d_bp_out, d_bsc);
+        with_form(e, [&](auto... par) {
+            launch_as("k_pose_schur", k_pose_schur<decltype(record_par(par))...>, dim3(xcd_grid(ev.P)), dim3(PS_BS), 0, s,
+                      ev, d_rec, rows.d_lmrec, rows.d_poses, hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hsc,
+                      rows.d_bp_out, d_bsc, record_par(par)...);
+        });
     }
     else if (ev.P > 0 && rows.mfma == 1)
-        CUGO_LAUNCH_T(k_hsc_diag_mfma, S, dim3(xcd_grid(ev.P)), dim3(HM_BS), 0, s, ev,
-                      hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hpp, d_bp, d_bl, d_Hpl, (const S*)d_T,
-                      d_Hsc, d_bsc);
+        launch_as("k_hsc_diag_mfma", k_hsc_diag_mfma<S>, dim3(xcd_grid(ev.P)), dim3(HM_BS), 0, s, ev,
+                  hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hpp, d_bp, d_bl, d_Hpl, (const S*)d_T,
+                  d_Hsc, d_bsc);
     else if (ev.P > 0)
-        CUGO_LAUNCH_T(k_hsc_diag, S, dim3(xcd_grid(ev.P)), dim3(HD_BS), 0, s, ev,
-                      hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hpp, d_bp, d_bl, d_Hpl, (const S*)d_T,
-                      d_Hsc, d_bsc);
+        launch_as("k_hsc_diag", k_hsc_diag<S>, dim3(xcd_grid(ev.P)), dim3(HD_BS), 0, s, ev,
+                  hs.d_rowptr, damp_hsc_diag ? lambda : 0.0, d_Hpp, d_bp, d_bl, d_Hpl, (const S*)d_T,
+                  d_Hsc, d_bsc);
 }
 
+// (the pair stays: its body is the Schur-form selection, which is left as it is)
 void launch_schur(hipStream_t s, const cugo_edges& e, const cugo_hsc_struct& hs, double lambda,
                   int damp_hsc_diag, const double* d_Hpp, const double* d_bp, const double* d_Hll,
                   const double* d_bl, const void* d_Hpl, double* d_invHll, void* d_T,
                   double* d_bsc, double* d_Hsc, bool have_T, SchurRows rows)
 {
-    if (e.block_f32)
-        launch_schur_t(s, e, hs, lambda, damp_hsc_diag, d_Hpp, d_bp, d_Hll, d_bl,
-                       static_cast<const float*>(d_Hpl), d_invHll, static_cast<float*>(d_T), d_bsc, d_Hsc, have_T, rows);
-    else
-        launch_schur_t(s, e, hs, lambda, damp_hsc_diag, d_Hpp, d_bp, d_Hll, d_bl,
-                       static_cast<const double*>(d_Hpl), d_invHll, static_cast<double*>(d_T), d_bsc, d_Hsc, have_T, rows);
+    with_storage(e, [&](auto S0) {
+        using S = decltype(S0);
+        launch_schur_t(s, e, hs, lambda, damp_hsc_diag, d_Hpp, d_bp, d_Hll, d_bl, static_cast<const S*>(d_Hpl), d_invHll,
+                       static_cast<S*>(d_T), d_bsc, d_Hsc, have_T, rows);
+    });
 }
 
 bool schur_rows_usable(const cugo_hsc_struct& hs, int max_row_nnz)
@@ -3115,47 +3054,6 @@ void launch_pose_rec(hipStream_t s, const cugo_edges& e, int n, int32_t* d_rec)
         CUGO_LAUNCH(k_pose_rec, dim3(div_up(n, BS)), dim3(BS), 0, s, ev, n, reinterpret_cast<int4*>(d_rec));
 }
 
-template <typename S>
-static int launch_backsubst_update_t(hipStream_t s, const cugo_edges& e, double lambda, double lambda_pose,
-                                      const double* d_invHll, const double* d_bl, const double* d_bp,
-                                      const S* d_Hpl, const double* d_xp, double* d_xl,
-                                      const double* d_poses_in, const double* d_lms_in, double* d_poses_out,
-                                      double* d_lms_out, ReduceScratch rs, double* d_scale, const double* d_lmrec,
-                                      bool from_records)
-{
-    const EV ev = make_ev(e);
-    const int nbl = div_up(ev.E > ev.L ? ev.E : ev.L, BS), nbp = div_up(ev.P, BS);
-    if (nbl + nbp > 0)
-    {
-        ::cugo_k::LaunchScope _scope("k_backsubst_landmarks", s);
-        // from_records: G^T dx_p from the build pass's records in the scratch instead of the G stream
-        const double* d_rec = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
-        if (from_records && d_lmrec && has_models(e))
-            hipLaunchKernelGGL((k_backsubst_landmarks<S, true, CamModelPar>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda,
-                               d_invHll, d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
-                               d_poses_in, d_poses_out, d_lmrec, d_rec, model_par(e));
-        else if (from_records && d_lmrec && e.has_rig)
-            hipLaunchKernelGGL((k_backsubst_landmarks<S, true, RigPar>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda,
-                               d_invHll, d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
-                               d_poses_in, d_poses_out, d_lmrec, d_rec, rig_par(e));
-        else if (from_records && d_lmrec && e.has_depth)
-            hipLaunchKernelGGL((k_backsubst_landmarks<S, true, double>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda,
-                               d_invHll, d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
-                               d_poses_in, d_poses_out, d_lmrec, d_rec, depth_par(e).s);
-        else if (from_records && d_lmrec)
-            hipLaunchKernelGGL((k_backsubst_landmarks<S, true>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda, d_invHll,
-                               d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
-                               d_poses_in, d_poses_out, d_lmrec, d_rec);
-        else
-            hipLaunchKernelGGL((k_backsubst_landmarks<S, false>), dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda, d_invHll,
-                               d_bl, d_Hpl, d_xp, d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp,
-                               d_poses_in, d_poses_out, d_lmrec, d_rec);
-    }
-    if (d_scale) // nullptr: the partials stay in the scratch for launch_errors_tail
-        CUGO_LAUNCH(k_sum_partials, dim3(1), dim3(SP_BS), 0, s, rs.d_partials, nbl + nbp, d_scale);
-    return nbl + nbp;
-}
-
 int launch_backsubst_update(hipStream_t s, const cugo_edges& e, double lambda, double lambda_pose,
                             const double* d_invHll, const double* d_bl, const double* d_bp,
                             const void* d_Hpl, const double* d_xp, double* d_xl,
@@ -3163,11 +3061,27 @@ int launch_backsubst_update(hipStream_t s, const cugo_edges& e, double lambda, d
                             double* d_lms_out, ReduceScratch rs, double* d_scale, const double* d_lmrec,
                             bool from_records)
 {
-    if (e.block_f32)
-        return launch_backsubst_update_t(s, e, lambda, lambda_pose, d_invHll, d_bl, d_bp, static_cast<const float*>(d_Hpl),
-                                  d_xp, d_xl, d_poses_in, d_lms_in, d_poses_out, d_lms_out, rs, d_scale, d_lmrec, from_records);
-    return launch_backsubst_update_t(s, e, lambda, lambda_pose, d_invHll, d_bl, d_bp, static_cast<const double*>(d_Hpl),
-                                  d_xp, d_xl, d_poses_in, d_lms_in, d_poses_out, d_lms_out, rs, d_scale, d_lmrec, from_records);
+    const EV ev = make_ev(e);
+    const int nbl = div_up(ev.E > ev.L ? ev.E : ev.L, BS), nbp = div_up(ev.P, BS);
+    if (nbl + nbp > 0)
+        with_storage(e, [&](auto S0) {
+            using S = decltype(S0);
+            // from_records: G^T dx_p from the build pass's records in the scratch instead of the G stream
+            const double* d_rec = rs.d_partials + scratch_partials(ev.E, ev.P, ev.L);
+            auto landmarks = [&](auto rec, auto... ds) {
+                launch_as("k_backsubst_landmarks", k_backsubst_landmarks<S, decltype(rec)::value, decltype(ds)...>,
+                          dim3(nbl + nbp), dim3(BS), 0, s, ev, lambda, d_invHll, d_bl, static_cast<const S*>(d_Hpl), d_xp,
+                          d_xl, d_lms_in, d_lms_out, rs.d_partials, nbl, lambda_pose, d_bp, d_poses_in, d_poses_out,
+                          d_lmrec, d_rec, ds...);
+            };
+            if (from_records && d_lmrec)
+                with_form(e, [&](auto... par) { landmarks(std::true_type(), record_par(par)...); });
+            else
+                landmarks(std::false_type());
+        });
+    if (d_scale) // nullptr: the partials stay in the scratch for launch_errors_tail
+        CUGO_LAUNCH(k_sum_partials, dim3(1), dim3(SP_BS), 0, s, rs.d_partials, nbl + nbp, d_scale);
+    return nbl + nbp;
 }
 
 } // namespace cugo_k

@@ -51,16 +51,24 @@ struct ReduceScratch
 };
 
 // --- edge / landmark / pose passes (ba_kernels.hip) ---------------------------------------
-// Depth slots (CUGO_EDGE_DEPTH): every launcher below that forms residuals or Jacobians
-// (launch_errors*, launch_edge_chi, launch_build, launch_schur's pose pass, launch_backsubst_update from records) picks
-// the depth-aware instantiation of its kernel iff ev.has_depth != 0 and takes the depth kind's robust kernel and
-// sqrt(ev.depth_weight) from ev; with ev.has_depth == 0 the kernels, and their arguments, are the ones there have
-// always been.  The caller has checked the members (c_api.cpp: check_depth; the engine's come from initialize()).
-// Camera extrinsics the same way: the same launchers pick the rig-aware instantiation iff
-// ev.has_rig != 0 and hand it ev.d_cam_ext ([n_cams][12], parallel to ev.d_cams); never together with ev.has_depth
-// (c_api.cpp: check_depth; the engine's initialize() refuses such a graph).
-// Camera models: iff ev.has_rig == CUGO_RIG_MODELS the same launchers pick the instantiation
-// with CamModelPar instead, and ev.d_cam_ext is then the model table [n_cams][17].
+// The form of an edge view: which instantiation of its kernel every launcher below that forms residuals or Jacobians
+// (launch_errors*, launch_edge_chi, launch_build, launch_schur's pose pass, launch_backsubst_update from records) picks,
+// and what it takes from ev for it (ba_kernels.hip: with_form, the one place).  In this order of precedence:
+//   Models  ev.has_rig == CUGO_RIG_MODELS: ev.d_cam_ext is the model table [n_cams][17]
+//   Rig     any other ev.has_rig != 0: ev.d_cam_ext holds the extrinsics [n_cams][12], parallel to ev.d_cams (section 18)
+//   Depth   ev.has_depth != 0: slots may carry CUGO_EDGE_DEPTH; the depth kind's robust kernel and sqrt(ev.depth_weight)
+//           come from ev (section 17)
+//   Plain   the kernels, and their arguments, are the ones there have always been
+// A table never goes together with ev.has_depth, and the caller has checked the members (c_api.cpp: check_edge_form;
+// the engine's come from initialize(), which refuses such a graph).
+enum class EdgeForm
+{
+    Plain,
+    Depth,
+    Rig,
+    Models
+};
+EdgeForm edge_form(const cugo_edges& ev);
 void launch_errors(hipStream_t s, const cugo_edges& ev, const double* d_poses, const double* d_lms,
                    cugo_robust rk, ReduceScratch rs, double* d_chi);
 
