@@ -75,6 +75,25 @@ OBS_MONO, OBS_STEREO, OBS_DEPTH = 2, 3, 4        # kind of a predicted observati
 CAM_TAB_STRIDE = 17
 
 
+RIG_DISTORTION = 3                               # cugo_edges.has_rig (CUGO_RIG_DISTORTION)
+DIST_TAB_STRIDE = 18
+
+
+def distortion_table(ext12, dist5, flags=None):
+    """the table d_cam_ext points to under has_rig = RIG_DISTORTION: [n][18] = {M row-major (9), t_s (3), k1, k2, p1, p2,
+    k3, flag}, from ext12 [n][12] (None: identities) and dist5 [n][5] = (k1, k2, p1, p2, k3) in OpenCV's order.  flags [n]:
+    0 undistorted / 1 distorted (None: distorted iff the entry's coefficients are not all zero)"""
+    d = np.asarray(dist5, np.float64).reshape(-1, 5)
+    n = len(d)
+    tab = np.zeros((n, DIST_TAB_STRIDE))
+    tab[:, :12] = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0.0]) if ext12 is None else np.asarray(ext12, np.float64).reshape(n, 12)
+    tab[:, 12:17] = d
+    tab[:, 17] = np.any(d != 0.0, axis=1) if flags is None else np.asarray(flags, np.float64).reshape(n)
+    if not np.all((tab[:, 17] == 0.0) | (tab[:, 17] == 1.0)):
+        raise CugoError("distortion_table: flag must be 0 (undistorted) or 1 (distorted)")
+    return tab
+
+
 def camera_model_table(ext12=None, model_k5=None, n=None):
     """the table d_cam_ext points to under has_rig = RIG_MODELS: [n][17] = {M row-major (9), t_s (3), k1, k2, k3, k4,
     model}, from ext12 [n][12] (None: identities) and model_k5 [n][5] = (k1, k2, k3, k4, model) (None: pinholes)"""
@@ -529,8 +548,11 @@ class Graph:
         check(lib().cugo_graph_add_landmarks(self._g, len(ids), _p(ids, _i32p), _p(x, _f64p), _p(f, _u8p)))
         self.lm_ids = np.concatenate([self.lm_ids, ids])
 
-    def add_edges(self, dim, pose_ids, lm_ids, meas, info, cam5=None, sensor=None, model=None):
-        """model: a projection model per edge, [n][5] = (k1, k2, k3, k4, type) with type 0 pinhole / 1 Kannala-Brandt; like
+    def add_edges(self, dim, pose_ids, lm_ids, meas, info, cam5=None, sensor=None, model=None, distortion=None):
+        """distortion: a radial-tangential lens distortion per edge, [n][5] = (k1, k2, p1, p2, k3) in OpenCV's order (the
+        measurements are then raw pixels); like cam5 and sensor it follows the camera (per_edge_camera) and does not go
+        together with model.  None: the set's (set_camera_distortion).
+        model: a projection model per edge, [n][5] = (k1, k2, k3, k4, type) with type 0 pinhole / 1 Kannala-Brandt; like
         cam5 and sensor it follows the camera (per_edge_camera).  None: the set's (set_camera_model).
         sensor: a sensor pose (q, t) body -> sensor per edge, [n][7] (a rig: the poses are then world -> body); it
         follows the camera, so it counts on a graph with per_edge_camera, like cam5.  None: the set's (set_sensor_pose)"""
@@ -541,6 +563,19 @@ class Graph:
         m = np.ascontiguousarray(np.asarray(meas, np.float64)[:, :dim])
         w = np.ascontiguousarray(info, np.float64)
         cam = None if cam5 is None else np.ascontiguousarray(cam5, np.float64)
+        if distortion is not None:
+            if model is not None:
+                raise CugoError("add_edges: distortion and model do not go together")
+            d5 = np.ascontiguousarray(distortion, np.float64)
+            if d5.shape != (n, 5):
+                raise CugoError("add_edges: distortion must be [n][5] (k1, k2, p1, p2, k3)")
+            sx = None if sensor is None else np.ascontiguousarray(sensor, np.float64)
+            if sx is not None and sx.shape != (n, 7):
+                raise CugoError("add_edges: sensor must be [n][7] (qx, qy, qz, qw, tx, ty, tz)")
+            check(lib().cugo_graph_add_edges_distorted(self._g, dim, n, _p(pi, _i32p), _p(li, _i32p), _p(m, _f64p),
+                                                       _p(w, _f64p), None if cam is None else _p(cam, _f64p),
+                                                       None if sx is None else _p(sx, _f64p), _p(d5, _f64p)))
+            return
         if model is not None:
             mk = np.ascontiguousarray(model, np.float64)
             if mk.shape != (n, 5):
@@ -576,6 +611,33 @@ class Graph:
         if k.shape != (4,):
             raise CugoError("set_camera_model: k4 must hold 4 numbers")
         check(lib().cugo_graph_set_camera_model(self._g, dim, int(model), _p(k, _f64p)))
+
+    def set_camera_distortion(self, dim, d5=None):
+        """the radial-tangential lens distortion of the mono (dim 2) or stereo (dim 3) set: d5 = (k1, k2, p1, p2, k3) in
+        OpenCV's order (None: zeros, no distortion).  The set's measurements are then raw pixels"""
+        d = np.zeros(5) if d5 is None else np.ascontiguousarray(d5, np.float64)
+        if d.shape != (5,):
+            raise CugoError("set_camera_distortion: d5 must hold 5 numbers")
+        check(lib().cugo_graph_set_camera_distortion(self._g, dim, _p(d, _f64p)))
+
+    def n_distorted_cameras(self):
+        """camera-table entries of the current flattening whose lens distortion is not all zero"""
+        n = lib().cugo_graph_n_distorted_cameras(self._g)
+        if n < 0:
+            check(n)
+        return n
+
+    def flat_camera_distortions(self):
+        """the lens distortions of the camera table of the current flattening, [n][5] = (k1, k2, p1, p2, k3), parallel to
+        flat_cameras()"""
+        n = lib().cugo_graph_get_flat_camera_distortions(self._g, 0, None)
+        if n < 0:
+            check(n)
+        d = np.zeros((n, 5))
+        rc = lib().cugo_graph_get_flat_camera_distortions(self._g, n, _p(d, _f64p))
+        if rc < 0:
+            check(rc)
+        return d
 
     def n_fisheye_cameras(self):
         """camera-table entries of the current flattening whose model is Kannala-Brandt"""
@@ -982,7 +1044,8 @@ class Graph:
         OBS_DEPTH (u, v, 1/Z_s; S in measurement units, the set's inverse-depth weight not applied).  cam: [5] or [n, 5]
         (fx, fy, cx, cy, bf); sensor: [7] or [n, 7] (q, t) body -> sensor, None: the identity; model: [5] or [n, 5]
         (k1, k2, k3, k4, type), type 0 pinhole / 1 Kannala-Brandt, None: a pinhole.  cam=None: the camera, sensor pose
-        and model of the graph's mono / stereo / depth set for that kind (sensor and model must then be None)."""
+        and model of the graph's mono / stereo / depth set for that kind (sensor and model must then be None; refused
+        when that set has a lens distortion, which these predictions do not model yet)."""
         a = np.ascontiguousarray(pose_ids, np.int32).reshape(-1)
         b = np.ascontiguousarray(lm_ids, np.int32).reshape(-1)
         if len(a) != len(b):

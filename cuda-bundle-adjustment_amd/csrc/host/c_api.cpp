@@ -64,7 +64,7 @@ cugo_k::ReduceScratch scratch_for(cugo_ctx* ctx, const cugo_edges* ev)
 namespace cugo_host
 {
 // The members of an edge view that go with its form (cugo_k::edge_form) are checked before anything is launched: with a
-// table (Rig, Models) d_cam_ext must be there, and the kernels that read one hold no depth code yet; with depth slots the
+// table (Rig, Models, Distortion) d_cam_ext must be there, and the kernels that read one hold no depth code yet; with depth slots the
 // kernels take sqrt(depth_weight) and the depth kind's robust kernel.  Nothing of either is read otherwise.
 // (not in the unnamed namespace: tests/test_edge_form_host.py links against it)
 void check_edge_form(const cugo_edges* ev, const char* who)
@@ -72,7 +72,7 @@ void check_edge_form(const cugo_edges* ev, const char* who)
     if (!ev)
         return;
     const cugo_k::EdgeForm form = cugo_k::edge_form(*ev);
-    if (form == cugo_k::EdgeForm::Rig || form == cugo_k::EdgeForm::Models)
+    if (form == cugo_k::EdgeForm::Rig || form == cugo_k::EdgeForm::Models || form == cugo_k::EdgeForm::Distortion)
     {
         if (!ev->d_cam_ext)
             throw std::runtime_error(std::string(who) + ": has_rig needs the extrinsics table d_cam_ext");
@@ -1284,10 +1284,11 @@ static cugo::CameraModel camera_model_of(const char* who, const double* k4, doub
     return m;
 }
 // mono / stereo edges; ext7 [n][7]: a sensor pose (q, t) per edge, or NULL (the set's applies); model5 [n][5]: a
-// projection model (k1..k4, type) per edge, or NULL (likewise)
+// projection model (k1..k4, type) per edge, or NULL (likewise); dist5 [n][5]: a lens distortion (k1, k2, p1, p2, k3) per
+// edge, or NULL (likewise)
 static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const int32_t* pose_ids, const int32_t* lm_ids,
                         const double* meas, const double* info, const double* cam5, const double* ext7,
-                        const double* model5 = nullptr)
+                        const double* model5 = nullptr, const double* dist5 = nullptr)
 {
     return guarded([&] {
         if (dim != 2 && dim != 3)
@@ -1302,6 +1303,12 @@ static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const in
             cugo::CameraModel model;
             if (model5)
                 model = camera_model_of(who, model5 + 5 * (size_t)i, model5[5 * (size_t)i + 4]);
+            cugo::CameraDistortion dist;
+            if (dist5)
+            {
+                const double* d = dist5 + 5 * (size_t)i;
+                dist = cugo::CameraDistortion(d[0], d[1], d[2], d[3], d[4]);
+            }
             cugo::Camera cam;
             if (cam5)
                 cam = cugo::Camera(cam5[5 * (size_t)i], cam5[5 * (size_t)i + 1], cam5[5 * (size_t)i + 2],
@@ -1319,6 +1326,8 @@ static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const in
                     e.setSensorPose(ext);
                 if (model5)
                     e.setCameraModel(model);
+                if (dist5)
+                    e.setDistortion(dist);
                 g->mono.addEdge(&e);
             }
             else
@@ -1334,6 +1343,8 @@ static int add_ba_edges(cugo_graph* g, const char* who, int dim, int n, const in
                     e.setSensorPose(ext);
                 if (model5)
                     e.setCameraModel(model);
+                if (dist5)
+                    e.setDistortion(dist);
                 g->stereo.addEdge(&e);
             }
         }
@@ -1394,6 +1405,43 @@ int cugo_graph_get_flat_camera_models(cugo_graph* g, int cap, double* model_k5)
         n = (int)(m.size() / 5);
         if (model_k5)
             std::copy(m.begin(), m.begin() + 5 * (size_t)std::min(n, std::max(cap, 0)), model_k5);
+    });
+    return rc == CUGO_OK ? n : rc;
+}
+int cugo_graph_add_edges_distorted(cugo_graph* g, int dim, int n, const int32_t* pose_ids, const int32_t* lm_ids,
+                                   const double* meas, const double* info, const double* cam5, const double* sensor_q_t7,
+                                   const double* dist5)
+{
+    return add_ba_edges(g, "cugo_graph_add_edges_distorted", dim, n, pose_ids, lm_ids, meas, info, cam5, sensor_q_t7,
+                        nullptr, dist5);
+}
+int cugo_graph_set_camera_distortion(cugo_graph* g, int dim, const double* d5)
+{
+    return guarded([&] {
+        if (dim != 2 && dim != 3)
+            throw std::runtime_error("cugo_graph_set_camera_distortion: dim must be 2 or 3");
+        const cugo::CameraDistortion d = d5 ? cugo::CameraDistortion(d5[0], d5[1], d5[2], d5[3], d5[4]) : cugo::CameraDistortion();
+        if (dim == 3)
+            g->stereo.setDistortion(d);
+        else
+            g->mono.setDistortion(d);
+    });
+}
+int cugo_graph_n_distorted_cameras(cugo_graph* g)
+{
+    int n = -1;
+    const int rc = guarded([&] { n = g->opt->nDistortedCameras(); });
+    return rc == CUGO_OK ? n : rc;
+}
+int cugo_graph_get_flat_camera_distortions(cugo_graph* g, int cap, double* dist5)
+{
+    int n = -1;
+    const int rc = guarded([&] {
+        std::vector<double> d;
+        g->opt->flatCameraDistortions(d);
+        n = (int)(d.size() / 5);
+        if (dist5)
+            std::copy(d.begin(), d.begin() + 5 * (size_t)std::min(n, std::max(cap, 0)), dist5);
     });
     return rc == CUGO_OK ? n : rc;
 }
@@ -2111,6 +2159,10 @@ int cugo_graph_predict_observations(cugo_graph* g, int n, const int32_t* pose_id
             const cugo::BaseEdgeSet& es = kind == CUGO_OBS_DEPTH    ? static_cast<const cugo::BaseEdgeSet&>(g->depth)
                                           : kind == CUGO_OBS_STEREO ? static_cast<const cugo::BaseEdgeSet&>(g->stereo)
                                                                     : static_cast<const cugo::BaseEdgeSet&>(g->mono);
+            // (answering for the undistorted camera would be silently wrong; a distorted kind is a later step)
+            if (!es.distortionData().isZero())
+                throw std::invalid_argument(std::string(who) + ": the set's camera has lens distortion (radial-tangential), "
+                                                               "which predicted observations do not model yet");
             const cugo::Camera& c = es.cameraData();
             const double set5[5] = {c.fx, c.fy, c.cx, c.cy, c.bf};
             const cugo::Se3D T = es.sensorPoseData();

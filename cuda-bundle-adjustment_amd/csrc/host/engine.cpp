@@ -1147,7 +1147,7 @@ struct Engine::Impl::SlotUpload
         const SlotArrays& sl = m.slots;
         f(m.d_e_pose, sl.pose), f(m.d_e_lm, sl.lm), f(m.d_flags, sl.flags), f(m.d_lm_ptr, m.h_lm_ptr);
         f(m.d_meas, sl.meas), f(m.d_omega, sl.omega), f(m.d_cams, g.cams);
-        if (g.has_models) // the model table takes the extrinsics' place
+        if (g.has_models || g.has_dist) // the model or distortion table takes the extrinsics' place
             f(m.d_cam_ext, m.h_cam_tab);
         else if (g.has_rig) // the extrinsics go up with the cameras (a table parallel to them)
             f(m.d_cam_ext, g.cam_ext);
@@ -1203,6 +1203,12 @@ static void refuse_unsupported(const FlatGraph& g, int n_relpose, bool sharded)
         {g.has_models && g.has_depth, "camera models (Kannala-Brandt) together with depth edge sets are not supported yet"},
         {g.has_models && sharded,
          "camera models (Kannala-Brandt) are not supported on a landmark-sharded (multi-GPU) optimiser yet"},
+        {g.has_dist && g.cam_dist.size() != 5 * n_cams, "lens distortion: the table must hold 5 numbers per camera"},
+        {g.has_dist && g.has_depth, "lens distortion (radial-tangential) together with depth edge sets is not supported yet"},
+        {g.has_dist && g.has_models,
+         "lens distortion (radial-tangential) and Kannala-Brandt cameras in one graph are not supported yet"},
+        {g.has_dist && sharded,
+         "lens distortion (radial-tangential) is not supported on a landmark-sharded (multi-GPU) optimiser yet"},
     };
     for (const auto& r : refusals)
         if (r.hit)
@@ -1210,14 +1216,30 @@ static void refuse_unsupported(const FlatGraph& g, int n_relpose, bool sharded)
 }
 
 // The model table of a graph with camera models, which takes the extrinsics' place on the device: {M, t_s, k1..k4, type}
-// per entry; a graph whose sensor poses are all identities has no cam_ext.  Empty without models.
+// per entry; a graph whose sensor poses are all identities has no cam_ext.  Likewise the distortion table of a graph with
+// lens distortion: {M, t_s, k1, k2, p1, p2, k3, flag} per entry, the flag 1.0 iff the entry's coefficients are not all
+// zero.  Empty without either.
 static void assemble_cam_table(const FlatGraph& g, std::vector<double>& tab)
 {
     static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
     tab.clear();
+    const size_t n = g.cams.size() / 5;
+    if (g.has_dist)
+    {
+        tab.resize(CUGO_DIST_TAB_STRIDE * n);
+        for (size_t k = 0; k < n; k++)
+        {
+            double* e = &tab[CUGO_DIST_TAB_STRIDE * k];
+            const double* x = g.has_rig ? &g.cam_ext[12 * k] : I12;
+            const double* d = &g.cam_dist[5 * k];
+            std::copy(x, x + 12, e);
+            std::copy(d, d + 5, e + 12);
+            e[17] = std::any_of(d, d + 5, [](double c) { return c != 0.0; }) ? 1.0 : 0.0;
+        }
+        return;
+    }
     if (!g.has_models)
         return;
-    const size_t n = g.cams.size() / 5;
     tab.resize(CUGO_CAM_TAB_STRIDE * n);
     for (size_t k = 0; k < n; k++)
     {
@@ -1246,7 +1268,7 @@ void Engine::initialize(FlatGraph& g)
     E_global_ = m.Etot + g.n_pose_edges() + n_relpose + g.lm_priors.n();
     refuse_unsupported(g, n_relpose, m.world > 1 || m.comm);
     // (every launcher of an edge pass picks its instantiation from this: cugo_k::edge_form)
-    m.ev.has_rig = g.has_models ? CUGO_RIG_MODELS : g.has_rig ? CUGO_RIG_EXTRINSICS : CUGO_RIG_NONE;
+    m.ev.has_rig = g.has_dist ? CUGO_RIG_DISTORTION : g.has_models ? CUGO_RIG_MODELS : g.has_rig ? CUGO_RIG_EXTRINSICS : CUGO_RIG_NONE;
     assemble_cam_table(g, m.h_cam_tab);
     // (k_hsc_offdiag_strip reads the list entry before a block's range: a pair block without products has none)
     if (n_relpose && m.opt.hsc_strip)

@@ -117,6 +117,12 @@ struct FlatGraph
     // kernels ONE table of stride 17 assembled from cam_ext (identities where that is empty) and this
     std::vector<double> cam_model;
     bool has_models = false;
+    // radial-tangential distortion (cugo_edges.has_rig == CUGO_RIG_DISTORTION): per camera-table entry (k1, k2, p1, p2,
+    // k3), n_cams x 5 (or empty: all zero); has_dist iff some entry's coefficients are not all zero.  The engine then
+    // hands the kernels ONE table of stride 18 assembled from cam_ext (identities where that is empty), this and a flag
+    // per entry.  Never together with has_models
+    std::vector<double> cam_dist;
+    bool has_dist = false;
     cugo_robust rk{CUGO_RK_NONE, 1.0, CUGO_RK_NONE, 1.0};
     // depth edge sets (flag bit CUGO_EDGE_DEPTH; cugo_edges.has_depth and the members behind it): whether the graph has
     // any, their robust kernel and their inverse-depth weight

@@ -120,6 +120,23 @@ int CudaGraphOptimisationImpl::nFisheyeCameras() const
             n += g.cam_model[5 * k + 4] != 0.0 ? 1 : 0;
     return n;
 }
+bool CudaGraphOptimisationImpl::flatCameraDistortions(std::vector<double>& dist5) const
+{
+    const FlatGraph& g = engine_->staging();
+    dist5 = g.cam_dist;
+    if (!g.has_dist)
+        dist5.assign(5 * (g.cams.size() / 5), 0.0);
+    return g.has_dist;
+}
+int CudaGraphOptimisationImpl::nDistortedCameras() const
+{
+    const FlatGraph& g = engine_->staging();
+    int n = 0;
+    if (g.has_dist)
+        for (size_t k = 0; k < g.cam_dist.size() / 5; k++)
+            n += std::any_of(&g.cam_dist[5 * k], &g.cam_dist[5 * k] + 5, [](double c) { return c != 0.0; }) ? 1 : 0;
+    return n;
+}
 int CudaGraphOptimisationImpl::nRigCameras() const
 {
     std::vector<double> cams, x;
@@ -528,6 +545,7 @@ void CudaGraphOptimisationImpl::initialize()
     g.cams.clear();
     g.cam_ext.clear(), g.has_rig = false;
     g.cam_model.clear(), g.has_models = false;
+    g.cam_dist.clear(), g.has_dist = false;
     // ---- vertex indices: free first (ascending id), fixed after -------------------------
     int nPfree = 0, nLfree = 0, nP = 0, nL = 0;
     for (BaseVertexSet* vs : vertexSets)
@@ -593,12 +611,13 @@ void CudaGraphOptimisationImpl::initialize()
         bool uniform = true;
         bool too_many_cams = false;
         bool fisheye_3d = false;      // a Kannala-Brandt model met on a 3-d (stereo or depth) edge
+        bool distorted_3d = false;    // a non-zero lens distortion met on a 3-d (stereo or depth) edge
     };
-    // A camera-table entry is keyed on CK = 5 + 7 + 5 numbers: the intrinsics, the sensor pose (q, t) as the caller gave
-    // it, and the projection model (k1..k4, type; a pinhole's coefficients are not looked at and count as zeros).  Two
-    // entries that differ in any of them are different entries; the key table is split into g.cams, g.cam_ext and
-    // g.cam_model behind the walk.
-    constexpr size_t CK = 17;
+    // A camera-table entry is keyed on CK = 5 + 7 + 5 + 5 numbers: the intrinsics, the sensor pose (q, t) as the caller
+    // gave it, the projection model (k1..k4, type; a pinhole's coefficients are not looked at and count as zeros) and the
+    // lens distortion (k1, k2, p1, p2, k3; a zero of either sign counts as zero).  Two entries that differ in any of them
+    // are different entries; the key table is split into g.cams, g.cam_ext, g.cam_model and g.cam_dist behind the walk.
+    constexpr size_t CK = 22;
     std::vector<double> camKeys;
     const unsigned hw = cugo_host::pool_threads();
     lap("graph: edge array alloc");
@@ -681,6 +700,7 @@ void CudaGraphOptimisationImpl::initialize()
         const Camera set_cam = es->cameraData();
         const Se3D set_ext = es->sensorPoseData();
         const CameraModel set_model = es->cameraModelData();
+        const CameraDistortion set_dist = es->distortionData();
         const EdgeContainer& ec = es->get();
         const size_t n = ec.size();
         const unsigned nthreads = n < 20000 ? 1u : hw;
@@ -733,10 +753,14 @@ void CudaGraphOptimisationImpl::initialize()
                 const bool kb = md.type != Pinhole;
                 if (kb && dim == 3)
                     c.fisheye_3d = true;
+                const CameraDistortion& dd = perCam ? e->distortionData() : set_dist;
+                if (dim == 3 && !dd.isZero())
+                    c.distorted_3d = true;
                 const double cv[CK] = {cm.fx,        cm.fy,        cm.cx,        cm.cy,        cm.bf,        sx.r.data[0],
                                        sx.r.data[1], sx.r.data[2], sx.r.data[3], sx.t.data[0], sx.t.data[1], sx.t.data[2],
                                        kb ? md.k[0] : 0.0, kb ? md.k[1] : 0.0, kb ? md.k[2] : 0.0, kb ? md.k[3] : 0.0,
-                                       (double)(int)md.type};
+                                       (double)(int)md.type,
+                                       dd.k1 + 0.0,  dd.k2 + 0.0,  dd.p1 + 0.0,  dd.p2 + 0.0,  dd.k3 + 0.0}; // (-0 + 0 = +0)
                 // deduplicate cameras: last-hit fast path, then a short linear scan
                 int ci = -1;
                 const size_t ncam = c.cams.size() / CK;
@@ -785,6 +809,12 @@ void CudaGraphOptimisationImpl::initialize()
                              std::to_string(si) + ")"
                        : "cugo: a Kannala-Brandt camera model on a stereo edge set is not defined: bf has no meaning there "
                          "(edge set " + std::to_string(si) + ")");
+            if (c.distorted_3d)
+                throw std::runtime_error(
+                    ds ? "cugo: lens distortion (radial-tangential) together with depth edge sets is not supported yet (edge set " +
+                             std::to_string(si) + ")"
+                       : "cugo: lens distortion (radial-tangential) on a stereo edge set is not supported: bf describes a "
+                         "rectified pair (edge set " + std::to_string(si) + ")");
             // merge this chunk's cameras into the global table (first-seen order is kept)
             std::vector<uint16_t> remap(c.cams.size() / CK);
             bool identity = true;
@@ -872,7 +902,30 @@ void CudaGraphOptimisationImpl::initialize()
                                          ": the coefficients k1..k4 must be finite");
         g.has_models = g.has_models || type != (int)Pinhole;
         g.cam_model.insert(g.cam_model.end(), key + 12, key + 17);
+        // the distortion: (k1, k2, p1, p2, k3); has_dist iff some entry's coefficients are not all zero
+        bool distorted = false;
+        for (int c = 17; c < 22; c++)
+        {
+            if (!std::isfinite(key[c]))
+                throw std::runtime_error("cugo: lens distortion (radial-tangential) of camera-table entry " +
+                                         std::to_string(k) + ": the coefficients k1, k2, p1, p2, k3 must be finite");
+            distorted = distorted || key[c] != 0.0;
+        }
+        if (distorted && type != (int)Pinhole)
+            throw std::runtime_error("cugo: lens distortion (radial-tangential) on a Kannala-Brandt camera (camera-table "
+                                     "entry " + std::to_string(k) + ") is not defined: the fisheye model has its own "
+                                     "coefficients");
+        g.has_dist = g.has_dist || distorted;
+        g.cam_dist.insert(g.cam_dist.end(), key + 17, key + 22);
     }
+    if (g.has_dist && g.has_depth)
+        throw std::runtime_error("cugo: lens distortion (radial-tangential) together with depth edge sets is not supported "
+                                 "yet");
+    if (g.has_dist && g.has_models)
+        throw std::runtime_error("cugo: lens distortion (radial-tangential) and Kannala-Brandt cameras in one graph are "
+                                 "not supported yet");
+    if (!g.has_dist)
+        g.cam_dist.clear(); // (no distortion: the graph runs the kernels it has always run)
     if (g.has_models && g.has_depth)
         throw std::runtime_error("cugo: camera models (Kannala-Brandt) together with depth edge sets are not supported "
                                  "yet");

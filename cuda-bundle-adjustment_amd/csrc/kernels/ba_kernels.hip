@@ -161,15 +161,27 @@ struct CamModelPar
 {
     const double* cam_tab;
 };
+// A DISTORTION table (cugo_edges.has_rig == CUGO_RIG_DISTORTION) likewise: cam_tab [n_cams][18] =
+// {the entry's 12 numbers, k1, k2, p1, p2, k3, flag}.  An entry whose flag is 0 runs RigPar's operations in RigPar's
+// order.  A distorted and a Kannala-Brandt entry never share a table: two forms, two instantiations.
+struct DistortPar
+{
+    const double* cam_tab;
+};
 template <typename... P>
 constexpr bool pack_has_model = (false || ... || std::is_same_v<P, CamModelPar>);
-// (the rig code below serves both packs: what differs is the stride and what edge_residual_rig / rig_B do with the entry)
 template <typename... P>
-constexpr bool pack_has_rig = (false || ... || (std::is_same_v<P, RigPar> || std::is_same_v<P, CamModelPar>));
+constexpr bool pack_has_dist = (false || ... || std::is_same_v<P, DistortPar>);
+// (the rig code below serves all three packs: what differs is the stride and what edge_residual_rig / rig_B do with the
+// entry)
+template <typename... P>
+constexpr bool pack_has_rig = (false || ... || (std::is_same_v<P, RigPar> || std::is_same_v<P, CamModelPar> ||
+                                                std::is_same_v<P, DistortPar>));
 // (the kernels that read records take the depth kind as its one number, sqrt(weight): record_par below)
 template <typename... P>
 constexpr bool pack_has_depth = (false || ... || (std::is_same_v<P, DepthPar> || std::is_same_v<P, double>));
-// the camera-kind element of a pack (DepthPar or its double, RigPar, CamModelPar), whatever stands in front of it
+// the camera-kind element of a pack (DepthPar or its double, RigPar, CamModelPar, DistortPar), whatever stands in front
+// of it
 template <typename T, typename... R>
 __device__ __forceinline__ decltype(auto) kind_of(const T& t, const R&... r)
 {
@@ -194,6 +206,14 @@ __device__ __forceinline__ const double* ext_of_slot(const EV& ev, const CamMode
 __device__ __forceinline__ const double* ext_of_record(const CamModelPar& mp, long long meta)
 {
     return mp.cam_tab + 17 * (int)(meta & 0xFFFF);
+}
+__device__ __forceinline__ const double* ext_of_slot(const EV& ev, const DistortPar& dp, int e)
+{
+    return ev.n_cams > 1 ? dp.cam_tab + 18 * (int)ev.cam[e] : dp.cam_tab;
+}
+__device__ __forceinline__ const double* ext_of_record(const DistortPar& dp, long long meta)
+{
+    return dp.cam_tab + 18 * (int)(meta & 0xFFFF);
 }
 
 struct EdgeIn
@@ -371,7 +391,7 @@ __global__ __launch_bounds__(BS) void k_errors(EV ev, const double* __restrict__
             // Routing it through the template with a helper that picks the robust kernel gave the same arithmetic but
             // other register figures for the instantiations that existed before — tools/kernel_resources.sh)
             if constexpr (RIG)
-                edge_residual_rig<pack_has_model<DP...>>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
+                edge_residual_rig<pack_has_model<DP...>, pack_has_dist<DP...>>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
                                   in.omega, in.cam, ext_of_slot(ev, kind_of(dp...), e), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
@@ -408,7 +428,7 @@ __global__ __launch_bounds__(BS) void k_edge_chi(EV ev, const double* __restrict
         const bool depth = is_depth<DEP>(fl);
         EdgeGeom g;
         if constexpr (RIG)
-            edge_residual_rig<pack_has_model<DP...>>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
+            edge_residual_rig<pack_has_model<DP...>, pack_has_dist<DP...>>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo,
                               in.omega, in.cam, ext_of_slot(ev, kind_of(dp...), e), in.stereo ? rk.s : rk.m, g);
         else if constexpr (DEP)
             edge_residual_k<true>(poses + 7 * (size_t)in.ip, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth,
@@ -529,7 +549,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
             if constexpr (RIG)
-                edge_residual_rig<pack_has_model<LP...>>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
+                edge_residual_rig<pack_has_model<LP...>, pack_has_dist<LP...>>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
                                   ext_of_slot(ev, kind_of(lp...), e), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
@@ -554,7 +574,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             {
                 double R[3][3];
                 quat_to_rot(pose, R);
-                rig_B<pack_has_model<LP...>>(g.Xc, in.cam, ext_of_slot(ev, kind_of(lp...), e), in.stereo, true, B);
+                rig_B<pack_has_model<LP...>, pack_has_dist<LP...>>(g.Xc, in.cam, ext_of_slot(ev, kind_of(lp...), e), in.stereo, true, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -628,7 +648,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             const double* pose = poses + 7 * (size_t)in.ip;
             EdgeGeom g;
             if constexpr (RIG)
-                edge_residual_rig<pack_has_model<LP...>>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
+                edge_residual_rig<pack_has_model<LP...>, pack_has_dist<LP...>>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, in.omega, in.cam,
                                   ext_of_slot(ev, kind_of(lp...), ee), in.stereo ? rk.s : rk.m, g);
             else if constexpr (DEP)
                 edge_residual_k<true>(pose, lms + 3 * (size_t)in.il, in.mu, in.mv, in.mr, in.stereo, depth, sd, in.omega,
@@ -641,7 +661,7 @@ __global__ __launch_bounds__(BS) void k_build_edges(EV ev, const double* __restr
             {
                 double R[3][3], B[3][3];
                 quat_to_rot(pose, R);
-                rig_B<pack_has_model<LP...>>(g.Xc, in.cam, ext_of_slot(ev, kind_of(lp...), ee), in.stereo, true, B);
+                rig_B<pack_has_model<LP...>, pack_has_dist<LP...>>(g.Xc, in.cam, ext_of_slot(ev, kind_of(lp...), ee), in.stereo, true, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -884,7 +904,7 @@ __global__ __launch_bounds__(BS) void k_build_poses(EV ev, const double* __restr
             if constexpr (pack_has_rig<DS...>)
             {
                 double B[3][3];
-                rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, w != 0.0, B);
+                rig_B<pack_has_model<DS...>, pack_has_dist<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, w != 0.0, B);
                 jac_pose_rig(Xc, B, JP);
             }
             else
@@ -1053,7 +1073,7 @@ __global__ __launch_bounds__(PS_BS, PS_WAVES<DS...>) void k_pose_schur(EV ev, co
             if constexpr (RIG)
             {
                 double B[3][3];
-                rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, wgt != 0.0, B);
+                rig_B<pack_has_model<DS...>, pack_has_dist<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, wgt != 0.0, B);
                 jac_landmark_rig(B, R, JL);
             }
             else
@@ -1090,7 +1110,7 @@ __global__ __launch_bounds__(PS_BS, PS_WAVES<DS...>) void k_pose_schur(EV ev, co
         if constexpr (RIG)
         { // (B formed again: the same function on the same inputs, and nothing of it lives across the barrier above)
             double B[3][3];
-            rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, wgt != 0.0, B);
+            rig_B<pack_has_model<DS...>, pack_has_dist<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), meta), stereo, wgt != 0.0, B);
             jac_pose_rig(Xc, B, JP);
         }
         else
@@ -2555,7 +2575,7 @@ __device__ __forceinline__ void gT_x_from_record(const double* r8, const double*
     {
         double R[3][3], B[3][3];
         quat_to_rot(pose, R);
-        rig_B<pack_has_model<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), bits), stereo, w != 0.0, B);
+        rig_B<pack_has_model<DS...>, pack_has_dist<DS...>>(Xc, cam, ext_of_record(kind_of(ds...), bits), stereo, w != 0.0, B);
         jac_landmark_rig(B, R, JL);
         jac_pose_rig(Xc, B, JP);
     }
@@ -2777,19 +2797,22 @@ static void launch_as(const char* name, void (*kernel)(KA...), dim3 grid, dim3 b
 
 EdgeForm edge_form(const cugo_edges& e)
 {
+    if (e.has_rig == CUGO_RIG_DISTORTION)
+        return EdgeForm::Distortion;
     if (e.has_rig)
         return e.has_rig == CUGO_RIG_MODELS ? EdgeForm::Models : EdgeForm::Rig;
     return e.has_depth ? EdgeForm::Depth : EdgeForm::Plain;
 }
 // THE place where the instantiation of an edge view is picked (edge_form, kernels.h): f is called with the parameter
 // object of the view's form — nothing, the DepthPar (robust kernel of the depth kind and s = sqrt(weight), formed once
-// here), the RigPar, or the CamModelPar (d_cam_ext is then the model table, stride 17) — and passes it on as the trailing
-// pack of its kernel: kernel<decltype(par)...>(..., par...)
+// here), the RigPar, the CamModelPar (d_cam_ext is then the model table, stride 17) or the DistortPar (the distortion
+// table, stride 18) — and passes it on as the trailing pack of its kernel: kernel<decltype(par)...>(..., par...)
 template <typename F>
 static void with_form(const cugo_edges& e, F&& f)
 {
     switch (edge_form(e))
     {
+    case EdgeForm::Distortion: return f(DistortPar{e.d_cam_ext});
     case EdgeForm::Models: return f(CamModelPar{e.d_cam_ext});
     case EdgeForm::Rig: return f(RigPar{e.d_cam_ext});
     case EdgeForm::Depth: return f(DepthPar{{e.rk_type_depth, e.rk_delta_depth}, std::sqrt(e.depth_weight)});
@@ -2801,6 +2824,7 @@ static void with_form(const cugo_edges& e, F&& f)
 static double record_par(const DepthPar& dp) { return dp.s; }
 static RigPar record_par(const RigPar& rp) { return rp; }
 static CamModelPar record_par(const CamModelPar& mp) { return mp; }
+static DistortPar record_par(const DistortPar& dp) { return dp; }
 // the block storage type S of an edge view (cugo_edges.block_f32): f is called with a float or a double
 template <typename F>
 static auto with_storage(const cugo_edges& e, F&& f)

@@ -338,10 +338,45 @@ __device__ __forceinline__ KbTerms kb_terms(const double* Xs, const double* __re
     return o;
 }
 
+// ---- radial-tangential distortion entries ---------------------------------------------------
+// A camera-table entry of a DISTORTION table (cugo_edges.has_rig == CUGO_RIG_DISTORTION) is 18 doubles: the 12 of the
+// extrinsic, then (k1, k2, p1, p2, k3) in OpenCV's order and the flag (0.0 undistorted, 1.0 distorted).  For a distorted
+// entry, at Xs = (x, y, z):
+//   iz = 1 / z,  a = x iz,  b = y iz,  r2 = a^2 + b^2
+//   rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),   dr = d rad / d r2 = k1 + r2 (2 k2 + 3 k3 r2)
+//   a' = a rad + 2 p1 a b + p2 (r2 + 2 a^2),   b' = b rad + p1 (r2 + 2 b^2) + 2 p2 a b
+//   pu = fx a' + cx,  pv = fy b' + cy
+//   Jaa = rad + 2 a^2 dr + 2 p1 b + 6 p2 a,   Jab = 2 a b dr + 2 p1 a + 2 p2 b,   Jbb = rad + 2 b^2 dr + 6 p1 b + 2 p2 a
+// Nothing here subtracts nearly equal numbers: one form, no near-axis branch.  z <= 0 is the caller's, as for the pinhole.
+struct DistTerms
+{
+    double a, b, ad, bd, Jaa, Jab, Jbb, iz; // (ad, bd) = (a', b')
+};
+__device__ __forceinline__ DistTerms dist_terms(const double* Xs, const double* __restrict__ d)
+{
+    const double k1 = d[0], k2 = d[1], p1 = d[2], p2 = d[3], k3 = d[4];
+    DistTerms o;
+    o.iz = 1.0 / Xs[2];
+    o.a = Xs[0] * o.iz;
+    o.b = Xs[1] * o.iz;
+    const double a2 = o.a * o.a, b2 = o.b * o.b, ab = o.a * o.b;
+    const double r2 = a2 + b2;
+    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+    const double dr = k1 + r2 * (2.0 * k2 + 3.0 * k3 * r2);
+    o.ad = o.a * rad + 2.0 * p1 * ab + p2 * (r2 + 2.0 * a2);
+    o.bd = o.b * rad + p1 * (r2 + 2.0 * b2) + 2.0 * p2 * ab;
+    o.Jaa = rad + 2.0 * a2 * dr + 2.0 * p1 * o.b + 6.0 * p2 * o.a;
+    o.Jab = 2.0 * ab * dr + 2.0 * p1 * o.a + 2.0 * p2 * o.b;
+    o.Jbb = rad + 2.0 * b2 * dr + 6.0 * p1 * o.b + 2.0 * p2 * o.a;
+    return o;
+}
+
 // residual, weight and chi of a mono or stereo slot seen through the extrinsic; g.Xc = Xb.
 // KB: ext is an entry of a model table (17 doubles); an entry whose flag is 0 takes the path below, operation for
 // operation.  A Kannala-Brandt entry has no third row: bf means nothing there and the stereo bit is not looked at.
-template <bool KB = false>
+// DIST: ext is an entry of a distortion table (18 doubles), likewise: flag 0 takes the path below, a distorted entry has
+// two rows.  Never together with KB: the two are different tables.
+template <bool KB = false, bool DIST = false>
 __device__ __forceinline__ void edge_residual_rig(const double* __restrict__ pose, const double* __restrict__ Xw,
                                                   double mu, double mv, double mr, bool stereo, double omega,
                                                   const double* __restrict__ cam, const double* __restrict__ ext,
@@ -356,6 +391,18 @@ __device__ __forceinline__ void edge_residual_rig(const double* __restrict__ pos
             const KbTerms kt = kb_terms(Xs, ext + 12);
             g.e[0] = (cam[0] * kt.rho * Xs[0] + cam[2]) - mu;
             g.e[1] = (cam[1] * kt.rho * Xs[1] + cam[3]) - mv;
+            g.e[2] = 0.0;
+            const double xk = omega * (g.e[0] * g.e[0] + g.e[1] * g.e[1]);
+            g.chi = rk_rho(rk, xk);
+            g.w = omega * rk_drho(rk, xk);
+            return;
+        }
+    if constexpr (DIST)
+        if (ext[17] != 0.0)
+        {
+            const DistTerms dt = dist_terms(Xs, ext + 12);
+            g.e[0] = (cam[0] * dt.ad + cam[2]) - mu;
+            g.e[1] = (cam[1] * dt.bd + cam[3]) - mv;
             g.e[2] = 0.0;
             const double xk = omega * (g.e[0] * g.e[0] + g.e[1] * g.e[1]);
             g.chi = rk_rho(rk, xk);
@@ -385,7 +432,9 @@ __device__ __forceinline__ void edge_residual_rig(const double* __restrict__ pos
 // Z_s = 0 behind a sensor pose, and 0 x inf would not do
 // KB: as for edge_residual_rig; for a Kannala-Brandt entry A = -d(pu, pv)/dXs, third row zero:
 //   A[0] = -fx (rho + x^2 c,  x y c,  -x D / R2),   A[1] = -fy (x y c,  rho + y^2 c,  -y D / R2)
-template <bool KB = false>
+// DIST: for a distorted entry A = -d(pu, pv)/dXs, third row zero:
+//   A[0] = -fx iz (Jaa,  Jab,  -(Jaa a + Jab b)),   A[1] = -fy iz (Jab,  Jbb,  -(Jab a + Jbb b))
+template <bool KB = false, bool DIST = false>
 __device__ __forceinline__ void rig_B(const double* Xb, const double* __restrict__ cam,
                                       const double* __restrict__ ext, bool stereo, bool live, double B[3][3])
 {
@@ -403,6 +452,29 @@ __device__ __forceinline__ void rig_B(const double* Xb, const double* __restrict
             A[1][0] = -(cam[1] * (Xs[0] * yc));
             A[1][1] = -(cam[1] * (kt.rho + Xs[1] * yc));
             A[1][2] = cam[1] * (Xs[1] * kt.dR);
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+            {
+                const double b0 = A[0][0] * ext[j] + A[0][1] * ext[3 + j] + A[0][2] * ext[6 + j];
+                const double b1 = A[1][0] * ext[j] + A[1][1] * ext[3 + j] + A[1][2] * ext[6 + j];
+                B[0][j] = live ? b0 : 0.0;
+                B[1][j] = live ? b1 : 0.0;
+                B[2][j] = 0.0;
+            }
+            return;
+        }
+    if constexpr (DIST)
+        if (ext[17] != 0.0)
+        {
+            const DistTerms dt = dist_terms(Xs, ext + 12);
+            const double fu = -(cam[0] * dt.iz), fv = -(cam[1] * dt.iz);
+            double A[2][3];
+            A[0][0] = fu * dt.Jaa;
+            A[0][1] = fu * dt.Jab;
+            A[0][2] = -(fu * (dt.Jaa * dt.a + dt.Jab * dt.b));
+            A[1][0] = fv * dt.Jab;
+            A[1][1] = fv * dt.Jbb;
+            A[1][2] = -(fv * (dt.Jab * dt.a + dt.Jbb * dt.b));
 #pragma unroll
             for (int j = 0; j < 3; j++)
             {

@@ -54,6 +54,7 @@ struct ReduceScratch
 // The form of an edge view: which instantiation of its kernel every launcher below that forms residuals or Jacobians
 // (launch_errors*, launch_edge_chi, launch_build, launch_schur's pose pass, launch_backsubst_update from records) picks,
 // and what it takes from ev for it (ba_kernels.hip: with_form, the one place).  In this order of precedence:
+//   Distortion  ev.has_rig == CUGO_RIG_DISTORTION: ev.d_cam_ext is the distortion table [n_cams][18] (section 20)
 //   Models  ev.has_rig == CUGO_RIG_MODELS: ev.d_cam_ext is the model table [n_cams][17]
 //   Rig     any other ev.has_rig != 0: ev.d_cam_ext holds the extrinsics [n_cams][12], parallel to ev.d_cams (section 18)
 //   Depth   ev.has_depth != 0: slots may carry CUGO_EDGE_DEPTH; the depth kind's robust kernel and sqrt(ev.depth_weight)
@@ -66,7 +67,8 @@ enum class EdgeForm
     Plain,
     Depth,
     Rig,
-    Models
+    Models,
+    Distortion
 };
 EdgeForm edge_form(const cugo_edges& ev);
 void launch_errors(hipStream_t s, const cugo_edges& ev, const double* d_poses, const double* d_lms,

@@ -167,6 +167,12 @@ public:
     bool flatCameraModels(std::vector<double>& model_k5) const;
     /** entries of that table whose model is KannalaBrandt */
     int nFisheyeCameras() const;
+    /** the radial-tangential distortions of that table (camera_distortion.h), parallel to flatCameras(): (k1, k2, p1, p2,
+     *  k3) per entry.  Returns whether any entry's coefficients are not all zero: only then do the edge kernels get the
+     *  distortion table (cugo_edges.has_rig == CUGO_RIG_DISTORTION), sensor poses included even if all are identities */
+    bool flatCameraDistortions(std::vector<double>& dist5) const;
+    /** entries of that table whose distortion is not all zero */
+    int nDistortedCameras() const;
     /** B, M, nnz(L), flops, supernodes, stages, front bytes, off-diagonal products, then per
      *  factorisation: potrf / trsm / syrk flops, extend-add bytes, backward bytes */
     std::vector<double> structureStats() const;

@@ -19,6 +19,7 @@
 #include <utility>
 #include <vector>
 
+#include "camera_distortion.h"
 #include "camera_model.h"
 #include "cugo_types.h"
 
@@ -498,6 +499,12 @@ public:
     virtual void setCameraModel(const CameraModel& model) noexcept = 0;
     virtual const CameraModel& cameraModelData() const noexcept = 0;
     virtual CameraModel& getCameraModel() noexcept = 0;
+    // Extension: the camera's radial-tangential distortion (camera_distortion.h; default all zero).  It follows the
+    // camera like the sensor pose and the model.  Non-zero coefficients are for mono pinhole edges; initialize() refuses
+    // them on stereo and depth edges and on a Kannala-Brandt camera.  The measurement is then a raw pixel
+    virtual void setDistortion(const CameraDistortion& distortion) noexcept = 0;
+    virtual const CameraDistortion& distortionData() const noexcept = 0;
+    virtual CameraDistortion& getDistortion() noexcept = 0;
 };
 
 // ref: Edge<DIM, E, VertexTypes...> src/optimisable_graph.h:416-503
@@ -581,6 +588,17 @@ public:
         return cameraModel_;
     }
     const CameraModel& cameraModelData() const noexcept override { return cameraModel_; }
+    void setDistortion(const CameraDistortion& distortion) noexcept override
+    {
+        touchOwner();
+        distortion_ = distortion;
+    }
+    CameraDistortion& getDistortion() noexcept override
+    {
+        touchOwner();
+        return distortion_;
+    }
+    const CameraDistortion& distortionData() const noexcept override { return distortion_; }
     void inactivate() noexcept override
     {
         touchOwner();
@@ -599,6 +617,7 @@ protected:
     Camera camera_;
     Se3D sensorPose_; // identity
     CameraModel cameraModel_; // Pinhole
+    CameraDistortion distortion_; // none
     BaseVertex* vertices[VertexSize];
     bool isActive_;
 };
@@ -645,6 +664,11 @@ public:
     virtual void setCameraModel(const CameraModel& model) noexcept = 0;
     virtual const CameraModel& cameraModelData() const noexcept = 0;
     virtual CameraModel& getCameraModel() noexcept = 0;
+    // Extension: the set's radial-tangential distortion (see BaseEdge::setDistortion); default all zero.  One MonoEdgeSet
+    // per distorted camera, each with its sensor pose and its coefficients, is a rig of calibrated cameras
+    virtual void setDistortion(const CameraDistortion& distortion) noexcept = 0;
+    virtual const CameraDistortion& distortionData() const noexcept = 0;
+    virtual CameraDistortion& getDistortion() noexcept = 0;
 };
 
 inline void BaseEdge::touchOwner() noexcept
@@ -743,6 +767,17 @@ public:
         return cameraModel_;
     }
     const CameraModel& cameraModelData() const noexcept override { return cameraModel_; }
+    void setDistortion(const CameraDistortion& distortion) noexcept override
+    {
+        touch();
+        distortion_ = distortion;
+    }
+    CameraDistortion& getDistortion() noexcept override
+    {
+        touch();
+        return distortion_;
+    }
+    const CameraDistortion& distortionData() const noexcept override { return distortion_; }
     void setOutlierThreshold(const Scalar t) noexcept
     {
         touch();
@@ -768,6 +803,7 @@ protected:
     Camera camera_;
     Se3D sensorPose_; // identity
     CameraModel cameraModel_; // Pinhole
+    CameraDistortion distortion_; // none
     bool isDirty_ = true;
 };
 

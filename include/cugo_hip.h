@@ -115,8 +115,9 @@ typedef struct cugo_edges
      * the entry; with n_cams == 1 entry 0 serves every slot.  has_rig == 0 (every zero-initialised struct): d_cam_ext
      * is not read and every entry point runs the kernels it has always run.  has_rig != 0 with d_cam_ext == NULL, or
      * together with has_depth != 0 (not yet), is CUGO_ERR_INVALID before anything is launched.
-     * Extension: camera models (Kannala-Brandt fisheye).  has_rig takes one of the CUGO_RIG_* values below; any other
-     * non-zero value means CUGO_RIG_EXTRINSICS, as it always did.  With has_rig == CUGO_RIG_MODELS d_cam_ext is a MODEL
+     * Extension: camera models (Kannala-Brandt fisheye).  has_rig takes one of the CUGO_RIG_* values below; every
+     * non-zero value other than CUGO_RIG_MODELS (2) and CUGO_RIG_DISTORTION (3) means CUGO_RIG_EXTRINSICS, as it always
+     * did (3 used to fall under that rule until the distortion tables below took the value).  With has_rig == CUGO_RIG_MODELS d_cam_ext is a MODEL
      * table of stride 17, d_cam_ext[17 k] = {M row-major (9), t_s (3), k1, k2, k3, k4, model}, model 0.0 (pinhole) or
      * 1.0 (Kannala-Brandt):
      *   theta = atan2(sqrt(x^2 + y^2), z),  theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
@@ -124,9 +125,21 @@ typedef struct cugo_edges
      * A pinhole entry of a model table gives the bits of the same entry under CUGO_RIG_EXTRINSICS.  A Kannala-Brandt
      * entry has two rows: bf has no meaning there, and a stereo slot on such an entry is NOT DEFINED at this level (the
      * graph level refuses it).  CUGO_RIG_MODELS with d_cam_ext == NULL or together with has_depth != 0 is
-     * CUGO_ERR_INVALID before anything is launched. */
+     * CUGO_ERR_INVALID before anything is launched.
+     * Extension: radial-tangential lens distortion (OpenCV's distCoeffs, Kalibr's radtan, ROS's plumb_bob).  With
+     * has_rig == CUGO_RIG_DISTORTION d_cam_ext is a DISTORTION table of stride 18, d_cam_ext[18 k] = {M row-major (9),
+     * t_s (3), k1, k2, p1, p2, k3, flag}, flag 0.0 (undistorted) or 1.0 (distorted); at Xs = (x, y, z):
+     *   a = x / z,  b = y / z,  r2 = a^2 + b^2,  rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3,
+     *   a' = a rad + 2 p1 a b + p2 (r2 + 2 a^2),  b' = b rad + p1 (r2 + 2 b^2) + 2 p2 a b,
+     *   pu = fx a' + cx,  pv = fy b' + cy;                       measurements are RAW (distorted) pixels.
+     * An undistorted entry of a distortion table gives the bits of the same entry under CUGO_RIG_EXTRINSICS, stereo
+     * slots included.  A distorted entry has two rows: bf has no meaning there and the stereo bit of a slot on it is not
+     * looked at for them (as on a Kannala-Brandt entry it still picks the robust kernel; the graph level refuses such a
+     * slot).  z <= 0 is the caller's problem, as for the pinhole.  A distorted
+     * and a Kannala-Brandt entry cannot share a table.  CUGO_RIG_DISTORTION with d_cam_ext == NULL or together with
+     * has_depth != 0 is CUGO_ERR_INVALID before anything is launched. */
     int has_rig;
-    const double* d_cam_ext; /* [n_cams][12], or [n_cams][17] with CUGO_RIG_MODELS */
+    const double* d_cam_ext; /* [n_cams][12], [n_cams][17] with CUGO_RIG_MODELS, [n_cams][18] with CUGO_RIG_DISTORTION */
 } cugo_edges;
 
 /* cugo_edges.has_rig */
@@ -134,6 +147,8 @@ typedef struct cugo_edges
 #define CUGO_RIG_EXTRINSICS 1 /* d_cam_ext [n_cams][12]: sensor poses */
 #define CUGO_RIG_MODELS 2     /* d_cam_ext [n_cams][17]: sensor poses, Kannala-Brandt coefficients, model flag */
 #define CUGO_CAM_TAB_STRIDE 17
+#define CUGO_RIG_DISTORTION 3 /* d_cam_ext [n_cams][18]: sensor poses, (k1, k2, p1, p2, k3), distortion flag */
+#define CUGO_DIST_TAB_STRIDE 18
 
 typedef struct cugo_robust
 {
@@ -760,6 +775,26 @@ int cugo_graph_add_edges_model(cugo_graph* g, int dim, int n, const int32_t* pos
                                const double* model_k5);
 int cugo_graph_n_fisheye_cameras(cugo_graph* g);
 int cugo_graph_get_flat_camera_models(cugo_graph* g, int cap, double* model_k5);
+/* Extension: radial-tangential lens distortion (cugo_edges.has_rig == CUGO_RIG_DISTORTION).  d5 = (k1, k2, p1, p2, k3)
+ * in OpenCV's order and meaning (NULL: zeros, no distortion); measurements on a distorted camera are raw pixels.  Like
+ * the sensor pose the distortion follows the camera: cugo_graph_set_camera_distortion sets that of the mono (dim 2) or
+ * stereo (dim 3) set; cugo_graph_add_edges_distorted is cugo_graph_add_edges with, per edge, a camera cam5 [n][5], a
+ * sensor pose sensor_q_t7 [n][7] and a distortion dist5 [n][5] — each of the three may be NULL and counts on a graph
+ * created with per_edge_camera only.  A graph whose distortions are all zero runs the kernels it ran before.
+ * cugo_graph_initialize refuses a non-zero distortion on stereo edges, together with depth edges (not yet), on a camera
+ * with a Kannala-Brandt model, in a graph that also has Kannala-Brandt cameras (not yet), on a landmark-sharded graph
+ * (not yet), and coefficients that are not finite.  cugo_graph_predict_observations with cam5 == NULL refuses a set
+ * whose distortion is not zero (a distorted kind there is a later step); with cam5 given it keeps describing an
+ * undistorted camera at the pose, as cugo_graph_reprojection_covariances does.
+ * cugo_graph_n_distorted_cameras: entries of the camera table of the current flattening whose distortion is not zero.
+ * cugo_graph_get_flat_camera_distortions (diagnostic): returns the number of entries of that table and fills the first
+ * `cap` of dist5 [cap][5] = (k1, k2, p1, p2, k3) where not NULL; parallel to cugo_graph_get_flat_cameras. */
+int cugo_graph_set_camera_distortion(cugo_graph* g, int dim, const double* d5);
+int cugo_graph_add_edges_distorted(cugo_graph* g, int dim, int n, const int32_t* pose_ids, const int32_t* landmark_ids,
+                                   const double* meas, const double* info, const double* cam5, const double* sensor_q_t7,
+                                   const double* dist5);
+int cugo_graph_n_distorted_cameras(cugo_graph* g);
+int cugo_graph_get_flat_camera_distortions(cugo_graph* g, int cap, double* dist5);
 /* Point-to-plane / point-to-line pose edges (the reference's PlaneEdgeSet / LineEdgeSet, include/icp_types.h), next to
  * or instead of the BA edges; residuals and conventions as for cugo_icp_edges above.  pointP [n][3]; plane: unit normal
  * [n][3] (used as given) and origin_distance [n]; line: two distinct points a, b [n][3]; info [n] or NULL (the set's
