@@ -133,6 +133,14 @@ class PriorEdges(C.Structure):
                 ("n_info", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int), ("delta", C.c_double)]
 
 
+class PointEdges(C.Structure):
+    """cugo_point_edges: point-to-point pose edges with 3 x 3 information, pose-sorted structure of arrays (cugo_hip.h):
+    d_p, d_z [3][n]; d_info [6][n_info], the upper triangle of Omega packed row-major (00 01 02 11 12 22), n_info = n or 1."""
+    _fields_ = [("n_poses_total", C.c_int), ("n_poses_free", C.c_int), ("n", C.c_int),
+                ("d_pose", C.c_void_p), ("d_pose_ptr", C.c_void_p), ("d_p", C.c_void_p), ("d_z", C.c_void_p),
+                ("d_info", C.c_void_p), ("n_info", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int), ("delta", C.c_double)]
+
+
 class LmPriorEdges(C.Structure):
     """cugo_lm_prior_edges: landmark position priors with 3 x 3 information, landmark-sorted structure of arrays
     (cugo_hip.h)."""
@@ -250,6 +258,22 @@ def icp_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, 
 def prior_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
     """cugo_prior_construct_quadratic_form_schur: as icp_construct_quadratic_form_schur, for PriorEdges"""
     check(lib().cugo_prior_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def point_compute_errors(ctx, ev, d_poses, d_chi, d_edge_chi=None):
+    """cugo_point_compute_errors: the chi2 of the point edges `ev` (PointEdges) to d_chi[0], and the term of every edge
+    to d_edge_chi [n] if given.  Handles and pointers as for icp_construct_quadratic_form_schur"""
+    check(lib().cugo_point_compute_errors(ctx, C.byref(ev), d_poses, d_chi, d_edge_chi))
+
+
+def point_construct_quadratic_form(ctx, ev, d_poses, d_Hpp, d_bp, d_chi=None):
+    """cugo_point_construct_quadratic_form: the terms ADDED to d_Hpp [n_poses_free][36] and d_bp [n_poses_free][6]"""
+    check(lib().cugo_point_construct_quadratic_form(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_chi))
+
+
+def point_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
+    """cugo_point_construct_quadratic_form_schur: as icp_construct_quadratic_form_schur, for PointEdges"""
+    check(lib().cugo_point_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
 
 
 def lm_prior_compute_errors(ctx, ev, d_lms, d_chi, d_edge_chi=None):
@@ -786,6 +810,52 @@ class Graph:
     def n_landmark_prior_edges(self):
         """landmark priors that count in the current flattening (priors on fixed landmarks are not counted)"""
         return lib().cugo_graph_n_landmark_prior_edges(self._g)
+
+    def add_point_edges(self, pose_ids, pointP, pointZ, info9=None):
+        """point-to-point pose edges (an extension; PointEdgeSet): residual R(q) p + t - z of the known points pointP [n, 3]
+        against their measurements pointZ [n, 3] in the pose's frame, cost r^T Omega r.  info9: [n, 3, 3] (or one 3 x 3 for
+        all; positive SEMI-definite); None for the set's matrix (set_point_information).  An unknown pose id refuses the
+        whole call"""
+        n = len(pose_ids)
+        if n == 0:
+            return
+        pi = np.ascontiguousarray(pose_ids, np.int32)
+        p = np.ascontiguousarray(np.asarray(pointP, np.float64).reshape(n, 3))
+        z = np.ascontiguousarray(np.asarray(pointZ, np.float64).reshape(n, 3))
+        w = None if info9 is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(info9, np.float64).reshape(-1, 9), (n, 9)))
+        check(lib().cugo_graph_add_point_edges(self._g, n, _p(pi, _i32p), _p(p, _f64p), _p(z, _f64p),
+                                               None if w is None else _p(w, _f64p)))
+
+    def set_point_information(self, info9):
+        """the point set's 3 x 3 information: the matrix that counts when per_edge_information is off.  An edge added
+        without a matrix of its own takes a COPY of the set's matrix at the time of the add; a later call does not
+        reach it when per_edge_information is on"""
+        w = np.ascontiguousarray(np.asarray(info9, np.float64).reshape(9))
+        check(lib().cugo_graph_set_point_information(self._g, _p(w, _f64p)))
+
+    def set_point_robust_kernel(self, rk_type, delta):
+        check(lib().cugo_graph_set_point_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
+
+    def n_point_edges(self):
+        """point edges that count in the current flattening (edges on fixed poses are not counted)"""
+        return lib().cugo_graph_n_point_edges(self._g)
+
+    def flat_point_edges(self):
+        """the point edges of the current flattening as the kernels read them (a diagnostic; works on a plan-only graph):
+        dict(pose [n] ascending flattened pose index, src [n] position of each edge among the edges added, p [3, n],
+        z [3, n], info [6, n_info] the packed upper triangles 00 01 02 11 12 22, n_info = n or 1)"""
+        ni = C.c_int(0)
+        n = lib().cugo_graph_get_flat_point_edges(self._g, 0, None, None, None, None, None, C.byref(ni))
+        if n < 0:
+            check(n)
+        pose, src = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        p, z, info = np.zeros((3, n)), np.zeros((3, n)), np.zeros((6, ni.value if n else 0))
+        rc = lib().cugo_graph_get_flat_point_edges(self._g, n, _p(pose, _i32p), _p(src, _i32p), _p(p, _f64p), _p(z, _f64p),
+                                                   _p(info, _f64p), C.byref(ni))
+        if rc < 0:
+            check(rc)
+        return dict(pose=pose, src=src, p=p, z=z, info=info, n_info=ni.value)
 
     def add_relpose_edges(self, pose_ids_a, pose_ids_b, q_t7, info36=None):
         """relative-pose SE(3) edges (an extension; RelPoseEdgeSet): residual [Log_SO3(R_D); t_D] of D = T_a T_b^-1 Z^-1

@@ -10,6 +10,7 @@
 #include "../../include/cuda_graph_optimisation.h"
 #include "../../include/icp_types.h"
 #include "../../include/landmark_prior_types.h"
+#include "../../include/point_edge_types.h"
 #include "../../include/prior_types.h"
 #include "../../include/relpose_types.h"
 #include "../kernels/kernels.h"
@@ -304,6 +305,62 @@ int cugo_icp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_icp_edges*
             cugo_k::launch_pose_chi_total(ctx->stream, "k_icp_chi_total",
                                           rs.d_partials + cugo_k::icp_scratch_doubles(*ev) - n_chi, n_chi, d_chi, false);
         }
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+} // extern "C"
+
+namespace
+{
+// as check_icp, for the one kind of the point edges
+cugo_k::PointScratch check_point(cugo_ctx* ctx, const cugo_point_edges* ev)
+{
+    if (!ev || ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total || ev->n < 0)
+        throw std::runtime_error("cugo_point: bad pose or edge counts");
+    const size_t need = cugo_k::point_scratch_doubles(*ev);
+    const cugo_k::ReduceScratch rs = pose_scratch_for(ctx, need);
+    check_pose_kind(ctx, "cugo_point", "", ev->n, ev->n_poses_total, ev->d_pose, ev->d_pose_ptr, ev->rk, ev->delta,
+                    !ev->d_p || !ev->d_z || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n));
+    check_pose_indices(ctx, "cugo_point", "point", {{ev->d_pose, ev->d_pose_ptr, ev->n, "k_point_check"}}, ev->n_poses_total,
+                       rs, need);
+    return cugo_k::point_scratch_in(rs, *ev);
+}
+} // namespace
+
+extern "C" {
+
+int cugo_point_compute_errors(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses, double* d_chi,
+                              double* d_edge_chi)
+{
+    return guarded([&] {
+        const cugo_k::PointScratch rs = check_point(ctx, ev);
+        cugo_k::launch_point_errors(ctx->stream, *ev, d_poses, rs, d_chi, false, d_edge_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_point_construct_quadratic_form(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses, double* d_Hpp,
+                                        double* d_bp, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::PointScratch rs = check_point(ctx, ev);
+        cugo_k::launch_point_build(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs, d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_point_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses,
+                                              const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::PointScratch rs = check_point(ctx, ev);
+        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
+            throw std::runtime_error("cugo_point: missing rowptr, Hsc, bp or bsc");
+        cugo_k::launch_point_chunks(ctx->stream, *ev, d_poses, true, rs);
+        cugo_k::launch_point_add_schur(ctx->stream, *ev, rs, d_rowptr, d_Hsc, d_bp, d_bsc);
+        if (d_chi)
+            cugo_k::launch_point_chi_total(ctx->stream, *ev, rs, d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
 }
@@ -1180,6 +1237,8 @@ struct cugo_graph
     std::deque<cugo::StereoEdge> stereo_store;
     cugo::DepthEdgeSet depth;
     std::deque<cugo::DepthEdge> depth_store;
+    cugo::PointEdgeSet point;
+    std::deque<cugo::PointEdge> point_store;
     bool attached = false;
     void attach()
     {
@@ -1194,7 +1253,8 @@ struct cugo_graph
         opt->addEdgeSet(&prior);
         opt->addEdgeSet(&relpose);
         opt->addEdgeSet(&lm_prior);
-        opt->addEdgeSet(&depth); // (last: the indices of the other sets in messages stay what they were)
+        opt->addEdgeSet(&depth); // (behind the others: the indices of the other sets in messages stay what they were)
+        opt->addEdgeSet(&point); // (likewise)
         attached = true;
     }
 };
@@ -1722,6 +1782,64 @@ int cugo_graph_set_landmark_prior_robust_kernel(cugo_graph* g, int type, double 
     return guarded([&] { g->lm_prior.setRobustKernel(rk_type_of(type), delta); });
 }
 int cugo_graph_n_landmark_prior_edges(cugo_graph* g) { return g->opt->nLandmarkPriorEdges(); }
+int cugo_graph_add_point_edges(cugo_graph* g, int n, const int32_t* pose_ids, const double* pointP, const double* pointZ,
+                               const double* info9)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids || !pointP || !pointZ)))
+            throw std::invalid_argument("cugo_graph_add_point_edges: missing arrays");
+        for (int i = 0; i < n; i++) // (all or nothing: an unknown id adds no edge)
+            (void)icp_pose(g, pose_ids[i]);
+        for (int i = 0; i < n; i++)
+        {
+            g->point_store.emplace_back();
+            cugo::PointEdge& e = g->point_store.back();
+            e.setVertex(icp_pose(g, pose_ids[i]), 0);
+            e.setMeasurement(cugo::PointToPointMatch<double>(pointP + 3 * (size_t)i, pointZ + 3 * (size_t)i,
+                                                             info9 ? info9 + 9 * (size_t)i : g->point.informationMatrix()));
+            g->point.addEdge(&e);
+        }
+    });
+}
+int cugo_graph_set_point_information(cugo_graph* g, const double* info9)
+{
+    return guarded([&] {
+        if (!info9)
+            throw std::invalid_argument("cugo_graph_set_point_information: no matrix");
+        g->point.setInformationMatrix(info9);
+    });
+}
+int cugo_graph_set_point_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    return guarded([&] { g->point.setRobustKernel(rk_type_of(type), delta); });
+}
+int cugo_graph_n_point_edges(cugo_graph* g) { return g->opt->nPointEdges(); }
+int cugo_graph_get_flat_point_edges(cugo_graph* g, int cap, int32_t* pose, int32_t* src_edge, double* p, double* z,
+                                    double* info, int* n_info)
+{
+    int n = -1;
+    const int rc = guarded([&] {
+        std::vector<int> q, s;
+        std::vector<double> vp, vz, vi;
+        const int ni = g->opt->flatPointEdges(q, s, vp, vz, vi);
+        n = (int)q.size();
+        if (n_info)
+            *n_info = ni;
+        if (cap < n)
+            return;
+        if (pose)
+            std::copy(q.begin(), q.end(), pose);
+        if (src_edge)
+            std::copy(s.begin(), s.end(), src_edge);
+        if (p)
+            std::copy(vp.begin(), vp.end(), p);
+        if (z)
+            std::copy(vz.begin(), vz.end(), z);
+        if (info && n > 0)
+            std::copy(vi.begin(), vi.end(), info);
+    });
+    return rc == CUGO_OK ? n : rc;
+}
 int cugo_graph_set_camera(cugo_graph* g, int dim, const double* c)
 {
     const cugo::Camera cam(c[0], c[1], c[2], c[3], c[4]);

@@ -170,8 +170,10 @@ struct Engine::Impl : cugo_k::LaunchHook
     // the relative-pose edges in container order with a plan (relpose_plan.h) against the Hsc pattern in place of a
     // sort; the views the kernels take; and a scratch of their own (the BA scratch holds live scale / chi2 partials and
     // records across the same span of the stream):
-    //     [ICP partials | ICP chunk chi2 totals | prior workgroup chi2 totals | relative-pose workgroup chi2 totals |
-    //      landmark-prior workgroup chi2 totals | 16 doubles of slack]
+    //     [point partials | ICP partials | ICP chunk chi2 totals | point chunk chi2 totals | prior workgroup chi2 totals |
+    //      relative-pose workgroup chi2 totals | landmark-prior workgroup chi2 totals | 16 doubles of slack]
+    // (the point-to-point edges, point_kernels.hip, are a fifth kind on the machinery of the ICP kinds; without them
+    // their two runs are empty and the layout is what it was)
     // The landmark position priors (FlatGraph::lm_priors, lm_prior_kernels.hip) sit on landmarks, not poses, but their
     // chi2 travels the same way, so they live here too: sorted by landmark (stable) with a CSR over all landmarks,
     // planar on the device.  Their terms ride in the BA build pass (launch_build with the view); only the chi2 has
@@ -188,11 +190,13 @@ struct Engine::Impl : cugo_k::LaunchHook
         cugo_icp_edges icp{};
         cugo_prior_edges prior{};
         cugo_relpose_edges relpose{};
-        int n_icp = 0, n_prior = 0, n_relpose = 0;
-        // totals an ICP pass / a prior pass / a relative-pose pass leaves (0: the pass is not launched)
-        int n_icp_chi = 0, n_prior_wg = 0, n_relpose_wg = 0;
+        cugo_point_edges point{};
+        int n_icp = 0, n_prior = 0, n_relpose = 0, n_point = 0;
+        // totals an ICP pass / a point pass / a prior pass / a relative-pose pass leaves (0: the pass is not launched)
+        int n_icp_chi = 0, n_point_chi = 0, n_prior_wg = 0, n_relpose_wg = 0;
         DevBuf<double> d_scratch;
-        size_t off_icp_chi = 0, off_prior_chi = 0, off_relpose_chi = 0, off_lm_prior_chi = 0; // the layout above, set by bind()
+        // the layout above, set by bind()
+        size_t off_icp = 0, off_icp_chi = 0, off_point_chi = 0, off_prior_chi = 0, off_relpose_chi = 0, off_lm_prior_chi = 0;
         // landmark position priors: sorted host copies (h_lmp_lm, h_lmp_ptr: what initialize() checks against the slot
         // layout), the device arrays, the view
         std::vector<int32_t> h_lmp_lm, h_lmp_ptr;
@@ -295,14 +299,15 @@ struct Engine::Impl : cugo_k::LaunchHook
         }
         double* relpose_chi() { return d_scratch.data() + off_relpose_chi; }
 
-        cugo_k::ReduceScratch icp_rs() { return {d_scratch.data(), d_scratch.size()}; }
+        cugo_k::ReduceScratch icp_rs() { return {d_scratch.data() + off_icp, d_scratch.size() - off_icp}; }
+        cugo_k::PointScratch point_rs() { return {d_scratch.data(), d_scratch.data() + off_point_chi}; }
         double* prior_chi() { return d_scratch.data() + off_prior_chi; }
         int n_edges(int k) const { return (int)kind[k].h_pose.size(); }
         const std::vector<int32_t>& icp_slot_source(int k, bool set) const { return set ? kind[k].slot_set : kind[k].slot_edge; }
-        // the chi2 totals of the last ICP, prior and relative-pose pass, one array; nullptr / 0 without such edges
+        // the chi2 totals of the last ICP, point, prior and relative-pose pass, one array; nullptr / 0 without such edges
         const double* chi_totals(int* n)
         {
-            *n = n_icp_chi + n_prior_wg + n_relpose_wg + n_lm_prior_wg;
+            *n = n_icp_chi + n_point_chi + n_prior_wg + n_relpose_wg + n_lm_prior_wg;
             return *n ? d_scratch.data() + off_icp_chi : nullptr;
         }
 
@@ -313,6 +318,7 @@ struct Engine::Impl : cugo_k::LaunchHook
             bind_lm_priors(g.lm_priors, Lall, L, stream, plan_only);
             n_icp = g.kinds[POSE_KIND_PLANE].n() + g.kinds[POSE_KIND_LINE].n();
             n_prior = g.kinds[POSE_KIND_PRIOR].n(), n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
+            n_point = g.kinds[POSE_KIND_POINT].n();
             for (int k = 0; k < POSE_KIND_COUNT; k++)
             {
                 KindBufs& b = kind[k];
@@ -360,15 +366,27 @@ struct Engine::Impl : cugo_k::LaunchHook
             // (run-time flags: the plan is still built with none, and an edge flagged here "counts for nothing")
             relpose.d_flags = bind_reject(POSE_KIND_RELPOSE, stream, plan_only);
             rp.plan_dirty = true;
-            // the scratch layout (the chunk totals end the ICP part)
+            const KindBufs& pt = kind[POSE_KIND_POINT];
+            point = cugo_point_edges{};
+            point.n_poses_total = Pall, point.n_poses_free = P, point.n = n_point;
+            point.d_pose = pt.d_pose.data(), point.d_pose_ptr = pt.d_ptr.data();
+            // (meas is planar: p [3][n], then z [3][n])
+            point.d_p = pt.d_meas.data(), point.d_z = pt.d_meas.data() + 3 * (size_t)n_point;
+            point.d_info = pt.d_weight.data(), point.n_info = pt.n_weight;
+            point.rk = g.kinds[POSE_KIND_POINT].rk, point.delta = g.kinds[POSE_KIND_POINT].delta;
+            bind_reject(POSE_KIND_POINT, stream, plan_only); // (never on: graph_optimisation.cpp refuses a threshold on the kind)
+            // the scratch layout (the chunk totals end the ICP part; the point totals follow them)
+            off_icp = n_point ? cugo_k::point_partial_doubles(point) : 0;
+            n_point_chi = n_point ? cugo_k::point_chunk_count(point) : 0;
             const size_t icp_doubles = n_icp ? cugo_k::icp_scratch_doubles(icp) : 0;
             n_icp_chi = n_icp ? cugo_k::icp_chunk_count(icp) : 0;
             n_prior_wg = cugo_k::prior_workgroups(prior), n_relpose_wg = cugo_k::relpose_workgroups(relpose);
-            off_icp_chi = icp_doubles - n_icp_chi, off_prior_chi = icp_doubles;
+            off_icp_chi = off_icp + icp_doubles - n_icp_chi, off_point_chi = off_icp + icp_doubles;
+            off_prior_chi = off_point_chi + (size_t)n_point_chi;
             off_relpose_chi = off_prior_chi + (size_t)n_prior_wg;
             off_lm_prior_chi = off_relpose_chi + (size_t)n_relpose_wg;
-            if ((n_icp || n_prior_wg || n_relpose_wg || n_lm_prior_wg) && !plan_only)
-                d_scratch.resize(icp_doubles + (size_t)n_prior_wg + (size_t)n_relpose_wg + (size_t)n_lm_prior_wg + 16);
+            if ((n_icp || n_point || n_prior_wg || n_relpose_wg || n_lm_prior_wg) && !plan_only)
+                d_scratch.resize(off_lm_prior_chi + (size_t)n_lm_prior_wg + 16);
         }
         // the plan against the Hsc pattern at hand (upper block CSR over the free poses): the engine made the pattern
         // from these very pairs, so a pair missing from it is a defect of the engine and throws
@@ -409,6 +427,14 @@ struct Engine::Impl : cugo_k::LaunchHook
                 if (d_chi)
                     cugo_k::launch_pose_chi_total(s, "k_icp_chi_total", d_scratch.data() + off_icp_chi, n_icp_chi, d_chi, true);
             }
+            if (n_point)
+            { // as the ICP kinds: the chunk pass, its add here or behind k_pose_schur
+                cugo_k::launch_point_chunks(s, point, poses, true, point_rs());
+                if (!one_stream)
+                    cugo_k::launch_point_add(s, point, point_rs(), Hpp, bp);
+                if (d_chi)
+                    cugo_k::launch_point_chi_total(s, point, point_rs(), d_chi, true);
+            }
             if (n_prior_wg)
             {
                 if (!one_stream)
@@ -447,6 +473,8 @@ struct Engine::Impl : cugo_k::LaunchHook
         {
             if (n_icp)
                 cugo_k::launch_icp_add_schur(s, icp, icp_rs(), rowptr, Hsc, bp, bsc);
+            if (n_point)
+                cugo_k::launch_point_add_schur(s, point, point_rs(), rowptr, Hsc, bp, bsc);
             if (n_prior_wg)
                 cugo_k::launch_prior_add_schur(s, prior, poses, rowptr, Hsc, bp, bsc, prior_chi());
             if (n_relpose_wg)
@@ -457,6 +485,8 @@ struct Engine::Impl : cugo_k::LaunchHook
         {
             if (n_icp)
                 cugo_k::launch_icp_chunks(s, icp, poses, false, icp_rs());
+            if (n_point)
+                cugo_k::launch_point_chunks(s, point, poses, false, point_rs());
             if (n_prior_wg)
                 cugo_k::launch_prior_errors(s, prior, poses, prior_chi());
             if (n_relpose_wg)
@@ -1274,6 +1304,9 @@ void Engine::initialize(FlatGraph& g)
     if (n_relpose && m.opt.hsc_strip)
         throw std::runtime_error("cugo: relative-pose edge sets cannot be combined with CUGO_HSC_STRIP=1: the row-strip "
                                  "form of the Schur complement cannot hold a block without landmark products");
+    if (g.kinds[POSE_KIND_POINT].n() && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: point-to-point edge sets (PointEdgeSet) are not supported on a landmark-sharded "
+                                 "(multi-GPU) optimiser yet");
     for (int k = POSE_KIND_PRIOR; k >= 0; k--) // (priors first: the message a graph with several kinds has always got)
         if (g.kinds[k].n() && (m.world > 1 || m.comm))
             throw std::runtime_error(std::string("cugo: ") + pose_kind_group(k) +
@@ -2063,6 +2096,18 @@ const std::vector<int32_t>& Engine::icp_slot_source(int kind, bool set) const
 int Engine::n_prior_edges() const { return impl_->pe.n_prior; }
 int Engine::n_relpose_edges() const { return impl_->pe.n_relpose; }
 int Engine::n_lm_prior_edges() const { return impl_->pe.n_lm_prior; }
+int Engine::n_point_edges() const { return impl_->pe.n_point; }
+int Engine::flat_point_edges(std::vector<int32_t>& pose, std::vector<int32_t>& src_edge, std::vector<double>& p,
+                             std::vector<double>& z, std::vector<double>& info) const
+{
+    const auto& k = impl_->pe.kind[POSE_KIND_POINT];
+    const size_t n = k.h_pose.size();
+    pose = k.h_pose, src_edge = k.slot_edge;
+    p.assign(k.h_meas.begin(), k.h_meas.begin() + 3 * n); // (meas is planar: p [3][n], then z [3][n])
+    z.assign(k.h_meas.begin() + 3 * n, k.h_meas.begin() + 6 * n);
+    info = k.h_weight;
+    return k.n_weight;
+}
 int Engine::n_poses_free() const { return impl_->P; }
 int Engine::n_landmarks_free() const { return impl_->L; }
 

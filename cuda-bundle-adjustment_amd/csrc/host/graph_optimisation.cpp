@@ -4,6 +4,7 @@
 #include "../../include/cuda_graph_optimisation.h"
 #include "../../include/icp_types.h"
 #include "../../include/landmark_prior_types.h"
+#include "../../include/point_edge_types.h"
 #include "../../include/prior_types.h"
 #include "../../include/relpose_types.h"
 
@@ -76,6 +77,15 @@ int CudaGraphOptimisationImpl::nIcpEdges(int kind) const { return engine_->n_icp
 int CudaGraphOptimisationImpl::nPriorEdges() const { return engine_->n_prior_edges(); }
 int CudaGraphOptimisationImpl::nRelPoseEdges() const { return engine_->n_relpose_edges(); }
 int CudaGraphOptimisationImpl::nLandmarkPriorEdges() const { return engine_->n_lm_prior_edges(); }
+int CudaGraphOptimisationImpl::nPointEdges() const { return engine_->n_point_edges(); }
+int CudaGraphOptimisationImpl::flatPointEdges(std::vector<int>& pose, std::vector<int>& srcEdge, std::vector<double>& p,
+                                              std::vector<double>& z, std::vector<double>& info) const
+{
+    std::vector<int32_t> q, s;
+    const int n_info = engine_->flat_point_edges(q, s, p, z, info);
+    pose.assign(q.begin(), q.end()), srcEdge.assign(s.begin(), s.end());
+    return n_info;
+}
 void CudaGraphOptimisationImpl::flatEdges(std::vector<int>& pose, std::vector<int>& landmark,
                                           std::vector<unsigned char>& flags, std::vector<double>& meas3) const
 {
@@ -430,6 +440,27 @@ static void priorPayload(BaseEdge* e, const double* setInformation, Refuse& refu
             weight[t++] = 0.5 * (A[6 * r + c] + A[6 * c + r]);
 }
 
+// point-to-point: p, z | the upper triangle of the symmetric part of the 3 x 3 Omega (the edge's own matrix, checked here,
+// or the set's, checked with the set)
+template <class Refuse>
+static void pointPayload(BaseEdge* e, const double* setInformation, Refuse& refuse, double* m, double* weight)
+{
+    const auto& mz = *static_cast<const PointToPointMatch<double>*>(e->measurementData());
+    for (int c = 0; c < 3; c++)
+    {
+        m[c] = mz.pointP[c], m[3 + c] = mz.pointZ[c];
+        if (!std::isfinite(m[c]) || !std::isfinite(m[3 + c]))
+            refuse("non-finite point or measured point");
+    }
+    const double* A = setInformation ? setInformation : mz.information;
+    if (!setInformation)
+        if (const char* bad = checkInformation<3>(A))
+            refuse(bad);
+    for (int r = 0, t = 0; r < 3; r++)
+        for (int c = r; c < 3; c++)
+            weight[t++] = 0.5 * (A[3 * r + c] + A[3 * c + r]);
+}
+
 // One LandmarkPriorEdgeSet (landmark_prior_types.h) into the flat arrays, in container order; the one place where these
 // edges are checked, as flattenPoseEdgeSet is for the pose kinds.  Every active edge must sit on a landmark vertex of one
 // of the optimiser's landmark sets and hold finite values and a symmetric positive semi-definite Omega (its own with
@@ -590,8 +621,8 @@ void CudaGraphOptimisationImpl::initialize()
     // the flattened order is exactly the container order.
     size_t cap = 0;
     g.has_depth = false, g.rk_type_depth = CUGO_RK_NONE, g.rk_delta_depth = 1.0, g.depth_weight = 1.0;
-    for (BaseEdgeSet* es : edgeSets) // (a LandmarkPriorEdgeSet is 3-d like a stereo set: the type tells them apart)
-        if (es->dim() != 1 && es->dim() != 6 && !dynamic_cast<LandmarkPriorEdgeSet*>(es))
+    for (BaseEdgeSet* es : edgeSets) // (a LandmarkPriorEdgeSet or PointEdgeSet is 3-d like a stereo set: the type tells them apart)
+        if (es->dim() != 1 && es->dim() != 6 && !dynamic_cast<LandmarkPriorEdgeSet*>(es) && !dynamic_cast<PointEdgeSet*>(es))
             cap += es->nedges();
     for (cugo_host::FlatPoseKind& fk : g.kinds)
         fk.clear();
@@ -629,6 +660,22 @@ void CudaGraphOptimisationImpl::initialize()
         if (auto* ls = dynamic_cast<LandmarkPriorEdgeSet*>(es))
         { // landmark_prior_types.h, an extension: by type, before the dispatch on dim() (stereo BA sets are 3-d as well)
             flattenLandmarkPriorSet(ls, (int)si, vertexSets, options.perEdgeInformation, g.lm_priors);
+            continue;
+        }
+        if (auto* pts = dynamic_cast<PointEdgeSet*>(es))
+        { // point_edge_types.h, an extension: by type as well.  Outlier rejection is not available on this kind
+            if (pts->getOutlierThreshold() > 0.0)
+                throw std::runtime_error("cugo: point-to-point edge set " + std::to_string(si) +
+                                         ": outlier rejection is not supported on PointEdgeSet yet (setOutlierThreshold "
+                                         "must stay 0, whatever poseEdgeOutlierRejection says)");
+            const double* setInformation = options.perEdgeInformation ? nullptr : pts->informationMatrix();
+            flattenPoseEdgeSet(
+                es, (int)si, 1, cugo_host::pose_kind_name(cugo_host::POSE_KIND_POINT), vertexSets, false,
+                g.kinds[cugo_host::POSE_KIND_POINT], poseSetEdges_[si],
+                [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
+                    pointPayload(e, setInformation, refuse, meas, weight);
+                },
+                [&] { return setInformation ? checkInformation<3>(setInformation) : nullptr; });
             continue;
         }
         if (dim == 1)

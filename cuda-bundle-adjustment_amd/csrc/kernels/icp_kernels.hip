@@ -26,15 +26,12 @@
 
 #include "ba_math.h"
 #include "kernels.h"
+#include "pose_chunks.h"
 
 namespace
 {
 
 using namespace cugo_dev;
-
-constexpr int ICP_CHUNK = 512; // edges per wave
-constexpr int ICP_NP = 28;     // doubles per partial
-constexpr int ICP_WG = 256;
 
 struct IcpKind
 {
@@ -132,39 +129,6 @@ __device__ __forceinline__ double icp_edge(const IcpKind& k, int e, const double
         }
     }
     return chi;
-}
-
-// 32 accumulators -> their 64-lane sums; afterwards a[0] of lane L holds the sum of accumulator L >> 1
-// (the halving exchange of ba_kernels.hip's wave_reduce32, fixed order)
-__device__ __forceinline__ void icp_wave_reduce32(double (&a)[32])
-{
-    const int lane = threadIdx.x & 63;
-#define CUGO_HALVE(N, OFF)                                     \
-    {                                                          \
-        const bool hi = (lane & OFF) != 0;                     \
-        _Pragma("unroll") for (int i = 0; i < N; i++)          \
-        {                                                      \
-            const double send = hi ? a[i] : a[i + N];          \
-            const double keep = hi ? a[i + N] : a[i];          \
-            a[i] = keep + __shfl_xor(send, OFF, 64);           \
-        }                                                      \
-    }
-    CUGO_HALVE(16, 32)
-    CUGO_HALVE(8, 16)
-    CUGO_HALVE(4, 8)
-    CUGO_HALVE(2, 4)
-    CUGO_HALVE(1, 2)
-#undef CUGO_HALVE
-    a[0] += __shfl_xor(a[0], 1, 64);
-}
-
-// sum over the wave in a fixed butterfly order (every lane gets it)
-__device__ __forceinline__ double icp_wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        x += __shfl_xor(x, off, 64);
-    return x;
 }
 
 // One wave per chunk of ICP_CHUNK edges of one kind.  FULL: partials of H, b and chi2; otherwise chi2 only (slot
@@ -270,12 +234,7 @@ __global__ __launch_bounds__(ICP_WG) __attribute__((amdgpu_waves_per_eu(6))) voi
 // sum of pose p's partials of one kind, element t, in chunk order
 __device__ __forceinline__ double icp_pose_sum(const IcpKind& k, int p, int t)
 {
-    const int i0 = k.pose_ptr[p], i1 = k.pose_ptr[p + 1];
-    double s = 0.0;
-    if (i1 > i0)
-        for (int c = i0 / ICP_CHUNK, c1 = (i1 - 1) / ICP_CHUNK; c <= c1; c++)
-            s += k.part[(size_t)(c + p) * ICP_NP + t];
-    return s;
+    return chunk_pose_sum(k.pose_ptr, k.part, p, t);
 }
 
 // 32 threads per free pose that has ICP edges; thread t < 27 adds element t of the pose's sums.  SCHUR = false: to

@@ -216,6 +216,33 @@ void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch
 // doubles of the scratch: what launch_errors_tail / launch_trial_tail_from_build sum into F-hat
 int icp_chunk_count(const cugo_icp_edges& ev);
 
+// --- point-to-point pose edges with 3 x 3 information (point_kernels.hip) -----------------
+// The launchers of the ICP kinds, for the one kind of cugo_point_edges.  A pass leaves its partials (point_partial_doubles()
+// doubles) and one chi2 total per chunk (point_chunk_count()) where PointScratch says: in one scratch behind one another
+// (point_scratch_in: the kernel-level C ABI), or the totals elsewhere (the LM loop keeps them beside the other kinds' totals)
+struct PointScratch
+{
+    double* d_part;
+    double* d_cchi;
+};
+size_t point_scratch_doubles(const cugo_point_edges& ev); // partials + totals
+size_t point_partial_doubles(const cugo_point_edges& ev);
+int point_chunk_count(const cugo_point_edges& ev);
+PointScratch point_scratch_in(ReduceScratch rs, const cugo_point_edges& ev);
+// ADDS the terms to d_Hpp / d_bp; chi2 total to d_chi[0] if given (added to what is there with chi_add)
+void launch_point_build(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
+                        PointScratch rs, double* d_chi, bool chi_add = false);
+// chi2 only (the same bits as launch_point_build's); d_edge_chi: per edge, or nullptr
+void launch_point_errors(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, PointScratch rs, double* d_chi,
+                         bool chi_add = false, double* d_edge_chi = nullptr);
+// the pieces: the chunk pass alone, the per-pose sums ADDED to d_Hpp / d_bp or to the Schur destination, the chi2 total
+void launch_point_chunks(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, bool full, PointScratch rs,
+                         double* d_edge_chi = nullptr);
+void launch_point_add(hipStream_t s, const cugo_point_edges& ev, PointScratch rs, double* d_Hpp, double* d_bp);
+void launch_point_add_schur(hipStream_t s, const cugo_point_edges& ev, PointScratch rs, const int32_t* d_rowptr,
+                            double* d_Hsc, double* d_bp, double* d_bsc);
+void launch_point_chi_total(hipStream_t s, const cugo_point_edges& ev, PointScratch rs, double* d_chi, bool chi_add);
+
 // --- SE(3) pose priors with 6 x 6 information (prior_kernels.hip) --------------------------
 // One kernel per pass: 32 lanes per free pose walk its priors in container order and ADD their sums straight to the
 // destination; every workgroup leaves one chi2 total in d_wg_chi [prior_workgroups()].  The LM loop appends these

@@ -148,6 +148,14 @@ public:
     /** landmark position priors of the current flattening that count: active, on a free landmark
      *  (landmark_prior_types.h, an extension) */
     int nLandmarkPriorEdges() const;
+    /** point-to-point pose edges of the current flattening that count: active, on a free pose (point_edge_types.h, an
+     *  extension) */
+    int nPointEdges() const;
+    /** the point edges of the current flattening as the kernels read them: sorted by pose (stable), planar — pose [n],
+     *  position of each edge in its set's container, p [3][n], z [3][n], info [6][n_info] (upper triangle, row-major
+     *  packed); returns n_info (n, or 1 when one matrix serves all).  Diagnostic */
+    int flatPointEdges(std::vector<int>& pose, std::vector<int>& srcEdge, std::vector<double>& p, std::vector<double>& z,
+                       std::vector<double>& info) const;
     /** the pose-landmark edges of the current flattening in flattening order (set by set, container order; mono,
      *  stereo and depth edges share the array): flattened pose and landmark index, CUGO_EDGE_* flags, measurement
      *  (3 per edge, the third 0 for a mono edge).  Diagnostic */

@@ -520,6 +520,51 @@ int cugo_icp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_icp_edges*
                                             const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi);
 
 /*
+ * Extension (the reference has no such edge): point-to-point pose edges, unary edges on a pose with a known 3-D point
+ * p, its measurement z in the pose's frame and a full 3 x 3 information matrix Omega (symmetric, positive SEMI-definite:
+ * singular matrices are legal).  Conventions as for cugo_icp_edges: y = R(q) p + t, left update, tangent order
+ * [omega, upsilon]:
+ *   r = y - z (3-vector),  J = dr/dxi = [ -[y]x | I ]  (3 x 6)
+ *   chi2 term rho(max(0, r^T Omega r)) with the set's robust kernel, weight w = rho';  H += w J^T Omega J,
+ *   b -= w J^T Omega r.
+ * Omega = omega n n^T with n.z = d is the plane edge, Omega = omega (I - u u^T) with z = a the line edge.  With Omega =
+ * (C_z + R C_p R^T)^-1 frozen per outer iteration the edge is that of generalised ICP.  The edges are SORTED by pose index
+ * (ascending), structure of arrays; pose_ptr is the CSR over the pose index.  Edges on fixed poses (index >=
+ * n_poses_free) and edges flagged CUGO_EDGE_INACTIVE contribute nothing.
+ */
+typedef struct cugo_point_edges
+{
+    int n_poses_total, n_poses_free;
+    int n;
+    const int32_t* d_pose;     /* [n] ascending */
+    const int32_t* d_pose_ptr; /* [n_poses_total+1] */
+    const double* d_p;         /* [3][n] the point p */
+    const double* d_z;         /* [3][n] its measurement z */
+    const double* d_info;      /* [6][n] or [6][1]: upper triangle of Omega, row-major packed 00 01 02 11 12 22 */
+    int n_info;                /* n or 1 */
+    const uint8_t* d_flags;    /* [n] CUGO_EDGE_INACTIVE, or NULL: all active */
+    int rk;                    /* CUGO_RK_* */
+    double delta;
+} cugo_point_edges;
+
+/* The three entry points of the ICP kinds, for the point edges: the chi2 total to d_chi[0] and, with d_edge_chi
+ * (optional, [n], sorted order), the chi2 term of every edge (0 for edges that do not count); the terms ADDED to d_Hpp
+ * [n_poses_free][36] / d_bp [n_poses_free][6]; the terms ADDED to the Schur destination (rowptr[p]: the block index of
+ * pose p's diagonal block in d_Hsc; b to d_bp and to d_bsc alike; the diagonal blocks and bp receive the bits the plain
+ * form adds).  The chi2 of a build pass has the bits of cugo_point_compute_errors.  A pose without a counting edge keeps
+ * the bits of its blocks.  Before launching, pose_ptr is checked on the host and the pose index of every edge against
+ * it on the device; a bad layout, an unknown kernel code or an n_info that is neither n nor 1 gives CUGO_ERR_INVALID
+ * (one flag is read back: the call synchronises once).  The values (finite, Omega symmetric positive semi-definite)
+ * are the caller's.  Deterministic, no atomics. */
+int cugo_point_compute_errors(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses, double* d_chi,
+                              double* d_edge_chi);
+int cugo_point_construct_quadratic_form(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses, double* d_Hpp,
+                                        double* d_bp, double* d_chi);
+int cugo_point_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses,
+                                              const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
+                                              double* d_chi);
+
+/*
  * Extension (the reference has no such edge): SE(3) pose priors, unary edges on a pose with a measurement
  * Z = (q_z, t_z) and a full 6 x 6 information matrix Omega (symmetric, positive semi-definite).  With the pose (q, t)
  * read as everywhere else and the left update T <- Exp([omega, upsilon]) T:
@@ -849,6 +894,29 @@ int cugo_graph_set_landmark_prior_information(cugo_graph* g, const double* info9
 int cugo_graph_set_landmark_prior_robust_kernel(cugo_graph* g, int type, double delta);
 /* active landmark priors in the current flattening (priors on fixed landmarks are not counted) */
 int cugo_graph_n_landmark_prior_edges(cugo_graph* g);
+/* Extension: point-to-point pose edges (PointEdgeSet, cuda-bundle-adjustment_amd/include/point_edge_types.h), next to the
+ * other sets or alone; term and conventions as for cugo_point_edges above.  pose_ids [n]: ids given to
+ * cugo_graph_add_poses (an unknown id refuses the whole call: nothing is added); pointP [n][3]: the known points;
+ * pointZ [n][3]: their measurements in the pose's frame; info9 [n][9]: Omega of every edge (symmetric, so row- and
+ * column-major agree), or NULL for a COPY of the set's matrix as it is at the time of the add
+ * (cugo_graph_set_point_information; the identity until it is set: a later change of the set's matrix does not reach an
+ * edge already added), with the per_edge_information rule of the pose priors (off: the set's matrix counts for all).  cugo_graph_initialize() refuses non-finite values, an Omega that is
+ * asymmetric beyond 1e-12 max|Omega| or has an eigenvalue below -1e-12 lambda_max (semi-definite is allowed), a pose of no
+ * pose set of the optimiser, an outlier threshold on the set and a sharded optimiser; edges on fixed poses and inactive
+ * edges count for nothing.  The set is no kind of cugo_graph_n_pose_edge_outliers (CUGO_POSE_KIND_*). */
+int cugo_graph_add_point_edges(cugo_graph* g, int n, const int32_t* pose_ids, const double* pointP, const double* pointZ,
+                               const double* info9);
+int cugo_graph_set_point_information(cugo_graph* g, const double* info9);
+int cugo_graph_set_point_robust_kernel(cugo_graph* g, int type, double delta);
+/* point edges that count in the current flattening (edges on fixed poses are not counted) */
+int cugo_graph_n_point_edges(cugo_graph* g);
+/* Diagnostic: the point edges of the current flattening as the kernels read them (works on a plan-only graph): sorted
+ * by pose (stable: insertion order inside a pose), planar.  Returns their number n (or a negative error) and *n_info (n,
+ * or 1 when one matrix serves all); with cap >= n fills the arrays that are not NULL: pose [n] (flattened index), src_edge
+ * [n] (position among the edges added), p [3][n], z [3][n], info [6][n_info] (upper triangle of the symmetric part of
+ * Omega, row-major packed 00 01 02 11 12 22). */
+int cugo_graph_get_flat_point_edges(cugo_graph* g, int cap, int32_t* pose, int32_t* src_edge, double* p, double* z,
+                                    double* info, int* n_info);
 /* Extension: relative-pose SE(3) edges (RelPoseEdgeSet, cuda-bundle-adjustment_amd/include/relpose_types.h), next to or
  * instead of the other sets; term and conventions as for cugo_relpose_edges above (Z ~ T_a T_b^-1).  pose_ids_a /
  * pose_ids_b [n]: ids given to cugo_graph_add_poses; q_t7 [n][7] the measured relative pose; info36 [n][36] or NULL for
