@@ -157,6 +157,15 @@ class RelPoseEdges(C.Structure):
                 ("rk", C.c_int), ("delta", C.c_double), ("plan", C.c_void_p)]
 
 
+class PointPairEdges(C.Structure):
+    """cugo_point_pair_edges: pose-pose point edges with 3 x 3 information in the SORTED order of their plan
+    (PointPairPlan; cugo_hip.h): d_pose_a, d_pose_b [n]; d_p, d_z [3][n]; d_info [6][n_info], n_info = n or 1."""
+    _fields_ = [("n_poses_total", C.c_int), ("n_poses_free", C.c_int), ("n", C.c_int),
+                ("d_pose_a", C.c_void_p), ("d_pose_b", C.c_void_p), ("d_p", C.c_void_p), ("d_z", C.c_void_p),
+                ("d_info", C.c_void_p), ("n_info", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int), ("delta", C.c_double),
+                ("plan", C.c_void_p)]
+
+
 class HscStruct(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("d_rowptr", C.c_void_p), ("d_colind", C.c_void_p),
                 ("d_off_ptr", C.c_void_p), ("d_off_ei", C.c_void_p), ("d_off_ej", C.c_void_p),
@@ -344,6 +353,44 @@ class RelPosePlan:
             self._p = C.c_void_p()
 
 
+class PointPairPlan:
+    """cugo_point_pair_plan: the stable sort of a set of pose-pose point edges into runs of one (a, b) orientation of a
+    pair, the incidence lists of the free poses and the runs of every pattern block (host arrays).  ctx: a cugo_ctx handle
+    (ctypes.c_void_p), or None for a host-only plan; rowptr / colind: the upper block-CSR pattern, or both None for a
+    plan without a destination (its pair_lo / pair_hi are what a pattern needs)"""
+    ARRAYS = ("perm", "edge_run", "run_ptr", "run_a", "run_b", "run_flags", "run_blk", "inc_ptr", "inc", "blk_id", "blk_ptr",
+              "blk_run", "pair_lo", "pair_hi")
+
+    def __init__(self, ctx, n_poses_total, n_poses_free, pose_a, pose_b, flags=None, rowptr=None, colind=None):
+        a, b = _i32(pose_a), _i32(pose_b)
+        rp, ci = (None if rowptr is None else _i32(rowptr)), (None if colind is None else _i32(colind))
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+        self._p = C.c_void_p()
+        self.n, self.n_poses_total, self.n_poses_free = len(a), int(n_poses_total), int(n_poses_free)
+        check(lib().cugo_point_pair_plan_create(ctx, len(a), self.n_poses_total, self.n_poses_free,
+                                                a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p),
+                                                None if fl is None else fl.ctypes.data_as(_u8p),
+                                                None if rp is None else rp.ctypes.data_as(_i32p),
+                                                None if ci is None else ci.ctypes.data_as(_i32p), C.byref(self._p)))
+
+    @property
+    def handle(self):
+        return self._p
+
+    def array(self, name):
+        """a copy of the plan array `name` (one of ARRAYS)"""
+        out = _i32p()
+        n = lib().cugo_point_pair_plan_array(self._p, name.encode(), C.byref(out))
+        if n < 0:
+            raise CugoError("cugo error %d: %s" % (n, lib().cugo_last_error().decode()))
+        return np.array(out[:n], np.int32)
+
+    def close(self):
+        if self._p:
+            lib().cugo_point_pair_plan_destroy(self._p)
+            self._p = C.c_void_p()
+
+
 class PlCovPlan:
     """cugo_plcov_plan: the plan of a batch of pose-landmark covariance queries (host only, no GPU): the pose pairs to
     ask cugo_chol_inverse_blocks for and, per query, the block every slot of its landmark reads.  lm_ptr / slot_pose:
@@ -421,6 +468,34 @@ def relpose_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_
     """cugo_relpose_construct_quadratic_form_schur: as prior_construct_quadratic_form_schur, plus the off-diagonal
     blocks into d_Hsc by the plan's block indices"""
     check(lib().cugo_relpose_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def point_pair_compute_errors(ctx, ev, d_poses, d_chi, d_edge_chi=None):
+    """cugo_point_pair_compute_errors: chi2 total of `ev` (PointPairEdges) to d_chi[0], optionally the term of every edge
+    (sorted order)"""
+    check(lib().cugo_point_pair_compute_errors(ctx, C.byref(ev), d_poses, d_chi, d_edge_chi))
+
+
+def point_pair_construct_quadratic_form(ctx, ev, d_poses, d_Hpp, d_bp, d_Hoff, d_chi=None):
+    """cugo_point_pair_construct_quadratic_form: diagonal terms ADDED to d_Hpp / d_bp, off-diagonal blocks to d_Hoff
+    [nnzb][36] by the plan's block indices"""
+    check(lib().cugo_point_pair_construct_quadratic_form(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_Hoff, d_chi))
+
+
+def point_pair_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
+    """cugo_point_pair_construct_quadratic_form_schur: the same terms into the Schur destination"""
+    check(lib().cugo_point_pair_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def point_pair_construct_quadratic_form_diag(ctx, ev, d_poses, d_Hpp, d_bp, d_chi=None):
+    """cugo_point_pair_construct_quadratic_form_diag: the diagonal terms and b alone; the off-diagonal partials stay in
+    the plan's scratch for point_pair_add_offdiag_schur"""
+    check(lib().cugo_point_pair_construct_quadratic_form_diag(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_chi))
+
+
+def point_pair_add_offdiag_schur(ctx, ev, d_Hsc):
+    """cugo_point_pair_add_offdiag_schur: the off-diagonal sums of the last build pass ADDED to d_Hsc by block index"""
+    check(lib().cugo_point_pair_add_offdiag_schur(ctx, C.byref(ev), d_Hsc))
 
 
 def pose_edges_reject(ctx, n, d_edge_chi, d_threshold, n_threshold, d_flags, d_rejected):
@@ -856,6 +931,63 @@ class Graph:
         if rc < 0:
             check(rc)
         return dict(pose=pose, src=src, p=p, z=z, info=info, n_info=ni.value)
+
+    def add_point_pair_edges(self, pose_ids_a, pose_ids_b, pointP, pointZ, info9=None):
+        """pose-pose point edges (an extension; PointPairEdgeSet) for scan-to-scan registration: the points pointP [n, 3]
+        measured in pose a's frame, the same physical points measured as pointZ [n, 3] in pose b's frame; residual
+        R_b R_a^T (p - t_a) + t_b - z, cost r^T Omega r with Omega in b's frame.  info9: [n, 3, 3] (or one 3 x 3 for all;
+        positive SEMI-definite); None for the set's matrix (set_point_pair_information).  An unknown pose id or a == b
+        refuses the whole call"""
+        n = len(pose_ids_a)
+        if n == 0:
+            return
+        ia, ib = np.ascontiguousarray(pose_ids_a, np.int32), np.ascontiguousarray(pose_ids_b, np.int32)
+        if len(ib) != n:
+            raise ValueError("pose_ids_a and pose_ids_b must have the same length")
+        p = np.ascontiguousarray(np.asarray(pointP, np.float64).reshape(n, 3))
+        z = np.ascontiguousarray(np.asarray(pointZ, np.float64).reshape(n, 3))
+        w = None if info9 is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(info9, np.float64).reshape(-1, 9), (n, 9)))
+        check(lib().cugo_graph_add_point_pair_edges(self._g, n, _p(ia, _i32p), _p(ib, _i32p), _p(p, _f64p), _p(z, _f64p),
+                                                    None if w is None else _p(w, _f64p)))
+
+    def set_point_pair_information(self, info9):
+        """the pair set's 3 x 3 information, with the rule of set_point_information"""
+        w = np.ascontiguousarray(np.asarray(info9, np.float64).reshape(9))
+        check(lib().cugo_graph_set_point_pair_information(self._g, _p(w, _f64p)))
+
+    def set_point_pair_robust_kernel(self, rk_type, delta):
+        check(lib().cugo_graph_set_point_pair_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
+
+    def set_point_pair_outlier_threshold(self, threshold):
+        """chi2 threshold of the pair set; initialize() refuses a positive one (outlier rejection on the set: not yet)"""
+        check(lib().cugo_graph_set_point_pair_outlier_threshold(self._g, C.c_double(threshold)))
+
+    def set_point_pair_active(self, active, first=0):
+        """active flags of the pair edges first, first + 1, ... (insertion order); takes effect at the next initialize()"""
+        a = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
+        check(lib().cugo_graph_set_point_pair_active(self._g, int(first), len(a), _p(a, _u8p)))
+
+    def n_point_pair_edges(self):
+        """pair edges that count in the current flattening (edges between two fixed poses do not)"""
+        return lib().cugo_graph_n_point_pair_edges(self._g)
+
+    def flat_point_pair_edges(self):
+        """the pair edges of the current flattening as the kernels read them (a diagnostic; works on a plan-only graph):
+        dict(pose_a, pose_b [n] flattened pose indices in the order of the plan (runs of one orientation of a pair, by
+        (lo, hi, orientation)), src [n] position of each edge among the edges added, p [3, n], z [3, n], info [6, n_info]
+        the packed upper triangles 00 01 02 11 12 22, n_info = n or 1)"""
+        ni = C.c_int(0)
+        n = lib().cugo_graph_get_flat_point_pair_edges(self._g, 0, None, None, None, None, None, None, C.byref(ni))
+        if n < 0:
+            check(n)
+        pa, pb, src = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        p, z, info = np.zeros((3, n)), np.zeros((3, n)), np.zeros((6, ni.value if n else 0))
+        rc = lib().cugo_graph_get_flat_point_pair_edges(self._g, n, _p(pa, _i32p), _p(pb, _i32p), _p(src, _i32p), _p(p, _f64p),
+                                                        _p(z, _f64p), _p(info, _f64p), C.byref(ni))
+        if rc < 0:
+            check(rc)
+        return dict(pose_a=pa, pose_b=pb, src=src, p=p, z=z, info=info, n_info=ni.value)
 
     def add_relpose_edges(self, pose_ids_a, pose_ids_b, q_t7, info36=None):
         """relative-pose SE(3) edges (an extension; RelPoseEdgeSet): residual [Log_SO3(R_D); t_D] of D = T_a T_b^-1 Z^-1

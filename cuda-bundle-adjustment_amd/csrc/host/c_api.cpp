@@ -11,6 +11,7 @@
 #include "../../include/icp_types.h"
 #include "../../include/landmark_prior_types.h"
 #include "../../include/point_edge_types.h"
+#include "../../include/point_pair_types.h"
 #include "../../include/prior_types.h"
 #include "../../include/relpose_types.h"
 #include "../kernels/kernels.h"
@@ -20,6 +21,7 @@
 #include "hip_util.h"
 #include "rccl_comm.h"
 #include "plcov_plan.h"
+#include "point_pair_plan.h"
 #include "relpose_plan.h"
 #include "schur_plan.h"
 
@@ -733,6 +735,205 @@ int cugo_relpose_add_offdiag_schur(cugo_ctx* ctx, const cugo_relpose_edges* ev, 
     });
 }
 
+} // extern "C"
+
+// the plan of a set of pose-pose point edges: the host plan (point_pair_plan.h) and, with a context, its copy on the
+// device and the scratch of the set's passes (partials, chunk totals, the flag of the index check)
+struct cugo_point_pair_plan
+{
+    cugo_host::PointPairPlanHost host;
+    bool on_device = false, has_pattern = false;
+    cugo_host::DevBuf<int32_t> edge_run, run_ptr, run_a, run_b, run_flags, inc_ptr, inc, blk_id, blk_ptr, blk_run;
+    mutable cugo_host::DevBuf<double> scratch;
+    mutable bool built = false; // the scratch holds the partials of a build pass
+    int n_runs() const { return (int)host.run_a.size(); }
+    cugo_k::PointPairPlanDev dev() const
+    {
+        return {host.n,         n_runs(),     host.n_poses_free, (int)host.blk_id.size(), edge_run.data(), run_ptr.data(),
+                run_a.data(),   run_b.data(), run_flags.data(),  inc_ptr.data(),          inc.data(),      blk_id.data(),
+                blk_ptr.data(), blk_run.data()};
+    }
+    cugo_k::PointPairScratch pair_scratch() const
+    {
+        return cugo_k::point_pair_scratch_in({scratch.data(), scratch.size()}, host.n, n_runs());
+    }
+};
+
+namespace
+{
+// counts against the plan, arrays, kernel code on the host; with check_indices, pose a / b of every edge against the
+// plan's runs on the device
+cugo_k::PointPairScratch check_point_pair(cugo_ctx* ctx, const cugo_point_pair_edges* ev, bool check_indices = true)
+{
+    if (!ctx)
+        throw std::runtime_error("cugo_point_pair: no context");
+    if (!ev || !ev->plan)
+        throw std::runtime_error("cugo_point_pair: no edges or no plan (cugo_point_pair_plan_create)");
+    const cugo_host::PointPairPlanHost& h = ev->plan->host;
+    if (ev->n != h.n || ev->n_poses_total != h.n_poses_total || ev->n_poses_free != h.n_poses_free)
+        throw std::runtime_error("cugo_point_pair: the pose or edge counts are not those of the plan");
+    if (!ev->plan->on_device)
+        throw std::runtime_error("cugo_point_pair: the plan is host-only (created without a context)");
+    if (!ev->plan->has_pattern)
+        throw std::runtime_error("cugo_point_pair: the plan was built without a pattern");
+    if (ev->rk < CUGO_RK_NONE || ev->rk > CUGO_RK_HUBER || (ev->rk != CUGO_RK_NONE && !(ev->delta > 0.0 && std::isfinite(ev->delta))))
+        throw std::runtime_error("cugo_point_pair: unknown robust kernel or bad delta");
+    if (ev->n > 0 && (!ev->d_pose_a || !ev->d_pose_b || !ev->d_p || !ev->d_z || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
+        throw std::runtime_error("cugo_point_pair: missing arrays, or n_info is neither n nor 1");
+    const cugo_k::PointPairScratch rs = ev->plan->pair_scratch();
+    if (check_indices &&
+        cugo_k::point_pair_check_indices(ctx->stream, *ev, ev->plan->dev(),
+                                         reinterpret_cast<int*>(ev->plan->scratch.data() + cugo_k::point_pair_scratch_doubles(h.n, ev->plan->n_runs()))))
+        throw std::runtime_error("cugo_point_pair: pose a or pose b of an edge is not that of its run: the edges are not in the plan's order");
+    return rs;
+}
+void point_pair_build(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses, cugo_k::PointPairScratch rs)
+{
+    if (!d_poses)
+        throw std::runtime_error("cugo_point_pair: missing poses");
+    ev->plan->built = false;
+    cugo_k::launch_point_pair_chunks(ctx->stream, *ev, ev->plan->dev(), d_poses, true, rs);
+    ev->plan->built = true;
+}
+void point_pair_chi_total(cugo_ctx* ctx, const cugo_point_pair_edges* ev, cugo_k::PointPairScratch rs, double* d_chi)
+{
+    if (!d_chi)
+        return;
+    if (ev->n > 0)
+        cugo_k::launch_point_pair_chi_total(ctx->stream, *ev, rs, d_chi, false);
+    else
+        CUGO_HIP(hipMemsetAsync(d_chi, 0, sizeof(double), ctx->stream));
+}
+bool joins_free_poses(const cugo_point_pair_edges* ev) { return !ev->plan->host.blk_id.empty(); }
+} // namespace
+
+extern "C" {
+
+int cugo_point_pair_plan_create(cugo_ctx* ctx, int n, int n_poses_total, int n_poses_free, const int32_t* h_pose_a,
+                                const int32_t* h_pose_b, const uint8_t* h_flags, const int32_t* h_rowptr,
+                                const int32_t* h_colind, cugo_point_pair_plan** out)
+{
+    return guarded([&] {
+        if (!out)
+            throw std::runtime_error("cugo_point_pair_plan_create: null argument");
+        *out = nullptr;
+        if (n > (1 << 26))
+            throw std::runtime_error("cugo_point_pair_plan_create: more than 2^26 edges");
+        auto p = std::make_unique<cugo_point_pair_plan>();
+        cugo_host::build_point_pair_plan(n, n_poses_total, n_poses_free, h_pose_a, h_pose_b, h_flags, h_rowptr, h_colind, p->host);
+        p->has_pattern = h_rowptr != nullptr;
+        if (ctx)
+        {
+            const cugo_host::PointPairPlanHost& h = p->host;
+            p->edge_run.upload(h.edge_run, ctx->stream);
+            p->run_ptr.upload(h.run_ptr, ctx->stream);
+            p->run_a.upload(h.run_a, ctx->stream);
+            p->run_b.upload(h.run_b, ctx->stream);
+            p->run_flags.upload(h.run_flags, ctx->stream);
+            p->inc_ptr.upload(h.inc_ptr, ctx->stream);
+            p->inc.upload(h.inc, ctx->stream);
+            p->blk_id.upload(h.blk_id, ctx->stream);
+            p->blk_ptr.upload(h.blk_ptr, ctx->stream);
+            p->blk_run.upload(h.blk_run, ctx->stream);
+            p->scratch.resize(cugo_k::point_pair_scratch_doubles(n, p->n_runs()) + 16); // (+ the flag of the index check)
+            CUGO_HIP(hipStreamSynchronize(ctx->stream));
+            p->on_device = true;
+        }
+        *out = p.release();
+    });
+}
+void cugo_point_pair_plan_destroy(cugo_point_pair_plan* plan) { delete plan; }
+
+int cugo_point_pair_plan_array(const cugo_point_pair_plan* plan, const char* name, const int32_t** out)
+{
+    if (!plan || !name || !out)
+        return CUGO_ERR_INVALID;
+    const cugo_host::PointPairPlanHost& h = plan->host;
+    const std::pair<const char*, const std::vector<int32_t>*> arrays[] = {
+        {"perm", &h.perm},       {"edge_run", &h.edge_run}, {"run_ptr", &h.run_ptr}, {"run_a", &h.run_a},   {"run_b", &h.run_b},
+        {"run_flags", &h.run_flags}, {"run_blk", &h.run_blk}, {"inc_ptr", &h.inc_ptr}, {"inc", &h.inc},       {"blk_id", &h.blk_id},
+        {"blk_ptr", &h.blk_ptr}, {"blk_run", &h.blk_run},   {"pair_lo", &h.pair_lo}, {"pair_hi", &h.pair_hi}};
+    for (const auto& a : arrays)
+        if (std::string(name) == a.first)
+        {
+            *out = a.second->data();
+            return (int)a.second->size();
+        }
+    set_last_error(std::string("cugo_point_pair_plan_array: unknown array ") + name);
+    return CUGO_ERR_INVALID;
+}
+
+int cugo_point_pair_compute_errors(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses, double* d_chi,
+                                   double* d_edge_chi)
+{
+    return guarded([&] {
+        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev);
+        if (!d_poses)
+            throw std::runtime_error("cugo_point_pair: missing poses");
+        cugo_k::launch_point_pair_chunks(ctx->stream, *ev, ev->plan->dev(), d_poses, false, rs, d_edge_chi);
+        point_pair_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_point_pair_construct_quadratic_form(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
+                                             double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev);
+        if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
+            throw std::runtime_error("cugo_point_pair: missing Hpp or bp");
+        if (!d_Hoff && joins_free_poses(ev))
+            throw std::runtime_error("cugo_point_pair: missing Hoff (a counting run joins two free poses)");
+        point_pair_build(ctx, ev, d_poses, rs);
+        cugo_k::launch_point_pair_add(ctx->stream, *ev, ev->plan->dev(), rs, d_Hpp, d_bp, d_Hoff);
+        point_pair_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_point_pair_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
+                                                   const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
+                                                   double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev);
+        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
+            throw std::runtime_error("cugo_point_pair: missing rowptr, Hsc, bp or bsc");
+        point_pair_build(ctx, ev, d_poses, rs);
+        cugo_k::launch_point_pair_add_schur(ctx->stream, *ev, ev->plan->dev(), rs, d_rowptr, d_Hsc, d_bp, d_bsc);
+        point_pair_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_point_pair_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
+                                                  double* d_Hpp, double* d_bp, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev);
+        if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
+            throw std::runtime_error("cugo_point_pair: missing Hpp or bp");
+        point_pair_build(ctx, ev, d_poses, rs);
+        cugo_k::launch_point_pair_add_diag(ctx->stream, *ev, ev->plan->dev(), rs, d_Hpp, d_bp);
+        point_pair_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
+int cugo_point_pair_add_offdiag_schur(cugo_ctx* ctx, const cugo_point_pair_edges* ev, double* d_Hsc)
+{
+    return guarded([&] {
+        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev, false); // (the build pass checked the indices)
+        if (!ev->plan->built)
+            throw std::runtime_error("cugo_point_pair_add_offdiag_schur: no build pass has left its partials in the plan's scratch");
+        if (!d_Hsc)
+            throw std::runtime_error("cugo_point_pair: missing Hsc");
+        cugo_k::launch_point_pair_add_offdiag(ctx->stream, *ev, ev->plan->dev(), rs, d_Hsc);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+
 int cugo_max_diagonal(cugo_ctx* ctx, const double* d_Hpp, int nP, const double* d_Hll, int nL,
                       double* d_out)
 {
@@ -1239,6 +1440,8 @@ struct cugo_graph
     std::deque<cugo::DepthEdge> depth_store;
     cugo::PointEdgeSet point;
     std::deque<cugo::PointEdge> point_store;
+    cugo::PointPairEdgeSet point_pair;
+    std::deque<cugo::PointPairEdge> point_pair_store;
     bool attached = false;
     void attach()
     {
@@ -1255,6 +1458,7 @@ struct cugo_graph
         opt->addEdgeSet(&lm_prior);
         opt->addEdgeSet(&depth); // (behind the others: the indices of the other sets in messages stay what they were)
         opt->addEdgeSet(&point); // (likewise)
+        opt->addEdgeSet(&point_pair);
         attached = true;
     }
 };
@@ -1829,6 +2033,85 @@ int cugo_graph_get_flat_point_edges(cugo_graph* g, int cap, int32_t* pose, int32
             return;
         if (pose)
             std::copy(q.begin(), q.end(), pose);
+        if (src_edge)
+            std::copy(s.begin(), s.end(), src_edge);
+        if (p)
+            std::copy(vp.begin(), vp.end(), p);
+        if (z)
+            std::copy(vz.begin(), vz.end(), z);
+        if (info && n > 0)
+            std::copy(vi.begin(), vi.end(), info);
+    });
+    return rc == CUGO_OK ? n : rc;
+}
+int cugo_graph_add_point_pair_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b,
+                                    const double* pointP, const double* pointZ, const double* info9)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids_a || !pose_ids_b || !pointP || !pointZ)))
+            throw std::invalid_argument("cugo_graph_add_point_pair_edges: missing arrays");
+        for (int i = 0; i < n; i++) // (all or nothing: an unknown id or a == b adds no edge)
+        {
+            (void)icp_pose(g, pose_ids_a[i]), (void)icp_pose(g, pose_ids_b[i]);
+            if (pose_ids_a[i] == pose_ids_b[i])
+                throw std::invalid_argument("cugo_graph_add_point_pair_edges: edge " + std::to_string(i) + " joins pose " +
+                                            std::to_string(pose_ids_a[i]) + " to itself (a == b)");
+        }
+        for (int i = 0; i < n; i++)
+        {
+            g->point_pair_store.emplace_back();
+            cugo::PointPairEdge& e = g->point_pair_store.back();
+            e.setVertex(icp_pose(g, pose_ids_a[i]), 0);
+            e.setVertex(icp_pose(g, pose_ids_b[i]), 1);
+            e.setMeasurement(cugo::PointToPointMatch<double>(pointP + 3 * (size_t)i, pointZ + 3 * (size_t)i,
+                                                             info9 ? info9 + 9 * (size_t)i : g->point_pair.informationMatrix()));
+            g->point_pair.addEdge(&e);
+        }
+    });
+}
+int cugo_graph_set_point_pair_information(cugo_graph* g, const double* info9)
+{
+    return guarded([&] {
+        if (!info9)
+            throw std::invalid_argument("cugo_graph_set_point_pair_information: no matrix");
+        g->point_pair.setInformationMatrix(info9);
+    });
+}
+int cugo_graph_set_point_pair_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    return guarded([&] { g->point_pair.setRobustKernel(rk_type_of(type), delta); });
+}
+int cugo_graph_set_point_pair_outlier_threshold(cugo_graph* g, double threshold)
+{
+    return guarded([&] { g->point_pair.setOutlierThreshold(threshold); });
+}
+int cugo_graph_set_point_pair_active(cugo_graph* g, int first, int n, const uint8_t* active)
+{
+    return guarded([&] {
+        if (first < 0 || n < 0 || (size_t)first + (size_t)n > g->point_pair_store.size() || (n > 0 && !active))
+            throw std::invalid_argument("cugo_graph_set_point_pair_active: bad edge range or no flags");
+        for (int i = 0; i < n; i++)
+            active[i] ? g->point_pair_store[(size_t)first + i].setActive() : g->point_pair_store[(size_t)first + i].inactivate();
+    });
+}
+int cugo_graph_n_point_pair_edges(cugo_graph* g) { return g->opt->nPointPairEdges(); }
+int cugo_graph_get_flat_point_pair_edges(cugo_graph* g, int cap, int32_t* pose_a, int32_t* pose_b, int32_t* src_edge, double* p,
+                                         double* z, double* info, int* n_info)
+{
+    int n = -1;
+    const int rc = guarded([&] {
+        std::vector<int> a, b, s;
+        std::vector<double> vp, vz, vi;
+        const int ni = g->opt->flatPointPairEdges(a, b, s, vp, vz, vi);
+        n = (int)a.size();
+        if (n_info)
+            *n_info = ni;
+        if (cap < n)
+            return;
+        if (pose_a)
+            std::copy(a.begin(), a.end(), pose_a);
+        if (pose_b)
+            std::copy(b.begin(), b.end(), pose_b);
         if (src_edge)
             std::copy(s.begin(), s.end(), src_edge);
         if (p)

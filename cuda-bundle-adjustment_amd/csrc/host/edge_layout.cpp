@@ -1,6 +1,7 @@
 // Host-only layout of a flattened graph (edge_layout.h).
 // ref: src/optimisable_graph.hpp:474-572 (EdgeSet::init), src/sparse_block_matrix.cpp:63-156 (Hsc pattern).
 #include "edge_layout.h"
+#include "point_pair_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -421,6 +422,16 @@ void sort_pose_edges_by_pose(const FlatPoseKind& fk, int Pall, int P, PoseKindHo
     std::vector<int32_t> pos(b.h_ptr.begin(), b.h_ptr.end() - 1), slot_of(n);
     for (int e = 0; e < n; e++) // container order inside a pose: the summation order depends on the graph alone
         slot_of[e] = pos[fk.pose[e]]++;
+    copy_pose_edges_planar(fk, slot_of.data(), b);
+}
+
+void sort_pose_edges_by_pair(const FlatPoseKind& fk, int Pall, int P, PointPairPlanHost& plan, PoseKindHost& b)
+{
+    const int n = fk.n();
+    build_point_pair_plan(n, Pall, P, fk.pose.data(), fk.pose_b.data(), nullptr, nullptr, nullptr, plan);
+    std::vector<int32_t> slot_of((size_t)n);
+    for (int i = 0; i < n; i++)
+        slot_of[(size_t)plan.perm[i]] = i;
     copy_pose_edges_planar(fk, slot_of.data(), b);
 }
 

@@ -74,6 +74,10 @@ void copy_pose_edges_planar(const FlatPoseKind& kind, const int32_t* slot_of, Po
 // a unary kind sorted by pose (stable: container order inside a pose), with the CSR h_ptr over all Pall poses; throws
 // on an edge that is not on a free pose
 void sort_pose_edges_by_pose(const FlatPoseKind& kind, int Pall, int P, PoseKindHost& out);
+// the pose-pose point kind sorted into the runs of its plan (point_pair_plan.h: by (lo, hi, orientation), stable: container
+// order inside a run).  The sort needs no pattern: `plan` comes back built without one
+struct PointPairPlanHost;
+void sort_pose_edges_by_pair(const FlatPoseKind& kind, int Pall, int P, PointPairPlanHost& plan, PoseKindHost& out);
 
 // ---- the Hsc structure on the host: pattern (upper block CSR, diagonal first) and, from the LOCAL slots, the
 // contributions of the off-diagonal blocks (ascending landmark inside a block).  use_plan() is asked once the pattern

@@ -21,6 +21,7 @@
 #include "options.h"
 #include "rccl_comm.h"
 #include "plcov_plan.h"
+#include "point_pair_plan.h"
 #include "relpose_plan.h"
 #include "schur_plan.h"
 #include "structure_gpu.h"
@@ -99,7 +100,8 @@ struct Engine::Impl : cugo_k::LaunchHook
     int Etot = 0;
     // global co-visibility: free landmark -> sorted free poses (free-free active edges, all shards)
     std::vector<int32_t> cov_ptr, cov_pose;
-    // The distinct (lo, hi) pairs of free poses that a counting relative-pose edge joins, ascending: each is a block of the
+    // The distinct (lo, hi) pairs of free poses that a counting relative-pose or pose-pose point edge joins (the union of
+    // the two kinds: a pair joined by both is one block every contributor adds into), ascending: each is a block of the
     // Hsc pattern whether or not the two poses share a landmark.  For the pattern alone a pair is a landmark seen by
     // exactly two poses: aug_* are the co-visibility lists with one such entry appended per pair (empty without pairs).
     // They feed the pattern builders only; products, contribution lists and sharding come from the real lists.
@@ -107,12 +109,13 @@ struct Engine::Impl : cugo_k::LaunchHook
     const std::vector<int32_t>& pat_ptr() const { return pair_lo.empty() ? cov_ptr : aug_ptr; }
     const std::vector<int32_t>& pat_pose() const { return pair_lo.empty() ? cov_pose : aug_pose; }
     int pat_lists() const { return L + (int)pair_lo.size(); }
-    void build_pair_lists(const FlatPoseKind& fr)
+    void build_pair_lists(const FlatPoseKind& fr, const FlatPoseKind& fp)
     {
         std::vector<std::pair<int32_t, int32_t>> pr;
-        for (int e = 0; e < fr.n(); e++)
-            if (fr.pose[e] < P && fr.pose_b[e] < P)
-                pr.emplace_back(std::min(fr.pose[e], fr.pose_b[e]), std::max(fr.pose[e], fr.pose_b[e]));
+        for (const FlatPoseKind* k : {&fr, &fp})
+            for (int e = 0; e < k->n(); e++)
+                if (k->pose[e] < P && k->pose_b[e] < P)
+                    pr.emplace_back(std::min(k->pose[e], k->pose_b[e]), std::max(k->pose[e], k->pose_b[e]));
         std::sort(pr.begin(), pr.end());
         pr.erase(std::unique(pr.begin(), pr.end()), pr.end());
         pair_lo.clear(), pair_hi.clear(), aug_ptr.clear(), aug_pose.clear();
@@ -170,10 +173,12 @@ struct Engine::Impl : cugo_k::LaunchHook
     // the relative-pose edges in container order with a plan (relpose_plan.h) against the Hsc pattern in place of a
     // sort; the views the kernels take; and a scratch of their own (the BA scratch holds live scale / chi2 partials and
     // records across the same span of the stream):
-    //     [point partials | ICP partials | ICP chunk chi2 totals | point chunk chi2 totals | prior workgroup chi2 totals |
-    //      relative-pose workgroup chi2 totals | landmark-prior workgroup chi2 totals | 16 doubles of slack]
-    // (the point-to-point edges, point_kernels.hip, are a fifth kind on the machinery of the ICP kinds; without them
-    // their two runs are empty and the layout is what it was)
+    //     [pair partials | point partials | ICP partials | ICP chunk chi2 totals | point chunk chi2 totals | prior workgroup
+    //      chi2 totals | relative-pose workgroup chi2 totals | landmark-prior workgroup chi2 totals | pair chunk chi2 totals |
+    //      16 doubles of slack]
+    // (the point-to-point edges, point_kernels.hip, are a fifth kind on the machinery of the ICP kinds, the pose-pose
+    // point edges, point_pair_kernels.hip, a sixth with a plan of their own (point_pair_plan.h); without a kind its runs
+    // are empty and the layout is what it was)
     // The landmark position priors (FlatGraph::lm_priors, lm_prior_kernels.hip) sit on landmarks, not poses, but their
     // chi2 travels the same way, so they live here too: sorted by landmark (stable) with a CSR over all landmarks,
     // planar on the device.  Their terms ride in the BA build pass (launch_build with the view); only the chi2 has
@@ -191,12 +196,14 @@ struct Engine::Impl : cugo_k::LaunchHook
         cugo_prior_edges prior{};
         cugo_relpose_edges relpose{};
         cugo_point_edges point{};
-        int n_icp = 0, n_prior = 0, n_relpose = 0, n_point = 0;
-        // totals an ICP pass / a point pass / a prior pass / a relative-pose pass leaves (0: the pass is not launched)
-        int n_icp_chi = 0, n_point_chi = 0, n_prior_wg = 0, n_relpose_wg = 0;
+        cugo_point_pair_edges pair{}; // (its plan member stays null: the launchers take the device plan)
+        int n_icp = 0, n_prior = 0, n_relpose = 0, n_point = 0, n_pair = 0;
+        // totals an ICP pass / a point pass / a prior pass / a relative-pose pass / a pair pass leaves (0: the pass is not launched)
+        int n_icp_chi = 0, n_point_chi = 0, n_prior_wg = 0, n_relpose_wg = 0, n_pair_chi = 0;
         DevBuf<double> d_scratch;
         // the layout above, set by bind()
-        size_t off_icp = 0, off_icp_chi = 0, off_point_chi = 0, off_prior_chi = 0, off_relpose_chi = 0, off_lm_prior_chi = 0;
+        size_t off_point = 0, off_icp = 0, off_icp_chi = 0, off_point_chi = 0, off_prior_chi = 0, off_relpose_chi = 0,
+               off_lm_prior_chi = 0, off_pair_chi = 0;
         // landmark position priors: sorted host copies (h_lmp_lm, h_lmp_ptr: what initialize() checks against the slot
         // layout), the device arrays, the view
         std::vector<int32_t> h_lmp_lm, h_lmp_ptr;
@@ -255,9 +262,17 @@ struct Engine::Impl : cugo_k::LaunchHook
         {
             DevBuf<int32_t> d_inc_ptr, d_inc, d_off_blk;
             RelPosePlanHost plan;
-            bool plan_dirty = true; // the plan is not that of the edges and the Hsc pattern at hand
+            bool plan_dirty = true; // the plans (this one and the pair kind's) are not those of the edges and the Hsc pattern at hand
             cugo_k::RelPosePlanDev dev{};
         } rp;
+        // the plan of the pose-pose point edges (point_pair_plan.h): bind() sorts the edges by it (no pattern is needed
+        // for the sort), bind_relpose_plan() rebuilds it against the Hsc pattern for the block indices
+        struct PairPlan
+        {
+            DevBuf<int32_t> d_edge_run, d_run_ptr, d_run_a, d_run_b, d_run_flags, d_inc_ptr, d_inc, d_blk_id, d_blk_ptr, d_blk_run;
+            PointPairPlanHost plan;
+            cugo_k::PointPairPlanDev dev{};
+        } pp;
         // Outlier rejection (Engine::reject_pose_outliers), per kind and only for a kind in which some threshold is
         // positive: the run-time flags the kind's view points at (all zero until edges go), a host copy of them, and the
         // thresholds in the order of the edges on the device (n or 1).  Every other kind keeps a NULL flag pointer in its
@@ -300,14 +315,15 @@ struct Engine::Impl : cugo_k::LaunchHook
         double* relpose_chi() { return d_scratch.data() + off_relpose_chi; }
 
         cugo_k::ReduceScratch icp_rs() { return {d_scratch.data() + off_icp, d_scratch.size() - off_icp}; }
-        cugo_k::PointScratch point_rs() { return {d_scratch.data(), d_scratch.data() + off_point_chi}; }
+        cugo_k::PointScratch point_rs() { return {d_scratch.data() + off_point, d_scratch.data() + off_point_chi}; }
+        cugo_k::PointPairScratch pair_rs() { return {d_scratch.data(), d_scratch.data() + off_pair_chi}; }
         double* prior_chi() { return d_scratch.data() + off_prior_chi; }
         int n_edges(int k) const { return (int)kind[k].h_pose.size(); }
         const std::vector<int32_t>& icp_slot_source(int k, bool set) const { return set ? kind[k].slot_set : kind[k].slot_edge; }
         // the chi2 totals of the last ICP, point, prior and relative-pose pass, one array; nullptr / 0 without such edges
         const double* chi_totals(int* n)
         {
-            *n = n_icp_chi + n_point_chi + n_prior_wg + n_relpose_wg + n_lm_prior_wg;
+            *n = n_icp_chi + n_point_chi + n_prior_wg + n_relpose_wg + n_lm_prior_wg + n_pair_chi;
             return *n ? d_scratch.data() + off_icp_chi : nullptr;
         }
 
@@ -318,15 +334,17 @@ struct Engine::Impl : cugo_k::LaunchHook
             bind_lm_priors(g.lm_priors, Lall, L, stream, plan_only);
             n_icp = g.kinds[POSE_KIND_PLANE].n() + g.kinds[POSE_KIND_LINE].n();
             n_prior = g.kinds[POSE_KIND_PRIOR].n(), n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
-            n_point = g.kinds[POSE_KIND_POINT].n();
+            n_point = g.kinds[POSE_KIND_POINT].n(), n_pair = g.kinds[POSE_KIND_PAIR].n();
             for (int k = 0; k < POSE_KIND_COUNT; k++)
             {
                 KindBufs& b = kind[k];
-                const bool binary = k == POSE_KIND_RELPOSE, is_icp = k == POSE_KIND_PLANE || k == POSE_KIND_LINE;
+                const bool binary = k == POSE_KIND_RELPOSE || k == POSE_KIND_PAIR, is_icp = k == POSE_KIND_PLANE || k == POSE_KIND_LINE;
                 if (!binary)
                     sort_pose_edges_by_pose(g.kinds[k], Pall, P, b);
-                else if (n_relpose > (1 << 26))
-                    throw std::runtime_error("cugo: more than 2^26 relative-pose edges");
+                else if (g.kinds[k].n() > (1 << 26))
+                    throw std::runtime_error(std::string("cugo: more than 2^26 ") + pose_kind_name(k) + " edges");
+                else if (k == POSE_KIND_PAIR)
+                    sort_pose_edges_by_pair(g.kinds[k], Pall, P, pp.plan, b);
                 else
                     copy_pose_edges_planar(g.kinds[k], nullptr, b);
                 // an empty kind uploads nothing, except that k_icp_finish reads the pose_ptr of BOTH ICP kinds whenever
@@ -375,8 +393,19 @@ struct Engine::Impl : cugo_k::LaunchHook
             point.d_info = pt.d_weight.data(), point.n_info = pt.n_weight;
             point.rk = g.kinds[POSE_KIND_POINT].rk, point.delta = g.kinds[POSE_KIND_POINT].delta;
             bind_reject(POSE_KIND_POINT, stream, plan_only); // (never on: graph_optimisation.cpp refuses a threshold on the kind)
-            // the scratch layout (the chunk totals end the ICP part; the point totals follow them)
-            off_icp = n_point ? cugo_k::point_partial_doubles(point) : 0;
+            const KindBufs& pa = kind[POSE_KIND_PAIR];
+            pair = cugo_point_pair_edges{};
+            pair.n_poses_total = Pall, pair.n_poses_free = P, pair.n = n_pair;
+            pair.d_pose_a = pa.d_pose.data(), pair.d_pose_b = pa.d_pose_b.data();
+            pair.d_p = pa.d_meas.data(), pair.d_z = pa.d_meas.data() + 3 * (size_t)n_pair; // (planar: p [3][n], then z [3][n])
+            pair.d_info = pa.d_weight.data(), pair.n_info = pa.n_weight;
+            pair.rk = g.kinds[POSE_KIND_PAIR].rk, pair.delta = g.kinds[POSE_KIND_PAIR].delta;
+            bind_reject(POSE_KIND_PAIR, stream, plan_only); // (never on, as for the point kind)
+            // the scratch layout (the pair partials lead; the chunk totals end the ICP part; the point totals follow them)
+            const int n_pair_runs = (int)pp.plan.run_a.size();
+            off_point = n_pair ? cugo_k::point_pair_partial_doubles(n_pair, n_pair_runs) : 0;
+            n_pair_chi = n_pair ? cugo_k::point_pair_chunk_count(n_pair) : 0;
+            off_icp = off_point + (n_point ? cugo_k::point_partial_doubles(point) : 0);
             n_point_chi = n_point ? cugo_k::point_chunk_count(point) : 0;
             const size_t icp_doubles = n_icp ? cugo_k::icp_scratch_doubles(icp) : 0;
             n_icp_chi = n_icp ? cugo_k::icp_chunk_count(icp) : 0;
@@ -385,8 +414,9 @@ struct Engine::Impl : cugo_k::LaunchHook
             off_prior_chi = off_point_chi + (size_t)n_point_chi;
             off_relpose_chi = off_prior_chi + (size_t)n_prior_wg;
             off_lm_prior_chi = off_relpose_chi + (size_t)n_relpose_wg;
-            if ((n_icp || n_point || n_prior_wg || n_relpose_wg || n_lm_prior_wg) && !plan_only)
-                d_scratch.resize(off_lm_prior_chi + (size_t)n_lm_prior_wg + 16);
+            off_pair_chi = off_lm_prior_chi + (size_t)n_lm_prior_wg;
+            if ((n_icp || n_point || n_prior_wg || n_relpose_wg || n_lm_prior_wg || n_pair) && !plan_only)
+                d_scratch.resize(off_pair_chi + (size_t)n_pair_chi + 16);
         }
         // the plan against the Hsc pattern at hand (upper block CSR over the free poses): the engine made the pattern
         // from these very pairs, so a pair missing from it is a defect of the engine and throws
@@ -396,6 +426,35 @@ struct Engine::Impl : cugo_k::LaunchHook
             if (!rp.plan_dirty)
                 return;
             rp.plan_dirty = false;
+            if (n_pair)
+            { // (the edges are in the plan's order already: the sort of sorted edges is the identity)
+                KindBufs& pa = kind[POSE_KIND_PAIR];
+                build_point_pair_plan(n_pair, pair.n_poses_total, pair.n_poses_free, pa.h_pose.data(), pa.h_pose_b.data(), nullptr,
+                                      rowptr.data(), colind.data(), pp.plan);
+                if (!plan_only)
+                {
+                    const PointPairPlanHost& h = pp.plan;
+                    pp.d_edge_run.upload(h.edge_run, stream), pp.d_run_ptr.upload(h.run_ptr, stream);
+                    pp.d_run_a.upload(h.run_a, stream), pp.d_run_b.upload(h.run_b, stream), pp.d_run_flags.upload(h.run_flags, stream);
+                    pp.d_inc_ptr.upload(h.inc_ptr, stream), pp.d_inc.upload(h.inc, stream);
+                    pp.d_blk_id.upload(h.blk_id, stream), pp.d_blk_ptr.upload(h.blk_ptr, stream), pp.d_blk_run.upload(h.blk_run, stream);
+                    CUGO_HIP(hipStreamSynchronize(stream));
+                    pp.dev = cugo_k::PointPairPlanDev{n_pair,
+                                                      (int)h.run_a.size(),
+                                                      pair.n_poses_free,
+                                                      (int)h.blk_id.size(),
+                                                      pp.d_edge_run.data(),
+                                                      pp.d_run_ptr.data(),
+                                                      pp.d_run_a.data(),
+                                                      pp.d_run_b.data(),
+                                                      pp.d_run_flags.data(),
+                                                      pp.d_inc_ptr.data(),
+                                                      pp.d_inc.data(),
+                                                      pp.d_blk_id.data(),
+                                                      pp.d_blk_ptr.data(),
+                                                      pp.d_blk_run.data()};
+                }
+            }
             if (!n_relpose)
                 return;
             KindBufs& rl = kind[POSE_KIND_RELPOSE];
@@ -435,6 +494,14 @@ struct Engine::Impl : cugo_k::LaunchHook
                 if (d_chi)
                     cugo_k::launch_point_chi_total(s, point, point_rs(), d_chi, true);
             }
+            if (n_pair)
+            { // the chunk pass of the four roles; the diagonal sums here or, with the off-diagonal ones, behind the Schur pass
+                cugo_k::launch_point_pair_chunks(s, pair, pp.dev, poses, true, pair_rs());
+                if (!one_stream)
+                    cugo_k::launch_point_pair_add_diag(s, pair, pp.dev, pair_rs(), Hpp, bp);
+                if (d_chi)
+                    cugo_k::launch_point_pair_chi_total(s, pair, pair_rs(), d_chi, true);
+            }
             if (n_prior_wg)
             {
                 if (!one_stream)
@@ -466,6 +533,10 @@ struct Engine::Impl : cugo_k::LaunchHook
         {
             if (n_relpose_wg)
                 cugo_k::launch_relpose_add_offdiag(s, relpose, rp.dev, poses, Hsc);
+            // (the pair kind adds the sums of the PARTIALS of the build pass at hand: queue_build wrote them with the H the
+            //  Schur pass has just consumed, and no error pass writes them)
+            if (n_pair)
+                cugo_k::launch_point_pair_add_offdiag(s, pair, pp.dev, pair_rs(), Hsc);
         }
         // one-stream form: the terms added to the diagonal blocks of Hsc, to bp and to bsc behind k_pose_schur (the
         // totals the prior launch leaves are those of the estimates at `poses` once more)
@@ -479,6 +550,8 @@ struct Engine::Impl : cugo_k::LaunchHook
                 cugo_k::launch_prior_add_schur(s, prior, poses, rowptr, Hsc, bp, bsc, prior_chi());
             if (n_relpose_wg)
                 cugo_k::launch_relpose_add_schur(s, relpose, rp.dev, poses, rowptr, Hsc, bp, bsc, relpose_chi());
+            if (n_pair)
+                cugo_k::launch_point_pair_add_schur(s, pair, pp.dev, pair_rs(), rowptr, Hsc, bp, bsc);
         }
         // error pass: chi_totals() at `poses` / `lms`
         void queue_errors(hipStream_t s, const double* poses, const double* lms)
@@ -493,6 +566,8 @@ struct Engine::Impl : cugo_k::LaunchHook
                 cugo_k::launch_relpose_errors(s, relpose, rp.dev, poses, relpose_chi());
             if (n_lm_prior_wg)
                 cugo_k::launch_lm_prior_errors(s, lm_prior, lms, lm_prior_chi());
+            if (n_pair)
+                cugo_k::launch_point_pair_chunks(s, pair, pp.dev, poses, false, pair_rs());
         }
     } pe;
     cugo_hsc_struct hs{};
@@ -1295,7 +1370,8 @@ void Engine::initialize(FlatGraph& g)
     m.init_rank = m.rank, m.init_world = m.world;
     m.Etot = g.n_edges();
     const int n_relpose = g.kinds[POSE_KIND_RELPOSE].n();
-    E_global_ = m.Etot + g.n_pose_edges() + n_relpose + g.lm_priors.n();
+    const int n_pair = g.kinds[POSE_KIND_PAIR].n();
+    E_global_ = m.Etot + g.n_pose_edges() + n_relpose + n_pair + g.lm_priors.n();
     refuse_unsupported(g, n_relpose, m.world > 1 || m.comm);
     // (every launcher of an edge pass picks its instantiation from this: cugo_k::edge_form)
     m.ev.has_rig = g.has_dist ? CUGO_RIG_DISTORTION : g.has_models ? CUGO_RIG_MODELS : g.has_rig ? CUGO_RIG_EXTRINSICS : CUGO_RIG_NONE;
@@ -1304,6 +1380,12 @@ void Engine::initialize(FlatGraph& g)
     if (n_relpose && m.opt.hsc_strip)
         throw std::runtime_error("cugo: relative-pose edge sets cannot be combined with CUGO_HSC_STRIP=1: the row-strip "
                                  "form of the Schur complement cannot hold a block without landmark products");
+    if (n_pair && m.opt.hsc_strip)
+        throw std::runtime_error("cugo: pose-pose point edge sets (PointPairEdgeSet) cannot be combined with CUGO_HSC_STRIP=1: "
+                                 "the row-strip form of the Schur complement cannot hold a block without landmark products");
+    if (n_pair && (m.world > 1 || m.comm))
+        throw std::runtime_error("cugo: pose-pose point edge sets (PointPairEdgeSet) are not supported on a landmark-sharded "
+                                 "(multi-GPU) optimiser yet");
     if (g.kinds[POSE_KIND_POINT].n() && (m.world > 1 || m.comm))
         throw std::runtime_error("cugo: point-to-point edge sets (PointEdgeSet) are not supported on a landmark-sharded "
                                  "(multi-GPU) optimiser yet");
@@ -1322,7 +1404,7 @@ void Engine::initialize(FlatGraph& g)
                                      " (flattened index), which no active BA edge observes; the back-substitution gives such "
                                      "a landmark a zero step (not supported)");
     build_covisibility(g, m.st_lm_cnt, m.st_order, m.cov_ptr, m.cov_pose);
-    m.build_pair_lists(g.kinds[POSE_KIND_RELPOSE]);
+    m.build_pair_lists(g.kinds[POSE_KIND_RELPOSE], g.kinds[POSE_KIND_PAIR]);
     laps.lap("engine: co-visibility");
     // the helper starts before the slot work ...
     const bool helper_started = m.start_pattern_helper(prof_);
@@ -1733,7 +1815,7 @@ void Engine::optimize(int niterations, std::vector<IterRecord>& records, bool ve
 
     if (m.structure_dirty)
         build_structure();
-    if (m.pe.n_relpose && m.pe.rp.plan_dirty)
+    if ((m.pe.n_relpose || m.pe.n_pair) && m.pe.rp.plan_dirty)
     {
         m.join_pattern(); // (the helper of initialize() writes the host pattern)
         m.pe.bind_relpose_plan(m.hsc_rowptr, m.hsc_colind, s, false);
@@ -2108,6 +2190,18 @@ int Engine::flat_point_edges(std::vector<int32_t>& pose, std::vector<int32_t>& s
     info = k.h_weight;
     return k.n_weight;
 }
+int Engine::n_point_pair_edges() const { return impl_->pe.n_pair; }
+int Engine::flat_point_pair_edges(std::vector<int32_t>& pose_a, std::vector<int32_t>& pose_b, std::vector<int32_t>& src_edge,
+                                  std::vector<double>& p, std::vector<double>& z, std::vector<double>& info) const
+{
+    const auto& k = impl_->pe.kind[POSE_KIND_PAIR];
+    const size_t n = k.h_pose.size();
+    pose_a = k.h_pose, pose_b = k.h_pose_b, src_edge = k.slot_edge;
+    p.assign(k.h_meas.begin(), k.h_meas.begin() + 3 * n); // (meas is planar: p [3][n], then z [3][n])
+    z.assign(k.h_meas.begin() + 3 * n, k.h_meas.begin() + 6 * n);
+    info = k.h_weight;
+    return k.n_weight;
+}
 int Engine::n_poses_free() const { return impl_->P; }
 int Engine::n_landmarks_free() const { return impl_->L; }
 
@@ -2140,7 +2234,7 @@ void Engine::queue_covariance_system()
     if (m.structure_dirty)
         build_structure();
     hipStream_t s = m.ctx.stream;
-    if (m.pe.n_relpose && m.pe.rp.plan_dirty)
+    if ((m.pe.n_relpose || m.pe.n_pair) && m.pe.rp.plan_dirty)
     {
         m.join_pattern(); // (the helper of initialize() writes the host pattern)
         m.pe.bind_relpose_plan(m.hsc_rowptr, m.hsc_colind, s, false);

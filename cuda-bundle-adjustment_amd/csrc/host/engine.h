@@ -28,6 +28,7 @@ enum PoseKind
     POSE_KIND_PRIOR,
     POSE_KIND_RELPOSE,
     POSE_KIND_POINT, // (unary; behind the four kinds of CUGO_POSE_KIND_*, whose values are those of this enum)
+    POSE_KIND_PAIR,  // (binary: pose-pose point edges, point_pair_types.h; internal as the point kind is)
     POSE_KIND_COUNT
 };
 struct FlatPoseKind
@@ -35,9 +36,9 @@ struct FlatPoseKind
     int kind = 0;                 // PoseKind
     int meas_w = 0, weight_w = 0; // doubles per edge: plane 7 (p, n, d) + 1, line 9 (p, a, unit direction) + 1, prior and
                                   // relative pose 7 (q x y z w, t) + 21 (upper triangle of Omega, row-major packed),
-                                  // point 6 (p, z) + 6 (upper triangle of the 3 x 3 Omega, row-major packed)
-    std::vector<int32_t> pose;    // free-first pose index per edge: always < P on a unary kind; a of a relative-pose edge
-    std::vector<int32_t> pose_b;  // relative pose: b (one of a, b may be a fixed pose, >= P); empty on the unary kinds
+                                  // point and pose-pose point 6 (p, z) + 6 (upper triangle of the 3 x 3 Omega, row-major packed)
+    std::vector<int32_t> pose;    // free-first pose index per edge: always < P on a unary kind; a of a binary edge
+    std::vector<int32_t> pose_b;  // relative pose and pose-pose point: b (one of a, b may be a fixed pose, >= P); empty on the unary kinds
     std::vector<double> meas;     // E x meas_w
     std::vector<double> weight;   // E x weight_w, or 1 x weight_w when one value serves all
     std::vector<int32_t> src_set, src_edge; // where an edge came from: edge set (position among the optimiser's edge
@@ -61,6 +62,7 @@ inline const char* pose_kind_name(int kind)
            : kind == POSE_KIND_LINE ? "point-to-line"
            : kind == POSE_KIND_PRIOR ? "pose prior"
            : kind == POSE_KIND_POINT ? "point-to-point"
+           : kind == POSE_KIND_PAIR  ? "pose-pose point"
                                      : "relative-pose";
 }
 inline const char* pose_kind_group(int kind)
@@ -68,6 +70,7 @@ inline const char* pose_kind_group(int kind)
     return kind == POSE_KIND_RELPOSE ? "relative-pose"
            : kind == POSE_KIND_PRIOR ? "pose prior"
            : kind == POSE_KIND_POINT ? "point-to-point"
+           : kind == POSE_KIND_PAIR  ? "pose-pose point"
                                      : "point-to-plane / point-to-line";
 }
 
@@ -142,7 +145,7 @@ struct FlatGraph
     FlatLmPriors lm_priors;
     FlatGraph()
     {
-        const int w[POSE_KIND_COUNT][2] = {{7, 1}, {9, 1}, {7, 21}, {7, 21}, {6, 6}};
+        const int w[POSE_KIND_COUNT][2] = {{7, 1}, {9, 1}, {7, 21}, {7, 21}, {6, 6}, {6, 6}};
         for (int k = 0; k < POSE_KIND_COUNT; k++)
             kinds[k].kind = k, kinds[k].meas_w = w[k][0], kinds[k].weight_w = w[k][1];
     }
@@ -277,7 +280,7 @@ public:
     const std::vector<double>& cov_lm() const { return cov_lm_; }
     int n_poses_free() const;
     int n_landmarks_free() const;
-    int n_active_edges() const { return E_global_; } // BA + ICP + point edges + priors (pose and landmark) + relative-pose edges of the current flattening
+    int n_active_edges() const { return E_global_; } // BA + ICP + point edges + priors (pose and landmark) + relative-pose and pose-pose point edges of the current flattening
     int n_icp_edges(int kind) const;                  // 0 plane, 1 line
     int n_prior_edges() const;
     int n_relpose_edges() const;
@@ -287,6 +290,12 @@ public:
     // the position of every edge in its set's container, p [3][n], z [3][n], info [6][n_info]; returns n_info (n or 1)
     int flat_point_edges(std::vector<int32_t>& pose, std::vector<int32_t>& src_edge, std::vector<double>& p,
                          std::vector<double>& z, std::vector<double>& info) const;
+    int n_point_pair_edges() const;
+    // Diagnostic: the pose-pose point edges of the current flattening as the kernels read them (the plan's sorted order,
+    // planar): pose a / pose b [n], the position of every edge in its set's container, p [3][n], z [3][n], info
+    // [6][n_info]; returns n_info (n or 1)
+    int flat_point_pair_edges(std::vector<int32_t>& pose_a, std::vector<int32_t>& pose_b, std::vector<int32_t>& src_edge,
+                              std::vector<double>& p, std::vector<double>& z, std::vector<double>& info) const;
     // sorted slot of a kind -> {edge set, position in the set} as FlatPoseKind recorded them (kept for a later
     // outlier rejection on these sets)
     const std::vector<int32_t>& icp_slot_source(int kind, bool set) const;

@@ -5,6 +5,7 @@
 #include "../../include/icp_types.h"
 #include "../../include/landmark_prior_types.h"
 #include "../../include/point_edge_types.h"
+#include "../../include/point_pair_types.h"
 #include "../../include/prior_types.h"
 #include "../../include/relpose_types.h"
 
@@ -84,6 +85,15 @@ int CudaGraphOptimisationImpl::flatPointEdges(std::vector<int>& pose, std::vecto
     std::vector<int32_t> q, s;
     const int n_info = engine_->flat_point_edges(q, s, p, z, info);
     pose.assign(q.begin(), q.end()), srcEdge.assign(s.begin(), s.end());
+    return n_info;
+}
+int CudaGraphOptimisationImpl::nPointPairEdges() const { return engine_->n_point_pair_edges(); }
+int CudaGraphOptimisationImpl::flatPointPairEdges(std::vector<int>& poseA, std::vector<int>& poseB, std::vector<int>& srcEdge,
+                                                  std::vector<double>& p, std::vector<double>& z, std::vector<double>& info) const
+{
+    std::vector<int32_t> a, b, s;
+    const int n_info = engine_->flat_point_pair_edges(a, b, s, p, z, info);
+    poseA.assign(a.begin(), a.end()), poseB.assign(b.begin(), b.end()), srcEdge.assign(s.begin(), s.end());
     return n_info;
 }
 void CudaGraphOptimisationImpl::flatEdges(std::vector<int>& pose, std::vector<int>& landmark,
@@ -621,8 +631,9 @@ void CudaGraphOptimisationImpl::initialize()
     // the flattened order is exactly the container order.
     size_t cap = 0;
     g.has_depth = false, g.rk_type_depth = CUGO_RK_NONE, g.rk_delta_depth = 1.0, g.depth_weight = 1.0;
-    for (BaseEdgeSet* es : edgeSets) // (a LandmarkPriorEdgeSet or PointEdgeSet is 3-d like a stereo set: the type tells them apart)
-        if (es->dim() != 1 && es->dim() != 6 && !dynamic_cast<LandmarkPriorEdgeSet*>(es) && !dynamic_cast<PointEdgeSet*>(es))
+    for (BaseEdgeSet* es : edgeSets) // (a LandmarkPriorEdgeSet, PointEdgeSet or PointPairEdgeSet is 3-d like a stereo set: the type tells them apart)
+        if (es->dim() != 1 && es->dim() != 6 && !dynamic_cast<LandmarkPriorEdgeSet*>(es) && !dynamic_cast<PointEdgeSet*>(es) &&
+            !dynamic_cast<PointPairEdgeSet*>(es))
             cap += es->nedges();
     for (cugo_host::FlatPoseKind& fk : g.kinds)
         fk.clear();
@@ -672,6 +683,22 @@ void CudaGraphOptimisationImpl::initialize()
             flattenPoseEdgeSet(
                 es, (int)si, 1, cugo_host::pose_kind_name(cugo_host::POSE_KIND_POINT), vertexSets, false,
                 g.kinds[cugo_host::POSE_KIND_POINT], poseSetEdges_[si],
+                [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
+                    pointPayload(e, setInformation, refuse, meas, weight);
+                },
+                [&] { return setInformation ? checkInformation<3>(setInformation) : nullptr; });
+            continue;
+        }
+        if (auto* pps = dynamic_cast<PointPairEdgeSet*>(es))
+        { // point_pair_types.h, an extension: by type as well; the point kind's payload and checks, two vertices
+            if (pps->getOutlierThreshold() > 0.0)
+                throw std::runtime_error("cugo: pose-pose point edge set " + std::to_string(si) +
+                                         ": outlier rejection is not supported on PointPairEdgeSet yet (setOutlierThreshold "
+                                         "must stay 0, whatever poseEdgeOutlierRejection says)");
+            const double* setInformation = options.perEdgeInformation ? nullptr : pps->informationMatrix();
+            flattenPoseEdgeSet(
+                es, (int)si, 2, cugo_host::pose_kind_name(cugo_host::POSE_KIND_PAIR), vertexSets, false,
+                g.kinds[cugo_host::POSE_KIND_PAIR], poseSetEdges_[si],
                 [&](BaseEdge* e, auto& refuse, double* meas, double* weight) {
                     pointPayload(e, setInformation, refuse, meas, weight);
                 },

@@ -300,6 +300,51 @@ void launch_relpose_add_schur(hipStream_t s, const cugo_relpose_edges& ev, const
 void launch_relpose_add_offdiag(hipStream_t s, const cugo_relpose_edges& ev, const RelPosePlanDev& plan, const double* d_poses,
                                 double* d_Hsc);
 
+// --- pose-pose point edges with 3 x 3 information (point_pair_kernels.hip) ------------------
+// the device side of a cugo_point_pair_plan (csrc/host/point_pair_plan.h)
+struct PointPairPlanDev
+{
+    int n, n_runs, n_poses_free, n_blocks; // n_blocks: pattern blocks touched
+    const int32_t* edge_run;                          // [n]
+    const int32_t *run_ptr, *run_a, *run_b, *run_flags; // [n_runs + 1], [n_runs] x 3
+    const int32_t *inc_ptr, *inc;                     // [n_poses_free + 1], run << 1 | side
+    const int32_t *blk_id, *blk_ptr, *blk_run;        // [n_blocks], [n_blocks + 1], runs of every touched block
+};
+// A chunk pass leaves its partials (point_pair_partial_doubles() doubles: four roles of chunks + runs slots) and one
+// chi2 total per chunk (point_pair_chunk_count()) where PointPairScratch says: behind one another in one scratch
+// (point_pair_scratch_in), or the totals elsewhere
+struct PointPairScratch
+{
+    double* d_part;
+    double* d_cchi;
+};
+size_t point_pair_scratch_doubles(int n, int n_runs); // partials + totals
+size_t point_pair_partial_doubles(int n, int n_runs);
+int point_pair_chunk_count(int n);
+PointPairScratch point_pair_scratch_in(ReduceScratch rs, int n, int n_runs);
+// 1 if d_pose_a / d_pose_b of an edge are not those of its run in the plan, else 0; d_bad: a device int.  Synchronises
+int point_pair_check_indices(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, int* d_bad);
+// the chunk pass — full: the partials of the four roles and chi2; otherwise chi2 only (role 0; of the partials only
+// element 27 of role 0's slots is written, which no finishing pass reads); d_edge_chi: errors only, sorted order
+void launch_point_pair_chunks(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, const double* d_poses,
+                              bool full, PointPairScratch rs, double* d_edge_chi = nullptr);
+// the sums of a full chunk pass ADDED: diagonal blocks and b to d_Hpp / d_bp, the off-diagonal blocks to d_Hoff by block
+// index if it is given ...
+void launch_point_pair_add(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+                           double* d_Hpp, double* d_bp, double* d_Hoff);
+// ... everything to the Schur destination (diagonal through d_rowptr, b to d_bp and d_bsc, off-diagonal by block index) ...
+void launch_point_pair_add_schur(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+                                 const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc);
+// ... or its pieces: the diagonal part alone, plain or Schur, and the off-diagonal sums alone ADDED to d_H by block index
+// (behind a Schur pass that has overwritten every block; reads the partials, not the poses)
+void launch_point_pair_add_diag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+                                double* d_Hpp, double* d_bp);
+void launch_point_pair_add_diag_schur(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan,
+                                      PointPairScratch rs, const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc);
+void launch_point_pair_add_offdiag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+                                   double* d_H);
+void launch_point_pair_chi_total(hipStream_t s, const cugo_point_pair_edges& ev, PointPairScratch rs, double* d_chi, bool chi_add);
+
 // chi_e per edge slot (outlier rejection, ref: computeOutliersKernel cuda_block_solver.cu:1135)
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,
                      cugo_robust rk, double* d_chi_e);

@@ -156,6 +156,15 @@ public:
      *  packed); returns n_info (n, or 1 when one matrix serves all).  Diagnostic */
     int flatPointEdges(std::vector<int>& pose, std::vector<int>& srcEdge, std::vector<double>& p, std::vector<double>& z,
                        std::vector<double>& info) const;
+    /** pose-pose point edges of the current flattening that count: active, at least one free end (point_pair_types.h, an
+     *  extension) */
+    int nPointPairEdges() const;
+    /** the pose-pose point edges of the current flattening as the kernels read them: in the order of their plan (runs of
+     *  one (a, b) orientation of a pair, ordered by (lo, hi, orientation); container order inside a run), planar — pose a
+     *  and pose b [n], position of each edge in its set's container, p [3][n], z [3][n], info [6][n_info] (upper triangle,
+     *  row-major packed); returns n_info (n, or 1 when one matrix serves all).  Diagnostic */
+    int flatPointPairEdges(std::vector<int>& poseA, std::vector<int>& poseB, std::vector<int>& srcEdge, std::vector<double>& p,
+                           std::vector<double>& z, std::vector<double>& info) const;
     /** the pose-landmark edges of the current flattening in flattening order (set by set, container order; mono,
      *  stereo and depth edges share the array): flattened pose and landmark index, CUGO_EDGE_* flags, measurement
      *  (3 per edge, the third 0 for a mono edge).  Diagnostic */

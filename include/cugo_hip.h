@@ -739,6 +739,89 @@ int cugo_relpose_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_relpose
 int cugo_relpose_add_offdiag_schur(cugo_ctx* ctx, const cugo_relpose_edges* ev, const double* d_poses, double* d_Hsc);
 
 /*
+ * Extension (the reference has no such edge): pose-pose point edges, binary edges between poses a and b for scan-to-scan
+ * registration.  An edge carries a point p measured in a's frame, the same physical point measured as z in b's frame,
+ * and a 3 x 3 information matrix Omega (symmetric, positive SEMI-definite: singular matrices are legal) expressed in
+ * b's frame.  Conventions as for cugo_point_edges: y = R(q) X + t is world -> frame, left update, tangent order
+ * [omega, upsilon]:
+ *   X = R_a^T (p - t_a),  y = R_b X + t_b,  r = y - z
+ *   J_b = dr/dxi_b = [ -[y]x | I ]  (the Jacobian of cugo_point_edges),  J_a = dr/dxi_a = R_BA [ [p]x | -I ],  R_BA = R_b R_a^T
+ *   chi2 term rho(max(0, r^T Omega r)) with the set's robust kernel, w = rho';  H_aa += w J_a^T Omega J_a,
+ *   H_bb += w J_b^T Omega J_b,  H_(lo,hi) += w J_lo^T Omega J_hi (lo < hi the two pose indices),  b_a -= w J_a^T Omega r,
+ *   b_b -= w J_b^T Omega r
+ * With T_a the identity the term on pose b is that of the cugo_point_edges edge (p, z, Omega).  An edge with one fixed
+ * end (index >= n_poses_free) counts in chi2 and adds only its free end's block and b; an edge between two fixed poses,
+ * or flagged CUGO_EDGE_INACTIVE, counts for nothing.
+ *
+ * The plan.  h_* are HOST arrays in the caller's order: the two pose indices and the flags of every edge (h_flags may be
+ * NULL: all active) and an upper block-CSR pattern over the free poses, as for cugo_relpose_plan_create (h_rowptr and
+ * h_colind may both be NULL: a plan without a destination, for its "pair_lo" / "pair_hi" alone; the kernels refuse it).
+ * The plan sorts the edges, stably, into RUNS: one run per (a, b) orientation of a pose pair, ordered by (lo, hi,
+ * orientation) so that the runs of one block are adjacent.  It holds the permutation, the runs, per free pose the
+ * counting runs its diagonal block is summed from, per block touched its runs, and the distinct pairs.  The same
+ * refusals as cugo_relpose_plan_create (CUGO_ERR_INVALID).  ctx == NULL gives a host-only plan.
+ */
+typedef struct cugo_point_pair_plan cugo_point_pair_plan;
+int cugo_point_pair_plan_create(cugo_ctx* ctx, int n, int n_poses_total, int n_poses_free, const int32_t* h_pose_a,
+                                const int32_t* h_pose_b, const uint8_t* h_flags, const int32_t* h_rowptr,
+                                const int32_t* h_colind, cugo_point_pair_plan** out);
+void cugo_point_pair_plan_destroy(cugo_point_pair_plan* plan);
+/* named int32 plan array: "perm" [n] (container index of the edge at sorted position i), "edge_run" [n], "run_ptr"
+ * [n_runs + 1], "run_a", "run_b", "run_flags" (1: a free, 2: b free, 4: a is hi, 8: the run counts), "run_blk" [n_runs],
+ * "inc_ptr" [n_poses_free + 1], "inc" (run << 1 | side; side 0: the pose is the run's a), "blk_id" [n_touched], "blk_ptr"
+ * [n_touched + 1], "blk_run", "pair_lo", "pair_hi".  The pointer is valid until the plan is destroyed.  Returns the
+ * length or a negative error. */
+int cugo_point_pair_plan_array(const cugo_point_pair_plan* plan, const char* name, const int32_t** out);
+
+/* The edges in the plan's SORTED order (position i holds edge perm[i] of the container), structure of arrays. */
+typedef struct cugo_point_pair_edges
+{
+    int n_poses_total, n_poses_free; /* those of the plan */
+    int n;                           /* that of the plan */
+    const int32_t* d_pose_a;         /* [n] pose a of every edge, sorted order */
+    const int32_t* d_pose_b;         /* [n] pose b */
+    const double* d_p;               /* [3][n] the point in a's frame */
+    const double* d_z;               /* [3][n] its measurement in b's frame */
+    const double* d_info;            /* [6][n] or [6][1]: upper triangle of Omega, row-major packed 00 01 02 11 12 22 */
+    int n_info;                      /* n or 1 */
+    const uint8_t* d_flags;          /* [n] CUGO_EDGE_INACTIVE, or NULL, sorted order.  A run that did not count under
+                                        the PLAN's flags stays out; an edge flagged here in addition counts for nothing */
+    int rk;                          /* CUGO_RK_* */
+    double delta;
+    const cugo_point_pair_plan* plan; /* with a device context and a pattern */
+} cugo_point_pair_edges;
+
+/* Writes the chi2 total to d_chi[0] (every counting edge once); with d_edge_chi (optional, [n], sorted order) also the
+ * chi2 term of every edge (0 for edges that do not count).  The counts, the arrays and the robust-kernel code are checked
+ * on the host, d_pose_a / d_pose_b of every edge against the plan's runs on the device; a mismatch gives
+ * CUGO_ERR_INVALID with nothing launched (one flag is read back: the call synchronises once).  Deterministic: no atomics,
+ * one summation order. */
+int cugo_point_pair_compute_errors(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses, double* d_chi,
+                                   double* d_edge_chi);
+/* ADDS the diagonal terms to d_Hpp [n_poses_free][36] and b to d_bp [n_poses_free][6] (layout and sign of
+ * cugo_point_construct_quadratic_form) and the off-diagonal terms to d_Hoff [nnzb][36]: block k of the plan's pattern, 6 x
+ * 6 column-major, holds H_(lo,hi) (rows: pose lo); the diagonal blocks of d_Hoff are not touched.  The two runs of a
+ * pair are summed into one block.  A free pose without a counting run and a block no counting run maps to keep their
+ * bits; fixed ends are never written.  chi2 total to d_chi[0] if d_chi != NULL (the bits of
+ * cugo_point_pair_compute_errors).  d_Hoff may be NULL when no counting run joins two free poses. */
+int cugo_point_pair_construct_quadratic_form(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
+                                             double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi);
+/* The same terms into the Schur destination: the diagonal term of pose p into block d_rowptr[p] of d_Hsc, the
+ * off-diagonal terms into d_Hsc by the plan's block indices, b into d_bp and d_bsc alike. */
+int cugo_point_pair_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
+                                                   const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
+                                                   double* d_chi);
+/* The split a two-stream LM loop makes of the same terms.  The build pass: the diagonal terms and b ADDED to d_Hpp / d_bp;
+ * the off-diagonal partials stay in the plan's scratch (a plan made with a context owns the scratch of its passes) ... */
+int cugo_point_pair_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
+                                                  double* d_Hpp, double* d_bp, double* d_chi);
+/* ... and the off-diagonal sums of those partials ADDED to d_Hsc by the plan's block indices.  It reads the PARTIALS the
+ * last cugo_point_pair_construct_quadratic_form* call left in the plan's scratch, not the poses (CUGO_ERR_INVALID before
+ * any such call); cugo_point_pair_compute_errors in between does not disturb them.  Nothing else is written.  The sums
+ * and their order are those of the Schur form. */
+int cugo_point_pair_add_offdiag_schur(cugo_ctx* ctx, const cugo_point_pair_edges* ev, double* d_Hsc);
+
+/*
  * Outlier pass of the four pose edge kinds (ref: EdgeSet::updateEdges, optimisable_graph.hpp:603-640), over the chi2
  * term of every edge as cugo_icp_compute_errors / cugo_prior_compute_errors / cugo_relpose_compute_errors write it.
  * Edge e becomes an outlier iff !(d_flags[e] & CUGO_EDGE_INACTIVE) && t_e > 0 && d_edge_chi[e] > t_e
@@ -917,6 +1000,33 @@ int cugo_graph_n_point_edges(cugo_graph* g);
  * Omega, row-major packed 00 01 02 11 12 22). */
 int cugo_graph_get_flat_point_edges(cugo_graph* g, int cap, int32_t* pose, int32_t* src_edge, double* p, double* z,
                                     double* info, int* n_info);
+/* Extension: pose-pose point edges (PointPairEdgeSet, cuda-bundle-adjustment_amd/include/point_pair_types.h) for
+ * scan-to-scan registration, next to the other sets or alone; term and conventions as for cugo_point_pair_edges above.
+ * pose_ids_a / pose_ids_b [n]: ids given to cugo_graph_add_poses (an unknown id, or a == b, refuses the whole call: nothing
+ * is added); pointP [n][3]: the points in a's frame; pointZ [n][3]: the same points measured in b's frame; info9 [n][9]:
+ * Omega of every edge in b's frame, or NULL for a COPY of the set's matrix at the time of the add
+ * (cugo_graph_set_point_pair_information; the identity until it is set), with the per_edge_information rule of the point
+ * edges.  cugo_graph_initialize() checks the values as for the point edges and refuses, naming the set: an outlier
+ * threshold > 0 on the set (cugo_graph_set_point_pair_outlier_threshold exists so that the set has every setter; not yet
+ * supported), a sharded optimiser and CUGO_HSC_STRIP=1.  Edges between two fixed poses and inactive edges count for
+ * nothing; an edge with one fixed end counts.  Every pair of free poses a counting edge joins is a block of the Schur
+ * complement's pattern.  The set is no kind of cugo_graph_n_pose_edge_outliers (CUGO_POSE_KIND_*). */
+int cugo_graph_add_point_pair_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b,
+                                    const double* pointP, const double* pointZ, const double* info9);
+int cugo_graph_set_point_pair_information(cugo_graph* g, const double* info9);
+int cugo_graph_set_point_pair_robust_kernel(cugo_graph* g, int type, double delta);
+int cugo_graph_set_point_pair_outlier_threshold(cugo_graph* g, double threshold);
+/* active flag of n edges from `first` on, in insertion order (active[i] != 0: active); counts as a change of the set */
+int cugo_graph_set_point_pair_active(cugo_graph* g, int first, int n, const uint8_t* active);
+/* pair edges that count in the current flattening: active, at least one free end */
+int cugo_graph_n_point_pair_edges(cugo_graph* g);
+/* Diagnostic: the pair edges of the current flattening as the kernels read them (works on a plan-only graph): in the
+ * order of their plan — runs of one (a, b) orientation of a pair, ordered by (lo, hi, orientation), insertion order inside
+ * a run —, planar.  Returns their number n (or a negative error) and *n_info (n, or 1 when one matrix serves all); with
+ * cap >= n fills the arrays that are not NULL: pose_a, pose_b [n] (flattened indices), src_edge [n] (position among the
+ * edges added), p [3][n], z [3][n], info [6][n_info] (upper triangle of the symmetric part of Omega, row-major packed). */
+int cugo_graph_get_flat_point_pair_edges(cugo_graph* g, int cap, int32_t* pose_a, int32_t* pose_b, int32_t* src_edge, double* p,
+                                         double* z, double* info, int* n_info);
 /* Extension: relative-pose SE(3) edges (RelPoseEdgeSet, cuda-bundle-adjustment_amd/include/relpose_types.h), next to or
  * instead of the other sets; term and conventions as for cugo_relpose_edges above (Z ~ T_a T_b^-1).  pose_ids_a /
  * pose_ids_b [n]: ids given to cugo_graph_add_poses; q_t7 [n][7] the measured relative pose; info36 [n][36] or NULL for
