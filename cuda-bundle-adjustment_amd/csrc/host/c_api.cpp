@@ -244,7 +244,7 @@ void check_pose_indices(cugo_ctx* ctx, const char* prefix, const char* who, std:
         throw std::runtime_error(std::string(prefix) + ": edges not sorted by pose, or a pose index disagrees with pose_ptr");
 }
 
-cugo_k::ReduceScratch check_icp(cugo_ctx* ctx, const cugo_icp_edges* ev)
+cugo_k::ChunkScratch check_icp(cugo_ctx* ctx, const cugo_icp_edges* ev)
 {
     if (!ev || ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total ||
         ev->n_plane < 0 || ev->n_line < 0)
@@ -264,7 +264,7 @@ cugo_k::ReduceScratch check_icp(cugo_ctx* ctx, const cugo_icp_edges* ev)
                        {{ev->d_plane_pose, ev->d_plane_pose_ptr, ev->n_plane, "k_icp_check"},
                         {ev->d_line_pose, ev->d_line_pose_ptr, ev->n_line, "k_icp_check"}},
                        P, rs, need);
-    return rs;
+    return cugo_k::icp_scratch_in(rs, *ev);
 }
 } // namespace
 
@@ -274,7 +274,7 @@ int cugo_icp_compute_errors(cugo_ctx* ctx, const cugo_icp_edges* ev, const doubl
                             double* d_edge_chi)
 {
     return guarded([&] {
-        const cugo_k::ReduceScratch rs = check_icp(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_icp(ctx, ev);
         cugo_k::launch_icp_errors(ctx->stream, *ev, d_poses, rs, d_chi, false, d_edge_chi);
         CUGO_HIP(hipGetLastError());
     });
@@ -284,7 +284,7 @@ int cugo_icp_construct_quadratic_form(cugo_ctx* ctx, const cugo_icp_edges* ev, c
                                       double* d_bp, double* d_chi)
 {
     return guarded([&] {
-        const cugo_k::ReduceScratch rs = check_icp(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_icp(ctx, ev);
         cugo_k::launch_icp_build(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs, d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
@@ -294,19 +294,15 @@ int cugo_icp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_icp_edges*
                                             const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi)
 {
     return guarded([&] {
-        const cugo_k::ReduceScratch rs = check_icp(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_icp(ctx, ev);
         if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
             throw std::runtime_error("cugo_icp: missing rowptr, Hsc, bp or bsc");
         // (what the one-stream form of the LM loop queues: the chunk pass, the per-pose sums into the Schur destination,
-        //  the chunk totals at the end of the ICP scratch)
+        //  the sum of the chunk totals)
         cugo_k::launch_icp_chunks(ctx->stream, *ev, d_poses, true, rs);
         cugo_k::launch_icp_add_schur(ctx->stream, *ev, rs, d_rowptr, d_Hsc, d_bp, d_bsc);
         if (d_chi)
-        {
-            const int n_chi = cugo_k::icp_chunk_count(*ev);
-            cugo_k::launch_pose_chi_total(ctx->stream, "k_icp_chi_total",
-                                          rs.d_partials + cugo_k::icp_scratch_doubles(*ev) - n_chi, n_chi, d_chi, false);
-        }
+            cugo_k::launch_icp_chi_total(ctx->stream, *ev, rs, d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
 }
@@ -316,7 +312,7 @@ int cugo_icp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_icp_edges*
 namespace
 {
 // as check_icp, for the one kind of the point edges
-cugo_k::PointScratch check_point(cugo_ctx* ctx, const cugo_point_edges* ev)
+cugo_k::ChunkScratch check_point(cugo_ctx* ctx, const cugo_point_edges* ev)
 {
     if (!ev || ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total || ev->n < 0)
         throw std::runtime_error("cugo_point: bad pose or edge counts");
@@ -336,7 +332,7 @@ int cugo_point_compute_errors(cugo_ctx* ctx, const cugo_point_edges* ev, const d
                               double* d_edge_chi)
 {
     return guarded([&] {
-        const cugo_k::PointScratch rs = check_point(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_point(ctx, ev);
         cugo_k::launch_point_errors(ctx->stream, *ev, d_poses, rs, d_chi, false, d_edge_chi);
         CUGO_HIP(hipGetLastError());
     });
@@ -346,7 +342,7 @@ int cugo_point_construct_quadratic_form(cugo_ctx* ctx, const cugo_point_edges* e
                                         double* d_bp, double* d_chi)
 {
     return guarded([&] {
-        const cugo_k::PointScratch rs = check_point(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_point(ctx, ev);
         cugo_k::launch_point_build(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs, d_chi, false);
         CUGO_HIP(hipGetLastError());
     });
@@ -356,7 +352,7 @@ int cugo_point_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_point_ed
                                               const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi)
 {
     return guarded([&] {
-        const cugo_k::PointScratch rs = check_point(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_point(ctx, ev);
         if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
             throw std::runtime_error("cugo_point: missing rowptr, Hsc, bp or bsc");
         cugo_k::launch_point_chunks(ctx->stream, *ev, d_poses, true, rs);
@@ -753,7 +749,7 @@ struct cugo_point_pair_plan
                 run_a.data(),   run_b.data(), run_flags.data(),  inc_ptr.data(),          inc.data(),      blk_id.data(),
                 blk_ptr.data(), blk_run.data()};
     }
-    cugo_k::PointPairScratch pair_scratch() const
+    cugo_k::ChunkScratch pair_scratch() const
     {
         return cugo_k::point_pair_scratch_in({scratch.data(), scratch.size()}, host.n, n_runs());
     }
@@ -763,7 +759,7 @@ namespace
 {
 // counts against the plan, arrays, kernel code on the host; with check_indices, pose a / b of every edge against the
 // plan's runs on the device
-cugo_k::PointPairScratch check_point_pair(cugo_ctx* ctx, const cugo_point_pair_edges* ev, bool check_indices = true)
+cugo_k::ChunkScratch check_point_pair(cugo_ctx* ctx, const cugo_point_pair_edges* ev, bool check_indices = true)
 {
     if (!ctx)
         throw std::runtime_error("cugo_point_pair: no context");
@@ -780,14 +776,14 @@ cugo_k::PointPairScratch check_point_pair(cugo_ctx* ctx, const cugo_point_pair_e
         throw std::runtime_error("cugo_point_pair: unknown robust kernel or bad delta");
     if (ev->n > 0 && (!ev->d_pose_a || !ev->d_pose_b || !ev->d_p || !ev->d_z || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
         throw std::runtime_error("cugo_point_pair: missing arrays, or n_info is neither n nor 1");
-    const cugo_k::PointPairScratch rs = ev->plan->pair_scratch();
+    const cugo_k::ChunkScratch rs = ev->plan->pair_scratch();
     if (check_indices &&
         cugo_k::point_pair_check_indices(ctx->stream, *ev, ev->plan->dev(),
                                          reinterpret_cast<int*>(ev->plan->scratch.data() + cugo_k::point_pair_scratch_doubles(h.n, ev->plan->n_runs()))))
         throw std::runtime_error("cugo_point_pair: pose a or pose b of an edge is not that of its run: the edges are not in the plan's order");
     return rs;
 }
-void point_pair_build(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses, cugo_k::PointPairScratch rs)
+void point_pair_build(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses, cugo_k::ChunkScratch rs)
 {
     if (!d_poses)
         throw std::runtime_error("cugo_point_pair: missing poses");
@@ -795,7 +791,7 @@ void point_pair_build(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const doub
     cugo_k::launch_point_pair_chunks(ctx->stream, *ev, ev->plan->dev(), d_poses, true, rs);
     ev->plan->built = true;
 }
-void point_pair_chi_total(cugo_ctx* ctx, const cugo_point_pair_edges* ev, cugo_k::PointPairScratch rs, double* d_chi)
+void point_pair_chi_total(cugo_ctx* ctx, const cugo_point_pair_edges* ev, cugo_k::ChunkScratch rs, double* d_chi)
 {
     if (!d_chi)
         return;
@@ -867,7 +863,7 @@ int cugo_point_pair_compute_errors(cugo_ctx* ctx, const cugo_point_pair_edges* e
                                    double* d_edge_chi)
 {
     return guarded([&] {
-        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev);
         if (!d_poses)
             throw std::runtime_error("cugo_point_pair: missing poses");
         cugo_k::launch_point_pair_chunks(ctx->stream, *ev, ev->plan->dev(), d_poses, false, rs, d_edge_chi);
@@ -880,7 +876,7 @@ int cugo_point_pair_construct_quadratic_form(cugo_ctx* ctx, const cugo_point_pai
                                              double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi)
 {
     return guarded([&] {
-        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev);
         if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
             throw std::runtime_error("cugo_point_pair: missing Hpp or bp");
         if (!d_Hoff && joins_free_poses(ev))
@@ -897,7 +893,7 @@ int cugo_point_pair_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_poi
                                                    double* d_chi)
 {
     return guarded([&] {
-        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev);
         if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
             throw std::runtime_error("cugo_point_pair: missing rowptr, Hsc, bp or bsc");
         point_pair_build(ctx, ev, d_poses, rs);
@@ -911,7 +907,7 @@ int cugo_point_pair_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_poin
                                                   double* d_Hpp, double* d_bp, double* d_chi)
 {
     return guarded([&] {
-        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev);
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev);
         if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
             throw std::runtime_error("cugo_point_pair: missing Hpp or bp");
         point_pair_build(ctx, ev, d_poses, rs);
@@ -924,7 +920,7 @@ int cugo_point_pair_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_poin
 int cugo_point_pair_add_offdiag_schur(cugo_ctx* ctx, const cugo_point_pair_edges* ev, double* d_Hsc)
 {
     return guarded([&] {
-        const cugo_k::PointPairScratch rs = check_point_pair(ctx, ev, false); // (the build pass checked the indices)
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev, false); // (the build pass checked the indices)
         if (!ev->plan->built)
             throw std::runtime_error("cugo_point_pair_add_offdiag_schur: no build pass has left its partials in the plan's scratch");
         if (!d_Hsc)

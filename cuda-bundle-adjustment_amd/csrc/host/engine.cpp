@@ -314,9 +314,9 @@ struct Engine::Impl : cugo_k::LaunchHook
         }
         double* relpose_chi() { return d_scratch.data() + off_relpose_chi; }
 
-        cugo_k::ReduceScratch icp_rs() { return {d_scratch.data() + off_icp, d_scratch.size() - off_icp}; }
-        cugo_k::PointScratch point_rs() { return {d_scratch.data() + off_point, d_scratch.data() + off_point_chi}; }
-        cugo_k::PointPairScratch pair_rs() { return {d_scratch.data(), d_scratch.data() + off_pair_chi}; }
+        cugo_k::ChunkScratch icp_rs() { return cugo_k::icp_scratch_in({d_scratch.data() + off_icp, d_scratch.size() - off_icp}, icp); }
+        cugo_k::ChunkScratch point_rs() { return {d_scratch.data() + off_point, d_scratch.data() + off_point_chi}; }
+        cugo_k::ChunkScratch pair_rs() { return {d_scratch.data(), d_scratch.data() + off_pair_chi}; }
         double* prior_chi() { return d_scratch.data() + off_prior_chi; }
         int n_edges(int k) const { return (int)kind[k].h_pose.size(); }
         const std::vector<int32_t>& icp_slot_source(int k, bool set) const { return set ? kind[k].slot_set : kind[k].slot_edge; }
@@ -484,7 +484,7 @@ struct Engine::Impl : cugo_k::LaunchHook
                 if (!one_stream)
                     cugo_k::launch_icp_add(s, icp, icp_rs(), Hpp, bp);
                 if (d_chi)
-                    cugo_k::launch_pose_chi_total(s, "k_icp_chi_total", d_scratch.data() + off_icp_chi, n_icp_chi, d_chi, true);
+                    cugo_k::launch_icp_chi_total(s, icp, icp_rs(), d_chi, true);
             }
             if (n_point)
             { // as the ICP kinds: the chunk pass, its add here or behind k_pose_schur

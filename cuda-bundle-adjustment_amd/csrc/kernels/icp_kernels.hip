@@ -8,24 +8,14 @@
 // the gradient of chi2, the solver takes H dx = b and the update applies exp(+dx) (k_backsubst_poses).  Edges on fixed
 // poses (index >= n_poses_free) and inactive edges contribute nothing.
 //
-// Layout and reduction (no atomics, one fixed order):  each kind's edges are sorted by pose index.  The edge range
-// is cut into chunks of ICP_CHUNK edges regardless of pose boundaries, one wave per chunk; a chunk writes one partial
-// of 28 doubles (21 of the upper triangle of H, 6 of b, chi2) per pose it touches.  Chunk c and pose p meet in at
-// most one partial, and along the sorted edges c and p never decrease and one of them grows at each step from one
-// (chunk, pose) pair to the next: c + p is therefore a unique slot index — no prefix sums, no plan.  The finishing
-// pass sums a pose's partials in chunk order (plane kind, then line kind) and adds them to Hpp / bp or, behind
-// k_pose_schur in the one-stream form of the LM loop, to the pose's diagonal block of Hsc, to bp and to bsc.  Every
-// chunk also leaves ONE chi2 total (its partials in the order it wrote them); the chi2 total of the pass is the sum of
-// the chunk totals — plane chunks, then line chunks: a plain array that the reduction ending an LM trial sums next to
-// the BA partials (ba_kernels.hip: k_sum_partials2).  The error pass forms the very same chunk totals, so its total
-// has the bits of the build pass's.
+// Layout and reduction are the chunk scheme of pose_chunks.h, twice: each kind's edges are sorted by pose index (the
+// key) and have their own partials, 21 of the upper triangle of H, 6 of b and chi2.  The finishing pass sums a pose's
+// partials in chunk order (plane kind, then line kind).  The chi2 total of a pass is the sum of the chunk totals —
+// plane chunks, then line chunks: a plain array that the reduction ending an LM trial sums next to the BA partials
+// (ba_kernels.hip: k_sum_partials2).
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <climits>
-#include <stdexcept>
 
-#include "ba_math.h"
-#include "kernels.h"
 #include "pose_chunks.h"
 
 namespace
@@ -47,8 +37,6 @@ struct IcpKind
     double* part; // [n_chunks + n_poses_total][ICP_NP]
     double* cchi; // [n_chunks] chi2 total of every chunk
 };
-
-__device__ __forceinline__ int n_chunks(int n) { return (n + ICP_CHUNK - 1) / ICP_CHUNK; }
 
 // contribution of edge e of one kind: v[0..20] upper triangle of w J^T J (row-major packed), v[21..26] -w J^T r;
 // returns the chi2 term
@@ -131,80 +119,6 @@ __device__ __forceinline__ double icp_edge(const IcpKind& k, int e, const double
     return chi;
 }
 
-// One wave per chunk of ICP_CHUNK edges of one kind.  FULL: partials of H, b and chi2; otherwise chi2 only (slot
-// element 27, the same value FULL writes there) and, with edge_chi, the chi2 term of every edge.
-template <bool LINE, bool FULL>
-__device__ void icp_chunk(const IcpKind& k, int c, int n_poses_free, const double* __restrict__ poses,
-                          double* __restrict__ edge_chi)
-{
-    const int lane = threadIdx.x & 63;
-    const int e0 = c * ICP_CHUNK, e1 = min(k.n, e0 + ICP_CHUNK);
-    int qcur = k.pose[e0]; // (wave-uniform)
-    double acc[32];
-#pragma unroll
-    for (int i = 0; i < 32; i++)
-        acc[i] = 0.0;
-    double chi_acc = 0.0, chunk_chi = 0.0;
-    auto flush = [&](int q) {
-        const double cs = icp_wave_sum(chi_acc);
-        chunk_chi += cs; // (the same value in every lane)
-        double* out = k.part + (size_t)(c + q) * ICP_NP;
-        if (FULL)
-        {
-            icp_wave_reduce32(acc);
-            if (!(lane & 1) && (lane >> 1) < 27)
-                out[lane >> 1] = acc[0];
-#pragma unroll
-            for (int i = 0; i < 32; i++)
-                acc[i] = 0.0;
-        }
-        if (lane == 0)
-            out[27] = cs;
-        chi_acc = 0.0;
-    };
-    for (int base = e0; base < e1; base += 64)
-    {
-        const int e = base + lane;
-        const bool in = e < e1;
-        const int q = in ? k.pose[e] : INT_MAX;
-        double v[32];
-        double chi = 0.0;
-        if (in && q < n_poses_free && !(k.flags && (k.flags[e] & CUGO_EDGE_INACTIVE)))
-            chi = icp_edge<LINE, FULL>(k, e, poses + 7 * (size_t)q, v);
-        else if (FULL)
-        {
-#pragma unroll
-            for (int i = 0; i < 27; i++)
-                v[i] = 0.0;
-        }
-        if (!FULL && edge_chi && in)
-            edge_chi[e] = chi;
-        // the poses of the 64 lanes ascend: the lanes of each pose in turn join the wave's accumulators
-        for (;;)
-        {
-            if (q == qcur)
-            {
-                chi_acc += chi;
-                if (FULL)
-                {
-#pragma unroll
-                    for (int i = 0; i < 27; i++)
-                        acc[i] += v[i];
-                }
-            }
-            const unsigned long long later = __ballot(in && q > qcur);
-            if (later == 0)
-                break;
-            const int qn = __shfl(q, __ffsll((long long)later) - 1, 64);
-            flush(qcur);
-            qcur = qn;
-        }
-    }
-    flush(qcur);
-    if (lane == 0)
-        k.cchi[c] = chunk_chi;
-}
-
 struct IcpArgs
 {
     IcpKind plane, line;
@@ -213,11 +127,26 @@ struct IcpArgs
     double* edge_chi; // error pass: [n_plane + n_line] or nullptr
 };
 
+// chunk c of one kind (pose_chunks.h: chunk_walk, keyed by pose)
+template <bool LINE, bool FULL>
+__device__ __forceinline__ void icp_chunk(const IcpKind& k, int c, int n_poses_free, const double* __restrict__ poses,
+                                          double* __restrict__ edge_chi)
+{
+    chunk_walk<FULL, true>(k.n, k.pose, c, k.part, k.cchi, edge_chi, [&](int e, bool in, int q, double (&v)[32]) {
+        if (in && q < n_poses_free && !(k.flags && (k.flags[e] & CUGO_EDGE_INACTIVE)))
+            return icp_edge<LINE, FULL>(k, e, poses + 7 * (size_t)q, v);
+        if (FULL)
+            chunk_zero(v);
+        return 0.0;
+    });
+}
+
+// one wave per chunk: the plane chunks, then the line chunks
 template <bool FULL>
 __device__ __forceinline__ void icp_chunks(const IcpArgs& a)
 {
     const int wave = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 6);
-    const int cp = n_chunks(a.plane.n), cl = n_chunks(a.line.n);
+    const int cp = chunk_count(a.plane.n), cl = chunk_count(a.line.n);
     if (wave < cp)
         icp_chunk<false, FULL>(a.plane, wave, a.n_poses_free, a.poses, a.edge_chi);
     else if (wave < cp + cl)
@@ -231,42 +160,27 @@ __global__ __launch_bounds__(ICP_WG) __attribute__((amdgpu_waves_per_eu(6))) voi
     icp_chunks<false>(a);
 }
 
-// sum of pose p's partials of one kind, element t, in chunk order
-__device__ __forceinline__ double icp_pose_sum(const IcpKind& k, int p, int t)
-{
-    return chunk_pose_sum(k.pose_ptr, k.part, p, t);
-}
-
-// 32 threads per free pose that has ICP edges; thread t < 27 adds element t of the pose's sums.  SCHUR = false: to
-// Hpp / bp (behind k_build_poses).  SCHUR = true: to the diagonal block of Hsc (the first block of the pose's row,
-// through rowptr), to bp and to bsc — behind k_pose_schur, which WRITES the three in the one-stream form of the loop
-// (there Hpp is not formed at all; the ICP terms of a pose enter its row of the Schur complement unchanged, as Hpp does)
+// the finishing pass (pose_chunks.h: chunk_finish) over the free poses that have ICP edges of either kind
 template <bool SCHUR>
 __global__ __launch_bounds__(ICP_WG) void k_icp_finish(IcpArgs a, double* __restrict__ H, const int32_t* __restrict__ rowptr,
                                                         double* __restrict__ bp, double* __restrict__ bsc)
 {
-    const int p = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 5), t = threadIdx.x & 31;
-    if (p >= a.n_poses_free || t >= 27)
-        return;
-    if (a.plane.pose_ptr[p] == a.plane.pose_ptr[p + 1] && a.line.pose_ptr[p] == a.line.pose_ptr[p + 1])
-        return; // (nothing to add: the pose's blocks keep their bits, and its partial slots were never written)
-    const double s = icp_pose_sum(a.plane, p, t) + icp_pose_sum(a.line, p, t);
-    int r = 0, c = 0;
-    if (t < 21)
-        tri6_unpack(t, r, c);
-    pose_term_add<SCHUR>(p, t, r, c, s, H, rowptr, bp, bsc);
+    chunk_finish<SCHUR>(
+        a.n_poses_free,
+        [&](int p) { return a.plane.pose_ptr[p] != a.plane.pose_ptr[p + 1] || a.line.pose_ptr[p] != a.line.pose_ptr[p + 1]; },
+        [&](int p, int t) { return chunk_key_sum(a.plane.pose_ptr, a.plane.part, p, t) + chunk_key_sum(a.line.pose_ptr, a.line.part, p, t); },
+        H, rowptr, bp, bsc);
 }
 
 // scratch = [plane partials (cp + n_poses_total slots) | line partials (cl + n_poses_total) | chunk totals (cp + cl)]
 struct IcpLayout
 {
-    size_t cp, cl, line_part, cchi, end;
-    explicit IcpLayout(const cugo_icp_edges& ev)
+    ChunkLayout plane, line;
+    size_t cchi, end;
+    explicit IcpLayout(const cugo_icp_edges& ev) : plane(ev.n_plane, ev.n_poses_total), line(ev.n_line, ev.n_poses_total)
     {
-        cp = (size_t)(ev.n_plane + ICP_CHUNK - 1) / ICP_CHUNK, cl = (size_t)(ev.n_line + ICP_CHUNK - 1) / ICP_CHUNK;
-        line_part = (cp + ev.n_poses_total) * ICP_NP;
-        cchi = (cp + cl + 2 * (size_t)ev.n_poses_total) * ICP_NP;
-        end = cchi + cp + cl;
+        cchi = plane.cchi + line.cchi;
+        end = cchi + plane.chunks + line.chunks;
     }
 };
 
@@ -282,80 +196,74 @@ IcpKind kind_of(const cugo_icp_edges& ev, bool line, double* part, double* cchi)
     return k;
 }
 
-IcpArgs args_of(const cugo_icp_edges& ev, const double* d_poses, cugo_k::ReduceScratch rs, double* d_edge_chi)
+IcpArgs args_of(const cugo_icp_edges& ev, const double* d_poses, cugo_k::ChunkScratch rs, double* d_edge_chi)
 {
-    if (rs.capacity < IcpLayout(ev).end)
-        throw std::runtime_error("cugo: ICP scratch too small");
     const IcpLayout lay(ev);
     IcpArgs a;
-    a.plane = kind_of(ev, false, rs.d_partials, rs.d_partials + lay.cchi);
-    a.line = kind_of(ev, true, rs.d_partials + lay.line_part, rs.d_partials + lay.cchi + lay.cp);
+    a.plane = kind_of(ev, false, rs.d_part, rs.d_cchi);
+    a.line = kind_of(ev, true, rs.d_part + lay.plane.cchi, rs.d_cchi + lay.plane.chunks);
     a.n_poses_free = ev.n_poses_free;
     a.poses = d_poses;
     a.edge_chi = d_edge_chi;
     return a;
 }
 
-unsigned finish_grid(const cugo_icp_edges& ev) { return (unsigned)((32 * (size_t)ev.n_poses_free + ICP_WG - 1) / ICP_WG); }
-
 } // namespace
 
 namespace cugo_k
 {
 
-size_t icp_scratch_doubles(const cugo_icp_edges& ev)
+size_t icp_scratch_doubles(const cugo_icp_edges& ev) { return IcpLayout(ev).end; }
+
+int icp_chunk_count(const cugo_icp_edges& ev) { return chunk_count(ev.n_plane) + chunk_count(ev.n_line); }
+
+ChunkScratch icp_scratch_in(ReduceScratch rs, const cugo_icp_edges& ev)
 {
-    return IcpLayout(ev).end;
+    const IcpLayout lay(ev);
+    return chunk_scratch_in(rs, lay.cchi, lay.end, "ICP");
 }
 
-void launch_icp_chunks(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, ReduceScratch rs,
+void launch_icp_chunks(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, ChunkScratch rs,
                        double* d_edge_chi)
 {
     const IcpArgs a = args_of(ev, d_poses, rs, full ? nullptr : d_edge_chi);
-    const IcpLayout lay(ev);
-    const size_t waves = lay.cp + lay.cl;
+    const size_t waves = (size_t)icp_chunk_count(ev);
     if (waves == 0)
         return;
-    const unsigned grid = (unsigned)((waves * 64 + ICP_WG - 1) / ICP_WG);
     if (full)
-        CUGO_LAUNCH(k_icp_chunks_build, dim3(grid), dim3(ICP_WG), 0, s, a);
+        CUGO_LAUNCH(k_icp_chunks_build, dim3(chunk_grid(waves)), dim3(ICP_WG), 0, s, a);
     else
-        CUGO_LAUNCH(k_icp_chunks_errors, dim3(grid), dim3(ICP_WG), 0, s, a);
+        CUGO_LAUNCH(k_icp_chunks_errors, dim3(chunk_grid(waves)), dim3(ICP_WG), 0, s, a);
 }
 
-void launch_icp_add(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_Hpp, double* d_bp)
+void launch_icp_add(hipStream_t s, const cugo_icp_edges& ev, ChunkScratch rs, double* d_Hpp, double* d_bp)
 {
     if (ev.n_poses_free <= 0 || ev.n_plane + ev.n_line == 0)
         return;
     const IcpArgs a = args_of(ev, nullptr, rs, nullptr);
     LaunchScope scope("k_icp_add", s);
-    hipLaunchKernelGGL(k_icp_finish<false>, dim3(finish_grid(ev)), dim3(ICP_WG), 0, s, a, d_Hpp,
+    hipLaunchKernelGGL(k_icp_finish<false>, dim3(finish_grid(ev.n_poses_free)), dim3(ICP_WG), 0, s, a, d_Hpp,
                        (const int32_t*)nullptr, d_bp, (double*)nullptr);
 }
 
-void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, const int32_t* d_rowptr,
+void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ChunkScratch rs, const int32_t* d_rowptr,
                           double* d_Hsc, double* d_bp, double* d_bsc)
 {
     if (ev.n_poses_free <= 0 || ev.n_plane + ev.n_line == 0)
         return;
     const IcpArgs a = args_of(ev, nullptr, rs, nullptr);
     LaunchScope scope("k_icp_add_schur", s);
-    hipLaunchKernelGGL(k_icp_finish<true>, dim3(finish_grid(ev)), dim3(ICP_WG), 0, s, a, d_Hsc, d_rowptr, d_bp, d_bsc);
+    hipLaunchKernelGGL(k_icp_finish<true>, dim3(finish_grid(ev.n_poses_free)), dim3(ICP_WG), 0, s, a, d_Hsc, d_rowptr, d_bp,
+                       d_bsc);
 }
 
-int icp_chunk_count(const cugo_icp_edges& ev)
+void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ChunkScratch rs, double* d_chi, bool chi_add)
 {
-    const IcpLayout lay(ev);
-    return (int)(lay.cp + lay.cl);
-}
-
-static void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_chi, bool chi_add)
-{
-    launch_pose_chi_total(s, "k_icp_chi_total", rs.d_partials + IcpLayout(ev).cchi, icp_chunk_count(ev), d_chi, chi_add);
+    launch_pose_chi_total(s, "k_icp_chi_total", rs.d_cchi, icp_chunk_count(ev), d_chi, chi_add);
 }
 
 void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
-                      ReduceScratch rs, double* d_chi, bool chi_add)
+                      ChunkScratch rs, double* d_chi, bool chi_add)
 {
     launch_icp_chunks(s, ev, d_poses, true, rs);
     launch_icp_add(s, ev, rs, d_Hpp, d_bp);
@@ -363,7 +271,7 @@ void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_p
         launch_icp_chi_total(s, ev, rs, d_chi, chi_add);
 }
 
-void launch_icp_errors(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, ReduceScratch rs, double* d_chi,
+void launch_icp_errors(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, ChunkScratch rs, double* d_chi,
                        bool chi_add, double* d_edge_chi)
 {
     launch_icp_chunks(s, ev, d_poses, false, rs, d_edge_chi);

@@ -49,6 +49,14 @@ struct ReduceScratch
     double* d_partials; // capacity doubles
     size_t capacity;
 };
+// where a pass of a chunked pose edge kind (pose_chunks.h: ICP, point, point pair) leaves its partials and its one
+// chi2 total per chunk: behind one another in one scratch (*_scratch_in, which checks the capacity: the kernel-level C
+// ABI, and the ICP kinds everywhere), or the totals elsewhere (the LM loop keeps them beside the other kinds' totals)
+struct ChunkScratch
+{
+    double* d_part;
+    double* d_cchi;
+};
 
 // --- edge / landmark / pose passes (ba_kernels.hip) ---------------------------------------
 // The form of an edge view: which instantiation of its kernel every launcher below that forms residuals or Jacobians
@@ -193,55 +201,51 @@ const int32_t* launch_pose_reject(hipStream_t s, int n, const double* d_edge_chi
                                   uint8_t* d_flags, int32_t* d_rejected, int32_t* d_work);
 
 // --- point-to-plane / point-to-line pose edges (icp_kernels.hip) -------------------------
-// scratch the launchers need (chunk partials, then one chi2 total per chunk at its end)
+// scratch the launchers need: [plane partials | line partials | one chi2 total per chunk, plane chunks then line chunks
+// (icp_chunk_count() of them: what launch_errors_tail / launch_trial_tail_from_build sum into F-hat)]
 size_t icp_scratch_doubles(const cugo_icp_edges& ev);
+int icp_chunk_count(const cugo_icp_edges& ev);
+ChunkScratch icp_scratch_in(ReduceScratch rs, const cugo_icp_edges& ev);
 // ADDS the ICP terms to d_Hpp / d_bp; chi2 total to d_chi[0] if given (added to what is there with chi_add)
 void launch_icp_build(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
-                      ReduceScratch rs, double* d_chi, bool chi_add = false);
+                      ChunkScratch rs, double* d_chi, bool chi_add = false);
 // chi2 only (the same bits as launch_icp_build's); d_edge_chi: per edge, plane edges first, or nullptr
-void launch_icp_errors(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, ReduceScratch rs, double* d_chi,
+void launch_icp_errors(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, ChunkScratch rs, double* d_chi,
                        bool chi_add = false, double* d_edge_chi = nullptr);
 // The pieces of the two above, for the LM loop (engine.cpp), which places them itself:
 // the chunk pass alone — full: the partials of H, b and chi2 of every (chunk, pose) pair; otherwise chi2 only — leaves
 // its partials and the chi2 total of every chunk in the scratch
-void launch_icp_chunks(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, ReduceScratch rs,
+void launch_icp_chunks(hipStream_t s, const cugo_icp_edges& ev, const double* d_poses, bool full, ChunkScratch rs,
                        double* d_edge_chi = nullptr);
 // the per-pose sums of a full chunk pass ADDED to d_Hpp / d_bp (behind k_build_poses) ...
-void launch_icp_add(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, double* d_Hpp, double* d_bp);
+void launch_icp_add(hipStream_t s, const cugo_icp_edges& ev, ChunkScratch rs, double* d_Hpp, double* d_bp);
 // ... or to the diagonal blocks of d_Hsc (upper block CSR d_rowptr: the first block of a row), d_bp and d_bsc (behind
 // k_pose_schur, which writes the three in the one-stream form)
-void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ReduceScratch rs, const int32_t* d_rowptr,
+void launch_icp_add_schur(hipStream_t s, const cugo_icp_edges& ev, ChunkScratch rs, const int32_t* d_rowptr,
                           double* d_Hsc, double* d_bp, double* d_bsc);
-// a chunk pass leaves the chi2 total of every chunk (plane chunks, then line chunks) in the LAST icp_chunk_count()
-// doubles of the scratch: what launch_errors_tail / launch_trial_tail_from_build sum into F-hat
-int icp_chunk_count(const cugo_icp_edges& ev);
+// the sum of the chunk totals to d_chi[0]
+void launch_icp_chi_total(hipStream_t s, const cugo_icp_edges& ev, ChunkScratch rs, double* d_chi, bool chi_add);
 
 // --- point-to-point pose edges with 3 x 3 information (point_kernels.hip) -----------------
 // The launchers of the ICP kinds, for the one kind of cugo_point_edges.  A pass leaves its partials (point_partial_doubles()
-// doubles) and one chi2 total per chunk (point_chunk_count()) where PointScratch says: in one scratch behind one another
-// (point_scratch_in: the kernel-level C ABI), or the totals elsewhere (the LM loop keeps them beside the other kinds' totals)
-struct PointScratch
-{
-    double* d_part;
-    double* d_cchi;
-};
+// doubles) and one chi2 total per chunk (point_chunk_count()) where its ChunkScratch says
 size_t point_scratch_doubles(const cugo_point_edges& ev); // partials + totals
 size_t point_partial_doubles(const cugo_point_edges& ev);
 int point_chunk_count(const cugo_point_edges& ev);
-PointScratch point_scratch_in(ReduceScratch rs, const cugo_point_edges& ev);
+ChunkScratch point_scratch_in(ReduceScratch rs, const cugo_point_edges& ev);
 // ADDS the terms to d_Hpp / d_bp; chi2 total to d_chi[0] if given (added to what is there with chi_add)
 void launch_point_build(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
-                        PointScratch rs, double* d_chi, bool chi_add = false);
+                        ChunkScratch rs, double* d_chi, bool chi_add = false);
 // chi2 only (the same bits as launch_point_build's); d_edge_chi: per edge, or nullptr
-void launch_point_errors(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, PointScratch rs, double* d_chi,
+void launch_point_errors(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, ChunkScratch rs, double* d_chi,
                          bool chi_add = false, double* d_edge_chi = nullptr);
 // the pieces: the chunk pass alone, the per-pose sums ADDED to d_Hpp / d_bp or to the Schur destination, the chi2 total
-void launch_point_chunks(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, bool full, PointScratch rs,
+void launch_point_chunks(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, bool full, ChunkScratch rs,
                          double* d_edge_chi = nullptr);
-void launch_point_add(hipStream_t s, const cugo_point_edges& ev, PointScratch rs, double* d_Hpp, double* d_bp);
-void launch_point_add_schur(hipStream_t s, const cugo_point_edges& ev, PointScratch rs, const int32_t* d_rowptr,
+void launch_point_add(hipStream_t s, const cugo_point_edges& ev, ChunkScratch rs, double* d_Hpp, double* d_bp);
+void launch_point_add_schur(hipStream_t s, const cugo_point_edges& ev, ChunkScratch rs, const int32_t* d_rowptr,
                             double* d_Hsc, double* d_bp, double* d_bsc);
-void launch_point_chi_total(hipStream_t s, const cugo_point_edges& ev, PointScratch rs, double* d_chi, bool chi_add);
+void launch_point_chi_total(hipStream_t s, const cugo_point_edges& ev, ChunkScratch rs, double* d_chi, bool chi_add);
 
 // --- SE(3) pose priors with 6 x 6 information (prior_kernels.hip) --------------------------
 // One kernel per pass: 32 lanes per free pose walk its priors in container order and ADD their sums straight to the
@@ -311,39 +315,33 @@ struct PointPairPlanDev
     const int32_t *blk_id, *blk_ptr, *blk_run;        // [n_blocks], [n_blocks + 1], runs of every touched block
 };
 // A chunk pass leaves its partials (point_pair_partial_doubles() doubles: four roles of chunks + runs slots) and one
-// chi2 total per chunk (point_pair_chunk_count()) where PointPairScratch says: behind one another in one scratch
-// (point_pair_scratch_in), or the totals elsewhere
-struct PointPairScratch
-{
-    double* d_part;
-    double* d_cchi;
-};
+// chi2 total per chunk (point_pair_chunk_count()) where its ChunkScratch says
 size_t point_pair_scratch_doubles(int n, int n_runs); // partials + totals
 size_t point_pair_partial_doubles(int n, int n_runs);
 int point_pair_chunk_count(int n);
-PointPairScratch point_pair_scratch_in(ReduceScratch rs, int n, int n_runs);
+ChunkScratch point_pair_scratch_in(ReduceScratch rs, int n, int n_runs);
 // 1 if d_pose_a / d_pose_b of an edge are not those of its run in the plan, else 0; d_bad: a device int.  Synchronises
 int point_pair_check_indices(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, int* d_bad);
 // the chunk pass — full: the partials of the four roles and chi2; otherwise chi2 only (role 0; of the partials only
 // element 27 of role 0's slots is written, which no finishing pass reads); d_edge_chi: errors only, sorted order
 void launch_point_pair_chunks(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, const double* d_poses,
-                              bool full, PointPairScratch rs, double* d_edge_chi = nullptr);
+                              bool full, ChunkScratch rs, double* d_edge_chi = nullptr);
 // the sums of a full chunk pass ADDED: diagonal blocks and b to d_Hpp / d_bp, the off-diagonal blocks to d_Hoff by block
 // index if it is given ...
-void launch_point_pair_add(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+void launch_point_pair_add(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,
                            double* d_Hpp, double* d_bp, double* d_Hoff);
 // ... everything to the Schur destination (diagonal through d_rowptr, b to d_bp and d_bsc, off-diagonal by block index) ...
-void launch_point_pair_add_schur(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+void launch_point_pair_add_schur(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,
                                  const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc);
 // ... or its pieces: the diagonal part alone, plain or Schur, and the off-diagonal sums alone ADDED to d_H by block index
 // (behind a Schur pass that has overwritten every block; reads the partials, not the poses)
-void launch_point_pair_add_diag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+void launch_point_pair_add_diag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,
                                 double* d_Hpp, double* d_bp);
 void launch_point_pair_add_diag_schur(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan,
-                                      PointPairScratch rs, const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc);
-void launch_point_pair_add_offdiag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+                                      ChunkScratch rs, const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc);
+void launch_point_pair_add_offdiag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,
                                    double* d_H);
-void launch_point_pair_chi_total(hipStream_t s, const cugo_point_pair_edges& ev, PointPairScratch rs, double* d_chi, bool chi_add);
+void launch_point_pair_chi_total(hipStream_t s, const cugo_point_pair_edges& ev, ChunkScratch rs, double* d_chi, bool chi_add);
 
 // chi_e per edge slot (outlier rejection, ref: computeOutliersKernel cuda_block_solver.cu:1135)
 void launch_edge_chi(hipStream_t s, const cugo_edges& e, const double* d_poses, const double* d_lms,

@@ -20,7 +20,7 @@
 // Layout and reduction.  The plan (csrc/host/point_pair_plan.h) sorts the edges into RUNS of one (a, b) orientation of a
 // pair; the runs of one block are adjacent.  One wave per chunk of ICP_CHUNK sorted edges walks its edges in groups of 64
 // lanes; the lanes of each run in turn join the wave's accumulators, which are reduced (icp_wave_reduce32) and stored
-// whenever a later run begins and at the chunk's end — the walk of point_chunks, keyed by run instead of pose.  An edge
+// whenever a later run begins and at the chunk's end — the chunk scheme of pose_chunks.h, keyed by run.  An edge
 // feeds 27 + 27 + 36 sums; instead of 90 accumulators per lane the launch has four ROLES (blockIdx.y), each of which
 // recomputes the edge and keeps at most 27 sums under static indices:
 //   role 0  self-a: H_aa (21) + b_a (6), and the chi2 of the edge     role 2  H_ab columns 0-2 (18)
@@ -34,11 +34,9 @@
 // off-diagonal partials, runs ascending, then chunk order, transposing a run whose a is hi, and ADD them to the block.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <climits>
 #include <stdexcept>
 
-#include "ba_math.h"
-#include "kernels.h"
+#include "point_term.h"
 #include "pose_chunks.h"
 
 namespace
@@ -66,36 +64,7 @@ struct PairArgs
     double* edge_chi; // error pass: [n] or nullptr
 };
 
-__device__ __forceinline__ size_t pair_slots(const PairArgs& k) { return (size_t)(k.n + ICP_CHUNK - 1) / ICP_CHUNK + k.plan.n_runs; }
-
-// v[0..20]: upper triangle, row-major packed, of w [S_u | I]^T O [S_u | I] with O symmetric (the H part of point_kernels.hip's
-// point_edge, which this repeats operation by operation)
-__device__ __forceinline__ void unary_block(const double (&u)[3], const double (&O)[3][3], double w, double (&v)[32])
-{
-    double G[3][3]; // O S_u: row a is u x (row a of O)
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-    {
-        G[a][0] = O[a][2] * u[1] - O[a][1] * u[2];
-        G[a][1] = O[a][0] * u[2] - O[a][2] * u[0];
-        G[a][2] = O[a][1] * u[0] - O[a][0] * u[1];
-    }
-    v[0] = w * (u[1] * G[2][0] - u[2] * G[1][0]);
-    v[1] = w * (u[1] * G[2][1] - u[2] * G[1][1]);
-    v[2] = w * (u[1] * G[2][2] - u[2] * G[1][2]);
-    v[6] = w * (u[2] * G[0][1] - u[0] * G[2][1]);
-    v[7] = w * (u[2] * G[0][2] - u[0] * G[2][2]);
-    v[11] = w * (u[0] * G[1][2] - u[1] * G[0][2]);
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-    {
-        v[3 + j] = w * G[j][0];
-        v[8 + j] = w * G[j][1];
-        v[12 + j] = w * G[j][2];
-    }
-    v[15] = w * O[0][0], v[16] = w * O[0][1], v[17] = w * O[0][2];
-    v[18] = w * O[1][1], v[19] = w * O[1][2], v[20] = w * O[2][2];
-}
+__device__ __forceinline__ size_t pair_slots(const PairArgs& k) { return ChunkLayout(k.n, k.plan.n_runs).slots; }
 
 // Edge e between poses a and b, seen by `role`.  Returns the chi2 term.  FULL and term: v[0..26] receive the role's
 // contribution (roles 2 and 3: v[6 c + i] = H_ab[i][3 (role - 2) + c], 18 values); FULL without term: zeros
@@ -117,33 +86,19 @@ __device__ __forceinline__ double pair_edge(const PairArgs& k, int e, int a, int
 #pragma unroll
     for (int i = 0; i < 3; i++)
         y[i] = Rb[i][0] * X[0] + Rb[i][1] * X[1] + Rb[i][2] * X[2] + pb[4 + i];
-    const double r0 = y[0] - k.z[e], r1 = y[1] - k.z[n + e], r2 = y[2] - k.z[2 * n + e];
-    const size_t s = k.n_info == 1 ? 1 : n; // [6][1]: one matrix for all
-    const int i6 = k.n_info == 1 ? 0 : e;
-    const double o00 = k.info[i6], o01 = k.info[s + i6], o02 = k.info[2 * s + i6];
-    const double o11 = k.info[3 * s + i6], o12 = k.info[4 * s + i6], o22 = k.info[5 * s + i6];
-    const double O[3][3] = {{o00, o01, o02}, {o01, o11, o12}, {o02, o12, o22}};
-    double q[3]; // Omega r
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-        q[i] = O[i][0] * r0 + O[i][1] * r1 + O[i][2] * r2;
-    const double x = fmax(0.0, r0 * q[0] + r1 * q[1] + r2 * q[2]);
-    const double chi = rk_rho(k.rk, x);
+    const double z[3] = {k.z[e], k.z[n + e], k.z[2 * n + e]};
+    double O[3][3], q[3], x; // Omega, Omega r
+    const double chi = point_residual(y, z, k.info, k.n_info, n, e, k.rk, O, q, x);
     if (FULL)
     {
-#pragma unroll
-        for (int i = 0; i < 27; i++)
-            v[i] = 0.0;
+        chunk_zero(v);
         if (term)
         {
             const double w = rk_drho(k.rk, x);
             if (role == 1)
             {
                 unary_block(y, O, w, v);
-                v[21] = -(w * (y[1] * q[2] - y[2] * q[1]));
-                v[22] = -(w * (y[2] * q[0] - y[0] * q[2]));
-                v[23] = -(w * (y[0] * q[1] - y[1] * q[0]));
-                v[24] = -(w * q[0]), v[25] = -(w * q[1]), v[26] = -(w * q[2]);
+                unary_b(y, q, -w, v);
             }
             else
             {
@@ -171,10 +126,7 @@ __device__ __forceinline__ double pair_edge(const PairArgs& k, int e, int a, int
                     for (int i = 0; i < 3; i++)
                         qp[i] = M[0][i] * q[0] + M[1][i] * q[1] + M[2][i] * q[2];
                     unary_block(pp, Op, w, v);
-                    v[21] = w * (pp[1] * qp[2] - pp[2] * qp[1]);
-                    v[22] = w * (pp[2] * qp[0] - pp[0] * qp[2]);
-                    v[23] = w * (pp[0] * qp[1] - pp[1] * qp[0]);
-                    v[24] = w * qp[0], v[25] = w * qp[1], v[26] = w * qp[2];
+                    unary_b(pp, qp, w, v);
                 }
                 else
                 {
@@ -203,90 +155,28 @@ __device__ __forceinline__ double pair_edge(const PairArgs& k, int e, int a, int
     return chi;
 }
 
-// One wave per (chunk of ICP_CHUNK sorted edges, role).  FULL: the role's partials, role 0 also chi2; otherwise (role 0
-// alone is launched) chi2 only: element 27 of role 0's slots, the same value FULL writes there, the chunk total and,
-// with edge_chi, the chi2 term of every edge.
+// One wave per (chunk of ICP_CHUNK sorted edges, role): pose_chunks.h's chunk_walk keyed by run, on the role's part of
+// the partials.  FULL: the role's partials, role 0 also chi2; otherwise (role 0 alone is launched) chi2 only: element 27
+// of role 0's slots, the chunk total and, with edge_chi, the chi2 term of every edge.
 template <bool FULL, int role>
 __device__ __forceinline__ void pair_chunks(const PairArgs& k)
 {
     const int c = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 6);
-    if (c >= (k.n + ICP_CHUNK - 1) / ICP_CHUNK)
+    if (c >= chunk_count(k.n))
         return;
-    const int lane = threadIdx.x & 63;
-    const int e0 = c * ICP_CHUNK, e1 = min(k.n, e0 + ICP_CHUNK);
     double* const part = k.part + (size_t)role * pair_slots(k) * ICP_NP;
-    int rcur = k.plan.edge_run[e0]; // (wave-uniform)
-    double acc[32];
-#pragma unroll
-    for (int i = 0; i < 32; i++)
-        acc[i] = 0.0;
-    double chi_acc = 0.0, chunk_chi = 0.0;
-    auto flush = [&](int r) {
-        double* out = part + (size_t)(c + r) * ICP_NP;
-        if (role == 0)
-        {
-            const double cs = icp_wave_sum(chi_acc);
-            chunk_chi += cs; // (the same value in every lane)
-            if (lane == 0)
-                out[27] = cs;
-            chi_acc = 0.0;
-        }
-        if (FULL)
-        {
-            icp_wave_reduce32(acc);
-            if (!(lane & 1) && (lane >> 1) < 27)
-                out[lane >> 1] = acc[0];
-#pragma unroll
-            for (int i = 0; i < 32; i++)
-                acc[i] = 0.0;
-        }
-    };
-    for (int base = e0; base < e1; base += 64)
-    {
-        const int e = base + lane;
-        const bool in = e < e1;
-        const int r = in ? k.plan.edge_run[e] : INT_MAX;
+    chunk_walk<FULL, role == 0, true>(k.n, k.plan.edge_run, c, part, k.cchi, k.edge_chi, [&](int e, bool in, int r, double (&v)[32]) {
         const int f = in ? k.plan.run_flags[r] : 0;
         const bool live = (f & RUN_COUNTS) && !(k.flags && (k.flags[e] & CUGO_EDGE_INACTIVE));
         // the role's destination exists: a free end's own block; the off-diagonal block of two free ends
         const int need = role == 0 ? RUN_A_FREE : role == 1 ? RUN_B_FREE : (RUN_A_FREE | RUN_B_FREE);
         const bool term = live && (f & need) == need;
-        double v[32];
-        double chi = 0.0;
         if (FULL ? term || (role == 0 && live) : live)
-            chi = pair_edge<FULL, role>(k, e, k.pose_a[e], k.pose_b[e], term, v);
-        else if (FULL)
-        {
-#pragma unroll
-            for (int i = 0; i < 27; i++)
-                v[i] = 0.0;
-        }
-        if (!FULL && k.edge_chi && in)
-            k.edge_chi[e] = chi;
-        // the runs of the 64 lanes ascend: the lanes of each run in turn join the wave's accumulators
-        for (;;)
-        {
-            if (r == rcur)
-            {
-                chi_acc += chi;
-                if (FULL)
-                {
-#pragma unroll
-                    for (int i = 0; i < 27; i++)
-                        acc[i] += v[i];
-                }
-            }
-            const unsigned long long later = __ballot(in && r > rcur);
-            if (later == 0)
-                break;
-            const int rn = __shfl(r, __ffsll((long long)later) - 1, 64);
-            flush(rcur);
-            rcur = rn;
-        }
-    }
-    flush(rcur);
-    if (role == 0 && lane == 0)
-        k.cchi[c] = chunk_chi;
+            return pair_edge<FULL, role>(k, e, k.pose_a[e], k.pose_b[e], term, v);
+        if (FULL)
+            chunk_zero(v);
+        return 0.0;
+    });
 }
 
 // the role is blockIdx.y (uniform over the workgroup); every role is an instantiation of its own, so that the kernel's
@@ -306,36 +196,27 @@ __global__ __launch_bounds__(ICP_WG) void k_point_pair_chunks_errors(PairArgs a)
 // element t of run r's partials of `role`, summed in chunk order
 __device__ __forceinline__ double run_sum(const PairArgs& k, int role, int r, int t)
 {
-    const double* __restrict__ part = k.part + (size_t)role * pair_slots(k) * ICP_NP;
-    const int i0 = k.plan.run_ptr[r], i1 = k.plan.run_ptr[r + 1];
-    double s = 0.0;
-    for (int c = i0 / ICP_CHUNK, c1 = (i1 - 1) / ICP_CHUNK; c <= c1; c++)
-        s += part[(size_t)(c + r) * ICP_NP + t];
-    return s;
+    return chunk_key_sum<false>(k.plan.run_ptr, k.part + (size_t)role * pair_slots(k) * ICP_NP, r, t);
 }
 
-// 32 threads per free pose; thread t < 27 adds element t of the pose's sums — over its (run, side) entries in incidence
-// order, each over its chunks in order — to Hpp / bp or, SCHUR, to the diagonal block of Hsc, to bp and to bsc
+// the finishing pass (pose_chunks.h: chunk_finish) over the free poses with an incidence: a pose's sum runs over its
+// (run, side) entries in incidence order, each over its chunks in order
 template <bool SCHUR>
 __global__ __launch_bounds__(ICP_WG) void k_point_pair_finish(PairArgs a, double* __restrict__ H, const int32_t* __restrict__ rowptr,
                                                                double* __restrict__ bp, double* __restrict__ bsc)
 {
-    const int p = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 5), t = threadIdx.x & 31;
-    if (p >= a.plan.n_poses_free || t >= 27)
-        return;
-    const int j0 = a.plan.inc_ptr[p], j1 = a.plan.inc_ptr[p + 1];
-    if (j0 == j1)
-        return; // (nothing to add: the pose's blocks keep their bits)
-    double s = 0.0;
-    for (int j = j0; j < j1; j++)
-    {
-        const int rs = a.plan.inc[j];
-        s += run_sum(a, rs & 1, rs >> 1, t);
-    }
-    int r = 0, c = 0;
-    if (t < 21)
-        tri6_unpack(t, r, c);
-    pose_term_add<SCHUR>(p, t, r, c, s, H, rowptr, bp, bsc);
+    chunk_finish<SCHUR>(
+        a.plan.n_poses_free, [&](int p) { return a.plan.inc_ptr[p] != a.plan.inc_ptr[p + 1]; },
+        [&](int p, int t) {
+            double s = 0.0;
+            for (int j = a.plan.inc_ptr[p], j1 = a.plan.inc_ptr[p + 1]; j < j1; j++)
+            {
+                const int rs = a.plan.inc[j];
+                s += run_sum(a, rs & 1, rs >> 1, t);
+            }
+            return s;
+        },
+        H, rowptr, bp, bsc);
 }
 
 // 64 threads per touched block; thread t < 36 adds element t (column-major: row t % 6 of pose lo, column t / 6 of pose
@@ -370,20 +251,8 @@ __global__ __launch_bounds__(ICP_WG) void k_point_pair_check(const int32_t* __re
     }
 }
 
-struct PairLayout
-{
-    size_t chunks, slots, cchi, end;
-    PairLayout(int n, int n_runs)
-    {
-        chunks = (size_t)(n + ICP_CHUNK - 1) / ICP_CHUNK;
-        slots = chunks + (size_t)n_runs;
-        cchi = N_ROLES * slots * ICP_NP;
-        end = cchi + chunks;
-    }
-};
-
 PairArgs args_of(const cugo_point_pair_edges& ev, const cugo_k::PointPairPlanDev& plan, const double* d_poses,
-                 cugo_k::PointPairScratch ps, double* d_edge_chi)
+                 cugo_k::ChunkScratch ps, double* d_edge_chi)
 {
     return PairArgs{ev.n,      ev.d_pose_a, ev.d_pose_b,          ev.d_p, ev.d_z,    ev.d_info, ev.n_info,
                     ev.d_flags, Robust{ev.rk, ev.delta}, plan, ps.d_part, ps.d_cchi, d_poses,   d_edge_chi};
@@ -394,16 +263,14 @@ PairArgs args_of(const cugo_point_pair_edges& ev, const cugo_k::PointPairPlanDev
 namespace cugo_k
 {
 
-size_t point_pair_scratch_doubles(int n, int n_runs) { return PairLayout(n, n_runs).end; }
-size_t point_pair_partial_doubles(int n, int n_runs) { return PairLayout(n, n_runs).cchi; }
-int point_pair_chunk_count(int n) { return (n + ICP_CHUNK - 1) / ICP_CHUNK; }
+size_t point_pair_scratch_doubles(int n, int n_runs) { return ChunkLayout(n, n_runs, N_ROLES).end; }
+size_t point_pair_partial_doubles(int n, int n_runs) { return ChunkLayout(n, n_runs, N_ROLES).cchi; }
+int point_pair_chunk_count(int n) { return chunk_count(n); }
 
-PointPairScratch point_pair_scratch_in(ReduceScratch rs, int n, int n_runs)
+ChunkScratch point_pair_scratch_in(ReduceScratch rs, int n, int n_runs)
 {
-    const PairLayout lay(n, n_runs);
-    if (rs.capacity < lay.end)
-        throw std::runtime_error("cugo: point pair edge scratch too small");
-    return PointPairScratch{rs.d_partials, rs.d_partials + lay.cchi};
+    const ChunkLayout lay(n, n_runs, N_ROLES);
+    return chunk_scratch_in(rs, lay.cchi, lay.end, "point pair edge");
 }
 
 int point_pair_check_indices(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, int* d_bad)
@@ -422,13 +289,13 @@ int point_pair_check_indices(hipStream_t s, const cugo_point_pair_edges& ev, con
 }
 
 void launch_point_pair_chunks(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, const double* d_poses,
-                              bool full, PointPairScratch rs, double* d_edge_chi)
+                              bool full, ChunkScratch rs, double* d_edge_chi)
 {
-    const size_t waves = PairLayout(ev.n, plan.n_runs).chunks;
+    const size_t waves = (size_t)chunk_count(ev.n);
     if (waves == 0)
         return;
     const PairArgs a = args_of(ev, plan, d_poses, rs, full ? nullptr : d_edge_chi);
-    const unsigned grid = (unsigned)((waves * 64 + ICP_WG - 1) / ICP_WG);
+    const unsigned grid = chunk_grid(waves);
     if (full)
         CUGO_LAUNCH(k_point_pair_chunks_build, dim3(grid, N_ROLES), dim3(ICP_WG), 0, s, a);
     else
@@ -436,12 +303,12 @@ void launch_point_pair_chunks(hipStream_t s, const cugo_point_pair_edges& ev, co
 }
 
 static void launch_finish(hipStream_t s, const char* label, bool schur, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan,
-                          PointPairScratch rs, double* d_H, const int32_t* d_rowptr, double* d_bp, double* d_bsc)
+                          ChunkScratch rs, double* d_H, const int32_t* d_rowptr, double* d_bp, double* d_bsc)
 {
     if (plan.n_poses_free <= 0 || ev.n == 0)
         return;
     const PairArgs a = args_of(ev, plan, nullptr, rs, nullptr);
-    const unsigned grid = (unsigned)((32 * (size_t)plan.n_poses_free + ICP_WG - 1) / ICP_WG);
+    const unsigned grid = finish_grid(plan.n_poses_free);
     LaunchScope scope(label, s);
     if (schur)
         hipLaunchKernelGGL(k_point_pair_finish<true>, dim3(grid), dim3(ICP_WG), 0, s, a, d_H, d_rowptr, d_bp, d_bsc);
@@ -449,19 +316,19 @@ static void launch_finish(hipStream_t s, const char* label, bool schur, const cu
         hipLaunchKernelGGL(k_point_pair_finish<false>, dim3(grid), dim3(ICP_WG), 0, s, a, d_H, d_rowptr, d_bp, d_bsc);
 }
 
-void launch_point_pair_add_diag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+void launch_point_pair_add_diag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,
                                 double* d_Hpp, double* d_bp)
 {
     launch_finish(s, "k_point_pair_add", false, ev, plan, rs, d_Hpp, nullptr, d_bp, nullptr);
 }
 
 void launch_point_pair_add_diag_schur(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan,
-                                      PointPairScratch rs, const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc)
+                                      ChunkScratch rs, const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc)
 {
     launch_finish(s, "k_point_pair_add_schur", true, ev, plan, rs, d_Hsc, d_rowptr, d_bp, d_bsc);
 }
 
-void launch_point_pair_add_offdiag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+void launch_point_pair_add_offdiag(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,
                                    double* d_H)
 {
     if (plan.n_blocks <= 0 || ev.n == 0)
@@ -471,7 +338,7 @@ void launch_point_pair_add_offdiag(hipStream_t s, const cugo_point_pair_edges& e
     CUGO_LAUNCH(k_point_pair_offdiag, dim3(grid), dim3(ICP_WG), 0, s, a, d_H);
 }
 
-void launch_point_pair_add(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+void launch_point_pair_add(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,
                            double* d_Hpp, double* d_bp, double* d_Hoff)
 {
     launch_point_pair_add_diag(s, ev, plan, rs, d_Hpp, d_bp);
@@ -479,14 +346,14 @@ void launch_point_pair_add(hipStream_t s, const cugo_point_pair_edges& ev, const
         launch_point_pair_add_offdiag(s, ev, plan, rs, d_Hoff);
 }
 
-void launch_point_pair_add_schur(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, PointPairScratch rs,
+void launch_point_pair_add_schur(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,
                                  const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc)
 {
     launch_point_pair_add_diag_schur(s, ev, plan, rs, d_rowptr, d_Hsc, d_bp, d_bsc);
     launch_point_pair_add_offdiag(s, ev, plan, rs, d_Hsc);
 }
 
-void launch_point_pair_chi_total(hipStream_t s, const cugo_point_pair_edges& ev, PointPairScratch rs, double* d_chi, bool chi_add)
+void launch_point_pair_chi_total(hipStream_t s, const cugo_point_pair_edges& ev, ChunkScratch rs, double* d_chi, bool chi_add)
 {
     launch_pose_chi_total(s, "k_point_pair_chi_total", rs.d_cchi, point_pair_chunk_count(ev.n), d_chi, chi_add);
 }
