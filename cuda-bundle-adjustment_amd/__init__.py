@@ -166,6 +166,26 @@ class PointPairEdges(C.Structure):
                 ("plan", C.c_void_p)]
 
 
+class GicpEdges(C.Structure):
+    """cugo_gicp_edges: the covariance form of PointEdges (generalised ICP, cugo_hip.h): d_cov_p, d_cov_z [6][n_cov], the
+    upper triangles of C_p (world frame) and C_z (the pose's frame), n_cov = n or 1; Omega = (C_z + R C_p R^T)^-1 is formed
+    at the poses of every pass."""
+    _fields_ = [("n_poses_total", C.c_int), ("n_poses_free", C.c_int), ("n", C.c_int),
+                ("d_pose", C.c_void_p), ("d_pose_ptr", C.c_void_p), ("d_p", C.c_void_p), ("d_z", C.c_void_p),
+                ("d_cov_p", C.c_void_p), ("d_cov_z", C.c_void_p), ("n_cov", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int),
+                ("delta", C.c_double)]
+
+
+class GicpPairEdges(C.Structure):
+    """cugo_gicp_pair_edges: the covariance form of PointPairEdges in the SORTED order of their plan (PointPairPlan: the
+    plan does not depend on the form): d_cov_p (a's frame), d_cov_z (b's frame) [6][n_cov], n_cov = n or 1; Omega =
+    (C_z + M C_p M^T)^-1 with M = R_b R_a^T is formed at the poses of every pass."""
+    _fields_ = [("n_poses_total", C.c_int), ("n_poses_free", C.c_int), ("n", C.c_int),
+                ("d_pose_a", C.c_void_p), ("d_pose_b", C.c_void_p), ("d_p", C.c_void_p), ("d_z", C.c_void_p),
+                ("d_cov_p", C.c_void_p), ("d_cov_z", C.c_void_p), ("n_cov", C.c_int), ("d_flags", C.c_void_p), ("rk", C.c_int),
+                ("delta", C.c_double), ("plan", C.c_void_p)]
+
+
 class HscStruct(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("d_rowptr", C.c_void_p), ("d_colind", C.c_void_p),
                 ("d_off_ptr", C.c_void_p), ("d_off_ei", C.c_void_p), ("d_off_ej", C.c_void_p),
@@ -283,6 +303,21 @@ def point_construct_quadratic_form(ctx, ev, d_poses, d_Hpp, d_bp, d_chi=None):
 def point_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
     """cugo_point_construct_quadratic_form_schur: as icp_construct_quadratic_form_schur, for PointEdges"""
     check(lib().cugo_point_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def gicp_compute_errors(ctx, ev, d_poses, d_chi, d_edge_chi=None):
+    """cugo_gicp_compute_errors: as point_compute_errors, for GicpEdges (Omega formed at d_poses)"""
+    check(lib().cugo_gicp_compute_errors(ctx, C.byref(ev), d_poses, d_chi, d_edge_chi))
+
+
+def gicp_construct_quadratic_form(ctx, ev, d_poses, d_Hpp, d_bp, d_chi=None):
+    """cugo_gicp_construct_quadratic_form: as point_construct_quadratic_form, for GicpEdges"""
+    check(lib().cugo_gicp_construct_quadratic_form(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_chi))
+
+
+def gicp_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
+    """cugo_gicp_construct_quadratic_form_schur: as point_construct_quadratic_form_schur, for GicpEdges"""
+    check(lib().cugo_gicp_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
 
 
 def lm_prior_compute_errors(ctx, ev, d_lms, d_chi, d_edge_chi=None):
@@ -496,6 +531,32 @@ def point_pair_construct_quadratic_form_diag(ctx, ev, d_poses, d_Hpp, d_bp, d_ch
 def point_pair_add_offdiag_schur(ctx, ev, d_Hsc):
     """cugo_point_pair_add_offdiag_schur: the off-diagonal sums of the last build pass ADDED to d_Hsc by block index"""
     check(lib().cugo_point_pair_add_offdiag_schur(ctx, C.byref(ev), d_Hsc))
+
+
+def gicp_pair_compute_errors(ctx, ev, d_poses, d_chi, d_edge_chi=None):
+    """cugo_gicp_pair_compute_errors: as point_pair_compute_errors, for GicpPairEdges (Omega formed at d_poses)"""
+    check(lib().cugo_gicp_pair_compute_errors(ctx, C.byref(ev), d_poses, d_chi, d_edge_chi))
+
+
+def gicp_pair_construct_quadratic_form(ctx, ev, d_poses, d_Hpp, d_bp, d_Hoff, d_chi=None):
+    """cugo_gicp_pair_construct_quadratic_form: as point_pair_construct_quadratic_form, for GicpPairEdges"""
+    check(lib().cugo_gicp_pair_construct_quadratic_form(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_Hoff, d_chi))
+
+
+def gicp_pair_construct_quadratic_form_schur(ctx, ev, d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi=None):
+    """cugo_gicp_pair_construct_quadratic_form_schur: the same terms into the Schur destination"""
+    check(lib().cugo_gicp_pair_construct_quadratic_form_schur(ctx, C.byref(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi))
+
+
+def gicp_pair_construct_quadratic_form_diag(ctx, ev, d_poses, d_Hpp, d_bp, d_chi=None):
+    """cugo_gicp_pair_construct_quadratic_form_diag: the diagonal terms and b alone; the off-diagonal partials stay in
+    the plan's scratch"""
+    check(lib().cugo_gicp_pair_construct_quadratic_form_diag(ctx, C.byref(ev), d_poses, d_Hpp, d_bp, d_chi))
+
+
+def gicp_pair_add_offdiag_schur(ctx, ev, d_Hsc):
+    """cugo_gicp_pair_add_offdiag_schur: the off-diagonal sums of the last build pass ADDED to d_Hsc by block index"""
+    check(lib().cugo_gicp_pair_add_offdiag_schur(ctx, C.byref(ev), d_Hsc))
 
 
 def pose_edges_reject(ctx, n, d_edge_chi, d_threshold, n_threshold, d_flags, d_rejected):
@@ -988,6 +1049,94 @@ class Graph:
         if rc < 0:
             check(rc)
         return dict(pose_a=pa, pose_b=pb, src=src, p=p, z=z, info=info, n_info=ni.value)
+
+    @staticmethod
+    def _cov9(c, n):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(c, np.float64).reshape(-1, 9), (n, 9)))
+
+    def add_gicp_edges(self, pose_ids, pointP, pointZ, covP9, covZ9):
+        """covariance-form point edges (an extension; GicpEdgeSet, generalised ICP against a fixed map): known points
+        pointP [n, 3] with covariances covP9 [n, 3, 3] in the world frame, their measurements pointZ with covZ9 in the
+        pose's frame (one 3 x 3 serves all); Omega = (C_z + R C_p R^T)^-1 is rebuilt at every linearisation and trial of
+        optimize().  An unknown pose id refuses the whole call"""
+        n = len(pose_ids)
+        if n == 0:
+            return
+        ids = np.ascontiguousarray(pose_ids, np.int32)
+        p = np.ascontiguousarray(np.asarray(pointP, np.float64).reshape(n, 3))
+        z = np.ascontiguousarray(np.asarray(pointZ, np.float64).reshape(n, 3))
+        cp, cz = self._cov9(covP9, n), self._cov9(covZ9, n)
+        check(lib().cugo_graph_add_gicp_edges(self._g, n, _p(ids, _i32p), _p(p, _f64p), _p(z, _f64p), _p(cp, _f64p), _p(cz, _f64p)))
+
+    def add_gicp_pair_edges(self, pose_ids_a, pose_ids_b, pointP, pointZ, covP9, covZ9):
+        """covariance-form pose-pose point edges (an extension; GicpPairEdgeSet, scan-to-scan generalised ICP): pointP,
+        covP9 in pose a's frame, pointZ, covZ9 in pose b's; Omega = (C_z + M C_p M^T)^-1 with M = R_b R_a^T follows the
+        poses inside optimize().  An unknown pose id or a == b refuses the whole call"""
+        n = len(pose_ids_a)
+        if n == 0:
+            return
+        ia, ib = np.ascontiguousarray(pose_ids_a, np.int32), np.ascontiguousarray(pose_ids_b, np.int32)
+        if len(ib) != n:
+            raise ValueError("pose_ids_a and pose_ids_b must have the same length")
+        p = np.ascontiguousarray(np.asarray(pointP, np.float64).reshape(n, 3))
+        z = np.ascontiguousarray(np.asarray(pointZ, np.float64).reshape(n, 3))
+        cp, cz = self._cov9(covP9, n), self._cov9(covZ9, n)
+        check(lib().cugo_graph_add_gicp_pair_edges(self._g, n, _p(ia, _i32p), _p(ib, _i32p), _p(p, _f64p), _p(z, _f64p),
+                                                   _p(cp, _f64p), _p(cz, _f64p)))
+
+    def set_gicp_robust_kernel(self, rk_type, delta):
+        check(lib().cugo_graph_set_gicp_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
+
+    def set_gicp_pair_robust_kernel(self, rk_type, delta):
+        check(lib().cugo_graph_set_gicp_pair_robust_kernel(self._g, int(rk_type), C.c_double(delta)))
+
+    def set_gicp_outlier_threshold(self, threshold):
+        """initialize() refuses a positive one (outlier rejection on the set: not yet)"""
+        check(lib().cugo_graph_set_gicp_outlier_threshold(self._g, C.c_double(threshold)))
+
+    def set_gicp_pair_outlier_threshold(self, threshold):
+        """initialize() refuses a positive one (outlier rejection on the set: not yet)"""
+        check(lib().cugo_graph_set_gicp_pair_outlier_threshold(self._g, C.c_double(threshold)))
+
+    def set_gicp_pair_active(self, active, first=0):
+        """active flags of the covariance-form pair edges first, first + 1, ...; takes effect at the next initialize()"""
+        a = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
+        check(lib().cugo_graph_set_gicp_pair_active(self._g, int(first), len(a), _p(a, _u8p)))
+
+    def n_gicp_edges(self):
+        return lib().cugo_graph_n_gicp_edges(self._g)
+
+    def n_gicp_pair_edges(self):
+        return lib().cugo_graph_n_gicp_pair_edges(self._g)
+
+    def flat_gicp_edges(self):
+        """the covariance-form point edges of the current flattening as the kernels read them (a diagnostic; works on a
+        plan-only graph): dict(pose, src [n], p, z [3, n], cov_p, cov_z [6, n_cov] packed upper triangles, n_cov = n or 1)"""
+        nc = C.c_int(0)
+        n = lib().cugo_graph_get_flat_gicp_edges(self._g, 0, None, None, None, None, None, None, C.byref(nc))
+        if n < 0:
+            check(n)
+        pose, src = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        p, z, cp, cz = np.zeros((3, n)), np.zeros((3, n)), np.zeros((6, nc.value)), np.zeros((6, nc.value))
+        rc = lib().cugo_graph_get_flat_gicp_edges(self._g, n, _p(pose, _i32p), _p(src, _i32p), _p(p, _f64p), _p(z, _f64p),
+                                                  _p(cp, _f64p), _p(cz, _f64p), C.byref(nc))
+        if rc < 0:
+            check(rc)
+        return dict(pose=pose, src=src, p=p, z=z, cov_p=cp, cov_z=cz, n_cov=nc.value)
+
+    def flat_gicp_pair_edges(self):
+        """as flat_point_pair_edges, with cov_p, cov_z [6, n_cov] in place of info"""
+        nc = C.c_int(0)
+        n = lib().cugo_graph_get_flat_gicp_pair_edges(self._g, 0, None, None, None, None, None, None, None, C.byref(nc))
+        if n < 0:
+            check(n)
+        pa, pb, src = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        p, z, cp, cz = np.zeros((3, n)), np.zeros((3, n)), np.zeros((6, nc.value)), np.zeros((6, nc.value))
+        rc = lib().cugo_graph_get_flat_gicp_pair_edges(self._g, n, _p(pa, _i32p), _p(pb, _i32p), _p(src, _i32p), _p(p, _f64p),
+                                                       _p(z, _f64p), _p(cp, _f64p), _p(cz, _f64p), C.byref(nc))
+        if rc < 0:
+            check(rc)
+        return dict(pose_a=pa, pose_b=pb, src=src, p=p, z=z, cov_p=cp, cov_z=cz, n_cov=nc.value)
 
     def add_relpose_edges(self, pose_ids_a, pose_ids_b, q_t7, info36=None):
         """relative-pose SE(3) edges (an extension; RelPoseEdgeSet): residual [Log_SO3(R_D); t_D] of D = T_a T_b^-1 Z^-1

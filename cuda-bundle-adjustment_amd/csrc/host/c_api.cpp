@@ -11,6 +11,7 @@
 #include "../../include/icp_types.h"
 #include "../../include/landmark_prior_types.h"
 #include "../../include/point_edge_types.h"
+#include "../../include/gicp_types.h"
 #include "../../include/point_pair_types.h"
 #include "../../include/prior_types.h"
 #include "../../include/relpose_types.h"
@@ -311,18 +312,67 @@ int cugo_icp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_icp_edges*
 
 namespace
 {
-// as check_icp, for the one kind of the point edges
-cugo_k::ChunkScratch check_point(cugo_ctx* ctx, const cugo_point_edges* ev)
+// as check_icp, for the one kind of the point edges.  Both forms come here as a cugo_point_edges view: the covariance
+// form (cugo_gicp_edges) with d_info = cov_p, n_info = n_cov and its cov_z beside it (PointView)
+struct PointView
 {
-    if (!ev || ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total || ev->n < 0)
-        throw std::runtime_error("cugo_point: bad pose or edge counts");
+    cugo_point_edges ev;
+    const double* d_cov_z; // nullptr: the information form
+    bool cov;
+    const char* who;
+};
+const cugo_point_edges NO_POINT_EDGES = {-1, -1, -1, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0.0}; // (refused)
+PointView view_of(const cugo_point_edges* ev) { return {ev ? *ev : NO_POINT_EDGES, nullptr, false, "cugo_point"}; }
+PointView view_of(const cugo_gicp_edges* g)
+{
+    if (!g)
+        return {NO_POINT_EDGES, nullptr, true, "cugo_gicp"};
+    return {{g->n_poses_total, g->n_poses_free, g->n, g->d_pose, g->d_pose_ptr, g->d_p, g->d_z, g->d_cov_p, g->n_cov, g->d_flags,
+             g->rk, g->delta},
+            g->d_cov_z, true, "cugo_gicp"};
+}
+cugo_k::ChunkScratch check_point(cugo_ctx* ctx, const PointView& v)
+{
+    const cugo_point_edges* ev = &v.ev;
+    if (ev->n_poses_total < 0 || ev->n_poses_free < 0 || ev->n_poses_free > ev->n_poses_total || ev->n < 0)
+        throw std::runtime_error(std::string(v.who) + ": bad pose or edge counts");
     const size_t need = cugo_k::point_scratch_doubles(*ev);
     const cugo_k::ReduceScratch rs = pose_scratch_for(ctx, need);
-    check_pose_kind(ctx, "cugo_point", "", ev->n, ev->n_poses_total, ev->d_pose, ev->d_pose_ptr, ev->rk, ev->delta,
-                    !ev->d_p || !ev->d_z || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n));
-    check_pose_indices(ctx, "cugo_point", "point", {{ev->d_pose, ev->d_pose_ptr, ev->n, "k_point_check"}}, ev->n_poses_total,
-                       rs, need);
+    check_pose_kind(ctx, v.who, "", ev->n, ev->n_poses_total, ev->d_pose, ev->d_pose_ptr, ev->rk, ev->delta,
+                    !ev->d_p || !ev->d_z || !ev->d_info || (v.cov && !v.d_cov_z) || (ev->n_info != 1 && ev->n_info != ev->n));
+    check_pose_indices(ctx, v.who, "point", {{ev->d_pose, ev->d_pose_ptr, ev->n, "k_point_check"}}, ev->n_poses_total, rs, need);
     return cugo_k::point_scratch_in(rs, *ev);
+}
+int point_errors(cugo_ctx* ctx, const PointView& v, const double* d_poses, double* d_chi, double* d_edge_chi)
+{
+    return guarded([&] {
+        const cugo_k::ChunkScratch rs = check_point(ctx, v);
+        cugo_k::launch_point_errors(ctx->stream, v.ev, d_poses, rs, d_chi, false, d_edge_chi, v.d_cov_z);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+int point_form(cugo_ctx* ctx, const PointView& v, const double* d_poses, double* d_Hpp, double* d_bp,
+               double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::ChunkScratch rs = check_point(ctx, v);
+        cugo_k::launch_point_build(ctx->stream, v.ev, d_poses, d_Hpp, d_bp, rs, d_chi, false, v.d_cov_z);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+int point_form_schur(cugo_ctx* ctx, const PointView& v, const double* d_poses, const int32_t* d_rowptr,
+                     double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_k::ChunkScratch rs = check_point(ctx, v);
+        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
+            throw std::runtime_error(std::string(v.who) + ": missing rowptr, Hsc, bp or bsc");
+        cugo_k::launch_point_chunks(ctx->stream, v.ev, d_poses, true, rs, nullptr, v.d_cov_z);
+        cugo_k::launch_point_add_schur(ctx->stream, v.ev, rs, d_rowptr, d_Hsc, d_bp, d_bsc);
+        if (d_chi)
+            cugo_k::launch_point_chi_total(ctx->stream, v.ev, rs, d_chi, false);
+        CUGO_HIP(hipGetLastError());
+    });
 }
 } // namespace
 
@@ -331,36 +381,32 @@ extern "C" {
 int cugo_point_compute_errors(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses, double* d_chi,
                               double* d_edge_chi)
 {
-    return guarded([&] {
-        const cugo_k::ChunkScratch rs = check_point(ctx, ev);
-        cugo_k::launch_point_errors(ctx->stream, *ev, d_poses, rs, d_chi, false, d_edge_chi);
-        CUGO_HIP(hipGetLastError());
-    });
+    return point_errors(ctx, view_of(ev), d_poses, d_chi, d_edge_chi);
 }
-
 int cugo_point_construct_quadratic_form(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses, double* d_Hpp,
                                         double* d_bp, double* d_chi)
 {
-    return guarded([&] {
-        const cugo_k::ChunkScratch rs = check_point(ctx, ev);
-        cugo_k::launch_point_build(ctx->stream, *ev, d_poses, d_Hpp, d_bp, rs, d_chi, false);
-        CUGO_HIP(hipGetLastError());
-    });
+    return point_form(ctx, view_of(ev), d_poses, d_Hpp, d_bp, d_chi);
 }
-
 int cugo_point_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_point_edges* ev, const double* d_poses,
                                               const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi)
 {
-    return guarded([&] {
-        const cugo_k::ChunkScratch rs = check_point(ctx, ev);
-        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
-            throw std::runtime_error("cugo_point: missing rowptr, Hsc, bp or bsc");
-        cugo_k::launch_point_chunks(ctx->stream, *ev, d_poses, true, rs);
-        cugo_k::launch_point_add_schur(ctx->stream, *ev, rs, d_rowptr, d_Hsc, d_bp, d_bsc);
-        if (d_chi)
-            cugo_k::launch_point_chi_total(ctx->stream, *ev, rs, d_chi, false);
-        CUGO_HIP(hipGetLastError());
-    });
+    return point_form_schur(ctx, view_of(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi);
+}
+
+int cugo_gicp_compute_errors(cugo_ctx* ctx, const cugo_gicp_edges* ev, const double* d_poses, double* d_chi, double* d_edge_chi)
+{
+    return point_errors(ctx, view_of(ev), d_poses, d_chi, d_edge_chi);
+}
+int cugo_gicp_construct_quadratic_form(cugo_ctx* ctx, const cugo_gicp_edges* ev, const double* d_poses, double* d_Hpp,
+                                       double* d_bp, double* d_chi)
+{
+    return point_form(ctx, view_of(ev), d_poses, d_Hpp, d_bp, d_chi);
+}
+int cugo_gicp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_gicp_edges* ev, const double* d_poses,
+                                             const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc, double* d_chi)
+{
+    return point_form_schur(ctx, view_of(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi);
 }
 
 } // extern "C"
@@ -757,39 +803,60 @@ struct cugo_point_pair_plan
 
 namespace
 {
+// Both forms come here as a cugo_point_pair_edges view: the covariance form (cugo_gicp_pair_edges) with d_info = cov_p,
+// n_info = n_cov and its cov_z beside it
+struct PairView
+{
+    cugo_point_pair_edges ev;
+    const double* d_cov_z; // nullptr: the information form
+    bool cov;
+    std::string who;
+};
+const cugo_point_pair_edges NO_PAIR_EDGES = {0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0.0, nullptr}; // (refused)
+PairView view_of(const cugo_point_pair_edges* ev) { return {ev ? *ev : NO_PAIR_EDGES, nullptr, false, "cugo_point_pair"}; }
+PairView view_of(const cugo_gicp_pair_edges* g)
+{
+    if (!g)
+        return {NO_PAIR_EDGES, nullptr, true, "cugo_gicp_pair"};
+    return {{g->n_poses_total, g->n_poses_free, g->n, g->d_pose_a, g->d_pose_b, g->d_p, g->d_z, g->d_cov_p, g->n_cov, g->d_flags,
+             g->rk, g->delta, g->plan},
+            g->d_cov_z, true, "cugo_gicp_pair"};
+}
 // counts against the plan, arrays, kernel code on the host; with check_indices, pose a / b of every edge against the
 // plan's runs on the device
-cugo_k::ChunkScratch check_point_pair(cugo_ctx* ctx, const cugo_point_pair_edges* ev, bool check_indices = true)
+cugo_k::ChunkScratch check_point_pair(cugo_ctx* ctx, const PairView& v, bool check_indices = true)
 {
+    const cugo_point_pair_edges* ev = &v.ev;
     if (!ctx)
-        throw std::runtime_error("cugo_point_pair: no context");
-    if (!ev || !ev->plan)
-        throw std::runtime_error("cugo_point_pair: no edges or no plan (cugo_point_pair_plan_create)");
+        throw std::runtime_error(v.who + ": no context");
+    if (!ev->plan)
+        throw std::runtime_error(v.who + ": no edges or no plan (cugo_point_pair_plan_create)");
     const cugo_host::PointPairPlanHost& h = ev->plan->host;
     if (ev->n != h.n || ev->n_poses_total != h.n_poses_total || ev->n_poses_free != h.n_poses_free)
-        throw std::runtime_error("cugo_point_pair: the pose or edge counts are not those of the plan");
+        throw std::runtime_error(v.who + ": the pose or edge counts are not those of the plan");
     if (!ev->plan->on_device)
-        throw std::runtime_error("cugo_point_pair: the plan is host-only (created without a context)");
+        throw std::runtime_error(v.who + ": the plan is host-only (created without a context)");
     if (!ev->plan->has_pattern)
-        throw std::runtime_error("cugo_point_pair: the plan was built without a pattern");
+        throw std::runtime_error(v.who + ": the plan was built without a pattern");
     if (ev->rk < CUGO_RK_NONE || ev->rk > CUGO_RK_HUBER || (ev->rk != CUGO_RK_NONE && !(ev->delta > 0.0 && std::isfinite(ev->delta))))
-        throw std::runtime_error("cugo_point_pair: unknown robust kernel or bad delta");
-    if (ev->n > 0 && (!ev->d_pose_a || !ev->d_pose_b || !ev->d_p || !ev->d_z || !ev->d_info || (ev->n_info != 1 && ev->n_info != ev->n)))
-        throw std::runtime_error("cugo_point_pair: missing arrays, or n_info is neither n nor 1");
+        throw std::runtime_error(v.who + ": unknown robust kernel or bad delta");
+    if (ev->n > 0 && (!ev->d_pose_a || !ev->d_pose_b || !ev->d_p || !ev->d_z || !ev->d_info || (v.cov && !v.d_cov_z) ||
+                      (ev->n_info != 1 && ev->n_info != ev->n)))
+        throw std::runtime_error(v.who + (v.cov ? ": missing arrays, or n_cov is neither n nor 1" : ": missing arrays, or n_info is neither n nor 1"));
     const cugo_k::ChunkScratch rs = ev->plan->pair_scratch();
     if (check_indices &&
         cugo_k::point_pair_check_indices(ctx->stream, *ev, ev->plan->dev(),
                                          reinterpret_cast<int*>(ev->plan->scratch.data() + cugo_k::point_pair_scratch_doubles(h.n, ev->plan->n_runs()))))
-        throw std::runtime_error("cugo_point_pair: pose a or pose b of an edge is not that of its run: the edges are not in the plan's order");
+        throw std::runtime_error(v.who + ": pose a or pose b of an edge is not that of its run: the edges are not in the plan's order");
     return rs;
 }
-void point_pair_build(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses, cugo_k::ChunkScratch rs)
+void point_pair_build(cugo_ctx* ctx, const PairView& v, const double* d_poses, cugo_k::ChunkScratch rs)
 {
     if (!d_poses)
-        throw std::runtime_error("cugo_point_pair: missing poses");
-    ev->plan->built = false;
-    cugo_k::launch_point_pair_chunks(ctx->stream, *ev, ev->plan->dev(), d_poses, true, rs);
-    ev->plan->built = true;
+        throw std::runtime_error(v.who + ": missing poses");
+    v.ev.plan->built = false;
+    cugo_k::launch_point_pair_chunks(ctx->stream, v.ev, v.ev.plan->dev(), d_poses, true, rs, nullptr, v.d_cov_z);
+    v.ev.plan->built = true;
 }
 void point_pair_chi_total(cugo_ctx* ctx, const cugo_point_pair_edges* ev, cugo_k::ChunkScratch rs, double* d_chi)
 {
@@ -801,6 +868,75 @@ void point_pair_chi_total(cugo_ctx* ctx, const cugo_point_pair_edges* ev, cugo_k
         CUGO_HIP(hipMemsetAsync(d_chi, 0, sizeof(double), ctx->stream));
 }
 bool joins_free_poses(const cugo_point_pair_edges* ev) { return !ev->plan->host.blk_id.empty(); }
+
+// the five passes of the pair kind, for either form
+int pair_errors(cugo_ctx* ctx, const PairView& v, const double* d_poses, double* d_chi, double* d_edge_chi)
+{
+    return guarded([&] {
+        const cugo_point_pair_edges* ev = &v.ev;
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, v);
+        if (!d_poses)
+            throw std::runtime_error(v.who + ": missing poses");
+        cugo_k::launch_point_pair_chunks(ctx->stream, *ev, ev->plan->dev(), d_poses, false, rs, d_edge_chi, v.d_cov_z);
+        point_pair_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+int pair_form(cugo_ctx* ctx, const PairView& v, const double* d_poses, double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_point_pair_edges* ev = &v.ev;
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, v);
+        if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
+            throw std::runtime_error(v.who + ": missing Hpp or bp");
+        if (!d_Hoff && joins_free_poses(ev))
+            throw std::runtime_error(v.who + ": missing Hoff (a counting run joins two free poses)");
+        point_pair_build(ctx, v, d_poses, rs);
+        cugo_k::launch_point_pair_add(ctx->stream, *ev, ev->plan->dev(), rs, d_Hpp, d_bp, d_Hoff);
+        point_pair_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+int pair_form_schur(cugo_ctx* ctx, const PairView& v, const double* d_poses, const int32_t* d_rowptr, double* d_Hsc, double* d_bp,
+                    double* d_bsc, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_point_pair_edges* ev = &v.ev;
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, v);
+        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
+            throw std::runtime_error(v.who + ": missing rowptr, Hsc, bp or bsc");
+        point_pair_build(ctx, v, d_poses, rs);
+        cugo_k::launch_point_pair_add_schur(ctx->stream, *ev, ev->plan->dev(), rs, d_rowptr, d_Hsc, d_bp, d_bsc);
+        point_pair_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+int pair_form_diag(cugo_ctx* ctx, const PairView& v, const double* d_poses, double* d_Hpp, double* d_bp, double* d_chi)
+{
+    return guarded([&] {
+        const cugo_point_pair_edges* ev = &v.ev;
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, v);
+        if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
+            throw std::runtime_error(v.who + ": missing Hpp or bp");
+        point_pair_build(ctx, v, d_poses, rs);
+        cugo_k::launch_point_pair_add_diag(ctx->stream, *ev, ev->plan->dev(), rs, d_Hpp, d_bp);
+        point_pair_chi_total(ctx, ev, rs, d_chi);
+        CUGO_HIP(hipGetLastError());
+    });
+}
+int pair_add_offdiag_schur(cugo_ctx* ctx, const PairView& v, double* d_Hsc)
+{
+    return guarded([&] {
+        const cugo_point_pair_edges* ev = &v.ev;
+        const cugo_k::ChunkScratch rs = check_point_pair(ctx, v, false); // (the build pass checked the indices)
+        if (!ev->plan->built)
+            throw std::runtime_error(v.who + "_add_offdiag_schur: no build pass has left its partials in the plan's scratch");
+        if (!d_Hsc)
+            throw std::runtime_error(v.who + ": missing Hsc");
+        cugo_k::launch_point_pair_add_offdiag(ctx->stream, *ev, ev->plan->dev(), rs, d_Hsc);
+        CUGO_HIP(hipGetLastError());
+    });
+}
 } // namespace
 
 extern "C" {
@@ -862,72 +998,53 @@ int cugo_point_pair_plan_array(const cugo_point_pair_plan* plan, const char* nam
 int cugo_point_pair_compute_errors(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses, double* d_chi,
                                    double* d_edge_chi)
 {
-    return guarded([&] {
-        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev);
-        if (!d_poses)
-            throw std::runtime_error("cugo_point_pair: missing poses");
-        cugo_k::launch_point_pair_chunks(ctx->stream, *ev, ev->plan->dev(), d_poses, false, rs, d_edge_chi);
-        point_pair_chi_total(ctx, ev, rs, d_chi);
-        CUGO_HIP(hipGetLastError());
-    });
+    return pair_errors(ctx, view_of(ev), d_poses, d_chi, d_edge_chi);
 }
-
 int cugo_point_pair_construct_quadratic_form(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
                                              double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi)
 {
-    return guarded([&] {
-        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev);
-        if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
-            throw std::runtime_error("cugo_point_pair: missing Hpp or bp");
-        if (!d_Hoff && joins_free_poses(ev))
-            throw std::runtime_error("cugo_point_pair: missing Hoff (a counting run joins two free poses)");
-        point_pair_build(ctx, ev, d_poses, rs);
-        cugo_k::launch_point_pair_add(ctx->stream, *ev, ev->plan->dev(), rs, d_Hpp, d_bp, d_Hoff);
-        point_pair_chi_total(ctx, ev, rs, d_chi);
-        CUGO_HIP(hipGetLastError());
-    });
+    return pair_form(ctx, view_of(ev), d_poses, d_Hpp, d_bp, d_Hoff, d_chi);
 }
-
 int cugo_point_pair_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
                                                    const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
                                                    double* d_chi)
 {
-    return guarded([&] {
-        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev);
-        if (!d_rowptr || !d_Hsc || !d_bp || !d_bsc)
-            throw std::runtime_error("cugo_point_pair: missing rowptr, Hsc, bp or bsc");
-        point_pair_build(ctx, ev, d_poses, rs);
-        cugo_k::launch_point_pair_add_schur(ctx->stream, *ev, ev->plan->dev(), rs, d_rowptr, d_Hsc, d_bp, d_bsc);
-        point_pair_chi_total(ctx, ev, rs, d_chi);
-        CUGO_HIP(hipGetLastError());
-    });
+    return pair_form_schur(ctx, view_of(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi);
 }
-
 int cugo_point_pair_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_point_pair_edges* ev, const double* d_poses,
                                                   double* d_Hpp, double* d_bp, double* d_chi)
 {
-    return guarded([&] {
-        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev);
-        if (ev->n > 0 && ev->n_poses_free > 0 && (!d_Hpp || !d_bp))
-            throw std::runtime_error("cugo_point_pair: missing Hpp or bp");
-        point_pair_build(ctx, ev, d_poses, rs);
-        cugo_k::launch_point_pair_add_diag(ctx->stream, *ev, ev->plan->dev(), rs, d_Hpp, d_bp);
-        point_pair_chi_total(ctx, ev, rs, d_chi);
-        CUGO_HIP(hipGetLastError());
-    });
+    return pair_form_diag(ctx, view_of(ev), d_poses, d_Hpp, d_bp, d_chi);
 }
-
 int cugo_point_pair_add_offdiag_schur(cugo_ctx* ctx, const cugo_point_pair_edges* ev, double* d_Hsc)
 {
-    return guarded([&] {
-        const cugo_k::ChunkScratch rs = check_point_pair(ctx, ev, false); // (the build pass checked the indices)
-        if (!ev->plan->built)
-            throw std::runtime_error("cugo_point_pair_add_offdiag_schur: no build pass has left its partials in the plan's scratch");
-        if (!d_Hsc)
-            throw std::runtime_error("cugo_point_pair: missing Hsc");
-        cugo_k::launch_point_pair_add_offdiag(ctx->stream, *ev, ev->plan->dev(), rs, d_Hsc);
-        CUGO_HIP(hipGetLastError());
-    });
+    return pair_add_offdiag_schur(ctx, view_of(ev), d_Hsc);
+}
+
+int cugo_gicp_pair_compute_errors(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, const double* d_poses, double* d_chi,
+                                  double* d_edge_chi)
+{
+    return pair_errors(ctx, view_of(ev), d_poses, d_chi, d_edge_chi);
+}
+int cugo_gicp_pair_construct_quadratic_form(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, const double* d_poses,
+                                            double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi)
+{
+    return pair_form(ctx, view_of(ev), d_poses, d_Hpp, d_bp, d_Hoff, d_chi);
+}
+int cugo_gicp_pair_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, const double* d_poses,
+                                                  const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
+                                                  double* d_chi)
+{
+    return pair_form_schur(ctx, view_of(ev), d_poses, d_rowptr, d_Hsc, d_bp, d_bsc, d_chi);
+}
+int cugo_gicp_pair_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, const double* d_poses,
+                                                 double* d_Hpp, double* d_bp, double* d_chi)
+{
+    return pair_form_diag(ctx, view_of(ev), d_poses, d_Hpp, d_bp, d_chi);
+}
+int cugo_gicp_pair_add_offdiag_schur(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, double* d_Hsc)
+{
+    return pair_add_offdiag_schur(ctx, view_of(ev), d_Hsc);
 }
 
 int cugo_max_diagonal(cugo_ctx* ctx, const double* d_Hpp, int nP, const double* d_Hll, int nL,
@@ -1438,6 +1555,10 @@ struct cugo_graph
     std::deque<cugo::PointEdge> point_store;
     cugo::PointPairEdgeSet point_pair;
     std::deque<cugo::PointPairEdge> point_pair_store;
+    cugo::GicpEdgeSet gicp;
+    std::deque<cugo::GicpEdge> gicp_store;
+    cugo::GicpPairEdgeSet gicp_pair;
+    std::deque<cugo::GicpPairEdge> gicp_pair_store;
     bool attached = false;
     void attach()
     {
@@ -1455,6 +1576,8 @@ struct cugo_graph
         opt->addEdgeSet(&depth); // (behind the others: the indices of the other sets in messages stay what they were)
         opt->addEdgeSet(&point); // (likewise)
         opt->addEdgeSet(&point_pair);
+        opt->addEdgeSet(&gicp); // (gicp_types.h: empty sets count for nothing)
+        opt->addEdgeSet(&gicp_pair);
         attached = true;
     }
 };
@@ -2116,6 +2239,135 @@ int cugo_graph_get_flat_point_pair_edges(cugo_graph* g, int cap, int32_t* pose_a
             std::copy(vz.begin(), vz.end(), z);
         if (info && n > 0)
             std::copy(vi.begin(), vi.end(), info);
+    });
+    return rc == CUGO_OK ? n : rc;
+}
+int cugo_graph_add_gicp_edges(cugo_graph* g, int n, const int32_t* pose_ids, const double* pointP, const double* pointZ,
+                              const double* covP9, const double* covZ9)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids || !pointP || !pointZ || !covP9 || !covZ9)))
+            throw std::invalid_argument("cugo_graph_add_gicp_edges: missing arrays");
+        for (int i = 0; i < n; i++) // (all or nothing: an unknown id adds no edge)
+            (void)icp_pose(g, pose_ids[i]);
+        for (int i = 0; i < n; i++)
+        {
+            g->gicp_store.emplace_back();
+            cugo::GicpEdge& e = g->gicp_store.back();
+            e.setVertex(icp_pose(g, pose_ids[i]), 0);
+            e.setMeasurement(cugo::PointCovarianceMatch<double>(pointP + 3 * (size_t)i, pointZ + 3 * (size_t)i, covP9 + 9 * (size_t)i,
+                                                                covZ9 + 9 * (size_t)i));
+            g->gicp.addEdge(&e);
+        }
+    });
+}
+int cugo_graph_add_gicp_pair_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b, const double* pointP,
+                                   const double* pointZ, const double* covP9, const double* covZ9)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && (!pose_ids_a || !pose_ids_b || !pointP || !pointZ || !covP9 || !covZ9)))
+            throw std::invalid_argument("cugo_graph_add_gicp_pair_edges: missing arrays");
+        for (int i = 0; i < n; i++) // (all or nothing: an unknown id or a == b adds no edge)
+        {
+            (void)icp_pose(g, pose_ids_a[i]), (void)icp_pose(g, pose_ids_b[i]);
+            if (pose_ids_a[i] == pose_ids_b[i])
+                throw std::invalid_argument("cugo_graph_add_gicp_pair_edges: edge " + std::to_string(i) + " joins pose " +
+                                            std::to_string(pose_ids_a[i]) + " to itself (a == b)");
+        }
+        for (int i = 0; i < n; i++)
+        {
+            g->gicp_pair_store.emplace_back();
+            cugo::GicpPairEdge& e = g->gicp_pair_store.back();
+            e.setVertex(icp_pose(g, pose_ids_a[i]), 0);
+            e.setVertex(icp_pose(g, pose_ids_b[i]), 1);
+            e.setMeasurement(cugo::PointCovarianceMatch<double>(pointP + 3 * (size_t)i, pointZ + 3 * (size_t)i, covP9 + 9 * (size_t)i,
+                                                                covZ9 + 9 * (size_t)i));
+            g->gicp_pair.addEdge(&e);
+        }
+    });
+}
+int cugo_graph_set_gicp_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    return guarded([&] { g->gicp.setRobustKernel(rk_type_of(type), delta); });
+}
+int cugo_graph_set_gicp_pair_robust_kernel(cugo_graph* g, int type, double delta)
+{
+    return guarded([&] { g->gicp_pair.setRobustKernel(rk_type_of(type), delta); });
+}
+int cugo_graph_set_gicp_outlier_threshold(cugo_graph* g, double threshold)
+{
+    return guarded([&] { g->gicp.setOutlierThreshold(threshold); });
+}
+int cugo_graph_set_gicp_pair_outlier_threshold(cugo_graph* g, double threshold)
+{
+    return guarded([&] { g->gicp_pair.setOutlierThreshold(threshold); });
+}
+int cugo_graph_set_gicp_pair_active(cugo_graph* g, int first, int n, const uint8_t* active)
+{
+    return guarded([&] {
+        if (first < 0 || n < 0 || (size_t)first + (size_t)n > g->gicp_pair_store.size() || (n > 0 && !active))
+            throw std::invalid_argument("cugo_graph_set_gicp_pair_active: bad edge range or no flags");
+        for (int i = 0; i < n; i++)
+            active[i] ? g->gicp_pair_store[(size_t)first + i].setActive() : g->gicp_pair_store[(size_t)first + i].inactivate();
+    });
+}
+int cugo_graph_n_gicp_edges(cugo_graph* g) { return g->opt->nGicpEdges(); }
+int cugo_graph_n_gicp_pair_edges(cugo_graph* g) { return g->opt->nGicpPairEdges(); }
+int cugo_graph_get_flat_gicp_edges(cugo_graph* g, int cap, int32_t* pose, int32_t* src_edge, double* p, double* z, double* cov_p,
+                                   double* cov_z, int* n_cov)
+{
+    int n = -1;
+    const int rc = guarded([&] {
+        std::vector<int> q, s;
+        std::vector<double> vp, vz, cp, cz;
+        const int nc = g->opt->flatGicpEdges(q, s, vp, vz, cp, cz);
+        n = (int)q.size();
+        if (n_cov)
+            *n_cov = nc;
+        if (cap < n)
+            return;
+        if (pose)
+            std::copy(q.begin(), q.end(), pose);
+        if (src_edge)
+            std::copy(s.begin(), s.end(), src_edge);
+        if (p)
+            std::copy(vp.begin(), vp.end(), p);
+        if (z)
+            std::copy(vz.begin(), vz.end(), z);
+        if (cov_p)
+            std::copy(cp.begin(), cp.end(), cov_p);
+        if (cov_z)
+            std::copy(cz.begin(), cz.end(), cov_z);
+    });
+    return rc == CUGO_OK ? n : rc;
+}
+int cugo_graph_get_flat_gicp_pair_edges(cugo_graph* g, int cap, int32_t* pose_a, int32_t* pose_b, int32_t* src_edge, double* p,
+                                        double* z, double* cov_p, double* cov_z, int* n_cov)
+{
+    int n = -1;
+    const int rc = guarded([&] {
+        std::vector<int> a, b, s;
+        std::vector<double> vp, vz, cp, cz;
+        const int nc = g->opt->flatGicpPairEdges(a, b, s, vp, vz, cp, cz);
+        n = (int)a.size();
+        if (n_cov)
+            *n_cov = nc;
+        if (cap < n)
+            return;
+        if (pose_a)
+            std::copy(a.begin(), a.end(), pose_a);
+        if (pose_b)
+            std::copy(b.begin(), b.end(), pose_b);
+        if (src_edge)
+            std::copy(s.begin(), s.end(), src_edge);
+        if (p)
+            std::copy(vp.begin(), vp.end(), p);
+        if (z)
+            std::copy(vz.begin(), vz.end(), z);
+        if (cov_p)
+            std::copy(cp.begin(), cp.end(), cov_p);
+        if (cov_z)
+            std::copy(cz.begin(), cz.end(), cov_z);
     });
     return rc == CUGO_OK ? n : rc;
 }

@@ -313,6 +313,11 @@ struct Engine::Impl : cugo_k::LaunchHook
             return r.d_flags.data();
         }
         double* relpose_chi() { return d_scratch.data() + off_relpose_chi; }
+        // the covariance form of the two point kinds (FlatPoseKind::cov): the weight buffer is [12][n_weight], the views'
+        // d_info is cov_p and cov_z follows it; nullptr picks the information form's kernels
+        bool point_cov = false, pair_cov = false;
+        const double* point_cov_z() const { return point_cov ? point.d_info + 6 * (size_t)point.n_info : nullptr; }
+        const double* pair_cov_z() const { return pair_cov ? pair.d_info + 6 * (size_t)pair.n_info : nullptr; }
 
         cugo_k::ChunkScratch icp_rs() { return cugo_k::icp_scratch_in({d_scratch.data() + off_icp, d_scratch.size() - off_icp}, icp); }
         cugo_k::ChunkScratch point_rs() { return {d_scratch.data() + off_point, d_scratch.data() + off_point_chi}; }
@@ -392,6 +397,7 @@ struct Engine::Impl : cugo_k::LaunchHook
             point.d_p = pt.d_meas.data(), point.d_z = pt.d_meas.data() + 3 * (size_t)n_point;
             point.d_info = pt.d_weight.data(), point.n_info = pt.n_weight;
             point.rk = g.kinds[POSE_KIND_POINT].rk, point.delta = g.kinds[POSE_KIND_POINT].delta;
+            point_cov = g.kinds[POSE_KIND_POINT].cov, pair_cov = g.kinds[POSE_KIND_PAIR].cov;
             bind_reject(POSE_KIND_POINT, stream, plan_only); // (never on: graph_optimisation.cpp refuses a threshold on the kind)
             const KindBufs& pa = kind[POSE_KIND_PAIR];
             pair = cugo_point_pair_edges{};
@@ -488,7 +494,7 @@ struct Engine::Impl : cugo_k::LaunchHook
             }
             if (n_point)
             { // as the ICP kinds: the chunk pass, its add here or behind k_pose_schur
-                cugo_k::launch_point_chunks(s, point, poses, true, point_rs());
+                cugo_k::launch_point_chunks(s, point, poses, true, point_rs(), nullptr, point_cov_z());
                 if (!one_stream)
                     cugo_k::launch_point_add(s, point, point_rs(), Hpp, bp);
                 if (d_chi)
@@ -496,7 +502,7 @@ struct Engine::Impl : cugo_k::LaunchHook
             }
             if (n_pair)
             { // the chunk pass of the four roles; the diagonal sums here or, with the off-diagonal ones, behind the Schur pass
-                cugo_k::launch_point_pair_chunks(s, pair, pp.dev, poses, true, pair_rs());
+                cugo_k::launch_point_pair_chunks(s, pair, pp.dev, poses, true, pair_rs(), nullptr, pair_cov_z());
                 if (!one_stream)
                     cugo_k::launch_point_pair_add_diag(s, pair, pp.dev, pair_rs(), Hpp, bp);
                 if (d_chi)
@@ -559,7 +565,7 @@ struct Engine::Impl : cugo_k::LaunchHook
             if (n_icp)
                 cugo_k::launch_icp_chunks(s, icp, poses, false, icp_rs());
             if (n_point)
-                cugo_k::launch_point_chunks(s, point, poses, false, point_rs());
+                cugo_k::launch_point_chunks(s, point, poses, false, point_rs(), nullptr, point_cov_z());
             if (n_prior_wg)
                 cugo_k::launch_prior_errors(s, prior, poses, prior_chi());
             if (n_relpose_wg)
@@ -567,7 +573,7 @@ struct Engine::Impl : cugo_k::LaunchHook
             if (n_lm_prior_wg)
                 cugo_k::launch_lm_prior_errors(s, lm_prior, lms, lm_prior_chi());
             if (n_pair)
-                cugo_k::launch_point_pair_chunks(s, pair, pp.dev, poses, false, pair_rs());
+                cugo_k::launch_point_pair_chunks(s, pair, pp.dev, poses, false, pair_rs(), nullptr, pair_cov_z());
         }
     } pe;
     cugo_hsc_struct hs{};
@@ -1381,14 +1387,18 @@ void Engine::initialize(FlatGraph& g)
         throw std::runtime_error("cugo: relative-pose edge sets cannot be combined with CUGO_HSC_STRIP=1: the row-strip "
                                  "form of the Schur complement cannot hold a block without landmark products");
     if (n_pair && m.opt.hsc_strip)
-        throw std::runtime_error("cugo: pose-pose point edge sets (PointPairEdgeSet) cannot be combined with CUGO_HSC_STRIP=1: "
+        throw std::runtime_error(std::string("cugo: pose-pose point edge sets (") +
+                                 (g.kinds[POSE_KIND_PAIR].cov ? "GicpPairEdgeSet" : "PointPairEdgeSet") +
+                                 ") cannot be combined with CUGO_HSC_STRIP=1: "
                                  "the row-strip form of the Schur complement cannot hold a block without landmark products");
     if (n_pair && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: pose-pose point edge sets (PointPairEdgeSet) are not supported on a landmark-sharded "
-                                 "(multi-GPU) optimiser yet");
+        throw std::runtime_error(std::string("cugo: pose-pose point edge sets (") +
+                                 (g.kinds[POSE_KIND_PAIR].cov ? "GicpPairEdgeSet" : "PointPairEdgeSet") +
+                                 ") are not supported on a landmark-sharded (multi-GPU) optimiser yet");
     if (g.kinds[POSE_KIND_POINT].n() && (m.world > 1 || m.comm))
-        throw std::runtime_error("cugo: point-to-point edge sets (PointEdgeSet) are not supported on a landmark-sharded "
-                                 "(multi-GPU) optimiser yet");
+        throw std::runtime_error(std::string("cugo: point-to-point edge sets (") +
+                                 (g.kinds[POSE_KIND_POINT].cov ? "GicpEdgeSet" : "PointEdgeSet") +
+                                 ") are not supported on a landmark-sharded (multi-GPU) optimiser yet");
     for (int k = POSE_KIND_PRIOR; k >= 0; k--) // (priors first: the message a graph with several kinds has always got)
         if (g.kinds[k].n() && (m.world > 1 || m.comm))
             throw std::runtime_error(std::string("cugo: ") + pose_kind_group(k) +
@@ -2191,6 +2201,8 @@ int Engine::flat_point_edges(std::vector<int32_t>& pose, std::vector<int32_t>& s
     return k.n_weight;
 }
 int Engine::n_point_pair_edges() const { return impl_->pe.n_pair; }
+bool Engine::point_edges_cov() const { return impl_->pe.point_cov; }
+bool Engine::point_pair_edges_cov() const { return impl_->pe.pair_cov; }
 int Engine::flat_point_pair_edges(std::vector<int32_t>& pose_a, std::vector<int32_t>& pose_b, std::vector<int32_t>& src_edge,
                                   std::vector<double>& p, std::vector<double>& z, std::vector<double>& info) const
 {

@@ -48,12 +48,18 @@ struct FlatPoseKind
     int rk = CUGO_RK_NONE;
     double delta = 1.0;
     bool rk_seen = false; // a non-empty edge set has settled rk / delta (further sets must agree)
+    // point and pose-pose point only: the COVARIANCE form (gicp_types.h).  weight_w is then 12: the upper triangles of
+    // C_p, then of C_z; the kernels form Omega from them at the poses of every pass
+    bool cov = false;
     int n() const { return (int)pose.size(); }
     void clear()
     {
         pose.clear(), pose_b.clear(), meas.clear(), weight.clear(), src_set.clear(), src_edge.clear(), threshold.clear();
         rk = CUGO_RK_NONE, delta = 1.0, rk_seen = false;
+        if (cov)
+            weight_w = 6, cov = false;
     }
+    void set_covariance_form() { cov = true, weight_w = 12; }
 };
 // a kind in messages about its edge sets, and in the engine's, which speak of the two ICP kinds as one
 inline const char* pose_kind_name(int kind)
@@ -291,6 +297,10 @@ public:
     int flat_point_edges(std::vector<int32_t>& pose, std::vector<int32_t>& src_edge, std::vector<double>& p,
                          std::vector<double>& z, std::vector<double>& info) const;
     int n_point_pair_edges() const;
+    // whether the point / pose-pose point kind of the current flattening is in the covariance form: `info` of the two
+    // diagnostics above is then [12][n_info], cov_p then cov_z
+    bool point_edges_cov() const;
+    bool point_pair_edges_cov() const;
     // Diagnostic: the pose-pose point edges of the current flattening as the kernels read them (the plan's sorted order,
     // planar): pose a / pose b [n], the position of every edge in its set's container, p [3][n], z [3][n], info
     // [6][n_info]; returns n_info (n or 1)

@@ -5,6 +5,7 @@
 #include "../../include/icp_types.h"
 #include "../../include/landmark_prior_types.h"
 #include "../../include/point_edge_types.h"
+#include "../../include/gicp_types.h"
 #include "../../include/point_pair_types.h"
 #include "../../include/prior_types.h"
 #include "../../include/relpose_types.h"
@@ -78,19 +79,60 @@ int CudaGraphOptimisationImpl::nIcpEdges(int kind) const { return engine_->n_icp
 int CudaGraphOptimisationImpl::nPriorEdges() const { return engine_->n_prior_edges(); }
 int CudaGraphOptimisationImpl::nRelPoseEdges() const { return engine_->n_relpose_edges(); }
 int CudaGraphOptimisationImpl::nLandmarkPriorEdges() const { return engine_->n_lm_prior_edges(); }
-int CudaGraphOptimisationImpl::nPointEdges() const { return engine_->n_point_edges(); }
+int CudaGraphOptimisationImpl::nPointEdges() const { return engine_->point_edges_cov() ? 0 : engine_->n_point_edges(); }
+int CudaGraphOptimisationImpl::nGicpEdges() const { return engine_->point_edges_cov() ? engine_->n_point_edges() : 0; }
+int CudaGraphOptimisationImpl::nGicpPairEdges() const { return engine_->point_pair_edges_cov() ? engine_->n_point_pair_edges() : 0; }
+// [12][n_cov] planar (cov_p, then cov_z) -> two [6][n_cov] arrays
+static void splitCovariances(const std::vector<double>& w, int n_cov, std::vector<double>& covP, std::vector<double>& covZ)
+{
+    covP.assign(w.begin(), w.begin() + 6 * (size_t)n_cov);
+    covZ.assign(w.begin() + 6 * (size_t)n_cov, w.begin() + 12 * (size_t)n_cov);
+}
+int CudaGraphOptimisationImpl::flatGicpEdges(std::vector<int>& pose, std::vector<int>& srcEdge, std::vector<double>& p,
+                                             std::vector<double>& z, std::vector<double>& covP, std::vector<double>& covZ) const
+{
+    pose.clear(), srcEdge.clear(), p.clear(), z.clear(), covP.clear(), covZ.clear();
+    if (!engine_->point_edges_cov())
+        return 0;
+    std::vector<int32_t> q, s;
+    std::vector<double> w;
+    const int n_cov = engine_->flat_point_edges(q, s, p, z, w);
+    pose.assign(q.begin(), q.end()), srcEdge.assign(s.begin(), s.end());
+    splitCovariances(w, n_cov, covP, covZ);
+    return n_cov;
+}
+int CudaGraphOptimisationImpl::flatGicpPairEdges(std::vector<int>& poseA, std::vector<int>& poseB, std::vector<int>& srcEdge,
+                                                 std::vector<double>& p, std::vector<double>& z, std::vector<double>& covP,
+                                                 std::vector<double>& covZ) const
+{
+    poseA.clear(), poseB.clear(), srcEdge.clear(), p.clear(), z.clear(), covP.clear(), covZ.clear();
+    if (!engine_->point_pair_edges_cov())
+        return 0;
+    std::vector<int32_t> a, b, s;
+    std::vector<double> w;
+    const int n_cov = engine_->flat_point_pair_edges(a, b, s, p, z, w);
+    poseA.assign(a.begin(), a.end()), poseB.assign(b.begin(), b.end()), srcEdge.assign(s.begin(), s.end());
+    splitCovariances(w, n_cov, covP, covZ);
+    return n_cov;
+}
 int CudaGraphOptimisationImpl::flatPointEdges(std::vector<int>& pose, std::vector<int>& srcEdge, std::vector<double>& p,
                                               std::vector<double>& z, std::vector<double>& info) const
 {
+    pose.clear(), srcEdge.clear(), p.clear(), z.clear(), info.clear();
+    if (engine_->point_edges_cov()) // (the kind holds covariances, [12][n_cov]: flatGicpEdges)
+        return 0;
     std::vector<int32_t> q, s;
     const int n_info = engine_->flat_point_edges(q, s, p, z, info);
     pose.assign(q.begin(), q.end()), srcEdge.assign(s.begin(), s.end());
     return n_info;
 }
-int CudaGraphOptimisationImpl::nPointPairEdges() const { return engine_->n_point_pair_edges(); }
+int CudaGraphOptimisationImpl::nPointPairEdges() const { return engine_->point_pair_edges_cov() ? 0 : engine_->n_point_pair_edges(); }
 int CudaGraphOptimisationImpl::flatPointPairEdges(std::vector<int>& poseA, std::vector<int>& poseB, std::vector<int>& srcEdge,
                                                   std::vector<double>& p, std::vector<double>& z, std::vector<double>& info) const
 {
+    poseA.clear(), poseB.clear(), srcEdge.clear(), p.clear(), z.clear(), info.clear();
+    if (engine_->point_pair_edges_cov()) // (the kind holds covariances, [12][n_cov]: flatGicpPairEdges)
+        return 0;
     std::vector<int32_t> a, b, s;
     const int n_info = engine_->flat_point_pair_edges(a, b, s, p, z, info);
     poseA.assign(a.begin(), a.end()), poseB.assign(b.begin(), b.end()), srcEdge.assign(s.begin(), s.end());
@@ -471,6 +513,48 @@ static void pointPayload(BaseEdge* e, const double* setInformation, Refuse& refu
             weight[t++] = 0.5 * (A[3 * r + c] + A[3 * c + r]);
 }
 
+// covariance form (gicp_types.h): p, z | the upper triangles of the symmetric parts of C_p, then C_z.  Each covariance
+// symmetric to 1e-12 max|C| and positive semi-definite to -1e-12 lambda_max; lambda_min(C_p) + lambda_min(C_z) >
+// 1e-12 (lambda_max(C_p) + lambda_max(C_z)): by Weyl's inequality S = C_z + M C_p M^T is then positive definite for
+// every rotation M
+template <class Refuse>
+static void gicpPayload(BaseEdge* e, Refuse& refuse, double* m, double* weight)
+{
+    const auto& mz = *static_cast<const PointCovarianceMatch<double>*>(e->measurementData());
+    for (int c = 0; c < 3; c++)
+    {
+        m[c] = mz.pointP[c], m[3 + c] = mz.pointZ[c];
+        if (!std::isfinite(m[c]) || !std::isfinite(m[3 + c]))
+            refuse("non-finite point or measured point");
+    }
+    double lo[2], hi[2];
+    const double* C[2] = {mz.covP, mz.covZ};
+    for (int k = 0; k < 2; k++)
+    {
+        const double* A = C[k];
+        double mx = 0.0;
+        for (int i = 0; i < 9; i++)
+        {
+            if (!std::isfinite(A[i]))
+                refuse(k ? "non-finite covariance covZ" : "non-finite covariance covP");
+            mx = std::max(mx, std::fabs(A[i]));
+        }
+        for (int i = 0; i < 3; i++)
+            for (int j = i + 1; j < 3; j++)
+                if (std::fabs(A[3 * i + j] - A[3 * j + i]) > 1e-12 * mx)
+                    refuse(k ? "the covariance covZ is not symmetric" : "the covariance covP is not symmetric");
+        symEigenRange<3>(A, lo[k], hi[k]);
+        if (lo[k] < -1e-12 * std::max(hi[k], 0.0) || hi[k] < 0.0)
+            refuse(k ? "the covariance covZ is not positive semi-definite" : "the covariance covP is not positive semi-definite");
+        for (int r = 0, t = 6 * k; r < 3; r++)
+            for (int c = r; c < 3; c++)
+                weight[t++] = 0.5 * (A[3 * r + c] + A[3 * c + r]);
+    }
+    if (!(lo[0] + lo[1] > 1e-12 * (hi[0] + hi[1])))
+        refuse("covP and covZ are both singular: lambda_min(covP) + lambda_min(covZ) must exceed 1e-12 (lambda_max(covP) + "
+               "lambda_max(covZ)) for C_z + M C_p M^T to be positive definite under every rotation");
+}
+
 // One LandmarkPriorEdgeSet (landmark_prior_types.h) into the flat arrays, in container order; the one place where these
 // edges are checked, as flattenPoseEdgeSet is for the pose kinds.  Every active edge must sit on a landmark vertex of one
 // of the optimiser's landmark sets and hold finite values and a symmetric positive semi-definite Omega (its own with
@@ -631,14 +715,17 @@ void CudaGraphOptimisationImpl::initialize()
     // the flattened order is exactly the container order.
     size_t cap = 0;
     g.has_depth = false, g.rk_type_depth = CUGO_RK_NONE, g.rk_delta_depth = 1.0, g.depth_weight = 1.0;
-    for (BaseEdgeSet* es : edgeSets) // (a LandmarkPriorEdgeSet, PointEdgeSet or PointPairEdgeSet is 3-d like a stereo set: the type tells them apart)
+    // (a LandmarkPriorEdgeSet, PointEdgeSet, PointPairEdgeSet, GicpEdgeSet or GicpPairEdgeSet is 3-d like a stereo set: the type
+    //  tells them apart)
+    for (BaseEdgeSet* es : edgeSets)
         if (es->dim() != 1 && es->dim() != 6 && !dynamic_cast<LandmarkPriorEdgeSet*>(es) && !dynamic_cast<PointEdgeSet*>(es) &&
-            !dynamic_cast<PointPairEdgeSet*>(es))
+            !dynamic_cast<PointPairEdgeSet*>(es) && !dynamic_cast<GicpEdgeSet*>(es) && !dynamic_cast<GicpPairEdgeSet*>(es))
             cap += es->nedges();
     for (cugo_host::FlatPoseKind& fk : g.kinds)
         fk.clear();
     g.lm_priors.clear();
     poseSetEdges_.assign(edgeSets.size(), {});
+    int pointFormSeen[2] = {-1, -1}; // per arity: 0 information form, 1 covariance form
     const bool rejection = options.poseEdgeOutlierRejection;
     g.e_pose.resize(cap), g.e_lm.resize(cap), g.e_flags.resize(cap);
     g.e_meas.resize(3 * cap), g.e_omega.resize(cap), g.e_cam.resize(cap);
@@ -671,6 +758,37 @@ void CudaGraphOptimisationImpl::initialize()
         if (auto* ls = dynamic_cast<LandmarkPriorEdgeSet*>(es))
         { // landmark_prior_types.h, an extension: by type, before the dispatch on dim() (stereo BA sets are 3-d as well)
             flattenLandmarkPriorSet(ls, (int)si, vertexSets, options.perEdgeInformation, g.lm_priors);
+            continue;
+        }
+        const bool gicp1 = dynamic_cast<GicpEdgeSet*>(es) != nullptr, gicp2 = dynamic_cast<GicpPairEdgeSet*>(es) != nullptr;
+        if (es->nedges() > 0 && (gicp1 || gicp2 || dynamic_cast<PointEdgeSet*>(es) || dynamic_cast<PointPairEdgeSet*>(es)))
+        { // one kind has one payload width: the two forms of one arity cannot share an optimiser (empty sets aside)
+            const bool pairKind = gicp2 || dynamic_cast<PointPairEdgeSet*>(es);
+            int& seen = pointFormSeen[pairKind ? 1 : 0];
+            const int form = gicp1 || gicp2 ? 1 : 0;
+            if (seen >= 0 && seen != form)
+                throw std::runtime_error(std::string("cugo: edge set ") + std::to_string(si) + " (" +
+                                         (pairKind ? (form ? "GicpPairEdgeSet" : "PointPairEdgeSet") : (form ? "GicpEdgeSet" : "PointEdgeSet")) +
+                                         "): a covariance-form set and an information-form set of the same arity (" +
+                                         (pairKind ? "GicpPairEdgeSet with PointPairEdgeSet" : "GicpEdgeSet with PointEdgeSet") +
+                                         ") cannot be combined in one optimiser yet");
+            seen = form;
+        }
+        if (gicp1 || gicp2)
+        { // gicp_types.h, an extension: the covariance form of the point kinds, by type as well
+            const char* cls = gicp2 ? "GicpPairEdgeSet" : "GicpEdgeSet";
+            if (es->getOutlierThreshold() > 0.0)
+                throw std::runtime_error(std::string("cugo: covariance-form point edge set ") + std::to_string(si) +
+                                         ": outlier rejection is not supported on " + cls + " yet (setOutlierThreshold "
+                                         "must stay 0, whatever poseEdgeOutlierRejection says)");
+            const int kind = gicp2 ? cugo_host::POSE_KIND_PAIR : cugo_host::POSE_KIND_POINT;
+            if (es->nedges() == 0)
+                continue;
+            g.kinds[kind].set_covariance_form();
+            flattenPoseEdgeSet(
+                es, (int)si, gicp2 ? 2 : 1, cls, vertexSets, false, g.kinds[kind], poseSetEdges_[si],
+                [&](BaseEdge* e, auto& refuse, double* meas, double* weight) { gicpPayload(e, refuse, meas, weight); },
+                [] { return (const char*)nullptr; });
             continue;
         }
         if (auto* pts = dynamic_cast<PointEdgeSet*>(es))

@@ -233,15 +233,17 @@ size_t point_scratch_doubles(const cugo_point_edges& ev); // partials + totals
 size_t point_partial_doubles(const cugo_point_edges& ev);
 int point_chunk_count(const cugo_point_edges& ev);
 ChunkScratch point_scratch_in(ReduceScratch rs, const cugo_point_edges& ev);
+// The covariance form (cugo_gicp_edges) runs through the same launchers: with d_cov_z the chunk pass is the covariance
+// instantiation, which reads ev.d_info as cov_p and ev.n_info as the count of both covariances.
 // ADDS the terms to d_Hpp / d_bp; chi2 total to d_chi[0] if given (added to what is there with chi_add)
 void launch_point_build(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
-                        ChunkScratch rs, double* d_chi, bool chi_add = false);
+                        ChunkScratch rs, double* d_chi, bool chi_add = false, const double* d_cov_z = nullptr);
 // chi2 only (the same bits as launch_point_build's); d_edge_chi: per edge, or nullptr
 void launch_point_errors(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, ChunkScratch rs, double* d_chi,
-                         bool chi_add = false, double* d_edge_chi = nullptr);
+                         bool chi_add = false, double* d_edge_chi = nullptr, const double* d_cov_z = nullptr);
 // the pieces: the chunk pass alone, the per-pose sums ADDED to d_Hpp / d_bp or to the Schur destination, the chi2 total
 void launch_point_chunks(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, bool full, ChunkScratch rs,
-                         double* d_edge_chi = nullptr);
+                         double* d_edge_chi = nullptr, const double* d_cov_z = nullptr);
 void launch_point_add(hipStream_t s, const cugo_point_edges& ev, ChunkScratch rs, double* d_Hpp, double* d_bp);
 void launch_point_add_schur(hipStream_t s, const cugo_point_edges& ev, ChunkScratch rs, const int32_t* d_rowptr,
                             double* d_Hsc, double* d_bp, double* d_bsc);
@@ -323,9 +325,10 @@ ChunkScratch point_pair_scratch_in(ReduceScratch rs, int n, int n_runs);
 // 1 if d_pose_a / d_pose_b of an edge are not those of its run in the plan, else 0; d_bad: a device int.  Synchronises
 int point_pair_check_indices(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, int* d_bad);
 // the chunk pass — full: the partials of the four roles and chi2; otherwise chi2 only (role 0; of the partials only
-// element 27 of role 0's slots is written, which no finishing pass reads); d_edge_chi: errors only, sorted order
+// element 27 of role 0's slots is written, which no finishing pass reads); d_edge_chi: errors only, sorted order.
+// With d_cov_z: the covariance instantiation (cugo_gicp_pair_edges), ev.d_info = cov_p, ev.n_info = the count of both
 void launch_point_pair_chunks(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, const double* d_poses,
-                              bool full, ChunkScratch rs, double* d_edge_chi = nullptr);
+                              bool full, ChunkScratch rs, double* d_edge_chi = nullptr, const double* d_cov_z = nullptr);
 // the sums of a full chunk pass ADDED: diagonal blocks and b to d_Hpp / d_bp, the off-diagonal blocks to d_Hoff by block
 // index if it is given ...
 void launch_point_pair_add(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, ChunkScratch rs,

@@ -8,6 +8,10 @@
 // (singular matrices are legal: Omega = omega n n^T with z on the plane is the plane edge, Omega = omega (I - u u^T) with
 // z = a the line edge); it comes as its upper triangle, row-major packed (00 01 02 11 12 22), [6][n] or [6][1].
 //
+// The covariance form (include/cugo_hip.h: cugo_gicp_edges; point_term.h): Omega = (C_z + R C_p R^T)^-1 formed at the poses
+// the pass is given, from the upper triangles cov_p (world frame) and cov_z (the pose's frame).  It is an instantiation of
+// its own of the chunk kernels (k_gicp_chunks_*); the information form's kernels carry no branch for it.
+//
 // Layout and reduction are the chunk scheme of pose_chunks.h, for one kind keyed by pose.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +25,7 @@ using namespace cugo_dev;
 
 struct PointArgs
 {
+    static constexpr bool COV = false;
     int n;
     const int32_t* pose;
     const int32_t* pose_ptr;
@@ -36,11 +41,17 @@ struct PointArgs
     const double* poses;
     double* edge_chi; // error pass: [n] or nullptr
 };
+// the covariance form: info is cov_p [6][n_info], n_info the count of both covariances
+struct GicpArgs : PointArgs
+{
+    static constexpr bool COV = true;
+    const double* cov_z; // [6][n] or [6][1]
+};
 
 // contribution of edge e: v[0..20] upper triangle of w J^T Omega J (row-major packed), v[21..26] -w J^T Omega r;
 // returns the chi2 term
-template <bool FULL>
-__device__ __forceinline__ double point_edge(const PointArgs& k, int e, const double* __restrict__ pose, double (&v)[32])
+template <bool FULL, class K>
+__device__ __forceinline__ double point_edge(const K& k, int e, const double* __restrict__ pose, double (&v)[32])
 {
     const size_t n = (size_t)k.n;
     const double pp[3] = {k.p[e], k.p[n + e], k.p[2 * n + e]};
@@ -48,7 +59,15 @@ __device__ __forceinline__ double point_edge(const PointArgs& k, int e, const do
     world_to_cam(pose, pp, y);
     const double z[3] = {k.z[e], k.z[n + e], k.z[2 * n + e]};
     double O[3][3], q[3], x;
-    const double chi = point_residual(y, z, k.info, k.n_info, n, e, k.rk, O, q, x);
+    double chi;
+    if constexpr (K::COV)
+    {
+        double R[3][3]; // M = R
+        quat_to_rot(pose, R);
+        chi = point_residual<true>(y, z, k.info, k.n_info, n, e, k.rk, O, q, x, k.cov_z, &R);
+    }
+    else
+        chi = point_residual(y, z, k.info, k.n_info, n, e, k.rk, O, q, x);
     if (FULL)
     {
         const double w = rk_drho(k.rk, x);
@@ -59,8 +78,8 @@ __device__ __forceinline__ double point_edge(const PointArgs& k, int e, const do
 }
 
 // one wave per chunk (pose_chunks.h: chunk_walk, keyed by pose)
-template <bool FULL>
-__device__ __forceinline__ void point_chunks(const PointArgs& k)
+template <bool FULL, class K>
+__device__ __forceinline__ void point_chunks(const K& k)
 {
     const int c = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 6);
     if (c >= chunk_count(k.n))
@@ -80,6 +99,10 @@ __global__ __launch_bounds__(ICP_WG) __attribute__((amdgpu_waves_per_eu(6))) voi
 {
     point_chunks<false>(a);
 }
+// the covariance form.  Its error pass holds M, two covariances and the factor next to the loads in flight: it does not fit
+// the 80 VGPRs of six waves per SIMD without spilling, so it keeps the bound of the workgroup size alone
+__global__ __launch_bounds__(ICP_WG) void k_gicp_chunks_build(GicpArgs a) { point_chunks<true>(a); }
+__global__ __launch_bounds__(ICP_WG) void k_gicp_chunks_errors(GicpArgs a) { point_chunks<false>(a); }
 
 // the finishing pass (pose_chunks.h: chunk_finish) over the free poses that have point edges
 template <bool SCHUR>
@@ -115,13 +138,21 @@ ChunkScratch point_scratch_in(ReduceScratch rs, const cugo_point_edges& ev)
 }
 
 void launch_point_chunks(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, bool full, ChunkScratch rs,
-                         double* d_edge_chi)
+                         double* d_edge_chi, const double* d_cov_z)
 {
     const PointArgs a = args_of(ev, d_poses, rs, full ? nullptr : d_edge_chi);
     const size_t waves = (size_t)chunk_count(ev.n);
     if (waves == 0)
         return;
-    if (full)
+    if (d_cov_z)
+    {
+        const GicpArgs g{a, d_cov_z};
+        if (full)
+            CUGO_LAUNCH(k_gicp_chunks_build, dim3(chunk_grid(waves)), dim3(ICP_WG), 0, s, g);
+        else
+            CUGO_LAUNCH(k_gicp_chunks_errors, dim3(chunk_grid(waves)), dim3(ICP_WG), 0, s, g);
+    }
+    else if (full)
         CUGO_LAUNCH(k_point_chunks_build, dim3(chunk_grid(waves)), dim3(ICP_WG), 0, s, a);
     else
         CUGO_LAUNCH(k_point_chunks_errors, dim3(chunk_grid(waves)), dim3(ICP_WG), 0, s, a);
@@ -154,18 +185,18 @@ void launch_point_chi_total(hipStream_t s, const cugo_point_edges& ev, ChunkScra
 }
 
 void launch_point_build(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, double* d_Hpp, double* d_bp,
-                        ChunkScratch rs, double* d_chi, bool chi_add)
+                        ChunkScratch rs, double* d_chi, bool chi_add, const double* d_cov_z)
 {
-    launch_point_chunks(s, ev, d_poses, true, rs);
+    launch_point_chunks(s, ev, d_poses, true, rs, nullptr, d_cov_z);
     launch_point_add(s, ev, rs, d_Hpp, d_bp);
     if (d_chi)
         launch_point_chi_total(s, ev, rs, d_chi, chi_add);
 }
 
 void launch_point_errors(hipStream_t s, const cugo_point_edges& ev, const double* d_poses, ChunkScratch rs, double* d_chi,
-                         bool chi_add, double* d_edge_chi)
+                         bool chi_add, double* d_edge_chi, const double* d_cov_z)
 {
-    launch_point_chunks(s, ev, d_poses, false, rs, d_edge_chi);
+    launch_point_chunks(s, ev, d_poses, false, rs, d_edge_chi, d_cov_z);
     if (d_chi)
         launch_point_chi_total(s, ev, rs, d_chi, chi_add);
 }

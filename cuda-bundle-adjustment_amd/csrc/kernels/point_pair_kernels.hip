@@ -11,6 +11,11 @@
 //   H_ab = w J_a^T Omega J_b = -w [ [p]x W ; W ],  W = N [S_y | I] = [ N S_y | N ]     (3 x 6; rows a, columns b)
 // With T_a the identity M = I, Omega' = Omega and the term on b is the unary point edge (p, z, Omega), term for term.
 //
+// The covariance form (include/cugo_hip.h: cugo_gicp_pair_edges; point_term.h): Omega = (C_z + M C_p M^T)^-1 formed at
+// the poses the pass is given, from cov_p (a's frame) and cov_z (b's frame).  Every role and the error pass form M and
+// Omega first, from the same inputs in the same operation order, and continue as above.  It is an instantiation of its
+// own of the chunk kernels (k_gicp_pair_chunks_*); the information form's kernels carry no branch for it.
+//
 // Invariants (the project's own for every pose kind):
 //   - no atomics and no summation order that depends on the schedule: one fixed order;
 //   - the error pass forms the chunk and (chunk, run) chi2 totals of the build pass bit for bit;
@@ -49,6 +54,7 @@ constexpr int N_ROLES = 4;
 
 struct PairArgs
 {
+    static constexpr bool COV = false;
     int n;
     const int32_t *pose_a, *pose_b; // [n] sorted order
     const double* p;                // [3][n]
@@ -63,13 +69,29 @@ struct PairArgs
     const double* poses;
     double* edge_chi; // error pass: [n] or nullptr
 };
+// the covariance form: info is cov_p [6][n_info], n_info the count of both covariances
+struct GicpPairArgs : PairArgs
+{
+    static constexpr bool COV = true;
+    const double* cov_z; // [6][n] or [6][1]
+};
+
+// M = R_b R_a^T
+__device__ __forceinline__ void pair_rotation(const double (&Ra)[3][3], const double (&Rb)[3][3], double (&M)[3][3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            M[i][j] = Rb[i][0] * Ra[j][0] + Rb[i][1] * Ra[j][1] + Rb[i][2] * Ra[j][2];
+}
 
 __device__ __forceinline__ size_t pair_slots(const PairArgs& k) { return ChunkLayout(k.n, k.plan.n_runs).slots; }
 
 // Edge e between poses a and b, seen by `role`.  Returns the chi2 term.  FULL and term: v[0..26] receive the role's
 // contribution (roles 2 and 3: v[6 c + i] = H_ab[i][3 (role - 2) + c], 18 values); FULL without term: zeros
-template <bool FULL, int role>
-__device__ __forceinline__ double pair_edge(const PairArgs& k, int e, int a, int b, bool term, double (&v)[32])
+template <bool FULL, int role, class K>
+__device__ __forceinline__ double pair_edge(const K& k, int e, int a, int b, bool term, double (&v)[32])
 {
     const size_t n = (size_t)k.n;
     const double* __restrict__ pa = k.poses + 7 * (size_t)a;
@@ -88,7 +110,15 @@ __device__ __forceinline__ double pair_edge(const PairArgs& k, int e, int a, int
         y[i] = Rb[i][0] * X[0] + Rb[i][1] * X[1] + Rb[i][2] * X[2] + pb[4 + i];
     const double z[3] = {k.z[e], k.z[n + e], k.z[2 * n + e]};
     double O[3][3], q[3], x; // Omega, Omega r
-    const double chi = point_residual(y, z, k.info, k.n_info, n, e, k.rk, O, q, x);
+    double Mc[3][3]; // R_b R_a^T of the covariance form, which needs it for Omega in every role
+    double chi;
+    if constexpr (K::COV)
+    {
+        pair_rotation(Ra, Rb, Mc);
+        chi = point_residual<true>(y, z, k.info, k.n_info, n, e, k.rk, O, q, x, k.cov_z, &Mc);
+    }
+    else
+        chi = point_residual(y, z, k.info, k.n_info, n, e, k.rk, O, q, x);
     if (FULL)
     {
         chunk_zero(v);
@@ -103,11 +133,22 @@ __device__ __forceinline__ double pair_edge(const PairArgs& k, int e, int a, int
             else
             {
                 double M[3][3], N[3][3]; // M = R_b R_a^T, N = M^T Omega
+                if constexpr (K::COV)
+                {
 #pragma unroll
-                for (int i = 0; i < 3; i++)
+                    for (int i = 0; i < 3; i++)
 #pragma unroll
-                    for (int j = 0; j < 3; j++)
-                        M[i][j] = Rb[i][0] * Ra[j][0] + Rb[i][1] * Ra[j][1] + Rb[i][2] * Ra[j][2];
+                        for (int j = 0; j < 3; j++)
+                            M[i][j] = Mc[i][j];
+                }
+                else
+                {
+#pragma unroll
+                    for (int i = 0; i < 3; i++)
+#pragma unroll
+                        for (int j = 0; j < 3; j++)
+                            M[i][j] = Rb[i][0] * Ra[j][0] + Rb[i][1] * Ra[j][1] + Rb[i][2] * Ra[j][2];
+                }
 #pragma unroll
                 for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -158,8 +199,8 @@ __device__ __forceinline__ double pair_edge(const PairArgs& k, int e, int a, int
 // One wave per (chunk of ICP_CHUNK sorted edges, role): pose_chunks.h's chunk_walk keyed by run, on the role's part of
 // the partials.  FULL: the role's partials, role 0 also chi2; otherwise (role 0 alone is launched) chi2 only: element 27
 // of role 0's slots, the chunk total and, with edge_chi, the chi2 term of every edge.
-template <bool FULL, int role>
-__device__ __forceinline__ void pair_chunks(const PairArgs& k)
+template <bool FULL, int role, class K>
+__device__ __forceinline__ void pair_chunks(const K& k)
 {
     const int c = (int)((blockIdx.x * (size_t)ICP_WG + threadIdx.x) >> 6);
     if (c >= chunk_count(k.n))
@@ -192,6 +233,18 @@ __global__ __launch_bounds__(ICP_WG) void k_point_pair_chunks_build(PairArgs a)
     }
 }
 __global__ __launch_bounds__(ICP_WG) void k_point_pair_chunks_errors(PairArgs a) { pair_chunks<false, 0>(a); }
+// the covariance form
+__global__ __launch_bounds__(ICP_WG) void k_gicp_pair_chunks_build(GicpPairArgs a)
+{
+    switch (blockIdx.y)
+    {
+    case 0: pair_chunks<true, 0>(a); break;
+    case 1: pair_chunks<true, 1>(a); break;
+    case 2: pair_chunks<true, 2>(a); break;
+    default: pair_chunks<true, 3>(a); break;
+    }
+}
+__global__ __launch_bounds__(ICP_WG) void k_gicp_pair_chunks_errors(GicpPairArgs a) { pair_chunks<false, 0>(a); }
 
 // element t of run r's partials of `role`, summed in chunk order
 __device__ __forceinline__ double run_sum(const PairArgs& k, int role, int r, int t)
@@ -289,14 +342,22 @@ int point_pair_check_indices(hipStream_t s, const cugo_point_pair_edges& ev, con
 }
 
 void launch_point_pair_chunks(hipStream_t s, const cugo_point_pair_edges& ev, const PointPairPlanDev& plan, const double* d_poses,
-                              bool full, ChunkScratch rs, double* d_edge_chi)
+                              bool full, ChunkScratch rs, double* d_edge_chi, const double* d_cov_z)
 {
     const size_t waves = (size_t)chunk_count(ev.n);
     if (waves == 0)
         return;
     const PairArgs a = args_of(ev, plan, d_poses, rs, full ? nullptr : d_edge_chi);
     const unsigned grid = chunk_grid(waves);
-    if (full)
+    if (d_cov_z)
+    {
+        const GicpPairArgs g{a, d_cov_z};
+        if (full)
+            CUGO_LAUNCH(k_gicp_pair_chunks_build, dim3(grid, N_ROLES), dim3(ICP_WG), 0, s, g);
+        else
+            CUGO_LAUNCH(k_gicp_pair_chunks_errors, dim3(grid), dim3(ICP_WG), 0, s, g);
+    }
+    else if (full)
         CUGO_LAUNCH(k_point_pair_chunks_build, dim3(grid, N_ROLES), dim3(ICP_WG), 0, s, a);
     else
         CUGO_LAUNCH(k_point_pair_chunks_errors, dim3(grid), dim3(ICP_WG), 0, s, a);

@@ -153,7 +153,8 @@ public:
     int nPointEdges() const;
     /** the point edges of the current flattening as the kernels read them: sorted by pose (stable), planar — pose [n],
      *  position of each edge in its set's container, p [3][n], z [3][n], info [6][n_info] (upper triangle, row-major
-     *  packed); returns n_info (n, or 1 when one matrix serves all).  Diagnostic */
+     *  packed); returns n_info (n, or 1 when one matrix serves all; nothing and 0 for a kind in the covariance form:
+     *  flatGicpEdges).  Diagnostic */
     int flatPointEdges(std::vector<int>& pose, std::vector<int>& srcEdge, std::vector<double>& p, std::vector<double>& z,
                        std::vector<double>& info) const;
     /** pose-pose point edges of the current flattening that count: active, at least one free end (point_pair_types.h, an
@@ -162,9 +163,20 @@ public:
     /** the pose-pose point edges of the current flattening as the kernels read them: in the order of their plan (runs of
      *  one (a, b) orientation of a pair, ordered by (lo, hi, orientation); container order inside a run), planar — pose a
      *  and pose b [n], position of each edge in its set's container, p [3][n], z [3][n], info [6][n_info] (upper triangle,
-     *  row-major packed); returns n_info (n, or 1 when one matrix serves all).  Diagnostic */
+     *  row-major packed); returns n_info (n, or 1 when one matrix serves all; nothing and 0 for a kind in the covariance
+     *  form: flatGicpPairEdges).  Diagnostic */
     int flatPointPairEdges(std::vector<int>& poseA, std::vector<int>& poseB, std::vector<int>& srcEdge, std::vector<double>& p,
                            std::vector<double>& z, std::vector<double>& info) const;
+    /** covariance-form point edges (GicpEdgeSet / GicpPairEdgeSet, gicp_types.h, an extension) of the current flattening
+     *  that count; nPointEdges() / nPointPairEdges() are 0 for a kind in the covariance form */
+    int nGicpEdges() const;
+    int nGicpPairEdges() const;
+    /** as flatPointEdges / flatPointPairEdges, with covP and covZ [6][n_cov] (upper triangles, row-major packed) in place
+     *  of info; returns n_cov (n, or 1 when one covariance pair serves all; 0 without such edges).  Diagnostic */
+    int flatGicpEdges(std::vector<int>& pose, std::vector<int>& srcEdge, std::vector<double>& p, std::vector<double>& z,
+                      std::vector<double>& covP, std::vector<double>& covZ) const;
+    int flatGicpPairEdges(std::vector<int>& poseA, std::vector<int>& poseB, std::vector<int>& srcEdge, std::vector<double>& p,
+                          std::vector<double>& z, std::vector<double>& covP, std::vector<double>& covZ) const;
     /** the pose-landmark edges of the current flattening in flattening order (set by set, container order; mono,
      *  stereo and depth edges share the array): flattened pose and landmark index, CUGO_EDGE_* flags, measurement
      *  (3 per edge, the third 0 for a mono edge).  Diagnostic */

@@ -14,7 +14,9 @@
 // of one of the optimiser's pose sets) and optimize() minimises the joint cost.  Edges on fixed poses and inactive edges
 // count for nothing.  Refused: setOutlierThreshold(t > 0) on the set (not yet supported, whatever
 // GraphOptimisationOptions::poseEdgeOutlierRejection says), point sets that disagree on the robust kernel, and
-// landmark-sharded optimisers.  Also reachable through the kernel-level C ABI (include/cugo_hip.h: cugo_point_edges,
+// landmark-sharded optimisers.  An Omega that follows the pose during a solve is GicpEdgeSet (gicp_types.h: Omega = (C_z +
+// R C_p R^T)^-1 rebuilt at every linearisation and trial); refused: a GicpEdgeSet and a PointEdgeSet with edges in one
+// optimiser.  Also reachable through the kernel-level C ABI (include/cugo_hip.h: cugo_point_edges,
 // cugo_point_compute_errors, cugo_point_construct_quadratic_form, cugo_point_construct_quadratic_form_schur).
 #pragma once
 #include <algorithm>

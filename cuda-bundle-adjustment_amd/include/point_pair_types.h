@@ -16,7 +16,8 @@
 // edge count for nothing.  Singular Omega is legal: plane-to-plane and line correspondences are special cases, as for the
 // point kind.
 // Uses: LiDAR / RGB-D multi-scan registration (Lu-Milios, multiway ICP, the refinement step behind a pose graph);
-// scan-to-scan generalised ICP with Omega = (C_q + R C_p R^T)^-1 frozen per outer iteration; submap alignment.
+// scan-to-scan generalised ICP with Omega = (C_q + R C_p R^T)^-1 frozen per outer iteration (GicpPairEdgeSet of
+// gicp_types.h rebuilds Omega at the poses of every pass); submap alignment.
 // The term is in csrc/kernels/point_pair_kernels.hip.  The set is a plain container like the others: add it with
 // addEdgeSet() next to any other set or alone; initialize() recognises it by type (its dim() is 3, like a stereo set's),
 // checks every active edge (finite values, Omega symmetric to 1e-12 max|Omega| and positive semi-definite to -1e-12
@@ -24,9 +25,10 @@
 // counting edge joins becomes a block of the Schur complement's pattern, as for relpose_types.h.
 // Refused, each with a message that names the set (a later change may lift each): setOutlierThreshold(t > 0) on the set,
 // whatever GraphOptimisationOptions::poseEdgeOutlierRejection says; pair sets that disagree on the robust kernel; a
-// landmark-sharded optimiser (setShard / setComm); CUGO_HSC_STRIP=1 (a pair block has no landmark product).  Not yet:
-// an Omega that follows the rotation during a solve, correspondences re-associated inside optimize(), a landmark-frame
-// variant.  Also reachable through the kernel-level C ABI (include/cugo_hip.h: cugo_point_pair_plan_create,
+// landmark-sharded optimiser (setShard / setComm); CUGO_HSC_STRIP=1 (a pair block has no landmark product).  An Omega
+// that follows the rotation during a solve is GicpPairEdgeSet (gicp_types.h: Omega = (C_q + M C_p M^T)^-1 rebuilt at
+// every linearisation and trial), which cannot share an optimiser with a PointPairEdgeSet that has edges and has the
+// refusals above.  Not yet: correspondences re-associated inside optimize(), a landmark-frame variant.  Also reachable through the kernel-level C ABI (include/cugo_hip.h: cugo_point_pair_plan_create,
 // cugo_point_pair_edges, cugo_point_pair_compute_errors, cugo_point_pair_construct_quadratic_form and its _schur, _diag
 // and cugo_point_pair_add_offdiag_schur forms).
 #pragma once

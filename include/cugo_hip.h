@@ -822,6 +822,79 @@ int cugo_point_pair_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_poin
 int cugo_point_pair_add_offdiag_schur(cugo_ctx* ctx, const cugo_point_pair_edges* ev, double* d_Hsc);
 
 /*
+ * Extension (the reference has no such edge): the COVARIANCE form of the two point kinds, the cost of generalised ICP.
+ * An edge carries two covariances instead of an information matrix, and Omega follows the poses:
+ *   S = C_z + M C_p M^T,  Omega = S^-1,   M = R (unary: C_p in the world frame, C_z in the pose's frame)
+ *                                         M = R_b R_a^T (pair: C_p in a's frame, C_z in b's frame)
+ * formed at the poses every pass is given: the chi2 of an error pass is the cost at those poses, the H and b of a build
+ * pass use the Omega of the linearisation point.  r, J, x = max(0, r^T Omega r), rho, w and the blocks of H and b are
+ * those of cugo_point_edges / cugo_point_pair_edges with this Omega.  The Jacobian does NOT differentiate Omega (no GICP
+ * implementation does), and log det S is not part of the cost.  S is formed as an upper triangle and mirrored, and
+ * inverted through its 3 x 3 L L^T factor.
+ * d_cov_p, d_cov_z: [6][n] or [6][1], the upper triangle row-major packed 00 01 02 11 12 22 (the layout of d_info); n_cov
+ * is the count of BOTH.  Every other member, the sorted layout, the plan, the checks, the error codes, d_edge_chi and
+ * the invariants (no atomics, one summation order, error-pass chi2 bits = build-pass chi2 bits, what has no counting
+ * edge or run keeps its bits, fixed ends are never written) are those of the information form; an n_cov that is neither
+ * n nor 1 gives CUGO_ERR_INVALID.  The values are the caller's: covariances symmetric positive semi-definite with S
+ * positive definite (lambda_min(C_p) + lambda_min(C_z) > 0 suffices for every rotation); an S that is not gives NaNs.
+ */
+typedef struct cugo_gicp_edges
+{
+    int n_poses_total, n_poses_free;
+    int n;
+    const int32_t* d_pose;     /* [n] ascending */
+    const int32_t* d_pose_ptr; /* [n_poses_total+1] */
+    const double* d_p;         /* [3][n] the point p (world) */
+    const double* d_z;         /* [3][n] its measurement z (the pose's frame) */
+    const double* d_cov_p;     /* [6][n] or [6][1]: upper triangle of C_p (world frame) */
+    const double* d_cov_z;     /* [6][n] or [6][1]: upper triangle of C_z (the pose's frame) */
+    int n_cov;                 /* n or 1 */
+    const uint8_t* d_flags;    /* [n] CUGO_EDGE_INACTIVE, or NULL: all active */
+    int rk;                    /* CUGO_RK_* */
+    double delta;
+} cugo_gicp_edges;
+
+/* as cugo_point_compute_errors / _construct_quadratic_form / _construct_quadratic_form_schur */
+int cugo_gicp_compute_errors(cugo_ctx* ctx, const cugo_gicp_edges* ev, const double* d_poses, double* d_chi,
+                             double* d_edge_chi);
+int cugo_gicp_construct_quadratic_form(cugo_ctx* ctx, const cugo_gicp_edges* ev, const double* d_poses, double* d_Hpp,
+                                       double* d_bp, double* d_chi);
+int cugo_gicp_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_gicp_edges* ev, const double* d_poses,
+                                             const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
+                                             double* d_chi);
+
+/* The pair kind, in the SORTED order of its plan (cugo_point_pair_plan_create: the plan does not depend on the form). */
+typedef struct cugo_gicp_pair_edges
+{
+    int n_poses_total, n_poses_free; /* those of the plan */
+    int n;                           /* that of the plan */
+    const int32_t* d_pose_a;         /* [n] pose a of every edge, sorted order */
+    const int32_t* d_pose_b;         /* [n] pose b */
+    const double* d_p;               /* [3][n] the point in a's frame */
+    const double* d_z;               /* [3][n] its measurement in b's frame */
+    const double* d_cov_p;           /* [6][n] or [6][1]: upper triangle of C_p (a's frame) */
+    const double* d_cov_z;           /* [6][n] or [6][1]: upper triangle of C_z (b's frame) */
+    int n_cov;                       /* n or 1 */
+    const uint8_t* d_flags;          /* as cugo_point_pair_edges.d_flags */
+    int rk;                          /* CUGO_RK_* */
+    double delta;
+    const cugo_point_pair_plan* plan; /* with a device context and a pattern */
+} cugo_gicp_pair_edges;
+
+/* as the cugo_point_pair_* call of the same name.  The partials a build pass leaves in the plan's scratch are those of
+ * the form that ran last: cugo_gicp_pair_add_offdiag_schur adds what the last build pass over the plan left. */
+int cugo_gicp_pair_compute_errors(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, const double* d_poses, double* d_chi,
+                                  double* d_edge_chi);
+int cugo_gicp_pair_construct_quadratic_form(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, const double* d_poses,
+                                            double* d_Hpp, double* d_bp, double* d_Hoff, double* d_chi);
+int cugo_gicp_pair_construct_quadratic_form_schur(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, const double* d_poses,
+                                                  const int32_t* d_rowptr, double* d_Hsc, double* d_bp, double* d_bsc,
+                                                  double* d_chi);
+int cugo_gicp_pair_construct_quadratic_form_diag(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, const double* d_poses,
+                                                 double* d_Hpp, double* d_bp, double* d_chi);
+int cugo_gicp_pair_add_offdiag_schur(cugo_ctx* ctx, const cugo_gicp_pair_edges* ev, double* d_Hsc);
+
+/*
  * Outlier pass of the four pose edge kinds (ref: EdgeSet::updateEdges, optimisable_graph.hpp:603-640), over the chi2
  * term of every edge as cugo_icp_compute_errors / cugo_prior_compute_errors / cugo_relpose_compute_errors write it.
  * Edge e becomes an outlier iff !(d_flags[e] & CUGO_EDGE_INACTIVE) && t_e > 0 && d_edge_chi[e] > t_e
@@ -1025,6 +1098,30 @@ int cugo_graph_n_point_pair_edges(cugo_graph* g);
  * a run —, planar.  Returns their number n (or a negative error) and *n_info (n, or 1 when one matrix serves all); with
  * cap >= n fills the arrays that are not NULL: pose_a, pose_b [n] (flattened indices), src_edge [n] (position among the
  * edges added), p [3][n], z [3][n], info [6][n_info] (upper triangle of the symmetric part of Omega, row-major packed). */
+/* Extension: the covariance form of the two point kinds (GicpEdgeSet / GicpPairEdgeSet,
+ * cuda-bundle-adjustment_amd/include/gicp_types.h; term: cugo_gicp_edges above): generalised ICP in ONE optimize(), Omega =
+ * (C_z + M C_p M^T)^-1 rebuilt at every linearisation and evaluated at the trial poses of every trial.  covP9 / covZ9: [n][9]
+ * (symmetric).  An unknown id, or a == b, refuses the whole call.  cugo_graph_initialize refuses, naming the set: a
+ * covariance that is not finite, symmetric (1e-12 max|C|) and positive semi-definite (-1e-12 lambda_max), lambda_min(C_p) +
+ * lambda_min(C_z) <= 1e-12 (lambda_max(C_p) + lambda_max(C_z)); these edges next to information-form point edges of the
+ * same arity; a positive outlier threshold; a sharded optimiser; CUGO_HSC_STRIP=1 with pair edges.  The flat getters work
+ * on a plan-only graph: cov_p, cov_z [6][n_cov] packed upper triangles, *n_cov = n or 1; they return n (copying only
+ * when cap >= n). */
+int cugo_graph_add_gicp_edges(cugo_graph* g, int n, const int32_t* pose_ids, const double* pointP, const double* pointZ,
+                              const double* covP9, const double* covZ9);
+int cugo_graph_add_gicp_pair_edges(cugo_graph* g, int n, const int32_t* pose_ids_a, const int32_t* pose_ids_b, const double* pointP,
+                                   const double* pointZ, const double* covP9, const double* covZ9);
+int cugo_graph_set_gicp_robust_kernel(cugo_graph* g, int type, double delta);
+int cugo_graph_set_gicp_pair_robust_kernel(cugo_graph* g, int type, double delta);
+int cugo_graph_set_gicp_outlier_threshold(cugo_graph* g, double threshold);
+int cugo_graph_set_gicp_pair_outlier_threshold(cugo_graph* g, double threshold);
+int cugo_graph_set_gicp_pair_active(cugo_graph* g, int first, int n, const uint8_t* active);
+int cugo_graph_n_gicp_edges(cugo_graph* g);
+int cugo_graph_n_gicp_pair_edges(cugo_graph* g);
+int cugo_graph_get_flat_gicp_edges(cugo_graph* g, int cap, int32_t* pose, int32_t* src_edge, double* p, double* z, double* cov_p,
+                                   double* cov_z, int* n_cov);
+int cugo_graph_get_flat_gicp_pair_edges(cugo_graph* g, int cap, int32_t* pose_a, int32_t* pose_b, int32_t* src_edge, double* p,
+                                        double* z, double* cov_p, double* cov_z, int* n_cov);
 int cugo_graph_get_flat_point_pair_edges(cugo_graph* g, int cap, int32_t* pose_a, int32_t* pose_b, int32_t* src_edge, double* p,
                                          double* z, double* info, int* n_info);
 /* Extension: relative-pose SE(3) edges (RelPoseEdgeSet, cuda-bundle-adjustment_amd/include/relpose_types.h), next to or
